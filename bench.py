@@ -2,12 +2,17 @@
 """TVTSv2 pretrain-step benchmark (BASELINE.json metric): video-text pairs/sec, ViT-B/16, 8 frames, mask 0.5,
 32-token captions, NT=4 captions per video, bf16 MFMA compute, synthetic data, random-init weights.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 A step = zero_grad, forward (text tower, space-time ViT, sort head), all-gather of embeddings, InfoNCE + 2*CE,
 backward, gradient all-reduce, fused HF-AdamW -- on a batch that is already resident in HBM.  Prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds what takes runs of its own: the
+instrumented roofline step (per-kernel GEMM / HBM figures, in-kernel clock samples) and the CPU oracle baseline.
+--dump-outputs DIR writes what the last timed step computed (losses, and a fixed seeded sample of the parameters, gradients
+and Adam moments it left) as DIR/<name>.npy, so that two builds can be compared output for output on the same inputs.
 """
 import argparse
 import json
@@ -231,6 +236,26 @@ def pmc_mfma_util(args):
             "by_family": {k: {"mfma_busy": v["mfma_busy"], "clock_mhz": 1e3 * v["clock_ghz"]} for k, v in d.get("by_family", {}).items()}}
 
 
+DUMP_SAMPLE = 1 << 20  # elements per sampled state buffer: 4 MiB of float32 each, 16 MiB for the four
+
+
+def dump_outputs(path, out, store):
+    """What the last timed step handed back (the two losses) and left in the optimizer state, as float32 .npy files.  The state
+    buffers (hundreds of MB) are sampled at DUMP_SAMPLE indices drawn from a fixed seed, the same ones for every buffer and run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: out[k].detach().float().reshape(-1) for k in ("loss1", "loss2") if out.get(k) is not None}
+    n = store.flat.numel()
+    idx = (torch.arange(n) if n <= DUMP_SAMPLE else
+           torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values).to(store.flat.device)
+    for name, t in (("params", store.flat), ("grad", store.grad), ("adam_m", getattr(store, "m", None)),
+                    ("adam_v", getattr(store, "v", None))):
+        if t is not None:
+            arrays[name + "_sample"] = t.reshape(-1)[idx].float()
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -268,6 +293,10 @@ def main():
                     "(profiles/r06_bench_product_path.txt) -- and the eager step is the trainer's own path.  Where the step is launch-bound (GRAPH_AUTO_WORK: up to 4 pairs of "
                     "ViT-B/16, ~800 launches for 9 ms of kernels) the host cannot keep up and the replay is taken automatically")
     ap.add_argument("--no-graph", action="store_true", help="eager launches whatever the batch")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also the instrumented roofline step and the CPU oracle "
+                    "baseline (each can be left out again with --no-roofline / --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32): the "
+                    "losses, and %d seeded sample elements of the parameters, gradients and Adam moments" % DUMP_SAMPLE)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=30.0)
     ap.add_argument("--no-roofline", action="store_true")
@@ -278,6 +307,8 @@ def main():
                     "1 = WebVid-style batch (no sorting head / loss, SURVEY.md 8d)")
     ap.add_argument("--cpu-threads", type=int, default=8)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline_worker(args.arch, args.frames, args.caption_len, args.cpu_pairs, args.cpu_seconds,
                                              args.cpu_threads, args.n_trans)), flush=True)
@@ -385,11 +416,11 @@ def main():
     graphs = None
     if use_graph:
         try:
-            graphs = []
+            graphs, graph_outs = [], []
             for gi in range(len(srcs)):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    out = one_step(gi, device_step=True)
+                    graph_outs.append(one_step(gi, device_step=True))
                 graphs.append(g)
             torch.cuda.synchronize()
         except Exception as e:  # stay correct: fall back to eager launches
@@ -406,6 +437,7 @@ def main():
     for i in range(args.steps):
         if graphs is not None:
             graphs[i % len(graphs)].replay()
+            out = graph_outs[i % len(graphs)]
         else:
             out = one_step(i, device_step=False)
     torch.cuda.synchronize()
@@ -441,6 +473,8 @@ def main():
             "text_range": "handed to the all-reduce at the join, behind the ViT ranges" if model.engine.text_side else "first (text tower in line)",
         }
     loss = float(out["loss1"]) + (float(out["loss2"]) if out["loss2"] is not None else 0.0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, model.store)
 
     fwd, bwd = (step_flops_per_pair_v1 if v1 else step_flops_per_pair)(a, T, args.caption_len, args.n_trans)
     # matmul FLOPs the step does NOT execute when the sort head's last block runs on the rows the model reads (engine.sort_forward):
@@ -493,7 +527,8 @@ def main():
         "step_mfma_frac": pairs_per_s * (fwd + bwd - skipped) / (world * PEAK_BF16_TFLOPS * 1e12),
     }
 
-    if not args.no_roofline:
+    roofline = args.full and not args.no_roofline
+    if roofline:
         # dominant kernel family = the bf16 MFMA GEMMs (gemm_nt_kernel / gemm_tn_kernel): one instrumented eager
         # step with a HIP event pair around every GEMM launch on the launch stream.  EVERY rank runs the step (it
         # contains the all-gather / all-reduce of the data-parallel path); rank 0 records.
@@ -517,7 +552,7 @@ def main():
         model.engine.text_side = eng_ts
         if world > 1:
             dist.barrier()
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roofline:
         recs, K.GEMM_PROFILE = K.GEMM_PROFILE, None
         hrecs, K.HBM_PROFILE = K.HBM_PROFILE, None
         cp, K.CLOCK_PROBE = K.CLOCK_PROBE, None
@@ -601,7 +636,7 @@ def main():
             for k, v in sorted(fam.items(), key=lambda kv: -kv[1][2])}
         line["roofline"]["hbm_kernels_note"] = ("HIP events around every launch of one eager step; attention entries include their "
                                                 "CLS merge / delta / finalize kernels; small-row LayerNorms (text / sort-head rows) apart")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args.arch, T, args.caption_len, pairs=args.cpu_pairs, max_seconds=args.cpu_seconds,
                                             n_trans=args.n_trans)
     if rank == 0:

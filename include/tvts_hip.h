@@ -452,7 +452,7 @@ int tvts_event_destroy(void* ev);
 /* clock under load (SURVEY.md 8d "confirm the peak on the box: clocks x CUs x MFMA rate"): the rate of the constant counter
    (s_memrealtime) in kHz, the CU count and the sheet's maximum shader clock of the device; the shader cycles themselves are sampled
    INSIDE a GEMM launch (TVTS_GEMM_CLOCK_SAMPLE).  No reference site: the reference has no roofline accounting. */
-/* p[0:nbytes] = 0 on the stream (hipMemsetAsync): optimizer.zero_grad() of the flat gradient buffer (v2/trainer/trainer.py:476) and
+/* p[0:nbytes] = 0 on the stream (a zero-fill kernel): optimizer.zero_grad() of the flat gradient buffer (v2/trainer/trainer.py:476) and
    the step's small accumulators */
 int tvts_zero_bytes(void* p, long nbytes, hipStream_t stream);
 int tvts_device_clock_info(int device, int* wall_clock_khz, int* cu_count, int* max_shader_khz);

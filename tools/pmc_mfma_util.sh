@@ -17,5 +17,6 @@ for p in sq grbm; do
     python bench.py --steps 1 --warmup 1 --no-graph --no-cpu-baseline --no-roofline --text-side off "$@" > gpurun_out/pmcu_$p.log 2>&1
   echo "pass $p rc=$?"
 done
-TVTS_BENCH_ORDER=gpurun_out/gemm_order_util.json python bench.py --steps 1 --warmup 1 --no-graph --no-cpu-baseline --text-side off "$@" > /dev/null 2> gpurun_out/pmcu_order.err
-python tools/pmc_mfma_join.py gpurun_out/gemm_order_util.json gpurun_out "$@" | tee gpurun_out/pmc_mfma_util.txt
+res=$(dirname "$(ls -d */pmcu_grbm | head -1)")   # the results directory the counter passes above wrote into
+TVTS_BENCH_ORDER=$res/gemm_order_util.json python bench.py --full --steps 1 --warmup 1 --no-graph --no-cpu-baseline --text-side off "$@" > /dev/null 2> $res/pmcu_order.err
+python tools/pmc_mfma_join.py $res/gemm_order_util.json $res "$@" | tee $res/pmc_mfma_util.txt

@@ -17,10 +17,10 @@ tools/pmc_mfma_util.sh > $out/pmc_mfma_util.log 2>&1
 cp gpurun_out/pmc_mfma_util.txt $out/pmc_mfma_util_B_16_t8_b192.txt
 cp gpurun_out/pmc_mfma_util.json $out/pmc_mfma_util_B_16_t8_b192.json
 cp gpurun_out/pmc_mfma_util.json profiles/${tag}_pmc_mfma_util_B_16_t8_b192.json
-python bench.py > $out/bench_default_driver_form.json 2> $out/bench_default.err                     # exactly what the driver runs
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' > $out/bench_default_b192.json
+python bench.py --full > $out/bench_default_driver_form.json 2> $out/bench_default.err              # the default line + roofline + CPU baseline
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' > $out/bench_default_b192.json
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --graph 2>/dev/null | grep '^{' > $out/bench_default_b192_graph_replay.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --dense-sort-head 2>/dev/null | grep '^{' > $out/bench_dense_sort_head.json
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --dense-sort-head 2>/dev/null | grep '^{' > $out/bench_dense_sort_head.json
 # (the text tower in line: in the timed steps it runs on its own stream beside the ViT, and a kernel's traced duration would then
 #  include the time it shared the chip with the other stream's kernels -- same kernels, same bits either way)
 tools/profile_step.sh ${tag}_default --text-side off > $out/profile_step.log 2>&1
@@ -28,25 +28,25 @@ cp gpurun_out/prof_${tag}_default/summary.txt $out/kernel_summary_default_b192.t
 cp gpurun_out/prof_${tag}_default/kernel_stats.csv $out/kernel_stats_default_b192.csv
 [ -x experiments/probes/mfma_power ] || make -C experiments probes > /dev/null 2>&1
 experiments/probes/mfma_power > $out/mfma_power_probe.txt 2>&1
-TVTS_BENCH_ORDER=gpurun_out/gemm_order.json python bench.py --steps 1 --warmup 1 --no-graph --no-cpu-baseline > /dev/null 2> $out/order.err
-python tools/pmc_join.py gpurun_out/gemm_order.json gpurun_out > $out/pmc_gemm_traffic_by_shape.txt 2>> $out/order.err
-{ python bench.py --batch 2 --steps 20 --warmup 5 --no-cpu-baseline
-  python bench.py --batch 12 --steps 20 --warmup 5 --no-cpu-baseline
-  python bench.py --batch 24 --steps 20 --warmup 5 --no-cpu-baseline
-  python bench.py --n-trans 1 --steps 20 --warmup 5 --no-cpu-baseline; } 2>/dev/null | grep '^{' > $out/bench_reference_batches.jsonl
-{ python bench.py --arch B_32 --batch 384 --steps 20 --warmup 5 --no-cpu-baseline
-  python bench.py --arch B_32 --batch 24 --steps 20 --warmup 5 --no-cpu-baseline; } 2>/dev/null | grep '^{' > $out/bench_b32_t8.jsonl
-{ python bench.py --arch H_14 --frames 16 --batch 48 --steps 8 --warmup 3 --no-cpu-baseline
-  python bench.py --arch H_14 --frames 16 --batch 48 --steps 8 --warmup 3 --no-cpu-baseline --fp8
-  python bench.py --arch H_14 --frames 16 --batch 48 --steps 8 --warmup 3 --no-cpu-baseline --fp8-dgrad
-  python bench.py --arch H_14 --frames 16 --batch 48 --steps 8 --warmup 3 --no-cpu-baseline --fp8-wgrad; } 2>/dev/null | grep '^{' > $out/bench_h14_t16_b48.jsonl
+TVTS_BENCH_ORDER=$out/gemm_order.json python bench.py --full --steps 1 --warmup 1 --no-graph --no-cpu-baseline > /dev/null 2> $out/order.err
+python tools/pmc_join.py $out/gemm_order.json "$(dirname $out)" > $out/pmc_gemm_traffic_by_shape.txt 2>> $out/order.err
+{ python bench.py --full --batch 2 --steps 20 --warmup 5 --no-cpu-baseline
+  python bench.py --full --batch 12 --steps 20 --warmup 5 --no-cpu-baseline
+  python bench.py --full --batch 24 --steps 20 --warmup 5 --no-cpu-baseline
+  python bench.py --full --n-trans 1 --steps 20 --warmup 5 --no-cpu-baseline; } 2>/dev/null | grep '^{' > $out/bench_reference_batches.jsonl
+{ python bench.py --full --arch B_32 --batch 384 --steps 20 --warmup 5 --no-cpu-baseline
+  python bench.py --full --arch B_32 --batch 24 --steps 20 --warmup 5 --no-cpu-baseline; } 2>/dev/null | grep '^{' > $out/bench_b32_t8.jsonl
+{ python bench.py --full --arch H_14 --frames 16 --batch 48 --steps 8 --warmup 3 --no-cpu-baseline
+  python bench.py --full --arch H_14 --frames 16 --batch 48 --steps 8 --warmup 3 --no-cpu-baseline --fp8
+  python bench.py --full --arch H_14 --frames 16 --batch 48 --steps 8 --warmup 3 --no-cpu-baseline --fp8-dgrad
+  python bench.py --full --arch H_14 --frames 16 --batch 48 --steps 8 --warmup 3 --no-cpu-baseline --fp8-wgrad; } 2>/dev/null | grep '^{' > $out/bench_h14_t16_b48.jsonl
 tools/profile_step.sh ${tag}_h14fp8 --arch H_14 --frames 16 --batch 48 --fp8-wgrad --text-side off > $out/profile_h14fp8.log 2>&1
 cp gpurun_out/prof_${tag}_h14fp8/summary.txt $out/kernel_summary_h14_b48_fp8_wgrad.txt
 python tools/tn_fp8_bench.py > $out/tn_fp8_bench.txt 2>&1
 PAIRS=48 python tools/gemm_fp8_cmp.py > $out/gemm_fp8_cmp.txt 2>&1
 PAIRS=192 python tools/attn_bench.py > $out/attn_bench.txt 2>&1
-{ python bench.py --arch v1 --frames 4 --batch 256 --steps 20 --warmup 5 --cpu-pairs 8
-  python bench.py --arch v1 --frames 16 --batch 64 --steps 20 --warmup 5 --no-cpu-baseline; } 2>/dev/null | grep '^{' > $out/bench_v1.jsonl
+{ python bench.py --full --arch v1 --frames 4 --batch 256 --steps 20 --warmup 5 --cpu-pairs 8
+  python bench.py --full --arch v1 --frames 16 --batch 64 --steps 20 --warmup 5 --no-cpu-baseline; } 2>/dev/null | grep '^{' > $out/bench_v1.jsonl
 PAIRS=192 python tools/attn_ablate.py > $out/attn_ablate.txt 2>&1
 tools/profile_step.sh ${tag}_v1 --arch v1 --frames 4 --batch 256 > $out/profile_v1.log 2>&1
 cp gpurun_out/prof_${tag}_v1/summary.txt $out/kernel_summary_v1_t4_b256.txt

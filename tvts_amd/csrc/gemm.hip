@@ -930,6 +930,12 @@ __global__ __launch_bounds__(256) void tn_reduce_grouped_kernel(TnGroup grp) {
 }
 
 // out[a,b] = (accumulate ? out[a,b] : 0) + sum_s ws[s][a][b];  colsum[a] += sum_s cs_ws[s][a]  (both in split order)
+// out[r, 0:Nb] = 0 for r < Na, row pitch ldo (the split partials without a workspace are fp32 atomics into a zeroed output)
+__global__ __launch_bounds__(256) void zero_rows_f32_kernel(float* __restrict__ out, int ldo, int Na, int Nb) {
+    const long n = (long)Na * Nb, stride = (long)gridDim.x * blockDim.x;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[(i / Nb) * ldo + i % Nb] = 0.f;
+}
+
 __global__ __launch_bounds__(256) void tn_reduce_kernel(const float* __restrict__ ws, int splits, int Na, int Nb,
                                                         float* __restrict__ out, int ldo, int accumulate,
                                                         const float* __restrict__ cs_ws, float* __restrict__ colsum) {
@@ -1034,8 +1040,11 @@ extern "C" int tvts_gemm_tn_bf16(const void* P, int ldp, const void* Q, int ldq,
     if ((opts & 32) && splits > 1 && !fused) return TVTS_EINVAL;
     if (fused) g.cnt = counters;
     if (!use_ws && !accumulate && splits > 1) {
-        hipError_t e = hipMemset2DAsync(out, (size_t)ldo * 4, 0, (size_t)Nb * 4, Na, stream);
-        if (e != hipSuccess) return (int)e;
+        // a kernel, not hipMemset2DAsync: captured memset nodes did not reliably zero their buffer on hipGraph replay (ROCm 7.x)
+        const long n = (long)Na * Nb;
+        long blocks = (n + 255) / 256;
+        if (blocks > 8192) blocks = 8192;
+        if (blocks > 0) hipLaunchKernelGGL(zero_rows_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, out, ldo, Na, Nb);
     }
     g.atomic = (accumulate || splits > 1) ? 1 : 0;
     g.n_items = g.tiles_ab * splits;

@@ -1009,7 +1009,7 @@ CLOCK_PROBE = None  # bench.py: dict(buf=int64 [n, 4] device tensor, i=0) while 
 
 
 def zero_(t):
-    """t[...] = 0 through the library (hipMemsetAsync on the current stream); t contiguous"""
+    """t[...] = 0 through the library (a zero-fill kernel on the current stream); t contiguous"""
     assert t.is_contiguous()
     _chk(_lib.load().tvts_zero_bytes(_p(t), t.numel() * t.element_size(), _stream()), "tvts_zero_bytes")
     return t
