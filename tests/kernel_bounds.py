@@ -1,0 +1,390 @@
+"""Per-element and per-row checks of kernel outputs against float64 references (a plain helper module, imported by the tests).
+
+A whole-tensor norm ``rel(got, ref) = |got - ref| / |ref|`` over 10^8 elements does not see an error that sits in a few hundred of
+them: one wrong row of a 150 720 x 768 product, one transposed 16 x 16 block or 16 zeroed values of one row all stay inside the
+4e-3 gate of a bf16 output (tests/test_kernel_bounds_cpu.py shows it).  The checks below look at every element (GEMMs, exact
+copies) or at every (row, head) slice (softmax attention, LayerNorm row reductions) and name the element and the tile it belongs to.
+
+References are float64 torch on the device of the inputs, built from the exact values the kernel read (bf16 operands, decoded
+e4m3 bytes times their scales), in row chunks so that a 150 720 x 3072 reference stays within a few GB.
+"""
+import math
+
+import torch
+
+U32 = 2.0 ** -24          # unit roundoff of fp32
+U_OUT = {torch.bfloat16: 2.0 ** -8, torch.float32: 2.0 ** -24}  # unit roundoff of the output type: |fl(v) - v| <= u |v| (RNE)
+SIG_BITS = {torch.bfloat16: 8, torch.float32: 24}
+# Transcendental error of the kernels' activation epilogues (fast exp2 / rcp, erf by Abramowitz & Stegun 7.1.26 with
+# |error| <= 1.5e-7): bounded by EPS_ACT * (|x| + |act(x)|) for act and EPS_ACT * (1 + 2|x| + |act'(x)|) for act'.
+EPS_ACT = 2.0 ** -20
+LIP_ACT = 1.13            # max |act'(x)| of QuickGELU (1.0998) and erf-GELU (1.1289): the Lipschitz constant of both
+LIP_DERIV = 0.86          # max |act''(x)| (QuickGELU 0.851, erf-GELU 0.798): the Lipschitz constant of act'
+TILE, SLAB, COLS = 256, 16, 16
+
+
+# ------------------------------------------------------------------------------------------------ reporting
+ACC_WORST = [0.0]  # worst accumulation-part ratio of the checks since the last pop_acc_worst()
+
+
+def pop_acc_worst():
+    v, ACC_WORST[0] = ACC_WORST[0], 0.0
+    return v
+
+
+class Report:
+    """Violations of |got - ref| <= bound, merged over row chunks; ``raise_if_bad`` names the first offender and its tile."""
+
+    def __init__(self, what):
+        self.what, self.count, self.first, self.worst, self.nonfinite, self.n = what, 0, None, 0.0, 0, 0
+        self.worst_acc = 0.0
+
+    def add(self, got, ref, bound, row0=0, out_dtype=None):
+        """out_dtype (the type the kernel rounded to; bound = u_out |ref| + acc): also measure how much of the pre-rounding part
+        acc is used, max(0, |err| - half ulp(got)) / acc -- the output rounding alone takes up to u_out |ref| of every bound, so the
+        total ratio of a correctly rounded result reaches ~1 by construction; this one shows the headroom of the accumulation"""
+        got = got.double() if got.dtype != torch.float64 else got
+        ref = ref.double() if ref.dtype != torch.float64 else ref
+        bound = bound.double() if torch.is_tensor(bound) else torch.tensor(float(bound), dtype=torch.float64, device=ref.device)
+        got2, ref2 = got.reshape(got.shape[0], -1) if got.dim() > 1 else got[:, None], ref.reshape(got.shape[0], -1) if ref.dim() > 1 else ref[:, None]
+        b2 = bound.expand(ref.shape).reshape(got2.shape) if bound.dim() > 0 else bound
+        err = (got2 - ref2).abs()
+        finite = torch.isfinite(got2)
+        bad = (~finite) | (err > b2)
+        self.n += got2.numel()
+        nb = int(bad.sum())
+        if nb:
+            self.count += nb
+            self.nonfinite += int((~finite).sum())
+            if self.first is None:
+                idx = int(torch.nonzero(bad.reshape(-1))[0])
+                r, c = divmod(idx, got2.shape[1])
+                self.first = (row0 + r, c, float(got2[r, c]), float(ref2[r, c]),
+                              float(b2[r, c] if b2.dim() > 0 else b2))
+        ratio = torch.where(finite, err / b2.clamp_min(1e-300), torch.zeros_like(err))
+        self.worst = max(self.worst, float(ratio.max()) if ratio.numel() else 0.0)
+        if out_dtype is not None and got2.numel():
+            ag = got2.abs()
+            half = torch.where(ag > 0, torch.exp2(torch.floor(torch.log2(ag.clamp_min(1e-300))) - SIG_BITS[out_dtype]), torch.zeros_like(ag))
+            acc = (b2 - U_OUT[out_dtype] * ref2.abs()).clamp_min(1e-300)
+            ex = torch.where(finite, (err - half).clamp_min(0.0) / acc, torch.zeros_like(err))
+            self.worst_acc = max(self.worst_acc, float(ex.max()))
+        return self
+
+    def raise_if_bad(self):
+        if not self.count:
+            ACC_WORST[0] = max(ACC_WORST[0], self.worst_acc)
+        if self.count:
+            r, c, g, ref, b = self.first
+            raise AssertionError(
+                f"{self.what}: {self.count} of {self.n} elements outside the bound ({self.nonfinite} non-finite); first at "
+                f"(row {r}, col {c}) got {g!r} ref {ref!r} bound {b:.3g}: 256x256 tile ({r // TILE}, {c // TILE}), 16-row slab "
+                f"{(r % TILE) // SLAB} of that tile (global slab {r // SLAB}), column group {c // COLS} (16 columns); worst "
+                f"|err| / bound = {self.worst:.3g}")
+        return self.worst
+
+
+def assert_within(got, ref, bound, what="output"):
+    """|got - ref| <= bound element by element (bound: tensor broadcastable to ref, or a number); any non-finite value fails.
+    Returns the worst |err| / bound (the headroom a test reports)."""
+    return Report(what).add(got, ref, bound).raise_if_bad()
+
+
+def assert_equal_bits(got, want, what="output"):
+    """bit-for-bit equality (NaNs included) with the first differing element named like assert_within does"""
+    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
+    ib = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[got.element_size()]
+    g, w = got.contiguous().view(ib), want.contiguous().view(ib)
+    diff = g != w
+    n = int(diff.sum())
+    if n:
+        d2 = diff.reshape(diff.shape[0], -1) if diff.dim() > 1 else diff[:, None]
+        r, c = divmod(int(torch.nonzero(d2.reshape(-1))[0]), d2.shape[1])
+        gv, wv = got.reshape(d2.shape)[r, c], want.reshape(d2.shape)[r, c]
+        raise AssertionError(f"{what}: {n} of {diff.numel()} elements differ; first at (row {r}, col {c}) got {gv.item()!r} "
+                             f"want {wv.item()!r}: 256x256 tile ({r // TILE}, {c // TILE}), 16-row slab {(r % TILE) // SLAB}, "
+                             f"column group {c // COLS}")
+
+
+def rows_rel(got, ref, groups=1, floor=0.05, out_dtype=None):
+    """relative L2 error of every (row, group) slice: got / ref [R, C] with C = groups * d (1-D: every element its own slice).
+    The denominator is max(|ref slice|, floor * mean |ref slice|) so that a slice whose reference is ~0 (a head of one row that
+    happens to cancel) does not divide by noise.  out_dtype: the type the kernel rounded its result to -- each element's error is
+    first reduced by half an ulp of got in that type (max(0, |err| - half ulp)), so that the tolerance measures the kernel's error
+    before its output rounding instead of the rounding noise every correct result carries."""
+    got, ref = got.double(), ref.double()
+    if got.dim() == 1:
+        got, ref = got[:, None], ref[:, None]
+    R = got.shape[0]
+    err = (got - ref).abs()
+    if out_dtype is not None:
+        ag = got.abs()
+        half = torch.where(ag > 0, torch.exp2(torch.floor(torch.log2(ag.clamp_min(1e-300))) - SIG_BITS[out_dtype]), torch.zeros_like(ag))
+        err = (err - half).clamp_min(0.0)
+    g = err.reshape(R, groups, -1)
+    r = ref.reshape(R, groups, -1)
+    num, den = g.norm(dim=2), r.norm(dim=2)
+    return num / torch.maximum(den, floor * den.mean().clamp_min(1e-300)), torch.isfinite(got).all()
+
+
+def assert_rows_within(got, ref, tol, groups=1, what="rows", floor=0.05, out_dtype=None):
+    """every (row, group) slice within tol relative L2 (rows_rel); returns the worst slice error"""
+    e, finite = rows_rel(got, ref, groups, floor, out_dtype)
+    worst = float(e.max())
+    bad = e > tol
+    if not bool(finite) or bool(bad.any()):
+        nb = int(bad.sum())
+        first = torch.nonzero(bad)[0].tolist() if nb else None
+        raise AssertionError(f"{what}: {nb} of {e.numel()} (row, group) slices above tol {tol:g} (all finite: {bool(finite)}); "
+                             f"first (row, group) = {first}; worst {worst:.3g}")
+    return worst
+
+
+# ------------------------------------------------------------------------------------------------ guarded outputs
+def guarded(M, N, dtype, device, rows=3, cols=8):
+    """an [M, N] output view with `rows` guard rows under it and `cols` guard columns right of it (leading dimension N + cols),
+    filled with NaN (0xFF bytes for integer types); -> (buffer, view)"""
+    if dtype.is_floating_point:
+        buf = torch.full((M + rows, N + cols), float("nan"), dtype=dtype, device=device)
+    else:
+        buf = torch.full((M + rows, N + cols), 0xFF, dtype=torch.uint8, device=device).view(dtype)
+    return buf, buf[:M, :N]
+
+
+def check_guards(buf, M, N, what="output"):
+    """the guard rows and columns of `guarded` are untouched"""
+    def untouched(t):
+        return bool(torch.isnan(t).all()) if t.dtype.is_floating_point else bool((t.view(torch.uint8) == 0xFF).all())
+    assert untouched(buf[M:]), f"{what}: rows past {M} were written"
+    assert untouched(buf[:M, N:]), f"{what}: columns past {N} were written (leading dimension {buf.shape[1]})"
+
+
+# ------------------------------------------------------------------------------------------------ GEMM references and bounds
+def decode_e4m3(q8):
+    """uint8 e4m3 (OCP, fn) bytes -> float64 values"""
+    return q8.view(torch.float8_e4m3fn).double()
+
+
+def gemm_ref(a, b, r0=0, r1=None, *, scale=None, bias=None, residual=None):
+    """rows r0:r1 of ref = scale * (a @ b^T) + bias + residual and of S = |scale| * (|a| @ |b|^T) + |bias| + |residual|, float64.
+    a [M, K], b [N, K] in any float type (decoded values); scale: None, a number, or float64 [M] (one per row)."""
+    r1 = a.shape[0] if r1 is None else r1
+    ac, bd = a[r0:r1].double(), b.double()
+    ref, S = ac @ bd.t(), ac.abs() @ bd.abs().t()
+    if scale is not None:
+        s = scale[r0:r1, None] if torch.is_tensor(scale) and scale.numel() > 1 else scale
+        ref, S = ref * s, S * (s.abs() if torch.is_tensor(s) else abs(s))
+    if bias is not None:
+        ref, S = ref + bias.double(), S + bias.double().abs()
+    if residual is not None:
+        rr = residual[r0:r1].double()
+        ref, S = ref + rr, S + rr.abs()
+    return ref, S
+
+
+def gemm_acc_bound(S, K, c=4):
+    """bound on |v - ref| of the fp32 value v the kernel holds before its output rounding: (K + c) u S / (1 - (K + c) u)"""
+    n = (K + c) * U32
+    return S * (n / (1.0 - n))
+
+
+def gemm_bound(ref, S, K, out_dtype, c=4, acc=None):
+    """Per-element bound for an MFMA product with fp32 accumulation, valid for ANY summation order.
+
+    Derivation.  The kernel forms v_ij = fl(sum of the K products a_ik b_jk, the bias and the residual) in fp32.  bf16 x bf16 and
+    e4m3 x e4m3 products are exact in fp32 (8 + 8 and 4 + 4 significand bits), so every rounding is one of the additions (and, for
+    fp8, the one or two multiplications by the scales).  Whatever the order -- a tile kernel's MFMA chain, split-K partials
+    reduced afterwards, stream-K, fp32 atomics -- the sum is a binary tree of n = K + c - 1 roundings, and the standard result
+    for recursive summation (Higham, Accuracy and Stability, Thm 4.3 / eq. 4.4) gives
+
+        |v_ij - ref_ij| <= gamma_n * S_ij,   gamma_n = n u / (1 - n u),   S_ij = sum_k |a_ik||b_jk| + |bias_j| (+ |res_ij|),
+
+    u = 2^-24.  Each scale multiplication is one more relative rounding of a partial whose magnitude is <= S, so it is covered
+    by c (default 4: bias, residual, two scale factors).  For fp8, S is taken over the decoded values times |sa sb|.  The
+    result is then rounded to nearest even in the output type: |out - v| <= u_out |v| (u_out = 2^-8 for bf16, 2^-24 for
+    fp32), and |v| <= |ref| + acc, so
+
+        |out_ij - ref_ij| <= u_out |ref_ij| + (1 + u_out) gamma_n S_ij.
+
+    A value just above a power of two can use the whole rounding term, so the total |err| / bound of a correct bf16 result
+    reaches ~1; Report measures the used share of the accumulation term separately (worst_acc).
+
+    No order-dependent term appears, so one bound serves every kernel form.  `acc`: the pre-rounding bound when it is not the
+    plain gamma_n S (activations and gates: act_bound / gate_bound)."""
+    acc = gemm_acc_bound(S, K, c) if acc is None else acc
+    u = U_OUT[out_dtype]
+    return u * ref.abs() + (1.0 + u) * acc + 1e-38
+
+
+def act_ref(x, act):
+    """float64 QuickGELU / erf-GELU"""
+    if act == "quick_gelu":
+        return x * torch.sigmoid(1.702 * x)
+    return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
+
+
+def act_deriv_ref(x, act):
+    if act == "quick_gelu":
+        s = torch.sigmoid(1.702 * x)
+        return s * (1.0 + 1.702 * x * (1.0 - s))
+    return 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0))) + x * torch.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
+
+
+def act_bound(pre_ref, pre_acc, act, out_dtype):
+    """y = act(v) with |v - pre_ref| <= pre_acc: |act(v) - act(pre_ref)| <= L pre_acc (L = LIP_ACT), plus the kernel's
+    transcendental error EPS_ACT (|x| + |act(x)|) (x within pre_acc of pre_ref: |x| <= |pre_ref| + pre_acc), then the output
+    rounding as in gemm_bound.  -> (ref, bound)"""
+    y = act_ref(pre_ref, act)
+    acc = LIP_ACT * pre_acc + EPS_ACT * (pre_ref.abs() + pre_acc + y.abs() + LIP_ACT * pre_acc)
+    acc = acc * (1 + 2 * U32)  # the multiply inside act and the fp32 rounding of y
+    u = U_OUT[out_dtype]
+    return y, u * y.abs() + (1.0 + u) * acc + 1e-38
+
+
+def gate_bound(z_ref, z_acc, h, act, out_dtype, deriv=False):
+    """out = z * g(h), h the exact (bf16) gate input, g = act' (or, deriv, g = h itself: the stored derivative).
+    |z g~ - z_ref g| <= |g| z_acc + |z_ref| eps_g + z_acc eps_g, eps_g = EPS_ACT (1 + 2|h| + |g|) (0 for deriv), plus the fp32
+    rounding of the product and the output rounding.  -> (ref, bound)"""
+    h = h.double()
+    g = h if deriv else act_deriv_ref(h, act)
+    eps_g = torch.zeros_like(g) if deriv else EPS_ACT * (1.0 + 2.0 * h.abs() + g.abs())
+    ref = z_ref * g
+    acc = g.abs() * z_acc + z_ref.abs() * eps_g + z_acc * eps_g
+    acc = acc + U32 * (ref.abs() + acc)
+    u = U_OUT[out_dtype]
+    return ref, u * ref.abs() + (1.0 + u) * acc + 1e-38
+
+
+def check_gemm(got, a, b, *, what, scale=None, bias=None, residual=None, act=None, preact=None, gate_h=None, gate_act=None,
+               deriv=False, add_bf16=None, K=None, c=4, chunk=8192):
+    """got[M, N] against the float64 product of a [M, K] and b [N, K] (decoded values), every element within gemm_bound /
+    act_bound / gate_bound; preact (the side output of an activation epilogue, bf16) is checked against the pre-activation, or
+    (deriv) against act' of it.  add_bf16: the bf16 residual stream added in the gate slot.  Returns the worst |err| / bound
+    over all the outputs checked."""
+    K = a.shape[1] if K is None else K
+    M = got.shape[0]
+    reps = [Report(what)] + ([Report(what + " (pre-activation side output)")] if preact is not None else [])
+    for r0 in range(0, M, chunk):
+        r1 = min(M, r0 + chunk)
+        ref, S = gemm_ref(a, b, r0, r1, scale=scale, bias=bias, residual=residual)
+        acc = gemm_acc_bound(S, K, c)
+        if act is not None:
+            y, bnd = act_bound(ref, acc, act, got.dtype)
+            reps[0].add(got[r0:r1], y, bnd, r0, got.dtype)
+            if preact is not None:
+                if deriv:
+                    d, dbnd = _deriv_bound(ref, acc, act)
+                    reps[1].add(preact[r0:r1], d, dbnd, r0, preact.dtype)
+                else:
+                    reps[1].add(preact[r0:r1], ref, gemm_bound(ref, S, K, preact.dtype, acc=acc), r0, preact.dtype)
+        elif gate_h is not None:
+            y, bnd = gate_bound(ref, acc, gate_h[r0:r1], gate_act, got.dtype, deriv=deriv)
+            reps[0].add(got[r0:r1], y, bnd, r0, got.dtype)
+        elif add_bf16 is not None:
+            hr = add_bf16[r0:r1].double()
+            ref2 = ref + hr
+            acc2 = acc + U32 * (ref2.abs() + acc)
+            reps[0].add(got[r0:r1], ref2, gemm_bound(ref2, S + hr.abs(), K, got.dtype, acc=acc2), r0, got.dtype)
+        else:
+            reps[0].add(got[r0:r1], ref, gemm_bound(ref, S, K, got.dtype, c=c), r0, got.dtype)
+        del ref, S, acc
+    return max(r.raise_if_bad() for r in reps)
+
+
+def _deriv_bound(pre_ref, pre_acc, act):
+    """the bf16 side output act'(v) of a side_deriv forward: |act''| <= LIP_DERIV over the reals (QuickGELU 0.851 at 0, erf-GELU
+    2 phi(0) = 0.798), plus EPS_ACT (1 + 2|x| + |act'|), then the bf16 rounding"""
+    d = act_deriv_ref(pre_ref, act)
+    acc = LIP_DERIV * pre_acc + EPS_ACT * (1.0 + 2.0 * (pre_ref.abs() + pre_acc) + d.abs() + LIP_DERIV * pre_acc)
+    u = U_OUT[torch.bfloat16]
+    return d, u * d.abs() + (1.0 + u) * acc + 1e-38
+
+
+# ------------------------------------------------------------------------------------------------ LayerNorm references and bounds
+def _gamma(n):
+    return n * U32 / (1.0 - n * U32)
+
+
+def ln_fwd_check(x, gamma, beta, eps, y=None, mean=None, rstd=None, *, what, chunk=16384):
+    """LayerNorm forward outputs against float64, per element.  x is what the kernel read (fp32, or bf16 widened).
+
+    Bound.  The kernel forms m = fl(sum x / W) and the variance in fp32 in some order (two-pass or E[x^2] - m^2):
+    |m - mean| <= gamma_W s1 with s1 = mean |x|; the variance is off by at most gamma_{W+4} (s2 + 2 s1^2) (s2 = mean x^2), so
+    rstd carries a relative error e_r <= gamma_{W+4} (s2 + 2 s1^2) / (var + eps) + 4u (the square root and its reciprocal).
+    y = (x - m) rstd g + b then errs by |g| rstd (|m - mean| + |x - mean| e_r) + 4u (|xhat g| + |b|), then the output rounding."""
+    W = x.shape[1]
+    reps = {k: Report(f"{what}: {k}") for k, t in (("y", y), ("mean", mean), ("rstd", rstd)) if t is not None}
+    g64, b64 = gamma.double(), beta.double()
+    for r0 in range(0, x.shape[0], chunk):
+        r1 = min(x.shape[0], r0 + chunk)
+        xc = x[r0:r1].double()
+        mu = xc.mean(1, keepdim=True)
+        var = ((xc - mu) ** 2).mean(1, keepdim=True)
+        rs = 1.0 / torch.sqrt(var + eps)
+        s1, s2 = xc.abs().mean(1, keepdim=True), (xc * xc).mean(1, keepdim=True)
+        e_m = _gamma(W + 1) * s1
+        e_r = _gamma(W + 4) * (s2 + 2 * s1 * s1) / (var + eps) + 4 * U32
+        xh = (xc - mu) * rs
+        if y is not None:
+            ref = xh * g64 + b64
+            acc = g64.abs() * rs * (e_m + (xc - mu).abs() * e_r) + 4 * U32 * ((xh * g64).abs() + b64.abs())
+            u = U_OUT[y.dtype]
+            reps["y"].add(y[r0:r1], ref, u * ref.abs() + (1 + u) * acc + 1e-38, r0, y.dtype)
+        if mean is not None:
+            reps["mean"].add(mean[r0:r1], mu[:, 0], (e_m + U32 * mu.abs())[:, 0] + 1e-38, r0)
+        if rstd is not None:
+            reps["rstd"].add(rstd[r0:r1], rs[:, 0], (rs * e_r * 1.01)[:, 0], r0)
+    return max(r.raise_if_bad() for r in reps.values())
+
+
+def ln_bwd_check(dy, x, mean, rstd, gamma, *, dx=None, dx_bf16=None, res1=None, res2=None, dgamma=None, dbeta=None,
+                 dgamma0=None, dbeta0=None, col_tol=None, col_worst=None, what, chunk=16384):
+    """LayerNorm backward outputs against float64 evaluated on the SAME mean / rstd the kernel read, per element (dx) and per
+    column (dgamma, dbeta).
+
+    Bound.  xhat = (x - mean) rstd is formed with |err| <= e_x = 3u (|xhat| + |x| rstd); with gd = g dy, the row means
+    c1 = mean gd and c2 = mean gd xhat carry |err| <= gamma_W mean |gd| and gamma_{W+3} mean |gd xhat| + mean(|gd| e_x);
+    dx = rstd (gd - c1 - xhat c2) + res1 + res2 then errs by rstd (u |gd| + e_c1 + |xhat| e_c2 + e_x |c2|) + 6u (|terms|).
+    dgamma / dbeta (sums over all M rows, accumulated into dgamma0 / dbeta0): a worst-case gamma_M bound is larger than the sums
+    themselves at M = 150 720, so every column is held to the calibrated relative tolerance col_tol (assert_rows_within); the
+    worst column error goes into col_worst[name]."""
+    M, W = x.shape
+    g64 = gamma.double()
+    reps = {}
+    colsum = {k: torch.zeros(W, dtype=torch.float64, device=x.device) for k in ("dg", "db")}
+    col_worst = {} if col_worst is None else col_worst
+    for k, t in (("dx", dx), ("dx_bf16", dx_bf16)):
+        if t is not None:
+            reps[k] = Report(f"{what}: {k}")
+    for r0 in range(0, M, chunk):
+        r1 = min(M, r0 + chunk)
+        xc, dyc = x[r0:r1].double(), dy[r0:r1].double()
+        mu, rs = mean[r0:r1].double()[:, None], rstd[r0:r1].double()[:, None]
+        xh = (xc - mu) * rs
+        e_x = 3 * U32 * (xh.abs() + xc.abs() * rs)
+        gd = g64 * dyc
+        c1 = gd.mean(1, keepdim=True)
+        c2 = (gd * xh).mean(1, keepdim=True)
+        e_c1 = _gamma(W + 1) * gd.abs().mean(1, keepdim=True)
+        e_c2 = _gamma(W + 4) * (gd * xh).abs().mean(1, keepdim=True) + (gd.abs() * e_x).mean(1, keepdim=True)
+        core = rs * (gd - c1 - xh * c2)
+        terms = rs * (gd.abs() + c1.abs() + (xh * c2).abs())
+        ref = core
+        acc = rs * (U32 * gd.abs() + e_c1 + xh.abs() * e_c2 + e_x * c2.abs()) + 6 * U32 * terms
+        for r in (res1, res2):
+            if r is not None:
+                rr = r[r0:r1].double()
+                ref = ref + rr
+                acc = acc + 2 * U32 * (rr.abs() + ref.abs())
+        for k, t in (("dx", dx), ("dx_bf16", dx_bf16)):
+            if t is not None:
+                u = U_OUT[t.dtype]
+                reps[k].add(t[r0:r1], ref, u * ref.abs() + (1 + u) * acc + 1e-38, r0, t.dtype)
+        colsum["dg"] += (dyc * xh).sum(0)
+        colsum["db"] += dyc.sum(0)
+    worst = max([r.raise_if_bad() for r in reps.values()] + [0.0])
+    for name, got, init, ref in (("dgamma", dgamma, dgamma0, colsum["dg"]), ("dbeta", dbeta, dbeta0, colsum["db"])):
+        if got is not None:
+            ref = ref + (init.double() if init is not None else 0.0)
+            col_worst[name] = assert_rows_within(got, ref, col_tol, what=f"{what}: {name} (per column)")
+    return worst

@@ -13,6 +13,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import tvts_oracle as O  # noqa: E402  (checker only)
+import kernel_bounds as KB  # noqa: E402  (per-element bounds against float64)
 
 DEV = "cuda:0"
 
@@ -65,6 +66,13 @@ def check_guard(buf, M):
     assert torch.isnan(buf[M:].float()).all(), "rows past M were written"
 
 
+def bound(name, v):
+    """the worst |err| / bound of a per-element check (kernel_bounds.py) and the worst used share of its accumulation term,
+    printed for the record"""
+    print(f"BOUND {name} {v:.4g} acc {KB.pop_acc_worst():.4g}")
+    return v
+
+
 # ------------------------------------------------------------------------------------------------ (a) the kernel
 PLAIN = [(40000, 512, 768), (150720, 2304, 768), (150720, 768, 3072), (40000, 3840, 1280), (40000, 5120, 1280),
          (40000, 3072, 256)]
@@ -84,6 +92,7 @@ def test_nt256p_bf16_plain_outputs(K, lib, M, N, Kd):
         assert torch.isfinite(out.float()).all()
         assert rel(out.float(), ref) < tol, (dt, rel(out.float(), ref))
         check_guard(buf, M)
+        bound(f"nt256p plain {M},{N},{Kd} {dt}", KB.check_gemm(out, a, b, bias=bias, what=f"nt256p plain {dt}"))
     # the 128x128 kernel on the same operands: the two tilings agree to fp32 summation-order noise
     assert K.gemm_nt_select(M, N, tile=128) == 128
     o128 = torch.empty(M, N, dtype=torch.float32, device=DEV)
@@ -115,6 +124,7 @@ def test_nt256p_bf16_first_patch_gives_the_bits_of_the_fp32_patch(K, lib, M, N, 
     buf, out = guard_out(M, N, torch.bfloat16)
     K.gemm_nt(a, b, out, bias=bias, tile=256)
     assert rel(out.float(), ref) < 4e-3
+    bound(f"nt256p bf16-first {M},{N},{Kd}", KB.check_gemm(out, a, b, bias=bias, what="nt256p bf16-first patch"))
 
 
 @pytest.mark.parametrize("M,N,Kd,odt", [(150720, 768, 768, torch.float32), (150720, 768, 768, torch.bfloat16),
@@ -129,6 +139,12 @@ def test_nt256p_bf16_residual_epilogue(K, lib, M, N, Kd, odt):
     K.gemm_nt(a, b, out, bias=bias, residual=res)
     assert rel(out.float(), ref) < (2e-5 if odt == torch.float32 else 4e-3)
     check_guard(buf, M)
+    w = KB.check_gemm(out, a, b, bias=bias, residual=res, what=f"nt256p residual {odt}")
+    gbuf, gout = KB.guarded(M, N, odt, DEV)  # guard rows AND columns (leading dimension N + 8)
+    K.gemm_nt(a, b, gout, bias=bias, residual=res)
+    KB.check_guards(gbuf, M, N, "nt256p residual")
+    KB.assert_equal_bits(gout, out, "nt256p residual, wider leading dimension")
+    bound(f"nt256p residual {M},{N},{Kd} {odt}", w)
 
 
 @pytest.mark.parametrize("M,N,Kd,act", [(150720, 3072, 768, "quick_gelu"), (40000, 5120, 1280, "gelu"),
@@ -144,10 +160,18 @@ def test_nt256p_bf16_activation_epilogue(K, lib, M, N, Kd, act):
     K.gemm_nt(a, b, out, bias=bias, act=act, preact=pre)
     assert rel(pre.float(), pre_ref) < 4e-3 and rel(out.float(), fn(pre_ref)) < 5e-3
     check_guard(buf, M); check_guard(pbuf, M)
+    w = KB.check_gemm(out, a, b, bias=bias, act=act, preact=pre, what=f"nt256p {act}")
+    gbuf, gout = KB.guarded(M, N, torch.bfloat16, DEV)
+    gpbuf, gpre = KB.guarded(M, N, torch.bfloat16, DEV)
+    K.gemm_nt(a, b, gout, bias=bias, act=act, preact=gpre)
+    KB.check_guards(gbuf, M, N, "nt256p act out"); KB.check_guards(gpbuf, M, N, "nt256p act preact")
+    KB.assert_equal_bits(gout, out, "nt256p act, wider ld"); KB.assert_equal_bits(gpre, pre, "nt256p preact, wider ld")
     # fp32 output of the same template
     out32 = torch.empty(M, N, dtype=torch.float32, device=DEV)
     K.gemm_nt(a, b, out32, bias=bias, act=act, preact=pre)
     assert rel(out32, fn(pre_ref)) < 5e-5
+    w = max(w, KB.check_gemm(out32, a, b, bias=bias, act=act, what=f"nt256p {act} fp32"))
+    bound(f"nt256p {act} {M},{N},{Kd}", w)
 
 
 @pytest.mark.parametrize("M,N,Kd,act", [(150720, 3072, 768, "quick_gelu"), (40000, 3840, 640, "gelu"),
@@ -164,6 +188,12 @@ def test_nt256p_bf16_gate_epilogue(K, lib, M, N, Kd, act):
     K.gemm_nt(a, b, out, gate_h=h, gate_act=act)
     assert rel(out.float(), ref) < 5e-3, rel(out.float(), ref)
     check_guard(buf, M)
+    w = KB.check_gemm(out, a, b, gate_h=h, gate_act=act, what=f"nt256p gate {act}")
+    gbuf, gout = KB.guarded(M, N, torch.bfloat16, DEV)
+    K.gemm_nt(a, b, gout, gate_h=h, gate_act=act)
+    KB.check_guards(gbuf, M, N, "nt256p gate")
+    KB.assert_equal_bits(gout, out, "nt256p gate, wider ld")
+    bound(f"nt256p gate {act} {M},{N},{Kd}", w)
 
 
 def test_nt256p_strided_views_and_forced_small_shapes(K, lib):
@@ -181,6 +211,7 @@ def test_nt256p_strided_views_and_forced_small_shapes(K, lib):
             ref = a.float() @ b.float().t()
             assert rel(out.float(), ref) < 4e-3, (M, N, Kd, rel(out.float(), ref))
             assert torch.isnan(obig[:, N:].float()).all()
+            bound(f"nt256p strided {M},{N},{Kd}", KB.check_gemm(out, a, b, what=f"nt256p strided {M},{N},{Kd}"))
 
 
 # ------------------------------------------------------------------------------------------------ (b) the engine step

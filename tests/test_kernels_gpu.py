@@ -1521,3 +1521,573 @@ def test_two_threads_call_different_shapes_and_options_concurrently(K):
         for r in both[sd]:
             for x, y in zip(r, alone[sd][0]):
                 assert torch.equal(x.view(torch.int16) if x.dtype == torch.bfloat16 else x, y.view(torch.int16) if y.dtype == torch.bfloat16 else y)
+
+
+# ------------------------------------------------------------------------------------------------ per-element bounds (kernel_bounds.py)
+# Whole-tensor rel gates above miss errors confined to a few hundred elements; these tests hold every element to a derived bound
+# (GEMM, LayerNorm), every (row, head) slice or dgamma / dbeta column to a calibrated tolerance, and exact operations to their bits,
+# with NaN / 0xFF guard rows and columns around what a kernel writes.  Each prints its worst |err| / bound ("BOUND" lines).
+import kernel_bounds as KB  # noqa: E402
+
+
+def _bound(name, v):
+    """print the worst |err| / bound and the worst used share of the bounds' accumulation terms (KB.Report.worst_acc)"""
+    print(f"BOUND {name} {v:.4g} acc {KB.pop_acc_worst():.4g}")
+    return v
+
+
+def _form(got, a, b, **kw):
+    """check_gemm of one form, its own line in the record"""
+    acc0 = KB.pop_acc_worst()
+    w = KB.check_gemm(got, a, b, **kw)
+    acc = KB.pop_acc_worst()
+    print(f"FORM {kw['what']} {w:.4g} acc {acc:.4g}")
+    KB.ACC_WORST[0] = max(acc0, acc)
+    return w
+
+
+# forms a parametrised shape must take (the shapes test_gemm_nt_streamk / test_gemm_nt_ring_gives_the_bits_of_the_128_kernel /
+# test_gemm_tn_fused_reduce_gives_the_bits_of_the_reduce_pass run them on): a refusal there fails instead of dropping the form
+NT_MUST_TAKE = {(9420, 768, 3072): {"streamk"}, (5856, 768, 768): {"ring", "ring4"}}
+TN_MUST_FUSE = {(9420, 768, 768), (40001, 768, 768), (4097, 1280, 640)}
+
+
+def _ops(M, N, Kd, seed, dev=DEV):
+    g = torch.Generator(device=dev).manual_seed(seed)
+    a = torch.randn(M, Kd, generator=g, device=dev).bfloat16()
+    b = (torch.randn(N, Kd, generator=g, device=dev) * Kd ** -0.5).bfloat16()
+    return a, b, torch.randn(N, generator=g, device=dev)
+
+
+@pytest.mark.parametrize("M,N,K_", [(1000, 768, 768), (77, 2304, 256), (9420, 768, 3072), (5856, 768, 768)])
+def test_gemm_nt_forms_within_the_bound(K, M, N, K_):
+    """NT plain / epilogues / side_deriv / stream-K / ring forms, every element within gemm_bound, guard rows and columns kept"""
+    a, b, bias = _ops(M, N, K_, seed=M + N)
+    res = torch.randn(M, N, device=DEV)
+    h = (torch.randn(M, N, device=DEV) * 1.5).bfloat16()
+    forms = [dict(tile=None), dict(tile=128), dict(tile=256), dict(streamk=True), dict(tile="ring"), dict(tile="ring4")]
+    worst = 0.0
+    taken = set()
+    for f in forms:
+        name = "streamk" if f.get("streamk") else str(f.get("tile"))
+        for dt in (torch.bfloat16, torch.float32):
+            buf, out = KB.guarded(M, N, dt, DEV)
+            sk0 = K.STREAMK_TAKEN[0]
+            try:
+                K.gemm_nt(a, b, out, bias=bias, **f)
+            except K.HipError:
+                assert f.get("streamk") or "ring" in str(f.get("tile")), f  # a form the shape cannot take refuses it (no silent fall-back)
+                print(f"FORM nt {name} {dt} refused at {M},{N},{K_}")
+                continue
+            if f.get("streamk"):
+                assert K.STREAMK_TAKEN[0] == sk0 + 1, "stream-K accepted but not taken"
+            taken.add(name)
+            worst = max(worst, KB.check_gemm(out, a, b, bias=bias, what=f"nt {f} {dt}"))
+            KB.check_guards(buf, M, N, f"nt {f} {dt}")
+        buf, out = KB.guarded(M, N, torch.float32, DEV)
+        if f.get("streamk") is None and "ring" not in str(f.get("tile")):
+            K.gemm_nt(a, b, out, bias=bias, residual=res, **f)
+            worst = max(worst, KB.check_gemm(out, a, b, bias=bias, residual=res, what=f"nt residual {f}"))
+            KB.check_guards(buf, M, N)
+    for act in ("quick_gelu", "gelu"):
+        for tile in (None, 128, 256):
+            for deriv in (False, True):
+                buf, out = KB.guarded(M, N, torch.bfloat16, DEV)
+                pbuf, pre = KB.guarded(M, N, torch.bfloat16, DEV)
+                K.gemm_nt(a, b, out, bias=bias, act=act, preact=pre, tile=tile, side_deriv=deriv)
+                worst = max(worst, KB.check_gemm(out, a, b, bias=bias, act=act, preact=pre, deriv=deriv, what=f"nt {act} {tile} {deriv}"))
+                KB.check_guards(buf, M, N); KB.check_guards(pbuf, M, N)
+                gbuf, gout = KB.guarded(M, N, torch.bfloat16, DEV)
+                hh = pre if deriv else h
+                K.gemm_nt(a, b, gout, gate_h=hh, gate_act=act, tile=tile, side_deriv=deriv)
+                worst = max(worst, KB.check_gemm(gout, a, b, gate_h=hh, gate_act=act, deriv=deriv, what=f"nt gate {act} {tile} {deriv}"))
+                KB.check_guards(gbuf, M, N)
+    buf, out = KB.guarded(M, N, torch.bfloat16, DEV)
+    K.gemm_nt(a, b, out, bias=bias, residual=h)  # the bf16 residual stream through the gate slot
+    worst = max(worst, KB.check_gemm(out, a, b, bias=bias, add_bf16=h, what="nt bf16 residual"))
+    KB.check_guards(buf, M, N)
+    missing = NT_MUST_TAKE.get((M, N, K_), set()) - taken
+    assert not missing, f"forms refused at {M},{N},{K_}: {missing}"
+    _bound(f"gemm_nt_forms[{M},{N},{K_}]", worst)
+
+
+@pytest.mark.parametrize("M,Na,Nb", [(9420, 768, 768), (40001, 768, 768), (4097, 1280, 640), (333, 248, 264)])
+def test_gemm_tn_forms_within_the_bound(K, M, Na, Nb):
+    """TN (weight gradient) in its 128 / 256 tiles, fused reduce, accumulate, and with no workspace (fp32 atomics into an output
+    zeroed by zero_rows_f32_kernel, row pitch ldo > Nb): every element within gemm_bound with K = M, guard columns untouched"""
+    g = torch.Generator(device=DEV).manual_seed(M)
+    p = torch.randn(M, Na, generator=g, device=DEV).bfloat16()
+    q = torch.randn(M, Nb, generator=g, device=DEV).bfloat16()
+    init = torch.randn(Na, Nb, generator=g, device=DEV)
+    pt, qt = p.t(), q.t()
+    worst = 0.0
+    fused_runs = 0
+    for kw in (dict(tile=128), dict(tile=256), dict(tile=128, fused=True), dict(tile=256, fused=True), dict(workspace=False),
+               dict(tile=256, workspace=False)):
+        for accumulate in (False, True):
+            buf, out = KB.guarded(Na, Nb, torch.float32, DEV)
+            if accumulate:
+                out.copy_(init)
+            sk0 = K.STREAMK_TAKEN[0]
+            try:
+                K.gemm_tn(p, q, out, accumulate=accumulate, **kw)
+            except K.HipError:
+                assert kw.get("fused"), kw  # the fused reduce needs a split; a one-split shape refuses it
+                print(f"FORM tn fused {kw} refused at {M},{Na},{Nb}")
+                continue
+            if kw.get("fused"):
+                assert K.STREAMK_TAKEN[0] == sk0 + 1, "fused reduce accepted but not taken"
+                fused_runs += 1
+            worst = max(worst, KB.check_gemm(out, pt, qt, residual=init if accumulate else None, K=M, what=f"tn {kw} acc={accumulate}"))
+            KB.check_guards(buf, Na, Nb, f"tn {kw} acc={accumulate}")
+    if (M, Na, Nb) in TN_MUST_FUSE:
+        assert fused_runs == 4, f"the fused reduce ran {fused_runs} of 4 times at {M},{Na},{Nb}"
+    _bound(f"gemm_tn_forms[{M},{Na},{Nb}]", worst)
+
+
+def test_gemm_tn_grouped_rows_linear_and_small_within_the_bound(K):
+    g = torch.Generator(device=DEV).manual_seed(3)
+    worst = 0.0
+    probs = []
+    for (M, Na, Nb) in ((9420, 768, 768), (9420, 768, 2304), (9420, 3072, 768)):
+        p = torch.randn(M, Na, generator=g, device=DEV).bfloat16()
+        q = torch.randn(M, Nb, generator=g, device=DEV).bfloat16()
+        probs.append(dict(p=p, q=q, out=torch.full((Na, Nb), float("nan"), device=DEV), M=M, accumulate=False, colsum=None))
+    K.TnGroup(probs, workspace=K._tn_workspace(torch.device(DEV))).run()
+    for pr in probs:
+        worst = max(worst, KB.check_gemm(pr["out"], pr["p"].t(), pr["q"].t(), K=pr["M"], what="tn grouped"))
+    # rows_linear: one row per clip (a strided view), bias + fp32 residual
+    for (R, N, Kd, S) in ((192, 768, 3072, 785), (48, 1280, 1280, 7)):
+        x = torch.randn(R * S, Kd, generator=g, device=DEV).bfloat16()
+        w = (torch.randn(N, Kd, generator=g, device=DEV) * Kd ** -0.5).bfloat16()
+        bias, res = torch.randn(N, generator=g, device=DEV), torch.randn(R, N, generator=g, device=DEV)
+        a = x[::S]
+        buf, out = KB.guarded(R, N, torch.float32, DEV)
+        K.rows_linear(a, w, out, bias=bias, residual=res)
+        worst = max(worst, KB.check_gemm(out, a, w, bias=bias, residual=res, what="rows_linear"))
+        KB.check_guards(buf, R, N)
+    # gemm_small (fp32 operands: the products round too -> c = 6), plain and A^T by strides, accumulate
+    for (M, N, Kd) in ((1536, 1536, 512), (333, 512, 1000), (65, 33, 17)):
+        a = torch.randn(M, Kd, generator=g, device=DEV)
+        b = torch.randn(Kd, N, generator=g, device=DEV)
+        bias = torch.randn(N, generator=g, device=DEV)
+        out = torch.full((M, N), float("nan"), device=DEV)
+        K.gemm_small(a, b, out, M=M, N=N, K=Kd, sa=(Kd, 1), sb=(N, 1), alpha=0.5, bias=bias)
+        worst = max(worst, KB.check_gemm(out, a, b.t(), scale=0.5, bias=bias, c=6, what="gemm_small"))
+        init = torch.randn(Kd, N, generator=g, device=DEV)
+        out2 = init.clone()
+        c_ = torch.randn(M, N, generator=g, device=DEV)
+        K.gemm_small(a, c_, out2, M=Kd, N=N, K=M, sa=(1, Kd), sb=(N, 1), accumulate=True)
+        worst = max(worst, KB.check_gemm(out2, a.t(), c_.t(), residual=init, c=6, what="gemm_small A^T accumulate"))
+    _bound("gemm_tn_grouped_rows_linear_small", worst)
+
+
+@pytest.mark.parametrize("M,N,K_", [(1000, 768, 768), (9420, 3072, 768), (777, 1280, 1280)])
+def test_gemm_fp8_forms_within_the_bound(K, M, N, K_):
+    """fp8 NT with tensor and row scales (bf16 / fp32 out, bias, residual, GELU + pre-activation), the fp8 gate form, fp8 TN;
+    S of the bound over the decoded e4m3 values times |sa sb|"""
+    g = torch.Generator(device=DEV).manual_seed(M + 1)
+    a = torch.randn(M, K_, generator=g, device=DEV) * torch.logspace(-3, 1, M, device=DEV)[:, None]
+    b = torch.randn(N, K_, generator=g, device=DEV) * K_ ** -0.5
+    bias, res = torch.randn(N, generator=g, device=DEV), torch.randn(M, N, generator=g, device=DEV)
+    b8, sb = K.quantize_fp8(b)
+    bd = KB.decode_e4m3(b8)
+    worst = 0.0
+    for kind in ("tensor", "rows"):
+        a8, sa = K.quantize_fp8(a) if kind == "tensor" else K.quantize_fp8_rows(a.bfloat16())
+        ad = KB.decode_e4m3(a8)
+        scale = sa.double() * sb.double() if kind == "rows" else float(sa) * float(sb)
+        for dt in (torch.bfloat16, torch.float32):
+            buf, out = KB.guarded(M, N, dt, DEV)
+            K.gemm_nt_fp8(a8, sa, b8, sb, out, bias=bias)
+            worst = max(worst, _form(out, ad, bd, scale=scale, bias=bias, what=f"fp8 {kind} {dt}"))
+            KB.check_guards(buf, M, N)
+        buf, out = KB.guarded(M, N, torch.float32, DEV)
+        K.gemm_nt_fp8(a8, sa, b8, sb, out, bias=bias, residual=res)
+        worst = max(worst, _form(out, ad, bd, scale=scale, bias=bias, residual=res, what=f"fp8 {kind} residual"))
+        KB.check_guards(buf, M, N, f"fp8 {kind} residual")
+        buf, out = KB.guarded(M, N, torch.bfloat16, DEV)
+        pbuf, pre = KB.guarded(M, N, torch.bfloat16, DEV)
+        K.gemm_nt_fp8(a8, sa, b8, sb, out, bias=bias, act="gelu", preact=pre)
+        worst = max(worst, _form(out, ad, bd, scale=scale, bias=bias, act="gelu", preact=pre, what=f"fp8 {kind} gelu"))
+        KB.check_guards(buf, M, N); KB.check_guards(pbuf, M, N)
+        h = (torch.randn(M, N, generator=g, device=DEV) * 1.5).bfloat16()
+        for act in ("quick_gelu", "gelu"):
+            buf, out = KB.guarded(M, N, torch.bfloat16, DEV)
+            K.gemm_nt_fp8(a8, sa, b8, sb, out, gate_h=h, gate_act=act)
+            worst = max(worst, _form(out, ad, bd, scale=scale, gate_h=h, gate_act=act, what=f"fp8 {kind} gate {act}"))
+            KB.check_guards(buf, M, N)
+    # TN: out (+)= sp sq P8^T Q8 over K = M tokens
+    p8, sp = K.quantize_fp8(a.bfloat16())
+    q8, sq = K.quantize_fp8(torch.randn(M, N // 2, generator=g, device=DEV))
+    init = torch.randn(K_, N // 2, generator=g, device=DEV)
+    for accumulate in (False, True):
+        for ws in (True, False):
+            out = init.clone() if accumulate else torch.full((K_, N // 2), float("nan"), device=DEV)
+            K.gemm_tn_fp8(p8, sp, q8, sq, out, accumulate=accumulate, workspace=ws)
+            worst = max(worst, _form(out, KB.decode_e4m3(p8).t(), KB.decode_e4m3(q8).t(), scale=float(sp) * float(sq),
+                                             residual=init if accumulate else None, K=M, what=f"fp8 tn acc={accumulate} ws={ws}"))
+    _bound(f"gemm_fp8_forms[{M},{N},{K_}]", worst)
+
+
+def test_gemm_nt_fp8_e4m3_copy_is_quantize_fp8_rows_of_the_output(K):
+    """q8out (the GELU and gate epilogues of the scaled-MFMA loop): with the bf16 result stored, the e4m3 copy equals
+    quantize_fp8_rows(out, tscale) of it bit for bit and amax is exact; without (store_out=False), within one e4m3 code of it (the
+    H/14 geometry of BASELINE config 5: 58 416 rows, 1280 / 5120 wide)"""
+    M = 58416
+    g = torch.Generator(device=DEV).manual_seed(8)
+    for (N, K_, form) in ((5120, 1280, "gelu"), (1280, 5120, "gate")):
+        a8, sa = K.quantize_fp8_rows(torch.randn(M, K_, generator=g, device=DEV).bfloat16())
+        b8, sb = K.quantize_fp8(torch.randn(N, K_, generator=g, device=DEV) * K_ ** -0.5)
+        ad, bd, scale = KB.decode_e4m3(a8), KB.decode_e4m3(b8), sa.double() * sb.double()
+        bias = torch.randn(N, generator=g, device=DEV)
+        h = (torch.randn(M, N, generator=g, device=DEV) * 1.5).bfloat16()
+        kw = dict(bias=bias, act="gelu") if form == "gelu" else dict(gate_h=h, gate_act="gelu")
+        ts = torch.tensor([2.0 / 448.0], device=DEV)
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
+        pre = torch.empty(M, N, dtype=torch.bfloat16, device=DEV) if form == "gelu" else None
+        q, am = torch.full((M, N), 0xFF, dtype=torch.uint8, device=DEV), torch.zeros(1, device=DEV)
+        K.gemm_nt_fp8(a8, sa, b8, sb, out, preact=pre, q8out=q, q8_scale=ts, q8_amax=am, **kw)
+        if form == "gelu":
+            w = KB.check_gemm(out, ad, bd, scale=scale, bias=bias, act="gelu", preact=pre, what="fp8 q8out gelu")
+        else:
+            w = KB.check_gemm(out, ad, bd, scale=scale, gate_h=h, gate_act="gelu", what="fp8 q8out gate")
+        _bound(f"fp8 q8out {form} out", w)
+        am_ref = torch.zeros(1, device=DEV)
+        q_ref, _ = K.quantize_fp8_rows(out, tscale=ts, amax=am_ref)
+        KB.assert_equal_bits(q, q_ref, f"fp8 q8out {form} bytes")
+        assert float(am) == float(out.float().abs().max()) == float(am_ref), (float(am), float(am_ref))
+        q2, am2 = torch.full((M, N), 0xFF, dtype=torch.uint8, device=DEV), torch.zeros(1, device=DEV)
+        K.gemm_nt_fp8(a8, sa, b8, sb, out, preact=pre, q8out=q2, q8_scale=ts, q8_amax=am2, store_out=False, **kw)
+        # alone, the copy is quantised straight from the fp32 result (gemm_nt256.h: no bf16 tensor is written, none is rounded
+        # first): the bytes are those of the stored form or the neighbouring e4m3 code (the double rounding through bf16 differs
+        # from one rounding), and amax is max |fp32 result|, within the bf16 rounding of the stored form's
+        d1, d2 = KB.decode_e4m3(q), KB.decode_e4m3(q2)
+        assert bool(torch.isfinite(d2).all())
+        mag = torch.maximum(d1.abs(), d2.abs()).clamp_min(2.0 ** -6)
+        spacing = torch.exp2(torch.floor(torch.log2(mag)) - 3)
+        KB.assert_within(d2, d1, spacing, f"fp8 q8out {form} bytes, store_out=False (one e4m3 code)")
+        assert abs(float(am2) - float(am)) <= 2.0 ** -8 * float(am), (float(am2), float(am))
+
+
+# ---- LayerNorm at the step's sizes: 150 720 x 768 (B/16, 192 pairs), 58 416 x 1280 (H/14, 48 pairs, 16 frames, 76 kept patches),
+# and a row count that is not a multiple of 4; past 8192 rows the forward's waves walk rows two at a time, the backward runs on a
+# persistent grid
+# per-column relative error of dgamma / dbeta, calibrated on the MI355X.  Worst measured over the three sizes: dgamma 1.02e-5,
+# dbeta 3.95e-6; on the hybrid stream dgamma 9.65e-6, dbeta 3.95e-6.  5e-5 is >= 3x each of them and under the whole-vector gates
+# (1e-4 for both in test_layernorm; 1e-3 / 1e-4 for dgamma / dbeta in test_layernorm_on_the_hybrid_stream)
+LN_COL_TOL = 5e-5
+
+
+@pytest.mark.parametrize("M,W,period", [(150720, 768, 785), (58416, 1280, 1217), (9421, 768, 0)])
+def test_layernorm_at_the_step_sizes_within_the_bound(K, M, W, period):
+    g = torch.Generator(device=DEV).manual_seed(M)
+    x = torch.randn(M, W, generator=g, device=DEV) * 2 + 0.3
+    gamma, beta = 1 + 0.1 * torch.randn(W, generator=g, device=DEV), 0.1 * torch.randn(W, generator=g, device=DEV)
+    eps = 1e-5
+    worst, cols = 0.0, {}
+    mean, rstd = torch.full((M,), float("nan"), device=DEV), torch.full((M,), float("nan"), device=DEV)
+    for xin in (x, x.bfloat16()):  # the fp32 stream input, the bf16 input (ln_fwd8; bf16 rows have no fp32-output form)
+        for odt in ((torch.bfloat16, torch.float32) if xin.dtype == torch.float32 else (torch.bfloat16,)):
+            buf, y = KB.guarded(M, W, odt, DEV)
+            K.layernorm_fwd(xin, gamma, beta, eps, y, mean, rstd)
+            worst = max(worst, KB.ln_fwd_check(xin.float(), gamma, beta, eps, y, mean, rstd, what=f"ln fwd {xin.dtype} -> {odt}"))
+            KB.check_guards(buf, M, W)
+        # the fused e4m3 copy: the bytes of quantize_fp8_rows of the bf16 output
+        y = torch.empty(M, W, dtype=torch.bfloat16, device=DEV)
+        q, rs = torch.full((M, W), 0xFF, dtype=torch.uint8, device=DEV), torch.empty(M, device=DEV)
+        K.layernorm_fwd(xin, gamma, beta, eps, y, torch.empty(M, device=DEV), torch.empty(M, device=DEV), q8=q, row_scale=rs)
+        worst = max(worst, KB.ln_fwd_check(xin.float(), gamma, beta, eps, y, what="ln fwd fp8 copy form"))
+        q_ref, rs_ref = K.quantize_fp8_rows(y)
+        KB.assert_equal_bits(q, q_ref, "ln fwd e4m3 copy"); KB.assert_equal_bits(rs, rs_ref, "ln fwd row scales")
+    # backward: fp32 x, fp32 res1 + bf16 res2, dgamma / dbeta accumulated into nonzero initial values
+    K.layernorm_fwd(x, gamma, beta, eps, torch.empty(M, W, dtype=torch.bfloat16, device=DEV), mean, rstd)
+    dy = torch.randn(M, W, generator=g, device=DEV).bfloat16()
+    res1, res2 = torch.randn(M, W, generator=g, device=DEV), torch.randn(M, W, generator=g, device=DEV).bfloat16()
+    dg0, db0 = torch.randn(W, generator=g, device=DEV), torch.randn(W, generator=g, device=DEV)
+    dg, db = dg0.clone(), db0.clone()
+    dbuf, dx = KB.guarded(M, W, torch.float32, DEV)
+    bbuf, dxb = KB.guarded(M, W, torch.bfloat16, DEV)
+    K.layernorm_bwd(dy, x, mean, rstd, gamma, dx, dx_bf16=dxb, res1=res1, res2=res2, dgamma=dg, dbeta=db)
+    worst = max(worst, KB.ln_bwd_check(dy, x, mean, rstd, gamma, dx=dx, dx_bf16=dxb, res1=res1, res2=res2, dgamma=dg, dbeta=db,
+                                       dgamma0=dg0, dbeta0=db0, col_tol=LN_COL_TOL, col_worst=cols, what="ln bwd"))
+    KB.check_guards(dbuf, M, W); KB.check_guards(bbuf, M, W)
+    if period:  # the hybrid stream: bf16 rows, the CLS rows (r % period == 0) in fp32 side arrays
+        Bc = M // period
+        cls_rows = torch.arange(Bc, device=DEV) * period
+        xs = x.bfloat16()
+        cls_x = x[cls_rows].contiguous()
+        xs[cls_rows] = 777.0
+        truth = xs.float()
+        truth[cls_rows] = cls_x
+        y = torch.empty(M, W, dtype=torch.bfloat16, device=DEV)
+        K.layernorm_fwd(xs, gamma, beta, eps, y, mean, rstd, cls_x=cls_x, cls_period=period)
+        worst = max(worst, KB.ln_fwd_check(truth, gamma, beta, eps, y, mean, rstd, what="ln fwd hybrid"))
+        res1h = torch.randn(M, W, generator=g, device=DEV)
+        cls_res1 = res1h[cls_rows].contiguous()
+        r1b = res1h.bfloat16()
+        truth_r1 = r1b.float()
+        truth_r1[cls_rows] = cls_res1
+        dg, db = dg0.clone(), db0.clone()
+        bbuf, dxb = KB.guarded(M, W, torch.bfloat16, DEV)
+        cls_dx = torch.full((Bc, W), float("nan"), device=DEV)
+        K.layernorm_bwd(dy, xs, mean, rstd, gamma, None, dx_bf16=dxb, res1=r1b, res2=res2, dgamma=dg, dbeta=db,
+                        cls_period=period, cls_x=cls_x, cls_res1=cls_res1, cls_dx=cls_dx)
+        worst = max(worst, KB.ln_bwd_check(dy, truth, mean, rstd, gamma, dx_bf16=dxb, res1=truth_r1, res2=res2, what="ln bwd hybrid"))
+        # the CLS rows' fp32 result, then dgamma / dbeta: the plain launch sums over the bf16-rounded stream rows (see the hybrid test)
+        worst = max(worst, KB.ln_bwd_check(dy[cls_rows], truth[cls_rows], mean[cls_rows], rstd[cls_rows], gamma, dx=cls_dx,
+                                           res1=cls_res1, res2=res2[cls_rows], what="ln bwd hybrid CLS rows"))
+        KB.check_guards(bbuf, M, W)
+        cw = {}
+        xs_seen = xs.float()  # (the stream rows were refreshed with the CLS rows' bf16 rounding by the forward)
+        KB.ln_bwd_check(dy, xs_seen, mean, rstd, gamma, dgamma=dg, dbeta=db, dgamma0=dg0, dbeta0=db0, col_tol=LN_COL_TOL, col_worst=cw,
+                        what="ln bwd hybrid")
+        cols["hybrid_dgamma"], cols["hybrid_dbeta"] = cw["dgamma"], cw["dbeta"]
+    _bound(f"layernorm[{M},{W}]", worst)
+    for k, v in cols.items():
+        _bound(f"layernorm[{M},{W}] {k} (per-column rel)", v)
+
+
+# ---- short-sequence attention (text tower: L = 32, causal, 8 heads, dh 64) where each wave walks several groups
+# per (row, head) relative L2 of the error beyond the bf16 rounding of each output value (rows_rel with out_dtype), calibrated on
+# the MI355X.  Worst measured over the short-sequence and divided tests: out 2.25e-3, dq 3.81e-3, dk 3.24e-3, dv 3.15e-3; each tol
+# >= 3x that and under the whole-tensor gates (8e-3 forward, 2e-2 backward)
+ATTN_ROW_TOL = {"out": 7e-3, "dq": 1.2e-2, "dk": 1.2e-2, "dv": 1.2e-2}
+
+
+def _ref_full_dev(qkv, heads, causal, dO):
+    """float64 autograd of softmax attention on the GPU (the checker of _ref_full, on the device)"""
+    B, S, W3 = qkv.shape
+    W = W3 // 3
+    dh = W // heads
+    x = qkv.double().clone().requires_grad_(True)
+    t = x.reshape(B, S, 3, heads, dh)
+    q, k, v = (t[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+    s = (q * dh ** -0.5) @ k.transpose(-1, -2)
+    if causal:
+        s = s + torch.full((S, S), float("-inf"), dtype=torch.float64, device=qkv.device).triu(1)
+    o = (torch.softmax(s, -1) @ v).permute(0, 2, 1, 3).reshape(B, S, W)
+    o.backward(dO.double())
+    return o.detach(), x.grad
+
+
+@pytest.mark.parametrize("B", [768, 1600])
+def test_short_sequence_attention_per_row_at_the_step_size(K, B):
+    heads, S, dh, causal = 8, 32, 64, True
+    W = heads * dh
+    g = torch.Generator(device=DEV).manual_seed(B)
+    qkv = torch.randn(B * S, 3 * W, generator=g, device=DEV).bfloat16()
+    dO = torch.randn(B * S, W, generator=g, device=DEV).bfloat16()
+    obuf, out = KB.guarded(B * S, W, torch.bfloat16, DEV)
+    lse, delta = torch.full((B * S, heads), float("nan"), device=DEV), torch.empty(B * S, heads, device=DEV)
+    K.attn_fwd("full", qkv, out, lse, B=B, heads=heads, S=S, causal=causal, head_dim=dh)
+    dbuf, dqkv = KB.guarded(B * S, 3 * W, torch.bfloat16, DEV)
+    K.attn_bwd("full", qkv, dO, out, lse, delta, dqkv, B=B, heads=heads, S=S, causal=causal, head_dim=dh)
+    torch.cuda.synchronize()
+    KB.check_guards(obuf, B * S, W); KB.check_guards(dbuf, B * S, 3 * W)
+    ro, rd = _ref_full_dev(qkv.view(B, S, 3 * W), heads, causal, dO.view(B, S, W))
+    ro, rd = ro.reshape(B * S, W), rd.reshape(B * S, 3 * W)
+    w = KB.assert_rows_within(out, ro, ATTN_ROW_TOL["out"], groups=heads, what="short attn out", out_dtype=torch.bfloat16)
+    _bound(f"short_attn[{B}] out (per-row rel)", w)
+    for nm, sl in (("dq", slice(0, W)), ("dk", slice(W, 2 * W)), ("dv", slice(2 * W, 3 * W))):
+        w = KB.assert_rows_within(dqkv[:, sl], rd[:, sl], ATTN_ROW_TOL[nm], groups=heads, what=f"short attn {nm}",
+                                  out_dtype=torch.bfloat16)
+        _bound(f"short_attn[{B}] {nm} (per-row rel)", w)
+
+
+# ---- divided space-time attention at the step's geometry, per (row, head) against float64 autograd of O.divided_attention_core
+DIVIDED = {"B16": dict(B=24, T=8, n=98, heads=12, dh=64), "H14": dict(B=2, T=16, n=76, heads=16, dh=80)}
+
+
+def _divided_case(geo, mode, seed):
+    c = DIVIDED[geo]
+    B, T, n, heads, dh = c["B"], c["T"], c["n"], c["heads"], c["dh"]
+    S, W = 1 + T * n, heads * dh
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    qkv = torch.randn(B * S, 3 * W, generator=g, device=DEV).bfloat16()
+    dO = torch.randn(B * S, W, generator=g, device=DEV).bfloat16()
+    x = qkv.view(B, S, 3 * W).double().requires_grad_(True)
+    ro = O.divided_attention_core(x, heads, mode, T, n)
+    ro.backward(dO.view(B, S, W).double())
+    return (B, T, n, heads, dh, S, W), qkv, dO, ro.detach().reshape(B * S, W), x.grad.reshape(B * S, 3 * W)
+
+
+def _rows_check(got, ref, tol, heads, B, S, what):
+    """every (row, head) slice, and the CLS rows (row 0 of every clip: the cross-group merges / sums) on their own"""
+    w = KB.assert_rows_within(got, ref, tol, groups=heads, what=what, out_dtype=torch.bfloat16)
+    cls = torch.arange(B, device=got.device) * S
+    wc = KB.assert_rows_within(got[cls], ref[cls], tol, groups=heads, what=what + " (CLS rows)", out_dtype=torch.bfloat16)
+    return w, wc
+
+
+@pytest.mark.parametrize("fused", [True, False])
+@pytest.mark.parametrize("mode", ["time", "space"])
+@pytest.mark.parametrize("geo", ["B16", "H14"])
+def test_divided_attention_per_row_at_the_step_geometry(K, geo, mode, fused):
+    """forward fused and split (the streaming kernels + CLS merge), backward in the fused single-launch kernels the engine runs.
+    (The split backward -- delta from the bf16 output, then separate dQ / dK,dV passes -- keeps its whole-tensor gates in
+    test_divided_attention / test_attention_site_backward: per (row, head) its time-mode dQ reaches 0.105 in a few slices of
+    B/16, which is not settled yet.)"""
+    (B, T, n, heads, dh, S, W), qkv, dO, ro, rd = _divided_case(geo, mode, seed=len(geo) + 7 * (mode == "time") + 3 * fused)
+    parts = max(T, -(-n // 28))
+    with K.options(attn_fused=fused):
+        obuf, out = KB.guarded(B * S, W, torch.bfloat16, DEV)
+        lse = torch.full((B * S, heads), float("nan"), device=DEV)
+        ws = torch.full((B * heads * parts * (dh + 2),), float("nan"), device=DEV)
+        K.attn_fwd_divided(mode, qkv, out, lse, ws, B=B, heads=heads, S=S, T=T, n=n, head_dim=dh)
+    with K.options(attn_fused=True):
+        dbuf, dqkv = KB.guarded(B * S, 3 * W, torch.bfloat16, DEV)
+        delta = torch.full((B * S, heads), float("nan"), device=DEV)
+        acc = torch.full((B, heads, parts, 3, dh), float("nan"), device=DEV)
+        K.attn_bwd(mode, qkv, dO, out, lse, delta, dqkv, B=B, heads=heads, S=S, T=T, n=n, cls_acc=acc, head_dim=dh)
+    torch.cuda.synchronize()
+    KB.check_guards(obuf, B * S, W, "divided attention out"); KB.check_guards(dbuf, B * S, 3 * W, "divided attention dqkv")
+    tag = f"divided[{geo},{mode},fwd {'fused' if fused else 'split'}]"
+    w, wc = _rows_check(out, ro, ATTN_ROW_TOL["out"], heads, B, S, tag + " out")
+    _bound(tag + " out (per-row rel)", w); _bound(tag + " out CLS (per-row rel)", wc)
+    for nm, sl in (("dq", slice(0, W)), ("dk", slice(W, 2 * W)), ("dv", slice(2 * W, 3 * W))):
+        w, wc = _rows_check(dqkv[:, sl], rd[:, sl], ATTN_ROW_TOL[nm], heads, B, S, f"{tag} {nm}")
+        _bound(f"{tag} {nm} (per-row rel)", w); _bound(f"{tag} {nm} CLS (per-row rel)", wc)
+
+
+@pytest.mark.parametrize("mode", ["time", "space"])
+def test_divided_attention_e4m3_copies_are_quantize_fp8_rows_of_the_outputs(K, mode):
+    """H/14 geometry (BASELINE config 5: n + 1 <= 112, T + 1 <= 32, the engine's _attn_q8): the per-tensor e4m3 copies the forward
+    and backward kernels write equal quantize_fp8_rows(result, tscale) of their bf16 results bit for bit, amax exact"""
+    (B, T, n, heads, dh, S, W), qkv, dO, ro, rd = _divided_case("H14", mode, seed=11)
+    parts = max(T, -(-n // 28))
+    out = torch.empty(B * S, W, dtype=torch.bfloat16, device=DEV)
+    lse = torch.empty(B * S, heads, device=DEV)
+    ws = torch.empty(B * heads * parts * (dh + 2), device=DEV)
+    ts = torch.tensor([1.5 / 448.0], device=DEV)
+    q, am = torch.full((B * S, W), 0xFF, dtype=torch.uint8, device=DEV), torch.zeros(1, device=DEV)
+    K.attn_fwd_divided(mode, qkv, out, lse, ws, B=B, heads=heads, S=S, T=T, n=n, head_dim=dh, q8out=q, q8_scale=ts, q8_amax=am)
+    torch.cuda.synchronize()
+    KB.assert_rows_within(out, ro, ATTN_ROW_TOL["out"], groups=heads, what="divided q8 out", out_dtype=torch.bfloat16)
+    am_ref = torch.zeros(1, device=DEV)
+    q_ref, _ = K.quantize_fp8_rows(out, tscale=ts, amax=am_ref)
+    KB.assert_equal_bits(q, q_ref, f"divided attention {mode} forward e4m3 copy")
+    assert float(am) == float(am_ref) == float(out.float().abs().max()), (float(am), float(am_ref))
+    dqkv = torch.empty(B * S, 3 * W, dtype=torch.bfloat16, device=DEV)
+    delta = torch.empty(B * S, heads, device=DEV)
+    acc = torch.empty(B, heads, parts, 3, dh, device=DEV)
+    q2, am2 = torch.full((B * S, 3 * W), 0xFF, dtype=torch.uint8, device=DEV), torch.zeros(1, device=DEV)
+    K.attn_bwd(mode, qkv, dO, out, lse, delta, dqkv, B=B, heads=heads, S=S, T=T, n=n, cls_acc=acc, head_dim=dh, q8out=q2,
+               q8_scale=ts, q8_amax=am2)
+    torch.cuda.synchronize()
+    KB.assert_rows_within(dqkv, rd, ATTN_ROW_TOL["dq"], groups=3 * heads, what="divided q8 dqkv", out_dtype=torch.bfloat16)
+    am2_ref = torch.zeros(1, device=DEV)
+    q2_ref, _ = K.quantize_fp8_rows(dqkv, tscale=ts, amax=am2_ref)
+    KB.assert_equal_bits(q2, q2_ref, f"divided attention {mode} backward e4m3 copy")
+    assert float(am2) == float(am2_ref) == float(dqkv.float().abs().max()), (float(am2), float(am2_ref))
+
+
+# ---- exact entry points: bit for bit, with guards around what they write
+def _fill_bits(shape, dtype, seed):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    return (torch.randn(*shape, generator=g, device=DEV) * 3).to(dtype)
+
+
+@pytest.mark.parametrize("W", [72, 768, 1280])
+def test_rows_move_is_exact(K, W):
+    Mf, R = 1000, 37
+    gen = torch.Generator(device="cpu").manual_seed(W)
+    rows = torch.cat([torch.tensor([0, Mf - 1]), torch.randperm(Mf - 2, generator=gen)[:R - 2] + 1]).to(torch.int32).to(DEV)
+    rl = rows.long()
+
+    def wide(M, dt, seed):  # leading dimension W + 8, guard columns NaN
+        buf = torch.full((M, W + 8), float("nan"), dtype=dt, device=DEV)
+        buf[:, :W] = _fill_bits((M, W), dt, seed)
+        return buf, buf[:, :W]
+
+    # gather, from fp32 and from bf16, into every packed combination
+    for src_dt in (torch.float32, torch.bfloat16):
+        fbuf, full = wide(Mf, src_dt, 1)
+        for want_f32, want_bf16 in ((True, True), (True, False), (False, True)):
+            pfb, pf = KB.guarded(R, W, torch.float32, DEV) if want_f32 else (None, None)
+            pbb, pb = KB.guarded(R, W, torch.bfloat16, DEV) if want_bf16 else (None, None)
+            K.rows_move("gather", rows, full_f32=full if src_dt == torch.float32 else None,
+                        full_bf16=full if src_dt == torch.bfloat16 else None, packed_f32=pf, packed_bf16=pb)
+            if pf is not None:
+                KB.assert_equal_bits(pf, full[rl].float(), "rows_move gather f32"); KB.check_guards(pfb, R, W)
+            if pb is not None:
+                KB.assert_equal_bits(pb, full[rl].bfloat16(), "rows_move gather bf16"); KB.check_guards(pbb, R, W)
+    # scatter: only the listed rows change, on both sides given
+    ff_buf, ff = wide(Mf, torch.float32, 2)
+    fb_buf, fb = wide(Mf, torch.bfloat16, 3)
+    pf, pb = _fill_bits((R, W), torch.float32, 4), _fill_bits((R, W), torch.bfloat16, 5)
+    want_f, want_b = ff_buf.clone(), fb_buf.clone()
+    want_f[rl, :W], want_b[rl, :W] = pf, pb
+    K.rows_move("scatter", rows, full_f32=ff, full_bf16=fb, packed_f32=pf, packed_bf16=pb)
+    KB.assert_equal_bits(ff_buf, want_f, "rows_move scatter f32"); KB.assert_equal_bits(fb_buf, want_b, "rows_move scatter bf16")
+    # scatter_add: fp32 add, the bf16 copy is the round-to-nearest-even of that sum
+    want_f = ff_buf.clone()
+    want_f[rl, :W] = ff[rl] + pf
+    want_b = fb_buf.clone()
+    want_b[rl, :W] = want_f[rl, :W].bfloat16()
+    K.rows_move("scatter_add", rows, full_f32=ff, full_bf16=fb, packed_f32=pf)
+    KB.assert_equal_bits(ff_buf, want_f, "rows_move scatter_add f32"); KB.assert_equal_bits(fb_buf, want_b, "rows_move scatter_add bf16")
+    want_f[rl, :W] = want_f[rl, :W] + pf
+    K.rows_move("scatter_add", rows, full_f32=ff, packed_f32=pf)  # without the bf16 copy
+    KB.assert_equal_bits(ff_buf, want_f, "rows_move scatter_add f32 only")
+    KB.assert_equal_bits(fb_buf, want_b, "rows_move scatter_add: the bf16 side untouched")
+
+
+def test_rows_gather_is_exact(K):
+    Mf, R, W = 3000, 300, 768
+    rows = torch.cat([torch.tensor([Mf - 1, 0]), torch.randperm(Mf - 2, generator=torch.Generator().manual_seed(1))[:R - 2] + 1])
+    rows = rows.to(torch.int32).to(DEV)
+    src_buf = torch.full((Mf, W + 8), float("nan"), device=DEV)
+    src_buf[:, :W] = _fill_bits((Mf, W), torch.float32, 6)
+    src = src_buf[:, :W]
+    dbuf, dst = KB.guarded(R, W, torch.float32, DEV)
+    K.rows_gather(src, rows, dst)
+    KB.assert_equal_bits(dst, src[rows.long()], "rows_gather"); KB.check_guards(dbuf, R, W)
+    big = src_buf.clone()
+    want = big.clone()
+    want[rows.long(), :W] = big[rows.long(), :W] + dst
+    K.rows_gather(dst, rows, big[:, :W], scatter_add=True)
+    KB.assert_equal_bits(big, want, "rows_gather scatter_add")
+    K.rows_gather(dst, rows[:0], big[:, :W], scatter_add=True)  # no rows: nothing launched, nothing written
+    KB.assert_equal_bits(big, want, "rows_gather without rows")
+
+
+def test_zero_cols_bf16_and_cast_bf16_f32_are_exact(K):
+    for rows, cols, ld in ((70001, 64, 776), (5, 8, 8), (3000, 768, 2304)):  # 70 001 x 8 vectors: past 2048 x 256, the grid-stride walk
+        x = _fill_bits((rows + 2, ld), torch.bfloat16, rows)
+        want = x.clone()
+        want[:rows, :cols] = 0
+        K.zero_cols_bf16(x[:rows], cols)
+        KB.assert_equal_bits(x, want, f"zero_cols_bf16 {rows} x {cols} / {ld}")
+    for n in (4, 1000, 8 * 1024 * 1024 + 4100):  # the last: more than 8192 x 256 x 4 elements, the grid-stride walk
+        src = _fill_bits((n,), torch.bfloat16, n)
+        src[:3] = torch.tensor([float("inf"), -0.0, float("nan")], dtype=torch.bfloat16)
+        dst = torch.full((n + 16,), float("nan"), device=DEV)
+        K.cast_bf16_f32(src, dst[:n])
+        KB.assert_equal_bits(dst[:n], src.float(), f"cast_bf16_f32 {n}")
+        assert torch.isnan(dst[n:]).all()
+
+
+def test_zero_fill_is_exact_at_every_alignment(K):
+    """tvts_zero_bytes: base 0 - 15 bytes past 16-byte alignment, lengths 0 / 1 / 15 / 16 / 17 / 33 / 4097, one length past
+    8192 x 256 x 16 B = 32 MiB (the grid-stride loop), an empty tensor (was EINVAL: a null pointer with nbytes == 0)"""
+    base = torch.full((8192,), 0xFF, dtype=torch.uint8, device=DEV)
+    assert base.data_ptr() % 16 == 0
+    for off in range(16):
+        for n in (0, 1, 15, 16, 17, 33, 4097):
+            base.fill_(0xFF)
+            K.zero_(base[64 + off:64 + off + n])
+            want = torch.full_like(base, 0xFF)
+            want[64 + off:64 + off + n] = 0
+            KB.assert_equal_bits(base, want, f"zero_ offset {off} length {n}")
+    big_n = 32 * 1024 * 1024 + 4099
+    big = torch.full((big_n + 64,), 0xFF, dtype=torch.uint8, device=DEV)
+    K.zero_(big[3:3 + big_n])
+    assert int(big[3:3 + big_n].count_nonzero()) == 0
+    assert bool((big[:3] == 0xFF).all()) and bool((big[3 + big_n:] == 0xFF).all())
+    f = torch.full((1001,), 5.0, device=DEV)
+    K.zero_(f)
+    assert int(f.count_nonzero()) == 0
+    K.zero_(torch.empty(0, device=DEV))            # an empty tensor: nothing to do, no error (torch's zero_() semantics)
+    K.zero_(torch.empty(0, 768, device=DEV))
+    torch.cuda.synchronize()

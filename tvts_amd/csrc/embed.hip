@@ -658,6 +658,9 @@ __global__ void rows_gather_kernel(const float* __restrict__ src, int lds_, cons
 }
 extern "C" int tvts_rows_gather(const float* src, int ld_src, const int* rows, int R, int W, float* dst, int ld_dst,
                                 int scatter_add, hipStream_t stream) {
+    if (R < 0 || W <= 0) return TVTS_EINVAL;
+    if (R == 0) return TVTS_OK;  // no rows: a zero-block grid is not a valid launch
+    if (!rows || !src || !dst) return TVTS_EINVAL;
     hipLaunchKernelGGL(rows_gather_kernel, dim3(R), dim3(256), 0, stream, src, ld_src, rows, R, W, dst, ld_dst, scatter_add);
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;

@@ -37,8 +37,8 @@ static __global__ void zero_bytes_kernel(unsigned char* __restrict__ p, long hea
 // the dense gradient buffers of the non-pruned paths.  A kernel, not hipMemsetAsync: captured memset nodes did not reliably zero
 // their buffer on hipGraph replay (ROCm 7.x: the second replay of the captured small-architecture step left garbage in the gradient)
 extern "C" int tvts_zero_bytes(void* p, long nbytes, hipStream_t stream) {
+    if (nbytes == 0) return TVTS_OK;  // an empty tensor: nothing to write, whatever its (possibly null) data pointer
     if (!p || nbytes < 0) return TVTS_EINVAL;
-    if (nbytes == 0) return TVTS_OK;
     const long mis = (long)((16 - ((uintptr_t)p & 15)) & 15);
     const long head = mis < nbytes ? mis : nbytes;
     const long n16 = (nbytes - head) / 16;
