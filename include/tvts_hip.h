@@ -238,7 +238,11 @@ int tvts_attn_bwd(int mode, const void* qkv, int ld, int B, int heads, int S, in
               int lddo, const void* O, int ldo, const float* lse2, float* delta, void* dqkv, int lddq, float* cls_acc,
               long cls_acc_elems, int opts, hipStream_t stream);
 /* forward of one divided-attention site including the CLS row (VarAttention.forward video_encoder_ViT_B_16.py:38-76);
- * cls_ws: fp32 scratch of >= B * heads * max(T, ceil(n / 28)) * (dh + 2) elements (partial softmax states of the CLS query) */
+ * cls_ws: fp32 scratch of >= B * heads * max(T, ceil(n / 28)) * (dh + 2) elements (partial softmax states of the CLS query).
+ * lse2 == NULL (here and in tvts_attn_fwd of every mode, tvts_attn_fwd_rowq, tvts_attn_fwd_tail; dh 64 and 80): a forward-only
+ * call that stores no log-sum-exp (the inference encoders); with lse2 given nothing changes.  Forward-only SPACE calls with
+ * 112 < n + 1 <= 272 (full frames: n = 196, 256) run a fused kernel of their own -- a block per (clip, head, frame), the group's
+ * K / V in LDS once, the CLS row from the per-frame partial states -- instead of the streaming kernel + the CLS-query pass. */
 int tvts_attn_fwd_divided(int mode, const void* qkv, int ld, int B, int heads, int S, int T, int n, void* out, int ldo,
                       float* lse2, float* cls_ws, long cls_ws_elems, int opts, hipStream_t stream);
 /* the two site entry points with the per-tensor e4m3 copy of their result written by the kernels themselves (BASELINE config 5: the

@@ -401,7 +401,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnGeom g, const bf16* _
             const bf16x4 v = {(bf16)(o[dt][0] * inv), (bf16)(o[dt][1] * inv), (bf16)(o[dt][2] * inv), (bf16)(o[dt][3] * inv)};
             *(bf16x4*)(op + dt * 16 + gq * 4) = v;
         }
-        if (gq == 0) lse2[(size_t)row * g.heads + r.h] = m_run + log2f(l_run);
+        if (gq == 0 && lse2) lse2[(size_t)row * g.heads + r.h] = m_run + log2f(l_run);
     }
 }
 
@@ -808,7 +808,7 @@ __global__ __launch_bounds__(256) void attn_fwd_shared_kernel(AttnGeom g, const 
             const int j = q0 + rr;
             return (active && j < r.nq) ? out + (size_t)q_row<MODE>(g, r, j) * ldo + hcol : nullptr; });
     }
-    if (active && qi < r.nq && gq == 0) lse2[(size_t)q_row<MODE>(g, r, qi) * g.heads + r.h] = m_run + log2f(l_run);
+    if (active && qi < r.nq && gq == 0 && lse2) lse2[(size_t)q_row<MODE>(g, r, qi) * g.heads + r.h] = m_run + log2f(l_run);
 }
 
 template <int MODE, bool TR, bool DROP = false>
@@ -1756,7 +1756,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_space_fused_kernel(AttnGeom g
                 return (j >= 1 && j < m) ? out + (size_t)k_row<MODE_SPACE>(g, r, j) * ldo + hcol : nullptr; }, &q8o);
         }
         if (qj >= 1 && qj < m) {
-            if (gq == 0) lse2[(size_t)k_row<MODE_SPACE>(g, r, qj) * g.heads + r.h] = mx + log2f(l);
+            if (gq == 0 && lse2) lse2[(size_t)k_row<MODE_SPACE>(g, r, qj) * g.heads + r.h] = mx + log2f(l);
         } else if (qj == 0) {  // this frame's partial softmax state of the CLS query
             float* cp = cls_part + ((size_t)(r.b * g.heads + r.h) * g.T + r.sub) * (DH + 2);
             if (gq == 0) { cp[0] = mx; cp[1] = l; }
@@ -1771,6 +1771,124 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_space_fused_kernel(AttnGeom g
         }
     }
     q8o.finish(g, lane);
+}
+
+// ================================================================================================
+// FUSED SPACE forward for FULL-FRAME groups, forward-only calls (lse2 == NULL): 112 < n + 1 <= 272 (n = 196 of B/16, n = 256 of
+// H/14 at mask ratio 0).  The ownership of attn_fwd_space_fused_kernel -- a block per (clip, head, frame), the group's K and V
+// staged in LDS once, every query tile of the group in the block, single-pass softmax over register-resident scores, the frame's
+// partial CLS state to cls_part for attn_cls_merge_kernel -- with SPACE_BIG_WAVES = 8 waves per block: K + V of 17 tiles take
+// 87 KB (dh 64) / 104 KB (dh 80) of LDS, so one block fits a CU, and eight waves instead of four keep two per SIMD.  Replaces
+// the streaming SPACE kernel (K / V read once per 64 queries) and the separate all-S CLS-query pass.  No log-sum-exp is stored.
+// ================================================================================================
+#define SPACE_BIG_MAX_TILES 17
+#define SPACE_BIG_WAVES 8
+template <int MT>
+__global__ __launch_bounds__(64 * SPACE_BIG_WAVES) void attn_fwd_space_big_kernel(AttnGeom g, const bf16* __restrict__ qkv,
+                                                                              bf16* __restrict__ out, int ldo,
+                                                                              float* __restrict__ cls_part) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];  // K | V tiles of the group | per-wave output-staging patches
+    constexpr int NW = SPACE_BIG_WAVES, NTH = 64 * NW;
+    constexpr int RA = MT * 16, TB = RA * VSTRIDE, NU = (MT + 1) / 2;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const Grp r = decode<MODE_SPACE>(g, blockIdx.x);
+    const int m = g.n + 1;  // <= RA (host)
+    char* Ks = smem;
+    char* Vs = Ks + TB;
+    char* opatch = Vs + TB + wave * 1024;
+    const int gq = lane >> 4, li = lane & 15;
+    const int hcol = r.h * DH;
+    {
+        constexpr int PER = (RA * NCH + NTH - 1) / NTH;
+        bf16x8 stg[2][PER];
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int i = 0; i < PER; ++i) {
+                const int c = tid + NTH * i, row = c / NCH, ch = c % NCH;
+                stg[t][i] = sel8(row < m, ldg8(qkv + (size_t)k_row<MODE_SPACE>(g, r, row < m ? row : 0) * g.ld + (1 + t) * g.W + hcol + ch * 8));
+            }
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int i = 0; i < PER; ++i) {
+                const int c = tid + NTH * i, row = c / NCH, ch = c % NCH;
+                if (row < RA) *(bf16x8*)(smem + t * TB + row * VSTRIDE + ch * 16) = stg[t][i];  // rows m .. RA: zeros
+            }
+    }
+    bf16x8 qf[KS];
+    {
+        const int qj = wave * 16 + li;
+        ld_frags(qkv + (size_t)k_row<MODE_SPACE>(g, r, qj < m ? qj : m - 1) * g.ld + hcol, gq, qf);
+    }
+    __syncthreads();
+    for (int qt = wave; qt < MT; qt += NW) {
+        const int qj = qt * 16 + li;
+        f32x4 st[2 * NU];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < 2 * NU; ++t) {
+            st[t] = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+            if (t < MT) {
+                f32x4 sc = {0, 0, 0, 0};
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks)
+                    sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row(Ks, t * 16 + li, ks, gq), qf[ks], sc, 0, 0, 0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int key = t * 16 + gq * 4 + e;
+                    const bool ok = key < m && !(key == 0 && qj == 0 && r.sub != 0);  // CLS x CLS: frame 0 only
+                    const float v = ok ? sc[e] * g.scale2 : -INFINITY;
+                    st[t][e] = v;
+                    mx = fmaxf(mx, v);
+                }
+            }
+        }
+        mx = group_max(mx);
+        float rs = 0.f;
+#pragma unroll
+        for (int t = 0; t < 2 * NU; ++t)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float pp = __builtin_amdgcn_exp2f(st[t][e] - mx);
+                st[t][e] = pp;
+                rs += pp;
+            }
+        const float l = group_sum(rs);
+        f32x4 o[DT];
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) o[dt] = (f32x4){0, 0, 0, 0};
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            bf16x8 pf;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) pf[j] = (bf16)st[2 * u + (j >> 2)][j & 3];
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt)
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_T_lim<true>(Vs, u, dt, lane, RA), pf, o[dt], 0, 0, 0);
+        }
+        {
+            const float inv = 1.0f / l;
+            f32x4 on[DT];
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) on[dt] = o[dt] * inv;
+            store_tile_rows(opatch, on, lane, [&](int rr) -> bf16* {
+                const int j = qt * 16 + rr;
+                return (j >= 1 && j < m) ? out + (size_t)k_row<MODE_SPACE>(g, r, j) * ldo + hcol : nullptr; });
+        }
+        if (qj == 0) {  // this frame's partial softmax state of the CLS query
+            float* cp = cls_part + ((size_t)(r.b * g.heads + r.h) * g.T + r.sub) * (DH + 2);
+            if (gq == 0) { cp[0] = mx; cp[1] = l; }
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) cp[2 + dt * 16 + gq * 4 + e] = o[dt][e];
+        }
+        if (qt + NW < MT) {
+            const int qn = (qt + NW) * 16 + li;
+            ld_frags(qkv + (size_t)k_row<MODE_SPACE>(g, r, qn < m ? qn : m - 1) * g.ld + hcol, gq, qf);
+        }
+    }
 }
 
 template <int MT, bool TR, int RS_ = 0>
@@ -1886,7 +2004,7 @@ __global__ __launch_bounds__(256) void attn_fwd_time_fused_kernel(AttnGeom g, co
                     const int j = qt * 16 + rr;
                     return (j >= 1 && j < m) ? out + (size_t)k_row<MODE_TIME>(g, r, j) * ldo + hcol : nullptr; }, &q8o);
             }
-            if (qj >= 1 && qj < m && gq == 0) lse2[(size_t)k_row<MODE_TIME>(g, r, qj) * g.heads + r.h] = mx + log2f(l);
+            if (qj >= 1 && qj < m && gq == 0 && lse2) lse2[(size_t)k_row<MODE_TIME>(g, r, qj) * g.heads + r.h] = mx + log2f(l);
             if (qt == 0) {  // column 0 = the CLS query: fold this group's state into the running one
                 const float Mn = fmaxf(Mr, mx);
                 const float a = __builtin_amdgcn_exp2f(Mr - Mn), b = __builtin_amdgcn_exp2f(mx - Mn);
@@ -2038,7 +2156,7 @@ __global__ __launch_bounds__(256) void attn_fwd_seq_fused_kernel(AttnGeom g, con
                     const int j = qt * 16 + rr;
                     return j < m ? out + (row0 + j) * ldo + hcol : nullptr; });
             }
-            if (qj < m && gq == 0) lse2[(row0 + qj) * g.heads + h] = mx + log2f(l);
+            if (qj < m && gq == 0 && lse2) lse2[(row0 + qj) * g.heads + h] = mx + log2f(l);
         }
     }
 }
@@ -2235,7 +2353,7 @@ __global__ void attn_cls_merge_kernel(const float* __restrict__ cls_part, int G,
             q8[row * ldo + h * DH + d] = (unsigned char)(pk & 0xff);
             ax = fabsf(x);
         }
-        if (d == 0) lse2[row * heads + h] = M + log2f(L);
+        if (d == 0 && lse2) lse2[row * heads + h] = M + log2f(L);
     }
     if (q8) amax_publish(q8_amax, wave_max(ax), threadIdx.x & 63);
 }
@@ -2772,6 +2890,25 @@ static int fwd_divided_impl(int mode, const void* qkv, int ld, int B, int heads,
     const bool fs = fused && use_tr && mode == MODE_SPACE && n + 1 <= FUSED_MAX_TILES * 16;
     const bool ft = fused && use_tr && mode == MODE_TIME && T + 1 <= 32;
     const int G = mode == MODE_SPACE ? T : ceil_div(n, TIME_CHUNK);
+    // forward-only SPACE calls with full-frame groups: attn_fwd_space_big_kernel + the CLS merge.  Calls that pass lse2 (the
+    // training forward) keep the streaming kernel + the CLS-query pass below.
+    const bool fb = !lse2 && !q8out && fused && use_tr && mode == MODE_SPACE && n + 1 > FUSED_MAX_TILES * 16 &&
+                    n + 1 <= SPACE_BIG_MAX_TILES * 16;
+    if (fb && cls_ws && cls_ws_elems >= (long)B * heads * T * (DH + 2)) {
+        typedef void (*KernB)(AttnGeom, const bf16*, bf16*, int, float*);
+        const int MT = n + 1 <= 160 ? 10 : n + 1 <= 208 ? 13 : 17;
+        const KernB kern = MT == 10 ? attn_fwd_space_big_kernel<10> : MT == 13 ? attn_fwd_space_big_kernel<13> : attn_fwd_space_big_kernel<17>;
+        const int lds_bytes = 2 * MT * 16 * VSTRIDE + SPACE_BIG_WAVES * 1024;
+        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
+            return TVTS_EINVAL;
+        hipLaunchKernelGGL(kern, dim3(B * heads * T), dim3(64 * SPACE_BIG_WAVES), lds_bytes, stream, g, (const bf16*)qkv, (bf16*)out,
+                           ldo, cls_ws);
+        TVTS_LAUNCH_CHECK();
+        hipLaunchKernelGGL(attn_cls_merge_kernel, dim3(B * heads), dim3(DH <= 64 ? 64 : 128), 0, stream, cls_ws, T, heads, S,
+                           (bf16*)out, ldo, (float*)nullptr, (unsigned char*)nullptr, (const float*)nullptr, (float*)nullptr);
+        TVTS_LAUNCH_CHECK();
+        return TVTS_OK;
+    }
     if ((fs || ft) && cls_ws && cls_ws_elems >= (long)B * heads * G * (DH + 2)) {
         typedef void (*Kern)(AttnGeom, const bf16*, bf16*, int, float*, float*);
         Kern kern = nullptr;

@@ -28,6 +28,27 @@ def class_embedding(model, prompt_ids: torch.Tensor, n_patches: int) -> torch.Te
 
 
 @torch.no_grad()
+def class_embeddings(model, prompt_ids_per_class) -> torch.Tensor:
+    """[C, E]: class_embedding of every class (a list of [P_c, ctx] prompt-id tensors), text only -- the prompts of all
+    classes through model.encode_text, without dummy frames.  Classes whose captions end at the same token position share a
+    pass: the caption length L of a pass is the longest caption in it, and a class keeps the L of its own pass in
+    class_embedding, so both evaluate the same arithmetic."""
+    ends = [int(p.argmax(-1).max()) for p in prompt_ids_per_class]
+    out = [None] * len(prompt_ids_per_class)
+    for end in sorted(set(ends)):
+        idx = [c for c, e in enumerate(ends) if e == end]
+        ids = torch.cat([prompt_ids_per_class[c][:, :end + 1].to("cpu", torch.int64) for c in idx])
+        emb = model.encode_text(ids)
+        o = 0
+        for c in idx:
+            P = prompt_ids_per_class[c].shape[0]
+            mean = _l2norm(emb[o:o + P]).mean(dim=0, keepdim=True)
+            out[c] = _l2norm(mean)[0]
+            o += P
+    return torch.stack(out)
+
+
+@torch.no_grad()
 def class_logits(video_emb: torch.Tensor, zeroshot_weights: torch.Tensor) -> torch.Tensor:
     """100 * normalise(video_emb) @ zeroshot_weights (:99-100); zeroshot_weights is [E, n_classes]."""
     v = _l2norm(video_emb)

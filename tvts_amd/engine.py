@@ -271,6 +271,7 @@ class Engine:
         self._back: Dict[str, torch.Tensor] = {}  # the allocations behind buf (grow-only, see _b)
         self._seen: Dict[str, int] = {}           # name -> the forward() count at which its shape last changed
         self._tick = 0
+        self._inf: Dict[str, torch.Tensor] = {}   # the forward-only encoders' workspaces, by role (see _ib)
         self.requires_grad = {name: True for name in store.shapes}
         self.ctx: dict = {}
         self.grad_ready = None  # optional callback(start, end): flat grad range is final (GradSync.reduce_range); may return a wait()
@@ -1339,6 +1340,192 @@ class Engine:
         self._text_join()
         if text_ready_at_join:
             self._ready("text_")
+
+    # ------------------------------------------------------------------ forward-only encoders (feature extraction, zero-shot)
+    # The same numerics as video_forward / text_forward without what only a backward reads: no per-layer activations (the
+    # workspaces below are keyed by ROLE, in a namespace of their own, and reused by every layer: peak ~ one layer), no
+    # act'(x) side output of c_fc, no LayerNorm mean / rstd, no attention log-sum-exp (lse2 = None; forward-only SPACE calls at
+    # full frames take their own fused kernel, attention.hip).  The last ViT block is evaluated for the CLS rows only.  Nothing
+    # of the training path's workspace is read, written or resized.
+    def _ib(self, role, shape, dtype=torch.bfloat16):
+        """encoder workspace `role`: a view of a grow-only byte buffer (roles are reused with other shapes / dtypes)"""
+        shape = tuple(int(s) for s in shape)
+        n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+        back = self._inf.get(role)
+        if back is None or back.numel() < n:
+            self._inf.pop(role, None)  # (the smaller buffer goes first)
+            back = self._inf[role] = torch.empty(max(n, 16), dtype=torch.uint8, device=self.dev)
+        return back[:n].view(dtype).view(shape)
+
+    def _inf_check(self):
+        a = self.arch
+        if a.get("family") == "v1":
+            raise NotImplementedError("the forward-only encoders are built for the v2 models")
+        if a.get("fp8") or a.get("fp8_dgrad") or a.get("fp8_wgrad"):
+            raise NotImplementedError("the forward-only encoders have no e4m3 form; use a bf16 architecture")
+
+    def _ln_inf(self, x, name, eps, y, rows=None, cls_x=None):
+        M = rows.numel() if rows is not None else x.shape[0]
+        kw = dict(cls_x=cls_x, cls_period=M // cls_x.shape[0]) if cls_x is not None else {}
+        K.layernorm_fwd(x, self.P.p(name + ".weight"), self.P.p(name + ".bias"), eps, y, rows=rows, M=M, **kw)
+
+    def _lin_inf(self, a, wname, bname, out, M, act=None, residual=None):
+        # (side_deriv as in _lin: the same epilogue instantiation, whose side output is skipped without preact)
+        K.gemm_nt(a, self.P.w(wname), out, M=M, bias=self.P.p(bname) if bname else None, residual=residual, act=act,
+                  side_deriv=act is not None and self.gate_deriv)
+
+    def _attn_inf(self, qkv, att, mode, B, T, n):
+        h = self.arch["heads"]
+        ws = self._ib("clsws", (B * h * max(T, -(-n // 28)) * (self.dh + 2),), torch.float32)
+        K.attn_fwd_divided(mode, qkv, att, None, ws, B=B, heads=h, S=1 + T * n, T=T, n=n, head_dim=self.dh)
+
+    def encode_video(self, video, keep_dev, B, T, crop=None, resize=None):
+        """-> [B, E] fp32 video embeddings (an encoder workspace: the next encoder call overwrites it).  video: fp32 [B, T, 3, H, W]
+        or uint8 [B, T, H0, W0, 3] on the device; keep_dev: int32 [B, n] kept patches per frame."""
+        self._inf_check()
+        a = self.arch
+        W, E, p, h = a["width"], a["embed"], a["patch"], a["heads"]
+        n = keep_dev.shape[1]
+        S = 1 + T * n
+        M, Mp, Kp = B * S, B * T * n, self.P.conv_kpad
+        # the embedding's fp32 temporaries live in the roles of the first block's qkv and MLP buffers (free until then)
+        cols = self._ib("ln", (Mp, Kp))
+        if video.dtype == torch.uint8:
+            K.patch_gather_u8(video, keep_dev, cols, B=B, T=T, n=n, img=a["image"], patch=p, crop=crop, resize=resize)
+        else:
+            K.patch_gather(video, keep_dev, cols, B=B, T=T, n=n, img=a["image"], patch=p)
+        pe = self._ib("h", (Mp, W), torch.float32)
+        K.gemm_nt(cols, self.P.w_conv(), pe, M=Mp)
+        tok = self._ib("qkv", (M, W), torch.float32)
+        K.vit_assemble(pe, self.P.p("video_model.class_embedding"), self.P.p("video_model.positional_embedding"),
+                       self.P.p("video_model.temporal_embedding"), keep_dev, tok, B=B, T=T, n=n)
+        sdt = torch.bfloat16 if self.bf16_residual else torch.float32
+        x = self._ib("x", (M, W), sdt)
+        self._ln_inf(tok, "video_model.ln_pre", 1e-5, x)
+        cls = self.cls32
+        vid_rows = self._ib("vid_rows", (B,), torch.int32)
+        vid_rows.copy_(torch.arange(B, device=self.dev, dtype=torch.int32) * S)
+        xc = None
+        if cls:  # the hybrid stream's CLS rows (fp32 [B, W]) beside the bf16 stream, as in video_forward
+            xc = self._ib("xc", (B, W), torch.float32)
+            self._ln_inf(tok, "video_model.ln_pre", 1e-5, xc, rows=vid_rows)
+        L = a["layers"]
+        for l in range(L):
+            pre = f"video_model.transformer.resblocks.{l}."
+            ln = self._ib("ln", (M, W))
+            self._ln_inf(x, pre + "ln_3", 1e-5, ln, cls_x=xc)
+            qkv = self._ib("qkv", (M, 3 * W))
+            self._lin_inf(ln, pre + "timeattn.qkv.weight", pre + "timeattn.qkv.bias", qkv, M)
+            att = self._ib("att", (M, W))
+            self._attn_inf(qkv, att, "time", B, T, n)
+            t_res = self._ib("tres", (M, W))
+            self._lin_inf(att, pre + "timeattn.proj.weight", pre + "timeattn.proj.bias", t_res, M, residual=x)
+            self._ln_inf(t_res, pre + "ln_1", 1e-5, ln)
+            self._lin_inf(ln, pre + "attn.qkv.weight", pre + "attn.qkv.bias", qkv, M)
+            if l < L - 1:
+                self._attn_inf(qkv, att, "space", B, T, n)
+                s = self._ib("s", (M, W), sdt)
+                self._lin_inf(att, pre + "attn.proj.weight", pre + "attn.proj.bias", s, M, residual=x)
+                sc = None
+                if cls:
+                    sc = self._ib("sc", (B, W), torch.float32)
+                    self._cls_lin(att, S, pre + "attn.proj.weight", pre + "attn.proj.bias", xc, sc)
+                self._ln_inf(s, pre + "ln_2", 1e-5, ln, cls_x=sc)
+                hact = self._ib("h", (M, 4 * W))
+                self._lin_inf(ln, pre + "mlp.c_fc.weight", pre + "mlp.c_fc.bias", hact, M, act=a["act"])
+                self._lin_inf(hact, pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", x, M, residual=s)  # (x is dead: in place)
+                if cls:
+                    self._cls_lin(hact, S, pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", sc, xc)
+                continue
+            # the last block for the CLS rows: the time branch and the space qkv above ran on every row (they make the keys and
+            # values of the CLS query); the CLS query attends all S keys (MODE_CLS), everything after it runs on B rows in fp32
+            K.attn_fwd("cls", qkv, att, None, B=B, heads=h, S=S, T=T, n=n, head_dim=self.dh)
+            if cls:
+                x_c = xc
+            else:
+                x_c = self._ib("xg", (B, W), torch.float32)
+                K.rows_move("gather", vid_rows, full_f32=x if sdt == torch.float32 else None,
+                            full_bf16=x if sdt == torch.bfloat16 else None, packed_f32=x_c)
+            att_c = att.view(B, S * W)[:, :W]
+            s_c = self._ib("sc", (B, W), torch.float32)
+            K.rows_linear(att_c, self.P.w(pre + "attn.proj.weight"), s_c, bias=self.P.p(pre + "attn.proj.bias"), residual=x_c)
+            ln_c = self._ib("lnc", (B, W))
+            self._ln_inf(s_c, pre + "ln_2", 1e-5, ln_c)
+            h_c = self._ib("hc", (B, 4 * W))
+            self._lin_inf(ln_c, pre + "mlp.c_fc.weight", pre + "mlp.c_fc.bias", h_c, B, act=a["act"])
+            xo_c = self._ib("xoc", (B, W), torch.float32)
+            K.rows_linear(h_c, self.P.w(pre + "mlp.c_proj.weight"), xo_c, bias=self.P.p(pre + "mlp.c_proj.bias"), residual=s_c)
+        emb = self._ib("vemb", (B, E), torch.float32)
+        if not self.pooled_tail:  # B models: ln_post, then x @ proj of the CLS rows (the embedding is the CLS row of the tokens)
+            lnp = self._ib("lnc", (B, W))
+            self._ln_inf(xo_c, "video_model.ln_post", 1e-5, lnp)
+            K.gemm_nt(lnp, self.P.wt("video_model.proj"), emb, M=B)
+            return emb
+        lnc = self._ib("lnpc", (B, W), torch.float32)  # H/14: pooled = ln_post(CLS) @ proj in fp32
+        self._ln_inf(xo_c, "video_model.ln_post", 1e-5, lnc)
+        K.gemm_small(lnc, self.P.p("video_model.proj"), emb, M=B, N=E, K=W, sa=(W, 1), sb=(E, 1))
+        return emb
+
+    def _block_inf(self, pre, nm, x, M, Wd, heads, Bn, S, causal, act, eps):
+        """_block_fwd without what its backward reads; x [M, Wd] fp32 is updated in place"""
+        ln = self._ib("ln", (M, Wd))
+        self._ln_inf(x, pre + nm["ln1"], eps, ln)
+        qkv = self._ib("qkv", (M, 3 * Wd))
+        self._lin_inf(ln, pre + nm["qkv_w"], pre + nm["qkv_b"], qkv, M)
+        att = self._ib("att", (M, Wd))
+        K.attn_fwd("full", qkv, att, None, B=Bn, heads=heads, S=S, causal=causal, head_dim=Wd // heads)
+        mid = self._ib("s", (M, Wd), torch.float32)
+        self._lin_inf(att, pre + nm["o_w"], pre + nm["o_b"], mid, M, residual=x)
+        self._ln_inf(mid, pre + nm["ln2"], eps, ln)
+        hact = self._ib("h", (M, 4 * Wd))
+        self._lin_inf(ln, pre + nm["fc_w"], pre + nm["fc_b"], hact, M, act=act)
+        self._lin_inf(hact, pre + nm["pj_w"], pre + nm["pj_b"], x, M, residual=mid)
+
+    def _used_rows_inf(self, pre, nm, x_in, M, Wd, heads, rows32, act, eps, attn_fwd):
+        """_used_rows_fwd without what its backward reads -> the block output at the R used rows, [R, Wd] fp32"""
+        R = rows32.numel()
+        ln = self._ib("ln", (M, Wd))
+        self._ln_inf(x_in, pre + nm["ln1"], eps, ln)
+        qkv = self._ib("qkv", (M, 3 * Wd))
+        self._lin_inf(ln, pre + nm["qkv_w"], pre + nm["qkv_b"], qkv, M)
+        att = self._ib("att", (M, Wd))
+        attn_fwd(qkv, att)
+        att_r, x_r = self._ib("att_r", (R, Wd)), self._ib("x_r", (R, Wd), torch.float32)
+        K.rows_move("gather", rows32, full_bf16=att, packed_bf16=att_r)
+        K.rows_move("gather", rows32, full_f32=x_in, packed_f32=x_r)
+        mid = self._ib("s", (R, Wd), torch.float32)
+        self._lin_inf(att_r, pre + nm["o_w"], pre + nm["o_b"], mid, R, residual=x_r)
+        ln2 = self._ib("lnc", (R, Wd))
+        self._ln_inf(mid, pre + nm["ln2"], eps, ln2)
+        hact = self._ib("h", (R, 4 * Wd))
+        self._lin_inf(ln2, pre + nm["fc_w"], pre + nm["fc_b"], hact, R, act=act)
+        xo = self._ib("xoc", (R, Wd), torch.float32)
+        self._lin_inf(hact, pre + nm["pj_w"], pre + nm["pj_b"], xo, R, residual=mid)
+        return xo
+
+    def encode_text(self, ids_dev, eot_rows, N, L, eot_index=None):
+        """-> [N, E] fp32 caption embeddings, the bits of text_forward (an encoder workspace).  eot_index as in text_forward."""
+        self._inf_check()
+        a = self.arch
+        Wt, M, ht = a["text_width"], N * L, a["text_heads"]
+        x = self._ib("x", (M, Wt), torch.float32)
+        K.text_embed(ids_dev, self.P.p("text_token_embedding.weight"), self.P.p("text_positional_embedding"), x, N=N, L=L)
+        lnf = self._ib("lnpc", (N, Wt), torch.float32)
+        last = a["text_layers"] - 1
+        for l in range(a["text_layers"]):
+            pre = f"text_model.resblocks.{l}."
+            if l == last and self.text_used_rows_only:
+                _, pos = eot_index if eot_index is not None else self.eot_index(eot_rows, L)
+                xr = self._used_rows_inf(pre, _TEXT_NAMES, x, M, Wt, ht, eot_rows, a["act"], 1e-5,
+                                         lambda qkv, att: K.attn_fwd_rowq(qkv, pos, att, None, B=N, heads=ht, S=L, head_dim=Wt // ht))
+                self._ln_inf(xr, "text_ln_final", 1e-5, lnf)
+                break
+            self._block_inf(pre, _TEXT_NAMES, x, M, Wt, ht, N, L, True, a["act"], 1e-5)
+        else:
+            self._ln_inf(x, "text_ln_final", 1e-5, lnf, rows=eot_rows)
+        t = self._ib("temb", (N, a["embed"]), torch.float32)
+        K.gemm_small(lnf, self.P.p("text_projection"), t, M=N, N=a["embed"], K=Wt, sa=(Wt, 1), sb=(a["embed"], 1))
+        return t
 
 
 class LossHead:

@@ -716,7 +716,8 @@ def attn_bwd_dkv(mode, qkv, dO, lse2, delta, dqkv, *, B, heads, S, T=0, n=0, cau
 
 def attn_fwd_divided(mode, qkv, out, lse2, cls_ws, *, B, heads, S, T, n, head_dim=64, q8out=None, q8_scale=None, q8_amax=None, **opt):
     """Forward of one divided-attention site (patch rows + CLS row); cls_ws is fp32 scratch.  q8out (uint8, out's shape and row
-    stride) + q8_scale / q8_amax: the kernels also write the per-tensor e4m3 copy of the output."""
+    stride) + q8_scale / q8_amax: the kernels also write the per-tensor e4m3 copy of the output.  lse2 = None (also in attn_fwd,
+    attn_fwd_rowq, attn_fwd_tail): a forward-only call, no log-sum-exp is stored (full-frame SPACE groups: a kernel of its own)."""
     lib = _lib.load()
     M = B * S
     with _hbm("attn_fwd_" + mode, _nb((qkv, M), (out, M), (q8out, M)) + 8 * M * heads):  # (launches its CLS merge kernel as well)

@@ -269,6 +269,52 @@ class TVTSv2Base(nn.Module):
             return out, out[:, 0, :].contiguous()
         return out[:, 1:, :].contiguous(), pooled.clone()  # H/14 (model_dist_TVTSv2_ViT_H_14.py:151-153)
 
+    # forward-only encoders (feature extraction / zero-shot: the reference's feature_extraction_* and zero_* scripts read the CLS
+    # embedding only): no per-layer activations, no backward-only outputs, the last block for the CLS rows (Engine.encode_video)
+    @torch.no_grad()
+    def encode_video(self, video, keep_ind=None):
+        """-> [B, E] video embeddings.  video: fp32 [B, T, 3, H, W] (or [B, 3, H, W]) or uint8 [B, T, H0, W0, 3] frames (centre
+        crop); keep_ind: [1, n] or [B, n] kept patches per frame, None = every patch."""
+        self._fresh_shadows()
+        a, dev = self.arch, self.store.device
+        if video.dtype == torch.uint8:
+            if video.dim() == 4:
+                video = video.unsqueeze(1)
+            if video.dim() != 5 or video.shape[-1] != 3:
+                raise ValueError("uint8 video must be [B, T, H, W, 3]")
+            v = video.to(dev).contiguous()
+        else:
+            if video.dim() == 4:
+                video = video.unsqueeze(1)
+            v = video.to(dev, torch.float32).contiguous()
+        B, T = v.shape[:2]
+        if T > a["num_frames"]:
+            raise ValueError(f"clips of {T} frames, the temporal embedding has {a['num_frames']} rows")
+        ppf = (a["image"] // a["patch"]) ** 2
+        kc = torch.arange(ppf).unsqueeze(0) if keep_ind is None else keep_ind
+        if kc.dim() != 2 or kc.shape[0] not in (1, B):
+            raise ValueError(f"keep_ind {tuple(kc.shape)}: expected [B, n_keep] (or [1, n_keep] for the whole batch)")
+        if kc.numel() and (int(kc.min()) < 0 or int(kc.max()) >= ppf):
+            raise IndexError(f"keep_ind must index the {ppf} patches of a frame")
+        keep = kc.expand(B, -1).to(dev, torch.int32).contiguous()
+        return self.engine.encode_video(v, keep, B, T).clone()
+
+    @torch.no_grad()
+    def encode_text(self, text):
+        """-> [N, E] caption embeddings (the values compute_text returns) from the token ids [N, context] alone."""
+        self._fresh_shadows()
+        a, dev = self.arch, self.store.device
+        ids = text.detach().to("cpu", torch.int64)
+        if ids.dim() != 2 or ids.numel() == 0:
+            raise ValueError(f"text: expected [N, context] token ids, got {tuple(ids.shape)}")
+        if int(ids.min()) < 0 or int(ids.max()) >= a["vocab"] or ids.shape[1] > a["context"]:
+            raise IndexError(f"token ids must lie in [0, {a['vocab']}) and captions within the context of {a['context']}")
+        eot = ids.argmax(-1)
+        L, N = int(eot.max()) + 1, ids.shape[0]
+        rows = (torch.arange(N) * L + eot).to(torch.int32).to(dev)
+        pos = eot.to(torch.int32).to(dev)
+        return self.engine.encode_text(ids[:, :L].to(torch.int32).contiguous().to(dev), rows, N, L, eot_index=(None, pos)).clone()
+
 
 class _SimFn(torch.autograd.Function):
     @staticmethod
