@@ -300,6 +300,17 @@ int tvts_attn80_fwd_rowq(const void* qkv, int ld, int B, int heads, int S, const
                          hipStream_t stream);
 int tvts_attn80_bwd_rowq(const void* qkv, int ld, int B, int heads, int S, const int* qpos, const void* dO, int lddo, const void* O,
                          int ldo, const float* lse2, float* delta, void* dqkv, int lddq, hipStream_t stream);
+/* Causal self-attention inside each sequence of a PACKED batch (seq_start as for tvts_text_embed_packed), head dim 64, forward-only
+ * (no log-sum-exp): qkv bf16 [M, 3 * heads * 64] -> out bf16 [M, heads * 64]; ld, ldo multiples of 8.  Every length 1 .. 80 in any
+ * mixture and order (the CLIP context is 77, CLIP/clip/model.py:330-336); max_len >= the longest sequence selects the tile classes that
+ * are launched (lengths 1-16, 17-32, 33-48, 49-80), max_len > 80 returns -22 and a longer sequence is left unwritten.  A wave owns a
+ * (sequence, head) group: neighbouring sequences of similar length (a length-sorted packing) keep the waves of a block together.
+ * _last: ONE query per sequence at its last row (the EOT token of a packed caption, CLIP/clip/model.py:343-354) over all its keys --
+ * the packed counterpart of tvts_attn_fwd_rowq; it writes the rows seq_start[i + 1] - 1 of out and no other. */
+int tvts_attn_fwd_packed(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, void* out, int ldo,
+                         hipStream_t stream);
+int tvts_attn_fwd_packed_last(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, void* out, int ldo,
+                              hipStream_t stream);
 int tvts_attn80_fwd_len(const void* qkv, int ld, int B, int heads, int S, const int* kv_len, void* out, int ldo, float* lse2,
                         hipStream_t stream);
 int tvts_attn80_bwd_len(const void* qkv, int ld, int B, int heads, int S, const int* kv_len, const void* dO, int lddo,
@@ -387,6 +398,14 @@ int tvts_patch_gather_tube(const float* video, const int* keep, int B, int tubes
                            void* out, int ldo, hipStream_t stream);
 int tvts_text_embed(const int* ids, int ld_ids, int N, int L, const float* emb, const float* pos, int Wt, float* x, int ldx,
                     hipStream_t stream);
+/* ---- PACKED variable-length captions (the forward-only text encoder of the SSv2 multiple-choice models,
+ * v2/downstream/zero_ssv2_mc_TVTSv2_ViT_B_16.py:60-88: C x B ragged captions per batch).  One descriptor for every sequence-aware entry
+ * point: seq_start, device int32[N + 1], ascending, seq_start[0] = 0, seq_start[N] = M; sequence i owns the token rows
+ * seq_start[i] .. seq_start[i + 1] - 1.  A sequence whose descriptor leaves [0, M) is skipped (nothing read or written for it).
+ * x[r] = emb[ids[r]] + pos[r - seq_start[i]] for the packed ids int32[M] (one fp32 add per element); rows whose token id is outside
+ * [0, vocab) or whose position is >= context are left unwritten. */
+int tvts_text_embed_packed(const int* ids, const int* seq_start, int N, int M, const float* emb, const float* pos, int Wt, int vocab,
+                           int context, float* x, int ldx, hipStream_t stream);
 /* order / seg (optional, device int32): the rows 0 .. N * L - 1 sorted by token id (ties in row order) and the starts of the runs
  * of equal ids in that list (N * L + 1 entries, non-decreasing, padded with N * L) -- with them both embedding gradients are
  * ordered sums (run-to-run reproducible), without them (NULL) a scatter of fp32 atomics like nn.Embedding's backward.  The runs
@@ -427,6 +446,10 @@ int tvts_l2norm_rows_bwd(const float* dxn, const float* xn, const float* inv, in
 int tvts_infonce(const float* x, int G, float* lse, float* dx, float* loss, hipStream_t stream);
 int tvts_cross_entropy(const float* logits, const int* labels, int R, int C, float scale, float* dlogits, float* loss,
                        hipStream_t stream);
+/* SSv2 multiple-choice scoring (v2/downstream/zero_ssv2_mc_TVTSv2_ViT_B_16.py:80-88) in one launch: text fp32 [C, B, E] (option-major,
+ * as the _mc models return it), video fp32 [B, E] -> logits[b, c] = 100 <v_b, t_cb> / (|v_b| |t_cb|), fp32 [B, C]; plain norms (no
+ * eps clamp), fixed summation order (two runs give the same bits) */
+int tvts_mc_logits(const float* text, const float* video, int C, int B, int E, float* logits, hipStream_t stream);
 /* validation: rank of the ground truth per query in sims[n_text, n_vid] (text x video);
  * mode 0 = model/metric.py:16-126 t2v_metrics (ranks[n_text], optimistic ties), mode 1 = :129-187 v2t_metrics
  * (ranks[n_vid], averaged ties, closest own caption); valid: optional n_text bytes, 0 = caption missing (query_masks) */

@@ -3,7 +3,10 @@
 `compute_video` under no_grad (Engine.video_forward) and of `encode_video` (Engine.encode_video) at the downstream geometry
 (12 unmasked frames), B/16 at 32 / 128 clips and H/14 at 8 / 32 clips; and the full-frame SPACE attention site alone, the
 streaming kernel + CLS-query pair (what calls with lse2 run) against the forward-only fused kernel.  One JSON line each.
-  --attn-only: the attention lines only (for a `rocprofv3 --kernel-trace --stats` run of its own)."""
+  --attn-only: the attention lines only (for a `rocprofv3 --kernel-trace --stats` run of its own).
+  --mc: the SSv2 multiple-choice workload instead (174 candidate captions for each of 16 clips): encode_text(packed=False) against
+  encode_text(packed=True), the packed attention site against the rectangular one, and the whole _mc forward; B/16 and H/14.
+  The caption lengths are a STAND-IN (uniform in [6, 24] from a fixed seed): the SSv2 label files are not part of this repository."""
 import argparse
 import json
 import os
@@ -46,12 +49,92 @@ def attention(K):
         torch.cuda.empty_cache()
 
 
+def median_alternated(fns, reps, warmup=3):
+    """{name: median seconds per call}, the calls alternated in one process, each timed with its own synchronisation"""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[k].append(time.perf_counter() - t0)
+    return {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+
+
+def multiple_choice(K, reps):
+    import importlib
+    from tvts_amd.model._common import pack_captions
+    C, B, T, lo, hi = 174, 16, 12, 6, 24
+    N = C * B
+    lens = torch.randint(lo, hi + 1, (N,), generator=torch.Generator().manual_seed(0))
+    note = f"caption lengths: stand-in, uniform in [{lo}, {hi}], seed 0 (the SSv2 label files are not available here)"
+    rows_packed, rows_rect = int(lens.sum()), N * int(lens.max())
+    for name, n in (("B_16", 196), ("H_14", 256)):
+        mod = importlib.import_module(f"tvts_amd.downstream.model_TVTSv2_ViT_{name}_mc")
+        m = getattr(mod, f"TVTSv2_{name}")(load_checkpoint=None, pretrained=False)
+        a = m.arch
+        g = torch.Generator().manual_seed(1)
+        ids = torch.zeros(N, a["context"], dtype=torch.int64)
+        ids[:, 0] = a["vocab"] - 2
+        body = torch.randint(1, a["vocab"] - 408, (N, a["context"]), generator=g)
+        col = torch.arange(a["context"]).unsqueeze(0)
+        inside = (col >= 1) & (col < (lens - 1).unsqueeze(1))
+        ids[inside] = body[inside]
+        ids[torch.arange(N), lens - 1] = a["vocab"] - 1
+        with torch.no_grad():
+            med = median_alternated({"rectangular": lambda: m.encode_text(ids), "packed": lambda: m.encode_text(ids, packed=True)}, reps)
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            pack_captions(ids, ids.argmax(-1))
+        host = (time.perf_counter() - t0) / reps
+        print(json.dumps({"what": f"encode_text, {name}, {N} captions", "note": note, "token rows packed": rows_packed,
+                          "token rows rectangular": rows_rect, "row ratio": rows_packed / rows_rect, "reps": reps,
+                          "rectangular ms (median)": 1e3 * med["rectangular"], "packed ms (median, host packing included)": 1e3 * med["packed"],
+                          "host packing ms (mean, inside the packed figure)": 1e3 * host,
+                          "packed / rectangular": med["packed"] / med["rectangular"]}), flush=True)
+        # the attention site alone, on the same captions
+        heads, L = a["text_heads"], int(lens.max())
+        W = heads * 64
+        _, seq_start, _, max_len = pack_captions(ids, ids.argmax(-1))
+        seq_start = seq_start.cuda()
+        gd = torch.Generator(device="cuda").manual_seed(2)
+        qp = torch.randn(rows_packed, 3 * W, generator=gd, device="cuda").bfloat16()
+        qr = torch.randn(rows_rect, 3 * W, generator=gd, device="cuda").bfloat16()
+        op, orr = torch.empty(rows_packed, W, dtype=torch.bfloat16, device="cuda"), torch.empty(rows_rect, W, dtype=torch.bfloat16, device="cuda")
+        med = median_alternated({"rectangular": lambda: K.attn_fwd("full", qr, orr, None, B=N, heads=heads, S=L, causal=True),
+                                 "packed": lambda: K.attn_fwd_packed(qp, seq_start, op, N=N, heads=heads, max_len=max_len)}, reps)
+        print(json.dumps({"what": f"text attention site, {name}, {N} captions, {heads} heads", "note": note,
+                          "rectangular S=%d us (median, launch + sync)" % L: 1e6 * med["rectangular"],
+                          "packed us (median, launch + sync)": 1e6 * med["packed"]}), flush=True)
+        del qp, qr, op, orr
+        # the whole multiple-choice forward
+        v = torch.randn(B, T, 3, 224, 224, generator=g).cuda()
+        data = {"text": ids, "video": v, "keep_ind": torch.arange(n).unsqueeze(0)}
+        m.engine._inf.clear()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        dt = median_alternated({"mc": lambda: m(data)}, max(reps // 4, 5), warmup=2)["mc"]
+        print(json.dumps({"what": f"multiple-choice forward, {name}, B={B} T={T} C={C}", "note": note, "clips/s": B / dt,
+                          "ms": 1e3 * dt, "peak GB": torch.cuda.max_memory_allocated() / 1e9}), flush=True)
+        del m, v, data
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--attn-only", action="store_true")
+    ap.add_argument("--mc", action="store_true")
+    ap.add_argument("--reps", type=int, default=20, help="--mc: timed repetitions of each form (median)")
     ap.add_argument("--iters", type=int, default=5)
     args = ap.parse_args()
     from tvts_amd import hip as K
+    if args.mc:
+        multiple_choice(K, max(args.reps, 20))
+        return
     attention(K)
     if args.attn_only:
         return

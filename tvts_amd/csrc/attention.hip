@@ -2958,3 +2958,8 @@ extern "C" int ABI(fwd_divided_q8)(int mode, const void* qkv, int ld, int B, int
     if (!q8out) return TVTS_EINVAL;
     return fwd_divided_impl(mode, qkv, ld, B, heads, S, T, n, out, ldo, lse2, cls_ws, cls_ws_elems, q8out, ldq8, q8_scale, q8_amax, opts, stream);
 }
+
+#if TVTS_DH == 64
+// packed variable-length causal attention (forward-only text encoder): tvts_attn_fwd_packed, tvts_attn_fwd_packed_last
+#include "attention_packed.h"
+#endif

@@ -406,6 +406,31 @@ extern "C" int tvts_text_embed(const int* ids, int ld_ids, int N, int L, const f
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;
 }
+// the same for PACKED captions: row r of ids [M] belongs to the sequence i with seq_start[i] <= r < seq_start[i + 1] (binary search,
+// block-uniform) and sits at position r - seq_start[i] of it.  A row whose position or token id is out of range is left unwritten.
+__global__ __launch_bounds__(128) void text_embed_packed_kernel(const int* __restrict__ ids, const int* __restrict__ seq_start, int N,
+                                                                const float* __restrict__ emb, const float* __restrict__ pos,
+                                                                int Wt, int vocab, int context, float* __restrict__ x, int ldx) {
+    const int row = blockIdx.x;
+    int lo = 0, hi = N;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (seq_start[mid] <= row) lo = mid; else hi = mid;
+    }
+    const int l = row - seq_start[lo], id = ids[row];
+    if (l < 0 || l >= context || id < 0 || id >= vocab) return;
+    for (int c = threadIdx.x * 4; c < Wt; c += 512)
+        *(f32x4*)(x + (size_t)row * ldx + c) = *(const f32x4*)(emb + (size_t)id * Wt + c) + *(const f32x4*)(pos + (size_t)l * Wt + c);
+}
+extern "C" int tvts_text_embed_packed(const int* ids, const int* seq_start, int N, int M, const float* emb, const float* pos, int Wt,
+                                      int vocab, int context, float* x, int ldx, hipStream_t stream) {
+    if (!ids || !seq_start || !emb || !pos || !x || N <= 0 || M <= 0 || vocab <= 0 || context <= 0 || Wt <= 0 || Wt % 4 || ldx % 4 ||
+        ldx < Wt)
+        return TVTS_EINVAL;
+    hipLaunchKernelGGL(text_embed_packed_kernel, dim3(M), dim3(128), 0, stream, ids, seq_start, N, emb, pos, Wt, vocab, context, x, ldx);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
 __global__ __launch_bounds__(256) void text_embed_bwd_kernel(const float* __restrict__ dx, int ldx, const int* __restrict__ ids,
                                                              int ld_ids, int N, int L, int Wt, float* __restrict__ demb,
                                                              float* __restrict__ dpos) {

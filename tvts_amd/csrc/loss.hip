@@ -207,3 +207,32 @@ extern "C" int tvts_retrieval_ranks(const float* sims, long ld, int n_text, int 
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;
 }
+
+// ---- SSv2 multiple-choice scoring (v2/downstream/zero_ssv2_mc_TVTSv2_ViT_B_16.py:80-88): every clip b against ITS OWN candidate
+// captions.  text [C, B, E] (option-major, as the _mc models return it), video [B, E] -> logits[b, c] = 100 <v_b, t_cb> /
+// (|v_b| |t_cb|), plain norms (no eps clamp, as the script).  A wave per (b, c): lanes stride the E columns, then a fixed xor
+// tree -- the summation order depends on E alone, so two runs give the same bits.
+__global__ __launch_bounds__(256) void mc_logits_kernel(const float* __restrict__ text, const float* __restrict__ video, int C, int B,
+                                                        int E, float* __restrict__ logits) {
+    const int lane = threadIdx.x & 63;
+    const int gid = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gid >= B * C) return;
+    const int b = gid / C, c = gid % C;
+    const float* t = text + ((size_t)c * B + b) * E;
+    const float* v = video + (size_t)b * E;
+    float tv = 0.f, tt = 0.f, vv = 0.f;
+    for (int e = lane; e < E; e += 64) {
+        const float a = t[e], w = v[e];
+        tv = __builtin_fmaf(a, w, tv);
+        tt = __builtin_fmaf(a, a, tt);
+        vv = __builtin_fmaf(w, w, vv);
+    }
+    tv = wave_sum(tv); tt = wave_sum(tt); vv = wave_sum(vv);
+    if (lane == 0) logits[(size_t)b * C + c] = 100.0f * tv / (sqrtf(tt) * sqrtf(vv));
+}
+extern "C" int tvts_mc_logits(const float* text, const float* video, int C, int B, int E, float* logits, hipStream_t stream) {
+    if (!text || !video || !logits || C <= 0 || B <= 0 || E <= 0) return TVTS_EINVAL;
+    hipLaunchKernelGGL(mc_logits_kernel, dim3(ceil_div(B * C, 4)), dim3(256), 0, stream, text, video, C, B, E, logits);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}

@@ -42,3 +42,23 @@ class DownstreamBase(TVTSv2Base):
         if return_embeds:
             return te, ve
         return sim_matrix(te, ve)
+
+
+class MCBase(DownstreamBase):
+    """SSv2 multiple choice (v2/downstream/model_TVTSv2_ViT_B_16_mc.py): every clip comes with its own C candidate captions.
+    forward(data) -> (text_embeddings [C, B, E], video_embeddings [B, E]); data['text'] is [C * B, context] in the script's row
+    order (row c * B + b), B is taken from data['video'].  The captions run through the packed variable-length text encoder, the
+    clips through encode_video; the state dict is the downstream one (the reference imports SortTransformer, never builds it)."""
+
+    @torch.no_grad()
+    def forward(self, data, return_embeds=True):
+        if not return_embeds:  # (the reference would hand the 3-D text embeddings to torch.mm here)
+            raise ValueError("the multiple-choice models return embeddings only: score them with zero_shot.mc_logits")
+        video, text = data["video"], data["text"]
+        bz = video.shape[0]
+        if text.dim() != 2 or text.shape[0] % bz:
+            raise ValueError(f"text {tuple(text.shape)}: expected [C * B, context] candidate captions for the {bz} clips of the batch")
+        keep = data.get("keep_ind")
+        ve = self.encode_video(video, keep)
+        te = self.encode_text(text, packed=True)
+        return te.view(text.shape[0] // bz, bz, -1), ve

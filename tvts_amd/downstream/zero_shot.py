@@ -28,11 +28,20 @@ def class_embedding(model, prompt_ids: torch.Tensor, n_patches: int) -> torch.Te
 
 
 @torch.no_grad()
-def class_embeddings(model, prompt_ids_per_class) -> torch.Tensor:
+def class_embeddings(model, prompt_ids_per_class, packed=False) -> torch.Tensor:
     """[C, E]: class_embedding of every class (a list of [P_c, ctx] prompt-id tensors), text only -- the prompts of all
     classes through model.encode_text, without dummy frames.  Classes whose captions end at the same token position share a
     pass: the caption length L of a pass is the longest caption in it, and a class keeps the L of its own pass in
-    class_embedding, so both evaluate the same arithmetic."""
+    class_embedding, so both evaluate the same arithmetic.
+    packed=True: the prompts of ALL classes go through one packed variable-length pass instead (encode_text(packed=True))."""
+    if packed:
+        emb = model.encode_text(torch.cat([p.to("cpu", torch.int64) for p in prompt_ids_per_class]), packed=True)
+        out, o = [], 0
+        for p in prompt_ids_per_class:
+            mean = _l2norm(emb[o:o + p.shape[0]]).mean(dim=0, keepdim=True)
+            out.append(_l2norm(mean)[0])
+            o += p.shape[0]
+        return torch.stack(out)
     ends = [int(p.argmax(-1).max()) for p in prompt_ids_per_class]
     out = [None] * len(prompt_ids_per_class)
     for end in sorted(set(ends)):
@@ -56,6 +65,19 @@ def class_logits(video_emb: torch.Tensor, zeroshot_weights: torch.Tensor) -> tor
     E, C = w.shape
     out = torch.empty(v.shape[0], C, dtype=torch.float32, device=v.device)
     K.gemm_small(v, w, out, M=v.shape[0], N=C, K=E, sa=(E, 1), sb=(C, 1), alpha=100.0)
+    return out
+
+
+@torch.no_grad()
+def mc_logits(text_features: torch.Tensor, video_features: torch.Tensor) -> torch.Tensor:
+    """The multiple-choice scoring of zero_ssv2_mc_TVTSv2_ViT_B_16.py:80-88: text_features [C, B, E] (option-major, as the _mc
+    models return them), video_features [B, E] -> logits [B, C] = 100 * cos(video b, option c of clip b), one HIP launch."""
+    t = text_features.contiguous().float()
+    v = video_features.contiguous().float()
+    if t.dim() != 3 or v.dim() != 2 or t.shape[1:] != v.shape:
+        raise ValueError(f"mc_logits: text {tuple(t.shape)} must be [C, B, E] for video {tuple(v.shape)} [B, E]")
+    out = torch.empty(v.shape[0], t.shape[0], dtype=torch.float32, device=v.device)
+    K.mc_logits(t, v, out)
     return out
 
 

@@ -1466,14 +1466,14 @@ class Engine:
         K.gemm_small(lnc, self.P.p("video_model.proj"), emb, M=B, N=E, K=W, sa=(W, 1), sb=(E, 1))
         return emb
 
-    def _block_inf(self, pre, nm, x, M, Wd, heads, Bn, S, causal, act, eps):
-        """_block_fwd without what its backward reads; x [M, Wd] fp32 is updated in place"""
+    def _block_inf(self, pre, nm, x, M, Wd, heads, act, eps, attn_fwd):
+        """_block_fwd without what its backward reads; x [M, Wd] fp32 is updated in place.  attn_fwd(qkv, att): the attention call"""
         ln = self._ib("ln", (M, Wd))
         self._ln_inf(x, pre + nm["ln1"], eps, ln)
         qkv = self._ib("qkv", (M, 3 * Wd))
         self._lin_inf(ln, pre + nm["qkv_w"], pre + nm["qkv_b"], qkv, M)
         att = self._ib("att", (M, Wd))
-        K.attn_fwd("full", qkv, att, None, B=Bn, heads=heads, S=S, causal=causal, head_dim=Wd // heads)
+        attn_fwd(qkv, att)
         mid = self._ib("s", (M, Wd), torch.float32)
         self._lin_inf(att, pre + nm["o_w"], pre + nm["o_b"], mid, M, residual=x)
         self._ln_inf(mid, pre + nm["ln2"], eps, ln)
@@ -1520,7 +1520,42 @@ class Engine:
                                          lambda qkv, att: K.attn_fwd_rowq(qkv, pos, att, None, B=N, heads=ht, S=L, head_dim=Wt // ht))
                 self._ln_inf(xr, "text_ln_final", 1e-5, lnf)
                 break
-            self._block_inf(pre, _TEXT_NAMES, x, M, Wt, ht, N, L, True, a["act"], 1e-5)
+            self._block_inf(pre, _TEXT_NAMES, x, M, Wt, ht, a["act"], 1e-5,
+                            lambda qkv, att: K.attn_fwd("full", qkv, att, None, B=N, heads=ht, S=L, causal=True, head_dim=Wt // ht))
+        else:
+            self._ln_inf(x, "text_ln_final", 1e-5, lnf, rows=eot_rows)
+        t = self._ib("temb", (N, a["embed"]), torch.float32)
+        K.gemm_small(lnf, self.P.p("text_projection"), t, M=N, N=a["embed"], K=Wt, sa=(Wt, 1), sb=(a["embed"], 1))
+        return t
+
+    def encode_text_packed(self, ids_packed, seq_start, N, max_len):
+        """encode_text over PACKED captions -> [N, E] fp32 (an encoder workspace).  ids_packed: int32 [M] on the device, every caption
+        cut behind its own EOT token (rows behind it cannot reach the EOT row: causal mask); seq_start: int32 [N + 1], caption i owns
+        rows seq_start[i] .. seq_start[i + 1] - 1 and is read at its last one; max_len >= the longest caption.  M = sum L_i rows go
+        through the LayerNorms and GEMMs instead of N * max L_i; pack captions of similar length next to each other.
+        The ids must be validated by the caller (TVTSv2Base.encode_text does): the embedding kernel leaves a row whose token id is
+        outside the vocabulary, or whose position is past the context, unwritten, and stale workspace contents would run through the tower."""
+        self._inf_check()
+        a = self.arch
+        Wt, M, ht = a["text_width"], ids_packed.numel(), a["text_heads"]
+        if Wt // ht != 64:
+            raise NotImplementedError("the packed attention kernels are built for head dim 64")
+        x = self._ib("x", (M, Wt), torch.float32)
+        K.text_embed_packed(ids_packed, seq_start, self.P.p("text_token_embedding.weight"), self.P.p("text_positional_embedding"), x, N=N)
+        eot_rows = self._ib("eot_rows", (N,), torch.int32)
+        torch.sub(seq_start[1:], 1, out=eot_rows)
+        lnf = self._ib("lnpc", (N, Wt), torch.float32)
+        last = a["text_layers"] - 1
+        for l in range(a["text_layers"]):
+            pre = f"text_model.resblocks.{l}."
+            if l == last and self.text_used_rows_only:
+                xr = self._used_rows_inf(pre, _TEXT_NAMES, x, M, Wt, ht, eot_rows, a["act"], 1e-5,
+                                         lambda qkv, att: K.attn_fwd_packed(qkv, seq_start, att, N=N, heads=ht, max_len=max_len,
+                                                                            last_only=True))
+                self._ln_inf(xr, "text_ln_final", 1e-5, lnf)
+                break
+            self._block_inf(pre, _TEXT_NAMES, x, M, Wt, ht, a["act"], 1e-5,
+                            lambda qkv, att: K.attn_fwd_packed(qkv, seq_start, att, N=N, heads=ht, max_len=max_len))
         else:
             self._ln_inf(x, "text_ln_final", 1e-5, lnf, rows=eot_rows)
         t = self._ib("temb", (N, a["embed"]), torch.float32)

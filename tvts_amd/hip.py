@@ -687,6 +687,18 @@ def attn_fwd_rowq(qkv, qpos, out, lse2, *, B, heads, S, head_dim=64):
          "tvts_attn_fwd_rowq")
 
 
+def attn_fwd_packed(qkv, seq_start, out, *, N, heads, max_len, last_only=False):
+    """causal attention inside each sequence of a packed batch (seq_start int32 [N + 1], rows seq_start[i] .. seq_start[i + 1] - 1),
+    head dim 64, forward-only.  last_only: one query per sequence at its last row; only those N rows of out are written."""
+    lib = _lib.load()
+    assert seq_start.dtype == torch.int32 and seq_start.numel() == N + 1
+    M = qkv.shape[0]
+    assert out.shape[0] == M
+    fn = lib.tvts_attn_fwd_packed_last if last_only else lib.tvts_attn_fwd_packed
+    _chk(fn(_p(qkv), _ld(qkv), _p(seq_start), N, M, heads, max_len, _p(out), _ld(out), _stream()),
+         "tvts_attn_fwd_packed_last" if last_only else "tvts_attn_fwd_packed")
+
+
 def attn_bwd_rowq(qkv, qpos, dO, O, lse2, delta, dqkv, *, B, heads, S, head_dim=64):
     """backward of attn_fwd_rowq into dqkv (zeroed here first: only the query row's dQ and the dK / dV of the keys it sees exist)."""
     lib = _lib.load()
@@ -828,6 +840,16 @@ def text_embed(ids, emb, pos, x, *, N, L):
          "tvts_text_embed")
 
 
+def text_embed_packed(ids, seq_start, emb, pos, x, *, N):
+    """x[r] = emb[ids[r]] + pos[r - seq_start[i]] for packed captions: ids int32 [M], seq_start int32 [N + 1] on the device."""
+    lib = _lib.load()
+    assert ids.dtype == torch.int32 and seq_start.dtype == torch.int32 and seq_start.numel() == N + 1
+    M = ids.numel()
+    assert x.shape[0] == M
+    _chk(lib.tvts_text_embed_packed(_p(ids), _p(seq_start), N, M, _p(emb), _p(pos), emb.shape[1], emb.shape[0], pos.shape[0], _p(x),
+                                    _ld(x), _stream()), "tvts_text_embed_packed")
+
+
 def token_sort(ids_cpu):
     """(order, seg) of tvts_text_embed_bwd for the [N, L] token ids of a batch (host tensors in, int32 host tensors out): the rows
     grouped into runs of equal token id (rows of a run in row order) and the starts of the runs padded to N * L + 1 entries.  The
@@ -930,6 +952,16 @@ def l2norm_rows_bwd(dxn, xn, inv, dx):
     lib = _lib.load()
     _chk(lib.tvts_l2norm_rows_bwd(_p(dxn), _p(xn), _p(inv), xn.shape[0], xn.shape[1], _p(dx), _stream()),
          "tvts_l2norm_rows_bwd")
+
+
+def mc_logits(text, video, logits):
+    """logits[b, c] = 100 * cos(video[b], text[c, b]): text fp32 [C, B, E], video fp32 [B, E], logits fp32 [B, C]"""
+    lib = _lib.load()
+    C, B, E = text.shape
+    assert text.dtype == video.dtype == logits.dtype == torch.float32
+    assert text.is_contiguous() and video.is_contiguous() and logits.is_contiguous()
+    assert tuple(video.shape) == (B, E) and tuple(logits.shape) == (B, C)
+    _chk(lib.tvts_mc_logits(_p(text), _p(video), C, B, E, _p(logits), _stream()), "tvts_mc_logits")
 
 
 def infonce(x, lse, dx, loss):

@@ -300,8 +300,10 @@ class TVTSv2Base(nn.Module):
         return self.engine.encode_video(v, keep, B, T).clone()
 
     @torch.no_grad()
-    def encode_text(self, text):
-        """-> [N, E] caption embeddings (the values compute_text returns) from the token ids [N, context] alone."""
+    def encode_text(self, text, packed=False):
+        """-> [N, E] caption embeddings (the values compute_text returns) from the token ids [N, context] alone.
+        packed=True: every caption is cut behind its own EOT token and the captions run as one packed variable-length pass
+        (Engine.encode_text_packed: sum L_i token rows instead of N * max L_i), sorted by length; rows in the caller's order."""
         self._fresh_shadows()
         a, dev = self.arch, self.store.device
         ids = text.detach().to("cpu", torch.int64)
@@ -310,10 +312,30 @@ class TVTSv2Base(nn.Module):
         if int(ids.min()) < 0 or int(ids.max()) >= a["vocab"] or ids.shape[1] > a["context"]:
             raise IndexError(f"token ids must lie in [0, {a['vocab']}) and captions within the context of {a['context']}")
         eot = ids.argmax(-1)
+        if packed:
+            ids_packed, seq_start, order, max_len = pack_captions(ids, eot)
+            t = self.engine.encode_text_packed(ids_packed.to(dev), seq_start.to(dev), ids.shape[0], max_len)
+            out = torch.empty_like(t)
+            out[order.to(dev)] = t
+            return out
         L, N = int(eot.max()) + 1, ids.shape[0]
         rows = (torch.arange(N) * L + eot).to(torch.int32).to(dev)
         pos = eot.to(torch.int32).to(dev)
         return self.engine.encode_text(ids[:, :L].to(torch.int32).contiguous().to(dev), rows, N, L, eot_index=(None, pos)).clone()
+
+
+def pack_captions(ids, eot):
+    """Host side of the packed text pass: ids int64 [N, context] and the EOT positions [N] (CPU) -> (ids_packed int32 [M],
+    seq_start int32 [N + 1], order int64 [N], max_len) with the captions cut behind their EOT token and laid out by ascending length
+    (stable); packed sequence k is caption order[k]."""
+    lens = (eot + 1).numpy()
+    order = np.argsort(lens, kind="stable")
+    ls = lens[order]
+    seq_start = np.zeros(len(ls) + 1, dtype=np.int32)
+    np.cumsum(ls, out=seq_start[1:])
+    flat = ids.numpy()[order]
+    keep = np.arange(flat.shape[1])[None, :] < ls[:, None]
+    return (torch.from_numpy(flat[keep].astype(np.int32)), torch.from_numpy(seq_start), torch.from_numpy(order), int(ls[-1]))
 
 
 class _SimFn(torch.autograd.Function):
