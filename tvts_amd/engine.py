@@ -347,6 +347,23 @@ class Engine:
     def _f(self, name, shape, zero=False):
         return self._b(name, shape, torch.float32, zero)
 
+    def _ib(self, role, shape, dtype=torch.bfloat16):
+        """encoder workspace `role`: a view of a grow-only byte buffer (roles are reused with other shapes / dtypes)"""
+        shape = tuple(int(s) for s in shape)
+        n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+        back = self._inf.get(role)
+        if back is None or back.numel() < n:
+            self._inf.pop(role, None)  # (the smaller buffer goes first)
+            back = self._inf[role] = torch.empty(max(n, 16), dtype=torch.uint8, device=self.dev)
+        return back[:n].view(dtype).view(shape)
+
+    def _w(self, tag, name, role, shape, dtype=torch.bfloat16):
+        """A buffer of the forward wiring, which both passes run ("The two passes of the forward" below): the training step's named
+        tensor tag + name, which its backward reads -- or, forward-only (tag None), the encoder workspace `role`."""
+        if tag is None:
+            return self._ib(role, shape, dtype)
+        return self._b(tag + name, shape, dtype)
+
     def _ones(self, n):
         """a vector of n ones (the bias gradients as 1^T dy products): a constant made once per length, never written again"""
         t = self.buf.get(("ones", n))
@@ -426,8 +443,10 @@ class Engine:
     def _lin(self, a, wname, bname, out, M, a8=None, q8_for=None, **epi):
         """q8_for: the weight whose GEMMs read `out` as their activation; in the per-tensor e4m3 regime the epilogue of this GEMM
         then writes that operand copy itself (the MLP's GELU output), instead of a quantiser pass over `out`."""
-        if epi.get("preact") is not None and self.gate_deriv:
-            epi["side_deriv"] = True  # the side output holds act'(x): the gate of the backward multiplies by it as is
+        if epi.get("act") is not None and self.gate_deriv:
+            # the side output `preact` holds act'(x), which the gate of the backward multiplies by as is (every call of the training
+            # step that passes act passes preact); forward-only there is no preact: the same epilogue instantiation, side output skipped
+            epi["side_deriv"] = True
         if wname in self.P.w8:  # fp8 weight/activation path (BASELINE config 4): forward GEMMs of the ViT blocks
             w8, ws, _ = self.P.w8[wname]
             if a8 is None:
@@ -547,13 +566,15 @@ class Engine:
     def _ln(self, x, name, eps, y, tag, rows=None, M=None, fp8_for=None, cls_x=None):
         """fp8_for: name of the weight the output feeds; when that GEMM runs in fp8 the LayerNorm also emits the e4m3 copy
         (returned, to be handed to _lin as a8).  cls_x: the fp32 CLS rows of the hybrid stream x (read instead of x's own CLS
-        rows, which receive their bf16 rounding)."""
+        rows, which receive their bf16 rounding).  tag: the names of mean / rstd for the backward, None = forward-only, not kept."""
         M = (rows.numel() if rows is not None else x.shape[0]) if M is None else M
         if cls_x is not None:
             kw_cls = dict(cls_x=cls_x, cls_period=M // cls_x.shape[0])
         else:
             kw_cls = {}
-        mean, rstd = self._f(tag + ".mean", (M,)), self._f(tag + ".rstd", (M,))
+        mean = rstd = None
+        if tag is not None:
+            mean, rstd = self._f(tag + ".mean", (M,)), self._f(tag + ".rstd", (M,))
         a8, kw = None, {}
         if fp8_for is not None and fp8_for in self.P.w8:
             q, sa, kw = self._q8(M, y.shape[1], "x." + fp8_for, persistent=True)
@@ -586,21 +607,21 @@ class Engine:
         return d8
 
     # ------------------------------------------------------------------ generic pre-LN block (text tower, sort head)
-    def _block_fwd(self, pre, nm, x_in, x_out, tag, M, Wd, heads, Bn, S, causal, act, eps):
-        hd = Wd // heads
-        ln1 = self._b(tag + ".ln1", (M, Wd))
-        self._ln(x_in, pre + nm["ln1"], eps, ln1, tag + ".ln1")
-        qkv = self._b(tag + ".qkv", (M, 3 * Wd))
+    def _block_fwd(self, pre, nm, x_in, x_out, tag, M, Wd, heads, act, eps, attn_fwd):
+        """attn_fwd(qkv, att, lse): the attention call.  tag None: forward-only (lse None, no act'(x) side output; x_out may be x_in)."""
+        w = self._w
+        ln1 = w(tag, ".ln1", "ln", (M, Wd))
+        self._ln(x_in, pre + nm["ln1"], eps, ln1, tag and tag + ".ln1")
+        qkv = w(tag, ".qkv", "qkv", (M, 3 * Wd))
         self._lin(ln1, pre + nm["qkv_w"], pre + nm["qkv_b"], qkv, M)
-        att = self._b(tag + ".att", (M, Wd))
-        lse = self._f(tag + ".lse", (M, heads))
-        K.attn_fwd("full", qkv, att, lse, B=Bn, heads=heads, S=S, causal=causal, head_dim=hd)
-        mid = self._f(tag + ".mid", (M, Wd))
+        att = w(tag, ".att", "att", (M, Wd))
+        attn_fwd(qkv, att, self._f(tag + ".lse", (M, heads)) if tag else None)
+        mid = w(tag, ".mid", "s", (M, Wd), torch.float32)
         self._lin(att, pre + nm["o_w"], pre + nm["o_b"], mid, M, residual=x_in)
-        ln2 = self._b(tag + ".ln2", (M, Wd))
-        self._ln(mid, pre + nm["ln2"], eps, ln2, tag + ".ln2")
-        h = self._b(tag + ".h", (M, 4 * Wd))
-        a = self._b(tag + ".a", (M, 4 * Wd))
+        ln2 = w(tag, ".ln2", "ln", (M, Wd))
+        self._ln(mid, pre + nm["ln2"], eps, ln2, tag and tag + ".ln2")
+        h = self._b(tag + ".h", (M, 4 * Wd)) if tag else None
+        a = w(tag, ".a", "h", (M, 4 * Wd))
         self._lin(ln2, pre + nm["fc_w"], pre + nm["fc_b"], a, M, act=act, preact=h)
         self._lin(a, pre + nm["pj_w"], pre + nm["pj_b"], x_out, M, residual=mid)
 
@@ -635,28 +656,44 @@ class Engine:
 
     def text_forward(self, ids_dev, eot_rows, N, L, eot_index=None):
         """eot_index: Engine.eot_index(eot_rows, L) kept by the caller (prepare_batch); made here when absent (eager use only)."""
-        a = self.arch
-        Wt, M = a["text_width"], N * L
-        x = self._f("txt.x0", (M, Wt))
-        K.text_embed(ids_dev, self.P.p("text_token_embedding.weight"), self.P.p("text_positional_embedding"), x, N=N, L=L)
-        lnf = self._f("txt.lnf", (N, Wt))
+        t, self._text_eot = self._text_padded(ids_dev, eot_rows, N, L, eot_index, "txt")  # (the backward takes the positions from here)
+        return t
+
+    def _text_padded(self, ids_dev, eot_rows, N, L, eot_index, tag):
+        """the text tower over N captions padded to L rows each -> (embeddings, the eot_index used)"""
+        ht, hd = self.arch["text_heads"], self.dh_text
+        if eot_index is None and self.text_used_rows_only:
+            eot_index = self.eot_index(eot_rows, L)
+        pos = None if eot_index is None else eot_index[1]
+        t = self._text_tower(
+            lambda x: K.text_embed(ids_dev, self.P.p("text_token_embedding.weight"), self.P.p("text_positional_embedding"), x, N=N, L=L),
+            lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=N, heads=ht, S=L, causal=True, head_dim=hd),
+            lambda qkv, att, lse: K.attn_fwd_rowq(qkv, pos, att, lse, B=N, heads=ht, S=L, head_dim=hd), eot_rows, N, N * L, tag)
+        return t, eot_index
+
+    def _text_tower(self, embed, attn, attn_last, eot_rows, N, M, tag=None):
+        """The CLIP text tower over the M token rows of N captions -> [N, E] fp32 caption embeddings.  embed(x): the embedding
+        kernel; attn / attn_last(qkv, att, lse): the attention call of a block / of the last block, whose only queries are the rows
+        eot_rows; tag: "txt" in the training step, None forward-only (one stream buffer, updated in place)."""
+        a, w = self.arch, self._w
+        Wt, ht = a["text_width"], a["text_heads"]
+        x = w(tag, ".x0", "x", (M, Wt), torch.float32)
+        embed(x)
+        lnf = w(tag, ".lnf", "lnpc", (N, Wt), torch.float32)
         last = a["text_layers"] - 1
         for l in range(a["text_layers"]):
+            pre, tg = f"text_model.resblocks.{l}.", tag and f"{tag}{l}"
             if l == last and self.text_used_rows_only:
                 # the model reads the last block's output at the EOT token of every caption only (CLIP/clip/model.py:343-354)
-                ht, hd = a["text_heads"], Wt // a["text_heads"]
-                rows64, pos = self._text_eot = eot_index if eot_index is not None else self.eot_index(eot_rows, L)
-                xr = self._used_rows_fwd(f"text_model.resblocks.{l}.", _TEXT_NAMES, x, f"txt{l}", M, Wt, ht, eot_rows, a["act"], 1e-5,
-                                         lambda qkv, att, lse: K.attn_fwd_rowq(qkv, pos, att, lse, B=N, heads=ht, S=L, head_dim=hd))
-                self._ln(xr, "text_ln_final", 1e-5, lnf, "txt.lnf")
+                xr = self._used_rows_fwd(pre, _TEXT_NAMES, x, tg, M, Wt, ht, eot_rows, a["act"], 1e-5, attn_last)
+                self._ln(xr, "text_ln_final", 1e-5, lnf, tag and tag + ".lnf")
                 break
-            xo = self._f(f"txt.x{l + 1}", (M, Wt))
-            self._block_fwd(f"text_model.resblocks.{l}.", _TEXT_NAMES, x, xo, f"txt{l}", M, Wt, a["text_heads"], N, L, True,
-                            a["act"], 1e-5)
+            xo = self._f(f"{tag}.x{l + 1}", (M, Wt)) if tag else x
+            self._block_fwd(pre, _TEXT_NAMES, x, xo, tg, M, Wt, ht, a["act"], 1e-5, attn)
             x = xo
         else:
-            self._ln(x, "text_ln_final", 1e-5, lnf, "txt.lnf", rows=eot_rows)
-        t = self._f("txt.t", (N, a["embed"]))
+            self._ln(x, "text_ln_final", 1e-5, lnf, tag and tag + ".lnf", rows=eot_rows)
+        t = w(tag, ".t", "temb", (N, a["embed"]), torch.float32)
         K.gemm_small(lnf, self.P.p("text_projection"), t, M=N, N=a["embed"], K=Wt, sa=(Wt, 1), sb=(a["embed"], 1))
         return t
 
@@ -713,8 +750,9 @@ class Engine:
         return out, (q, sc)
 
     def _st_attention_fwd(self, qkv, att, lse, mode, B, T, n, q8_for=None):
+        """lse None: forward-only (no log-sum-exp is stored; full-frame SPACE calls take their own fused kernel, attention.hip)"""
         h, S = self.arch["heads"], 1 + T * n
-        ws = self._f("vit.clsws", (B * h * max(T, -(-n // 28)) * (self.dh + 2),))
+        ws = self._w(None if lse is None else "vit", ".clsws", "clsws", (B * h * max(T, -(-n // 28)) * (self.dh + 2),), torch.float32)
         kw8 = {}
         if q8_for is not None and q8_for in self.P.w8:
             kw8, nxt = self._attn_q8(B * S, att.shape[1], "x." + q8_for, T, n, persistent=True, consumer=q8_for)
@@ -736,69 +774,90 @@ class Engine:
         cls_acc = self._f(scr + ".clsacc", (B, h, max(T, -(-n // 28)), 3, hd))
         K.attn_bwd(mode, qkv, datt, att, lse, delta, dqkv, B=B, heads=h, S=S, T=T, n=n, cls_acc=cls_acc, head_dim=hd, **kw8)
 
-    def video_forward(self, video, keep_dev, B, T, vid_rows=None):
-        a = self.arch
-        W, E, p = a["width"], a["embed"], a["patch"]
-        n = keep_dev.shape[1]
-        S = 1 + T * n
-        M, Mp, Kp = B * S, B * T * n, self.P.conv_kpad
-        cols = self._b("vit.im2col", (Mp, Kp))
+    def _vit_embed(self, video, keep_dev, B, T, vid_rows, crop, resize, tag):
+        """patch gather (fp32 clips or uint8 frames) -> conv GEMM -> token assembly -> ln_pre: (the residual stream x [B * S, W],
+        the fp32 CLS rows [B, W] of the hybrid stream or None).  Forward-only (tag None) the fp32 temporaries live in the roles of
+        the first block's LayerNorm, MLP and qkv buffers (free until then)."""
+        a, w = self.arch, self._w
+        W, p, n = a["width"], a["patch"], keep_dev.shape[1]
+        M, Mp = B * (1 + T * n), B * T * n
+        cols = w(tag, ".im2col", "ln", (Mp, self.P.conv_kpad))
         if video.dtype == torch.uint8:
-            K.patch_gather_u8(video, keep_dev, cols, B=B, T=T, n=n, img=a["image"], patch=p, crop=self.ctx.get("crop"),
-                              resize=self.ctx.get("resize"))
+            K.patch_gather_u8(video, keep_dev, cols, B=B, T=T, n=n, img=a["image"], patch=p, crop=crop, resize=resize)
         else:
             K.patch_gather(video, keep_dev, cols, B=B, T=T, n=n, img=a["image"], patch=p)
-        pe = self._f("vit.patch", (Mp, W))
+        pe = w(tag, ".patch", "h", (Mp, W), torch.float32)
         K.gemm_nt(cols, self.P.w_conv(), pe, M=Mp)
-        tok = self._f("vit.tok", (M, W))
+        tok = w(tag, ".tok", "qkv", (M, W), torch.float32)
         K.vit_assemble(pe, self.P.p("video_model.class_embedding"), self.P.p("video_model.positional_embedding"),
                        self.P.p("video_model.temporal_embedding"), keep_dev, tok, B=B, T=T, n=n)
-        lowres = self.bf16_residual
-        xbuf = self._b if lowres else self._f   # the residual stream's buffers: bf16 or fp32
-        x = xbuf("vit.x0", (M, W))
-        self._ln(tok, "video_model.ln_pre", 1e-5, x, "vit.lnpre")
-        cls = self.cls32
+        x = w(tag, ".x0", "x", (M, W), torch.bfloat16 if self.bf16_residual else torch.float32)  # the residual stream: bf16 or fp32
+        self._ln(tok, "video_model.ln_pre", 1e-5, x, tag and tag + ".lnpre")
+        xc = None
+        if self.cls32:  # the hybrid stream's CLS rows start as ln_pre's fp32 output on those rows
+            xc = w(tag, ".xc0", "xc", (B, W), torch.float32)
+            self._ln(tok, "video_model.ln_pre", 1e-5, xc, tag and tag + ".lnpre_c", rows=vid_rows)
+        return x, xc
+
+    def _vit_block_head(self, pre, x, xc, tg, B, T, n):
+        """What every row of a space-time block goes through in both passes, up to the space attention's input:
+        ln_3 -> time qkv -> time attention -> t_res -> ln_1 -> space qkv.  -> qkv_s"""
+        a, w = self.arch, self._w
+        W, M = a["width"], x.shape[0]
+        ln3 = w(tg, ".ln3", "ln", (M, W))
+        a8 = self._ln(x, pre + "ln_3", 1e-5, ln3, tg and tg + ".ln3", fp8_for=pre + "timeattn.qkv.weight", cls_x=xc)
+        qkv_t = w(tg, ".qkv_t", "qkv", (M, 3 * W))
+        self._lin(ln3, pre + "timeattn.qkv.weight", pre + "timeattn.qkv.bias", qkv_t, M, a8=a8)
+        att_t, lse_t = w(tg, ".att_t", "att", (M, W)), (self._f(tg + ".lse_t", (M, a["heads"])) if tg else None)
+        self._st_attention_fwd(qkv_t, att_t, lse_t, "time", B, T, n, q8_for=pre + "timeattn.proj.weight")
+        # the time residual only feeds ln_1 (the space branch restarts from x, video_encoder_ViT_B_16.py:121): bf16
+        t_res = w(tg, ".t_res", "tres", (M, W))
+        self._lin(att_t, pre + "timeattn.proj.weight", pre + "timeattn.proj.bias", t_res, M, residual=x)
+        ln1 = w(tg, ".ln1", "ln", (M, W))
+        a8 = self._ln(t_res, pre + "ln_1", 1e-5, ln1, tg and tg + ".ln1", fp8_for=pre + "attn.qkv.weight")
+        qkv_s = w(tg, ".qkv_s", "qkv", (M, 3 * W))
+        self._lin(ln1, pre + "attn.qkv.weight", pre + "attn.qkv.bias", qkv_s, M, a8=a8)
+        return qkv_s
+
+    def _vit_block(self, l, x, xc, tag, B, T, n):
+        """space-time block l on every row: (x, xc) -> the next (x, xc); forward-only (tag None) in place"""
+        a, w = self.arch, self._w
+        pre, tg = f"video_model.transformer.resblocks.{l}.", tag and f"{tag}{l}"
+        W, M, S = a["width"], x.shape[0], 1 + T * n
+        qkv_s = self._vit_block_head(pre, x, xc, tg, B, T, n)
+        att_s, lse_s = w(tg, ".att_s", "att", (M, W)), (self._f(tg + ".lse_s", (M, a["heads"])) if tg else None)
+        self._st_attention_fwd(qkv_s, att_s, lse_s, "space", B, T, n, q8_for=pre + "attn.proj.weight")
+        s_res = w(tg, ".s_res", "s", (M, W), x.dtype)  # residual from the block INPUT x (video_encoder_ViT_B_16.py:121)
+        self._lin(att_s, pre + "attn.proj.weight", pre + "attn.proj.bias", s_res, M, residual=x)
+        s_res_c = None
+        if xc is not None:
+            s_res_c = w(tg, ".s_res_c", "sc", (B, W), torch.float32)
+            self._cls_lin(att_s, S, pre + "attn.proj.weight", pre + "attn.proj.bias", xc, s_res_c)
+        ln2 = w(tg, ".ln2", "ln", (M, W))
+        a8 = self._ln(s_res, pre + "ln_2", 1e-5, ln2, tg and tg + ".ln2", fp8_for=pre + "mlp.c_fc.weight", cls_x=s_res_c)
+        h, act = (self._b(tg + ".h", (M, 4 * W)) if tg else None), w(tg, ".a", "h", (M, 4 * W))
+        self._lin(ln2, pre + "mlp.c_fc.weight", pre + "mlp.c_fc.bias", act, M, act=a["act"], preact=h, a8=a8,
+                  q8_for=pre + "mlp.c_proj.weight")
+        xo = self._b(f"{tag}.x{l + 1}", (M, W), x.dtype) if tag else x  # (forward-only: x is dead)
+        self._lin(act, pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", xo, M, residual=s_res)
+        if xc is not None:
+            xcn = self._f(f"{tag}.xc{l + 1}", (B, W)) if tag else xc
+            self._cls_lin(act, S, pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", s_res_c, xcn)
+            xc = xcn
+        return xo, xc
+
+    def video_forward(self, video, keep_dev, B, T, vid_rows=None):
+        a = self.arch
+        W, E = a["width"], a["embed"]
+        n = keep_dev.shape[1]
+        S = 1 + T * n
+        M = B * S
+        lowres, cls = self.bf16_residual, self.cls32
         if vid_rows is None:
             vid_rows = (torch.arange(B, device=self.dev) * S).to(torch.int32)
-        xc = None
-        if cls:  # the hybrid stream's CLS rows start as ln_pre's fp32 output on those rows
-            xc = self._f("vit.xc0", (B, W))
-            self._ln(tok, "video_model.ln_pre", 1e-5, xc, "vit.lnpre_c", rows=vid_rows)
+        x, xc = self._vit_embed(video, keep_dev, B, T, vid_rows, self.ctx.get("crop"), self.ctx.get("resize"), "vit")
         for l in range(a["layers"]):
-            pre, tg = f"video_model.transformer.resblocks.{l}.", f"vit{l}"
-            ln3 = self._b(tg + ".ln3", (M, W))
-            a8 = self._ln(x, pre + "ln_3", 1e-5, ln3, tg + ".ln3", fp8_for=pre + "timeattn.qkv.weight", cls_x=xc)
-            qkv_t = self._b(tg + ".qkv_t", (M, 3 * W))
-            self._lin(ln3, pre + "timeattn.qkv.weight", pre + "timeattn.qkv.bias", qkv_t, M, a8=a8)
-            att_t, lse_t = self._b(tg + ".att_t", (M, W)), self._f(tg + ".lse_t", (M, a["heads"]))
-            self._st_attention_fwd(qkv_t, att_t, lse_t, "time", B, T, n, q8_for=pre + "timeattn.proj.weight")
-            # the time residual only feeds ln_1 (the space branch restarts from x, video_encoder_ViT_B_16.py:121): bf16
-            t_res = self._b(tg + ".t_res", (M, W))
-            self._lin(att_t, pre + "timeattn.proj.weight", pre + "timeattn.proj.bias", t_res, M, residual=x)
-            ln1 = self._b(tg + ".ln1", (M, W))
-            a8 = self._ln(t_res, pre + "ln_1", 1e-5, ln1, tg + ".ln1", fp8_for=pre + "attn.qkv.weight")
-            qkv_s = self._b(tg + ".qkv_s", (M, 3 * W))
-            self._lin(ln1, pre + "attn.qkv.weight", pre + "attn.qkv.bias", qkv_s, M, a8=a8)
-            att_s, lse_s = self._b(tg + ".att_s", (M, W)), self._f(tg + ".lse_s", (M, a["heads"]))
-            self._st_attention_fwd(qkv_s, att_s, lse_s, "space", B, T, n, q8_for=pre + "attn.proj.weight")
-            s_res = xbuf(tg + ".s_res", (M, W))  # residual from the block INPUT x (video_encoder_ViT_B_16.py:121)
-            self._lin(att_s, pre + "attn.proj.weight", pre + "attn.proj.bias", s_res, M, residual=x)
-            s_res_c = None
-            if cls:
-                s_res_c = self._f(tg + ".s_res_c", (B, W))
-                self._cls_lin(att_s, S, pre + "attn.proj.weight", pre + "attn.proj.bias", xc, s_res_c)
-            ln2 = self._b(tg + ".ln2", (M, W))
-            a8 = self._ln(s_res, pre + "ln_2", 1e-5, ln2, tg + ".ln2", fp8_for=pre + "mlp.c_fc.weight", cls_x=s_res_c)
-            h, act = self._b(tg + ".h", (M, 4 * W)), self._b(tg + ".a", (M, 4 * W))
-            self._lin(ln2, pre + "mlp.c_fc.weight", pre + "mlp.c_fc.bias", act, M, act=a["act"], preact=h, a8=a8,
-                      q8_for=pre + "mlp.c_proj.weight")
-            xo = xbuf(f"vit.x{l + 1}", (M, W))
-            self._lin(act, pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", xo, M, residual=s_res)
-            if cls:
-                xcn = self._f(f"vit.xc{l + 1}", (B, W))
-                self._cls_lin(act, S, pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", s_res_c, xcn)
-                xc = xcn
-            x = xo
+            x, xc = self._vit_block(l, x, xc, "vit", B, T, n)
         out = self._f("vit.out", (M, E))
         if not self.pooled_tail:  # B models: ln_post on every token, all S projected rows feed the sort head
             lnp = self._b("vit.lnpost", (M, W))
@@ -981,6 +1040,7 @@ class Engine:
         rows = self.ctx["sort_rows"]
         nf = self._f("srt.nf", (B * NT, E))
         last = a["sort_depth"] - 1
+        attn = lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hs, S=So, causal=False, head_dim=E // hs)  # noqa: E731
         for l in range(a["sort_depth"]):
             if l == last and self.sort_used_rows_only and NT <= 16:
                 # the head reads the last block's output at the NT transcript rows only (sort_transformer.py:131-141)
@@ -988,7 +1048,7 @@ class Engine:
                 self._ln(xr, "pred_model.norm", 1e-6, nf, "srt.norm")
                 break
             xo = self._f(f"srt.x{l + 1}", (Mo, E))
-            self._block_fwd(f"pred_model.blocks.{l}.", _SORT_NAMES, x, xo, f"srt{l}", Mo, E, hs, B, So, False, "gelu", 1e-6)
+            self._block_fwd(f"pred_model.blocks.{l}.", _SORT_NAMES, x, xo, f"srt{l}", Mo, E, hs, "gelu", 1e-6, attn)
             x = xo
         else:
             self._ln(x, "pred_model.norm", 1e-6, nf, "srt.norm", rows=rows)
@@ -1021,25 +1081,25 @@ class Engine:
     # gradient enters.  LayerNorm 1 and the qkv projection stay dense (keys / values of every token); the attention output
     # (attn_fwd: a query-restricted kernel writing the used rows of `att`), the output projection, the residual, LayerNorm 2 and the
     # MLP are computed for the R used rows; backward: dQ for those rows, dK / dV -- and through them the gradient of every input
-    # row -- dense.  Returns the block output at the used rows, [R, Wd] fp32.
+    # row -- dense.  Returns the block output at the used rows, [R, Wd] fp32.  tag None: forward-only, as in _block_fwd.
     def _used_rows_fwd(self, pre, nm, x_in, tag, M, Wd, heads, rows32, act, eps, attn_fwd):
-        R = rows32.numel()
-        ln1 = self._b(tag + ".ln1", (M, Wd))
-        self._ln(x_in, pre + nm["ln1"], eps, ln1, tag + ".ln1")
-        qkv = self._b(tag + ".qkv", (M, 3 * Wd))
+        R, w, f32 = rows32.numel(), self._w, torch.float32
+        ln1 = w(tag, ".ln1", "ln", (M, Wd))
+        self._ln(x_in, pre + nm["ln1"], eps, ln1, tag and tag + ".ln1")
+        qkv = w(tag, ".qkv", "qkv", (M, 3 * Wd))
         self._lin(ln1, pre + nm["qkv_w"], pre + nm["qkv_b"], qkv, M)
-        att, lse = self._b(tag + ".att", (M, Wd)), self._f(tag + ".lse", (M, heads))
-        attn_fwd(qkv, att, lse)
-        att_r, x_r = self._b(tag + ".att_r", (R, Wd)), self._f(tag + ".x_r", (R, Wd))
+        att = w(tag, ".att", "att", (M, Wd))
+        attn_fwd(qkv, att, self._f(tag + ".lse", (M, heads)) if tag else None)
+        att_r, x_r = w(tag, ".att_r", "att_r", (R, Wd)), w(tag, ".x_r", "x_r", (R, Wd), f32)
         K.rows_move("gather", rows32, full_bf16=att, packed_bf16=att_r)   # (row gathers of R x Wd elements)
         K.rows_move("gather", rows32, full_f32=x_in, packed_f32=x_r)
-        mid = self._f(tag + ".mid", (R, Wd))
+        mid = w(tag, ".mid", "s", (R, Wd), f32)
         self._lin(att_r, pre + nm["o_w"], pre + nm["o_b"], mid, R, residual=x_r)
-        ln2 = self._b(tag + ".ln2", (R, Wd))
-        self._ln(mid, pre + nm["ln2"], eps, ln2, tag + ".ln2")
-        h, hact = self._b(tag + ".h", (R, 4 * Wd)), self._b(tag + ".a", (R, 4 * Wd))
+        ln2 = w(tag, ".ln2", "lnc", (R, Wd))
+        self._ln(mid, pre + nm["ln2"], eps, ln2, tag and tag + ".ln2")
+        h, hact = (self._b(tag + ".h", (R, 4 * Wd)) if tag else None), w(tag, ".a", "h", (R, 4 * Wd))
         self._lin(ln2, pre + nm["fc_w"], pre + nm["fc_b"], hact, R, act=act, preact=h)
-        xo = self._f(tag + ".xo_r", (R, Wd))
+        xo = w(tag, ".xo_r", "xoc", (R, Wd), f32)
         self._lin(hact, pre + nm["pj_w"], pre + nm["pj_b"], xo, R, residual=mid)
         return xo
 
@@ -1342,21 +1402,18 @@ class Engine:
             self._ready("text_")
 
     # ------------------------------------------------------------------ forward-only encoders (feature extraction, zero-shot)
-    # The same numerics as video_forward / text_forward without what only a backward reads: no per-layer activations (the
-    # workspaces below are keyed by ROLE, in a namespace of their own, and reused by every layer: peak ~ one layer), no
-    # act'(x) side output of c_fc, no LayerNorm mean / rstd, no attention log-sum-exp (lse2 = None; forward-only SPACE calls at
-    # full frames take their own fused kernel, attention.hip).  The last ViT block is evaluated for the CLS rows only.  Nothing
-    # of the training path's workspace is read, written or resized.
-    def _ib(self, role, shape, dtype=torch.bfloat16):
-        """encoder workspace `role`: a view of a grow-only byte buffer (roles are reused with other shapes / dtypes)"""
-        shape = tuple(int(s) for s in shape)
-        n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        back = self._inf.get(role)
-        if back is None or back.numel() < n:
-            self._inf.pop(role, None)  # (the smaller buffer goes first)
-            back = self._inf[role] = torch.empty(max(n, 16), dtype=torch.uint8, device=self.dev)
-        return back[:n].view(dtype).view(shape)
-
+    # The two passes of the forward.  There is ONE forward wiring (_ln, _lin, _st_attention_fwd, _block_fwd, _used_rows_fwd,
+    # _text_tower, _vit_embed, _vit_block_head, _vit_block); the training step and the encoders below both run it, and the `tag`
+    # argument is all that tells them apart:
+    #   tag = a name   every buffer is the named tensor tag + name of self.buf (_b), one per layer, kept for the backward; the
+    #                  tensors only a backward reads are produced: LayerNorm mean / rstd, the attention log-sum-exp, the act'(x)
+    #                  side output of c_fc;
+    #   tag = None     every buffer is an encoder workspace (_ib) keyed by ROLE, in a namespace of its own (self._inf), reused by
+    #                  every layer (peak ~ one layer) with the residual stream updated in place; the backward-only tensors are
+    #                  neither allocated nor written (lse2 = None: SPACE calls at full frames take their own fused kernel).
+    # Same entry points, weights, epilogue options and epsilons either way.  What the encoders add of their own: the last ViT
+    # block runs its second half for the CLS rows only, and the e4m3 architectures are refused (the e4m3 branches of _ln / _lin
+    # never see tag None).  Nothing of the training step's workspace is read, written or resized by an encoder call.
     def _inf_check(self):
         a = self.arch
         if a.get("family") == "v1":
@@ -1364,169 +1421,56 @@ class Engine:
         if a.get("fp8") or a.get("fp8_dgrad") or a.get("fp8_wgrad"):
             raise NotImplementedError("the forward-only encoders have no e4m3 form; use a bf16 architecture")
 
-    def _ln_inf(self, x, name, eps, y, rows=None, cls_x=None):
-        M = rows.numel() if rows is not None else x.shape[0]
-        kw = dict(cls_x=cls_x, cls_period=M // cls_x.shape[0]) if cls_x is not None else {}
-        K.layernorm_fwd(x, self.P.p(name + ".weight"), self.P.p(name + ".bias"), eps, y, rows=rows, M=M, **kw)
-
-    def _lin_inf(self, a, wname, bname, out, M, act=None, residual=None):
-        # (side_deriv as in _lin: the same epilogue instantiation, whose side output is skipped without preact)
-        K.gemm_nt(a, self.P.w(wname), out, M=M, bias=self.P.p(bname) if bname else None, residual=residual, act=act,
-                  side_deriv=act is not None and self.gate_deriv)
-
-    def _attn_inf(self, qkv, att, mode, B, T, n):
-        h = self.arch["heads"]
-        ws = self._ib("clsws", (B * h * max(T, -(-n // 28)) * (self.dh + 2),), torch.float32)
-        K.attn_fwd_divided(mode, qkv, att, None, ws, B=B, heads=h, S=1 + T * n, T=T, n=n, head_dim=self.dh)
-
     def encode_video(self, video, keep_dev, B, T, crop=None, resize=None):
         """-> [B, E] fp32 video embeddings (an encoder workspace: the next encoder call overwrites it).  video: fp32 [B, T, 3, H, W]
         or uint8 [B, T, H0, W0, 3] on the device; keep_dev: int32 [B, n] kept patches per frame."""
         self._inf_check()
-        a = self.arch
-        W, E, p, h = a["width"], a["embed"], a["patch"], a["heads"]
+        a, f32 = self.arch, torch.float32
+        W, E, h = a["width"], a["embed"], a["heads"]
         n = keep_dev.shape[1]
         S = 1 + T * n
-        M, Mp, Kp = B * S, B * T * n, self.P.conv_kpad
-        # the embedding's fp32 temporaries live in the roles of the first block's qkv and MLP buffers (free until then)
-        cols = self._ib("ln", (Mp, Kp))
-        if video.dtype == torch.uint8:
-            K.patch_gather_u8(video, keep_dev, cols, B=B, T=T, n=n, img=a["image"], patch=p, crop=crop, resize=resize)
-        else:
-            K.patch_gather(video, keep_dev, cols, B=B, T=T, n=n, img=a["image"], patch=p)
-        pe = self._ib("h", (Mp, W), torch.float32)
-        K.gemm_nt(cols, self.P.w_conv(), pe, M=Mp)
-        tok = self._ib("qkv", (M, W), torch.float32)
-        K.vit_assemble(pe, self.P.p("video_model.class_embedding"), self.P.p("video_model.positional_embedding"),
-                       self.P.p("video_model.temporal_embedding"), keep_dev, tok, B=B, T=T, n=n)
-        sdt = torch.bfloat16 if self.bf16_residual else torch.float32
-        x = self._ib("x", (M, W), sdt)
-        self._ln_inf(tok, "video_model.ln_pre", 1e-5, x)
-        cls = self.cls32
+        M = B * S
         vid_rows = self._ib("vid_rows", (B,), torch.int32)
         vid_rows.copy_(torch.arange(B, device=self.dev, dtype=torch.int32) * S)
-        xc = None
-        if cls:  # the hybrid stream's CLS rows (fp32 [B, W]) beside the bf16 stream, as in video_forward
-            xc = self._ib("xc", (B, W), torch.float32)
-            self._ln_inf(tok, "video_model.ln_pre", 1e-5, xc, rows=vid_rows)
-        L = a["layers"]
-        for l in range(L):
-            pre = f"video_model.transformer.resblocks.{l}."
-            ln = self._ib("ln", (M, W))
-            self._ln_inf(x, pre + "ln_3", 1e-5, ln, cls_x=xc)
-            qkv = self._ib("qkv", (M, 3 * W))
-            self._lin_inf(ln, pre + "timeattn.qkv.weight", pre + "timeattn.qkv.bias", qkv, M)
-            att = self._ib("att", (M, W))
-            self._attn_inf(qkv, att, "time", B, T, n)
-            t_res = self._ib("tres", (M, W))
-            self._lin_inf(att, pre + "timeattn.proj.weight", pre + "timeattn.proj.bias", t_res, M, residual=x)
-            self._ln_inf(t_res, pre + "ln_1", 1e-5, ln)
-            self._lin_inf(ln, pre + "attn.qkv.weight", pre + "attn.qkv.bias", qkv, M)
-            if l < L - 1:
-                self._attn_inf(qkv, att, "space", B, T, n)
-                s = self._ib("s", (M, W), sdt)
-                self._lin_inf(att, pre + "attn.proj.weight", pre + "attn.proj.bias", s, M, residual=x)
-                sc = None
-                if cls:
-                    sc = self._ib("sc", (B, W), torch.float32)
-                    self._cls_lin(att, S, pre + "attn.proj.weight", pre + "attn.proj.bias", xc, sc)
-                self._ln_inf(s, pre + "ln_2", 1e-5, ln, cls_x=sc)
-                hact = self._ib("h", (M, 4 * W))
-                self._lin_inf(ln, pre + "mlp.c_fc.weight", pre + "mlp.c_fc.bias", hact, M, act=a["act"])
-                self._lin_inf(hact, pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", x, M, residual=s)  # (x is dead: in place)
-                if cls:
-                    self._cls_lin(hact, S, pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", sc, xc)
-                continue
-            # the last block for the CLS rows: the time branch and the space qkv above ran on every row (they make the keys and
-            # values of the CLS query); the CLS query attends all S keys (MODE_CLS), everything after it runs on B rows in fp32
-            K.attn_fwd("cls", qkv, att, None, B=B, heads=h, S=S, T=T, n=n, head_dim=self.dh)
-            if cls:
-                x_c = xc
-            else:
-                x_c = self._ib("xg", (B, W), torch.float32)
-                K.rows_move("gather", vid_rows, full_f32=x if sdt == torch.float32 else None,
-                            full_bf16=x if sdt == torch.bfloat16 else None, packed_f32=x_c)
-            att_c = att.view(B, S * W)[:, :W]
-            s_c = self._ib("sc", (B, W), torch.float32)
-            K.rows_linear(att_c, self.P.w(pre + "attn.proj.weight"), s_c, bias=self.P.p(pre + "attn.proj.bias"), residual=x_c)
-            ln_c = self._ib("lnc", (B, W))
-            self._ln_inf(s_c, pre + "ln_2", 1e-5, ln_c)
-            h_c = self._ib("hc", (B, 4 * W))
-            self._lin_inf(ln_c, pre + "mlp.c_fc.weight", pre + "mlp.c_fc.bias", h_c, B, act=a["act"])
-            xo_c = self._ib("xoc", (B, W), torch.float32)
-            K.rows_linear(h_c, self.P.w(pre + "mlp.c_proj.weight"), xo_c, bias=self.P.p(pre + "mlp.c_proj.bias"), residual=s_c)
-        emb = self._ib("vemb", (B, E), torch.float32)
+        x, xc = self._vit_embed(video, keep_dev, B, T, vid_rows, crop, resize, None)
+        for l in range(a["layers"] - 1):
+            x, xc = self._vit_block(l, x, xc, None, B, T, n)
+        # the last block for the CLS rows: the time branch and the space qkv run on every row (they make the keys and values of
+        # the CLS query); the CLS query attends all S keys (MODE_CLS), everything after it runs on B rows in fp32
+        pre = f"video_model.transformer.resblocks.{a['layers'] - 1}."
+        qkv = self._vit_block_head(pre, x, xc, None, B, T, n)
+        att = self._ib("att", (M, W))
+        K.attn_fwd("cls", qkv, att, None, B=B, heads=h, S=S, T=T, n=n, head_dim=self.dh)
+        if xc is not None:
+            x_c = xc
+        else:
+            x_c = self._ib("xg", (B, W), f32)
+            K.rows_move("gather", vid_rows, full_f32=x if x.dtype == f32 else None,
+                        full_bf16=x if x.dtype == torch.bfloat16 else None, packed_f32=x_c)
+        att_c = att.view(B, S * W)[:, :W]
+        s_c = self._ib("sc", (B, W), f32)
+        K.rows_linear(att_c, self.P.w(pre + "attn.proj.weight"), s_c, bias=self.P.p(pre + "attn.proj.bias"), residual=x_c)
+        ln_c = self._ib("lnc", (B, W))
+        self._ln(s_c, pre + "ln_2", 1e-5, ln_c, None)
+        h_c = self._ib("hc", (B, 4 * W))
+        self._lin(ln_c, pre + "mlp.c_fc.weight", pre + "mlp.c_fc.bias", h_c, B, act=a["act"])
+        xo_c = self._ib("xoc", (B, W), f32)
+        K.rows_linear(h_c, self.P.w(pre + "mlp.c_proj.weight"), xo_c, bias=self.P.p(pre + "mlp.c_proj.bias"), residual=s_c)
+        emb = self._ib("vemb", (B, E), f32)
         if not self.pooled_tail:  # B models: ln_post, then x @ proj of the CLS rows (the embedding is the CLS row of the tokens)
             lnp = self._ib("lnc", (B, W))
-            self._ln_inf(xo_c, "video_model.ln_post", 1e-5, lnp)
+            self._ln(xo_c, "video_model.ln_post", 1e-5, lnp, None)
             K.gemm_nt(lnp, self.P.wt("video_model.proj"), emb, M=B)
             return emb
-        lnc = self._ib("lnpc", (B, W), torch.float32)  # H/14: pooled = ln_post(CLS) @ proj in fp32
-        self._ln_inf(xo_c, "video_model.ln_post", 1e-5, lnc)
+        lnc = self._ib("lnpc", (B, W), f32)  # H/14: pooled = ln_post(CLS) @ proj in fp32
+        self._ln(xo_c, "video_model.ln_post", 1e-5, lnc, None)
         K.gemm_small(lnc, self.P.p("video_model.proj"), emb, M=B, N=E, K=W, sa=(W, 1), sb=(E, 1))
         return emb
-
-    def _block_inf(self, pre, nm, x, M, Wd, heads, act, eps, attn_fwd):
-        """_block_fwd without what its backward reads; x [M, Wd] fp32 is updated in place.  attn_fwd(qkv, att): the attention call"""
-        ln = self._ib("ln", (M, Wd))
-        self._ln_inf(x, pre + nm["ln1"], eps, ln)
-        qkv = self._ib("qkv", (M, 3 * Wd))
-        self._lin_inf(ln, pre + nm["qkv_w"], pre + nm["qkv_b"], qkv, M)
-        att = self._ib("att", (M, Wd))
-        attn_fwd(qkv, att)
-        mid = self._ib("s", (M, Wd), torch.float32)
-        self._lin_inf(att, pre + nm["o_w"], pre + nm["o_b"], mid, M, residual=x)
-        self._ln_inf(mid, pre + nm["ln2"], eps, ln)
-        hact = self._ib("h", (M, 4 * Wd))
-        self._lin_inf(ln, pre + nm["fc_w"], pre + nm["fc_b"], hact, M, act=act)
-        self._lin_inf(hact, pre + nm["pj_w"], pre + nm["pj_b"], x, M, residual=mid)
-
-    def _used_rows_inf(self, pre, nm, x_in, M, Wd, heads, rows32, act, eps, attn_fwd):
-        """_used_rows_fwd without what its backward reads -> the block output at the R used rows, [R, Wd] fp32"""
-        R = rows32.numel()
-        ln = self._ib("ln", (M, Wd))
-        self._ln_inf(x_in, pre + nm["ln1"], eps, ln)
-        qkv = self._ib("qkv", (M, 3 * Wd))
-        self._lin_inf(ln, pre + nm["qkv_w"], pre + nm["qkv_b"], qkv, M)
-        att = self._ib("att", (M, Wd))
-        attn_fwd(qkv, att)
-        att_r, x_r = self._ib("att_r", (R, Wd)), self._ib("x_r", (R, Wd), torch.float32)
-        K.rows_move("gather", rows32, full_bf16=att, packed_bf16=att_r)
-        K.rows_move("gather", rows32, full_f32=x_in, packed_f32=x_r)
-        mid = self._ib("s", (R, Wd), torch.float32)
-        self._lin_inf(att_r, pre + nm["o_w"], pre + nm["o_b"], mid, R, residual=x_r)
-        ln2 = self._ib("lnc", (R, Wd))
-        self._ln_inf(mid, pre + nm["ln2"], eps, ln2)
-        hact = self._ib("h", (R, 4 * Wd))
-        self._lin_inf(ln2, pre + nm["fc_w"], pre + nm["fc_b"], hact, R, act=act)
-        xo = self._ib("xoc", (R, Wd), torch.float32)
-        self._lin_inf(hact, pre + nm["pj_w"], pre + nm["pj_b"], xo, R, residual=mid)
-        return xo
 
     def encode_text(self, ids_dev, eot_rows, N, L, eot_index=None):
         """-> [N, E] fp32 caption embeddings, the bits of text_forward (an encoder workspace).  eot_index as in text_forward."""
         self._inf_check()
-        a = self.arch
-        Wt, M, ht = a["text_width"], N * L, a["text_heads"]
-        x = self._ib("x", (M, Wt), torch.float32)
-        K.text_embed(ids_dev, self.P.p("text_token_embedding.weight"), self.P.p("text_positional_embedding"), x, N=N, L=L)
-        lnf = self._ib("lnpc", (N, Wt), torch.float32)
-        last = a["text_layers"] - 1
-        for l in range(a["text_layers"]):
-            pre = f"text_model.resblocks.{l}."
-            if l == last and self.text_used_rows_only:
-                _, pos = eot_index if eot_index is not None else self.eot_index(eot_rows, L)
-                xr = self._used_rows_inf(pre, _TEXT_NAMES, x, M, Wt, ht, eot_rows, a["act"], 1e-5,
-                                         lambda qkv, att: K.attn_fwd_rowq(qkv, pos, att, None, B=N, heads=ht, S=L, head_dim=Wt // ht))
-                self._ln_inf(xr, "text_ln_final", 1e-5, lnf)
-                break
-            self._block_inf(pre, _TEXT_NAMES, x, M, Wt, ht, a["act"], 1e-5,
-                            lambda qkv, att: K.attn_fwd("full", qkv, att, None, B=N, heads=ht, S=L, causal=True, head_dim=Wt // ht))
-        else:
-            self._ln_inf(x, "text_ln_final", 1e-5, lnf, rows=eot_rows)
-        t = self._ib("temb", (N, a["embed"]), torch.float32)
-        K.gemm_small(lnf, self.P.p("text_projection"), t, M=N, N=a["embed"], K=Wt, sa=(Wt, 1), sb=(a["embed"], 1))
-        return t
+        return self._text_padded(ids_dev, eot_rows, N, L, eot_index, None)[0]
 
     def encode_text_packed(self, ids_packed, seq_start, N, max_len):
         """encode_text over PACKED captions -> [N, E] fp32 (an encoder workspace).  ids_packed: int32 [M] on the device, every caption
@@ -1536,31 +1480,17 @@ class Engine:
         The ids must be validated by the caller (TVTSv2Base.encode_text does): the embedding kernel leaves a row whose token id is
         outside the vocabulary, or whose position is past the context, unwritten, and stale workspace contents would run through the tower."""
         self._inf_check()
-        a = self.arch
-        Wt, M, ht = a["text_width"], ids_packed.numel(), a["text_heads"]
-        if Wt // ht != 64:
+        ht = self.arch["text_heads"]
+        if self.dh_text != 64:
             raise NotImplementedError("the packed attention kernels are built for head dim 64")
-        x = self._ib("x", (M, Wt), torch.float32)
-        K.text_embed_packed(ids_packed, seq_start, self.P.p("text_token_embedding.weight"), self.P.p("text_positional_embedding"), x, N=N)
         eot_rows = self._ib("eot_rows", (N,), torch.int32)
         torch.sub(seq_start[1:], 1, out=eot_rows)
-        lnf = self._ib("lnpc", (N, Wt), torch.float32)
-        last = a["text_layers"] - 1
-        for l in range(a["text_layers"]):
-            pre = f"text_model.resblocks.{l}."
-            if l == last and self.text_used_rows_only:
-                xr = self._used_rows_inf(pre, _TEXT_NAMES, x, M, Wt, ht, eot_rows, a["act"], 1e-5,
-                                         lambda qkv, att: K.attn_fwd_packed(qkv, seq_start, att, N=N, heads=ht, max_len=max_len,
-                                                                            last_only=True))
-                self._ln_inf(xr, "text_ln_final", 1e-5, lnf)
-                break
-            self._block_inf(pre, _TEXT_NAMES, x, M, Wt, ht, a["act"], 1e-5,
-                            lambda qkv, att: K.attn_fwd_packed(qkv, seq_start, att, N=N, heads=ht, max_len=max_len))
-        else:
-            self._ln_inf(x, "text_ln_final", 1e-5, lnf, rows=eot_rows)
-        t = self._ib("temb", (N, a["embed"]), torch.float32)
-        K.gemm_small(lnf, self.P.p("text_projection"), t, M=N, N=a["embed"], K=Wt, sa=(Wt, 1), sb=(a["embed"], 1))
-        return t
+        return self._text_tower(
+            lambda x: K.text_embed_packed(ids_packed, seq_start, self.P.p("text_token_embedding.weight"),
+                                          self.P.p("text_positional_embedding"), x, N=N),
+            lambda qkv, att, lse: K.attn_fwd_packed(qkv, seq_start, att, N=N, heads=ht, max_len=max_len),
+            lambda qkv, att, lse: K.attn_fwd_packed(qkv, seq_start, att, N=N, heads=ht, max_len=max_len, last_only=True),
+            eot_rows, N, ids_packed.numel())
 
 
 class LossHead:

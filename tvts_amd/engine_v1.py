@@ -208,10 +208,11 @@ class EngineV1(Engine):
         tok = self._f("vit.x0", (M, W))
         K.vit_assemble(pe, P.p("video_model.cls_token").view(W), P.p("video_model.pos_embed").view(-1, W),
                        P.p("video_model.temporal_embed").view(-1, W), keep, tok, B=B, T=tubes, n=n)
-        x = tok
+        x, hv = tok, a["heads"]
+        attn = lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hv, S=S, causal=False, head_dim=W // hv)  # noqa: E731
         for l in range(a["layers"]):
             xo = self._f(f"vit.x{l + 1}", (M, W))
-            self._block_fwd(f"video_model.blocks.{l}.", _VIT_NAMES, x, xo, f"vit{l}", M, W, a["heads"], B, S, False, "gelu", 1e-6)
+            self._block_fwd(f"video_model.blocks.{l}.", _VIT_NAMES, x, xo, f"vit{l}", M, W, hv, "gelu", 1e-6, attn)
             x = xo
         out = self._f("vit.out", (M, W))
         self._ln(x, "video_model.norm", 1e-6, out, "vit.norm")
