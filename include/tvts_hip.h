@@ -168,6 +168,13 @@ int tvts_gemm_small_f32(const float* A, long sai, long sak, const float* B, long
  * residual-adding projections (`x + attn(...)`, `x + mlp(...)`, video_encoder_ViT_B_16.py:121-124): one row per clip, lda = S * K. */
 int tvts_rows_linear_bf16(const void* A, long lda, const void* W, int ldw, int R, int N, int K, const float* bias, const float* residual,
                           int ldr, float* out, int ldo, hipStream_t stream);
+/* the same rows on e4m3 operands: out[r, n] = residual[r, n] + bias[n] + row_scale[r] * w_scale[0] * sum_k A8[r * lda + k] W8[n * ldw + k]
+ * (A8, W8 OCP e4m3 bytes; row_scale[R] as tvts_quant_fp8_rows writes it, w_scale the weight's device scalar; fp32 accumulation in a
+ * fixed order; K % 64 == 0, lda / ldw % 16 == 0 (bytes), both base addresses 16-byte aligned, any N; bias / residual optional).  The
+ * CLS rows of the forward-only encoder's last block on an e4m3 architecture: the products of attn.proj / mlp.c_proj that the training
+ * forward forms on the e4m3 copies for every row (nn.Linear sites of video_encoder_ViT_H_14.py), one row per clip, lda = S * K. */
+int tvts_rows_linear_fp8(const void* A8, long lda, const float* row_scale, const void* W8, int ldw, const float* w_scale, int R, int N,
+                         int K, const float* bias, const float* residual, int ldr, float* out, int ldo, hipStream_t stream);
 /* bias gradient: out[n] += sum_m X[m,n].  workspace (optional): partial sums of row ranges, added in range order (deterministic, and
  * a grid over the rows as well as the columns); without it one block per 64 columns walks every row */
 int tvts_colsum_bf16(const void* X, int ld, int M, int N, float* out, float* workspace, long workspace_elems, hipStream_t stream);

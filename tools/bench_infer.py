@@ -6,7 +6,9 @@ streaming kernel + CLS-query pair (what calls with lse2 run) against the forward
   --attn-only: the attention lines only (for a `rocprofv3 --kernel-trace --stats` run of its own).
   --mc: the SSv2 multiple-choice workload instead (174 candidate captions for each of 16 clips): encode_text(packed=False) against
   encode_text(packed=True), the packed attention site against the rectangular one, and the whole _mc forward; B/16 and H/14.
-  The caption lengths are a STAND-IN (uniform in [6, 24] from a fixed seed): the SSv2 label files are not part of this repository."""
+  The caption lengths are a STAND-IN (uniform in [6, 24] from a fixed seed): the SSv2 label files are not part of this repository.
+  --fp8: H/14 `encode_video` on the e4m3 architecture (arch["fp8"]: the blocks' GEMMs on e4m3 copies, per-token activation scales)
+  against the bf16 architecture, same random weights, at the H/14 clip counts above; one line per form."""
 import argparse
 import json
 import os
@@ -124,16 +126,51 @@ def multiple_choice(K, reps):
         torch.cuda.empty_cache()
 
 
+def fp8_encoders(iters):
+    """H/14 encode_video, bf16 against e4m3 (one model alive at a time); the e4m3 line also carries the worst per-clip cosine of
+    its embeddings against the bf16 model's"""
+    from tvts_amd.arch import ARCHS
+    from tvts_amd.downstream.model_TVTSv2_ViT_H_14 import TVTSv2_H_14
+    name, n = "H_14", 256
+    keep = torch.arange(n).unsqueeze(0)
+    ref = {}
+    for form, over in (("bf16", {}), ("e4m3", {"fp8": True})):
+        m = TVTSv2_H_14(load_checkpoint=None, arch=dict(ARCHS[name], **over), pretrained=False)
+        for cfg, _, B in CONFIGS:
+            if cfg != name:
+                continue
+            v = torch.randn(B, 12, 3, 224, 224, generator=torch.Generator().manual_seed(1)).cuda()
+            m.engine._inf.clear()
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            dt = timed(lambda: m.encode_video(v, keep), iters)
+            line = {"what": f"encode_video, {name} T=12 n={n}, {form}", "clips": B, "clips/s": B / dt,
+                    "peak GB": torch.cuda.max_memory_allocated() / 1e9}
+            e = m.encode_video(v, keep).double().cpu()
+            if form == "bf16":
+                ref[B] = e
+            else:
+                line["worst cosine against bf16"] = float(torch.nn.functional.cosine_similarity(e, ref[B], dim=1).min())
+            print(json.dumps(line), flush=True)
+            del v
+        del m
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--attn-only", action="store_true")
     ap.add_argument("--mc", action="store_true")
+    ap.add_argument("--fp8", action="store_true")
     ap.add_argument("--reps", type=int, default=20, help="--mc: timed repetitions of each form (median)")
     ap.add_argument("--iters", type=int, default=5)
     args = ap.parse_args()
     from tvts_amd import hip as K
     if args.mc:
         multiple_choice(K, max(args.reps, 20))
+        return
+    if args.fp8:
+        fp8_encoders(args.iters)
         return
     attention(K)
     if args.attn_only:

@@ -1426,6 +1426,103 @@ extern "C" int tvts_rows_linear_bf16(const void* A, long lda, const void* W, int
 }
 
 // ------------------------------------------------------------------------------------------------
+// The same few rows on the e4m3 operand copies: out[r, n] = residual[r, n] + bias[n] + row_scale[r] * w_scale[0] * sum_k A8[r * lda + k] * W8[n * ldw + k]
+// (A8 / W8 OCP e4m3 bytes, one scale per activation row as tvts_quant_fp8_rows writes them, one for the weight; out / residual fp32) --
+// the CLS rows of the forward-only encoder's last block on an e4m3 architecture, whose training forward multiplies the e4m3 copies of
+// attn.proj / mlp.c_proj for every row.  Bound by reading the weight once at one byte per element.
+// Decoded operands, fp32 FMAs on the vector ALU: every product-and-add is ONE round-to-nearest fp32 operation, so the result obeys
+// the recursive-summation bound of K - 1 roundings whatever the operands.  (The unscaled 16x16x32 e4m3 MFMA does not: measured
+// on an MI355X at K = 128 it left |err| = 1.04 x that bound on one element of a 3 x 64 product -- about K u S, a truncating adder
+// inside the instruction -- so the matrix pipe is not used here.)
+// A block owns a 16-row x 16-column output tile.  The 16 activation rows are decoded ONCE per 512-deep K chunk into LDS (fp32,
+// 32 KB); thread (c = t & 15, ks = t >> 4) owns column n0 + c and the 16-byte pieces ks, ks + 16, ... of its weight row: one
+// 16-byte load, 16 decoded values, 16 FMAs per activation row against LDS values that the 16 lanes of a k-slice read as a
+// broadcast.  The 16 k-slices are added through LDS in slice order: a fixed order, the same bits on every call.  N is free: the
+// lanes of a ragged last tile read the last weight row again and store nothing; rows past R read row R - 1 likewise.
+// ------------------------------------------------------------------------------------------------
+constexpr int RL8_KC = 512;
+__device__ __forceinline__ void decode16_e4m3(const int* v, float* f) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const f32x2_ lo = __builtin_amdgcn_cvt_pk_f32_fp8(v[e], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(v[e], true);
+        f[e * 4 + 0] = lo[0]; f[e * 4 + 1] = lo[1]; f[e * 4 + 2] = hi[0]; f[e * 4 + 3] = hi[1];
+    }
+}
+__global__ __launch_bounds__(256) void rows_linear_fp8_kernel(const unsigned char* __restrict__ A, long lda, const float* __restrict__ row_scale,
+                                                              const unsigned char* __restrict__ W, int ldw, const float* __restrict__ w_scale,
+                                                              int R, int N, int K, const float* __restrict__ bias,
+                                                              const float* __restrict__ residual, int ldr, float* __restrict__ out, int ldo) {
+    typedef __attribute__((ext_vector_type(4))) int i32x4;
+    __shared__ __attribute__((aligned(16))) float sa[16 * RL8_KC];  // [row][k of the chunk]; afterwards the k-slices' partials
+    const int c = threadIdx.x & 15, ks = threadIdx.x >> 4;
+    const int n0 = blockIdx.x * 16, r0 = blockIdx.y * 16;
+    const int col = n0 + c < N ? n0 + c : N - 1;
+    const unsigned char* wp = W + (size_t)col * ldw;
+    float acc[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int k0 = 0; k0 < K; k0 += RL8_KC) {
+        const int kc = K - k0 < RL8_KC ? K - k0 : RL8_KC;  // (a multiple of 64)
+        const int pieces = kc >> 4;
+        __syncthreads();  // the previous chunk has been read
+        for (int p = threadIdx.x; p < 16 * pieces; p += 256) {
+            const int r = p / pieces, q = p - r * pieces;
+            const int row = r0 + r < R ? r0 + r : R - 1;
+            const i32x4 v = *(const i32x4*)(A + (size_t)row * lda + k0 + q * 16);
+            const int vi[4] = {v[0], v[1], v[2], v[3]};
+            float f[16];
+            decode16_e4m3(vi, f);
+            float* d = sa + r * RL8_KC + q * 16;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) *(f32x4*)(d + e * 4) = (f32x4){f[e * 4], f[e * 4 + 1], f[e * 4 + 2], f[e * 4 + 3]};
+        }
+        __syncthreads();
+        for (int kk = ks * 16; kk < kc; kk += 256) {
+            const i32x4 wv = *(const i32x4*)(wp + k0 + kk);
+            const int wi[4] = {wv[0], wv[1], wv[2], wv[3]};
+            float w[16];
+            decode16_e4m3(wi, w);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float* a = sa + r * RL8_KC + kk;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const f32x4 av = *(const f32x4*)(a + e * 4);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[r] = __builtin_fmaf(av[j], w[e * 4 + j], acc[r]);
+                }
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sa[(ks * 16 + r) * 16 + c] = acc[r];
+    __syncthreads();
+    const int m = threadIdx.x >> 4, n = threadIdx.x & 15;
+    if (r0 + m < R && n0 + n < N) {
+        float v = sa[m * 16 + n];
+#pragma unroll
+        for (int s = 1; s < 16; ++s) v += sa[(s * 16 + m) * 16 + n];
+        v *= w_scale[0] * row_scale[r0 + m];
+        if (bias) v += bias[n0 + n];
+        if (residual) v += residual[(size_t)(r0 + m) * ldr + n0 + n];
+        out[(size_t)(r0 + m) * ldo + n0 + n] = v;
+    }
+}
+
+extern "C" int tvts_rows_linear_fp8(const void* A8, long lda, const float* row_scale, const void* W8, int ldw, const float* w_scale, int R,
+                                    int N, int K, const float* bias, const float* residual, int ldr, float* out, int ldo,
+                                    hipStream_t stream) {
+    if (R <= 0 || N <= 0 || K <= 0 || !A8 || !W8 || !row_scale || !w_scale || !out) return TVTS_EINVAL;
+    // 16-byte loads: K in whole 64-byte lines, rows that start on 16-byte boundaries
+    if (K % 64 || lda % 16 || ldw % 16 || ((size_t)A8 | (size_t)W8) % 16 || ldo < N || (residual && ldr < N)) return TVTS_EINVAL;
+    hipLaunchKernelGGL(rows_linear_fp8_kernel, dim3(ceil_div(N, 16), ceil_div(R, 16)), dim3(256), 0, stream, (const unsigned char*)A8, lda,
+                       row_scale, (const unsigned char*)W8, ldw, w_scale, R, N, K, bias, residual, ldr, out, ldo);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // bias gradient: out[n] += sum_m X[m,n]  (bf16 in).  A block owns 64 columns and one of gridDim.y row ranges: 8 column threads
 // (8 columns each) x 32 row lanes striding the range, merged through LDS in row-lane order.  With a workspace the row ranges'
 // sums go to partials [range][N] that colsum_ranges_kernel adds in range order -- no atomics, run-to-run reproducible, and

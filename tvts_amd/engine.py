@@ -401,7 +401,13 @@ class Engine:
 
     def _q8(self, M, W, name, persistent=False):
         """Buffers for the e4m3 copy of tensor `name` [M, W]: (bytes, scale operand for the GEMMs, kwargs for the producing kernel).
-        persistent: the bytes outlive the next producer of the same width (an activation the weight gradient reads in the backward)."""
+        persistent: the bytes outlive the next producer of the same width (an activation the weight gradient reads in the backward).
+        name None: forward-only (the encoders).  Always the per-token regime, which has no state: the bytes and the row scales are
+        encoder workspaces keyed by role and width, reused by every layer; no scale slot is looked up, made or written."""
+        if name is None:
+            q = self._ib("q8.%d" % W, (M, W), torch.uint8)
+            rs = self._ib("q8.row_scale", (max(M, 2),), torch.float32)  # (never a 1-element tensor, as below)
+            return q, rs, dict(row_scale=rs)
         q = self._b(("fp8.x." + name) if (persistent and self.fp8_wgrad) else "fp8.q%d" % W, (M, W), torch.uint8)
         if not self.fp8_wgrad:
             rs = self._f("fp8.row_scale", (max(M, 2),))  # never a 1-element tensor: that means "one scale for the tensor"
@@ -440,13 +446,23 @@ class Engine:
         q, sc, kw = self._q8(M, W, name, persistent=persistent)
         return dict(q8out=q, q8_scale=sc, q8_amax=kw["amax"]), (q, sc)
 
-    def _lin(self, a, wname, bname, out, M, a8=None, q8_for=None, **epi):
+    def _lin(self, a, wname, bname, out, M, a8=None, q8_for=None, fwd_only=False, **epi):
         """q8_for: the weight whose GEMMs read `out` as their activation; in the per-tensor e4m3 regime the epilogue of this GEMM
-        then writes that operand copy itself (the MLP's GELU output), instead of a quantiser pass over `out`."""
+        then writes that operand copy itself (the MLP's GELU output), instead of a quantiser pass over `out`.
+        fwd_only (the encoders' blocks, tag None): an e4m3 layer runs in the per-token regime whatever _f8_tensor_mode says, on
+        encoder workspaces, and leaves the backward's bookkeeping (_x8, _x8_ready, _x8_only) and the scale table alone."""
         if epi.get("act") is not None and self.gate_deriv:
             # the side output `preact` holds act'(x), which the gate of the backward multiplies by as is (every call of the training
             # step that passes act passes preact); forward-only there is no preact: the same epilogue instantiation, side output skipped
             epi["side_deriv"] = True
+        if wname in self.P.w8 and fwd_only:
+            w8, ws, _ = self.P.w8[wname]
+            if a8 is None:  # activations that do not come out of a LayerNorm: one pass
+                q, sa, kw = self._q8(M, a.shape[1], None)
+                K.quantize_fp8_rows(a[:M], q=q, **kw)
+                a8 = (q, sa)
+            K.gemm_nt_fp8(a8[0], a8[1], w8, ws, out[:M], bias=self.P.p(bname) if bname else None, **epi)
+            return
         if wname in self.P.w8:  # fp8 weight/activation path (BASELINE config 4): forward GEMMs of the ViT blocks
             w8, ws, _ = self.P.w8[wname]
             if a8 is None:
@@ -468,13 +484,14 @@ class Engine:
             return
         K.gemm_nt(a, self.P.w(wname), out, M=M, bias=self.P.p(bname) if bname else None, **epi)
 
-    def _cls_lin(self, a, S, wname, bname, res_c, out_c):
+    def _cls_lin(self, a, S, wname, bname, res_c, out_c, fwd_only=False):
         """The CLS rows of the hybrid stream through a residual-adding linear layer: out_c [B, N] = res_c + a[b * S, :] @ W^T + bias,
         fp32 result and fp32 residual (the stream's own rows take the bf16 residual epilogue).  a: the [B * S, K] bf16 operand of the
         block's GEMM; its CLS rows are addressed as a [B, K] matrix with the row stride S * K -- the same operand bytes and the same
-        bf16 weight shadow, always on the bf16 MFMA path (also when the block's GEMMs multiply e4m3 copies)."""
+        bf16 weight shadow, always on the bf16 MFMA path (also when the block's GEMMs multiply e4m3 copies).  fwd_only: an encoder
+        call, whose operands always exist in bf16 (per-token regime) and which reads nothing the training step recorded."""
         Bc = out_c.shape[0]
-        if wname in self._x8_only:  # the operand only exists as e4m3 bytes (arch["fp8_q8_only"]): the same rows of that copy
+        if wname in self._x8_only and not fwd_only:  # the operand only exists as e4m3 bytes (arch["fp8_q8_only"]): the same rows of that copy
             q, sa = self._x8[wname]
             w8, ws, _ = self.P.w8[wname]
             K.gemm_nt_fp8(q[:Bc * S].view(Bc, -1)[:, :q.shape[1]], sa, w8, ws, out_c, bias=self.P.p(bname) if bname else None, residual=res_c)
@@ -576,7 +593,14 @@ class Engine:
         if tag is not None:
             mean, rstd = self._f(tag + ".mean", (M,)), self._f(tag + ".rstd", (M,))
         a8, kw = None, {}
-        if fp8_for is not None and fp8_for in self.P.w8:
+        if fp8_for is not None and fp8_for in self.P.w8 and tag is None:
+            # forward-only: per-token copy in an encoder workspace; its GEMM is the only reader of this LayerNorm's output, so where
+            # the e4m3-only form of the kernel exists (bf16 rows, W % 8 == 0, W <= 1536) the bf16 tensor is not written at all
+            q, sa, kw = self._q8(M, y.shape[1], None)
+            a8, kw = (q, sa), dict(kw, q8=q)
+            if rows is None and x.dtype == torch.bfloat16 and y.shape[1] % 8 == 0 and y.shape[1] <= 1536 and x.stride(0) % 8 == 0:
+                y = None
+        elif fp8_for is not None and fp8_for in self.P.w8:
             q, sa, kw = self._q8(M, y.shape[1], "x." + fp8_for, persistent=True)
             a8, kw = (q, sa), dict(kw, q8=q)
             # arch["fp8_q8_only"]: under per-tensor scales the forward GEMM and the weight gradient both multiply the e4m3 bytes,
@@ -754,7 +778,7 @@ class Engine:
         h, S = self.arch["heads"], 1 + T * n
         ws = self._w(None if lse is None else "vit", ".clsws", "clsws", (B * h * max(T, -(-n // 28)) * (self.dh + 2),), torch.float32)
         kw8 = {}
-        if q8_for is not None and q8_for in self.P.w8:
+        if lse is not None and q8_for is not None and q8_for in self.P.w8:  # (forward-only: per token, the projection quantises)
             kw8, nxt = self._attn_q8(B * S, att.shape[1], "x." + q8_for, T, n, persistent=True, consumer=q8_for)
             if nxt is not None:
                 self._x8_ready[q8_for] = nxt
@@ -803,46 +827,46 @@ class Engine:
         """What every row of a space-time block goes through in both passes, up to the space attention's input:
         ln_3 -> time qkv -> time attention -> t_res -> ln_1 -> space qkv.  -> qkv_s"""
         a, w = self.arch, self._w
-        W, M = a["width"], x.shape[0]
+        W, M, fo = a["width"], x.shape[0], tg is None
         ln3 = w(tg, ".ln3", "ln", (M, W))
         a8 = self._ln(x, pre + "ln_3", 1e-5, ln3, tg and tg + ".ln3", fp8_for=pre + "timeattn.qkv.weight", cls_x=xc)
         qkv_t = w(tg, ".qkv_t", "qkv", (M, 3 * W))
-        self._lin(ln3, pre + "timeattn.qkv.weight", pre + "timeattn.qkv.bias", qkv_t, M, a8=a8)
+        self._lin(ln3, pre + "timeattn.qkv.weight", pre + "timeattn.qkv.bias", qkv_t, M, a8=a8, fwd_only=fo)
         att_t, lse_t = w(tg, ".att_t", "att", (M, W)), (self._f(tg + ".lse_t", (M, a["heads"])) if tg else None)
         self._st_attention_fwd(qkv_t, att_t, lse_t, "time", B, T, n, q8_for=pre + "timeattn.proj.weight")
         # the time residual only feeds ln_1 (the space branch restarts from x, video_encoder_ViT_B_16.py:121): bf16
         t_res = w(tg, ".t_res", "tres", (M, W))
-        self._lin(att_t, pre + "timeattn.proj.weight", pre + "timeattn.proj.bias", t_res, M, residual=x)
+        self._lin(att_t, pre + "timeattn.proj.weight", pre + "timeattn.proj.bias", t_res, M, residual=x, fwd_only=fo)
         ln1 = w(tg, ".ln1", "ln", (M, W))
         a8 = self._ln(t_res, pre + "ln_1", 1e-5, ln1, tg and tg + ".ln1", fp8_for=pre + "attn.qkv.weight")
         qkv_s = w(tg, ".qkv_s", "qkv", (M, 3 * W))
-        self._lin(ln1, pre + "attn.qkv.weight", pre + "attn.qkv.bias", qkv_s, M, a8=a8)
+        self._lin(ln1, pre + "attn.qkv.weight", pre + "attn.qkv.bias", qkv_s, M, a8=a8, fwd_only=fo)
         return qkv_s
 
     def _vit_block(self, l, x, xc, tag, B, T, n):
         """space-time block l on every row: (x, xc) -> the next (x, xc); forward-only (tag None) in place"""
         a, w = self.arch, self._w
         pre, tg = f"video_model.transformer.resblocks.{l}.", tag and f"{tag}{l}"
-        W, M, S = a["width"], x.shape[0], 1 + T * n
+        W, M, S, fo = a["width"], x.shape[0], 1 + T * n, tag is None
         qkv_s = self._vit_block_head(pre, x, xc, tg, B, T, n)
         att_s, lse_s = w(tg, ".att_s", "att", (M, W)), (self._f(tg + ".lse_s", (M, a["heads"])) if tg else None)
         self._st_attention_fwd(qkv_s, att_s, lse_s, "space", B, T, n, q8_for=pre + "attn.proj.weight")
         s_res = w(tg, ".s_res", "s", (M, W), x.dtype)  # residual from the block INPUT x (video_encoder_ViT_B_16.py:121)
-        self._lin(att_s, pre + "attn.proj.weight", pre + "attn.proj.bias", s_res, M, residual=x)
+        self._lin(att_s, pre + "attn.proj.weight", pre + "attn.proj.bias", s_res, M, residual=x, fwd_only=fo)
         s_res_c = None
         if xc is not None:
             s_res_c = w(tg, ".s_res_c", "sc", (B, W), torch.float32)
-            self._cls_lin(att_s, S, pre + "attn.proj.weight", pre + "attn.proj.bias", xc, s_res_c)
+            self._cls_lin(att_s, S, pre + "attn.proj.weight", pre + "attn.proj.bias", xc, s_res_c, fwd_only=fo)
         ln2 = w(tg, ".ln2", "ln", (M, W))
         a8 = self._ln(s_res, pre + "ln_2", 1e-5, ln2, tg and tg + ".ln2", fp8_for=pre + "mlp.c_fc.weight", cls_x=s_res_c)
         h, act = (self._b(tg + ".h", (M, 4 * W)) if tg else None), w(tg, ".a", "h", (M, 4 * W))
         self._lin(ln2, pre + "mlp.c_fc.weight", pre + "mlp.c_fc.bias", act, M, act=a["act"], preact=h, a8=a8,
-                  q8_for=pre + "mlp.c_proj.weight")
+                  q8_for=pre + "mlp.c_proj.weight", fwd_only=fo)
         xo = self._b(f"{tag}.x{l + 1}", (M, W), x.dtype) if tag else x  # (forward-only: x is dead)
-        self._lin(act, pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", xo, M, residual=s_res)
+        self._lin(act, pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", xo, M, residual=s_res, fwd_only=fo)
         if xc is not None:
             xcn = self._f(f"{tag}.xc{l + 1}", (B, W)) if tag else xc
-            self._cls_lin(act, S, pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", s_res_c, xcn)
+            self._cls_lin(act, S, pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", s_res_c, xcn, fwd_only=fo)
             xc = xcn
         return xo, xc
 
@@ -1412,14 +1436,32 @@ class Engine:
     #                  every layer (peak ~ one layer) with the residual stream updated in place; the backward-only tensors are
     #                  neither allocated nor written (lse2 = None: SPACE calls at full frames take their own fused kernel).
     # Same entry points, weights, epilogue options and epsilons either way.  What the encoders add of their own: the last ViT
-    # block runs its second half for the CLS rows only, and the e4m3 architectures are refused (the e4m3 branches of _ln / _lin
-    # never see tag None).  Nothing of the training step's workspace is read, written or resized by an encoder call.
+    # block runs its second half for the CLS rows only.  Nothing of the training step's workspace is read, written or resized by an
+    # encoder call.
+    # e4m3 architectures (fp8 / fp8_dgrad / fp8_wgrad): the blocks' six linear layers multiply the e4m3 weight copies of ParamStore.w8
+    # in the PER-TOKEN regime -- activation rows under their own scale, from the LayerNorm in front of qkv / c_fc or from one
+    # quantiser pass -- which has no state: no calibration, and on an fp8_wgrad model also after _f8_tensor_mode has come on; the
+    # scale table (_f8_scale, _f8_amax, _f8_ids) and the backward's operand bookkeeping (_x8, _x8_ready, _x8_only) are neither read
+    # nor written.  The e4m3 bytes and row scales are the encoder workspaces "q8.<width>" / "q8.row_scale" (_q8 with name None).
+    # The last block's CLS tail multiplies the e4m3 copies of attn.proj and mlp.c_proj as well (tvts_rows_linear_fp8 over the B
+    # quantised CLS rows).  The text tower is never quantised: encode_text* run what they run on a bf16 architecture.
     def _inf_check(self):
         a = self.arch
         if a.get("family") == "v1":
             raise NotImplementedError("the forward-only encoders are built for the v2 models")
-        if a.get("fp8") or a.get("fp8_dgrad") or a.get("fp8_wgrad"):
-            raise NotImplementedError("the forward-only encoders have no e4m3 form; use a bf16 architecture")
+
+    def _cls_tail_lin(self, a_c, wname, bname, res_c, out_c):
+        """a residual-adding projection of the last block on the B CLS rows a_c (bf16, possibly a strided row view) -> out_c fp32:
+        on the weight's e4m3 copy where the architecture has one (the rows quantised per token like every other row of the layer,
+        tvts_quant_fp8_rows over the strided view), on the bf16 shadow otherwise"""
+        bias = self.P.p(bname)
+        if wname in self.P.w8:
+            w8, ws, _ = self.P.w8[wname]
+            q, rs, kw = self._q8(a_c.shape[0], a_c.shape[1], None)
+            K.quantize_fp8_rows(a_c, q=q, **kw)
+            K.rows_linear_fp8(q, rs, w8, ws, out_c, bias=bias, residual=res_c)
+            return
+        K.rows_linear(a_c, self.P.w(wname), out_c, bias=bias, residual=res_c)
 
     def encode_video(self, video, keep_dev, B, T, crop=None, resize=None):
         """-> [B, E] fp32 video embeddings (an encoder workspace: the next encoder call overwrites it).  video: fp32 [B, T, 3, H, W]
@@ -1449,13 +1491,13 @@ class Engine:
                         full_bf16=x if x.dtype == torch.bfloat16 else None, packed_f32=x_c)
         att_c = att.view(B, S * W)[:, :W]
         s_c = self._ib("sc", (B, W), f32)
-        K.rows_linear(att_c, self.P.w(pre + "attn.proj.weight"), s_c, bias=self.P.p(pre + "attn.proj.bias"), residual=x_c)
+        self._cls_tail_lin(att_c, pre + "attn.proj.weight", pre + "attn.proj.bias", x_c, s_c)
         ln_c = self._ib("lnc", (B, W))
-        self._ln(s_c, pre + "ln_2", 1e-5, ln_c, None)
+        a8 = self._ln(s_c, pre + "ln_2", 1e-5, ln_c, None, fp8_for=pre + "mlp.c_fc.weight")
         h_c = self._ib("hc", (B, 4 * W))
-        self._lin(ln_c, pre + "mlp.c_fc.weight", pre + "mlp.c_fc.bias", h_c, B, act=a["act"])
+        self._lin(ln_c, pre + "mlp.c_fc.weight", pre + "mlp.c_fc.bias", h_c, B, act=a["act"], a8=a8, fwd_only=True)
         xo_c = self._ib("xoc", (B, W), f32)
-        K.rows_linear(h_c, self.P.w(pre + "mlp.c_proj.weight"), xo_c, bias=self.P.p(pre + "mlp.c_proj.bias"), residual=s_c)
+        self._cls_tail_lin(h_c, pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", s_c, xo_c)
         emb = self._ib("vemb", (B, E), f32)
         if not self.pooled_tail:  # B models: ln_post, then x @ proj of the CLS rows (the embedding is the CLS row of the tokens)
             lnp = self._ib("lnc", (B, W))

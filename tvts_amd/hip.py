@@ -498,6 +498,19 @@ def rows_linear(a, w, out, *, bias=None, residual=None):
                                    _ld(residual) if residual is not None else 0, _p(out), _ld(out), _stream()), "tvts_rows_linear_bf16")
 
 
+def rows_linear_fp8(a8, row_scale, w8, w_scale, out, *, bias=None, residual=None):
+    """out[R, N] (fp32) = residual + bias + row_scale[r] * w_scale * (a8[R, K] @ w8[N, K]^T) for a FEW rows on e4m3 operands: a8 uint8
+    (a strided row view is fine: one row per clip) under one scale per row (quantize_fp8_rows), w8 / w_scale as in ParamStore.w8"""
+    lib = _lib.load()
+    assert a8.dtype == torch.uint8 and w8.dtype == torch.uint8 and out.dtype == torch.float32 and a8.stride(1) == 1
+    R, Kd = a8.shape
+    N = w8.shape[0]
+    assert w8.shape[1] == Kd and tuple(out.shape) == (R, N) and (residual is None or tuple(residual.shape) == (R, N))
+    assert row_scale.dtype == torch.float32 and row_scale.numel() >= R and w_scale.dtype == torch.float32 and (bias is None or bias.numel() == N)
+    _chk(lib.tvts_rows_linear_fp8(_p(a8), a8.stride(0), _p(row_scale), _p(w8), _ld(w8), _p(w_scale), R, N, Kd, _p(bias), _p(residual),
+                                  _ld(residual) if residual is not None else 0, _p(out), _ld(out), _stream()), "tvts_rows_linear_fp8")
+
+
 def colsum(x, out, *, M=None):
     lib = _lib.load()
     M = x.shape[0] if M is None else M
