@@ -79,13 +79,14 @@ def engine(arch, params, cls=Engine):
     return cls(store)
 
 
-def train(arch, steps=1, v1=False):
+def train(arch, steps=1, v1=False, n_trans=None):
     mod = V if v1 else O
     eng = engine(arch, mod.synth_params(arch, seed=5), EngineV1 if v1 else Engine)
-    batch = mod.synth_batch(arch, B=4, T=4, seed=6, caption_len=11)
+    batch = mod.synth_batch(arch, B=4, T=4, seed=6, n_trans=n_trans, caption_len=11)
     for _ in range(steps):
         te, ve, pred = eng.forward(eng.prepare_batch(batch))
-        eng.backward(torch.full_like(te, 0.01), torch.full_like(ve, 0.01), torch.full_like(pred, 0.01))
+        d_pred = None if pred is None else torch.full_like(pred, 0.01)  # (one transcript per clip: no sorting loss)
+        eng.backward(torch.full_like(te, 0.01), torch.full_like(ve, 0.01), d_pred)
         eng.end_step()
 
 
@@ -122,6 +123,14 @@ SCENARIOS = {
     "train-h-tiny": lambda: train(A.small_arch_h(tn_grouped=True)),  # (grouped weight gradients on: TnGroup.run is in the trace)
     "train-fp8": lambda: train(A.small_arch(fp8_wgrad=True), steps=2),  # calibration step, end_step(), tensor-mode step
     "train-v1": lambda: train(A.small_arch_v1(), v1=True),
+    "train-dense-last": lambda: train(A.small_arch(sort_used_rows_only=False, text_used_rows_only=False)),  # last blocks on every row
+    "train-wgrad-side": lambda: train(A.small_arch(wgrad_stream=True)),
+    "train-fp8-dgrad": lambda: train(A.small_arch(fp8=True, fp8_dgrad=True)),  # per-token e4m3 with input gradients
+    "train-h-fp32": lambda: train(A.small_arch_h(hybrid_stream=False)),  # the two non-hybrid pooled tails
+    "train-h-bf16res": lambda: train(A.small_arch_h(bf16_residual=True)),
+    "train-nt1": lambda: train(A.small_arch(), n_trans=1),  # no sort head: pred is None
+    "train-h-nt1": lambda: train(A.small_arch_h(), n_trans=1),  # ... and the pooled tail then has no token gradient
+    "train-v1-dense": lambda: train(A.small_arch_v1(sort_used_rows_only=False), v1=True),
     "enc-video": enc_video,
     "enc-text": enc_text,
 }

@@ -89,6 +89,7 @@ ONE_OFF = collections.OrderedDict([
     ("bench_eager_vs_graph.jsonl", "round-3 eager against replayed step (superseded by bench_product_path: the replayed step is now slower)"),
     ("next_rows.jsonl", "validation forward + metrics (N1), downstream model (N2), uint8-fed step (N3) throughput"),
     ("forward_unify_trace.txt", "`tools/launch_trace.py` before / after the training step and the forward-only encoders were given one forward wiring: the same launches on the same buffers, scenario by scenario"),
+    ("backward_unify.txt", "the same check for the backward wiring (one pre-LN block, one tower walk per direction, `video_backward` in stages), over the widened scenario set; the eager step against the parent commit in alternating runs at 12 and 192 pairs"),
 ])
 
 

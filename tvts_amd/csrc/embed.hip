@@ -692,7 +692,7 @@ extern "C" int tvts_rows_gather(const float* src, int ld_src, const int* rows, i
 }
 
 // ---------------------------------------------------------------------------------------------- rows between a token-row matrix and a packed [R, W] one
-// (the "used rows" blocks: the last block of the sort head / the text tower runs on the R rows the model reads, engine.py::_used_rows_*)
+// (the "used rows" blocks: the last block of the sort head / the text tower runs on the R rows the model reads, engine.py::_block_fwd / _block_bwd with rows)
 //   mode 0 gather        packed[r] = full[rows[r]]: source full_f32 if given else full_bf16; packed_f32 and / or packed_bf16 written
 //   mode 1 scatter       full[rows[r]] = packed[r], per element type given on BOTH sides
 //   mode 2 scatter-add   full_f32[rows[r]] += packed_f32[r]; full_bf16[rows[r]] = bf16(that sum) when given (the bf16 copy of the row)

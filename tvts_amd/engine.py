@@ -630,44 +630,109 @@ class Engine:
                         dbeta=self.P.g(name + ".bias") if tr else None, rows=rows, M=M, **kw)
         return d8
 
-    # ------------------------------------------------------------------ generic pre-LN block (text tower, sort head)
-    def _block_fwd(self, pre, nm, x_in, x_out, tag, M, Wd, heads, act, eps, attn_fwd):
-        """attn_fwd(qkv, att, lse): the attention call.  tag None: forward-only (lse None, no act'(x) side output; x_out may be x_in)."""
-        w = self._w
+    # ------------------------------------------------------------------ generic pre-LN block and tower (text, sort head, v1 ViT)
+    # `rows` (int32 token rows): a block whose output the model reads at those R rows only, and into whose other output rows no
+    # gradient enters.  LayerNorm 1 and the qkv projection stay dense (keys / values of every token); the attention output
+    # (attn_fwd: a query-restricted kernel writing the used rows of `att`), the output projection, the residual, LayerNorm 2 and the
+    # MLP are computed for the R used rows; backward: dQ for those rows, dK / dV -- and through them the gradient of every input
+    # row -- dense.
+    def _block_fwd(self, pre, nm, x_in, x_out, tag, heads, act, eps, attn_fwd, rows=None):
+        """attn_fwd(qkv, att, lse): the attention call.  tag None: forward-only (lse None, no act'(x) side output; x_out may be x_in).
+        -> x_out, or with `rows` the block output at those rows, packed [R, Wd] fp32 (x_out is not used)."""
+        w, f32 = self._w, torch.float32
+        M, Wd = x_in.shape
+        R = M if rows is None else rows.numel()
         ln1 = w(tag, ".ln1", "ln", (M, Wd))
         self._ln(x_in, pre + nm["ln1"], eps, ln1, tag and tag + ".ln1")
         qkv = w(tag, ".qkv", "qkv", (M, 3 * Wd))
         self._lin(ln1, pre + nm["qkv_w"], pre + nm["qkv_b"], qkv, M)
         att = w(tag, ".att", "att", (M, Wd))
         attn_fwd(qkv, att, self._f(tag + ".lse", (M, heads)) if tag else None)
-        mid = w(tag, ".mid", "s", (M, Wd), torch.float32)
-        self._lin(att, pre + nm["o_w"], pre + nm["o_b"], mid, M, residual=x_in)
-        ln2 = w(tag, ".ln2", "ln", (M, Wd))
+        res = x_in
+        if rows is not None:
+            att_r, res = w(tag, ".att_r", "att_r", (R, Wd)), w(tag, ".x_r", "x_r", (R, Wd), f32)
+            K.rows_move("gather", rows, full_bf16=att, packed_bf16=att_r)   # (row gathers of R x Wd elements)
+            K.rows_move("gather", rows, full_f32=x_in, packed_f32=res)
+            att, x_out = att_r, w(tag, ".xo_r", "xoc", (R, Wd), f32)
+        mid = w(tag, ".mid", "s", (R, Wd), f32)
+        self._lin(att, pre + nm["o_w"], pre + nm["o_b"], mid, R, residual=res)
+        ln2 = w(tag, ".ln2", "ln" if rows is None else "lnc", (R, Wd))
         self._ln(mid, pre + nm["ln2"], eps, ln2, tag and tag + ".ln2")
-        h = self._b(tag + ".h", (M, 4 * Wd)) if tag else None
-        a = w(tag, ".a", "h", (M, 4 * Wd))
-        self._lin(ln2, pre + nm["fc_w"], pre + nm["fc_b"], a, M, act=act, preact=h)
-        self._lin(a, pre + nm["pj_w"], pre + nm["pj_b"], x_out, M, residual=mid)
+        h = self._b(tag + ".h", (R, 4 * Wd)) if tag else None
+        a = w(tag, ".a", "h", (R, 4 * Wd))
+        self._lin(ln2, pre + nm["fc_w"], pre + nm["fc_b"], a, R, act=act, preact=h)
+        self._lin(a, pre + nm["pj_w"], pre + nm["pj_b"], x_out, R, residual=mid)
+        return x_out
 
-    def _block_bwd(self, pre, nm, x_in, dx, dxb, dx_in, dxb_in, tag, M, Wd, heads, Bn, S, causal, act, scr):
-        """dx/dxb: grad wrt block output (fp32 / bf16).  Writes grad wrt block input to dx_in/dxb_in."""
+    def _block_bwd(self, pre, nm, x_in, dx, dxb, dx_in, dxb_in, tag, scr, heads, act, attn_bwd, rows=None):
+        """dx / dxb: fp32 / bf16 gradient of the block output (with `rows`: at those R rows, packed); attn_bwd(qkv, datt, att, lse,
+        delta, dqkv): the attention call.  Writes the gradient of every input row to dx_in / dxb_in."""
         B_ = self.buf
-        hd = Wd // heads
-        dh = self._b(scr + ".dh", (M, 4 * Wd))
-        dln = self._b(scr + ".dln", (M, Wd))
-        self._lin_bwd(dxb, B_[tag + ".a"], pre + nm["pj_w"], pre + nm["pj_b"], dh, M, gate_h=B_[tag + ".h"], gate_act=act)
-        self._lin_bwd(dh, B_[tag + ".ln2"], pre + nm["fc_w"], pre + nm["fc_b"], dln, M)
-        dmid = self._f(scr + ".dmid", (M, Wd))
-        dmidb = self._b(scr + ".dmidb", (M, Wd))
-        self._ln_bwd(dln, B_[tag + ".mid"], pre + nm["ln2"], tag + ".ln2", dmid, dx_bf16=dmidb, res1=dx)
-        datt = self._b(scr + ".datt", (M, Wd))
-        self._lin_bwd(dmidb, B_[tag + ".att"], pre + nm["o_w"], pre + nm["o_b"], datt, M)
+        M, Wd = x_in.shape
+        R, r = (M, "") if rows is None else (rows.numel(), "_r")
+        dh, dln_r = self._b(scr + ".dh" + r, (R, 4 * Wd)), self._b(scr + ".dln" + r, (R, Wd))
+        self._lin_bwd(dxb, B_[tag + ".a"], pre + nm["pj_w"], pre + nm["pj_b"], dh, R, gate_h=B_[tag + ".h"], gate_act=act)
+        self._lin_bwd(dh, B_[tag + ".ln2"], pre + nm["fc_w"], pre + nm["fc_b"], dln_r, R)
+        dmid, dmidb = self._f(scr + ".dmid" + r, (R, Wd)), self._b(scr + ".dmidb" + r, (R, Wd))
+        self._ln_bwd(dln_r, B_[tag + ".mid"], pre + nm["ln2"], tag + ".ln2", dmid, dx_bf16=dmidb, res1=dx)
+        datt = self._b(scr + ".datt" + r, (R, Wd))
+        self._lin_bwd(dmidb, B_[tag + ".att" + r], pre + nm["o_w"], pre + nm["o_b"], datt, R)
+        if rows is not None:
+            datt_r, datt = datt, self._b(scr + ".datt", (M, Wd))  # token-row indexed like the attention output; only the R rows are read
+            K.rows_move("scatter", rows, full_bf16=datt, packed_bf16=datt_r)
         dqkv = self._b(scr + ".dqkv", (M, 3 * Wd))
         delta = self._f(scr + ".delta", (M, heads))
-        qkv, lse = B_[tag + ".qkv"], B_[tag + ".lse"]
-        K.attn_bwd("full", qkv, datt, B_[tag + ".att"], lse, delta, dqkv, B=Bn, heads=heads, S=S, causal=causal, head_dim=hd)
+        attn_bwd(B_[tag + ".qkv"], datt, B_[tag + ".att"], B_[tag + ".lse"], delta, dqkv)
+        dln = self._b(scr + ".dln", (M, Wd))  # (the dense block: dln_r again)
         self._lin_bwd(dqkv, B_[tag + ".ln1"], pre + nm["qkv_w"], pre + nm["qkv_b"], dln, M)
-        self._ln_bwd(dln, x_in, pre + nm["ln1"], tag + ".ln1", dx_in, dx_bf16=dxb_in, res1=dmid)
+        # the residual path, + dmid: inside the LayerNorm backward, or at the used rows behind it (fp32 sum, bf16 copy refreshed
+        # for those rows)
+        self._ln_bwd(dln, x_in, pre + nm["ln1"], tag + ".ln1", dx_in, dx_bf16=dxb_in, res1=dmid if rows is None else None)
+        if rows is not None:
+            K.rows_move("scatter_add", rows, full_f32=dx_in, full_bf16=dxb_in, packed_f32=dmid)
+
+    def _blocks_fwd(self, pre, nm, x, tag, depth, heads, act, eps, attn, rows=None, attn_rows=None):
+        """x through the blocks pre + "0." ... of a pre-LN tower -> the stream behind the last block -- or, with `rows`, that
+        block's output at those rows (packed; attn_rows: its attention call), for the caller's final LayerNorm and head.
+        tag: block l keeps its tensors as tag + "l" + name and writes the stream tag + ".x<l + 1>"; None: forward-only, in place."""
+        for l in range(depth):
+            used = rows if l == depth - 1 else None
+            xo = None if used is not None else self._f(f"{tag}.x{l + 1}", x.shape) if tag else x
+            x = self._block_fwd(f"{pre}{l}.", nm, x, xo, tag and f"{tag}{l}", heads, act, eps, attn if used is None else attn_rows,
+                                rows=used)
+        return x
+
+    @staticmethod
+    def _ab(depth, l):
+        """The gradient stream of a tower of `depth` blocks ping-pongs between two buffers, "A" and "B": what enters the last block
+        from behind is in A; -> the one that block l writes the gradient of its input to."""
+        return "B" if (depth - l) % 2 == 1 else "A"
+
+    def _head_ln_bwd(self, dy, name, tag, ln_tag, depth, rows, packed):
+        """The backward of a tower's final LayerNorm, which read the last block's output at `rows` -> dx, dxb for _blocks_bwd:
+        packed [R, Wd] when that block ran on those rows only, over every row (zero off `rows`) otherwise."""
+        if packed:
+            xo = self.buf[f"{tag}{depth - 1}.xo_r"]
+            dx, dxb = self._f(tag + ".dx_r", xo.shape), self._b(tag + ".dxb_r", xo.shape)
+            self._ln_bwd(dy, xo, name, ln_tag, dx, dx_bf16=dxb)
+        else:
+            x = self.buf[f"{tag}.x{depth}"]
+            dx, dxb = self._f(tag + ".dxA", x.shape, zero=True), self._b(tag + ".dxbA", x.shape, zero=True)
+            self._ln_bwd(dy, x, name, ln_tag, dx, dx_bf16=dxb, rows=rows)
+        return dx, dxb
+
+    def _blocks_bwd(self, pre, nm, tag, depth, dx, dxb, heads, act, attn_bwd, rows=None, attn_bwd_rows=None, after=None):
+        """The backward of _blocks_fwd.  dx / dxb: fp32 / bf16 gradient of what it returned -> the fp32 gradient of its input x.
+        The blocks' input gradients alternate between tag + ".dxA|B" / ".dxbA|B" (_ab); after(l): called behind block l."""
+        for l in reversed(range(depth)):
+            x_in, nx, used = self.buf[f"{tag}.x{l}"], self._ab(depth, l), rows if l == depth - 1 else None
+            dxi, dxbi = self._f(f"{tag}.dx{nx}", x_in.shape), self._b(f"{tag}.dxb{nx}", x_in.shape)
+            self._block_bwd(f"{pre}{l}.", nm, x_in, dx, dxb, dxi, dxbi, f"{tag}{l}", tag + ".s", heads, act,
+                            attn_bwd if used is None else attn_bwd_rows, rows=used)
+            dx, dxb = dxi, dxbi
+            if after is not None:
+                after(l)
+        return dx
 
     # ------------------------------------------------------------------ text tower
     @staticmethod
@@ -700,59 +765,36 @@ class Engine:
         kernel; attn / attn_last(qkv, att, lse): the attention call of a block / of the last block, whose only queries are the rows
         eot_rows; tag: "txt" in the training step, None forward-only (one stream buffer, updated in place)."""
         a, w = self.arch, self._w
-        Wt, ht = a["text_width"], a["text_heads"]
+        Wt = a["text_width"]
         x = w(tag, ".x0", "x", (M, Wt), torch.float32)
         embed(x)
+        # the model reads the last block's output at the EOT token of every caption only (CLIP/clip/model.py:343-354)
+        packed = self.text_used_rows_only
+        x = self._blocks_fwd("text_model.resblocks.", _TEXT_NAMES, x, tag, a["text_layers"], a["text_heads"], a["act"], 1e-5, attn,
+                             eot_rows if packed else None, attn_last)
         lnf = w(tag, ".lnf", "lnpc", (N, Wt), torch.float32)
-        last = a["text_layers"] - 1
-        for l in range(a["text_layers"]):
-            pre, tg = f"text_model.resblocks.{l}.", tag and f"{tag}{l}"
-            if l == last and self.text_used_rows_only:
-                # the model reads the last block's output at the EOT token of every caption only (CLIP/clip/model.py:343-354)
-                xr = self._used_rows_fwd(pre, _TEXT_NAMES, x, tg, M, Wt, ht, eot_rows, a["act"], 1e-5, attn_last)
-                self._ln(xr, "text_ln_final", 1e-5, lnf, tag and tag + ".lnf")
-                break
-            xo = self._f(f"{tag}.x{l + 1}", (M, Wt)) if tag else x
-            self._block_fwd(pre, _TEXT_NAMES, x, xo, tg, M, Wt, ht, a["act"], 1e-5, attn)
-            x = xo
-        else:
-            self._ln(x, "text_ln_final", 1e-5, lnf, tag and tag + ".lnf", rows=eot_rows)
+        self._ln(x, "text_ln_final", 1e-5, lnf, tag and tag + ".lnf", rows=None if packed else eot_rows)
         t = w(tag, ".t", "temb", (N, a["embed"]), torch.float32)
         K.gemm_small(lnf, self.P.p("text_projection"), t, M=N, N=a["embed"], K=Wt, sa=(Wt, 1), sb=(a["embed"], 1))
         return t
 
     def text_backward(self, dt, ids_dev, eot_rows, N, L, tok_sort=None):
         a = self.arch
-        Wt, E, M = a["text_width"], a["embed"], N * L
+        Wt, E = a["text_width"], a["embed"]
         lnf = self.buf["txt.lnf"]
         if self.requires_grad["text_projection"]:  # dproj[Wt,E] += lnf^T dt
             K.gemm_small(lnf, dt, self.P.g("text_projection"), M=Wt, N=E, K=N, sa=(1, Wt), sb=(E, 1), accumulate=True)
         dlnf = self._f("txt.dlnf", (N, Wt))
         K.gemm_small(dt, self.P.p("text_projection"), dlnf, M=N, N=Wt, K=E, sa=(E, 1), sb=(1, E))
-        pruned = self.text_used_rows_only
-        if pruned:  # the gradient of the last block's output exists at the EOT rows only: [N, Wt]
-            dx, dxb = self._f("txt.dx_r", (N, Wt)), self._b("txt.dxb_r", (N, Wt))
-            self._ln_bwd(dlnf, self.buf[f"txt{a['text_layers'] - 1}.xo_r"], "text_ln_final", "txt.lnf", dx, dx_bf16=dxb)
-        else:
-            dx = self._f("txt.dxA", (M, Wt), zero=True)
-            dxb = self._b("txt.dxbA", (M, Wt), zero=True)
-            self._ln_bwd(dlnf, self.buf[f"txt.x{a['text_layers']}"], "text_ln_final", "txt.lnf", dx, dx_bf16=dxb, rows=eot_rows)
-        for l in reversed(range(a["text_layers"])):
-            nx = "B" if (a["text_layers"] - l) % 2 == 1 else "A"
-            dxi = self._f("txt.dx" + nx, (M, Wt))
-            dxbi = self._b("txt.dxb" + nx, (M, Wt))
-            if pruned and l == a["text_layers"] - 1:
-                ht, hd = a["text_heads"], Wt // a["text_heads"]
-                rows64, pos = self._text_eot  # the forward's tensors (the batch's when it came through prepare_batch)
-                self._used_rows_bwd(f"text_model.resblocks.{l}.", _TEXT_NAMES, self.buf[f"txt.x{l}"], dx, dxb, dxi, dxbi, f"txt{l}",
-                                    "txt.s", M, Wt, ht, eot_rows, a["act"],
-                                    lambda qkv, datt, att, lse, delta, dqkv: K.attn_bwd_rowq(
-                                        qkv, pos, datt, att, lse, delta, dqkv, B=N, heads=ht, S=L, head_dim=hd))
-                dx, dxb = dxi, dxbi
-                continue
-            self._block_bwd(f"text_model.resblocks.{l}.", _TEXT_NAMES, self.buf[f"txt.x{l}"], dx, dxb, dxi, dxbi, f"txt{l}",
-                            M, Wt, a["text_heads"], N, L, True, a["act"], "txt.s")
-            dx, dxb = dxi, dxbi
+        packed = self.text_used_rows_only  # the gradient of the last block's output exists at the EOT rows only: [N, Wt]
+        dx, dxb = self._head_ln_bwd(dlnf, "text_ln_final", "txt", "txt.lnf", a["text_layers"], eot_rows, packed)
+        ht, hd = a["text_heads"], self.dh_text
+        pos = self._text_eot[1] if packed else None  # the forward's tensor (the batch's when it came through prepare_batch)
+        dx = self._blocks_bwd(
+            "text_model.resblocks.", _TEXT_NAMES, "txt", a["text_layers"], dx, dxb, ht, a["act"],
+            lambda qkv, *t: K.attn_bwd("full", qkv, *t, B=N, heads=ht, S=L, causal=True, head_dim=hd),
+            eot_rows if packed else None,
+            lambda qkv, *t: K.attn_bwd_rowq(qkv, pos, *t, B=N, heads=ht, S=L, head_dim=hd))
         if self.requires_grad["text_token_embedding.weight"] or self.requires_grad["text_positional_embedding"]:
             K.text_embed_bwd(dx, ids_dev, self.P.g("text_token_embedding.weight"), self.P.g("text_positional_embedding"),
                              N=N, L=L, tok_sort=tok_sort)
@@ -910,26 +952,18 @@ class Engine:
         K.gemm_small(lnc, self.P.p("video_model.proj"), pooled, M=B, N=E, K=W, sa=(W, 1), sb=(E, 1))
         return out, pooled
 
-    def video_backward(self, dout_b, keep_dev, B, T, d_pooled=None):
-        """dout_b: bf16 [B*S, E] grad of the projected tokens (B models: CLS rows carry the embedding grad; H/14: None
-        when there is no sorting loss); d_pooled: fp32 [B, E] grad of the pooled embedding (H/14 only)."""
-        a, B_ = self.arch, self.buf
-        W, E, p = a["width"], a["embed"], a["patch"]
-        n = keep_dev.shape[1]
-        S = 1 + T * n
-        M, Mp = B * S, B * T * n
-        rg = self.requires_grad
-        dln = self._b("vit.s.dln", (M, W))
-        # the residual-stream gradient in bf16 (self.bf16_grad_stream, see __init__): measured alone +1.4 % (the three LayerNorm
-        # backwards of a block move 3.2 instead of 4.6 GB) at 2.4x the error of the embedding-side gradients, which sit behind
-        # ln_pre's cancellation (5.8 % instead of 2.4 % rel-L2; profiles/r03_bf16_streams_ab.txt)
-        lowp = self.bf16_grad_stream
-        lowres = self.bf16_residual
-        cls = self.cls32   # hybrid stream: the CLS rows of the gradient chain in fp32 side arrays dxc / dsrc [B, W]
-        dxc = dsrc = None
+    def _vit_tail_bwd(self, dout_b, d_pooled, B, M):
+        """The backward of video_forward's two tails (all tokens / pooled + patches) -> dx, dxb: the fp32 / bf16 gradient of the
+        last block's output (dx None where only the bf16 one is kept), dxc: its fp32 CLS rows [B, W] in the hybrid stream, dxb8:
+        the e4m3 copy of dxb when ln_post's backward wrote one."""
+        a, B_, rg = self.arch, self.buf, self.requires_grad
+        W, E = a["width"], a["embed"]
+        lowp, cls = self.bf16_grad_stream, self.cls32
+        dxc = None
         dxb = self._b("vit.dxbA", (M, W))
         dx = None if (lowp and not self.pooled_tail) else self._f("vit.dxA", (M, W))
         if not self.pooled_tail:
+            dln = self._b("vit.s.dln", (M, W))
             if rg["video_model.proj"]:  # dproj[W,E] += lnpost^T dout
                 K.gemm_tn(B_["vit.lnpost"], dout_b, self.P.g("video_model.proj"), M=M, accumulate=True)
             K.gemm_nt(dout_b, self.P.w("video_model.proj"), dln, M=M)
@@ -938,33 +972,114 @@ class Engine:
             dxb8 = self._ln_bwd(dln, B_[f"vit.x{a['layers']}"], "video_model.ln_post", "vit.lnpost", dx, dx_bf16=dxb,
                                 fp8_for=f"video_model.transformer.resblocks.{a['layers'] - 1}.mlp.c_proj.weight",
                                 cls_x=B_[f"vit.xc{a['layers']}"] if cls else None, cls_dx=dxc)
-        else:
-            dxb8 = None
-            # patch-token branch (no LN): dproj += x^T dout, dx = dout proj^T (CLS rows of dout are zero)
-            if dout_b is not None:
-                if rg["video_model.proj"]:
-                    K.gemm_tn(B_["vit.xlast_b"], dout_b, self.P.g("video_model.proj"), M=M, accumulate=True)
-                K.gemm_nt(dout_b, self.P.w("video_model.proj"), dx, M=M)
-            else:
-                K.zero_(dx)
-            # pooled branch, fp32: dproj += lnc^T d_pooled, d_lnc = d_pooled proj^T, ln_post backward on the CLS rows only
-            lnc = B_["vit.lnpost_cls"]
+            return dx, dxb, dxc, dxb8
+        # patch-token branch (no LN): dproj += x^T dout, dx = dout proj^T (CLS rows of dout are zero)
+        if dout_b is not None:
             if rg["video_model.proj"]:
-                K.gemm_small(lnc, d_pooled, self.P.g("video_model.proj"), M=W, N=E, K=B, sa=(1, W), sb=(E, 1), accumulate=True)
-            dlnc = self._f("vit.s.dlnc", (B, W))
-            K.gemm_small(d_pooled, self.P.p("video_model.proj"), dlnc, M=B, N=W, K=E, sa=(E, 1), sb=(1, E))
-            if lowres:  # ln_post backward on the fp32 copy of the CLS rows, added into those rows of dx
-                # (hybrid stream: those rows of dx are zero -- no gradient enters the CLS rows through the patch-token branch -- so
-                # the LayerNorm's result IS the fp32 CLS chain's first value)
-                dxc = self._f("vit.dxcA" if cls else "vit.s.dxcls", (B, W))
-                self._ln_bwd(dlnc, B_["vit.xcls32"], "video_model.ln_post", "vit.lnpost", dxc)
-                K.rows_move("scatter_add", self.ctx["vid_rows"], full_f32=dx, packed_f32=dxc)
-            else:
-                self._ln_bwd(dlnc, B_[f"vit.x{a['layers']}"], "video_model.ln_post", "vit.lnpost", dx, res1=dx,
-                             rows=self.ctx["vid_rows"])
-            K.cast_f32_bf16(dx, dxb)
-        datt = self._b("vit.s.datt", (M, W))
+                K.gemm_tn(B_["vit.xlast_b"], dout_b, self.P.g("video_model.proj"), M=M, accumulate=True)
+            K.gemm_nt(dout_b, self.P.w("video_model.proj"), dx, M=M)
+        else:
+            K.zero_(dx)
+        # pooled branch, fp32: dproj += lnc^T d_pooled, d_lnc = d_pooled proj^T, ln_post backward on the CLS rows only
+        lnc = B_["vit.lnpost_cls"]
+        if rg["video_model.proj"]:
+            K.gemm_small(lnc, d_pooled, self.P.g("video_model.proj"), M=W, N=E, K=B, sa=(1, W), sb=(E, 1), accumulate=True)
+        dlnc = self._f("vit.s.dlnc", (B, W))
+        K.gemm_small(d_pooled, self.P.p("video_model.proj"), dlnc, M=B, N=W, K=E, sa=(E, 1), sb=(1, E))
+        if self.bf16_residual:  # ln_post backward on the fp32 copy of the CLS rows, added into those rows of dx
+            # (hybrid stream: those rows of dx are zero -- no gradient enters the CLS rows through the patch-token branch -- so
+            # the LayerNorm's result IS the fp32 CLS chain's first value)
+            dc = self._f("vit.dxcA" if cls else "vit.s.dxcls", (B, W))
+            self._ln_bwd(dlnc, B_["vit.xcls32"], "video_model.ln_post", "vit.lnpost", dc)
+            K.rows_move("scatter_add", self.ctx["vid_rows"], full_f32=dx, packed_f32=dc)
+            dxc = dc if cls else None
+        else:
+            self._ln_bwd(dlnc, B_[f"vit.x{a['layers']}"], "video_model.ln_post", "vit.lnpost", dx, res1=dx,
+                         rows=self.ctx["vid_rows"])
+        K.cast_f32_bf16(dx, dxb)
+        return dx, dxb, dxc, None
+
+    def _vit_block_bwd(self, l, dx, dxb, dxc, dxb8, B, T, n, par, wg, join):
+        """Space-time block l backward, the mirror of _vit_block: the gradient of its output (dx, dxb, dxc, dxb8 as _vit_tail_bwd
+        returns them) -> the same four for its input.  wg: what every weight gradient's _lin_bwd is told (side, defer); par: suffix
+        of the buffers those weight gradients read late; join(): called once all six are issued, before the block's input
+        gradient is written."""
+        a, B_ = self.arch, self.buf
+        pre, tg = f"video_model.transformer.resblocks.{l}.", f"vit{l}"
+        M, W = dxb.shape
+        # the residual-stream gradient in bf16 (self.bf16_grad_stream, see __init__): measured alone +1.4 % (the three LayerNorm
+        # backwards of a block move 3.2 instead of 4.6 GB) at 2.4x the error of the embedding-side gradients, which sit behind
+        # ln_pre's cancellation (5.8 % instead of 2.4 % rel-L2; profiles/r03_bf16_streams_ab.txt)
+        lowp = self.bf16_grad_stream
+        cls = self.cls32   # hybrid stream: the CLS rows of the gradient chain in fp32 side arrays dxc / dsrc [B, W]
+        dln, datt = self._b("vit.s.dln", (M, W)), self._b("vit.s.datt", (M, W))
         dsr = None if lowp else self._f("vit.s.dsres", (M, W))
+        dh = self._b("vit.s.dh" + par, (M, 4 * W))
+        dsrb = self._b("vit.s.dsresb" + par, (M, W))
+        dtrb = self._b("vit.s.dtresb" + par, (M, W))
+        dqkv = self._b("vit.s.dqkv" + par, (M, 3 * W))
+        dqkv_t = self._b("vit.s.dqkv_t" + par, (M, 3 * W)) if (wg["side"] or wg["defer"] is not None) else dqkv
+        # (e4m3 input gradients: the LayerNorm backward that produces an output gradient also writes its e4m3 copy, d*8)
+        self._lin_bwd(dxb, B_[tg + ".a"], pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", dh, M, dy8=dxb8,
+                      q8_for=pre + "mlp.c_fc.weight", gate_h=B_[tg + ".h"], gate_act=a["act"], **wg)
+        self._lin_bwd(dh, B_[tg + ".ln2"], pre + "mlp.c_fc.weight", pre + "mlp.c_fc.bias", dln, M, **wg)
+        dsrc = self._f("vit.s.dsrc", (B, W)) if cls else None
+        dsrb8 = self._ln_bwd(dln, B_[tg + ".s_res"], pre + "ln_2", tg + ".ln2", dsr, dx_bf16=dsrb, res1=dxb if lowp else dx,
+                             fp8_for=pre + "attn.proj.weight", cls_x=B_[tg + ".s_res_c"] if cls else None,
+                             cls_res1=dxc, cls_dx=dsrc)
+        # spatial attention branch
+        self._lin_bwd(dsrb, B_[tg + ".att_s"], pre + "attn.proj.weight", pre + "attn.proj.bias", datt, M, dy8=dsrb8, **wg)
+        self._st_attention_bwd(B_[tg + ".qkv_s"], B_[tg + ".att_s"], datt, B_[tg + ".lse_s"], dqkv, "space", B, T, n, "vit.s",
+                               q8_for=pre + "attn.qkv.weight")
+        self._lin_bwd(dqkv, B_[tg + ".ln1"], pre + "attn.qkv.weight", pre + "attn.qkv.bias", dln, M, **wg)
+        # the time-residual gradient is a side branch (t_res only feeds ln_1): it lives in bf16 only -- as the operand of
+        # the timeattn.proj GEMMs and as the bf16 residual term of the ln_3 backward
+        dtrb8 = self._ln_bwd(dln, B_[tg + ".t_res"], pre + "ln_1", tg + ".ln1", None, dx_bf16=dtrb,
+                             fp8_for=pre + "timeattn.proj.weight")
+        # temporal attention branch
+        self._lin_bwd(dtrb, B_[tg + ".att_t"], pre + "timeattn.proj.weight", pre + "timeattn.proj.bias", datt, M, dy8=dtrb8, **wg)
+        self._st_attention_bwd(B_[tg + ".qkv_t"], B_[tg + ".att_t"], datt, B_[tg + ".lse_t"], dqkv_t, "time", B, T, n, "vit.s",
+                               q8_for=pre + "timeattn.qkv.weight")
+        self._lin_bwd(dqkv_t, B_[tg + ".ln3"], pre + "timeattn.qkv.weight", pre + "timeattn.qkv.bias", dln, M, **wg)
+        join()
+        nx = self._ab(a["layers"], l)
+        dxbi = self._b("vit.dxb" + nx, (M, W))
+        dxi = None if lowp else self._f("vit.dx" + nx, (M, W))
+        # x feeds ln_3, the time residual and the space residual
+        dxci = self._f("vit.dxc" + nx, (B, W)) if cls else None
+        dxb8 = self._ln_bwd(dln, B_[f"vit.x{l}"], pre + "ln_3", tg + ".ln3", dxi, dx_bf16=dxbi, res1=dsrb if lowp else dsr, res2=dtrb,
+                            fp8_for=f"video_model.transformer.resblocks.{l - 1}.mlp.c_proj.weight" if l > 0 else None,
+                            cls_x=B_[f"vit.xc{l}"] if cls else None, cls_res1=dsrc, cls_dx=dxci)
+        return dxi, dxbi, dxci, dxb8
+
+    def _vit_embed_bwd(self, dx, keep_dev, B, T):
+        """The backward of _vit_embed: ln_pre -> token assembly -> conv weight gradient; the embedding stage's gradients are final."""
+        B_ = self.buf
+        W, n = self.arch["width"], keep_dev.shape[1]
+        M, Mp = B * (1 + T * n), B * T * n
+        dtok = self._f("vit.dtok", (M, W))
+        self._ln_bwd(dx, B_["vit.tok"], "video_model.ln_pre", "vit.lnpre", dtok)
+        dpatch = self._b("vit.dpatch", (Mp, W))
+        K.vit_assemble_bwd(dtok, keep_dev, dpatch, self.P.g("video_model.class_embedding"),
+                           self.P.g("video_model.positional_embedding"), self.P.g("video_model.temporal_embedding"),
+                           B=B, T=T, n=n)
+        if self.requires_grad["video_model.conv1.weight"]:
+            if self.P.conv_pad is None:
+                K.gemm_tn(dpatch, B_["vit.im2col"], self.P.g2d("video_model.conv1.weight"), M=Mp, accumulate=True)
+            else:  # K padded to 64: wgrad into a [W, Kpad] scratch, the 588 real columns are folded into the gradient
+                scr = self._f("vit.s.dconv", (W, self.P.conv_kpad))
+                K.gemm_tn(dpatch, B_["vit.im2col"], scr, M=Mp, accumulate=False)
+                K.add_rows_f32(self.P.g2d("video_model.conv1.weight"), scr)
+        self._ready("video_model.class_embedding", "video_model.positional_embedding", "video_model.proj",
+                    "video_model.temporal_embedding", "video_model.conv1.", "video_model.ln_pre.")
+        self._ready("video_model.ln_post.")
+
+    def video_backward(self, dout_b, keep_dev, B, T, d_pooled=None):
+        """dout_b: bf16 [B*S, E] grad of the projected tokens (B models: CLS rows carry the embedding grad; H/14: None
+        when there is no sorting loss); d_pooled: fp32 [B, E] grad of the pooled embedding (H/14 only)."""
+        n = keep_dev.shape[1]
+        M = B * (1 + T * n)
+        dx, dxb, dxc, dxb8 = self._vit_tail_bwd(dout_b, d_pooled, B, M)
         # the weight gradients of the blocks on the side stream: the output gradients they read (dh, dsrb, dqkv of the space and of
         # the time branch, dtrb, and the block's own dxb) then live in buffers of the layer's parity, and the chain joins the side
         # stream's work of layer l + 1 before layer l overwrites the first of them (its ln_3 backward writes the dxb that layer
@@ -976,184 +1091,62 @@ class Engine:
         cur = torch.cuda.current_stream(self.dev)
         if side:
             self._side()  # the stream exists before anything records on it or joins it (all weights frozen: no launch creates it)
-        for l in reversed(range(a["layers"])):
-            pre, tg = f"video_model.transformer.resblocks.{l}.", f"vit{l}"
-            x_in = B_[f"vit.x{l}"]
-            par = str(l % 2) if side else ""
+        for l in reversed(range(self.arch["layers"])):
             defer = [] if grouped else None
-            dh = self._b("vit.s.dh" + par, (M, 4 * W))
-            dsrb = self._b("vit.s.dsresb" + par, (M, W))
-            dtrb = self._b("vit.s.dtresb" + par, (M, W))
-            dqkv = self._b("vit.s.dqkv" + par, (M, 3 * W))
-            dqkv_t = self._b("vit.s.dqkv_t" + par, (M, 3 * W)) if (side or grouped) else dqkv
-            # (e4m3 input gradients: the LayerNorm backward that produces an output gradient also writes its e4m3 copy, d*8)
-            self._lin_bwd(dxb, B_[tg + ".a"], pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", dh, M, dy8=dxb8, side=side, defer=defer,
-                          q8_for=pre + "mlp.c_fc.weight", gate_h=B_[tg + ".h"], gate_act=a["act"])
-            self._lin_bwd(dh, B_[tg + ".ln2"], pre + "mlp.c_fc.weight", pre + "mlp.c_fc.bias", dln, M, side=side, defer=defer)
-            if cls:
-                dsrc = self._f("vit.s.dsrc", (B, W))
-            dsrb8 = self._ln_bwd(dln, B_[tg + ".s_res"], pre + "ln_2", tg + ".ln2", dsr, dx_bf16=dsrb, res1=dxb if lowp else dx,
-                                 fp8_for=pre + "attn.proj.weight", cls_x=B_[tg + ".s_res_c"] if cls else None,
-                                 cls_res1=dxc if cls else None, cls_dx=dsrc)
-            # spatial attention branch
-            self._lin_bwd(dsrb, B_[tg + ".att_s"], pre + "attn.proj.weight", pre + "attn.proj.bias", datt, M, dy8=dsrb8, side=side,
-                          defer=defer)
-            self._st_attention_bwd(B_[tg + ".qkv_s"], B_[tg + ".att_s"], datt, B_[tg + ".lse_s"], dqkv, "space", B, T, n, "vit.s",
-                                   q8_for=pre + "attn.qkv.weight")
-            self._lin_bwd(dqkv, B_[tg + ".ln1"], pre + "attn.qkv.weight", pre + "attn.qkv.bias", dln, M, side=side, defer=defer)
-            # the time-residual gradient is a side branch (t_res only feeds ln_1): it lives in bf16 only -- as the operand of
-            # the timeattn.proj GEMMs and as the bf16 residual term of the ln_3 backward
-            dtrb8 = self._ln_bwd(dln, B_[tg + ".t_res"], pre + "ln_1", tg + ".ln1", None, dx_bf16=dtrb,
-                                 fp8_for=pre + "timeattn.proj.weight")
-            # temporal attention branch
-            self._lin_bwd(dtrb, B_[tg + ".att_t"], pre + "timeattn.proj.weight", pre + "timeattn.proj.bias", datt, M, dy8=dtrb8,
-                          side=side, defer=defer)
-            self._st_attention_bwd(B_[tg + ".qkv_t"], B_[tg + ".att_t"], datt, B_[tg + ".lse_t"], dqkv_t, "time", B, T, n, "vit.s",
-                                   q8_for=pre + "timeattn.qkv.weight")
-            self._lin_bwd(dqkv_t, B_[tg + ".ln3"], pre + "timeattn.qkv.weight", pre + "timeattn.qkv.bias", dln, M, side=side, defer=defer)
-            if grouped:  # the block's six weight gradients (+ bias gradients) in one launch, their partials in one reduce launch:
-                self._tn_group_run(l, defer)  # every output gradient they read is still intact (dqkv of the two branches apart)
-            if side:
-                side_done[l] = torch.cuda.Event()
-                side_done[l].record(self._wg_stream)
-                if l + 1 in side_done:  # layer l + 1's weight gradients are final: its dxb may be overwritten, its range may travel
-                    cur.wait_event(side_done.pop(l + 1))
-                    self._ready(f"video_model.transformer.resblocks.{l + 1}.")
-            nx = "B" if (a["layers"] - l) % 2 == 1 else "A"
-            dxbi = self._b("vit.dxb" + nx, (M, W))
-            dxi = None if lowp else self._f("vit.dx" + nx, (M, W))
-            # x feeds ln_3, the time residual and the space residual
-            dxci = self._f("vit.dxc" + nx, (B, W)) if cls else None
-            dxb8 = self._ln_bwd(dln, x_in, pre + "ln_3", tg + ".ln3", dxi, dx_bf16=dxbi, res1=dsrb if lowp else dsr, res2=dtrb,
-                                fp8_for=f"video_model.transformer.resblocks.{l - 1}.mlp.c_proj.weight" if l > 0 else None,
-                                cls_x=B_[f"vit.xc{l}"] if cls else None, cls_res1=dsrc, cls_dx=dxci)
-            dx, dxb, dxc = dxi, dxbi, dxci
+
+            def join(l=l, defer=defer):
+                if grouped:  # the block's six weight gradients (+ bias gradients) in one launch, their partials in one reduce launch:
+                    self._tn_group_run(l, defer)  # every output gradient they read is still intact (dqkv of the two branches apart)
+                if side:
+                    side_done[l] = torch.cuda.Event()
+                    side_done[l].record(self._wg_stream)
+                    if l + 1 in side_done:  # layer l + 1's weight gradients are final: its dxb may be overwritten, its range may travel
+                        cur.wait_event(side_done.pop(l + 1))
+                        self._ready(f"video_model.transformer.resblocks.{l + 1}.")
+
+            dx, dxb, dxc, dxb8 = self._vit_block_bwd(l, dx, dxb, dxc, dxb8, B, T, n, str(l % 2) if side else "",
+                                                     dict(side=side, defer=defer), join)
             if not side:
-                self._ready(pre)
+                self._ready(f"video_model.transformer.resblocks.{l}.")
         if side:
             cur.wait_stream(self._wg_stream)
             self._ready("video_model.transformer.resblocks.0.")
-        dtok = self._f("vit.dtok", (M, W))
-        self._ln_bwd(dxb if lowp else dx, B_["vit.tok"], "video_model.ln_pre", "vit.lnpre", dtok)
-        dpatch = self._b("vit.dpatch", (Mp, W))
-        K.vit_assemble_bwd(dtok, keep_dev, dpatch, self.P.g("video_model.class_embedding"),
-                           self.P.g("video_model.positional_embedding"), self.P.g("video_model.temporal_embedding"),
-                           B=B, T=T, n=n)
-        if rg["video_model.conv1.weight"]:
-            if self.P.conv_pad is None:
-                K.gemm_tn(dpatch, B_["vit.im2col"], self.P.g2d("video_model.conv1.weight"), M=Mp, accumulate=True)
-            else:  # K padded to 64: wgrad into a [W, Kpad] scratch, the 588 real columns are folded into the gradient
-                scr = self._f("vit.s.dconv", (W, self.P.conv_kpad))
-                K.gemm_tn(dpatch, B_["vit.im2col"], scr, M=Mp, accumulate=False)
-                K.add_rows_f32(self.P.g2d("video_model.conv1.weight"), scr)
-        self._ready("video_model.class_embedding", "video_model.positional_embedding", "video_model.proj",
-                    "video_model.temporal_embedding", "video_model.conv1.", "video_model.ln_pre.")
-        self._ready("video_model.ln_post.")
+        self._vit_embed_bwd(dxb if self.bf16_grad_stream else dx, keep_dev, B, T)
 
     # ------------------------------------------------------------------ sort head
+    # SortTransformer.forward_features normalises and classifies x[:, x_len:] only (v2/model/sort_transformer.py:131-141): of the last
+    # block's [B, Sv + NT, E] output the NT transcript rows of every sample are read, the Sv video rows never are, and no gradient
+    # enters them.  So the LAST block runs on those R = B * NT rows (_block_fwd with rows): same loss, same gradient for every
+    # parameter and every input row as the dense evaluation (tests/test_model_gpu.py::test_sort_head_used_rows_only);
+    # arch["sort_used_rows_only"] = False evaluates the block densely like the reference does.
     def sort_forward(self, out, text_before, B, S, NT):
         a = self.arch
-        E, hs = self.sort_width, a["sort_heads"]
+        E, hs, depth = self.sort_width, a["sort_heads"], a["sort_depth"]
         off = 1 if self.pooled_tail else 0  # H/14 hands the sort head the patch tokens without CLS
         Sv = S - off
         So = Sv + NT
-        Mo = B * So
-        xs = self._f("srt.x0", (Mo, E))
+        xs = self._f("srt.x0", (B * So, E))
         K.sort_assemble(out, text_before, self.P.p("pred_model.type_embed").view(2, E), xs, B=B, S=S, off=off, Sv=Sv, NT=NT)
-        x = xs
-        rows = self.ctx["sort_rows"]
+        rows, packed = self.ctx["sort_rows"], self.sort_used_rows_only and NT <= 16
+        x = self._blocks_fwd(
+            "pred_model.blocks.", _SORT_NAMES, xs, "srt", depth, hs, "gelu", 1e-6,
+            lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hs, S=So, causal=False, head_dim=E // hs),
+            rows if packed else None,
+            lambda qkv, att, lse: K.attn_fwd_tail(qkv, att, lse, B=B, heads=hs, S=So, nq=NT, head_dim=E // hs))
         nf = self._f("srt.nf", (B * NT, E))
-        last = a["sort_depth"] - 1
-        attn = lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hs, S=So, causal=False, head_dim=E // hs)  # noqa: E731
-        for l in range(a["sort_depth"]):
-            if l == last and self.sort_used_rows_only and NT <= 16:
-                # the head reads the last block's output at the NT transcript rows only (sort_transformer.py:131-141)
-                xr = self._sort_last_fwd(f"pred_model.blocks.{l}.", x, f"srt{l}", Mo, E, hs, B, So, NT)
-                self._ln(xr, "pred_model.norm", 1e-6, nf, "srt.norm")
-                break
-            xo = self._f(f"srt.x{l + 1}", (Mo, E))
-            self._block_fwd(f"pred_model.blocks.{l}.", _SORT_NAMES, x, xo, f"srt{l}", Mo, E, hs, "gelu", 1e-6, attn)
-            x = xo
-        else:
-            self._ln(x, "pred_model.norm", 1e-6, nf, "srt.norm", rows=rows)
+        self._ln(x, "pred_model.norm", 1e-6, nf, "srt.norm", rows=None if packed else rows)
         pred = self._f("srt.pred", (B * NT, a["n_trans"]))
         C = a["n_trans"]
         K.gemm_small(nf, self.P.p("pred_model.head.weight"), pred, M=B * NT, N=C, K=E, sa=(E, 1), sb=(1, E),
                      bias=self.P.p("pred_model.head.bias"))
         return pred
 
-    # ---- the LAST block of the sort head on the rows the model uses.  SortTransformer.forward_features normalises and classifies
-    # x[:, x_len:] only (v2/model/sort_transformer.py:131-141): of the last block's [B, Sv + NT, E] output the NT transcript rows of
-    # every sample are read, the Sv video rows never are, and no gradient enters them.  Keys and values of the block's attention
-    # still come from every token, so LayerNorm 1 and the qkv projection run on all rows; the attention output, the output
-    # projection, the residual, LayerNorm 2 and the MLP are computed for the R = B * NT used rows, and in the backward dQ exists for
-    # those rows only while dK / dV (and through them the gradient of every input row) are dense.  Same loss, same gradient for
-    # every parameter and every input row as the dense evaluation (tests/test_model_gpu.py::test_sort_head_used_rows_only);
-    # arch["sort_used_rows_only"] = False evaluates the block densely like the reference does.
-    def _sort_last_fwd(self, pre, x_in, tag, Mo, E, heads, B, So, NT):
-        return self._used_rows_fwd(pre, _SORT_NAMES, x_in, tag, Mo, E, heads, self.ctx["sort_rows"], "gelu", 1e-6,
-                                   lambda qkv, att, lse: K.attn_fwd_tail(qkv, att, lse, B=B, heads=heads, S=So, nq=NT, head_dim=E // heads))
-
-    def _sort_last_bwd(self, pre, x_in, dxr, dxbr, dx_in, dxb_in, tag, Mo, E, heads, B, So, NT):
-        def attn_bwd(qkv, datt, att, lse, delta, dqkv):
-            K.zero_cols_bf16(dqkv, E)  # dQ of the rows that are no queries (dK / dV are written for every row)
-            K.attn_bwd_tail(qkv, datt, att, lse, delta, dqkv, B=B, heads=heads, S=So, nq=NT, head_dim=E // heads)
-        self._used_rows_bwd(pre, _SORT_NAMES, x_in, dxr, dxbr, dx_in, dxb_in, tag, "srt.s", Mo, E, heads, self.ctx["sort_rows"],
-                            "gelu", attn_bwd)
-
-    # A pre-LN block whose output the model reads at R rows only (rows64: their token rows), and into whose other output rows no
-    # gradient enters.  LayerNorm 1 and the qkv projection stay dense (keys / values of every token); the attention output
-    # (attn_fwd: a query-restricted kernel writing the used rows of `att`), the output projection, the residual, LayerNorm 2 and the
-    # MLP are computed for the R used rows; backward: dQ for those rows, dK / dV -- and through them the gradient of every input
-    # row -- dense.  Returns the block output at the used rows, [R, Wd] fp32.  tag None: forward-only, as in _block_fwd.
-    def _used_rows_fwd(self, pre, nm, x_in, tag, M, Wd, heads, rows32, act, eps, attn_fwd):
-        R, w, f32 = rows32.numel(), self._w, torch.float32
-        ln1 = w(tag, ".ln1", "ln", (M, Wd))
-        self._ln(x_in, pre + nm["ln1"], eps, ln1, tag and tag + ".ln1")
-        qkv = w(tag, ".qkv", "qkv", (M, 3 * Wd))
-        self._lin(ln1, pre + nm["qkv_w"], pre + nm["qkv_b"], qkv, M)
-        att = w(tag, ".att", "att", (M, Wd))
-        attn_fwd(qkv, att, self._f(tag + ".lse", (M, heads)) if tag else None)
-        att_r, x_r = w(tag, ".att_r", "att_r", (R, Wd)), w(tag, ".x_r", "x_r", (R, Wd), f32)
-        K.rows_move("gather", rows32, full_bf16=att, packed_bf16=att_r)   # (row gathers of R x Wd elements)
-        K.rows_move("gather", rows32, full_f32=x_in, packed_f32=x_r)
-        mid = w(tag, ".mid", "s", (R, Wd), f32)
-        self._lin(att_r, pre + nm["o_w"], pre + nm["o_b"], mid, R, residual=x_r)
-        ln2 = w(tag, ".ln2", "lnc", (R, Wd))
-        self._ln(mid, pre + nm["ln2"], eps, ln2, tag and tag + ".ln2")
-        h, hact = (self._b(tag + ".h", (R, 4 * Wd)) if tag else None), w(tag, ".a", "h", (R, 4 * Wd))
-        self._lin(ln2, pre + nm["fc_w"], pre + nm["fc_b"], hact, R, act=act, preact=h)
-        xo = w(tag, ".xo_r", "xoc", (R, Wd), f32)
-        self._lin(hact, pre + nm["pj_w"], pre + nm["pj_b"], xo, R, residual=mid)
-        return xo
-
-    def _used_rows_bwd(self, pre, nm, x_in, dxr, dxbr, dx_in, dxb_in, tag, scr, M, Wd, heads, rows32, act, attn_bwd):
-        """dxr / dxbr: fp32 / bf16 gradient of the block output at the R used rows; writes the gradient of every input row."""
-        R, B_ = rows32.numel(), self.buf
-        dh, dln = self._b(scr + ".dh_r", (R, 4 * Wd)), self._b(scr + ".dln_r", (R, Wd))
-        self._lin_bwd(dxbr, B_[tag + ".a"], pre + nm["pj_w"], pre + nm["pj_b"], dh, R, gate_h=B_[tag + ".h"], gate_act=act)
-        self._lin_bwd(dh, B_[tag + ".ln2"], pre + nm["fc_w"], pre + nm["fc_b"], dln, R)
-        dmid, dmidb = self._f(scr + ".dmid_r", (R, Wd)), self._b(scr + ".dmidb_r", (R, Wd))
-        self._ln_bwd(dln, B_[tag + ".mid"], pre + nm["ln2"], tag + ".ln2", dmid, dx_bf16=dmidb, res1=dxr)
-        datt_r = self._b(scr + ".datt_r", (R, Wd))
-        self._lin_bwd(dmidb, B_[tag + ".att_r"], pre + nm["o_w"], pre + nm["o_b"], datt_r, R)
-        datt = self._b(scr + ".datt", (M, Wd))            # token-row indexed like the attention output; only the R rows are read
-        K.rows_move("scatter", rows32, full_bf16=datt, packed_bf16=datt_r)
-        dqkv = self._b(scr + ".dqkv", (M, 3 * Wd))
-        delta = self._f(scr + ".delta", (M, heads))
-        attn_bwd(B_[tag + ".qkv"], datt, B_[tag + ".att"], B_[tag + ".lse"], delta, dqkv)
-        dlnf = self._b(scr + ".dln", (M, Wd))
-        self._lin_bwd(dqkv, B_[tag + ".ln1"], pre + nm["qkv_w"], pre + nm["qkv_b"], dlnf, M)
-        self._ln_bwd(dlnf, x_in, pre + nm["ln1"], tag + ".ln1", dx_in, dx_bf16=dxb_in)
-        # the residual path: + dmid at the used rows (fp32 sum, bf16 copy refreshed for those rows)
-        K.rows_move("scatter_add", rows32, full_f32=dx_in, full_bf16=dxb_in, packed_f32=dmid)
-
     def sort_backward(self, dpred, B, S, NT):
         """-> fp32 grad of the sort-head input xs [B*So, E]."""
         a, B_ = self.arch, self.buf
-        E, hs, C = self.sort_width, a["sort_heads"], a["n_trans"]
+        E, hs, C, depth = self.sort_width, a["sort_heads"], a["n_trans"], a["sort_depth"]
         So = S - (1 if self.pooled_tail else 0) + NT
-        Mo, R = B * So, B * NT
+        R = B * NT
         nf = B_["srt.nf"]
         K.gemm_small(dpred, nf, self.P.g("pred_model.head.weight"), M=C, N=E, K=R, sa=(1, C), sb=(E, 1), accumulate=True)
         ones = self._ones(R)
@@ -1161,25 +1154,16 @@ class Engine:
                      accumulate=True)
         dnf = self._f("srt.dnf", (R, E))
         K.gemm_small(dpred, self.P.p("pred_model.head.weight"), dnf, M=R, N=E, K=C, sa=(C, 1), sb=(E, 1))
-        pruned = self.sort_used_rows_only and NT <= 16
-        if pruned:  # gradient of the last block's output exists at the transcript rows only: [R, E]
-            dx, dxb = self._f("srt.dx_r", (R, E)), self._b("srt.dxb_r", (R, E))
-            self._ln_bwd(dnf, B_[f"srt{a['sort_depth'] - 1}.xo_r"], "pred_model.norm", "srt.norm", dx, dx_bf16=dxb)
-        else:
-            dx = self._f("srt.dxA", (Mo, E), zero=True)
-            dxb = self._b("srt.dxbA", (Mo, E), zero=True)
-            self._ln_bwd(dnf, B_[f"srt.x{a['sort_depth']}"], "pred_model.norm", "srt.norm", dx, dx_bf16=dxb, rows=self.ctx["sort_rows"])
-        for l in reversed(range(a["sort_depth"])):
-            nx = "B" if (a["sort_depth"] - l) % 2 == 1 else "A"
-            dxi, dxbi = self._f("srt.dx" + nx, (Mo, E)), self._b("srt.dxb" + nx, (Mo, E))
-            if pruned and l == a["sort_depth"] - 1:
-                self._sort_last_bwd(f"pred_model.blocks.{l}.", B_[f"srt.x{l}"], dx, dxb, dxi, dxbi, f"srt{l}", Mo, E, hs, B, So, NT)
-                dx, dxb = dxi, dxbi
-                continue
-            self._block_bwd(f"pred_model.blocks.{l}.", _SORT_NAMES, B_[f"srt.x{l}"], dx, dxb, dxi, dxbi, f"srt{l}", Mo, E,
-                            hs, B, So, False, "gelu", "srt.s")
-            dx, dxb = dxi, dxbi
-        return dx
+        rows, packed = self.ctx["sort_rows"], self.sort_used_rows_only and NT <= 16  # (gradient at the transcript rows only: [R, E])
+        dx, dxb = self._head_ln_bwd(dnf, "pred_model.norm", "srt", "srt.norm", depth, rows, packed)
+
+        def attn_bwd_rows(qkv, datt, att, lse, delta, dqkv):
+            K.zero_cols_bf16(dqkv, E)  # dQ of the rows that are no queries (dK / dV are written for every row)
+            K.attn_bwd_tail(qkv, datt, att, lse, delta, dqkv, B=B, heads=hs, S=So, nq=NT, head_dim=E // hs)
+        return self._blocks_bwd(
+            "pred_model.blocks.", _SORT_NAMES, "srt", depth, dx, dxb, hs, "gelu",
+            lambda qkv, *t: K.attn_bwd("full", qkv, *t, B=B, heads=hs, S=So, causal=False, head_dim=E // hs),
+            rows if packed else None, attn_bwd_rows)
 
     # ------------------------------------------------------------------ whole model
     def _clip_to_device(self, video: torch.Tensor) -> torch.Tensor:
@@ -1426,7 +1410,7 @@ class Engine:
             self._ready("text_")
 
     # ------------------------------------------------------------------ forward-only encoders (feature extraction, zero-shot)
-    # The two passes of the forward.  There is ONE forward wiring (_ln, _lin, _st_attention_fwd, _block_fwd, _used_rows_fwd,
+    # The two passes of the forward.  There is ONE forward wiring (_ln, _lin, _st_attention_fwd, _block_fwd, _blocks_fwd,
     # _text_tower, _vit_embed, _vit_block_head, _vit_block); the training step and the encoders below both run it, and the `tag`
     # argument is all that tells them apart:
     #   tag = a name   every buffer is the named tensor tag + name of self.buf (_b), one per layer, kept for the backward; the

@@ -180,8 +180,7 @@ class EngineV1(Engine):
         dx = self._f("txt.dxA", (M, Wt), zero=True)
         K.rows_gather(dbefore, cls_rows, dx, scatter_add=True)  # only the [CLS] rows of the last hidden state are consumed
         for l in reversed(range(a["text_layers"])):
-            nx = "B" if (a["text_layers"] - l) % 2 == 1 else "A"
-            dxi = self._f("txt.dx" + nx, (M, Wt))
+            dxi = self._f("txt.dx" + self._ab(a["text_layers"], l), (M, Wt))
             self._pln_bwd(f"text_model.transformer.layer.{l}.", B_[f"txt.x{l}b"], dx, dxi, f"txt{l}", M, N, L, kv_len, layer=l)
             dx = dxi
         if self._drop_active > 0.0:  # through the embedding dropout
@@ -208,12 +207,9 @@ class EngineV1(Engine):
         tok = self._f("vit.x0", (M, W))
         K.vit_assemble(pe, P.p("video_model.cls_token").view(W), P.p("video_model.pos_embed").view(-1, W),
                        P.p("video_model.temporal_embed").view(-1, W), keep, tok, B=B, T=tubes, n=n)
-        x, hv = tok, a["heads"]
-        attn = lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hv, S=S, causal=False, head_dim=W // hv)  # noqa: E731
-        for l in range(a["layers"]):
-            xo = self._f(f"vit.x{l + 1}", (M, W))
-            self._block_fwd(f"video_model.blocks.{l}.", _VIT_NAMES, x, xo, f"vit{l}", M, W, hv, "gelu", 1e-6, attn)
-            x = xo
+        hv = a["heads"]
+        x = self._blocks_fwd("video_model.blocks.", _VIT_NAMES, tok, "vit", a["layers"], hv, "gelu", 1e-6,
+                             lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hv, S=S, causal=False, head_dim=W // hv))
         out = self._f("vit.out", (M, W))
         self._ln(x, "video_model.norm", 1e-6, out, "vit.norm")
         cls = self._f("vit.cls", (B, W))
@@ -231,13 +227,10 @@ class EngineV1(Engine):
         M, Mp = B * S, B * tubes * n
         dx, dxb = self._f("vit.dxA", (M, W)), self._b("vit.dxbA", (M, W))
         self._ln_bwd(dout_b, B_[f"vit.x{a['layers']}"], "video_model.norm", "vit.norm", dx, dx_bf16=dxb)
-        for l in reversed(range(a["layers"])):
-            nx = "B" if (a["layers"] - l) % 2 == 1 else "A"
-            dxi, dxbi = self._f("vit.dx" + nx, (M, W)), self._b("vit.dxb" + nx, (M, W))
-            self._block_bwd(f"video_model.blocks.{l}.", _VIT_NAMES, B_[f"vit.x{l}"], dx, dxb, dxi, dxbi, f"vit{l}", M, W, a["heads"],
-                            B, S, False, "gelu", "vit.s")
-            dx, dxb = dxi, dxbi
-            self._ready(f"video_model.blocks.{l}.")
+        hv = a["heads"]
+        dx = self._blocks_bwd("video_model.blocks.", _VIT_NAMES, "vit", a["layers"], dx, dxb, hv, "gelu",
+                              lambda qkv, *t: K.attn_bwd("full", qkv, *t, B=B, heads=hv, S=S, causal=False, head_dim=W // hv),
+                              after=lambda l: self._ready(f"video_model.blocks.{l}."))
         dpatch = self._b("vit.dpatch", (Mp, W))
         K.vit_assemble_bwd(dx, keep, dpatch, P.g("video_model.cls_token").view(W), P.g("video_model.pos_embed").view(-1, W),
                            P.g("video_model.temporal_embed").view(-1, W), B=B, T=tubes, n=n)
