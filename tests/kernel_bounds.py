@@ -388,3 +388,178 @@ def ln_bwd_check(dy, x, mean, rstd, gamma, *, dx=None, dx_bf16=None, res1=None, 
             ref = ref + (init.double() if init is not None else 0.0)
             col_worst[name] = assert_rows_within(got, ref, col_tol, what=f"{what}: {name} (per column)")
     return worst
+
+
+# ------------------------------------------------------------------------------------------------ attention references
+# per (row, head) relative L2 of the error beyond the bf16 rounding of each output value (rows_rel with out_dtype), calibrated on
+# the MI355X.  Worst measured over the short-sequence and divided tests: out 2.25e-3, dq 3.81e-3, dk 3.24e-3, dv 3.15e-3; each tol
+# >= 3x that and under the whole-tensor gates (8e-3 forward, 2e-2 backward).  The streaming FULL, kv_len, dropout, tail, one-row and
+# split divided kernels of tests/test_attention_rows_gpu.py, against float64 on the output and lse2 they read, stay under the same
+# table without a case of their own: worst out 2.58e-3 (kv_len dropout), dq 3.22e-3 (split, B/16 time), dk 3.03e-3, dv 2.87e-3
+# (profiles/r09_attention_rows_bounds.txt); the bf16 roundings of P and dS alone give 2.9e-3 .. 4.2e-3 in float64
+# (tests/test_kernel_bounds_cpu.py::test_bf16_rounding_emulation_sits_inside_the_attention_tolerances)
+ATTN_ROW_TOL = {"out": 7e-3, "dq": 1.2e-2, "dk": 1.2e-2, "dv": 1.2e-2}
+LSE2_TOL = 1e-3           # absolute, log2 domain: the gate test_short_sequence_attention holds between two kernels
+# the divided geometries of the step (tests/test_kernels_gpu.py, tests/test_attention_rows_gpu.py)
+DIVIDED = {"B16": dict(B=24, T=8, n=98, heads=12, dh=64), "H14": dict(B=2, T=16, n=76, heads=16, dh=80)}
+LOG2E = 1.4426950408889634
+LN2 = math.log(2.0)
+
+
+def bound_line(name, v):
+    """print the worst |err| / bound and the worst used share of the bounds' accumulation terms (Report.worst_acc)"""
+    print(f"BOUND {name} {v:.4g} acc {pop_acc_worst():.4g}")
+    return v
+
+
+def rows_check(got, ref, tol, heads, B, S, what):
+    """every (row, head) slice, and the CLS rows (row 0 of every clip: the cross-group merges / sums) on their own"""
+    w = assert_rows_within(got, ref, tol, groups=heads, what=what, out_dtype=torch.bfloat16)
+    cls = torch.arange(B, device=got.device) * S
+    wc = assert_rows_within(got[cls], ref[cls], tol, groups=heads, what=what + " (CLS rows)", out_dtype=torch.bfloat16)
+    return w, wc
+
+
+def _heads_of(x, heads, dh):
+    """[B, S, heads * dh] -> float64 [B, heads, S, dh]"""
+    B, S, _ = x.shape
+    return x.double().reshape(B, S, heads, dh).permute(0, 2, 1, 3)
+
+
+def _merged(x):
+    """[B, heads, S, dh] -> [B, S, heads * dh]"""
+    B, h, S, dh = x.shape
+    return x.permute(0, 2, 1, 3).reshape(B, S, h * dh)
+
+
+def attn_allowed(B, S, device, *, causal=False, kv_len=None, allowed=None):
+    """bool [B, 1, S, S]: query row q of sequence b attends key k.  causal: k <= q; kv_len (int [B]): k < clamp(kv_len[b], 1, S);
+    allowed: a bool [S, S] relation of its own (the divided geometries: divided_allowed)"""
+    ok = torch.ones(B, 1, S, S, dtype=torch.bool, device=device)
+    if causal:
+        ok = ok & torch.ones(S, S, dtype=torch.bool, device=device).tril()
+    if kv_len is not None:
+        L = kv_len.to(device).long().clamp(1, S)
+        ok = ok & (torch.arange(S, device=device)[None, :] < L[:, None])[:, None, None, :]
+    if allowed is not None:
+        ok = ok & allowed.to(device)
+    return ok
+
+
+def _drop_factor(drop_mask, p, like):
+    """the factor dropout puts on the probabilities: 1 / (1 - p) where drop_mask is nonzero (kept), 0 where it is zero"""
+    if drop_mask is None:
+        return None
+    return (drop_mask.to(like.device) != 0).to(like.dtype) / (1.0 - p)
+
+
+def _bf16r(t):
+    return t.bfloat16().double()
+
+
+def attn_fwd_ref(qkv, heads, dh, *, causal=False, kv_len=None, drop_mask=None, p=0.0, allowed=None, emulate=False):
+    """softmax attention of a packed [B, S, 3W] (q | k | v) tensor in float64 -> (out [B, S, W], lse2 [B, S, heads],
+    P [B, heads, S, S]).  lse2: log2-domain log-sum-exp of the UNdropped scores, scale dh**-0.5 * log2(e); masked keys have
+    probability 0; dropout multiplies the probabilities after the softmax (drop_mask [B, heads, S, S]: nonzero = kept).
+    Differentiable (attn_autograd).  emulate: P rounded to bf16 before P.V, the one rounding the algorithm cannot avoid."""
+    B, S, W3 = qkv.shape
+    W = W3 // 3
+    q, k, v = (_heads_of(qkv[..., i * W:(i + 1) * W], heads, dh) for i in range(3))
+    ok = attn_allowed(B, S, qkv.device, causal=causal, kv_len=kv_len, allowed=allowed)
+    s2 = (q @ k.transpose(-1, -2)) * (dh ** -0.5 * LOG2E)
+    s2 = s2.masked_fill(~ok, float("-inf"))
+    lse2 = torch.logsumexp(s2 * LN2, -1) / LN2
+    P = torch.exp2(s2 - lse2[..., None])
+    f = _drop_factor(drop_mask, p, P)
+    Pd = P if f is None else P * f
+    if emulate:
+        Pd = _bf16r(Pd)
+    return _merged(Pd @ v), lse2.permute(0, 2, 1), P
+
+
+def attn_autograd(qkv, dO, heads, dh, **kw):
+    """float64 autograd of attn_fwd_ref -> (out, dqkv)"""
+    x = qkv.double().clone().requires_grad_(True)
+    out, _, _ = attn_fwd_ref(x, heads, dh, **kw)
+    out.backward(dO.double())
+    return out.detach(), x.grad
+
+
+def attn_bwd_same_inputs(qkv, dO, O_read, lse2_read, heads, dh, *, causal=False, kv_len=None, drop_mask=None, p=0.0, q_rows=None,
+                         allowed=None, emulate=False):
+    """dqkv [B, S, 3W] in float64 from the values a backward kernel READS: the packed qkv, dO, the saved output O_read (bf16,
+    widened) and the saved log-sum-exp lse2_read [B, S, heads] -- the way ln_bwd_check holds the LayerNorm backward to the
+    mean / rstd it read.  P = exp2(scale2 s - lse2_read) (0 where masked), delta = rowsum(dO o O_read), dV = P_drop^T dO,
+    dP = (dO V^T) mask / (1 - p), dS = P o (dP - delta), dQ = scale dS K, dK = scale dS^T Q.
+    q_rows (bool [B, S]): the query rows that exist (tail / one-row forms); every other row contributes nothing, whatever
+    dO / O_read / lse2_read hold there (NaN included).  emulate: P_drop and dS rounded to bf16 before their products."""
+    B, S, W3 = qkv.shape
+    W = W3 // 3
+    q, k, v = (_heads_of(qkv[..., i * W:(i + 1) * W], heads, dh) for i in range(3))
+    ok = attn_allowed(B, S, qkv.device, causal=causal, kv_len=kv_len, allowed=allowed)
+    dOh, Oh = _heads_of(dO, heads, dh), _heads_of(O_read, heads, dh)
+    lse = lse2_read.double().permute(0, 2, 1)
+    if q_rows is not None:
+        qr = q_rows.to(qkv.device)[:, None, :]
+        ok = ok & qr[..., None]
+        dOh, Oh = torch.where(qr[..., None], dOh, torch.zeros_like(dOh)), torch.where(qr[..., None], Oh, torch.zeros_like(Oh))
+        lse = torch.where(qr, lse, torch.zeros_like(lse))
+    scale = dh ** -0.5
+    s2 = (q @ k.transpose(-1, -2)) * (scale * LOG2E)
+    P = torch.where(ok, torch.exp2(s2 - lse[..., None]), torch.zeros_like(s2))
+    f = _drop_factor(drop_mask, p, P)
+    delta = (dOh * Oh).sum(-1)
+    Pd = P if f is None else P * f
+    dP = dOh @ v.transpose(-1, -2)
+    if f is not None:
+        dP = dP * f
+    dS = P * (dP - delta[..., None])
+    if emulate:
+        Pd, dS = _bf16r(Pd), _bf16r(dS)
+    dV = Pd.transpose(-1, -2) @ dOh
+    dQ = scale * (dS @ k)
+    dK = scale * (dS.transpose(-1, -2) @ q)
+    return torch.cat([_merged(dQ), _merged(dK), _merged(dV)], -1)
+
+
+_DIVIDED_ALLOWED = {}
+
+
+def divided_allowed(mode, T, n):
+    """bool [S, S] (S = 1 + T n): which keys each query of the divided space / time attention sees, READ OFF
+    oracle.divided_attention_core instead of restated: with q = k = 0 every visible key gets the same weight, and with one head
+    of dh = S and V = I the output row q is that weight on exactly the keys q sees."""
+    key = (mode, T, n)
+    if key not in _DIVIDED_ALLOWED:
+        from oracle import tvts_oracle as O
+        S = 1 + T * n
+        x = torch.zeros(1, S, 3 * S, dtype=torch.float64)
+        x[0, :, 2 * S:] = torch.eye(S, dtype=torch.float64)
+        _DIVIDED_ALLOWED[key] = O.divided_attention_core(x, 1, mode, T, n)[0] > 0
+    return _DIVIDED_ALLOWED[key]
+
+
+def divided_fwd_ref(qkv, heads, dh, mode, T, n, **kw):
+    """attn_fwd_ref in the divided geometry: a patch query sees the CLS key and its group, the CLS query every key"""
+    return attn_fwd_ref(qkv, heads, dh, allowed=divided_allowed(mode, T, n), **kw)
+
+
+def divided_bwd_same_inputs(qkv, dO, O_read, lse2_read, heads, dh, mode, T, n, **kw):
+    return attn_bwd_same_inputs(qkv, dO, O_read, lse2_read, heads, dh, allowed=divided_allowed(mode, T, n), **kw)
+
+
+def attn_conditioning(qkv, dO, heads, dh, *, floor=0.05, **kw):
+    """How far float64 autograd is from ANY backward that takes delta from the saved bf16 output: per (row, head) rows_rel of
+    attn_bwd_same_inputs(O_read = bf16(O_exact), lse2_exact) against autograd -> {"dq" | "dk" | "dv": [B * S, heads]}.
+    A property of the inputs alone (no kernel): with few keys dP - delta cancels and the rounding of O shows through in dQ / dK."""
+    B, S, W3 = qkv.shape
+    W = W3 // 3
+    out, ref = attn_autograd(qkv, dO, heads, dh, **kw)
+    with torch.no_grad():
+        _, lse2, _ = attn_fwd_ref(qkv, heads, dh, **kw)
+        got = attn_bwd_same_inputs(qkv, dO, out.bfloat16(), lse2, heads, dh, **kw)
+    res = {}
+    for i, nm in enumerate(("dq", "dk", "dv")):
+        sl = slice(i * W, (i + 1) * W)
+        res[nm] = rows_rel(got[..., sl].reshape(B * S, W), ref[..., sl].reshape(B * S, W), heads, floor)[0]
+    return res

@@ -637,11 +637,22 @@ def attn_fwd_len(qkv, kv_len, out, lse2, *, B, heads, S, head_dim=64):
 
 
 def attn_bwd_len(qkv, kv_len, dO, O, lse2, delta, dqkv, *, B, heads, S, head_dim=64):
-    """backward of attn_fwd_len into dqkv (zeroed here first: the padded positions' dK / dV rows are not written)."""
+    """backward of attn_fwd_len into dqkv (zeroed here first: the padded positions' dK / dV rows are not written).
+    dqkv: bf16 [B * S, 3W], contiguous or a row-major view with a wider leading dimension (a multiple of 8, 16-byte base)."""
     lib = _lib.load()
-    zero_(dqkv)
+    _zero_rows(dqkv)
     _chk(_attn_fn(lib, "bwd_len", head_dim)(_p(qkv), _ld(qkv), B, heads, S, _p(kv_len), _p(dO), _ld(dO), _p(O), _ld(O), _p(lse2),
                                             _p(delta), _p(dqkv), _ld(dqkv), _stream()), "tvts_attn_bwd_len")
+
+
+def _zero_rows(t):
+    """t[...] = 0 for a row-major bf16 matrix: one fill when it is contiguous, row by row when it is a view with a wider leading
+    dimension (the columns right of it are not touched; columns and leading dimension multiples of 8, 16-byte base)"""
+    assert t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1, "dqkv: a row-major bf16 matrix"
+    if t.is_contiguous():
+        zero_(t)
+    else:
+        zero_cols_bf16(t, t.shape[1])
 
 
 DROP_SITE_STRIDE = 0x632BE59BD9B4E019  # odd 64-bit constant: site k of a step uses seed_dev[0] + k * this (mod 2^64)
@@ -661,8 +672,9 @@ def attn_fwd_len_drop(qkv, kv_len, out, lse2, *, B, heads, S, p, seed, site, hea
 
 
 def attn_bwd_len_drop(qkv, kv_len, dO, O, lse2, delta, dqkv, *, B, heads, S, p, seed, site, head_dim=64):
+    """backward of attn_fwd_len_drop (the mask regenerated from seed / site); dqkv as in attn_bwd_len, zeroed here first"""
     lib = _lib.load()
-    zero_(dqkv)
+    _zero_rows(dqkv)
     _chk(_attn_fn(lib, "bwd_len_drop", head_dim)(_p(qkv), _ld(qkv), B, heads, S, _p(kv_len), _p(dO), _ld(dO), _p(O), _ld(O),
                                                  _p(lse2), _p(delta), _p(dqkv), _ld(dqkv), float(p), _p(seed), _site(site),
                                                  _stream()), "tvts_attn_bwd_len_drop")
@@ -713,9 +725,10 @@ def attn_fwd_packed(qkv, seq_start, out, *, N, heads, max_len, last_only=False):
 
 
 def attn_bwd_rowq(qkv, qpos, dO, O, lse2, delta, dqkv, *, B, heads, S, head_dim=64):
-    """backward of attn_fwd_rowq into dqkv (zeroed here first: only the query row's dQ and the dK / dV of the keys it sees exist)."""
+    """backward of attn_fwd_rowq into dqkv (zeroed here first: only the query row's dQ and the dK / dV of the keys it sees exist).
+    dqkv: bf16 [B * S, 3W], contiguous or a row-major view with a wider leading dimension (a multiple of 8, 16-byte base)."""
     lib = _lib.load()
-    zero_(dqkv)
+    _zero_rows(dqkv)
     _chk(_attn_fn(lib, "bwd_rowq", head_dim)(_p(qkv), _ld(qkv), B, heads, S, _p(qpos), _p(dO), _ld(dO), _p(O), _ld(O), _p(lse2),
                                              _p(delta), _p(dqkv), _ld(dqkv), _stream()), "tvts_attn_bwd_rowq")
 
