@@ -563,3 +563,254 @@ def attn_conditioning(qkv, dO, heads, dh, *, floor=0.05, **kw):
         sl = slice(i * W, (i + 1) * W)
         res[nm] = rows_rel(got[..., sl].reshape(B * S, W), ref[..., sl].reshape(B * S, W), heads, floor)[0]
     return res
+
+
+# ------------------------------------------------------------------------------------------------ ordered sums (embed kernels)
+def sum_bound(S, n, out_dtype=torch.float32, init=None, ref=None, c=2):
+    """Per-element bound for an fp32 sum of n addends, accumulated (`+=`) into an output that held `init`, in ANY order.
+
+    Derivation (as gemm_bound).  The kernels add their rows in a fixed order of their own -- a thread's running sum, per-block
+    partials, thread groups combined through LDS -- and finish with `out += t`.  Whatever the order, the n addends and the initial
+    value are the leaves of a binary tree of n roundings, and recursive summation (Higham, Thm 4.3 / eq. 4.4) gives
+
+        |got - ref| <= gamma_{n + c} * (S + |init|),   gamma_k = k u / (1 - k u),   u = 2^-24,
+
+    S the float64 sum of the absolute addends.  c (default 2) covers what a kernel does to the finished sum besides adding: the
+    division of a mean, one scale factor.  The addends themselves are exact (fp32 values read from memory).  n may be a tensor
+    (one count per row: the rows of an embedding table get as many addends as tokens point at them).  For an output that is
+    then rounded to bf16 pass out_dtype and `ref`: u_out |ref| is added as in gemm_bound."""
+    S = S.double() if torch.is_tensor(S) else torch.tensor(float(S), dtype=torch.float64)
+    if init is not None:
+        S = S + (init.double().abs() if torch.is_tensor(init) else abs(float(init)))
+    k = (n.double() if torch.is_tensor(n) else float(n)) + c
+    acc = S * (k * U32 / (1.0 - k * U32))
+    if out_dtype == torch.float32:
+        return acc + 1e-45
+    u = U_OUT[out_dtype]
+    return u * ref.double().abs() + (1.0 + u) * acc + 1e-45
+
+
+# ------------------------------------------------------------------------------------------------ loss heads
+# Relative error of the loss kernels' __expf / __logf (hardware exp2 / log2 and one multiplication by log2 e / ln 2): taken at the
+# project's figure for the fast transcendentals.  In a log-sum-exp it also absorbs the rounding of the arguments x - max
+# (2u |x - max| per term, weighted by the softmax probabilities: <= 2u log G, under 2^-20 for G < 2900).
+EPS_LOSS = EPS_ACT
+
+
+def f32_const(v):
+    """the fp32 value a kernel receives for the double v (eps, the betas, lr, wd), as a Python float"""
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def l2norm_check(x, eps, xn, inv, *, what):
+    """xn = x / max(|x|, eps) and inv = +-1 / max(|x|, eps) (negative: the row was clamped, |x| <= eps) of l2norm_rows against
+    float64, per element.  eps is taken as the fp32 value the kernel compares with.
+
+    Bound.  s = fl(sum x^2) has only positive addends: relative error gamma_{E+c}; the square root halves it and adds its own
+    rounding (counted twice: the build has no fast-math flag, but no claim of a correctly rounded sqrtf is relied on), the division
+    1 / max(nrm, eps) two more, the product x * iv one:  |xn - ref| <= (gamma_{E+2} / 2 + 5u) |ref|,  |inv - ref| <= (gamma_{E+2} / 2
+    + 4u) |ref|.  A clamped row divides by eps itself, which only removes terms.  The sign of inv must be the reference's unless
+    the float64 norm is within that relative error of eps (a row of norm exactly eps may land on either side).  -> worst ratio"""
+    E = x.shape[1]
+    e32 = f32_const(eps)
+    x64 = x.double()
+    nrm = x64.pow(2).sum(1).sqrt()
+    d = nrm.clamp_min(e32)
+    r_n = _gamma(E + 2) / 2 + 5 * U32
+    w = assert_within(xn, x64 / d[:, None], (x64 / d[:, None]).abs() * r_n + 1e-45, f"{what}: xn")
+    w = max(w, assert_within(inv.abs(), 1.0 / d, (1.0 / d) * (r_n - U32) + 1e-45, f"{what}: |inv|"))
+    sure = (nrm - e32).abs() > r_n * nrm + 1e-300
+    want_clamped = nrm <= e32
+    wrong = sure & ((inv < 0) != want_clamped)
+    if bool(wrong.any()):
+        r = int(torch.nonzero(wrong)[0])
+        raise AssertionError(f"{what}: clamp flag (sign of inv) wrong on {int(wrong.sum())} rows; first row {r}: norm {float(nrm[r])!r} "
+                             f"eps {e32!r} inv {float(inv[r])!r}")
+    return w
+
+
+def l2norm_bwd_ref(dxn, xn, inv):
+    """float64 dx = |inv| (dxn - xn <xn, dxn>), or |inv| dxn on the rows whose inv is negative (clamped), and the bound's pieces"""
+    d, n = dxn.double(), xn.double()
+    iv = inv.double().abs()[:, None]
+    clamped = (inv < 0)[:, None]
+    s = (n * d).sum(1, keepdim=True)
+    return torch.where(clamped, iv * d, iv * (d - n * s)), (d, n, iv, clamped, s)
+
+
+def l2norm_bwd_check(dxn, xn, inv, dx, *, what):
+    """dx of l2norm_rows_bwd against float64 evaluated on the xn and inv the kernel READ (as ln_bwd_check does with mean / rstd).
+
+    Bound.  The dot s = <xn, dxn> is an fp32 sum of E rounded products: |s~ - s| <= e_s = sum_bound(sum |xn dxn|, E, c=3).  Then
+    t = xn s~ (one rounding), d - t (one), the product with inv (one):
+        |dx - ref| <= |inv| (|xn| e_s + u |xn s| + u (|d| + |xn s| + |xn| e_s)) + u |ref|.
+    A clamped row is the one product inv * d: u |ref|.  -> worst ratio"""
+    E = dxn.shape[1]
+    ref, (d, n, iv, clamped, s) = l2norm_bwd_ref(dxn, xn, inv)
+    e_s = sum_bound((n * d).abs().sum(1, keepdim=True), E, c=3)
+    t = (n * s).abs()
+    acc = iv * (n.abs() * e_s + U32 * t + U32 * (d.abs() + t + n.abs() * e_s)) + U32 * ref.abs()
+    bound = torch.where(clamped, U32 * ref.abs(), acc) + 1e-45
+    return assert_within(dx, ref, bound, f"{what}: dx")
+
+
+def lse_bound(ref, mx, n):
+    """|lse - ref| of an fp32 log-sum-exp m + log(sum exp(x - m)) over n terms: every exponential carries a relative error EPS_LOSS,
+    so does the sum (absolute EPS_LOSS after the logarithm); the n - 1 additions of terms in (0, 1] give gamma_{n+2} relative on the
+    sum (the same after the logarithm); the logarithm itself EPS_LOSS (1 + |log s|) with log s = ref - max; the last addition u |ref|.
+    An online (max, sum) walk multiplies its running sum by further exponentials <= 1: counted in EPS_LOSS' headroom over the 1 ulp
+    hardware exp2, and measured (the `acc` figure of the BOUND lines)."""
+    return U32 * ref.abs() + _gamma(n + 2) + 2 * EPS_LOSS * (1.0 + (ref - mx).abs())
+
+
+def infonce_ref(x, loss0=0.0):
+    """float64 references and bounds of tvts_infonce on the x [G, G] the kernel read -> dict(lse, lse_b, dx, dx_b, loss, loss_b)"""
+    G = x.shape[0]
+    x64 = x.double()
+    rl, cl = torch.logsumexp(x64, 1), torch.logsumexp(x64, 0)
+    d_rl, d_cl = lse_bound(rl, x64.max(1).values, G), lse_bound(cl, x64.max(0).values, G)
+    ar, ac = x64 - rl[:, None], x64 - cl[None, :]
+    pr, pc = torch.exp(ar), torch.exp(ac)
+    dx = (pr + pc - 2.0 * torch.eye(G, dtype=torch.float64, device=x.device)) / G
+    dx_b = (pr * (EPS_LOSS + U32 * ar.abs() + d_rl[:, None]) + pc * (EPS_LOSS + U32 * ac.abs() + d_cl[None, :])) / G + 2 * U32 * dx.abs() + 1e-45
+    dg = x64.diagonal()
+    loss = float(loss0) - float((2.0 * dg - rl - cl).sum()) / G
+    S = float((2.0 * dg.abs() + rl.abs() + cl.abs()).sum()) / G
+    loss_b = float(sum_bound(S, 3 * G, init=loss0)) + float((d_rl + d_cl).sum()) / G
+    return dict(lse=torch.cat([rl, cl]), lse_b=torch.cat([d_rl, d_cl]), dx=dx, dx_b=dx_b, loss=loss, loss_b=loss_b, pr=pr, pc=pc)
+
+
+def infonce_check(x, lse=None, dx=None, loss=None, loss0=0.0, *, what):
+    """tvts_infonce's lse [2G] (rows | columns), dx [G, G] and loss (accumulated into loss0) against float64 on the x the kernel read.
+
+    lse:  lse_bound -- u |ref| + gamma_{G+2} + 2 EPS_LOSS (1 + |ref - max|), absolute.
+    dx = (e^{x - rowlse} + e^{x - collse} - 2 delta) / G: each exponential p carries the relative error EPS_LOSS + u |x - lse| (the
+          rounded argument) + d_lse (the error of the lse it subtracts, lse_bound); the two errors are divided by G, and the sum, the
+          subtraction of 2 and the division add 2u |dx|.
+    loss = loss0 - (1 / G) sum_i (2 x_ii - rowlse_i - collse_i): a sum_bound over its 3G terms (and loss0), plus the mean of the d_lse
+          of the 2G values it reads.  -> {"lse" | "dx" | "loss": worst ratio}"""
+    r = infonce_ref(x, loss0)
+    out = {}
+    if lse is not None:
+        out["lse"] = assert_within(lse, r["lse"], r["lse_b"], f"{what}: lse")
+    if dx is not None:
+        out["dx"] = assert_within(dx, r["dx"], r["dx_b"], f"{what}: dx")
+    if loss is not None:
+        got = float(loss)
+        assert math.isfinite(got) and abs(got - r["loss"]) <= r["loss_b"], f"{what}: loss {got!r} ref {r['loss']!r} bound {r['loss_b']:.3g}"
+        out["loss"] = abs(got - r["loss"]) / r["loss_b"]
+    return out
+
+
+def ce_check(logits, labels, scale, dlogits=None, loss=None, loss0=0.0, *, what):
+    """tvts_cross_entropy against float64: loss = loss0 + scale * mean_r (lse_r - x[r, label_r]), dlogits = scale (softmax - onehot) / R.
+
+    lse_r: lse_bound over C terms (d_r).  dlogits: the exponential e^{x - lse} carries EPS_LOSS + u |x - lse| + d_r relative; the
+    subtraction of the one-hot, the product with scale and the division (two roundings) add 4u |ref|.  loss: the kernel adds the R
+    non-negative differences lse_r - x[r, label_r] (one rounding each, exact operands apart from d_r): a sum_bound over R addends
+    (times |scale| / R; c = 5: that subtraction, the product, the division twice) and loss0, plus |scale| mean d_r.  -> {name: worst ratio}"""
+    R, C = logits.shape
+    x64 = logits.double()
+    lb = labels.long()
+    lse = torch.logsumexp(x64, 1)
+    d = lse_bound(lse, x64.max(1).values, C)
+    a = x64 - lse[:, None]
+    p = torch.exp(a)
+    onehot = torch.zeros_like(p).scatter_(1, lb[:, None], 1.0)
+    ref = scale * (p - onehot) / R
+    out = {}
+    if dlogits is not None:
+        b = abs(scale) / R * p * (EPS_LOSS + U32 * a.abs() + d[:, None]) + 4 * U32 * ref.abs() + 1e-45
+        out["dlogits"] = assert_within(dlogits, ref, b, f"{what}: dlogits")
+    if loss is not None:
+        xl = x64.gather(1, lb[:, None])[:, 0]
+        lref = float(loss0) + scale * float((lse - xl).sum()) / R
+        S = abs(scale) / R * float((lse - xl).sum())
+        lb_ = float(sum_bound(S, R, init=loss0, c=5)) + abs(scale) * float(d.sum()) / R
+        got = float(loss)
+        assert math.isfinite(got) and abs(got - lref) <= lb_, f"{what}: loss {got!r} ref {lref!r} bound {lb_:.3g}"
+        out["loss"] = abs(got - lref) / lb_
+    return out
+
+
+def contrastive_bound(v, t, temp, eps):
+    """float64 autograd of the contrastive head (cosine similarity / temp, InfoNCE both ways) and a per-element bound on the dv / dt
+    that LossHead.contrastive returns, composed from the stage bounds above -> (loss, dv, dt, e_dv, e_dt).
+
+    Stages.  vn, tn: relative error r_n (l2norm_check).  x = vn tn^T / temp: gemm_acc_bound(K = E) plus 2 r_n S for the operands,
+    e_x its largest element.  dx: infonce_ref's dx_b, plus the softmax' response to a shift of every x by <= e_x: each probability
+    changes by a factor within e^{+-2 e_x}, so |delta dx| <= 2.01 e_x (P_row + P_col) / G.  dvn = dx tn / temp (dtn = dx^T vn / temp):
+    (e_dx |tn| + r_n |dx| |tn|) / temp plus gemm_acc_bound(K = G).  dv = inv (dvn - vn <vn, dvn>): the propagated
+    inv (e_dvn + |vn| (<|vn|, e_dvn> + r_n <|vn|, |dvn|>)), 4 r_n on every term for the errors of vn and inv, and l2norm_bwd_check's own rounding terms."""
+    G, E = v.shape
+    e32 = f32_const(eps)
+    vr, tr = v.double().clone().requires_grad_(True), t.double().clone().requires_grad_(True)
+    nv, nt = vr.norm(dim=1, keepdim=True).clamp_min(e32), tr.norm(dim=1, keepdim=True).clamp_min(e32)
+    x = (vr / nv) @ (tr / nt).t() / temp
+    loss = -(torch.log_softmax(x, 1).diagonal().mean() + torch.log_softmax(x.t(), 1).diagonal().mean())
+    loss.backward()
+    with torch.no_grad():
+        vn, tn, iv, it = (vr / nv).detach(), (tr / nt).detach(), 1.0 / nv, 1.0 / nt
+        r_n = _gamma(E + 2) / 2 + 5 * U32
+        Sx = vn.abs() @ tn.abs().t() / temp
+        e_x = float((gemm_acc_bound(Sx, E) + 2 * r_n * Sx + U32 * x.abs()).max())
+        r = infonce_ref(x.detach())
+        e_dx = r["dx_b"] + 2.01 * e_x * (r["pr"] + r["pc"]) / G
+        dx = r["dx"]
+        out = []
+        for dxm, e_dxm, a, b, ia in ((dx, e_dx, vn, tn, iv), (dx.t(), e_dx.t(), tn, vn, it)):
+            S = dxm.abs() @ b.abs() / temp
+            dn = dxm @ b / temp
+            e_dn = (e_dxm @ b.abs()) / temp + r_n * S + gemm_acc_bound(S, G)
+            s = (a * dn).sum(1, keepdim=True)
+            terms = ia * (dn.abs() + a.abs() * s.abs())
+            sa = (a * dn).abs().sum(1, keepdim=True)
+            e_s = (a.abs() * e_dn).sum(1, keepdim=True) + r_n * sa + sum_bound(sa, E, c=3)
+            out.append(ia * (e_dn + a.abs() * e_s) + (4 * r_n + 4 * U32) * terms + 1e-45)
+    return float(loss.detach()), vr.grad, tr.grad, out[0], out[1]
+
+
+# ------------------------------------------------------------------------------------------------ AdamW
+def adamw_check(p0, g, m0, v0, p1, m1, v1, shadow, *, lr, wd, step, beta1=0.9, beta2=0.999, eps=1e-6, grad_scale=1.0, what):
+    """One Hugging Face AdamW step of tvts_adamw_hf on one parameter group, against float64 from the fp32 p0, g, m0, v0 the kernel
+    read; p1, m1, v1 per element, the bf16 shadow bit for bit as bf16(p1).
+
+    The constants are the fp32 values the kernel receives: b1 = fp32(beta1), o1 = fp32(1 - beta1) (b2, o2 alike), fp32(eps),
+    fp32(lr), fp32(wd), and the step size ss = fp32(lr sqrt(1 - beta2^t) / (1 - beta1^t)) formed in double from the double betas.
+    With gg = g grad_scale (one rounding, u):
+      m1 = b1 m0 + o1 gg              |err| <= e_m = 3u (|b1 m0| + |o1 gg|)              (two products, gg, the sum)
+      v1 = b2 v0 + o2 gg gg           |err| <= e_v = 5u v1                               (gg twice, two products, the sum; all terms >= 0)
+      r  = sqrt(v1)                   |err| <= e_r = (e_v / 2 v1 + 2u) r = 4.5u r        (sqrt counted as two roundings)
+      d  = r + eps                    |err| <= e_d = e_r + u d
+      q  = ss m1 / d                  |err| <= e_q = ss e_m / d + |q| (5u + e_d / d)      (ss: one ulp between the host's and the
+                                                                                          device's pow; product; division twice; 1u slack)
+      p' = p0 - q                     |err| <= e_q + u |p'|
+      p1 = p' - (lr wd) p'  (wd > 0)  |err| <= (1 + lr wd) e_p' + 2u |lr wd p'| + u |p1|
+    An element with g = 0, m0 = v0 = 0 keeps p exactly (q = 0 / eps).  -> worst ratio"""
+    b1, b2 = f32_const(beta1), f32_const(beta2)
+    o1, o2 = f32_const(1.0 - beta1), f32_const(1.0 - beta2)
+    e32, lr32, wd32, gs = f32_const(eps), f32_const(lr), f32_const(wd), f32_const(grad_scale)
+    ss = f32_const(lr32 * math.sqrt(1.0 - beta2 ** step) / (1.0 - beta1 ** step))
+    p, gg, m, v = p0.double(), g.double() * gs, m0.double(), v0.double()
+    mr = b1 * m + o1 * gg
+    e_m = 3 * U32 * ((b1 * m).abs() + (o1 * gg).abs())
+    vr = b2 * v + o2 * gg * gg
+    e_v = 5 * U32 * vr
+    r = vr.sqrt()
+    e_r = 4.5 * U32 * r * 1.001
+    d = r + e32
+    e_d = e_r + U32 * d
+    q = ss * mr / d
+    e_q = ss * e_m / d + q.abs() * (5 * U32 + e_d / d) * 1.001
+    pr = p - q
+    e_p = e_q + U32 * pr.abs()
+    if wd32 > 0:
+        dec = lr32 * wd32
+        pr2 = pr - dec * pr
+        e_p = (1 + dec) * e_p + 2 * U32 * (dec * pr).abs() + U32 * pr2.abs()
+        pr = pr2
+    w = assert_within(m1, mr, e_m + 1e-45, f"{what}: m")
+    w = max(w, assert_within(v1, vr, e_v + 1e-45, f"{what}: v"))
+    w = max(w, assert_within(p1, pr, e_p + 1e-45, f"{what}: p"))
+    assert_equal_bits(shadow, p1.bfloat16(), f"{what}: bf16 shadow")
+    return w

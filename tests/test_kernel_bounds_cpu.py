@@ -475,3 +475,177 @@ def test_bf16_rounding_emulation_sits_inside_the_attention_tolerances():
             assert TOL[nm] / 10 < v < TOL[nm], (name, nm, v)
             worst[nm] = max(worst.get(nm, 0.0), v)
     assert max(worst.values()) < 4.5e-3, worst
+
+
+# ------------------------------------------------------------------------------------------------ embed / loss / AdamW helpers
+def f32_sum_in_groups(parts, groups=16):
+    """colsum_partials_kernel's order in fp32 torch: every group adds its partials p = g, g + 16, ... in order, the groups in order"""
+    acc = torch.zeros(parts.shape[1])
+    for g in range(groups):
+        s = torch.zeros(parts.shape[1])
+        for p in range(g, parts.shape[0], groups):
+            s = s + parts[p]
+        acc = acc + s
+    return acc
+
+
+def test_sum_bound_passes_fp32_orders_and_catches_a_missing_addend():
+    """54 partials (18 clips x 3 slot groups) added into a non-zero output: three fp32 orders pass; the smallest addend missing from
+    ONE column fails and the column is named"""
+    g = torch.Generator().manual_seed(11)
+    parts, init = torch.randn(54, 96, generator=g), torch.randn(96, generator=g)
+    ref = parts.double().sum(0) + init.double()
+    bound = KB.sum_bound(parts.double().abs().sum(0), 54, init=init)
+    for got in (init + f32_sum_in_groups(parts), init + parts.sum(0), (init + parts.flip(0).cumsum(0)[-1])):
+        assert KB.assert_within(got, ref, bound, "column sums") < 1.0
+    col = 37
+    k = int(parts[:, col].abs().argmin())  # the SMALLEST addend of that column
+    bad = init + f32_sum_in_groups(parts)
+    bad[col] -= parts[k, col]
+    assert abs(float(parts[k, col])) < 0.05
+    fails(lambda: KB.assert_within(bad, ref, bound, "column sums"), "row 37")  # (a 1-D output: its elements are the rows)
+    # bf16 output form
+    b16 = KB.sum_bound(parts.double().abs().sum(0), 54, torch.bfloat16, init=init, ref=ref)
+    assert KB.assert_within((init + parts.sum(0)).bfloat16(), ref, b16, "bf16 column sums") <= 1.0
+
+
+def test_bit_equality_catches_two_swapped_gathered_rows():
+    g = torch.Generator().manual_seed(12)
+    emb, pos = torch.randn(20, 32, generator=g), torch.randn(7, 32, generator=g)
+    ids = torch.randint(0, 20, (3, 7), generator=g)
+    want = (emb[ids] + pos).reshape(21, 32)
+    KB.assert_equal_bits(want.clone(), want, "gather")
+    bad = want.clone()
+    bad[[4, 11]] = want[[11, 4]]
+    assert rel(bad, want) > 0  # (a whole-tensor gate of 1e-6 sees this one too; the point is that the row is named)
+    fails(lambda: KB.assert_equal_bits(bad, want, "gather"), "row 4")
+
+
+def l2_standin(x, eps):
+    e = torch.tensor(eps, dtype=torch.float32)
+    nrm = (x * x).sum(1).sqrt()
+    iv = 1.0 / torch.maximum(nrm, e)
+    return x * iv[:, None], torch.where(nrm > e, iv, -iv)
+
+
+def l2_bwd_standin(dxn, xn, inv):
+    s = (xn * dxn).sum(1, keepdim=True)
+    return torch.where((inv < 0)[:, None], -inv[:, None] * dxn, inv[:, None] * (dxn - xn * s))
+
+
+def test_l2norm_checks_pass_fp32_and_catch_an_inverted_clamp_flag():
+    g = torch.Generator().manual_seed(13)
+    for E in (1, 64, 65, 512):
+        x = torch.randn(9, E, generator=g)
+        u = x[:5].double() / x[:5].double().norm(dim=1, keepdim=True)
+        x[0] = 0.0
+        x[1] = (u[1] * 1e-10).float()
+        x[2] = 0.0
+        x[2, E // 2] = KB.f32_const(1e-8)
+        x[3], x[4] = (u[3] * 1e-3).float(), (u[4] * 1e3).float()
+        xn, inv = l2_standin(x, 1e-8)
+        assert KB.l2norm_check(x, 1e-8, xn, inv, what="l2norm") <= 1.0
+        assert bool((inv[:3] < 0).all()) and bool((inv[3:] > 0).all())
+        dxn = torch.randn(9, E, generator=g)
+        assert KB.l2norm_bwd_check(dxn, xn, inv, l2_bwd_standin(dxn, xn, inv), what="l2norm_bwd") <= 1.0
+        for row in (1, 4):  # a clamped row marked unclamped, an ordinary row marked clamped
+            bad = inv.clone()
+            bad[row] = -bad[row]
+            fails(lambda: KB.l2norm_check(x, 1e-8, xn, bad, what="l2norm"), "clamp flag", f"row {row}")
+        if E > 1:  # the backward follows the flag it reads: the other branch's values fail against it
+            bad = inv.clone()
+            bad[4] = -bad[4]
+            fails(lambda: KB.l2norm_bwd_check(dxn, xn, bad, l2_bwd_standin(dxn, xn, inv), what="l2norm_bwd"), "row 4")
+
+
+def infonce_standin(x, lse=None):
+    G = x.shape[0]
+    if lse is None:
+        lse = torch.cat([torch.logsumexp(x, 1), torch.logsumexp(x, 0)])
+    dx = (torch.exp(x - lse[:G, None]) + torch.exp(x - lse[None, G:]) - 2.0 * torch.eye(G)) / G
+    loss = -(2.0 * x.diagonal() - lse[:G] - lse[G:]).sum() / G
+    return lse, dx, loss
+
+
+def test_infonce_check_passes_fp32_and_catches_one_column_lse_off_by_1e_5():
+    """... which the old gates (rel < 1e-4 on dv / dt after the two GEMMs, 2e-5 on the loss) let through"""
+    g = torch.Generator().manual_seed(14)
+    G, E, temp = 65, 64, 0.05
+    v, t = torch.randn(G, E, generator=g), torch.randn(G, E, generator=g)
+    loss_ref, dv_ref, dt_ref, e_dv, e_dt = KB.contrastive_bound(v, t, temp, 1e-8)
+    vn, vi = l2_standin(v, 1e-8)
+    tn, ti = l2_standin(t, 1e-8)
+    x = (vn @ tn.t()) * (1.0 / temp)
+    lse, dx, loss = infonce_standin(x)
+    res = KB.infonce_check(x, lse, dx, loss + 0.75, loss0=0.75, what="infonce")
+    assert max(res.values()) <= 1.0, res
+
+    def head(dx):
+        dv = l2_bwd_standin((dx @ tn) * (1.0 / temp), vn, vi)
+        return dv, l2_bwd_standin((dx.t() @ vn) * (1.0 / temp), tn, ti)
+    dv, dt = head(dx)
+    for got, ref, e in ((dv, dv_ref, e_dv), (dt, dt_ref, e_dt)):  # the composed bound holds for the fp32 chain, with room
+        assert KB.assert_within(got, ref, e, "contrastive") < 0.5
+    bad = lse.clone()
+    bad[G + 17] += 1e-5
+    _, dx_bad, loss_bad = infonce_standin(x, bad)
+    dvb, dtb = head(dx_bad)
+    assert rel(dvb, dv_ref) < 1e-4 and rel(dtb, dt_ref) < 1e-4 and abs(float(loss_bad) - loss_ref) < 2e-5 * max(1.0, abs(loss_ref))
+    fails(lambda: KB.infonce_check(x, bad, None, None, what="infonce"), "infonce: lse", f"row {G + 17}")
+    # (dx_bad itself stays inside its bound: that bound carries the lse bound, so the lse check is the one that sees the fault)
+    KB.infonce_check(x, None, dx_bad, None, what="infonce")
+    # small G and the edge values of the GPU test
+    for G2 in (1, 2, 3, 5):
+        x2 = torch.rand(G2, G2, generator=g) * 40.0 - 20.0
+        x2[0, 0] = 21.0
+        l2, d2, s2 = infonce_standin(x2)
+        assert max(KB.infonce_check(x2, l2, d2, s2, what="infonce small").values()) <= 1.0
+
+
+def test_ce_check_passes_fp32_and_catches_a_wrong_label_row():
+    g = torch.Generator().manual_seed(15)
+    for R, C in ((1, 1), (257, 4), (768, 7)):
+        x = torch.randn(R, C, generator=g) * 3.0
+        lab = torch.randint(0, C, (R,), generator=g, dtype=torch.int32)
+        lse = torch.logsumexp(x, 1)
+        onehot = torch.zeros(R, C).scatter_(1, lab.long()[:, None], 1.0)
+        dl = 2.0 * (torch.exp(x - lse[:, None]) - onehot) / R
+        loss = 0.25 + 2.0 * (lse - x.gather(1, lab.long()[:, None])[:, 0]).sum() / R
+        assert max(KB.ce_check(x, lab, 2.0, dl, loss, loss0=0.25, what="ce").values()) <= 1.0
+        if C > 1:
+            bad = dl.clone()
+            bad[R // 2] = 2.0 * (torch.exp(x[R // 2] - lse[R // 2]) - onehot[R // 2].roll(1)) / R
+            fails(lambda: KB.ce_check(x, lab, 2.0, bad, None, what="ce"), f"row {R // 2}")
+            fails(lambda: KB.ce_check(x, lab, 2.0, None, loss + 1e-3, loss0=0.25, what="ce"), "loss")
+
+
+def adamw_standin(p, g, m, v, lr, wd, step, gs, beta1=0.9, beta2=0.999, eps=1e-6, m_beta=None):
+    f = lambda z: torch.tensor(z, dtype=torch.float32)  # noqa: E731
+    ss = f(float(f(lr)) * math.sqrt(1.0 - beta2 ** step) / (1.0 - beta1 ** step))
+    gg = g * f(gs)
+    m1 = f(beta1 if m_beta is None else m_beta) * m + f(1.0 - beta1) * gg
+    v1 = f(beta2) * v + f(1.0 - beta2) * gg * gg
+    p1 = p - ss * m1 / (v1.sqrt() + f(eps))
+    if wd > 0:
+        p1 = p1 - f(lr) * f(wd) * p1
+    return p1, m1, v1, p1.bfloat16()
+
+
+def test_adamw_check_passes_fp32_and_catches_m_updated_with_beta2():
+    g = torch.Generator().manual_seed(16)
+    n = 1024
+    p, gr = torch.randn(n, generator=g), torch.randn(n, generator=g) * 0.1
+    m, v = torch.randn(n, generator=g) * 0.05, torch.rand(n, generator=g) * 1e-2
+    gr[:8], m[:16], v[:16] = 0.0, 0.0, 0.0
+    gr[8:16] = 1e-12
+    p[16] = -1e4
+    for step in (1, 2, 1000):
+        for lr, wd in ((1e-2, 0.05), (1e-4, 0.0)):
+            out = adamw_standin(p, gr, m, v, lr, wd, step, 0.5)
+            assert KB.adamw_check(p, gr, m, v, *out, lr=lr, wd=wd, step=step, grad_scale=0.5, what="adamw") <= 1.0
+            bad = adamw_standin(p, gr, m, v, lr, wd, step, 0.5, m_beta=0.999)
+            fails(lambda: KB.adamw_check(p, gr, m, v, *bad, lr=lr, wd=wd, step=step, grad_scale=0.5, what="adamw"), "adamw: m")
+    out = adamw_standin(p, gr, m, v, 1e-2, 0.05, 2, 0.5)
+    sh = out[3].clone()
+    sh[5] = sh[6]
+    fails(lambda: KB.adamw_check(p, gr, m, v, out[0], out[1], out[2], sh, lr=1e-2, wd=0.05, step=2, grad_scale=0.5, what="adamw"), "bf16 shadow")

@@ -643,7 +643,7 @@ __global__ __launch_bounds__(256) void sort_assemble_bwd_kernel(const float* __r
             if (part0) {  // per-block partials, added in block order by colsum_partials_kernel
                 part0[((size_t)b * gridDim.y + blockIdx.y) * E + c] = s0;
                 if (blockIdx.y == 0) part1[(size_t)b * E + c] = s1;
-            } else {
+            } else if (dtype) {  // no dtype: only dout is wanted
                 atomicAdd(dtype + c, s0);
                 if (blockIdx.y == 0) atomicAdd(dtype + E + c, s1);
             }
