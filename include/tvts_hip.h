@@ -307,6 +307,16 @@ int tvts_attn80_fwd_rowq(const void* qkv, int ld, int B, int heads, int S, const
                          hipStream_t stream);
 int tvts_attn80_bwd_rowq(const void* qkv, int ld, int B, int heads, int S, const int* qpos, const void* dO, int lddo, const void* O,
                          int ldo, const float* lse2, float* delta, void* dqkv, int lddq, hipStream_t stream);
+/* ONE query per sequence at token row 0 over the keys 0 .. nk - 1: nk = S, or with kv_len (device int32[B], optional)
+ * nk = clamp(kv_len[b], 1, S), the clamp of tvts_attn_fwd_len.  Forward-only: it writes row b * S of out (and of lse2, if given) and
+ * nothing else.  Two sites: the last block of the v1 ViT in the forward-only encoder, which the model reads at the normed CLS token
+ * (v1/downstream/video_encoder_zero.py:198-199 `self.norm(x)[:, 0]`), and the last DistilBERT block, whose only consumer is the [CLS]
+ * row (v1/model/model_dist_TVTS.py:131-141).  tvts_attn_fwd_len itself takes lse2 == NULL as well (the forward-only DistilBERT
+ * blocks in front of the last), with the output bits of the call with lse2. */
+int tvts_attn_fwd_first(const void* qkv, int ld, int B, int heads, int S, const int* kv_len, void* out, int ldo, float* lse2,
+                        hipStream_t stream);
+int tvts_attn80_fwd_first(const void* qkv, int ld, int B, int heads, int S, const int* kv_len, void* out, int ldo, float* lse2,
+                          hipStream_t stream);
 /* Causal self-attention inside each sequence of a PACKED batch (seq_start as for tvts_text_embed_packed), head dim 64, forward-only
  * (no log-sum-exp): qkv bf16 [M, 3 * heads * 64] -> out bf16 [M, heads * 64]; ld, ldo multiples of 8.  Every length 1 .. 80 in any
  * mixture and order (the CLIP context is 77, CLIP/clip/model.py:330-336); max_len >= the longest sequence selects the tile classes that
@@ -403,6 +413,20 @@ int tvts_vit_assemble_bwd(const float* dtok, int ldt, const int* keep, int keep_
  * in the Conv3d weight's (c, t, py, px) column order; patch % 8 == 0 */
 int tvts_patch_gather_tube(const float* video, const int* keep, int B, int tubes, int tubelet, int n, int img, int patch,
                            void* out, int ldo, hipStream_t stream);
+/* the same gather for CHANNEL-MAJOR fp32 clips [B, 3, tubes * tubelet, img, img], the layout the v1 downstream classes take
+ * (v1/downstream/video_encoder_zero.py:91-96,177: forward_features hands x to the Conv3d as it comes); ldo % 8 == 0 and
+ * ldo >= 3 * tubelet * patch^2 here and in the uint8 form (a wider leading dimension is left untouched) */
+int tvts_patch_gather_tube_cm(const float* video, const int* keep, int B, int tubes, int tubelet, int n, int img, int patch,
+                              void* out, int ldo, hipStream_t stream);
+/* ... and for uint8 frames [B, tubes * tubelet, H0, W0, 3]: crop (device [B,2] (top, left), or NULL for the centre crop with the
+ * round-half-to-even offsets of tvts_patch_gather_u8) + ClipToTensor + Normalize of the v1 downstream pipeline
+ * (v1/downstream/ssv2.py:61-63) fused into the tubelet gather: out = bf16((u / 255.0f - mean) / std), the operations and their order
+ * those of tvts_patch_gather_u8, so the bytes equal tvts_patch_gather_tube's on host-normalised frames.  mean3 / std3 are HOST
+ * arrays; patch % 8 == 0, img > 0, H0 >= img, W0 >= img.  crop is DEVICE data and is not checked: the caller keeps
+ * 0 <= top <= H0 - img and 0 <= left <= W0 - img for every sample (a crop outside reads outside the frames) */
+int tvts_patch_gather_tube_u8(const unsigned char* frames, int H0, int W0, const int* crop, const int* keep, int B, int tubes,
+                              int tubelet, int n, int img, int patch, const float* mean3, const float* std3, void* out, int ldo,
+                              hipStream_t stream);
 int tvts_text_embed(const int* ids, int ld_ids, int N, int L, const float* emb, const float* pos, int Wt, float* x, int ldx,
                     hipStream_t stream);
 /* ---- PACKED variable-length captions (the forward-only text encoder of the SSv2 multiple-choice models,
@@ -462,6 +486,14 @@ int tvts_mc_logits(const float* text, const float* video, int C, int B, int E, f
  * (ranks[n_vid], averaged ties, closest own caption); valid: optional n_text bytes, 0 = caption missing (query_masks) */
 int tvts_retrieval_ranks(const float* sims, long ld, int n_text, int n_vid, int mode, const unsigned char* valid,
                          float* ranks, hipStream_t stream);
+
+/* v1's zero-shot protocol, video-to-video retrieval by label (v1/downstream/run_class_zero.py:344-413): row i of sims[nq, >= N] holds
+ * the similarities of query video q0 + i to all N videos, element [i, q0 + i] is read as -1000 (the script's self-mask :385-387; sims
+ * is not modified), labels int32[N].  ranks[i] = #{ j : labels[j] != labels[q] and s'[i, j] > best_i } with best_i = max{ s'[i, j] :
+ * labels[j] == labels[q] } (self included at -1000): `ranks < k` is the script's hit among the first k of argsort(-scores), k <= 10
+ * (:389-404).  Strict > (ties optimistic, as mode 0 above); exact integers; 0 <= q0, q0 + nq <= N, ld >= N, N < 2^24 (the counts are
+ * summed in fp32, exact below that; -22 otherwise). */
+int tvts_v2v_ranks(const float* sims, long ld, int nq, int q0, int N, const int* labels, float* ranks, hipStream_t stream);
 
 /* ---- optimizer (optim.hip): transformers.AdamW as built at train_dist_TVTSv2_ViT_B_16.py:118-125 */
 /* step_dev (optional): the step counter in device memory (hipGraph replay); hyper_dev (optional, needs step_dev): lr[4] | wd[4]

@@ -8,7 +8,9 @@ streaming kernel + CLS-query pair (what calls with lse2 run) against the forward
   encode_text(packed=True), the packed attention site against the rectangular one, and the whole _mc forward; B/16 and H/14.
   The caption lengths are a STAND-IN (uniform in [6, 24] from a fixed seed): the SSv2 label files are not part of this repository.
   --fp8: H/14 `encode_video` on the e4m3 architecture (arch["fp8"]: the blocks' GEMMs on e4m3 copies, per-token activation scales)
-  against the bf16 architecture, same random weights, at the H/14 clip counts above; one line per form."""
+  against the bf16 architecture, same random weights, at the H/14 clip counts above; one line per form.
+  --v1: the v1 model (tubelet ViT-B/16, joint attention) at 16 full frames (S = 1569): `TVTS.encode_video` (fp32 and uint8 clips)
+  against the eval-mode training forward `compute_video` under no_grad, clips/s and peak allocated GB at 4 / 16 clips."""
 import argparse
 import json
 import os
@@ -157,11 +159,43 @@ def fp8_encoders(iters):
         torch.cuda.empty_cache()
 
 
+def v1_encoders(iters):
+    """the v1 model with random weights (a one-layer text tower: it takes no part), 16 frames, every patch of every tube"""
+    import types
+    from tvts_amd.arch import ARCH_V1
+    from tvts_amd.model.model_dist_TVTS import TVTS
+    m = TVTS(types.SimpleNamespace(local_rank=0, rank=0, world_size=1), arch=dict(ARCH_V1, text_layers=1, sort_depth=1)).eval()
+    T, ppf = 16, 196
+    eng = m.engine
+    for B in (4, 16):
+        g = torch.Generator().manual_seed(1)
+        v = torch.randn(B, T, 3, 224, 224, generator=g).cuda()
+        u8 = torch.randint(0, 256, (B, T, 224, 224, 3), generator=g, dtype=torch.uint8).cuda()
+        keep = torch.arange(ppf).view(1, 1, ppf).expand(B, T // 2, ppf)
+        line = {"what": f"video embeddings, v1 T={T} S={1 + T // 2 * ppf}", "clips": B}
+        for form, fn in (("training forward (eval mode)", lambda: m.compute_video(v, keep)),
+                         ("encode_video", lambda: m.encode_video(v)), ("encode_video uint8", lambda: m.encode_video(u8))):
+            eng.buf.clear(); eng._back.clear(); eng._seen.clear(); eng._inf.clear()
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            try:
+                with torch.no_grad():
+                    dt = timed(fn, iters)
+                line[form + " clips/s"] = B / dt
+                line[form + " peak GB"] = torch.cuda.max_memory_allocated() / 1e9
+            except torch.cuda.OutOfMemoryError:
+                line[form + " clips/s"] = None
+                line[form + " peak GB"] = "out of memory"
+        print(json.dumps(line), flush=True)
+        del v, u8
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--attn-only", action="store_true")
     ap.add_argument("--mc", action="store_true")
     ap.add_argument("--fp8", action="store_true")
+    ap.add_argument("--v1", action="store_true")
     ap.add_argument("--reps", type=int, default=20, help="--mc: timed repetitions of each form (median)")
     ap.add_argument("--iters", type=int, default=5)
     args = ap.parse_args()
@@ -171,6 +205,9 @@ def main():
         return
     if args.fp8:
         fp8_encoders(args.iters)
+        return
+    if args.v1:
+        v1_encoders(args.iters)
         return
     attention(K)
     if args.attn_only:

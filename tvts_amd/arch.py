@@ -60,10 +60,36 @@ def small_arch_v1(**over) -> dict:
     return a
 
 
+def _video_shapes_v1(a, o):
+    W = a["width"]
+    o["video_model.cls_token"] = (1, 1, W)
+    o["video_model.pos_embed"] = (1, patches_per_frame(a) + 1, W)
+    o["video_model.temporal_embed"] = (1, a["num_frames"] // a["tubelet"], W)
+    o["video_model.patch_embed.proj.weight"] = (W, 3, a["tubelet"], a["patch"], a["patch"])
+    o["video_model.patch_embed.proj.bias"] = (W,)
+    for i in range(a["layers"]):
+        p = f"video_model.blocks.{i}."
+        for k, shp in (("norm1.weight", (W,)), ("norm1.bias", (W,)), ("attn.qkv.weight", (3 * W, W)), ("attn.qkv.bias", (3 * W,)),
+                       ("attn.proj.weight", (W, W)), ("attn.proj.bias", (W,)), ("norm2.weight", (W,)), ("norm2.bias", (W,)),
+                       ("mlp.fc1.weight", (4 * W, W)), ("mlp.fc1.bias", (4 * W,)), ("mlp.fc2.weight", (W, 4 * W)),
+                       ("mlp.fc2.bias", (W,))):
+            o[p + k] = shp
+    o["video_model.norm.weight"] = (W,)
+    o["video_model.norm.bias"] = (W,)
+
+
 def param_shapes_v1(a) -> "OrderedDict[str, Tuple[int, ...]]":
     """state-dict keys of v1 `TVTS` in registration order: text_model (Hugging Face DistilBertModel), video_model, txt_proj,
-    vid_proj, pred_model (model_dist_TVTS.py:34,58,62-76)"""
+    vid_proj, pred_model (model_dist_TVTS.py:34,58,62-76).  a["towers"] == "video": the video tower alone, plus `head.*` when
+    a["head_classes"] > 0 -- the parameter set of the v1 downstream classes (v1/downstream/video_encoder_zero.py:100-161,
+    video_encoder.py), which strip the `video_model.` prefix themselves."""
     o: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    if a.get("towers") == "video":
+        _video_shapes_v1(a, o)
+        if a.get("head_classes", 0) > 0:
+            o["head.weight"] = (a["head_classes"], a["width"])
+            o["head.bias"] = (a["head_classes"],)
+        return o
     Wt, Ff, W, E, Ws = a["text_width"], a["text_ffn"], a["width"], a["embed"], a["sort_width"]
     o["text_model.embeddings.word_embeddings.weight"] = (a["vocab"], Wt)
     o["text_model.embeddings.position_embeddings.weight"] = (a["max_pos"], Wt)
@@ -82,20 +108,7 @@ def param_shapes_v1(a) -> "OrderedDict[str, Tuple[int, ...]]":
         o[p + "ffn.lin2.bias"] = (Wt,)
         o[p + "output_layer_norm.weight"] = (Wt,)
         o[p + "output_layer_norm.bias"] = (Wt,)
-    o["video_model.cls_token"] = (1, 1, W)
-    o["video_model.pos_embed"] = (1, patches_per_frame(a) + 1, W)
-    o["video_model.temporal_embed"] = (1, a["num_frames"] // a["tubelet"], W)
-    o["video_model.patch_embed.proj.weight"] = (W, 3, a["tubelet"], a["patch"], a["patch"])
-    o["video_model.patch_embed.proj.bias"] = (W,)
-    for i in range(a["layers"]):
-        p = f"video_model.blocks.{i}."
-        for k, shp in (("norm1.weight", (W,)), ("norm1.bias", (W,)), ("attn.qkv.weight", (3 * W, W)), ("attn.qkv.bias", (3 * W,)),
-                       ("attn.proj.weight", (W, W)), ("attn.proj.bias", (W,)), ("norm2.weight", (W,)), ("norm2.bias", (W,)),
-                       ("mlp.fc1.weight", (4 * W, W)), ("mlp.fc1.bias", (4 * W,)), ("mlp.fc2.weight", (W, 4 * W)),
-                       ("mlp.fc2.bias", (W,))):
-            o[p + k] = shp
-    o["video_model.norm.weight"] = (W,)
-    o["video_model.norm.bias"] = (W,)
+    _video_shapes_v1(a, o)
     o["txt_proj.1.weight"] = (E, Wt)
     o["txt_proj.1.bias"] = (E,)
     o["vid_proj.0.weight"] = (E, W)
@@ -202,13 +215,16 @@ def param_shapes(arch) -> "OrderedDict[str, Tuple[int, ...]]":
     return o
 
 
-def is_mfma_weight(name: str, shape) -> bool:
-    """Parameters consumed by the bf16 MFMA GEMMs (they get bf16 shadows, plain and transposed)."""
+def is_mfma_weight(name: str, shape, arch=None) -> bool:
+    """Parameters consumed by the bf16 MFMA GEMMs (they get bf16 shadows, plain and transposed).  arch: the store's architecture,
+    for rules that hold in one parameter set only."""
     if name in ("video_model.proj", "video_model.conv1.weight", "video_model.patch_embed.proj.weight"):
         return True
     if name in ("txt_proj.1.weight", "vid_proj.0.weight"):  # v1 projections of [N, W] rows: the small fp32 kernel
         return False
     if name.startswith("pred_model.head"):
+        return False
+    if arch is not None and arch.get("towers") == "video" and name.startswith("head."):  # v1 downstream classifier: small fp32 kernel
         return False
     return len(shape) == 2 and name.endswith(("weight", "in_proj_weight")) and "embedding" not in name
 

@@ -58,7 +58,7 @@ struct AttnGeom {
     int q8_only;            // fused divided kernels with a q8 copy: 1 = the patch rows' bf16 values are NOT stored (opts bit 7; the CLS
                             // row, which the merge / finalize kernels write, keeps both forms)
     int ablate;             // dev knob (opts bits 4..6 of tvts_attn_bwd): 1 skip phase A, 2 skip phase B, 4 skip global loads
-    const int* kv_len;      // FULL only, optional: valid keys per sequence (keys >= kv_len[b] are padding and masked)
+    const int* kv_len;      // FULL (and the first-row CLS form), optional: valid keys per sequence (keys >= kv_len[b] are padding and masked)
     int cls_nq, cls_q0;     // CLS geometry generalised: cls_nq (<= 16) queries at tokens cls_q0 .. of the sequence (1, 0 = the CLS token)
     const int* cls_qpos;    // ... or ONE query per sequence at token cls_qpos[b] that sees the keys 0 .. cls_qpos[b] (causal)
     int cls_parts;          // fused backward: > 0 = cls_acc holds one partial per block ([B, heads, cls_parts, 3, dh]); 0 = atomics
@@ -130,6 +130,7 @@ __device__ __forceinline__ Grp decode(const AttnGeom& g, int gid) {
     else if (MODE == MODE_CLS) {
         r.sub = 0; r.b = gid; r.nq = g.cls_nq; r.nk = g.S;
         if (g.cls_qpos) { r.nq = 1; r.nk = g.cls_qpos[gid] + 1; }
+        else if (g.kv_len) { const int l = g.kv_len[gid]; r.nk = l < 1 ? 1 : (l < g.S ? l : g.S); }  // fwd_first: padded keys masked
     }
     else {
         r.sub = 0; r.b = gid; r.nq = g.S; r.nk = g.S;
@@ -2681,6 +2682,22 @@ extern "C" int ABI(fwd_tail)(const void* qkv, int ld, int B, int heads, int S, i
     if (rc) return rc;
     if (nq < 1 || nq > 16 || nq > S || ldo % 4) return TVTS_EINVAL;
     g.cls_nq = nq; g.cls_q0 = S - nq;
+    DISPATCH_MODE(attn_fwd_kernel, MODE_CLS, dim3(B * heads), dim3(256), 0, stream, g, (const bf16*)qkv, (bf16*)out, ldo, lse2);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+// ---- ONE query per sequence at token row 0 over the keys 0 .. nk - 1, nk = S or (kv_len: device int32[B]) clamp(kv_len[b], 1, S) as
+// in the FULL geometry: the last block of the v1 ViT in the forward-only encoder, read at the normed CLS token only
+// (v1/downstream/video_encoder_zero.py:198-199), and the last DistilBERT block, whose only consumer is the [CLS] row
+// (v1/model/model_dist_TVTS.py:131-141).  Forward-only; writes row b * S of out (and of lse2, if given) and nothing else.
+extern "C" int ABI(fwd_first)(const void* qkv, int ld, int B, int heads, int S, const int* kv_len, void* out, int ldo, float* lse2,
+                              hipStream_t stream) {
+    ATTN_OPTS(0);
+    AttnGeom g;
+    int rc = make_geom(g, MODE_CLS, B, heads, S, 0, 0, 0, ld);
+    if (rc) return rc;
+    if (!qkv || !out || ldo % 4) return TVTS_EINVAL;
+    g.kv_len = kv_len;
     DISPATCH_MODE(attn_fwd_kernel, MODE_CLS, dim3(B * heads), dim3(256), 0, stream, g, (const bf16*)qkv, (bf16*)out, ldo, lse2);
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;

@@ -97,6 +97,81 @@ extern "C" int tvts_patch_gather_tube(const float* video, const int* keep, int B
     return TVTS_OK;
 }
 
+// The same gather for CHANNEL-MAJOR clips [B, 3, T, H, W], the layout the v1 downstream classes take (their forward hands x to the
+// Conv3d as it comes, v1/downstream/video_encoder_zero.py:91-96,177): only the source address differs from the kernel above.
+__global__ __launch_bounds__(256) void patch_gather_tube_cm_kernel(const float* __restrict__ video, const int* __restrict__ keep,
+                                                                   int B, int tubes, int tb, int n, int img, int p,
+                                                                   bf16* __restrict__ out, int ldo) {
+    const int pp = p * p, K = 3 * tb * pp;
+    const int row = blockIdx.x;  // (b, tube, i)
+    const int i = row % n, tu = (row / n) % tubes, b = row / (n * tubes);
+    const int g = img / p;
+    const int pi = keep[(size_t)(b * tubes + tu) * n + i];
+    const int gy = pi / g, gx = pi % g;
+    const int T = tubes * tb;
+    for (int c8 = threadIdx.x * 8; c8 < K; c8 += 256 * 8) {
+        const int ch = c8 / (tb * pp), r1 = c8 % (tb * pp), t = r1 / pp, rem = r1 % pp, py = rem / p, px = rem % p;  // px % 8 == 0
+        const float* src = video + ((((size_t)(b * 3 + ch) * T + tu * tb + t) * img + gy * p + py) * img + gx * p + px);
+        const f32x4 a = *(const f32x4*)src, c = *(const f32x4*)(src + 4);
+        bf16x8 o = {(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], (bf16)c[0], (bf16)c[1], (bf16)c[2], (bf16)c[3]};
+        *(bf16x8*)(out + (size_t)row * ldo + c8) = o;
+    }
+}
+extern "C" int tvts_patch_gather_tube_cm(const float* video, const int* keep, int B, int tubes, int tubelet, int n, int img,
+                                         int patch, void* out, int ldo, hipStream_t stream) {
+    if (!video || !keep || !out || B <= 0 || tubes <= 0 || tubelet <= 0 || n <= 0 || patch <= 0 || img <= 0 || img % patch || patch % 8 ||
+        ldo % 8 || ldo < 3 * tubelet * patch * patch)
+        return TVTS_EINVAL;
+    hipLaunchKernelGGL(patch_gather_tube_cm_kernel, dim3(B * tubes * n), dim3(256), 0, stream, video, keep, B, tubes, tubelet, n,
+                       img, patch, (bf16*)out, ldo);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
+// ... and for the uint8 wire format: frames uint8 [B, T, H0, W0, 3] as the decoder leaves them, crop (an offset per sample, or the
+// centre crop with the round-half-to-even offsets of patch_gather_u8_kernel below), ClipToTensor (/ 255) and Normalize
+// ((v - mean) / std) of v1/downstream/ssv2.py:61-63 fused into the tubelet gather.  The operations and their order are those of
+// patch_gather_u8_kernel, so the bytes equal the fp32 kernel's on host-normalised frames.  A thread converts 8 neighbouring px
+// (24 interleaved source bytes apart by 3) and stores them as one 16-byte row piece.
+__global__ __launch_bounds__(256) void patch_gather_tube_u8_kernel(const unsigned char* __restrict__ frames, int H0, int W0,
+                                                                   const int* __restrict__ crop, const int* __restrict__ keep,
+                                                                   int B, int tubes, int tb, int n, int img, int p, float m0,
+                                                                   float m1, float m2, float s0, float s1, float s2,
+                                                                   bf16* __restrict__ out, int ldo) {
+    const int pp = p * p, K = 3 * tb * pp;
+    const int row = blockIdx.x;  // (b, tube, i)
+    const int i = row % n, tu = (row / n) % tubes, b = row / (n * tubes);
+    const int g = img / p;
+    const int pi = keep[(size_t)(b * tubes + tu) * n + i];
+    const int gy = pi / g, gx = pi % g;
+    const int T = tubes * tb;
+    const int dy = H0 - img, dx = W0 - img;
+    const int y0 = crop ? crop[2 * b] : (dy >> 1) + ((dy & 1) & (dy >> 1)), x0 = crop ? crop[2 * b + 1] : (dx >> 1) + ((dx & 1) & (dx >> 1));
+    for (int c8 = threadIdx.x * 8; c8 < K; c8 += 256 * 8) {
+        const int ch = c8 / (tb * pp), r1 = c8 % (tb * pp), t = r1 / pp, rem = r1 % pp, py = rem / p, px = rem % p;  // px % 8 == 0
+        const unsigned char* src = frames + (((size_t)(b * T + tu * tb + t) * H0 + y0 + gy * p + py) * W0 + x0 + gx * p + px) * 3 + ch;
+        const float mean = ch == 0 ? m0 : ch == 1 ? m1 : m2, sd = ch == 0 ? s0 : ch == 1 ? s1 : s2;
+        bf16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float u = (float)src[3 * e];
+            o[e] = (bf16)((u / 255.0f - mean) / sd);
+        }
+        *(bf16x8*)(out + (size_t)row * ldo + c8) = o;
+    }
+}
+extern "C" int tvts_patch_gather_tube_u8(const unsigned char* frames, int H0, int W0, const int* crop, const int* keep, int B,
+                                         int tubes, int tubelet, int n, int img, int patch, const float* mean3, const float* std3,
+                                         void* out, int ldo, hipStream_t stream) {
+    if (!frames || !keep || !out || !mean3 || !std3 || B <= 0 || tubes <= 0 || tubelet <= 0 || n <= 0 || patch <= 0 || img <= 0 || img % patch ||
+        patch % 8 || H0 < img || W0 < img || ldo % 8 || ldo < 3 * tubelet * patch * patch)
+        return TVTS_EINVAL;
+    hipLaunchKernelGGL(patch_gather_tube_u8_kernel, dim3(B * tubes * n), dim3(256), 0, stream, frames, H0, W0, crop, keep, B, tubes,
+                       tubelet, n, img, patch, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (bf16*)out, ldo);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
 // uint8 wire format: the frames arrive as the decoder leaves them -- uint8, H x W x 3 interleaved, already
 // resized on the host -- and the rest of the reference's transform chain runs here, fused into the tube-mask gather:
 // crop (video_transform.CenterCrop / RandomCrop = an offset per sample), ClipToTensor (float32 / 255) and Normalize

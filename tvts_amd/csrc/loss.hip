@@ -208,6 +208,48 @@ extern "C" int tvts_retrieval_ranks(const float* sims, long ld, int n_text, int 
     return TVTS_OK;
 }
 
+// ---- v1's published zero-shot protocol: video-to-video retrieval by label (v1/downstream/run_class_zero.py:344-413).  Row i of
+// sims holds the similarities of query video q = q0 + i to all N videos; element [i, q] is READ as -1000 (the script's self-mask,
+// :385-387; the matrix is not modified).  ranks[i] = #{ j : labels[j] != labels[q] and s'[i, j] > best_i }, best_i = max{ s'[i, j] :
+// labels[j] == labels[q] } (the query itself included, at -1000): the number of wrong-label videos in front of the first right-label
+// one, so that `ranks < k` is the script's hit within the first k of argsort(-scores) for every k <= 10 (:389-404).  Ties are
+// counted optimistically (strict >), like mode 0 above.  One block per query row, two passes over it (max, then count -- both exact
+// and order-independent; the second pass of a long row comes from L2).
+__global__ __launch_bounds__(256) void v2v_rank_kernel(const float* __restrict__ x, long ld, int q0, int N,
+                                                       const int* __restrict__ labels, float* __restrict__ ranks) {
+    __shared__ float redf[4];
+    __shared__ int redi[4];
+    const int i = blockIdx.x, q = q0 + i;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* row = x + (long)i * ld;
+    const int lq = labels[q];
+    float best = -INFINITY;
+    for (int j = threadIdx.x; j < N; j += 256) {
+        const float v = j == q ? -1000.0f : row[j];
+        if (labels[j] == lq) best = fmaxf(best, v);
+    }
+    best = wave_max(best);
+    if (lane == 0) redf[wave] = best;
+    __syncthreads();
+    best = fmaxf(fmaxf(redf[0], redf[1]), fmaxf(redf[2], redf[3]));
+    int greater = 0;
+    for (int j = threadIdx.x; j < N; j += 256) {
+        const float v = j == q ? -1000.0f : row[j];
+        greater += labels[j] != lq && v > best;
+    }
+    greater = (int)wave_sum((float)greater);  // counts < 2^24: exact in fp32
+    if (lane == 0) redi[wave] = greater;
+    __syncthreads();
+    if (threadIdx.x == 0) ranks[i] = (float)(redi[0] + redi[1] + redi[2] + redi[3]);
+}
+extern "C" int tvts_v2v_ranks(const float* sims, long ld, int nq, int q0, int N, const int* labels, float* ranks,
+                              hipStream_t stream) {
+    if (!sims || !labels || !ranks || N <= 0 || nq <= 0 || q0 < 0 || (long)q0 + nq > N || ld < N || N >= (1 << 24)) return TVTS_EINVAL;
+    hipLaunchKernelGGL(v2v_rank_kernel, dim3(nq), dim3(256), 0, stream, sims, ld, q0, N, labels, ranks);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
 // ---- SSv2 multiple-choice scoring (v2/downstream/zero_ssv2_mc_TVTSv2_ViT_B_16.py:80-88): every clip b against ITS OWN candidate
 // captions.  text [C, B, E] (option-major, as the _mc models return it), video [B, E] -> logits[b, c] = 100 <v_b, t_cb> /
 // (|v_b| |t_cb|), plain norms (no eps clamp, as the script).  A wave per (b, c): lanes stride the E columns, then a fixed xor

@@ -1,0 +1,130 @@
+"""Drop-in for v1/downstream/video_encoder_zero.py and v1/downstream/video_encoder.py: ``VisionTransformer(img_size=224,
+patch_size=16, ..., num_frames=16, tubelet_size=2)`` -- the pretrain video tower without mask (Conv3d tubelet embedding, joint
+space-time attention, pre-LN blocks), read at the normed CLS token (video_encoder_zero.py:176-207), plus ``head`` when
+``num_classes > 0`` (video_encoder.py:204-208) -- over the forward-only encoder of the HIP engine (EngineV1.encode_video).
+
+Same constructor keywords, same state-dict keys in the same order (``cls_token, pos_embed, temporal_embed, patch_embed.proj.*,
+blocks.i.*, norm.*[, head.*]``), so ``model.load_state_dict(state_dict, strict=False)`` works as v1/downstream/run_class_zero.py
+uses it (:336-340); ``VisionTransformer.from_pretrain(checkpoint, ...)`` applies the script's ``module.video_model.`` key filter.
+The parameter store holds the video tower and the head only (no DistilBERT, no sorting head).  Inference only: every call runs
+under ``no_grad``, parameters have ``requires_grad=False``; dropout / drop-path rates are accepted and have no effect.
+"""
+from __future__ import annotations
+
+import functools
+
+import torch
+import torch.nn as nn
+
+from .. import hip as K
+from ..arch import ARCH_V1
+from ..engine import ParamStore
+from ..engine_v1 import EngineV1
+from ..model._common import _require_gpu
+from ..model.model_dist_TVTS import _encode_video_v1, reference_init_v1_
+
+_PREFIX = "video_model."
+
+
+def _norm_eps(norm_layer):
+    """the eps of the reference's norm_layer argument: None = partial(nn.LayerNorm, eps=1e-6) (video_encoder_zero.py:122)"""
+    if norm_layer is None:
+        return 1e-6
+    if isinstance(norm_layer, functools.partial) and norm_layer.func is nn.LayerNorm and not norm_layer.args:
+        return float(norm_layer.keywords.get("eps", 1e-5))
+    if norm_layer is nn.LayerNorm:
+        return 1e-5
+    raise NotImplementedError("norm_layer: only nn.LayerNorm is built")
+
+
+class VisionTransformer(nn.Module):
+    def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=0, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4.,
+                 qkv_bias=True, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0., norm_layer=None, num_frames=16,
+                 tubelet_size=2, representation_size=None, device_index=0, init_seed=0):
+        super().__init__()
+        if not qkv_bias:
+            raise NotImplementedError("qkv_bias=False is not built (every shipped v1 checkpoint has the bias)")
+        if representation_size:
+            raise NotImplementedError("representation_size (the pre_logits layer) is not built")
+        if embed_dim % num_heads or embed_dim // num_heads != 64:
+            raise NotImplementedError(f"the v1 encoder's attention kernels are used at head dim 64, not {embed_dim}/{num_heads}")
+        if in_chans != 3 or float(mlp_ratio) != 4.0:
+            raise NotImplementedError("in_chans = 3 and mlp_ratio = 4 are what is built")
+        if qk_scale is not None and abs(float(qk_scale) - 64 ** -0.5) > 1e-12:
+            raise NotImplementedError("qk_scale other than head_dim ** -0.5 is not built")
+        if _norm_eps(norm_layer) != 1e-6:
+            raise NotImplementedError("LayerNorm eps other than 1e-6 is not built")
+        img_size = img_size[0] if isinstance(img_size, (tuple, list)) else img_size
+        patch_size = patch_size[0] if isinstance(patch_size, (tuple, list)) else patch_size
+        if img_size % patch_size or patch_size % 8 or tubelet_size < 1 or num_frames < tubelet_size or num_classes < 0:
+            raise ValueError("img_size must be a multiple of patch_size, patch_size of 8, num_frames >= tubelet_size >= 1")
+        self.num_classes = int(num_classes)
+        self.num_features = self.embed_dim = int(embed_dim)
+        self.tubelet_size = int(tubelet_size)
+        self.patches_per_frame = (img_size // patch_size) ** 2
+        self.arch = dict(ARCH_V1, name="v1_video", image=int(img_size), patch=int(patch_size), tubelet=int(tubelet_size),
+                         width=int(embed_dim), heads=int(num_heads), layers=int(depth), num_frames=int(num_frames),
+                         towers="video", head_classes=self.num_classes, sort_head=False)
+        dev = _require_gpu(device_index)
+        self.store = ParamStore(self.arch, dev)
+        self.engine = EngineV1(self.store)
+        self.engine.training = False
+        reference_init_v1_(self.store, init_seed)
+        for name in self.store.shapes:  # the reference's names: the tower's without the pretrain model's prefix
+            parts = (name[len(_PREFIX):] if name.startswith(_PREFIX) else name).split(".")
+            mod = self
+            for p in parts[:-1]:
+                if p not in mod._modules:
+                    mod.add_module(p, nn.Module())
+                mod = mod._modules[p]
+            mod.register_parameter(parts[-1], nn.Parameter(self.store.p(name), requires_grad=False))
+        self._versions = None
+        self.eval()
+
+    @staticmethod
+    def pretrain_state_dict(checkpoint):
+        """the video tower's entries of a pretrain checkpoint ({'state_dict': ...} or the state dict itself) under this class's
+        names: the key filter of v1/downstream/run_class_zero.py:336-338"""
+        sd = checkpoint["state_dict"] if "state_dict" in checkpoint else checkpoint
+        return {k.replace("module.video_model.", ""): v for k, v in sd.items() if "module.video_model." in k}
+
+    @classmethod
+    def from_pretrain(cls, checkpoint, **kwargs):
+        """a model with the video tower of a pretrain checkpoint loaded the way the script does (strict=False: `head.*` keeps its
+        initialisation); checkpoint: a path, {'state_dict': ...} or a state dict with `module.video_model.` keys"""
+        if isinstance(checkpoint, (str, bytes)) or hasattr(checkpoint, "__fspath__"):
+            checkpoint = torch.load(checkpoint, map_location="cpu", weights_only=False)
+        model = cls(**kwargs)
+        sd = cls.pretrain_state_dict(checkpoint)
+        if not sd:
+            raise KeyError("the checkpoint has no `module.video_model.` entries")
+        model.load_state_dict(sd, strict=False)
+        return model
+
+    def no_weight_decay(self):
+        return {"pos_embed", "cls_token"}
+
+    def _fresh_shadows(self):
+        """re-derive the bf16 weight shadows iff some parameter changed since the last refresh (load_state_dict copies in place)"""
+        vers = tuple(p._version for p in self.parameters())
+        if vers != self._versions:
+            self.store.refresh_shadows()
+            self._versions = vers
+
+    @torch.no_grad()
+    def forward_features(self, x):
+        """x: fp32 [B, 3, T, H, W] (the reference's layout) or uint8 frames [B, T, H0, W0, 3] (centre crop + normalisation on the
+        device) -> [B, embed_dim] = norm(blocks(tokens))[:, 0]"""
+        self._fresh_shadows()
+        feat, _ = _encode_video_v1(self.engine, x, None, channel_major=True, project=False)
+        return feat.clone()
+
+    @torch.no_grad()
+    def forward(self, x):
+        feat = self.forward_features(x)
+        if self.num_classes == 0:
+            return feat
+        B, W, C = feat.shape[0], self.embed_dim, self.num_classes
+        logits = torch.empty(B, C, dtype=torch.float32, device=feat.device)
+        K.gemm_small(feat, self.store.p("head.weight"), logits, M=B, N=C, K=W, sa=(W, 1), sb=(1, W), bias=self.store.p("head.bias"))
+        return logits

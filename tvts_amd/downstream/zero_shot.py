@@ -86,3 +86,34 @@ def accuracy(logits: torch.Tensor, target: torch.Tensor, topk=(1,)):
     own = logits.gather(1, target.view(-1, 1).long())
     higher = (logits > own).sum(dim=1)  # classes scoring above the target
     return [float((higher < k).sum()) for k in topk]
+
+
+# ---- v1's published zero-shot protocol: video-to-video retrieval by label (v1/downstream/run_class_zero.py:344-413)
+@torch.no_grad()
+def v2v_ranks(feats: torch.Tensor, labels: torch.Tensor, chunk: int = 2048) -> torch.Tensor:
+    """ranks [N] (fp32, exact integers) of the script's protocol: features [N, D] are normalised as its sim_matrix does (norms
+    clamped at 1e-8, :348-356), every video queries all the others (its own score read as -1000, :385-387), and
+    ranks[q] = the number of other-label videos scoring above the best same-label one -- `ranks < k` is the script's hit among the
+    first k of argsort(-scores) for k <= 10 (:389-404).  The similarities are formed `chunk` query rows at a time
+    (tvts_gemm_small_f32 into a [chunk, N] workspace, then tvts_v2v_ranks): the [N, N] matrix never exists."""
+    x = feats.contiguous().float()
+    if x.dim() != 2 or x.shape[0] == 0 or labels.numel() != x.shape[0] or chunk < 1:
+        raise ValueError(f"v2v_ranks: features {tuple(x.shape)} need one label each, got {tuple(labels.shape)}")
+    N, D = x.shape
+    lab = labels.reshape(-1).to(x.device, torch.int32).contiguous()
+    xn, inv = torch.empty_like(x), torch.empty(N, dtype=torch.float32, device=x.device)
+    K.l2norm_rows(x, xn, inv, 1e-8)
+    chunk = min(int(chunk), N)
+    sims = torch.empty(chunk, N, dtype=torch.float32, device=x.device)
+    ranks = torch.empty(N, dtype=torch.float32, device=x.device)
+    for q0 in range(0, N, chunk):
+        nq = min(chunk, N - q0)
+        K.gemm_small(xn[q0:], xn, sims, M=nq, N=N, K=D, sa=(D, 1), sb=(1, D))
+        K.v2v_ranks(sims[:nq], q0, lab, ranks[q0:q0 + nq])
+    return ranks
+
+
+def recall_at(ranks, ks=(1, 5, 10)):
+    """R@k in percent, as the script prints them (:407-409): 100 * #{ranks < k} / N"""
+    r = torch.as_tensor(ranks).reshape(-1)
+    return [100.0 * float((r < k).sum()) / r.numel() for k in ks]

@@ -56,7 +56,7 @@ class ParamStore:
         self.toff: Dict[str, int] = {}
         toff, tiles = 0, []
         for name, shape in self.shapes.items():
-            if not is_mfma_weight(name, shape):
+            if not is_mfma_weight(name, shape, arch):
                 continue
             R, C = shape[0], int(np.prod(shape[1:]))
             self.toff[name] = toff

@@ -307,3 +307,105 @@ class EngineV1(Engine):
         else:
             K.sort_assemble_bwd(None, dcls, dout, None, B=B, S=S, off=0, Sv=S, NT=NT)
         self.video_backward_v1(dout, pb["keep"], B, pb["tubes"])
+
+    # ------------------------------------------------------------------ forward-only encoders (feature extraction, retrieval)
+    # The v1 counterparts of Engine.encode_video / encode_text: the same kernels in the same order as video_forward_v1 /
+    # text_forward_v1, on the encoder workspaces (_ib) instead of the step's named tensors -- nothing of Engine.buf is read,
+    # written or resized, so a call between two training steps leaves the step alone.  No log-sum-exp, no pre-activations, no
+    # LayerNorm statistics are kept, and the LAST block of either tower runs for the rows the model reads: its keys / values come
+    # from every row, its one query per sequence is the CLS / [CLS] row (tvts_attn_fwd_first), and everything behind the attention
+    # (output projection, residuals, LayerNorms, MLP / FFN) is computed for those B (N) rows only.
+    # Seed rule: the text encoder NEVER applies dropout and NEVER advances drop_seed, whatever `training` says -- it is an
+    # inference call, and an encoder call between two training steps must not shift the step's mask sequence.
+    # Base-class refusal (_inf_check) stays for encode_text_packed: there is no packed DistilBERT pass.
+    def encode_video(self, video, keep, B, tubes, crop=None, channel_major=False, project=True):
+        """-> (feat [B, W] fp32 = the normed CLS token, emb [B, E] = vid_proj(feat)).  Both are encoder workspaces: the next
+        encoder call overwrites them.  project=False returns emb = None (a store without vid_proj: the downstream class).
+        video, on the device: fp32 [B, T, 3, H, W]; fp32 [B, 3, T, H, W] with channel_major (the layout of the v1 downstream
+        classes); or uint8 [B, T, H0, W0, 3].  keep: int32 [B, tubes, n].
+        crop (uint8 only): int32 [B, 2] (top, left) inside the frame, None = centre crop.  It is an argument of the engine alone:
+        TVTS.encode_video and the downstream class always take the centre crop."""
+        a, P, f32 = self.arch, self.P, torch.float32
+        W, E, p, tb, hv = a["width"], a["embed"], a["patch"], a["tubelet"], a["heads"]
+        n = keep.shape[2]
+        S = 1 + tubes * n
+        M, Mp = B * S, B * tubes * n
+        cols = self._ib("im2col", (Mp, P.conv_k))
+        if video.dtype == torch.uint8:
+            K.patch_gather_tube_u8(video, keep, cols, B=B, tubes=tubes, tubelet=tb, n=n, img=a["image"], patch=p, crop=crop)
+        else:
+            K.patch_gather_tube(video, keep, cols, B=B, tubes=tubes, tubelet=tb, n=n, img=a["image"], patch=p,
+                                channel_major=channel_major)
+        pe = self._ib("patch", (Mp, W), f32)
+        K.gemm_nt(cols, P.w_conv(), pe, M=Mp, bias=P.p("video_model.patch_embed.proj.bias"))
+        tok = self._ib("x", (M, W), f32)
+        K.vit_assemble(pe, P.p("video_model.cls_token").view(W), P.p("video_model.pos_embed").view(-1, W),
+                       P.p("video_model.temporal_embed").view(-1, W), keep, tok, B=B, T=tubes, n=n)
+        vid_rows = self._ib("vid_rows", (B,), torch.int32)
+        vid_rows.copy_(torch.arange(B, device=self.dev, dtype=torch.int32) * S)
+        x_c = self._blocks_fwd(
+            "video_model.blocks.", _VIT_NAMES, tok, None, a["layers"], hv, "gelu", 1e-6,
+            lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hv, S=S, causal=False, head_dim=W // hv),
+            rows=vid_rows, attn_rows=lambda qkv, att, lse: K.attn_fwd_first(qkv, None, att, lse, B=B, heads=hv, S=S, head_dim=W // hv))
+        feat = self._ib("vfeat", (B, W), f32)
+        self._ln(x_c, "video_model.norm", 1e-6, feat, None)
+        if not project:
+            return feat, None
+        emb = self._ib("vemb", (B, E), f32)
+        K.gemm_small(feat, P.p("vid_proj.0.weight"), emb, M=B, N=E, K=W, sa=(W, 1), sb=(1, W), bias=P.p("vid_proj.0.bias"))
+        return feat, emb
+
+    def encode_text(self, ids, kv_len, N, L):
+        """-> (before [N, Wt] fp32 = DistilBERT's last hidden state at [CLS], emb [N, E] = txt_proj(relu(before))); both encoder
+        workspaces.  ids int32 [N, L], kv_len int32 [N] (right-padded captions) on the device.  No dropout, drop_seed untouched."""
+        a, P, f32 = self.arch, self.P, torch.float32
+        Wt, h, Ff, E, M, nl = a["text_width"], a["text_heads"], a["text_ffn"], a["embed"], N * L, a["text_layers"]
+        emb = self._ib("s", (M, Wt), f32)
+        K.text_embed(ids, P.p("text_model.embeddings.word_embeddings.weight"),
+                     P.p("text_model.embeddings.position_embeddings.weight"), emb, N=N, L=L)
+        x, xb = self._ib("x", (M, Wt), f32), self._ib("ln", (M, Wt))
+        self._ln(emb, "text_model.embeddings.LayerNorm", 1e-12, x, None)
+        K.cast_f32_bf16(x, xb)
+        for l in range(nl):  # POST-LN blocks, x / xb updated in place (forward-only _pln_fwd)
+            pre = f"text_model.transformer.layer.{l}."
+            last = l == nl - 1
+            R = N if last else M
+            qkv = self._ib("qkv", (M, 3 * Wt))
+            for i, lin in enumerate(("q_lin", "k_lin", "v_lin")):
+                w_, b_ = P.w(pre + f"attention.{lin}.weight"), P.p(pre + f"attention.{lin}.bias")
+                if last and i == 0:  # the one query of every caption: its [CLS] row (row stride L of the operand and of qkv)
+                    K.gemm_nt(xb.view(N, L * Wt)[:, :Wt], w_, qkv.view(N, L * 3 * Wt)[:, :Wt], M=N, bias=b_)
+                else:
+                    K.gemm_nt(xb, w_, qkv[:, i * Wt:(i + 1) * Wt], M=M, bias=b_)
+            att = self._ib("att", (M, Wt))
+            res = x
+            if last:
+                K.attn_fwd_first(qkv, kv_len, att, None, B=N, heads=h, S=L, head_dim=self.dh_text)
+                att_r, res = self._ib("att_r", (N, Wt)), self._ib("x_r", (N, Wt), f32)
+                cls_rows = self._ib("cls_rows", (N,), torch.int32)
+                cls_rows.copy_(torch.arange(N, device=self.dev, dtype=torch.int32) * L)
+                K.rows_move("gather", cls_rows, full_bf16=att, packed_bf16=att_r)
+                K.rows_move("gather", cls_rows, full_f32=x, packed_f32=res)
+                att = att_r
+            else:
+                K.attn_fwd_len(qkv, kv_len, att, None, B=N, heads=h, S=L, head_dim=self.dh_text)
+            pre1 = self._ib("s", (R, Wt), f32)
+            self._lin(att, pre + "attention.out_lin.weight", pre + "attention.out_lin.bias", pre1, R, residual=res)
+            x1, x1b = self._ib("x1", (R, Wt), f32), self._ib("lnc", (R, Wt))
+            self._ln(pre1, pre + "sa_layer_norm", 1e-12, x1, None)
+            K.cast_f32_bf16(x1, x1b)
+            hact = self._ib("h", (R, Ff))
+            self._lin(x1b, pre + "ffn.lin1.weight", pre + "ffn.lin1.bias", hact, R, act="gelu")
+            pre2 = self._ib("s", (R, Wt), f32)  # (pre1 is dead: x1 carries the residual)
+            self._lin(hact, pre + "ffn.lin2.weight", pre + "ffn.lin2.bias", pre2, R, residual=x1)
+            if last:
+                before = self._ib("tbefore", (N, Wt), f32)
+                self._ln(pre2, pre + "output_layer_norm", 1e-12, before, None)
+            else:
+                self._ln(pre2, pre + "output_layer_norm", 1e-12, x, None)
+                K.cast_f32_bf16(x, xb)
+        act = self._ib("trelu", (N, Wt), f32)
+        K.relu(before, act)
+        t = self._ib("temb", (N, E), f32)
+        K.gemm_small(act, P.p("txt_proj.1.weight"), t, M=N, N=E, K=Wt, sa=(Wt, 1), sb=(1, Wt), bias=P.p("txt_proj.1.bias"))
+        return before, t

@@ -712,6 +712,16 @@ def attn_fwd_rowq(qkv, qpos, out, lse2, *, B, heads, S, head_dim=64):
          "tvts_attn_fwd_rowq")
 
 
+def attn_fwd_first(qkv, kv_len, out, lse2, *, B, heads, S, head_dim=64):
+    """one query per sequence at token row 0 over the keys 0 .. nk - 1 (nk = S, or clamp(kv_len[b], 1, S) with the int32 device
+    tensor kv_len); forward-only: row b*S of out (and of lse2, if given) is written and no other."""
+    lib = _lib.load()
+    assert kv_len is None or (kv_len.dtype == torch.int32 and kv_len.numel() == B)
+    assert qkv.shape[0] >= B * S and out.shape[0] >= B * S
+    _chk(_attn_fn(lib, "fwd_first", head_dim)(_p(qkv), _ld(qkv), B, heads, S, _p(kv_len), _p(out), _ld(out), _p(lse2), _stream()),
+         "tvts_attn_fwd_first")
+
+
 def attn_fwd_packed(qkv, seq_start, out, *, N, heads, max_len, last_only=False):
     """causal attention inside each sequence of a packed batch (seq_start int32 [N + 1], rows seq_start[i] .. seq_start[i + 1] - 1),
     head dim 64, forward-only.  last_only: one query per sequence at its last row; only those N rows of out are written."""
@@ -851,12 +861,31 @@ def vit_assemble_bwd(dtok, keep, dpatch, dcls, dpos, dtemporal, *, B, T, n):
          "tvts_vit_assemble_bwd")
 
 
-def patch_gather_tube(video, keep, out, *, B, tubes, tubelet, n, img, patch):
-    """v1 tubelet im2col: video fp32 [B, T, 3, img, img], keep int32 [B, tubes, n] -> out bf16 [B*tubes*n, 3*tubelet*patch^2]"""
+def patch_gather_tube(video, keep, out, *, B, tubes, tubelet, n, img, patch, channel_major=False):
+    """v1 tubelet im2col: video fp32 [B, T, 3, img, img] (channel_major: [B, 3, T, img, img], the layout of the v1 downstream
+    classes), keep int32 [B, tubes, n] -> out bf16 [B*tubes*n, 3*tubelet*patch^2]"""
     lib = _lib.load()
     assert video.dtype == torch.float32 and keep.dtype == torch.int32 and keep.dim() == 3
+    if channel_major:
+        assert video.is_contiguous() and tuple(video.shape) == (B, 3, tubes * tubelet, img, img) and tuple(keep.shape) == (B, tubes, n)
+        _chk(lib.tvts_patch_gather_tube_cm(_p(video), _p(keep), B, tubes, tubelet, n, img, patch, _p(out), _ld(out), _stream()),
+             "tvts_patch_gather_tube_cm")
+        return
     _chk(lib.tvts_patch_gather_tube(_p(video), _p(keep), B, tubes, tubelet, n, img, patch, _p(out), _ld(out), _stream()),
          "tvts_patch_gather_tube")
+
+
+def patch_gather_tube_u8(frames, keep, out, *, B, tubes, tubelet, n, img, patch, crop=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """v1 tubelet im2col from uint8 frames [B, T, H0, W0, 3] on the device: crop (int32 [B, 2] (top, left), None = centre crop),
+    / 255 and Normalize fused into the gather; keep int32 [B, tubes, n] -> out bf16 [B*tubes*n, 3*tubelet*patch^2]"""
+    lib = _lib.load()
+    assert frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() == 5 and frames.shape[-1] == 3
+    assert frames.shape[0] == B and frames.shape[1] == tubes * tubelet
+    assert keep.dtype == torch.int32 and keep.is_contiguous() and tuple(keep.shape) == (B, tubes, n)
+    assert crop is None or (crop.dtype == torch.int32 and crop.is_contiguous() and tuple(crop.shape) == (B, 2))
+    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    _chk(lib.tvts_patch_gather_tube_u8(_p(frames), frames.shape[2], frames.shape[3], _p(crop), _p(keep), B, tubes, tubelet, n, img,
+                                       patch, m3, s3, _p(out), _ld(out), _stream()), "tvts_patch_gather_tube_u8")
 
 
 def text_embed(ids, emb, pos, x, *, N, L):
@@ -1012,6 +1041,23 @@ def retrieval_ranks(sims, mode, valid=None):
     assert valid is None or (valid.dtype == torch.uint8 and valid.numel() == nt and valid.is_contiguous())
     _chk(lib.tvts_retrieval_ranks(_p(sims), sims.stride(0), nt, nv, 0 if mode == "t2v" else 1, _p(valid), _p(ranks), _stream()),
          "tvts_retrieval_ranks")
+    return ranks
+
+
+def v2v_ranks(sims, q0, labels, ranks=None, N=None):
+    """label-matched video-to-video ranks (v1/downstream/run_class_zero.py:344-413): row i of sims fp32 [nq, >= N] = query video
+    q0 + i against all N videos (its own entry is read as -1000), labels int32 [N] -> ranks fp32 [nq] = the number of
+    other-label videos scoring above the best same-label one."""
+    lib = _lib.load()
+    assert sims.dtype == torch.float32 and sims.dim() == 2 and sims.stride(1) == 1
+    assert labels.dtype == torch.int32 and labels.is_contiguous()
+    N = labels.numel() if N is None else N
+    nq = sims.shape[0]
+    assert sims.shape[1] >= N and labels.numel() >= N
+    if ranks is None:
+        ranks = torch.empty(nq, dtype=torch.float32, device=sims.device)
+    assert ranks.dtype == torch.float32 and ranks.is_contiguous() and ranks.numel() >= nq
+    _chk(lib.tvts_v2v_ranks(_p(sims), sims.stride(0), nq, int(q0), N, _p(labels), _p(ranks), _stream()), "tvts_v2v_ranks")
     return ranks
 
 

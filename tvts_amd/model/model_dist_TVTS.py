@@ -91,3 +91,69 @@ class TVTS(TVTSv2Base):
         S = 1 + tubes * keep.shape[2]
         out, emb = self.engine.video_forward_v1(v, keep, B, tubes, (torch.arange(B) * S).to(torch.int32).to(self.store.device))
         return out.view(B, S, -1).clone(), emb.clone()
+
+    # forward-only encoders (feature extraction, retrieval): EngineV1.encode_video / encode_text -- no per-layer activations, the
+    # last block of either tower for the rows the model reads, never any dropout (whatever .training says) and no advance of
+    # the training step's mask seed
+    @torch.no_grad()
+    def encode_video(self, video, keep_ind=None, project=True):
+        """-> [B, E] video embeddings, or with project=False the normed CLS feature [B, W] (compute_video's tokens[:, 0]).
+        video: fp32 [B, T, 3, H, W] or uint8 [B, T, H0, W0, 3] frames (centre crop, / 255, ImageNet Normalize on the device);
+        keep_ind: kept patches per tube [tubes, n] (every clip) or [B, tubes, n], None = every patch of every tube."""
+        self._fresh_shadows()
+        feat, emb = _encode_video_v1(self.engine, video, keep_ind, channel_major=False, project=project)
+        return (emb if project else feat).clone()
+
+    @torch.no_grad()
+    def encode_text(self, text_dict):
+        """-> [N, E] caption embeddings (compute_text's second output in eval mode) from the tokenizer's
+        {'input_ids', 'attention_mask'} (right-padded)."""
+        self._fresh_shadows()
+        a, dev = self.arch, self.store.device
+        ids = text_dict["input_ids"].detach().to("cpu", torch.int64)
+        mask = text_dict["attention_mask"].detach().to("cpu", torch.int64)
+        if ids.dim() != 2 or ids.numel() == 0 or mask.shape != ids.shape:
+            raise ValueError(f"text: expected [N, L] input_ids and attention_mask, got {tuple(ids.shape)} / {tuple(mask.shape)}")
+        lens = mask.sum(-1)
+        if not bool((mask == (torch.arange(mask.shape[1])[None] < lens[:, None])).all()) or int(lens.min()) < 1:
+            raise ValueError("attention_mask must be a non-empty right-padded prefix mask")
+        N, L = ids.shape[0], int(lens.max())
+        if int(ids.min()) < 0 or int(ids.max()) >= a["vocab"] or L > a["max_pos"]:
+            raise IndexError(f"token ids must lie in [0, {a['vocab']}) and captions within the {a['max_pos']} positions")
+        _, t = self.engine.encode_text(ids[:, :L].to(torch.int32).contiguous().to(dev), lens.to(torch.int32).to(dev), N, L)
+        return t.clone()
+
+
+def _encode_video_v1(engine, video, keep_ind, channel_major, project):
+    """the argument checks of the v1 video encoders (TVTS.encode_video, downstream VisionTransformer) in front of
+    EngineV1.encode_video; mirrors TVTSv2Base.encode_video.  channel_major: fp32 clips arrive as [B, 3, T, H, W]."""
+    a, dev = engine.arch, engine.dev
+    if video.dim() != 5:
+        raise ValueError(f"video: expected a 5-D clip batch, got {tuple(video.shape)}")
+    if video.dtype == torch.uint8:
+        if video.shape[-1] != 3 or video.shape[2] < a["image"] or video.shape[3] < a["image"]:
+            raise ValueError(f"uint8 video must be [B, T, H, W, 3] with H, W >= {a['image']}, got {tuple(video.shape)}")
+        v = video.to(dev).contiguous()
+        T, channel_major = v.shape[1], False
+    else:
+        want = (3, None, a["image"], a["image"]) if channel_major else (None, 3, a["image"], a["image"])
+        if any(w is not None and w != s for w, s in zip(want, video.shape[1:])):
+            raise ValueError(f"video must be fp32 {'[B, 3, T, H, W]' if channel_major else '[B, T, 3, H, W]'} with H = W = "
+                             f"{a['image']} (or uint8 [B, T, H0, W0, 3]), got {tuple(video.shape)}")
+        v = video.to(dev, torch.float32).contiguous()
+        T = v.shape[2] if channel_major else v.shape[1]
+    B, tb = v.shape[0], a["tubelet"]
+    if T == 0 or T % tb:
+        raise ValueError(f"clips of {T} frames: not a multiple of the tubelet size {tb}")
+    if T > a["num_frames"]:
+        raise ValueError(f"clips of {T} frames, the temporal embedding has {a['num_frames'] // tb} rows of {tb} frames")
+    tubes, ppf = T // tb, (a["image"] // a["patch"]) ** 2
+    kc = torch.arange(ppf).view(1, 1, ppf).expand(1, tubes, ppf) if keep_ind is None else keep_ind
+    if kc.dim() == 2:
+        kc = kc.unsqueeze(0)
+    if kc.dim() != 3 or kc.shape[0] not in (1, B) or kc.shape[1] != tubes or kc.shape[2] == 0:
+        raise ValueError(f"keep_ind {tuple(kc.shape)}: expected [{tubes}, n_keep] or [{B}, {tubes}, n_keep]")
+    if int(kc.min()) < 0 or int(kc.max()) >= ppf:
+        raise IndexError(f"keep_ind must index the {ppf} patches of a frame")
+    keep = kc.expand(B, -1, -1).to(dev, torch.int32).contiguous()
+    return engine.encode_video(v, keep, B, tubes, channel_major=channel_major, project=project)
