@@ -79,11 +79,15 @@ def engine(arch, params, cls=Engine):
     return cls(store)
 
 
-def train(arch, steps=1, v1=False, n_trans=None):
+def train(arch, steps=1, v1=False, n_trans=None, training=True, between=None):
+    """between(eng): called between two steps (what runs there must leave the next step's launches and buffers alone)"""
     mod = V if v1 else O
     eng = engine(arch, mod.synth_params(arch, seed=5), EngineV1 if v1 else Engine)
+    eng.training = training  # (read by the v1 engine only: False = the text tower's dropout off)
     batch = mod.synth_batch(arch, B=4, T=4, seed=6, n_trans=n_trans, caption_len=11)
-    for _ in range(steps):
+    for i in range(steps):
+        if i and between is not None:
+            between(eng)
         te, ve, pred = eng.forward(eng.prepare_batch(batch))
         d_pred = None if pred is None else torch.full_like(pred, 0.01)  # (one transcript per clip: no sorting loss)
         eng.backward(torch.full_like(te, 0.01), torch.full_like(ve, 0.01), d_pred)
@@ -117,6 +121,57 @@ def enc_text():
     eng.encode_text_packed(packed.to(DEV), seq_start.to(DEV), N, max_len)
 
 
+def v1_video_calls(eng, arch):
+    """every input form of EngineV1.encode_video at B = 3, T = 4"""
+    B, T, tubes, img = 3, 4, 4 // arch["tubelet"], arch["image"]
+    b = V.synth_batch(arch, B=B, T=T, seed=7, n_trans=1)
+    keep = b["keep_ind"].to(DEV, torch.int32).contiguous()
+    g = torch.Generator().manual_seed(8)
+    frames = torch.randint(0, 256, (B, T, img + 16, img + 32, 3), generator=g, dtype=torch.uint8).to(DEV)
+    crop = torch.stack([torch.randint(0, 17, (B,), generator=g), torch.randint(0, 33, (B,), generator=g)], 1).to(torch.int32).to(DEV)
+    clip = b["video"].to(DEV)
+    eng.encode_video(clip, keep, B, tubes)
+    eng.encode_video(clip.permute(0, 2, 1, 3, 4).contiguous(), keep, B, tubes, channel_major=True)
+    eng.encode_video(frames, keep, B, tubes)  # (crop None: the centre crop)
+    eng.encode_video(frames, keep, B, tubes, crop=crop)
+    eng.encode_video(clip, keep, B, tubes, project=False)
+    ppf = (img // arch["patch"]) ** 2
+    eng.encode_video(clip, torch.arange(ppf, dtype=torch.int32).expand(B, tubes, ppf).contiguous().to(DEV), B, tubes)
+
+
+def v1_captions(arch):
+    """N = 6 right-padded captions of enc_text's lengths ([CLS], words, [SEP]) -> the arguments of EngineV1.encode_text"""
+    g, lens = torch.Generator().manual_seed(9), torch.tensor((5, 9, 11, 7, 16, 9))
+    N, L = lens.numel(), int(lens.max())
+    ids = torch.zeros(N, L, dtype=torch.int64)
+    for r, cl in enumerate(lens.tolist()):
+        ids[r, 0], ids[r, cl - 1] = arch["vocab"] - 2, arch["vocab"] - 1
+        ids[r, 1:cl - 1] = torch.randint(1, arch["vocab"] - 2, (cl - 2,), generator=g)
+    return ids.to(torch.int32).to(DEV), lens.to(torch.int32).to(DEV), N, L
+
+
+def enc_v1_video():
+    arch = A.small_arch_v1()
+    v1_video_calls(engine(arch, V.synth_params(arch, seed=5), EngineV1), arch)
+
+
+def enc_v1_text():
+    arch = A.small_arch_v1()
+    eng = engine(arch, V.synth_params(arch, seed=5), EngineV1)
+    halves, caps = [], v1_captions(arch)
+    for eng.training in (True, False):  # an encoder call never applies dropout: the same launches either way
+        n = len(LINES)
+        eng.encode_text(*caps)
+        halves.append(LINES[n:])
+    assert halves[0] == halves[1], "encode_text depends on engine.training"
+
+
+def train_v1_enc_train():
+    """an encoder call of either tower between two steps: the second step's lines show the first step's buffers"""
+    arch = A.small_arch_v1()
+    train(arch, steps=2, v1=True, between=lambda eng: (eng.encode_text(*v1_captions(arch)), v1_video_calls(eng, arch)))
+
+
 SCENARIOS = {
     "train-small": lambda: train(A.small_arch()),
     "train-small-fp32": lambda: train(A.small_arch(hybrid_stream=False)),
@@ -133,6 +188,10 @@ SCENARIOS = {
     "train-v1-dense": lambda: train(A.small_arch_v1(sort_used_rows_only=False), v1=True),
     "enc-video": enc_video,
     "enc-text": enc_text,
+    "enc-v1-video": enc_v1_video,
+    "enc-v1-text": enc_v1_text,
+    "train-v1-eval": lambda: train(A.small_arch_v1(), v1=True, training=False),  # the dp == 0 branches of _pln_fwd / _pln_bwd
+    "train-v1-enc-train": train_v1_enc_train,
 }
 
 if __name__ == "__main__":

@@ -90,6 +90,8 @@ ONE_OFF = collections.OrderedDict([
     ("next_rows.jsonl", "validation forward + metrics (N1), downstream model (N2), uint8-fed step (N3) throughput"),
     ("forward_unify_trace.txt", "`tools/launch_trace.py` before / after the training step and the forward-only encoders were given one forward wiring: the same launches on the same buffers, scenario by scenario"),
     ("backward_unify.txt", "the same check for the backward wiring (one pre-LN block, one tower walk per direction, `video_backward` in stages), over the widened scenario set; the eager step against the parent commit in alternating runs at 12 and 192 pairs"),
+    ("attention_rows_bounds.txt", "`BOUND` lines of `pytest tests/test_attention_rows_gpu.py -m gpu -s`: the worst (row, head) slice of every streaming / kv_len / dropout / tail / one-row / split divided attention case against float64 on the kernel's own inputs (worst over all: out 2.58e-3, dq 3.22e-3, dk 3.03e-3, dv 2.87e-3; tolerances `tests/kernel_bounds.py::ATTN_ROW_TOL`)"),
+    ("v1_forward_wiring.txt", "`tools/launch_trace.py` before / after the v1 step and the v1 encoders were given one forward wiring (one DistilBERT block and tower walk, one tubelet embed, the small dense heads stated once), with four v1 scenarios added; encoder and training-step outputs bit for bit against the parent commit; the v1 eager step and `tools/bench_infer.py --v1` against the parent in alternating runs"),
 ])
 
 

@@ -371,6 +371,25 @@ class Engine:
             t = self.buf[("ones", n)] = torch.ones(n, dtype=torch.float32, device=self.dev)
         return t
 
+    def _row_starts(self, role, count, stride):
+        """encoder workspace `role`: int32 [count], the first row of every sequence of `stride` rows (its CLS / [CLS] token)"""
+        t = self._ib(role, (count,), torch.int32)
+        t.copy_(torch.arange(count, device=self.dev, dtype=torch.int32) * stride)
+        return t
+
+    # small dense heads (an nn.Linear with bias on a few rows, fp32: txt_proj / vid_proj of the v1 model, the sort head's classifier)
+    def _head_lin(self, x, wname, bname, out, R):
+        """out [R, O] = x [R, I] W^T + b, W = the parameter wname [O, I]"""
+        O, I = self.P.shapes[wname]
+        K.gemm_small(x, self.P.p(wname), out, M=R, N=O, K=I, sa=(I, 1), sb=(1, I), bias=self.P.p(bname))
+
+    def _head_lin_bwd(self, dy, x, wname, bname, dx, R):
+        """its backward, three launches in this order: dW += dy^T x, db += 1^T dy, dx = dy W"""
+        O, I = self.P.shapes[wname]
+        K.gemm_small(dy, x, self.P.g(wname), M=O, N=I, K=R, sa=(1, O), sb=(I, 1), accumulate=True)
+        K.gemm_small(self._ones(R), dy, self.P.g(bname).view(1, O), M=1, N=O, K=R, sa=(0, 1), sb=(O, 1), accumulate=True)
+        K.gemm_small(dy, self.P.p(wname), dx, M=R, N=I, K=O, sa=(O, 1), sb=(I, 1))
+
     # ------------------------------------------------------------------ e4m3 copies (BASELINE config 4 / 5)
     # Two regimes of the e4m3 operand copies:
     #   per TOKEN  (arch["fp8"], arch["fp8_dgrad"]): one scale per row, written by the producing LayerNorm or by a one-pass row
@@ -1136,24 +1155,17 @@ class Engine:
         nf = self._f("srt.nf", (B * NT, E))
         self._ln(x, "pred_model.norm", 1e-6, nf, "srt.norm", rows=None if packed else rows)
         pred = self._f("srt.pred", (B * NT, a["n_trans"]))
-        C = a["n_trans"]
-        K.gemm_small(nf, self.P.p("pred_model.head.weight"), pred, M=B * NT, N=C, K=E, sa=(E, 1), sb=(1, E),
-                     bias=self.P.p("pred_model.head.bias"))
+        self._head_lin(nf, "pred_model.head.weight", "pred_model.head.bias", pred, B * NT)
         return pred
 
     def sort_backward(self, dpred, B, S, NT):
         """-> fp32 grad of the sort-head input xs [B*So, E]."""
         a, B_ = self.arch, self.buf
-        E, hs, C, depth = self.sort_width, a["sort_heads"], a["n_trans"], a["sort_depth"]
+        E, hs, depth = self.sort_width, a["sort_heads"], a["sort_depth"]
         So = S - (1 if self.pooled_tail else 0) + NT
         R = B * NT
-        nf = B_["srt.nf"]
-        K.gemm_small(dpred, nf, self.P.g("pred_model.head.weight"), M=C, N=E, K=R, sa=(1, C), sb=(E, 1), accumulate=True)
-        ones = self._ones(R)
-        K.gemm_small(ones, dpred, self.P.g("pred_model.head.bias").view(1, C), M=1, N=C, K=R, sa=(0, 1), sb=(C, 1),
-                     accumulate=True)
         dnf = self._f("srt.dnf", (R, E))
-        K.gemm_small(dpred, self.P.p("pred_model.head.weight"), dnf, M=R, N=E, K=C, sa=(C, 1), sb=(E, 1))
+        self._head_lin_bwd(dpred, B_["srt.nf"], "pred_model.head.weight", "pred_model.head.bias", dnf, R)
         rows, packed = self.ctx["sort_rows"], self.sort_used_rows_only and NT <= 16  # (gradient at the transcript rows only: [R, E])
         dx, dxb = self._head_ln_bwd(dnf, "pred_model.norm", "srt", "srt.norm", depth, rows, packed)
 
@@ -1456,8 +1468,7 @@ class Engine:
         n = keep_dev.shape[1]
         S = 1 + T * n
         M = B * S
-        vid_rows = self._ib("vid_rows", (B,), torch.int32)
-        vid_rows.copy_(torch.arange(B, device=self.dev, dtype=torch.int32) * S)
+        vid_rows = self._row_starts("vid_rows", B, S)
         x, xc = self._vit_embed(video, keep_dev, B, T, vid_rows, crop, resize, None)
         for l in range(a["layers"] - 1):
             x, xc = self._vit_block(l, x, xc, None, B, T, n)

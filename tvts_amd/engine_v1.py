@@ -73,35 +73,54 @@ class EngineV1(Engine):
             self.drop_seed.add_(self.DROP_STEP_STRIDE)
 
     # ------------------------------------------------------------------ DistilBERT text tower
-    def _pln_fwd(self, pre, x, xb, x_out, xb_out, tag, M, N, L, kv_len, layer=0):
-        """one POST-LN DistilBERT block: x (fp32) / xb (bf16 copy) -> x_out / xb_out"""
-        a, P = self.arch, self.P
-        dp = self._drop_active
-        Wt, h = a["text_width"], a["text_heads"]
-        qkv = self._b(tag + ".qkv", (M, 3 * Wt))
+    # One wiring for both passes, like the v2 towers (Engine._w): with a `tag` the buffers are the step's named tensors, which the
+    # backward reads; with tag None they are encoder workspaces, no log-sum-exp and no pre-activation is written, and there is NO
+    # dropout whatever _drop_active says.
+    def _pln_fwd(self, pre, x, xb, x_out, xb_out, tag, M, N, L, kv_len, layer=0, rows=None):
+        """one POST-LN DistilBERT block over N captions of L rows: x (fp32) / xb (bf16 copy) -> x_out / xb_out.
+        rows (forward-only): the [CLS] row of every caption, for a last block whose output is read there only -- keys / values
+        from every row, one query per caption (tvts_attn_fwd_first), everything behind the attention on N rows: x_out is [N, Wt]."""
+        a, P, w, f32 = self.arch, self.P, self._w, torch.float32
+        dp = self._drop_active if tag else 0.0
+        Wt, h, Ff = a["text_width"], a["text_heads"], a["text_ffn"]
+        R = M if rows is None else N
+        qkv = w(tag, ".qkv", "qkv", (M, 3 * Wt))
         for i, lin in enumerate(("q_lin", "k_lin", "v_lin")):  # three projections into the packed [M, 3 Wt] buffer
-            K.gemm_nt(xb, P.w(pre + f"attention.{lin}.weight"), qkv[:, i * Wt:(i + 1) * Wt], M=M, bias=P.p(pre + f"attention.{lin}.bias"))
-        att, lse = self._b(tag + ".att", (M, Wt)), self._f(tag + ".lse", (M, h))
-        if dp > 0.0:  # weights = dropout(softmax(scores)) inside the kernel
+            w_, b_ = P.w(pre + f"attention.{lin}.weight"), P.p(pre + f"attention.{lin}.bias")
+            if rows is not None and i == 0:  # the one query of every caption: its [CLS] row (row stride L of the operand and of qkv)
+                K.gemm_nt(xb.view(N, L * Wt)[:, :Wt], w_, qkv.view(N, L * 3 * Wt)[:, :Wt], M=N, bias=b_)
+            else:
+                K.gemm_nt(xb, w_, qkv[:, i * Wt:(i + 1) * Wt], M=M, bias=b_)
+        att, lse = w(tag, ".att", "att", (M, Wt)), (self._f(tag + ".lse", (M, h)) if tag else None)
+        res = x
+        if rows is not None:
+            assert tag is None, "the backward of the DistilBERT block is dense"
+            K.attn_fwd_first(qkv, kv_len, att, None, B=N, heads=h, S=L, head_dim=self.dh_text)
+            att_r, res = self._ib("att_r", (N, Wt)), self._ib("x_r", (N, Wt), f32)
+            K.rows_move("gather", rows, full_bf16=att, packed_bf16=att_r)
+            K.rows_move("gather", rows, full_f32=x, packed_f32=res)
+            att = att_r
+        elif dp > 0.0:  # weights = dropout(softmax(scores)) inside the kernel
             K.attn_fwd_len_drop(qkv, kv_len, att, lse, B=N, heads=h, S=L, p=dp, seed=self.drop_seed, site=1 + 2 * layer, head_dim=self.dh_text)
         else:
             K.attn_fwd_len(qkv, kv_len, att, lse, B=N, heads=h, S=L, head_dim=self.dh_text)
-        pre1 = self._f(tag + ".pre1", (M, Wt))
-        self._lin(att, pre + "attention.out_lin.weight", pre + "attention.out_lin.bias", pre1, M, residual=x)
-        x1, x1b = self._f(tag + ".x1", (M, Wt)), self._b(tag + ".x1b", (M, Wt))
-        self._ln(pre1, pre + "sa_layer_norm", 1e-12, x1, tag + ".ln_sa")
+        pre1 = w(tag, ".pre1", "s", (R, Wt), f32)
+        self._lin(att, pre + "attention.out_lin.weight", pre + "attention.out_lin.bias", pre1, R, residual=res)
+        x1, x1b = w(tag, ".x1", "x1", (R, Wt), f32), w(tag, ".x1b", "lnc", (R, Wt))
+        self._ln(pre1, pre + "sa_layer_norm", 1e-12, x1, tag and tag + ".ln_sa")
         K.cast_f32_bf16(x1, x1b)
-        hpre, hact = self._b(tag + ".h", (M, a["text_ffn"])), self._b(tag + ".a", (M, a["text_ffn"]))
-        self._lin(x1b, pre + "ffn.lin1.weight", pre + "ffn.lin1.bias", hact, M, act="gelu", preact=hpre)
-        pre2 = self._f(tag + ".pre2", (M, Wt))
+        hpre, hact = (self._b(tag + ".h", (R, Ff)) if tag else None), w(tag, ".a", "h", (R, Ff))
+        self._lin(x1b, pre + "ffn.lin1.weight", pre + "ffn.lin1.bias", hact, R, act="gelu", preact=hpre)
+        pre2 = w(tag, ".pre2", "s", (R, Wt), f32)  # (forward-only pre1 is dead here: x1 carries the residual)
         if dp > 0.0:  # pre2 = dropout(lin2(.)) + x1
-            y2 = self._f("txt.s.y2", (M, Wt))
-            self._lin(hact, pre + "ffn.lin2.weight", pre + "ffn.lin2.bias", y2, M)
+            y2 = self._f("txt.s.y2", (R, Wt))
+            self._lin(hact, pre + "ffn.lin2.weight", pre + "ffn.lin2.bias", y2, R)
             K.dropout_rows(y2, p=dp, seed=self.drop_seed, site=2 + 2 * layer, residual=x1, out=pre2)
         else:
-            self._lin(hact, pre + "ffn.lin2.weight", pre + "ffn.lin2.bias", pre2, M, residual=x1)
-        self._ln(pre2, pre + "output_layer_norm", 1e-12, x_out, tag + ".ln_out")
-        K.cast_f32_bf16(x_out, xb_out)
+            self._lin(hact, pre + "ffn.lin2.weight", pre + "ffn.lin2.bias", pre2, R, residual=x1)
+        self._ln(pre2, pre + "output_layer_norm", 1e-12, x_out, tag and tag + ".ln_out")
+        if xb_out is not None:
+            K.cast_f32_bf16(x_out, xb_out)
 
     def _pln_bwd(self, pre, xb_in, dx_out, dx_in, tag, M, N, L, kv_len, layer=0):
         """dx_out: fp32 grad wrt the block output; writes the fp32 grad wrt the block input into dx_in."""
@@ -139,42 +158,50 @@ class EngineV1(Engine):
                           residual=acc)
             acc = dst
 
-    def text_forward_v1(self, ids, kv_len, cls_rows, N, L):
-        """-> (text_before [N, Wt] fp32 = last hidden state of [CLS], text_emb [N, E] = txt_proj(relu(.)))"""
-        a, P = self.arch, self.P
-        Wt, M, E = a["text_width"], N * L, a["embed"]
-        emb = self._f("txt.emb", (M, Wt))
+    def _text_tower_v1(self, ids, kv_len, cls_rows, N, L, tag):
+        """DistilBERT over N right-padded captions of L rows -> (before [N, Wt] fp32 = the last hidden state at [CLS],
+        [N, E] = txt_proj(relu(before))).  tag "txt": the training step -- every block dense, every stream kept; None: forward-only
+        -- one stream x / xb updated in place, the last block for the [CLS] rows."""
+        a, P, w, f32 = self.arch, self.P, self._w, torch.float32
+        Wt, M, E, nl = a["text_width"], N * L, a["embed"], a["text_layers"]
+        dp = self._drop_active if tag else 0.0
+        emb = w(tag, ".emb", "s", (M, Wt), f32)
         K.text_embed(ids, P.p("text_model.embeddings.word_embeddings.weight"),
                      P.p("text_model.embeddings.position_embeddings.weight"), emb, N=N, L=L)
-        x, xb = self._f("txt.x0", (M, Wt)), self._b("txt.x0b", (M, Wt))
-        self._advance_drop_seed()
-        if self._drop_active > 0.0:  # Embeddings: dropout(LayerNorm(word + position))
-            xln = self._f("txt.xln", (M, Wt))
-            self._ln(emb, "text_model.embeddings.LayerNorm", 1e-12, xln, "txt.ln_emb")
-            K.dropout_rows(xln, p=self._drop_active, seed=self.drop_seed, site=0, out=x, out_bf16=xb)
+        x, xb = w(tag, ".x0", "x", (M, Wt), f32), w(tag, ".x0b", "ln", (M, Wt))
+        if dp > 0.0:  # Embeddings: dropout(LayerNorm(word + position))
+            xln = self._f(tag + ".xln", (M, Wt))
+            self._ln(emb, "text_model.embeddings.LayerNorm", 1e-12, xln, tag + ".ln_emb")
+            K.dropout_rows(xln, p=dp, seed=self.drop_seed, site=0, out=x, out_bf16=xb)
         else:
-            self._ln(emb, "text_model.embeddings.LayerNorm", 1e-12, x, "txt.ln_emb")
+            self._ln(emb, "text_model.embeddings.LayerNorm", 1e-12, x, tag and tag + ".ln_emb")
             K.cast_f32_bf16(x, xb)
-        for l in range(a["text_layers"]):
-            xo, xbo = self._f(f"txt.x{l + 1}", (M, Wt)), self._b(f"txt.x{l + 1}b", (M, Wt))
-            self._pln_fwd(f"text_model.transformer.layer.{l}.", x, xb, xo, xbo, f"txt{l}", M, N, L, kv_len, layer=l)
+        packed = tag is None  # forward-only the last block runs for the rows the model reads; the step's backward is dense
+        for l in range(nl - packed):
+            xo, xbo = w(tag, f".x{l + 1}", "x", (M, Wt), f32), w(tag, f".x{l + 1}b", "ln", (M, Wt))
+            self._pln_fwd(f"text_model.transformer.layer.{l}.", x, xb, xo, xbo, tag and f"{tag}{l}", M, N, L, kv_len, layer=l)
             x, xb = xo, xbo
-        before = self._f("txt.before", (N, Wt))
-        K.rows_gather(x, cls_rows, before)
-        act = self._f("txt.relu", (N, Wt))
+        before = w(tag, ".before", "tbefore", (N, Wt), f32)
+        if packed:
+            self._pln_fwd(f"text_model.transformer.layer.{nl - 1}.", x, xb, before, None, None, M, N, L, kv_len, layer=nl - 1, rows=cls_rows)
+        else:
+            K.rows_gather(x, cls_rows, before)
+        act = w(tag, ".relu", "trelu", (N, Wt), f32)
         K.relu(before, act)
-        t = self._f("txt.t", (N, E))
-        K.gemm_small(act, P.p("txt_proj.1.weight"), t, M=N, N=E, K=Wt, sa=(Wt, 1), sb=(1, Wt), bias=P.p("txt_proj.1.bias"))
+        t = w(tag, ".t", "temb", (N, E), f32)
+        self._head_lin(act, "txt_proj.1.weight", "txt_proj.1.bias", t, N)
         return before, t
+
+    def text_forward_v1(self, ids, kv_len, cls_rows, N, L):
+        """the training step's text tower (new dropout masks per call in training mode) -> (text_before, text_emb) as _text_tower_v1"""
+        self._advance_drop_seed()
+        return self._text_tower_v1(ids, kv_len, cls_rows, N, L, "txt")
 
     def text_backward_v1(self, dt, ids, kv_len, cls_rows, N, L, tok_sort=None):
         a, P, B_ = self.arch, self.P, self.buf
-        Wt, M, E = a["text_width"], N * L, a["embed"]
-        K.gemm_small(dt, B_["txt.relu"], P.g("txt_proj.1.weight"), M=E, N=Wt, K=N, sa=(1, E), sb=(Wt, 1), accumulate=True)
-        ones = self._ones(N)
-        K.gemm_small(ones, dt, P.g("txt_proj.1.bias").view(1, E), M=1, N=E, K=N, sa=(0, 1), sb=(E, 1), accumulate=True)
+        Wt, M = a["text_width"], N * L
         dact = self._f("txt.dact", (N, Wt))
-        K.gemm_small(dt, P.p("txt_proj.1.weight"), dact, M=N, N=Wt, K=E, sa=(E, 1), sb=(Wt, 1))
+        self._head_lin_bwd(dt, B_["txt.relu"], "txt_proj.1.weight", "txt_proj.1.bias", dact, N)
         dbefore = self._f("txt.dbefore", (N, Wt))
         K.relu(B_["txt.before"], dbefore, dy=dact)
         dx = self._f("txt.dxA", (M, Wt), zero=True)
@@ -193,29 +220,39 @@ class EngineV1(Engine):
                          P.g("text_model.embeddings.position_embeddings.weight"), N=N, L=L, tok_sort=tok_sort)
 
     # ------------------------------------------------------------------ tubelet ViT with joint attention
-    def video_forward_v1(self, video, keep, B, tubes, cls_rows):
-        """-> (tokens [B*S, W] fp32 after the final norm, video_emb [B, E])"""
-        a, P = self.arch, self.P
-        W, E, p, tb = a["width"], a["embed"], a["patch"], a["tubelet"]
-        n = keep.shape[2]
-        S = 1 + tubes * n
-        M, Mp = B * S, B * tubes * n
-        cols = self._b("vit.im2col", (Mp, P.conv_k))
-        K.patch_gather_tube(video, keep, cols, B=B, tubes=tubes, tubelet=tb, n=n, img=a["image"], patch=p)
-        pe = self._f("vit.patch", (Mp, W))
+    def _vit_embed_v1(self, video, keep, B, tubes, tag, crop=None, channel_major=False):
+        """tubelet gather over the kept patches (fp32 clips, channel-major ones, or uint8 frames with their crop) -> patch GEMM ->
+        token assembly: the tokens [B * S, W] fp32 in front of the first block"""
+        a, P, w = self.arch, self.P, self._w
+        W, p, tb, n = a["width"], a["patch"], a["tubelet"], keep.shape[2]
+        M, Mp = B * (1 + tubes * n), B * tubes * n
+        cols = w(tag, ".im2col", "im2col", (Mp, P.conv_k))
+        if video.dtype == torch.uint8:
+            K.patch_gather_tube_u8(video, keep, cols, B=B, tubes=tubes, tubelet=tb, n=n, img=a["image"], patch=p, crop=crop)
+        else:
+            K.patch_gather_tube(video, keep, cols, B=B, tubes=tubes, tubelet=tb, n=n, img=a["image"], patch=p,
+                                channel_major=channel_major)
+        pe = w(tag, ".patch", "patch", (Mp, W), torch.float32)
         K.gemm_nt(cols, P.w_conv(), pe, M=Mp, bias=P.p("video_model.patch_embed.proj.bias"))
-        tok = self._f("vit.x0", (M, W))
+        tok = w(tag, ".x0", "x", (M, W), torch.float32)
         K.vit_assemble(pe, P.p("video_model.cls_token").view(W), P.p("video_model.pos_embed").view(-1, W),
                        P.p("video_model.temporal_embed").view(-1, W), keep, tok, B=B, T=tubes, n=n)
-        hv = a["heads"]
+        return tok
+
+    def video_forward_v1(self, video, keep, B, tubes, cls_rows):
+        """-> (tokens [B*S, W] fp32 after the final norm, video_emb [B, E])"""
+        a = self.arch
+        W, E, hv = a["width"], a["embed"], a["heads"]
+        S = 1 + tubes * keep.shape[2]
+        tok = self._vit_embed_v1(video, keep, B, tubes, "vit")
         x = self._blocks_fwd("video_model.blocks.", _VIT_NAMES, tok, "vit", a["layers"], hv, "gelu", 1e-6,
                              lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hv, S=S, causal=False, head_dim=W // hv))
-        out = self._f("vit.out", (M, W))
+        out = self._f("vit.out", (B * S, W))
         self._ln(x, "video_model.norm", 1e-6, out, "vit.norm")
         cls = self._f("vit.cls", (B, W))
         K.rows_gather(out, cls_rows, cls)
         emb = self._f("mdl.video_emb", (B, E))
-        K.gemm_small(cls, P.p("vid_proj.0.weight"), emb, M=B, N=E, K=W, sa=(W, 1), sb=(1, W), bias=P.p("vid_proj.0.bias"))
+        self._head_lin(cls, "vid_proj.0.weight", "vid_proj.0.bias", emb, B)
         return out, emb
 
     def video_backward_v1(self, dout_b, keep, B, tubes):
@@ -247,19 +284,17 @@ class EngineV1(Engine):
         video = self._clip_to_device(data["video"]).to(torch.float32).contiguous()
         B, T = video.shape[:2]
         tubes = T // a["tubelet"]
-        ids = data["text"]["input_ids"].detach().to("cpu", torch.int64)
-        mask = data["text"]["attention_mask"].detach().to("cpu", torch.int64)
-        lens = mask.sum(-1)
-        assert bool((mask == (torch.arange(mask.shape[1])[None] < lens[:, None])).all()), "attention_mask must be a right-padded prefix mask"
-        N, L = ids.shape
-        L = int(lens.max())
+        from .model.model_dist_TVTS import right_padded, tokenizer_inputs  # (that module imports this one)
+        text = {k: data["text"][k].detach().to("cpu", torch.int64) for k in ("input_ids", "attention_mask")}
+        assert right_padded(text["attention_mask"]), "attention_mask must be a right-padded prefix mask"
+        ids, kv_len, N, L = tokenizer_inputs(text, self.dev)
         NT = N // B
         keep = data["keep_ind"][:, :tubes].to(torch.int32).contiguous().to(self.dev)
         n = keep.shape[2]
         S = 1 + tubes * n
         So = S + NT
-        return dict(video=video, ids=ids[:, :L].to(torch.int32).contiguous().to(self.dev), kv_len=lens.to(torch.int32).to(self.dev),
-                    tok_sort=tuple(t.to(self.dev) for t in K.token_sort(ids[:, :L])),  # ordered word-embedding gradient sums
+        return dict(video=video, ids=ids, kv_len=kv_len,
+                    tok_sort=tuple(t.to(self.dev) for t in K.token_sort(text["input_ids"][:, :L])),  # ordered word-embedding gradient sums
                     txt_cls_rows=(torch.arange(N) * L).to(torch.int32).to(self.dev), keep=keep, B=B, T=T, tubes=tubes, N=N, NT=NT, L=L,
                     n=n, S=S, vid_rows=(torch.arange(B) * S).to(torch.int32).to(self.dev),
                     sort_rows=(torch.arange(B)[:, None] * So + S + torch.arange(NT)[None, :]).reshape(-1).to(torch.int32).to(self.dev),
@@ -292,12 +327,8 @@ class EngineV1(Engine):
             self._ready("text_model.")
             self._ready("txt_proj.")
         # vid_proj on the CLS token: dW += d_video^T cls, db += colsum, d_cls = d_video W
-        cls = self.buf["vit.cls"]
-        K.gemm_small(d_video, cls, P.g("vid_proj.0.weight"), M=E, N=W, K=B, sa=(1, E), sb=(W, 1), accumulate=True)
-        ones = self._ones(B)
-        K.gemm_small(ones, d_video, P.g("vid_proj.0.bias").view(1, E), M=1, N=E, K=B, sa=(0, 1), sb=(E, 1), accumulate=True)
         dcls = self._f("vit.dcls", (B, W))
-        K.gemm_small(d_video, P.p("vid_proj.0.weight"), dcls, M=B, N=W, K=E, sa=(E, 1), sb=(W, 1))
+        self._head_lin_bwd(d_video, self.buf["vit.cls"], "vid_proj.0.weight", "vid_proj.0.bias", dcls, B)
         self._ready("vid_proj.")
         dout = self._b("mdl.dout", (B * S, W))
         if d_pred is not None:
@@ -309,14 +340,16 @@ class EngineV1(Engine):
         self.video_backward_v1(dout, pb["keep"], B, pb["tubes"])
 
     # ------------------------------------------------------------------ forward-only encoders (feature extraction, retrieval)
-    # The v1 counterparts of Engine.encode_video / encode_text: the same kernels in the same order as video_forward_v1 /
-    # text_forward_v1, on the encoder workspaces (_ib) instead of the step's named tensors -- nothing of Engine.buf is read,
-    # written or resized, so a call between two training steps leaves the step alone.  No log-sum-exp, no pre-activations, no
-    # LayerNorm statistics are kept, and the LAST block of either tower runs for the rows the model reads: its keys / values come
-    # from every row, its one query per sequence is the CLS / [CLS] row (tvts_attn_fwd_first), and everything behind the attention
-    # (output projection, residuals, LayerNorms, MLP / FFN) is computed for those B (N) rows only.
+    # The v1 counterparts of Engine.encode_video / encode_text.  They run the training step's own forward wiring -- _vit_embed_v1
+    # and Engine._blocks_fwd, _text_tower_v1 over _pln_fwd, _head_lin -- with tag None: every buffer is an encoder workspace (_ib)
+    # instead of a named tensor of the step, so nothing of Engine.buf is read, written or resized and a call between two training
+    # steps leaves the step alone.  No log-sum-exp, no pre-activations, no LayerNorm statistics are kept, and the LAST block of
+    # either tower runs for the rows the model reads: its keys / values come from every row, its one query per sequence is the
+    # CLS / [CLS] row (tvts_attn_fwd_first), and everything behind the attention (output projection, residuals, LayerNorms,
+    # MLP / FFN) is computed for those B (N) rows only.
     # Seed rule: the text encoder NEVER applies dropout and NEVER advances drop_seed, whatever `training` says -- it is an
     # inference call, and an encoder call between two training steps must not shift the step's mask sequence.
+    # (_advance_drop_seed is text_forward_v1's alone, and with tag None _pln_fwd / _text_tower_v1 do not look at _drop_active.)
     # Base-class refusal (_inf_check) stays for encode_text_packed: there is no packed DistilBERT pass.
     def encode_video(self, video, keep, B, tubes, crop=None, channel_major=False, project=True):
         """-> (feat [B, W] fp32 = the normed CLS token, emb [B, E] = vid_proj(feat)).  Both are encoder workspaces: the next
@@ -325,87 +358,24 @@ class EngineV1(Engine):
         classes); or uint8 [B, T, H0, W0, 3].  keep: int32 [B, tubes, n].
         crop (uint8 only): int32 [B, 2] (top, left) inside the frame, None = centre crop.  It is an argument of the engine alone:
         TVTS.encode_video and the downstream class always take the centre crop."""
-        a, P, f32 = self.arch, self.P, torch.float32
-        W, E, p, tb, hv = a["width"], a["embed"], a["patch"], a["tubelet"], a["heads"]
-        n = keep.shape[2]
-        S = 1 + tubes * n
-        M, Mp = B * S, B * tubes * n
-        cols = self._ib("im2col", (Mp, P.conv_k))
-        if video.dtype == torch.uint8:
-            K.patch_gather_tube_u8(video, keep, cols, B=B, tubes=tubes, tubelet=tb, n=n, img=a["image"], patch=p, crop=crop)
-        else:
-            K.patch_gather_tube(video, keep, cols, B=B, tubes=tubes, tubelet=tb, n=n, img=a["image"], patch=p,
-                                channel_major=channel_major)
-        pe = self._ib("patch", (Mp, W), f32)
-        K.gemm_nt(cols, P.w_conv(), pe, M=Mp, bias=P.p("video_model.patch_embed.proj.bias"))
-        tok = self._ib("x", (M, W), f32)
-        K.vit_assemble(pe, P.p("video_model.cls_token").view(W), P.p("video_model.pos_embed").view(-1, W),
-                       P.p("video_model.temporal_embed").view(-1, W), keep, tok, B=B, T=tubes, n=n)
-        vid_rows = self._ib("vid_rows", (B,), torch.int32)
-        vid_rows.copy_(torch.arange(B, device=self.dev, dtype=torch.int32) * S)
+        a, f32 = self.arch, torch.float32
+        W, E, hv = a["width"], a["embed"], a["heads"]
+        S = 1 + tubes * keep.shape[2]
+        tok = self._vit_embed_v1(video, keep, B, tubes, None, crop, channel_major)
         x_c = self._blocks_fwd(
             "video_model.blocks.", _VIT_NAMES, tok, None, a["layers"], hv, "gelu", 1e-6,
             lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hv, S=S, causal=False, head_dim=W // hv),
-            rows=vid_rows, attn_rows=lambda qkv, att, lse: K.attn_fwd_first(qkv, None, att, lse, B=B, heads=hv, S=S, head_dim=W // hv))
+            rows=self._row_starts("vid_rows", B, S),
+            attn_rows=lambda qkv, att, lse: K.attn_fwd_first(qkv, None, att, lse, B=B, heads=hv, S=S, head_dim=W // hv))
         feat = self._ib("vfeat", (B, W), f32)
         self._ln(x_c, "video_model.norm", 1e-6, feat, None)
         if not project:
             return feat, None
         emb = self._ib("vemb", (B, E), f32)
-        K.gemm_small(feat, P.p("vid_proj.0.weight"), emb, M=B, N=E, K=W, sa=(W, 1), sb=(1, W), bias=P.p("vid_proj.0.bias"))
+        self._head_lin(feat, "vid_proj.0.weight", "vid_proj.0.bias", emb, B)
         return feat, emb
 
     def encode_text(self, ids, kv_len, N, L):
         """-> (before [N, Wt] fp32 = DistilBERT's last hidden state at [CLS], emb [N, E] = txt_proj(relu(before))); both encoder
         workspaces.  ids int32 [N, L], kv_len int32 [N] (right-padded captions) on the device.  No dropout, drop_seed untouched."""
-        a, P, f32 = self.arch, self.P, torch.float32
-        Wt, h, Ff, E, M, nl = a["text_width"], a["text_heads"], a["text_ffn"], a["embed"], N * L, a["text_layers"]
-        emb = self._ib("s", (M, Wt), f32)
-        K.text_embed(ids, P.p("text_model.embeddings.word_embeddings.weight"),
-                     P.p("text_model.embeddings.position_embeddings.weight"), emb, N=N, L=L)
-        x, xb = self._ib("x", (M, Wt), f32), self._ib("ln", (M, Wt))
-        self._ln(emb, "text_model.embeddings.LayerNorm", 1e-12, x, None)
-        K.cast_f32_bf16(x, xb)
-        for l in range(nl):  # POST-LN blocks, x / xb updated in place (forward-only _pln_fwd)
-            pre = f"text_model.transformer.layer.{l}."
-            last = l == nl - 1
-            R = N if last else M
-            qkv = self._ib("qkv", (M, 3 * Wt))
-            for i, lin in enumerate(("q_lin", "k_lin", "v_lin")):
-                w_, b_ = P.w(pre + f"attention.{lin}.weight"), P.p(pre + f"attention.{lin}.bias")
-                if last and i == 0:  # the one query of every caption: its [CLS] row (row stride L of the operand and of qkv)
-                    K.gemm_nt(xb.view(N, L * Wt)[:, :Wt], w_, qkv.view(N, L * 3 * Wt)[:, :Wt], M=N, bias=b_)
-                else:
-                    K.gemm_nt(xb, w_, qkv[:, i * Wt:(i + 1) * Wt], M=M, bias=b_)
-            att = self._ib("att", (M, Wt))
-            res = x
-            if last:
-                K.attn_fwd_first(qkv, kv_len, att, None, B=N, heads=h, S=L, head_dim=self.dh_text)
-                att_r, res = self._ib("att_r", (N, Wt)), self._ib("x_r", (N, Wt), f32)
-                cls_rows = self._ib("cls_rows", (N,), torch.int32)
-                cls_rows.copy_(torch.arange(N, device=self.dev, dtype=torch.int32) * L)
-                K.rows_move("gather", cls_rows, full_bf16=att, packed_bf16=att_r)
-                K.rows_move("gather", cls_rows, full_f32=x, packed_f32=res)
-                att = att_r
-            else:
-                K.attn_fwd_len(qkv, kv_len, att, None, B=N, heads=h, S=L, head_dim=self.dh_text)
-            pre1 = self._ib("s", (R, Wt), f32)
-            self._lin(att, pre + "attention.out_lin.weight", pre + "attention.out_lin.bias", pre1, R, residual=res)
-            x1, x1b = self._ib("x1", (R, Wt), f32), self._ib("lnc", (R, Wt))
-            self._ln(pre1, pre + "sa_layer_norm", 1e-12, x1, None)
-            K.cast_f32_bf16(x1, x1b)
-            hact = self._ib("h", (R, Ff))
-            self._lin(x1b, pre + "ffn.lin1.weight", pre + "ffn.lin1.bias", hact, R, act="gelu")
-            pre2 = self._ib("s", (R, Wt), f32)  # (pre1 is dead: x1 carries the residual)
-            self._lin(hact, pre + "ffn.lin2.weight", pre + "ffn.lin2.bias", pre2, R, residual=x1)
-            if last:
-                before = self._ib("tbefore", (N, Wt), f32)
-                self._ln(pre2, pre + "output_layer_norm", 1e-12, before, None)
-            else:
-                self._ln(pre2, pre + "output_layer_norm", 1e-12, x, None)
-                K.cast_f32_bf16(x, xb)
-        act = self._ib("trelu", (N, Wt), f32)
-        K.relu(before, act)
-        t = self._ib("temb", (N, E), f32)
-        K.gemm_small(act, P.p("txt_proj.1.weight"), t, M=N, N=E, K=Wt, sa=(Wt, 1), sb=(1, Wt), bias=P.p("txt_proj.1.bias"))
-        return before, t
+        return self._text_tower_v1(ids, kv_len, self._row_starts("cls_rows", N, L), N, L, None)

@@ -45,6 +45,29 @@ def reference_init_v1_(store, seed: int = 0):
         store.p(name).copy_(t.to(store.device))
 
 
+def right_padded(mask) -> bool:
+    """is every row of the [N, L] attention mask a run of ones followed by zeros?"""
+    return bool((mask == (torch.arange(mask.shape[1])[None] < mask.sum(-1)[:, None])).all())
+
+
+def tokenizer_inputs(text, device, validate=False, arch=None):
+    """the tokenizer's {'input_ids', 'attention_mask'} (right-padded) -> (ids int32 [N, L] on the device, cut at the longest
+    caption; kv_len int32 [N] on the device, the captions' lengths; N; L): the text arguments of EngineV1.text_forward_v1 /
+    encode_text.  validate: refuse what the kernels would not survive or would silently misread -- ValueError for shapes and
+    masks, IndexError for token ids outside arch's vocabulary and captions longer than its position table."""
+    ids = text["input_ids"].detach().to("cpu", torch.int64)
+    mask = text["attention_mask"].detach().to("cpu", torch.int64)
+    if validate and (ids.dim() != 2 or ids.numel() == 0 or mask.shape != ids.shape):
+        raise ValueError(f"text: expected [N, L] input_ids and attention_mask, got {tuple(ids.shape)} / {tuple(mask.shape)}")
+    lens = mask.sum(-1)
+    if validate and (not right_padded(mask) or int(lens.min()) < 1):
+        raise ValueError("attention_mask must be a non-empty right-padded prefix mask")
+    N, L = ids.shape[0], int(lens.max())
+    if validate and (int(ids.min()) < 0 or int(ids.max()) >= arch["vocab"] or L > arch["max_pos"]):
+        raise IndexError(f"token ids must lie in [0, {arch['vocab']}) and captions within the {arch['max_pos']} positions")
+    return ids[:, :L].to(torch.int32).contiguous().to(device), lens.to(torch.int32).to(device), N, L
+
+
 class TVTS(TVTSv2Base):
     ENGINE = EngineV1
     INIT = staticmethod(reference_init_v1_)
@@ -73,12 +96,8 @@ class TVTS(TVTSv2Base):
         self._fresh_shadows()
         eng = self.engine
         eng.training = self.training
-        ids = text_data["input_ids"].detach().to("cpu", torch.int64)
-        lens = text_data["attention_mask"].detach().to("cpu", torch.int64).sum(-1)
-        N, L = ids.shape[0], int(lens.max())
-        dev = self.store.device
-        before, t = eng.text_forward_v1(ids[:, :L].to(torch.int32).contiguous().to(dev), lens.to(torch.int32).to(dev),
-                                        (torch.arange(N) * L).to(torch.int32).to(dev), N, L)
+        ids, kv_len, N, L = tokenizer_inputs(text_data, self.store.device)
+        before, t = eng.text_forward_v1(ids, kv_len, (torch.arange(N) * L).to(torch.int32).to(self.store.device), N, L)
         return before.clone(), t.clone()
 
     def compute_video(self, video_data, keep_ind):
@@ -109,18 +128,7 @@ class TVTS(TVTSv2Base):
         """-> [N, E] caption embeddings (compute_text's second output in eval mode) from the tokenizer's
         {'input_ids', 'attention_mask'} (right-padded)."""
         self._fresh_shadows()
-        a, dev = self.arch, self.store.device
-        ids = text_dict["input_ids"].detach().to("cpu", torch.int64)
-        mask = text_dict["attention_mask"].detach().to("cpu", torch.int64)
-        if ids.dim() != 2 or ids.numel() == 0 or mask.shape != ids.shape:
-            raise ValueError(f"text: expected [N, L] input_ids and attention_mask, got {tuple(ids.shape)} / {tuple(mask.shape)}")
-        lens = mask.sum(-1)
-        if not bool((mask == (torch.arange(mask.shape[1])[None] < lens[:, None])).all()) or int(lens.min()) < 1:
-            raise ValueError("attention_mask must be a non-empty right-padded prefix mask")
-        N, L = ids.shape[0], int(lens.max())
-        if int(ids.min()) < 0 or int(ids.max()) >= a["vocab"] or L > a["max_pos"]:
-            raise IndexError(f"token ids must lie in [0, {a['vocab']}) and captions within the {a['max_pos']} positions")
-        _, t = self.engine.encode_text(ids[:, :L].to(torch.int32).contiguous().to(dev), lens.to(torch.int32).to(dev), N, L)
+        _, t = self.engine.encode_text(*tokenizer_inputs(text_dict, self.store.device, validate=True, arch=self.arch))
         return t.clone()
 
 
