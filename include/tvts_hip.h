@@ -510,6 +510,37 @@ int tvts_pad_rows_bf16(const void* src, int ld_src, void* dst, int ld_dst, int r
 int tvts_add_rows_f32(float* dst, int ld_dst, const float* src, int ld_src, int rows, int cols, hipStream_t stream);
 int tvts_probe_tr16(const void* in, void* out, hipStream_t stream);
 
+/* ---- v1 action-recognition fine-tuning (finetune.hip): what v1/downstream/run_class_finetuning.py adds on top of the tower */
+/* timm DropPath as v1/downstream/video_encoder.py:65,71-72 uses it, rates video_encoder.py:138: scale[nsites, B] fp32, site 2 l =
+ * the attention branch of block l, 2 l + 1 = its MLP branch; sample b of site s is kept iff the upper 32 bits of the counter-based
+ * generator at (seed_dev[0] + (site_base + s) * site stride, b) are >= p_sites[s] * 2^32 (mixing: see the kernel comment);
+ * scale = keep ? 1 / (1 - p) : 0; p <= 0 gives exactly 1.0f.  p_sites: device fp32 [nsites]. */
+int tvts_drop_path_table(const long* seed_dev, long site_base, const float* p_sites, int nsites, int B, float* scale,
+                         hipStream_t stream);
+/* video_encoder.py:71-72 `x + drop_path(branch(x))`: out[r, :] = residual[r, :] + scale[r / S] * y[r, :] (fp32 y / residual, fp32
+ * and / or bf16 out, 16-byte accesses: cols % 4 == 0, strides % 4 == 0).  residual == NULL: the backward, out = scale[r / S] * y.
+ * scale 0 copies the residual's bits (exact zeros without one); scale 1 is the plain fp32 add.  rows % S == 0. */
+int tvts_drop_path_rows(const float* y, long ldy, long rows, int cols, int S, const float* scale, const float* residual, long ldr,
+                        float* out, long ldo, void* out_bf16, long ldob, hipStream_t stream);
+/* run_class_finetuning.py:423-427: timm SoftTargetCrossEntropy on soft_targets [B, C] (mean_b sum_c -t log_softmax(x)), or -- labels
+ * int32 [B] + smoothing -- LabelSmoothingCrossEntropy ((1 - eps) nll + eps mean_c(-logp); eps = 0: nn.CrossEntropyLoss).  Exactly
+ * one of soft_targets / labels.  loss_acc[0] += scale * loss (fixed summation order); dlogits (optional) = scale / B * (softmax *
+ * sum_c t - t); hits (optional) = #{b : argmax x == argmax t} (engine_for_finetuning.py:104).  ws: fp32 [2 B] scratch. */
+int tvts_soft_ce(const float* logits, long ld, int B, int C, const float* soft_targets, long ldt, const int* labels,
+                 float smoothing, float scale, float* loss_acc, float* dlogits, long ldd, int* hits, float* ws, hipStream_t stream);
+/* torch.nn.utils.clip_grad_norm_ as v1/downstream/utils.py:366 calls it, without the host round trip: two-stage fixed-order sum of
+ * squares over the 1024-element chunks of g whose chunk_group != 255 (partial: fp32 [nchunks] scratch), norm_coef[0] = norm =
+ * |grad_scale| sqrt(sum), norm_coef[1] = coef = min(1, max_norm / (norm + 1e-6)), 1 when max_norm <= 0 (clipping off). */
+int tvts_grad_sumsq(const float* g, const unsigned char* chunk_group, int nchunks, float* partial, float max_norm,
+                    float grad_scale, float* norm_coef, hipStream_t stream);
+/* torch.optim.AdamW as optim_factory.py:129-130 builds it over the layer-decay groups of optim_factory.py:51-90: p *= 1 - lr wd;
+ * m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g g; p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps), bias corrections in double from
+ * `step` or from step_dev[0] (same bits).  g = stored gradient * grad_scale * norm_coef[1] (norm_coef optional).  hyper_dev: device
+ * fp32 lr[64] | wd[64]; chunk table as tvts_adamw_hf, groups 0..63, 255 = frozen (every bit kept); bf16 shadow in the same pass. */
+int tvts_adamw_torch(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
+                     const float* hyper_dev, int step, const int* step_dev, double beta1, double beta2, double eps,
+                     float grad_scale, const float* norm_coef, hipStream_t stream);
+
 /* ---- timing helper for bench.py: HIP events on the stream the kernels run on */
 int tvts_event_create(void** ev);
 int tvts_event_record(void* ev, hipStream_t stream);

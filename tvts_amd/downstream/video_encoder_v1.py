@@ -6,8 +6,11 @@ space-time attention, pre-LN blocks), read at the normed CLS token (video_encode
 Same constructor keywords, same state-dict keys in the same order (``cls_token, pos_embed, temporal_embed, patch_embed.proj.*,
 blocks.i.*, norm.*[, head.*]``), so ``model.load_state_dict(state_dict, strict=False)`` works as v1/downstream/run_class_zero.py
 uses it (:336-340); ``VisionTransformer.from_pretrain(checkpoint, ...)`` applies the script's ``module.video_model.`` key filter.
-The parameter store holds the video tower and the head only (no DistilBERT, no sorting head).  Inference only: every call runs
-under ``no_grad``, parameters have ``requires_grad=False``; dropout / drop-path rates are accepted and have no effect.
+The parameter store holds the video tower and the head only (no DistilBERT, no sorting head).  ``forward`` / ``forward_features``
+are inference calls in every module mode: they run under ``no_grad``, parameters have ``requires_grad=False`` (there is no autograd
+graph; the hand-written backward writes into the store's flat gradient buffer), dropout rates are accepted and have no effect, and
+``drop_path_rate`` has no effect on them either.  Training this class -- action-recognition fine-tuning and linear probing -- is
+``tvts_amd.downstream.finetune_v1.FinetuneStep``, which reads ``drop_path_rate``, ``grad_views()`` and ``set_trainable()`` here.
 """
 from __future__ import annotations
 
@@ -69,6 +72,8 @@ class VisionTransformer(nn.Module):
         self.store = ParamStore(self.arch, dev)
         self.engine = EngineV1(self.store)
         self.engine.training = False
+        self.drop_path_rate = float(drop_path_rate)  # stochastic depth of FinetuneStep (video_encoder.py:138); forward ignores it
+        self.engine.drop_path_rate = self.drop_path_rate
         reference_init_v1_(self.store, init_seed)
         for name in self.store.shapes:  # the reference's names: the tower's without the pretrain model's prefix
             parts = (name[len(_PREFIX):] if name.startswith(_PREFIX) else name).split(".")
@@ -103,6 +108,32 @@ class VisionTransformer(nn.Module):
 
     def no_weight_decay(self):
         return {"pos_embed", "cls_token"}
+
+    # ---- what finetune_v1 needs: names, gradient views, the trainable map, the shadow bookkeeping
+    @staticmethod
+    def store_name(name: str) -> str:
+        """the parameter store's name of the parameter `name` of this module"""
+        return name if name.startswith("head.") else _PREFIX + name
+
+    def grad_views(self):
+        """{parameter name: view of the store's flat fp32 gradient buffer}, in named_parameters() order"""
+        return {n: self.store.g(self.store_name(n)) for n, _ in self.named_parameters()}
+
+    def set_trainable(self, trainable: str = "all"):
+        """the engine's requires_grad map: "all" -- every parameter; "head" -- linear probing, head.* only
+        (run_class_linear.py:342-346).  -> {parameter name: bool}"""
+        if trainable not in ("all", "head"):
+            raise ValueError("trainable: 'all' or 'head'")
+        if self.num_classes == 0:
+            raise ValueError("a model without head (num_classes = 0) has nothing to fine-tune")
+        out = {}
+        for n, _ in self.named_parameters():
+            out[n] = self.engine.requires_grad[self.store_name(n)] = trainable == "all" or n.startswith("head.")
+        return out
+
+    def mark_shadows_fresh(self):
+        """the fused optimizer rewrote the bf16 shadows together with the parameters"""
+        self._versions = tuple(p._version for p in self.parameters())
 
     def _fresh_shadows(self):
         """re-derive the bf16 weight shadows iff some parameter changed since the last refresh (load_state_dict copies in place)"""

@@ -655,9 +655,12 @@ class Engine:
     # (attn_fwd: a query-restricted kernel writing the used rows of `att`), the output projection, the residual, LayerNorm 2 and the
     # MLP are computed for the R used rows; backward: dQ for those rows, dK / dV -- and through them the gradient of every input
     # row -- dense.
-    def _block_fwd(self, pre, nm, x_in, x_out, tag, heads, act, eps, attn_fwd, rows=None):
+    def _block_fwd(self, pre, nm, x_in, x_out, tag, heads, act, eps, attn_fwd, rows=None, drop_path=None):
         """attn_fwd(qkv, att, lse): the attention call.  tag None: forward-only (lse None, no act'(x) side output; x_out may be x_in).
-        -> x_out, or with `rows` the block output at those rows, packed [R, Wd] fp32 (x_out is not used)."""
+        -> x_out, or with `rows` the block output at those rows, packed [R, Wd] fp32 (x_out is not used).
+        drop_path (dense training blocks only): (scale_attn [B], scale_mlp [B], rows per sample) -- stochastic depth: each branch's
+        projection, bias included, goes to an fp32 scratch and tvts_drop_path_rows forms residual + scale[sample] * branch."""
+        assert drop_path is None or (rows is None and tag is not None)
         w, f32 = self._w, torch.float32
         M, Wd = x_in.shape
         R = M if rows is None else rows.numel()
@@ -674,27 +677,45 @@ class Engine:
             K.rows_move("gather", rows, full_f32=x_in, packed_f32=res)
             att, x_out = att_r, w(tag, ".xo_r", "xoc", (R, Wd), f32)
         mid = w(tag, ".mid", "s", (R, Wd), f32)
-        self._lin(att, pre + nm["o_w"], pre + nm["o_b"], mid, R, residual=res)
+        if drop_path is None:
+            self._lin(att, pre + nm["o_w"], pre + nm["o_b"], mid, R, residual=res)
+        else:
+            y = self._f("dp.y", (R, Wd))
+            self._lin(att, pre + nm["o_w"], pre + nm["o_b"], y, R)
+            K.drop_path_rows(y, drop_path[0], drop_path[2], residual=res, out=mid)
         ln2 = w(tag, ".ln2", "ln" if rows is None else "lnc", (R, Wd))
         self._ln(mid, pre + nm["ln2"], eps, ln2, tag and tag + ".ln2")
         h = self._b(tag + ".h", (R, 4 * Wd)) if tag else None
         a = w(tag, ".a", "h", (R, 4 * Wd))
         self._lin(ln2, pre + nm["fc_w"], pre + nm["fc_b"], a, R, act=act, preact=h)
-        self._lin(a, pre + nm["pj_w"], pre + nm["pj_b"], x_out, R, residual=mid)
+        if drop_path is None:
+            self._lin(a, pre + nm["pj_w"], pre + nm["pj_b"], x_out, R, residual=mid)
+        else:
+            self._lin(a, pre + nm["pj_w"], pre + nm["pj_b"], y, R)
+            K.drop_path_rows(y, drop_path[1], drop_path[2], residual=mid, out=x_out)
         return x_out
 
-    def _block_bwd(self, pre, nm, x_in, dx, dxb, dx_in, dxb_in, tag, scr, heads, act, attn_bwd, rows=None):
+    def _block_bwd(self, pre, nm, x_in, dx, dxb, dx_in, dxb_in, tag, scr, heads, act, attn_bwd, rows=None, drop_path=None):
         """dx / dxb: fp32 / bf16 gradient of the block output (with `rows`: at those R rows, packed); attn_bwd(qkv, datt, att, lse,
-        delta, dqkv): the attention call.  Writes the gradient of every input row to dx_in / dxb_in."""
+        delta, dqkv): the attention call.  Writes the gradient of every input row to dx_in / dxb_in.
+        drop_path: as _block_fwd -- the gradient entering a branch is scale[sample] * (gradient of the sum), formed from the fp32
+        gradient as the bf16 operand of _lin_bwd; the residual path keeps the unscaled gradient."""
+        assert drop_path is None or rows is None
         B_ = self.buf
         M, Wd = x_in.shape
         R, r = (M, "") if rows is None else (rows.numel(), "_r")
         dh, dln_r = self._b(scr + ".dh" + r, (R, 4 * Wd)), self._b(scr + ".dln" + r, (R, Wd))
+        if drop_path is not None:
+            dxb = self._b(scr + ".dpb", (R, Wd))
+            K.drop_path_rows(dx, drop_path[1], drop_path[2], out_bf16=dxb)
         self._lin_bwd(dxb, B_[tag + ".a"], pre + nm["pj_w"], pre + nm["pj_b"], dh, R, gate_h=B_[tag + ".h"], gate_act=act)
         self._lin_bwd(dh, B_[tag + ".ln2"], pre + nm["fc_w"], pre + nm["fc_b"], dln_r, R)
         dmid, dmidb = self._f(scr + ".dmid" + r, (R, Wd)), self._b(scr + ".dmidb" + r, (R, Wd))
         self._ln_bwd(dln_r, B_[tag + ".mid"], pre + nm["ln2"], tag + ".ln2", dmid, dx_bf16=dmidb, res1=dx)
         datt = self._b(scr + ".datt" + r, (R, Wd))
+        if drop_path is not None:
+            dmidb = self._b(scr + ".dpb", (R, Wd))  # (the MLP branch's operand is consumed: same stream, nothing deferred)
+            K.drop_path_rows(dmid, drop_path[0], drop_path[2], out_bf16=dmidb)
         self._lin_bwd(dmidb, B_[tag + ".att" + r], pre + nm["o_w"], pre + nm["o_b"], datt, R)
         if rows is not None:
             datt_r, datt = datt, self._b(scr + ".datt", (M, Wd))  # token-row indexed like the attention output; only the R rows are read
@@ -710,16 +731,23 @@ class Engine:
         if rows is not None:
             K.rows_move("scatter_add", rows, full_f32=dx_in, full_bf16=dxb_in, packed_f32=dmid)
 
-    def _blocks_fwd(self, pre, nm, x, tag, depth, heads, act, eps, attn, rows=None, attn_rows=None):
+    def _blocks_fwd(self, pre, nm, x, tag, depth, heads, act, eps, attn, rows=None, attn_rows=None, drop_path=None):
         """x through the blocks pre + "0." ... of a pre-LN tower -> the stream behind the last block -- or, with `rows`, that
         block's output at those rows (packed; attn_rows: its attention call), for the caller's final LayerNorm and head.
-        tag: block l keeps its tensors as tag + "l" + name and writes the stream tag + ".x<l + 1>"; None: forward-only, in place."""
+        tag: block l keeps its tensors as tag + "l" + name and writes the stream tag + ".x<l + 1>"; None: forward-only, in place.
+        drop_path: (scale table fp32 [2 * depth, B], rows per sample) of a stochastic-depth step, row 2 l for the attention branch of
+        block l and 2 l + 1 for its MLP branch (tvts_drop_path_table); None: no stochastic depth."""
         for l in range(depth):
             used = rows if l == depth - 1 else None
             xo = None if used is not None else self._f(f"{tag}.x{l + 1}", x.shape) if tag else x
             x = self._block_fwd(f"{pre}{l}.", nm, x, xo, tag and f"{tag}{l}", heads, act, eps, attn if used is None else attn_rows,
-                                rows=used)
+                                rows=used, drop_path=self._dp_of(drop_path, l))
         return x
+
+    @staticmethod
+    def _dp_of(drop_path, l):
+        """block l's share of a tower's drop_path argument"""
+        return None if drop_path is None else (drop_path[0][2 * l], drop_path[0][2 * l + 1], drop_path[1])
 
     @staticmethod
     def _ab(depth, l):
@@ -740,14 +768,15 @@ class Engine:
             self._ln_bwd(dy, x, name, ln_tag, dx, dx_bf16=dxb, rows=rows)
         return dx, dxb
 
-    def _blocks_bwd(self, pre, nm, tag, depth, dx, dxb, heads, act, attn_bwd, rows=None, attn_bwd_rows=None, after=None):
-        """The backward of _blocks_fwd.  dx / dxb: fp32 / bf16 gradient of what it returned -> the fp32 gradient of its input x.
+    def _blocks_bwd(self, pre, nm, tag, depth, dx, dxb, heads, act, attn_bwd, rows=None, attn_bwd_rows=None, after=None,
+                    drop_path=None):
+        """The backward of _blocks_fwd (drop_path: the forward's).  dx / dxb: fp32 / bf16 gradient of what it returned -> the fp32 gradient of its input x.
         The blocks' input gradients alternate between tag + ".dxA|B" / ".dxbA|B" (_ab); after(l): called behind block l."""
         for l in reversed(range(depth)):
             x_in, nx, used = self.buf[f"{tag}.x{l}"], self._ab(depth, l), rows if l == depth - 1 else None
             dxi, dxbi = self._f(f"{tag}.dx{nx}", x_in.shape), self._b(f"{tag}.dxb{nx}", x_in.shape)
             self._block_bwd(f"{pre}{l}.", nm, x_in, dx, dxb, dxi, dxbi, f"{tag}{l}", tag + ".s", heads, act,
-                            attn_bwd if used is None else attn_bwd_rows, rows=used)
+                            attn_bwd if used is None else attn_bwd_rows, rows=used, drop_path=self._dp_of(drop_path, l))
             dx, dxb = dxi, dxbi
             if after is not None:
                 after(l)

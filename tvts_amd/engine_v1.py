@@ -276,6 +276,88 @@ class EngineV1(Engine):
         self._ready("video_model.cls_token", "video_model.pos_embed", "video_model.temporal_embed", "video_model.patch_embed.")
         self._ready("video_model.norm.")
 
+    # ------------------------------------------------------------------ action-recognition fine-tuning (v1/downstream)
+    # The downstream class with num_classes > 0 as run_class_finetuning.py trains it: every patch kept, timm DropPath on both
+    # branches of every block (video_encoder.py:65,71-72,138), `norm` at the CLS rows, `head`.  The blocks are the training step's
+    # own wiring (_blocks_fwd / _blocks_bwd) with its drop_path hook; the last block runs dense.
+    # Seed rule: every finetune_forward advances drop_seed once, by a device op (DROP_STEP_STRIDE, per-rank offsets as for the text
+    # dropout), then draws the step's table from it -- branch s of block l is site FT_SITE_BASE + 2 l (+ 1).  The backward re-reads
+    # the table the forward left.  The forward-only encoders never touch the seed.
+    FT_SITE_BASE = 1 << 20   # clear of the text tower's dropout sites (0 .. 2 * text_layers)
+    drop_path_rate = 0.0     # the downstream class sets its constructor argument here
+    drop_path_override = None  # fp32 device [2 * depth, B]: used instead of the drawn table (replaying a reference run's masks)
+
+    def _ft_table(self, B):
+        """the step's scale table [2 * depth, B] (None: no stochastic depth in this step)"""
+        depth = self.arch["layers"]
+        if self.drop_path_override is not None:
+            t = self.drop_path_override
+            assert t.dtype == torch.float32 and tuple(t.shape) == (2 * depth, B) and t.is_cuda and t.is_contiguous()
+            return t
+        rate = float(self.drop_path_rate)
+        if rate <= 0.0:
+            return None
+        ent = self.buf.get(("ft.dp_rates", rate))
+        if ent is None:  # video_encoder.py:138, each block's rate for both of its branches
+            dpr = [torch.linspace(0, rate, depth)[l].item() for l in range(depth)]
+            ent = self.buf[("ft.dp_rates", rate)] = torch.tensor([r for r in dpr for _ in (0, 1)], dtype=torch.float32, device=self.dev)
+        table = self._f("ft.dp_table", (2 * depth, B))
+        K.drop_path_table(self.drop_seed, ent, table, site_base=self.FT_SITE_BASE)
+        return table
+
+    def finetune_forward(self, video, B, tubes, channel_major=True, crop=None):
+        """-> logits [B, C] fp32 (a named tensor of the step).  video on the device: fp32 [B, 3, T, H, W] (channel_major, the
+        downstream layout), fp32 [B, T, 3, H, W], or uint8 [B, T, H0, W0, 3] with crop int32 [B, 2] (None: centre)."""
+        a = self.arch
+        W, hv, C, depth = a["width"], a["heads"], a["head_classes"], a["layers"]
+        ppf = (a["image"] // a["patch"]) ** 2
+        S = 1 + tubes * ppf
+        self._tick += 1
+        self.drop_seed.add_(self.DROP_STEP_STRIDE)
+        table = self._ft_table(B)
+        keep = self.buf.get(("ft.keep", B, tubes))
+        if keep is None:
+            keep = self.buf[("ft.keep", B, tubes)] = torch.arange(ppf, dtype=torch.int32, device=self.dev).repeat(B, tubes, 1).contiguous()
+            self.buf[("ft.cls_rows", B, S)] = (torch.arange(B, device=self.dev) * S).to(torch.int32)
+        cls_rows = self.buf[("ft.cls_rows", B, S)]
+        tok = self._vit_embed_v1(video, keep, B, tubes, "ft", crop, channel_major)
+        dp = None if table is None else (table, S)
+        x = self._blocks_fwd("video_model.blocks.", _VIT_NAMES, tok, "ft", depth, hv, "gelu", 1e-6,
+                             lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hv, S=S, causal=False, head_dim=W // hv),
+                             drop_path=dp)
+        feat = self._f("ft.feat", (B, W))
+        self._ln(x, "video_model.norm", 1e-6, feat, "ft.norm", rows=cls_rows)
+        logits = self._f("ft.logits", (B, C))
+        self._head_lin(feat, "head.weight", "head.bias", logits, B)
+        self.ft_ctx = dict(B=B, tubes=tubes, S=S, keep=keep, cls_rows=cls_rows, drop_path=dp)
+        return logits
+
+    def finetune_backward(self, dlogits, trainable="all"):
+        """dlogits fp32 [B, C] -> the gradients, ACCUMULATED into the store.  trainable "head": linear probing
+        (run_class_linear.py:342-346), nothing behind the head runs."""
+        if trainable not in ("all", "head"):
+            raise ValueError("trainable: 'all' or 'head'")
+        a, c, P, B_ = self.arch, self.ft_ctx, self.P, self.buf
+        B, S, tubes, W, hv, depth = c["B"], c["S"], c["tubes"], a["width"], a["heads"], a["layers"]
+        dfeat = self._f("ft.dfeat", (B, W))
+        self._head_lin_bwd(dlogits, B_["ft.feat"], "head.weight", "head.bias", dfeat, B)
+        self._ready("head.")
+        if trainable == "head":
+            return
+        dx, dxb = self._head_ln_bwd(dfeat, "video_model.norm", "ft", "ft.norm", depth, c["cls_rows"], False)
+        dx = self._blocks_bwd("video_model.blocks.", _VIT_NAMES, "ft", depth, dx, dxb, hv, "gelu",
+                              lambda qkv, *t: K.attn_bwd("full", qkv, *t, B=B, heads=hv, S=S, causal=False, head_dim=W // hv),
+                              after=lambda l: self._ready(f"video_model.blocks.{l}."), drop_path=c["drop_path"])
+        n = c["keep"].shape[2]
+        Mp = B * tubes * n
+        dpatch = self._b("ft.dpatch", (Mp, W))
+        K.vit_assemble_bwd(dx, c["keep"], dpatch, P.g("video_model.cls_token").view(W), P.g("video_model.pos_embed").view(-1, W),
+                           P.g("video_model.temporal_embed").view(-1, W), B=B, T=tubes, n=n)
+        K.gemm_tn(dpatch, B_["ft.im2col"], P.g2d("video_model.patch_embed.proj.weight"), M=Mp, accumulate=True,
+                  colsum=P.g("video_model.patch_embed.proj.bias"))
+        self._ready("video_model.cls_token", "video_model.pos_embed", "video_model.temporal_embed", "video_model.patch_embed.")
+        self._ready("video_model.norm.")
+
     # ------------------------------------------------------------------ whole model
     def prepare_batch(self, data: dict):
         """v1 batch dict (v1/trainer/trainer.py:121-131): text = the tokenizer's {'input_ids', 'attention_mask'} (right-padded),

@@ -1075,6 +1075,66 @@ def adamw_hf(p, g, m, v, shadow, chunk_group, lr4, wd4, step, beta1=0.9, beta2=0
     _chk(rc, "tvts_adamw_hf")
 
 
+# ---- v1 fine-tuning step (finetune.hip)
+def drop_path_table(seed, p_sites, scale, *, site_base=0):
+    """scale [nsites, B] fp32 = the stochastic-depth draw of one step: 1 / (1 - p) for a kept sample, 0 for a dropped one, exactly
+    1.0 where p_sites[s] == 0.  seed: int64 device scalar; p_sites: fp32 device [nsites]."""
+    assert seed.dtype == torch.int64 and p_sites.dtype == torch.float32 and scale.dtype == torch.float32
+    assert scale.dim() == 2 and scale.is_contiguous() and p_sites.is_contiguous() and p_sites.numel() == scale.shape[0]
+    _chk(_lib.load().tvts_drop_path_table(_p(seed), int(site_base), _p(p_sites), scale.shape[0], scale.shape[1], _p(scale), _stream()),
+         "tvts_drop_path_table")
+
+
+def drop_path_rows(y, scale, S, *, residual=None, out=None, out_bf16=None):
+    """out[r] = residual[r] + scale[r // S] * y[r] (fp32 and / or bf16 out); without residual: out[r] = scale[r // S] * y[r], the
+    backward of the branch.  scale: fp32 [rows // S] (one row of the step's table)."""
+    assert y.dtype == torch.float32 and scale.dtype == torch.float32 and scale.is_contiguous() and y.shape[0] % S == 0
+    assert scale.numel() >= y.shape[0] // S
+    for t, dt in ((residual, torch.float32), (out, torch.float32), (out_bf16, torch.bfloat16)):
+        assert t is None or (t.dtype == dt and t.shape == y.shape)
+    with _hbm("drop_path", _nb((y, y.shape[0]), (residual, y.shape[0]), (out, y.shape[0]), (out_bf16, y.shape[0]))):
+        rc = _lib.load().tvts_drop_path_rows(_p(y), _ld(y), y.shape[0], y.shape[1], int(S), _p(scale), _p(residual),
+                                             _ld(residual) if residual is not None else 0, _p(out), _ld(out) if out is not None else 0,
+                                             _p(out_bf16), _ld(out_bf16) if out_bf16 is not None else 0, _stream())
+    _chk(rc, "tvts_drop_path_rows")
+
+
+def soft_ce(logits, loss_acc, ws, *, soft_targets=None, labels=None, smoothing=0.0, scale=1.0, dlogits=None, hits=None):
+    """loss_acc[0] += scale * CE(logits, targets) (soft targets fp32 [B, C], or int32 labels + smoothing); dlogits / hits optional.
+    ws: fp32 scratch of >= 2 B elements."""
+    B, C = logits.shape
+    assert logits.dtype == torch.float32 and loss_acc.dtype == torch.float32 and ws.dtype == torch.float32 and ws.numel() >= 2 * B
+    assert soft_targets is None or (soft_targets.dtype == torch.float32 and soft_targets.shape == logits.shape)
+    assert labels is None or (labels.dtype == torch.int32 and labels.numel() == B and labels.is_contiguous())
+    assert dlogits is None or (dlogits.dtype == torch.float32 and dlogits.shape == logits.shape)
+    assert hits is None or hits.dtype == torch.int32
+    _chk(_lib.load().tvts_soft_ce(_p(logits), _ld(logits), B, C, _p(soft_targets), _ld(soft_targets) if soft_targets is not None else 0,
+                                  _p(labels), float(smoothing), float(scale), _p(loss_acc), _p(dlogits),
+                                  _ld(dlogits) if dlogits is not None else 0, _p(hits), _p(ws), _stream()), "tvts_soft_ce")
+
+
+def grad_sumsq(g, chunk_group, partial, norm_coef, *, max_norm=0.0, grad_scale=1.0):
+    """norm_coef[0] = the global norm of the gradient chunks whose group is not 255, norm_coef[1] = the clip coefficient
+    min(1, max_norm / (norm + 1e-6)) (1 with max_norm <= 0); everything stays on the device."""
+    n = chunk_group.numel()
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.numel() >= n * 1024 and chunk_group.dtype == torch.uint8
+    assert partial.dtype == torch.float32 and partial.numel() >= n and norm_coef.dtype == torch.float32 and norm_coef.numel() >= 2
+    _chk(_lib.load().tvts_grad_sumsq(_p(g), _p(chunk_group), n, _p(partial), float(max_norm or 0.0), float(grad_scale), _p(norm_coef),
+                                     _stream()), "tvts_grad_sumsq")
+
+
+def adamw_torch(p, g, m, v, shadow, chunk_group, hyper_dev, step, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, step_dev=None,
+                norm_coef=None):
+    """one torch.optim.AdamW step over the flat buffers; hyper_dev: device fp32 lr[64] | wd[64]"""
+    n = chunk_group.numel()
+    assert hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= 128 and chunk_group.dtype == torch.uint8
+    assert all(t.numel() >= n * 1024 for t in (p, g, m, v)) and (shadow is None or shadow.numel() >= n * 1024)
+    with _hbm("adamw", lambda: 30.0 * 1024 * float((chunk_group < 64).sum())):
+        rc = _lib.load().tvts_adamw_torch(_p(p), _p(g), _p(m), _p(v), _p(shadow), _p(chunk_group), n, _p(hyper_dev), int(step),
+                                          _p(step_dev), beta1, beta2, eps, grad_scale, _p(norm_coef), _stream())
+    _chk(rc, "tvts_adamw_torch")
+
+
 def cast_f32_bf16(src, dst):
     lib = _lib.load()
     _chk(lib.tvts_cast_f32_bf16(_p(src), _p(dst), src.numel(), _stream()), "tvts_cast_f32_bf16")
