@@ -24,14 +24,17 @@ enum { TVTS_ATTN_FULL = 0, TVTS_ATTN_SPACE = 1, TVTS_ATTN_TIME = 2, TVTS_ATTN_CL
 /* `opts` of the GEMM entry points (OR them; 0 = automatic) */
 enum {
     TVTS_GEMM_TILE_128 = 1,     /* force the persistent 128x128 kernel */
-    TVTS_GEMM_TILE_256 = 2,     /* force the pipelined 256x256 kernel (-22 if the shape cannot take it) */
+    TVTS_GEMM_TILE_256 = 2,     /* force the pipelined 256x256 kernel: -22 if ldc / ldp / ldh is not a multiple of 8 (its 16-byte epilogue
+                                   accesses); a result with N % 8 != 0 is not this kernel's to take and runs on the 128x128 one
+                                   (tvts_gemm_nt_select reports 128 for it) */
     TVTS_GEMM_FP8_K32 = 4,      /* tvts_gemm_nt_fp8*: the 16x16x32 fp8 MFMA main loop (bf16 issue rate) instead of the K = 128 scaled
                                    MFMA; both accumulate the same products in fp32 */
     TVTS_TN_NO_EARLY_DMA = 4,   /* tvts_gemm_tn_bf16: LDS-DMA through the builtin path (the one operands past 4 GiB take) */
     TVTS_TN_AFAST_0 = 8,        /* tvts_gemm_tn_bf16: tile walk of an m-range, b-dimension fastest ... */
     TVTS_TN_AFAST_1 = 16,       /* ... or a-dimension fastest (default: the shorter one) */
     TVTS_GEMM_STREAMK = 32,     /* tvts_gemm_nt_bf16 / tvts_gemm_tn_bf16: force the stream-K walk (work split by K stage, ordered sum of the
-                                   partial tiles in the block that arrives last); -22 without a workspace or on a shape it cannot take */
+                                   partial tiles in the block that arrives last); -22 without a workspace or on a shape it cannot take (one K stage, fewer
+                                   than 8 tiles, and -- the walk exists on the 256x256 kernel only -- ldc / ldp / ldh not a multiple of 8) */
     TVTS_GEMM_NO_STREAMK = 64,  /* ... never take it */
     TVTS_GEMM_RING = 128,       /* tvts_gemm_nt_bf16: force the ring form of the 128-column kernel (one block per CU, three 64-deep stages
                                    in flight: the small-batch kernel; same bits as TVTS_GEMM_TILE_128); -22 if an operand is too large
@@ -75,7 +78,11 @@ enum {
  *      takes when an output of few tiles would leave the persistent grid a fraction of a round (the reference's own per-GPU
  *      batches of 12 / 24 pairs): fp32 partial tiles + one arrival counter per output tile.  Its first 64 KiB must be ZERO
  *      on the first call and are zero again after every call; one workspace serves one stream (calls in flight at the same
- *      time need workspaces of their own).  Without it the tile-granular walk is the only one. */
+ *      time need workspaces of their own).  Without it the tile-granular walk is the only one.
+ *      Refused with -22 before any launch: a null A / B / out, M / N / K <= 0, K % 64, N % 4, lda / ldb % 8, ldc / ldr / ldp / ldh % 4
+ *      (% 8 for ldc / ldp / ldh under TVTS_GEMM_TILE_256), a leading dimension shorter than its row -- lda < K, ldb < K, ldc < N, and
+ *      ldr / ldp / ldh < N when that matrix is given (so 0, a broadcast row, is refused: no caller passes one) --, act together with
+ *      gate_h, workspace_bytes < 0. */
 int tvts_gemm_nt_bf16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, const float* bias,
                       const float* residual, int ldr, int act, void* preact, int ldp, const void* gate_h, int ldh,
                       int gate_act, void* out, int ldc, int out_f32, void* workspace, long workspace_bytes, int opts,
@@ -85,7 +92,9 @@ long tvts_gemm_nt_workspace_bytes(void);
  * double-buffered kernel, 1128 / 1192 = the ring kernel (TVTS_GEMM_RING) with 128 / 192 tile rows: lets a parity test assert that
  * the kernel it means to exercise is the one that ran */
 int tvts_gemm_nt_select(int M, int N, int opts);
-/* weight gradient: out[Na,Nb] (+)= P[M,Na]^T . Q[M,Nb], bf16 in, fp32 out (autograd of the Linear sites above) */
+/* weight gradient: out[Na,Nb] (+)= P[M,Na]^T . Q[M,Nb], bf16 in, fp32 out (autograd of the Linear sites above).
+ * Refused with -22 before any launch: a null P / Q / out, M / Na / Nb <= 0, Na / Nb / ldp / ldq % 8, ldo % 4, ldp < Na, ldq < Nb,
+ * ldo < Nb, workspace_elems < 0. */
 /* colsum (optional): colsum[a] += sum_m P[m,a] -- the bias gradient, fused into the same pass.
  * workspace (optional, workspace_elems floats): scratch for the split-M partials; with it the kernel stores
  * partials that are combined in range order (deterministic), without it the partials meet through fp32 atomics.
@@ -113,7 +122,9 @@ long tvts_gemm_tn_grouped_table_bytes(int n);
 int tvts_gemm_tn_select(int M, int Na, int Nb, int opts);
 /* fp8 (OCP e4m3) operands with scales in device memory, fp32 accumulate: the GEMM of BASELINE config 4's weight / activation
  * path (nn.Linear sites of video_encoder_ViT_H_14.py); K % 128 == 0, lda / ldb % 16 == 0 (bytes).  scale_b: one scale for the
- * weight; scale_a: one scale for the tensor, or (scale_a_rows != 0) M per-row scales as written by tvts_quant_fp8_rows */
+ * weight; scale_a: one scale for the tensor, or (scale_a_rows != 0) M per-row scales as written by tvts_quant_fp8_rows.
+ * Refused with -22 before any launch (here and in tvts_gemm_nt_fp8_gate): a null A / B / scale, sizes <= 0, K % 128, N % 8,
+ * lda / ldb % 16, ldc / ldp / ldh / ldq8 % 8, ldr % 4, lda < K, ldb < K, and ldc / ldr / ldp / ldh / ldq8 < N for every matrix given */
 int tvts_gemm_nt_fp8(const void* A, int lda, const void* B, int ldb, int M, int N, int K, const float* scale_a,
                      int scale_a_rows, const float* scale_b, const float* bias, const float* residual, int ldr, int act, void* preact, int ldp,
                      void* out, int ldc, int out_f32, void* q8out, int ldq8, const float* q8_scale, float* q8_amax, int opts,
@@ -131,14 +142,18 @@ int tvts_gemm_nt_fp8_gate(const void* A, int lda, const void* B, int ldb, int M,
                           hipStream_t stream);
 /* weight gradient of such a layer on e4m3 operands: out[Na,Nb] (+)= scale_p * scale_q * sum_m P8[m,Na] * Q8[m,Nb].  The contraction runs
  * over the tokens, so the operands carry ONE scale per tensor (device scalars; tvts_quant_fp8 / tvts_quant_fp8_rows2 write such
- * copies) -- not the per-token scales of the forward / input-gradient operands.  Na, Nb, ldp, ldq (bytes) multiples of 16.
+ * copies) -- not the per-token scales of the forward / input-gradient operands.  Na, Nb, ldp, ldq (bytes) multiples of 16;
+ * -22 also for a null P8 / Q8 / out / scale, ldp < Na, ldq < Nb, ldo < Nb, workspace_elems < 0.
  * workspace: split-M partials, reduced in range order (deterministic).  colsum (optional): colsum[a] += scale_p * sum_m P8[m,a] --
  * the bias gradient from the SAME e4m3 bytes the weight gradient is made of (a ones operand on the matrix pipe). */
 int tvts_gemm_tn_fp8(const void* P8, int ldp, const void* Q8, int ldq, int M, int Na, int Nb, const float* scale_p,
                      const float* scale_q, float* out, int ldo, int accumulate, float* colsum, float* workspace,
                      long workspace_elems, int opts, hipStream_t stream);
 /* (main loop of tvts_gemm_nt_fp8*: v_mfma_scale_f32_16x16x128_f8f6f4 with unit scales, the fp8 issue rate of gfx950;
- * TVTS_GEMM_FP8_K32 selects the 16x16x32 fp8 form) */
+ * TVTS_GEMM_FP8_K32 selects the 16x16x32 fp8 form.  Both e4m3 instructions leave an error of about 2^-12 of an element's largest
+ * product whatever the contraction length, which only a long contraction's fp32-accumulation bound covers: contractions shorter
+ * than 512 -- K of tvts_gemm_nt_fp8 / _fp8_gate, M of tvts_gemm_tn_fp8 -- run with the e4m3 values decoded to bf16 in registers
+ * (exact) on the bf16 MFMA, whichever main loop `opts` names) */
 /* per-tensor fp8 quantisation: amax[0] = max |x| ; q = rne(x * 448 / amax) as e4m3, scale_out[0] = amax / 448 */
 int tvts_amax(const void* x, int is_f32, long ld, int rows, int cols, float* amax, hipStream_t stream);
 int tvts_quant_fp8(const void* x, int is_f32, long ld, int rows, int cols, const float* amax, void* out, long ldo,
@@ -164,7 +179,8 @@ int tvts_fp8_update_scales(float* amax, float* scale, int n, hipStream_t stream)
 int tvts_gemm_small_f32(const float* A, long sai, long sak, const float* B, long sbk, long sbj, int M, int N, int K,
                         float alpha, const float* bias, float* C, long ldc, int accumulate, hipStream_t stream);
 /* a FEW rows through a linear layer with fp32 result and fp32 residual: out[r, n] = residual[r, n] + bias[n] + sum_k A[r * lda + k] W[n * ldw + k]
- * (A, W bf16; N % 16 == 0, K % 32 == 0; bias / residual optional).  The CLS rows of the hybrid residual stream through the blocks'
+ * (A, W bf16; N % 16 == 0, K % 32 == 0, lda / ldw % 8 == 0 and >= K, ldo >= N, ldr >= N with a residual, else -22; bias / residual
+ * optional).  The CLS rows of the hybrid residual stream through the blocks'
  * residual-adding projections (`x + attn(...)`, `x + mlp(...)`, video_encoder_ViT_B_16.py:121-124): one row per clip, lda = S * K. */
 int tvts_rows_linear_bf16(const void* A, long lda, const void* W, int ldw, int R, int N, int K, const float* bias, const float* residual,
                           int ldr, float* out, int ldo, hipStream_t stream);
@@ -176,7 +192,8 @@ int tvts_rows_linear_bf16(const void* A, long lda, const void* W, int ldw, int R
 int tvts_rows_linear_fp8(const void* A8, long lda, const float* row_scale, const void* W8, int ldw, const float* w_scale, int R, int N,
                          int K, const float* bias, const float* residual, int ldr, float* out, int ldo, hipStream_t stream);
 /* bias gradient: out[n] += sum_m X[m,n].  workspace (optional): partial sums of row ranges, added in range order (deterministic, and
- * a grid over the rows as well as the columns); without it one block per 64 columns walks every row */
+ * a grid over the rows as well as the columns); without it one block per 64 columns walks every row.  N % 8 == 0, ld % 8 == 0,
+ * ld >= N, X / out not null, workspace_elems >= 0, else -22 */
 int tvts_colsum_bf16(const void* X, int ld, int M, int N, float* out, float* workspace, long workspace_elems, hipStream_t stream);
 
 /* ---- LayerNorm (norm.hip): video_encoder_ViT_B_16.py:79-85 (eps 1e-5), sort_transformer.py:99 (eps 1e-6) */

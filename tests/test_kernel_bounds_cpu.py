@@ -649,3 +649,80 @@ def test_adamw_check_passes_fp32_and_catches_m_updated_with_beta2():
     sh = out[3].clone()
     sh[5] = sh[6]
     fails(lambda: KB.adamw_check(p, gr, m, v, out[0], out[1], out[2], sh, lr=1e-2, wd=0.05, step=2, grad_scale=0.5, what="adamw"), "bf16 shadow")
+
+
+# ------------------------------------------------------------------------------------------------ GEMM edge shapes
+# The smallest shapes of tests/test_gemm_edges_gpu.py: the checks those tests apply CAN fail there (every edge mistake a kernel can
+# make is rejected) and a correct result cannot (the fp32 emulation passes every form's bound).
+EDGE_NT = [(1, 4, 64), (129, 132, 64), (257, 264, 320)]  # (M, N, K)
+EDGE_TN = [(1, 8, 8), (65, 120, 136)]                    # (M, Na, Nb)
+
+
+def edge_tn_operands(M, Na, Nb, seed):
+    g = torch.Generator().manual_seed(seed)
+    p, q = torch.randn(M, Na, generator=g).bfloat16(), torch.randn(M, Nb, generator=g).bfloat16()
+    return p, q, torch.randn(Na, Nb, generator=g), torch.randn(Na, generator=g)
+
+
+def test_fp32_emulation_passes_every_forms_bound_at_the_edge_shapes():
+    for (M, N, Kd) in EDGE_NT:
+        a, b, bias = operands(M, N, Kd, seed=100 + M)
+        g = torch.Generator().manual_seed(200 + M)
+        res, h = torch.randn(M, N, generator=g), (torch.randn(M, N, generator=g) * 1.5).bfloat16()
+        z = a.float() @ b.float().t()
+        pre = z + bias
+        check(z.bfloat16(), a, b)                                                # plain, no bias
+        for dt in (torch.float32, torch.bfloat16):
+            check(pre.to(dt), a, b, bias=bias)
+            check((pre + res).to(dt), a, b, bias=bias, residual=res)
+        check((pre + h.float()).bfloat16(), a, b, bias=bias, add_bf16=h)         # the bf16 residual stream
+        for act in ("quick_gelu", "gelu"):
+            y = KB.act_ref(pre.double(), act).float()
+            d = KB.act_deriv_ref(pre.double(), act).float()
+            check(y.bfloat16(), a, b, bias=bias, act=act, preact=pre.bfloat16())
+            check(y.bfloat16(), a, b, bias=bias, act=act, preact=d.bfloat16(), deriv=True)
+            check((z * KB.act_deriv_ref(h.double(), act).float()).bfloat16(), a, b, gate_h=h, gate_act=act)
+            check((z * h.float()).bfloat16(), a, b, gate_h=h, gate_act=act, deriv=True)
+    for (M, Na, Nb) in EDGE_TN:
+        p, q, init, cs0 = edge_tn_operands(M, Na, Nb, seed=300 + M)
+        out = p.float().t() @ q.float()
+        check(out, p.t(), q.t(), K=M)
+        check(init + out, p.t(), q.t(), residual=init, K=M)
+        bound = KB.sum_bound(p.double().abs().sum(0), M, init=cs0)
+        assert KB.assert_within(cs0 + p.float().sum(0), p.double().sum(0) + cs0.double(), bound, "colsum") <= 1.0
+
+
+def test_edge_mistakes_are_rejected_at_every_edge_shape():
+    """what a kernel gets wrong at a tile edge, applied to the correct result: the last 64-deep k stage left out, the last row
+    computed from row M - 2 of a (a clamp one row short), the last four columns computed from the four before them (the N - 8
+    clamp where N - 4 was meant); for TN a tail row m = M counted in with the values of row M - 1 (the clamped row not zeroed)
+    and the column sum missing the last row.  Each must fail at each shape, for fp32 and bf16 results.  Two combinations do not
+    exist: M = 1 has no row M - 2 and N = 4 no four columns before the last four (the kernels' clamps cannot go there either)."""
+    done = set()
+    for (M, N, Kd) in EDGE_NT:
+        a, b, bias = operands(M, N, Kd, seed=100 + M)
+        ok = a.float() @ b.float().t() + bias
+        muts = {"last k stage left out": a[:, :Kd - 64].float() @ b[:, :Kd - 64].float().t() + bias}
+        if M >= 2:
+            x = ok.clone()
+            x[-1] = a[M - 2].float() @ b.float().t() + bias
+            muts["last row from row M - 2"] = x
+        if N >= 8:
+            x = ok.clone()
+            x[:, N - 4:] = ok[:, N - 8:N - 4]
+            muts["last four columns from the four before"] = x
+        for name, x in muts.items():
+            for dt in (torch.float32, torch.bfloat16):
+                check(ok.to(dt), a, b, bias=bias)
+                fails(lambda: check(x.to(dt), a, b, bias=bias), "outside the bound")
+            done.add(name)
+    assert len(done) == 3
+    for (M, Na, Nb) in EDGE_TN:
+        p, q, init, cs0 = edge_tn_operands(M, Na, Nb, seed=300 + M)
+        ok = init + p.float().t() @ q.float()
+        tail = ok + p[M - 1].float()[:, None] * q[M - 1].float()[None, :]
+        fails(lambda: check(tail, p.t(), q.t(), residual=init, K=M), "outside the bound")
+        fails(lambda: check(tail - init, p.t(), q.t(), K=M), "outside the bound")
+        ref, bound = p.double().sum(0) + cs0.double(), KB.sum_bound(p.double().abs().sum(0), M, init=cs0)
+        fails(lambda: KB.assert_within(cs0 + p[:M - 1].float().sum(0), ref, bound, "colsum"), "outside the bound")
+        fails(lambda: KB.assert_within(cs0 + p.float().sum(0) + p[M - 1].float(), ref, bound, "colsum"), "outside the bound")  # ... or the tail row twice

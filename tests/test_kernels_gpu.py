@@ -1528,16 +1528,7 @@ def test_two_threads_call_different_shapes_and_options_concurrently(K):
 # (GEMM, LayerNorm), every (row, head) slice or dgamma / dbeta column to a calibrated tolerance, and exact operations to their bits,
 # with NaN / 0xFF guard rows and columns around what a kernel writes.  Each prints its worst |err| / bound ("BOUND" lines).
 import kernel_bounds as KB  # noqa: E402
-
-
-def _form(got, a, b, **kw):
-    """check_gemm of one form, its own line in the record"""
-    acc0 = KB.pop_acc_worst()
-    w = KB.check_gemm(got, a, b, **kw)
-    acc = KB.pop_acc_worst()
-    print(f"FORM {kw['what']} {w:.4g} acc {acc:.4g}")
-    KB.ACC_WORST[0] = max(acc0, acc)
-    return w
+import gemm_cases as GC  # noqa: E402  (the form loops, shared with tests/test_gemm_edges_gpu.py)
 
 
 # forms a parametrised shape must take (the shapes test_gemm_nt_streamk / test_gemm_nt_ring_gives_the_bits_of_the_128_kernel /
@@ -1560,48 +1551,8 @@ def test_gemm_nt_forms_within_the_bound(K, M, N, K_):
     res = torch.randn(M, N, device=DEV)
     h = (torch.randn(M, N, device=DEV) * 1.5).bfloat16()
     forms = [dict(tile=None), dict(tile=128), dict(tile=256), dict(streamk=True), dict(tile="ring"), dict(tile="ring4")]
-    worst = 0.0
-    taken = set()
-    for f in forms:
-        name = "streamk" if f.get("streamk") else str(f.get("tile"))
-        for dt in (torch.bfloat16, torch.float32):
-            buf, out = KB.guarded(M, N, dt, DEV)
-            sk0 = K.STREAMK_TAKEN[0]
-            try:
-                K.gemm_nt(a, b, out, bias=bias, **f)
-            except K.HipError:
-                assert f.get("streamk") or "ring" in str(f.get("tile")), f  # a form the shape cannot take refuses it (no silent fall-back)
-                print(f"FORM nt {name} {dt} refused at {M},{N},{K_}")
-                continue
-            if f.get("streamk"):
-                assert K.STREAMK_TAKEN[0] == sk0 + 1, "stream-K accepted but not taken"
-            taken.add(name)
-            worst = max(worst, KB.check_gemm(out, a, b, bias=bias, what=f"nt {f} {dt}"))
-            KB.check_guards(buf, M, N, f"nt {f} {dt}")
-        buf, out = KB.guarded(M, N, torch.float32, DEV)
-        if f.get("streamk") is None and "ring" not in str(f.get("tile")):
-            K.gemm_nt(a, b, out, bias=bias, residual=res, **f)
-            worst = max(worst, KB.check_gemm(out, a, b, bias=bias, residual=res, what=f"nt residual {f}"))
-            KB.check_guards(buf, M, N)
-    for act in ("quick_gelu", "gelu"):
-        for tile in (None, 128, 256):
-            for deriv in (False, True):
-                buf, out = KB.guarded(M, N, torch.bfloat16, DEV)
-                pbuf, pre = KB.guarded(M, N, torch.bfloat16, DEV)
-                K.gemm_nt(a, b, out, bias=bias, act=act, preact=pre, tile=tile, side_deriv=deriv)
-                worst = max(worst, KB.check_gemm(out, a, b, bias=bias, act=act, preact=pre, deriv=deriv, what=f"nt {act} {tile} {deriv}"))
-                KB.check_guards(buf, M, N); KB.check_guards(pbuf, M, N)
-                gbuf, gout = KB.guarded(M, N, torch.bfloat16, DEV)
-                hh = pre if deriv else h
-                K.gemm_nt(a, b, gout, gate_h=hh, gate_act=act, tile=tile, side_deriv=deriv)
-                worst = max(worst, KB.check_gemm(gout, a, b, gate_h=hh, gate_act=act, deriv=deriv, what=f"nt gate {act} {tile} {deriv}"))
-                KB.check_guards(gbuf, M, N)
-    buf, out = KB.guarded(M, N, torch.bfloat16, DEV)
-    K.gemm_nt(a, b, out, bias=bias, residual=h)  # the bf16 residual stream through the gate slot
-    worst = max(worst, KB.check_gemm(out, a, b, bias=bias, add_bf16=h, what="nt bf16 residual"))
-    KB.check_guards(buf, M, N)
-    missing = NT_MUST_TAKE.get((M, N, K_), set()) - taken
-    assert not missing, f"forms refused at {M},{N},{K_}: {missing}"
+    worst, _ = GC.nt_forms(K, a, b, bias, res, h, forms=forms, act_forms=[dict(tile=None), dict(tile=128), dict(tile=256)],
+                           must_take=NT_MUST_TAKE.get((M, N, K_), set()))
     KB.bound_line(f"gemm_nt_forms[{M},{N},{K_}]", worst)
 
 
@@ -1613,27 +1564,8 @@ def test_gemm_tn_forms_within_the_bound(K, M, Na, Nb):
     p = torch.randn(M, Na, generator=g, device=DEV).bfloat16()
     q = torch.randn(M, Nb, generator=g, device=DEV).bfloat16()
     init = torch.randn(Na, Nb, generator=g, device=DEV)
-    pt, qt = p.t(), q.t()
-    worst = 0.0
-    fused_runs = 0
-    for kw in (dict(tile=128), dict(tile=256), dict(tile=128, fused=True), dict(tile=256, fused=True), dict(workspace=False),
-               dict(tile=256, workspace=False)):
-        for accumulate in (False, True):
-            buf, out = KB.guarded(Na, Nb, torch.float32, DEV)
-            if accumulate:
-                out.copy_(init)
-            sk0 = K.STREAMK_TAKEN[0]
-            try:
-                K.gemm_tn(p, q, out, accumulate=accumulate, **kw)
-            except K.HipError:
-                assert kw.get("fused"), kw  # the fused reduce needs a split; a one-split shape refuses it
-                print(f"FORM tn fused {kw} refused at {M},{Na},{Nb}")
-                continue
-            if kw.get("fused"):
-                assert K.STREAMK_TAKEN[0] == sk0 + 1, "fused reduce accepted but not taken"
-                fused_runs += 1
-            worst = max(worst, KB.check_gemm(out, pt, qt, residual=init if accumulate else None, K=M, what=f"tn {kw} acc={accumulate}"))
-            KB.check_guards(buf, Na, Nb, f"tn {kw} acc={accumulate}")
+    worst, fused_runs = GC.tn_forms(K, p, q, init, (dict(tile=128), dict(tile=256), dict(tile=128, fused=True), dict(tile=256, fused=True),
+                                                    dict(workspace=False), dict(tile=256, workspace=False)))
     if (M, Na, Nb) in TN_MUST_FUSE:
         assert fused_runs == 4, f"the fused reduce ran {fused_runs} of 4 times at {M},{Na},{Nb}"
     KB.bound_line(f"gemm_tn_forms[{M},{Na},{Nb}]", worst)
@@ -1685,42 +1617,12 @@ def test_gemm_fp8_forms_within_the_bound(K, M, N, K_):
     b = torch.randn(N, K_, generator=g, device=DEV) * K_ ** -0.5
     bias, res = torch.randn(N, generator=g, device=DEV), torch.randn(M, N, generator=g, device=DEV)
     b8, sb = K.quantize_fp8(b)
-    bd = KB.decode_e4m3(b8)
-    worst = 0.0
-    for kind in ("tensor", "rows"):
-        a8, sa = K.quantize_fp8(a) if kind == "tensor" else K.quantize_fp8_rows(a.bfloat16())
-        ad = KB.decode_e4m3(a8)
-        scale = sa.double() * sb.double() if kind == "rows" else float(sa) * float(sb)
-        for dt in (torch.bfloat16, torch.float32):
-            buf, out = KB.guarded(M, N, dt, DEV)
-            K.gemm_nt_fp8(a8, sa, b8, sb, out, bias=bias)
-            worst = max(worst, _form(out, ad, bd, scale=scale, bias=bias, what=f"fp8 {kind} {dt}"))
-            KB.check_guards(buf, M, N)
-        buf, out = KB.guarded(M, N, torch.float32, DEV)
-        K.gemm_nt_fp8(a8, sa, b8, sb, out, bias=bias, residual=res)
-        worst = max(worst, _form(out, ad, bd, scale=scale, bias=bias, residual=res, what=f"fp8 {kind} residual"))
-        KB.check_guards(buf, M, N, f"fp8 {kind} residual")
-        buf, out = KB.guarded(M, N, torch.bfloat16, DEV)
-        pbuf, pre = KB.guarded(M, N, torch.bfloat16, DEV)
-        K.gemm_nt_fp8(a8, sa, b8, sb, out, bias=bias, act="gelu", preact=pre)
-        worst = max(worst, _form(out, ad, bd, scale=scale, bias=bias, act="gelu", preact=pre, what=f"fp8 {kind} gelu"))
-        KB.check_guards(buf, M, N); KB.check_guards(pbuf, M, N)
-        h = (torch.randn(M, N, generator=g, device=DEV) * 1.5).bfloat16()
-        for act in ("quick_gelu", "gelu"):
-            buf, out = KB.guarded(M, N, torch.bfloat16, DEV)
-            K.gemm_nt_fp8(a8, sa, b8, sb, out, gate_h=h, gate_act=act)
-            worst = max(worst, _form(out, ad, bd, scale=scale, gate_h=h, gate_act=act, what=f"fp8 {kind} gate {act}"))
-            KB.check_guards(buf, M, N)
+    worst = GC.fp8_nt_forms(K, a, b8, sb, bias, res, g)
     # TN: out (+)= sp sq P8^T Q8 over K = M tokens
     p8, sp = K.quantize_fp8(a.bfloat16())
     q8, sq = K.quantize_fp8(torch.randn(M, N // 2, generator=g, device=DEV))
     init = torch.randn(K_, N // 2, generator=g, device=DEV)
-    for accumulate in (False, True):
-        for ws in (True, False):
-            out = init.clone() if accumulate else torch.full((K_, N // 2), float("nan"), device=DEV)
-            K.gemm_tn_fp8(p8, sp, q8, sq, out, accumulate=accumulate, workspace=ws)
-            worst = max(worst, _form(out, KB.decode_e4m3(p8).t(), KB.decode_e4m3(q8).t(), scale=float(sp) * float(sq),
-                                             residual=init if accumulate else None, K=M, what=f"fp8 tn acc={accumulate} ws={ws}"))
+    worst = max(worst, GC.fp8_tn_forms(K, p8, sp, q8, sq, init))
     KB.bound_line(f"gemm_fp8_forms[{M},{N},{K_}]", worst)
 
 

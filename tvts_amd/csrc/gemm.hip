@@ -338,6 +338,22 @@ static int launch_nt256(GemmNT& g, int act, int gate_act, bool gated, int opts, 
             if (gated) kern = gate_act == ACT_QUICK_GELU ? gemm_nt256p_kernel<0, 1, true, QF> : gate_act == ACT_GELU_ERF ? gemm_nt256p_kernel<0, 2, true, QF> : nullptr;
             else kern = act == ACT_QUICK_GELU ? gemm_nt256p_kernel<1, 0, true, QF> : act == ACT_GELU_ERF ? gemm_nt256p_kernel<2, 0, true, QF> : nullptr;
         }
+        // a contraction under FP8_EXACT_BELOW e4m3 values (g.K counts them in pairs): the same kernels with the fragments decoded to bf16
+        // (gemm_nt256.h, ABL & 33554432), whichever main loop the call names; every form above has its twin
+        if (2 * g.K < FP8_EXACT_BELOW && kern) {
+            constexpr int D8 = SD | 33554432, D8Q = D8 | 1048576;
+            if (g.q8) {
+                if (gated) kern = gate_act == ACT_QUICK_GELU ? gemm_nt256p_kernel<0, 1, true, D8Q> : gemm_nt256p_kernel<0, 2, true, D8Q>;
+                else kern = act == ACT_QUICK_GELU ? gemm_nt256p_kernel<1, 0, true, D8Q> : gemm_nt256p_kernel<2, 0, true, D8Q>;
+            } else if (gated) {
+                kern = gate_act == ACT_QUICK_GELU ? gemm_nt256p_kernel<0, 1, true, D8> : gate_act == ACT_GELU_ERF ? gemm_nt256p_kernel<0, 2, true, D8>
+                                                                                       : gemm_nt256p_kernel<0, 3, true, D8>;
+            } else if (act == ACT_NONE) {
+                kern = g.residual ? gemm_nt256p_kernel<0, 0, true, 256 | D8> : gemm_nt256p_kernel<0, 0, true, D8>;
+            } else {
+                kern = act == ACT_QUICK_GELU ? gemm_nt256p_kernel<1, 0, true, D8> : gemm_nt256p_kernel<2, 0, true, D8>;
+            }
+        }
     }
     if constexpr (!FP8) {
         if (g.sk_ws) {  // stream-K: the generic patch epilogue (bias and side inputs are read by the block that sums the pieces)
@@ -473,9 +489,12 @@ extern "C" int tvts_gemm_nt_bf16(const void* A, int lda, const void* B, int ldb,
                                  const float* bias, const float* residual, int ldr, int act, void* preact,
                                  int ldp, const void* gate_h, int ldh, int gate_act, void* out, int ldc,
                                  int out_f32, void* workspace, long workspace_bytes, int opts, hipStream_t stream) {
-    if (M <= 0 || N <= 0 || K <= 0) return TVTS_EINVAL;
+    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !out || workspace_bytes < 0) return TVTS_EINVAL;
     if (K % BK != 0 || N % 4 != 0 || lda % 8 != 0 || ldb % 8 != 0) return TVTS_EINVAL;
     if ((ldc % 4) || (residual && (ldr % 4)) || (preact && (ldp % 4)) || (gate_h && (ldh % 4))) return TVTS_EINVAL;
+    // a row of every matrix the call names holds at least its width: a shorter pitch (0 included) would make rows overlap or run past the buffer
+    if (lda < K || ldb < K || ldc < N || (residual && ldr < N) || (preact && ldp < N) || (gate_h && ldh < N)) return TVTS_EINVAL;
+    if (gate_h && act != ACT_NONE) return TVTS_EINVAL;  // an activation and a gate exclude each other (every kernel below says the same)
     GemmNT g;
     g.A = (const bf16*)A; g.lda = lda; g.B = (const bf16*)B; g.ldb = ldb;
     g.M = M; g.N = N; g.K = K; g.bias = bias; g.residual = residual; g.ldr = ldr; g.act = act;
@@ -485,7 +504,8 @@ extern "C" int tvts_gemm_nt_bf16(const void* A, int lda, const void* B, int ldb,
     g.sk_ws = nullptr; g.sk_cnt = nullptr; g.sk_tol = 0; g.q8 = nullptr; g.ldq8 = 0; g.q8_scale = nullptr; g.q8_amax = nullptr;
     if (nt_use_256(M, N, K, workspace != nullptr, opts)) {
         if (ldc % 8 || (preact && ldp % 8) || (gate_h && ldh % 8)) {
-            if (opt_tile(opts) == 256) return TVTS_EINVAL;  // forced, but the 16-byte epilogue accesses do not fit
+            // forced (the tile, or the stream-K walk that only this kernel has), but the 16-byte epilogue accesses do not fit
+            if (opt_tile(opts) == 256 || (opts & 32)) return TVTS_EINVAL;
         } else {
             return launch_nt256<false>(g, act, gate_act, gate_h != nullptr, opts, stream, workspace, workspace_bytes);
         }
@@ -519,8 +539,9 @@ extern "C" int tvts_gemm_nt_fp8(const void* A, int lda, const void* B, int ldb, 
                                 int scale_a_rows, const float* scale_b, const float* bias, const float* residual, int ldr, int act, void* preact,
                                 int ldp, void* out, int ldc, int out_f32, void* q8out, int ldq8, const float* q8_scale, float* q8_amax,
                                 int opts, hipStream_t stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || !scale_a || !scale_b || (q8out && !q8_scale) || (!out && !q8out)) return TVTS_EINVAL;
+    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !scale_a || !scale_b || (q8out && !q8_scale) || (!out && !q8out)) return TVTS_EINVAL;
     if (K % 128 || N % 8 || lda % 16 || ldb % 16 || ldc % 8 || (residual && ldr % 4) || (preact && ldp % 8)) return TVTS_EINVAL;
+    if (lda < K || ldb < K || (out && ldc < N) || (residual && ldr < N) || (preact && ldp < N) || (q8out && ldq8 < N)) return TVTS_EINVAL;
     GemmNT g;
     g.A = (const bf16*)A; g.lda = lda / 2; g.B = (const bf16*)B; g.ldb = ldb / 2;  // byte-identical bf16 view, half as wide
     g.M = M; g.N = N; g.K = K / 2; g.bias = bias; g.residual = residual; g.ldr = ldr; g.act = act;
@@ -539,8 +560,9 @@ extern "C" int tvts_gemm_nt_fp8_gate(const void* A, int lda, const void* B, int 
                                      int scale_a_rows, const float* scale_b, const float* bias, const void* gate_h, int ldh,
                                      int gate_act, void* out, int ldc, void* q8out, int ldq8, const float* q8_scale, float* q8_amax,
                                      int opts, hipStream_t stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || !scale_a || !scale_b || !gate_h || (q8out && !q8_scale) || (!out && !q8out)) return TVTS_EINVAL;
+    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !scale_a || !scale_b || !gate_h || (q8out && !q8_scale) || (!out && !q8out)) return TVTS_EINVAL;
     if (K % 128 || N % 8 || lda % 16 || ldb % 16 || ldc % 8 || ldh % 8) return TVTS_EINVAL;
+    if (lda < K || ldb < K || (out && ldc < N) || ldh < N || (q8out && ldq8 < N)) return TVTS_EINVAL;
     GemmNT g;
     g.A = (const bf16*)A; g.lda = lda / 2; g.B = (const bf16*)B; g.ldb = ldb / 2;
     g.M = M; g.N = N; g.K = K / 2; g.bias = bias; g.residual = nullptr; g.ldr = 0; g.act = ACT_NONE;
@@ -997,8 +1019,9 @@ extern "C" int tvts_gemm_tn_select(int M, int Na, int Nb, int opts) { return tn_
 extern "C" int tvts_gemm_tn_bf16(const void* P, int ldp, const void* Q, int ldq, int M, int Na, int Nb,
                                  float* out, int ldo, int accumulate, float* colsum, float* workspace,
                                  long workspace_elems, int* counters, int n_counters, int opts, hipStream_t stream) {
-    if (M <= 0 || Na <= 0 || Nb <= 0) return TVTS_EINVAL;
+    if (M <= 0 || Na <= 0 || Nb <= 0 || !P || !Q || !out || workspace_elems < 0) return TVTS_EINVAL;
     if (Na % 8 || Nb % 8 || ldp % 8 || ldq % 8 || ldo % 4) return TVTS_EINVAL;
+    if (ldp < Na || ldq < Nb || ldo < Nb) return TVTS_EINVAL;
     GemmTN g;
     g.ws = nullptr; g.cs_ws = nullptr; g.splits = 1; g.early_dma = 0; g.tiles_a = 0; g.a_fast = 0; g.cnt = nullptr; g.accumulate = accumulate;
     g.P = (const bf16*)P; g.ldp = ldp; g.Q = (const bf16*)Q; g.ldq = ldq; g.M = M; g.Na = Na; g.Nb = Nb;
@@ -1166,8 +1189,9 @@ extern "C" int tvts_gemm_tn_bf16_grouped(const void* problems, int n, void* tabl
 extern "C" int tvts_gemm_tn_fp8(const void* P8, int ldp, const void* Q8, int ldq, int M, int Na, int Nb, const float* scale_p,
                                 const float* scale_q, float* out, int ldo, int accumulate, float* colsum, float* workspace,
                                 long workspace_elems, int opts, hipStream_t stream) {
-    if (M <= 0 || Na <= 0 || Nb <= 0 || !scale_p || !scale_q) return TVTS_EINVAL;
+    if (M <= 0 || Na <= 0 || Nb <= 0 || !P8 || !Q8 || !out || !scale_p || !scale_q || workspace_elems < 0) return TVTS_EINVAL;
     if (Na % 16 || Nb % 16 || ldp % 16 || ldq % 16 || ldo % 4) return TVTS_EINVAL;
+    if (ldp < Na || ldq < Nb || ldo < Nb) return TVTS_EINVAL;
     if ((unsigned long long)M * (unsigned long long)(ldp > ldq ? ldp : ldq) >= (1ull << 32)) return TVTS_EINVAL;  // 32-bit DMA offsets
     GemmTN8 g;
     g.P = (const unsigned char*)P8; g.ldp = ldp; g.Q = (const unsigned char*)Q8; g.ldq = ldq; g.M = M; g.Na = Na; g.Nb = Nb;
@@ -1202,9 +1226,10 @@ extern "C" int tvts_gemm_tn_fp8(const void* P8, int ldp, const void* Q8, int ldq
     }
     g.n_items = g.tiles_ab * splits;
     const int grid = ceil_div(g.n_items, 8) * 8;
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_tn8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    void (*kern)(GemmTN8) = M < FP8_EXACT_BELOW ? gemm_tn8_kernel<true> : gemm_tn8_kernel<false>;  // (short contractions: decoded to bf16)
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(gemm_tn8_kernel, dim3(grid), dim3(512), 131072, stream, g);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 131072, stream, g);
     if (splits > 1) {
         const long n4 = (long)Na * Nb / 4;
         int rb = (int)((n4 + 255) / 256);
@@ -1419,6 +1444,7 @@ extern "C" int tvts_rows_linear_bf16(const void* A, long lda, const void* W, int
                                      const float* residual, int ldr, float* out, int ldo, hipStream_t stream) {
     if (R <= 0 || N <= 0 || K <= 0 || !A || !W || !out) return TVTS_EINVAL;
     if (N % 16 || K % 32 || lda % 8 || ldw % 8) return TVTS_EINVAL;
+    if (lda < K || ldw < K || ldo < N || (residual && ldr < N)) return TVTS_EINVAL;
     hipLaunchKernelGGL(rows_linear_kernel, dim3(N / 16, ceil_div(R, 16)), dim3(256), 0, stream, (const bf16*)A, lda, (const bf16*)W, ldw,
                        R, N, K, bias, residual, ldr, out, ldo);
     TVTS_LAUNCH_CHECK();
@@ -1565,7 +1591,7 @@ __global__ __launch_bounds__(256) void colsum_ranges_kernel(const float* __restr
 
 extern "C" int tvts_colsum_bf16(const void* X, int ld, int M, int N, float* out, float* workspace, long workspace_elems,
                                 hipStream_t stream) {
-    if (M <= 0 || N <= 0 || N % 8 || ld % 8) return TVTS_EINVAL;
+    if (M <= 0 || N <= 0 || N % 8 || ld % 8 || !X || !out || ld < N || workspace_elems < 0) return TVTS_EINVAL;
     int ranges = ceil_div(M, 4096);
     if (ranges > 256) ranges = 256;
     if (workspace == nullptr || (long)ranges * N > workspace_elems) ranges = 1;

@@ -64,6 +64,9 @@ __device__ __forceinline__ void tn8_mask(tn8_i32x8& f, int valid, int lane) {
     }
 }
 
+// DEC (contractions shorter than FP8_EXACT_BELOW, gemm_nt256.h): every 32-byte operand is decoded to four bf16 fragments and multiplied
+// by four bf16 MFMAs -- lane group g's 8 k-slots of MFMA j are its tokens 32 g + 8 j + (0..7), the same for P and Q
+template <bool DEC>
 __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(GemmTN8 g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 stages][P rows 0-63 | P rows 64-127 | Q 0-63 | Q 64-127], 16 KiB each
     const int tid = threadIdx.x;
@@ -143,7 +146,11 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(GemmTN8 g) {
 #define TN8_OFF(ct) (fbase + (fx ^ (((unsigned)((ct) >> 1) << 5) | ((unsigned)((ct) & 1) << 4))))
     int mx_one = 0x7F7F7F7F;  // E8M0 127 = 1.0 in every byte of the scale operand
     asm volatile("" : "+v"(mx_one));
-#define TN8_MFMA(bv, av, c) asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0]" : "+v"(c) : "v"(bv), "v"(av), "v"(mx_one))
+#define TN8_MFMA(bv, av, c)                                                                             \
+    if constexpr (DEC) {                                                                                \
+        _Pragma("unroll") for (int d_ = 0; d_ < 4; ++d_)                                                \
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(e4m3x8_to_bf16(bv[2 * d_], bv[2 * d_ + 1]), e4m3x8_to_bf16(av[2 * d_], av[2 * d_ + 1]), c, 0, 0, 0); \
+    } else asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0]" : "+v"(c) : "v"(bv), "v"(av), "v"(mx_one))
     tn8_i32x8 pQ[2][2], qQ[4];
     // bias gradient: wave (wa, wb) of a first-column block sums a-tiles 2 wb, 2 wb + 1 of its half = pair wb of the stage's four P pairs
     const bool do_cs = g.colsum != nullptr && tb == 0;  // block-uniform
