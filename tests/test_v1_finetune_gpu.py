@@ -464,6 +464,19 @@ def test_seed_advances_once_per_step_and_resumes(K, fx):
     assert tabs[0].numpy().tobytes() == fx["f"]["tables"][0].tobytes()  # (the fixture's masks are this seed's draw)
 
 
+def test_unsynced_hyper_table_is_refused_under_capture(K, monkeypatch):
+    """as FusedHFAdamW: a device-step launch on a capturing stream cannot upload lr / weight_decay, so param_groups changed after
+    sync_hyper() are refused.  No graph is built: only the host-side check of _begin() runs, the capture query patched"""
+    _, opt = stepper(build())
+    opt.sync_hyper()
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
+    opt._begin(True)  # the table matches param_groups: accepted
+    opt.param_groups[0]["lr"] *= 0.5
+    with pytest.raises(RuntimeError, match="FusedTorchAdamW: call sync_hyper"):
+        opt._begin(True)
+    assert opt.global_step == 1 and int(opt.step_dev.item()) == 1  # (the refusal came before the counters moved)
+
+
 def test_inference_between_steps_changes_nothing(K, fx):
     a, b = build(), build()
     sa, _ = stepper(a)

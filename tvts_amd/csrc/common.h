@@ -37,6 +37,24 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// Block reductions of a 256-thread block through four floats of LDS: butterfly inside each wave, then the four wave results
+// combined by every thread alike, always in the same order -- two runs over the same bits give the same bits.
+// block_sum_256 opens with a barrier, so `sh` may still be read from a reduction just before it; block_max_256 has none: give it
+// an `sh` that no earlier reduction of the kernel uses.
+__device__ __forceinline__ float block_sum_256(float v, float* sh) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+__device__ __forceinline__ float block_max_256(float v, float* sh) {
+    v = wave_max(v);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+}
+
 // QuickGELU x*sigmoid(1.702x) and its derivative on the fast transcendental path (v_exp_f32 + v_rcp_f32, ~1 ulp):
 // the epilogue evaluates 64 K of these per output tile while the matrix pipe waits.
 __device__ __forceinline__ float fast_sigmoid(float z) {
@@ -173,6 +191,14 @@ __device__ __forceinline__ float q8_scale(const float* tscale, float row_amax) {
         return s > 0.f ? s : 1.0f;
     }
     return row_amax > 0.f ? row_amax / 448.0f : 1.0f;
+}
+
+// four values * inv -> four OCP e4m3 bytes (rne, saturating at +-448), the first in the low byte
+__device__ __forceinline__ int pack4_e4m3(float a, float b, float c, float e, float inv) {
+    int p = 0;
+    p = __builtin_amdgcn_cvt_pk_fp8_f32(fminf(fmaxf(a * inv, -448.0f), 448.0f), fminf(fmaxf(b * inv, -448.0f), 448.0f), p, false);
+    p = __builtin_amdgcn_cvt_pk_fp8_f32(fminf(fmaxf(c * inv, -448.0f), 448.0f), fminf(fmaxf(e * inv, -448.0f), 448.0f), p, true);
+    return p;
 }
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }

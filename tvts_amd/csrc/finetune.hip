@@ -6,7 +6,7 @@
 //   tvts_soft_ce           soft-target / label-smoothing cross entropy on [B, C] logits: loss, dlogits, top-1 hit count
 //   tvts_grad_sumsq        global gradient norm over the trainable chunks of the flat gradient buffer + the clip coefficient,
 //                          both left in device memory
-//   tvts_adamw_torch       multi-tensor torch.optim.AdamW arithmetic over up to 64 parameter groups
+// (the step's optimizer, tvts_adamw_torch, is in optim.hip beside tvts_adamw_hf: the two share one chunk frame)
 //
 // Every reduction here runs in a FIXED order (no float atomics): two runs over the same bits give the same bits.
 #include "common.h"
@@ -95,14 +95,8 @@ extern "C" int tvts_drop_path_rows(const float* y, long ldy, long rows, int cols
 }
 
 // ---------------------------------------------------------------------------------------------- block reductions, fixed order
-// 256 threads: butterfly inside each wave, then the four wave results in wave order, by every thread alike
-__device__ __forceinline__ float block_sum256(float v, float* sh) {
-    v = wave_sum(v);
-    __syncthreads();  // (sh may still be read from the previous reduction)
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
+// 256 threads: butterfly inside each wave, then the four wave results in wave order, by every thread alike (sums: block_sum_256
+// of common.h)
 // (value, index): the larger value, the smaller index among equal values; NaN never wins
 __device__ __forceinline__ void amax_pair(float& v, int& i, float v2, int i2) {
     if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
@@ -152,11 +146,11 @@ __global__ __launch_bounds__(256) void soft_ce_rows_kernel(const float* __restri
     }
     ix = block_argmax256(mx, ix, shv, shi);
     it = tr ? block_argmax256(mt, it, shv, shi) : lab;
-    st = block_sum256(st, shv);
+    st = block_sum_256(st, shv);
     const float xmax = xr[ix < C ? ix : 0];
     float se = 0.f;
     for (int c = tid; c < C; c += 256) se += expf(xr[c] - xmax);
-    se = block_sum256(se, shv);
+    se = block_sum_256(se, shv);
     const float lse = logf(se), inv = 1.0f / se, g = gscale / (float)B;
     float acc = 0.f;
     for (int c = tid; c < C; c += 256) {
@@ -165,7 +159,7 @@ __global__ __launch_bounds__(256) void soft_ce_rows_kernel(const float* __restri
         if (t != 0.f) acc -= t * (z - lse);  // (t == 0 contributes nothing, also where logp = -inf)
         if (dlogits) dlogits[(long)b * ldd + c] = g * (expf(z) * inv * st - t);
     }
-    acc = block_sum256(acc, shv);
+    acc = block_sum_256(acc, shv);
     if (tid == 0) {
         ws[b] = acc;
         ws[B + b] = ix == it ? 1.0f : 0.f;
@@ -176,8 +170,8 @@ __global__ __launch_bounds__(256) void soft_ce_finish_kernel(const float* __rest
     __shared__ float sh[4];
     float l = 0.f, h = 0.f;
     for (int b = threadIdx.x; b < B; b += 256) { l += ws[b]; h += ws[B + b]; }
-    l = block_sum256(l, sh);
-    h = block_sum256(h, sh);  // (exact: integers below 2^24)
+    l = block_sum_256(l, sh);
+    h = block_sum_256(h, sh);  // (exact: integers below 2^24)
     if (threadIdx.x == 0) {
         loss_acc[0] += gscale * (l / (float)B);
         if (hits) hits[0] = (int)h;
@@ -211,7 +205,7 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict
         return;
     }
     const f32x4 v = *(const f32x4*)(g + (size_t)blockIdx.x * 1024 + threadIdx.x * 4);
-    const float s = block_sum256((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]), sh);
+    const float s = block_sum_256((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]), sh);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 __global__ __launch_bounds__(1024) void grad_norm_coef_kernel(const float* __restrict__ partial, int nchunks, float max_norm,
@@ -238,60 +232,6 @@ extern "C" int tvts_grad_sumsq(const float* g, const unsigned char* chunk_group,
     if (!g || !chunk_group || !partial || !norm_coef || nchunks <= 0 || ((size_t)g % 16)) return TVTS_EINVAL;
     hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nchunks), dim3(256), 0, stream, g, chunk_group, partial);
     hipLaunchKernelGGL(grad_norm_coef_kernel, dim3(1), dim3(1024), 0, stream, partial, nchunks, max_norm, grad_scale, norm_coef);
-    TVTS_LAUNCH_CHECK();
-    return TVTS_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- torch.optim.AdamW, multi-tensor
-// The optimizer run_class_finetuning.py builds through optim_factory.create_optimizer (opt "adamw") over the layer-decay parameter
-// groups (28 of them on ViT-B).  Per element, in torch's order (torch/optim/adamw.py, single-tensor form):
-//     p  *= 1 - lr wd                                   (the factor formed in double, rounded once)
-//     m   = b1 m + (1 - b1) g
-//     v   = b2 v + (1 - b2) g g
-//     p  -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)  (lr / bc1 and sqrt(bc2) formed in double, rounded once each)
-// with bc1 = 1 - b1^t, bc2 = 1 - b2^t in double from the double betas; t = step_dev[0] when given, else the host's `step` -- the
-// same device code either way, so both give the same bits.  g = stored gradient * grad_scale * norm_coef[1] (the clip coefficient
-// tvts_grad_sumsq left in device memory; no coefficient when norm_coef is null).  hyper_dev: lr[64] | wd[64] in device memory.
-// Chunk table as tvts_adamw_hf (1024 elements per chunk, one group byte each); a chunk of group >= 64 (255 = frozen) keeps every bit.
-__global__ __launch_bounds__(256) void adamw_torch_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                          float* __restrict__ v, bf16* __restrict__ shadow,
-                                                          const unsigned char* __restrict__ chunk_group,
-                                                          const float* __restrict__ hyper_dev, int step,
-                                                          const int* __restrict__ step_dev, double beta1d, double beta2d, float beta1,
-                                                          float beta2, float omb1, float omb2, float eps, float grad_scale,
-                                                          const float* __restrict__ norm_coef) {
-#pragma clang fp contract(off)
-    const int grp = chunk_group[blockIdx.x];
-    if (grp > 63) return;
-    const float lr = hyper_dev[grp], wd = hyper_dev[64 + grp];
-    const double st = (double)(step_dev ? step_dev[0] : step);
-    const double bc1 = 1.0 - pow(beta1d, st), bc2 = 1.0 - pow(beta2d, st);
-    const float decay = (float)(1.0 - (double)lr * (double)wd);
-    const float ss = (float)((double)lr / bc1), rs = (float)sqrt(bc2);
-    const float gs = norm_coef ? grad_scale * norm_coef[1] : grad_scale;
-    const size_t i = (size_t)blockIdx.x * 1024 + threadIdx.x * 4;
-    f32x4 pv = *(f32x4*)(p + i), mv = *(f32x4*)(m + i), vv = *(f32x4*)(v + i);
-    const f32x4 gv = *(const f32x4*)(g + i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float gg = gv[e] * gs;
-        pv[e] *= decay;
-        mv[e] = beta1 * mv[e] + omb1 * gg;
-        vv[e] = beta2 * vv[e] + omb2 * gg * gg;
-        pv[e] -= ss * mv[e] / (sqrtf(vv[e]) / rs + eps);
-    }
-    *(f32x4*)(p + i) = pv;
-    *(f32x4*)(m + i) = mv;
-    *(f32x4*)(v + i) = vv;
-    if (shadow) *(bf16x4*)(shadow + i) = (bf16x4){(bf16)pv[0], (bf16)pv[1], (bf16)pv[2], (bf16)pv[3]};
-}
-extern "C" int tvts_adamw_torch(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group,
-                                int nchunks, const float* hyper_dev, int step, const int* step_dev, double beta1, double beta2,
-                                double eps, float grad_scale, const float* norm_coef, hipStream_t stream) {
-    if (!p || !g || !m || !v || !chunk_group || !hyper_dev || nchunks <= 0 || (step <= 0 && !step_dev)) return TVTS_EINVAL;
-    hipLaunchKernelGGL(adamw_torch_kernel, dim3(nchunks), dim3(256), 0, stream, p, g, m, v, (bf16*)shadow_bf16, chunk_group,
-                       hyper_dev, step, step_dev, beta1, beta2, (float)beta1, (float)beta2, (float)(1.0 - beta1),
-                       (float)(1.0 - beta2), (float)eps, grad_scale, norm_coef);
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;
 }

@@ -96,14 +96,7 @@ __global__ __launch_bounds__(256) void infonce_grad_kernel(const float* __restri
     if (i == j) d -= 2.f;
     dx[idx] = d / (float)G;
 }
-// A block's 256 partial sums -> one value, always in the same order (lane butterfly, then the four waves left to right): the
-// loss scalars are run-to-run reproducible (they were fp32 atomics up to round 2).
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
+// (block_sum_256 adds a block's 256 partial sums in a fixed order: the loss scalars are run-to-run reproducible)
 // loss += -(1/G) sum_i [(x_ii - rowlse_i) + (x_ii - collse_i)]: ONE block, thread t takes i = t, t + 256, ... in order
 __global__ __launch_bounds__(256) void infonce_loss_kernel(const float* __restrict__ x, const float* __restrict__ lse, int G,
                                                            float* __restrict__ loss) {
@@ -228,10 +221,7 @@ __global__ __launch_bounds__(256) void v2v_rank_kernel(const float* __restrict__
         const float v = j == q ? -1000.0f : row[j];
         if (labels[j] == lq) best = fmaxf(best, v);
     }
-    best = wave_max(best);
-    if (lane == 0) redf[wave] = best;
-    __syncthreads();
-    best = fmaxf(fmaxf(redf[0], redf[1]), fmaxf(redf[2], redf[3]));
+    best = block_max_256(best, redf);
     int greater = 0;
     for (int j = threadIdx.x; j < N; j += 256) {
         const float v = j == q ? -1000.0f : row[j];

@@ -133,13 +133,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const TX* __restrict__ x, i
             for (int it = 0; it < IT; ++it) {
                 const int c = lane * 4 + it * 256;
                 if (c < W) {
-                    float f[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) f[e] = fminf(fmaxf(ob[it][e] * inv, -448.0f), 448.0f);
-                    int pk = 0;
-                    pk = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], pk, false);
-                    pk = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], pk, true);
-                    *(int*)(q8 + (size_t)r * ldq + c) = pk;
+                    *(int*)(q8 + (size_t)r * ldq + c) = pack4_e4m3(ob[it][0], ob[it][1], ob[it][2], ob[it][3], inv);
                 }
             }
             if (lane == 0 && row_scale) row_scale[r] = scale;
@@ -297,14 +291,8 @@ __global__ __launch_bounds__(256) void ln_fwd8_kernel(const bf16* __restrict__ x
             for (int p = 0; p < NP; ++p) {
                 const int c = lane * 8 + p * 512;
                 if (c < W) {
-                    float f[8];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) f[e] = fminf(fmaxf((float)ob[p][e] * inv, -448.0f), 448.0f);
-                    int p0 = 0, p1 = 0;
-                    p0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], p0, false);
-                    p0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], p0, true);
-                    p1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], p1, false);
-                    p1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], p1, true);
+                    const int p0 = pack4_e4m3((float)ob[p][0], (float)ob[p][1], (float)ob[p][2], (float)ob[p][3], inv);
+                    const int p1 = pack4_e4m3((float)ob[p][4], (float)ob[p][5], (float)ob[p][6], (float)ob[p][7], inv);
                     typedef __attribute__((ext_vector_type(2))) int i32x2_;
                     *(i32x2_*)(q8 + (size_t)r * ldq + c) = (i32x2_){p0, p1};
                 }
@@ -562,13 +550,8 @@ __global__ __launch_bounds__(256, (ln_bwd_per_cu<TDY, IT, R1, R2, TX, TR1>())) v
                     f32x4 o;
                     if (KEEP) o = ob[it];
                     else o = out_of(it);
-                    float f[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) f[e] = fminf(fmaxf((float)(bf16)o[e] * inv, -448.0f), 448.0f);
-                    int pk = 0;
-                    pk = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], pk, false);
-                    pk = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], pk, true);
-                    *(int*)(q8 + (size_t)cur.xr * ldq + c) = pk;
+                    *(int*)(q8 + (size_t)cur.xr * ldq + c) =
+                        pack4_e4m3((float)(bf16)o[0], (float)(bf16)o[1], (float)(bf16)o[2], (float)(bf16)o[3], inv);
                 }
             }
             if (lane == 0 && row_scale) row_scale[cur.xr] = scale;

@@ -6,10 +6,31 @@
 //                        One launch for all ~400 tensors: the flat buffers are cut into 1024-element chunks and a
 //                        byte table gives each chunk its parameter group (255 = frozen / padding).  The same pass
 //                        applies the data-parallel 1/world gradient scale and refreshes the bf16 weight shadow.
+//   tvts_adamw_torch     the same frame with torch.optim.AdamW arithmetic over up to 64 groups (the v1 fine-tuning step)
 //   tvts_cast_f32_bf16   shadow refresh when an external optimizer owned the update (drop-in path)
 //   tvts_transpose_bf16_batched   [N,K] -> [K,N] copies of every GEMM weight (dgrad operand), one launch
 //   tvts_pad_rows_bf16 / tvts_add_rows_f32   K-padding of the 14x14 patch-embedding weight and its wgrad (H/14)
 #include "common.h"
+
+// The frame of both AdamW kernels: one block per 1024-element chunk, four elements per lane.  `prologue(grp)` runs once the
+// chunk is known to step (its group byte is below NGROUPS; a foreign group, 255 = frozen, keeps every bit) and returns the rule
+// that updates four elements of p / m / v from their gradients; the frame loads, stores and writes the bf16 shadow.
+template <int NGROUPS, typename Prologue>
+__device__ __forceinline__ void adamw_chunk(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                            float* __restrict__ v, bf16* __restrict__ shadow,
+                                            const unsigned char* __restrict__ chunk_group, Prologue prologue) {
+    const int grp = chunk_group[blockIdx.x];
+    if (grp >= NGROUPS) return;
+    const auto update4 = prologue(grp);
+    const size_t i = (size_t)blockIdx.x * 1024 + threadIdx.x * 4;
+    f32x4 pv = *(f32x4*)(p + i), mv = *(f32x4*)(m + i), vv = *(f32x4*)(v + i);
+    const f32x4 gv = *(const f32x4*)(g + i);
+    update4(pv, mv, vv, gv);
+    *(f32x4*)(p + i) = pv;
+    *(f32x4*)(m + i) = mv;
+    *(f32x4*)(v + i) = vv;
+    if (shadow) *(bf16x4*)(shadow + i) = (bf16x4){(bf16)pv[0], (bf16)pv[1], (bf16)pv[2], (bf16)pv[3]};
+}
 
 struct AdamGroups { float lr[4]; float wd[4]; float step_size[4]; };
 
@@ -19,35 +40,30 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
                                                     float beta2, float omb1, float omb2, float eps, float grad_scale,
                                                     const int* __restrict__ step_dev, const float* __restrict__ hyper_dev,
                                                     double beta1d, double beta2d) {
-    const int grp = chunk_group[blockIdx.x];
-    if (grp > 3) return;
-    if (hyper_dev) {  // lr[4] | wd[4] in device memory: a captured launch follows the LR schedule without re-capture
-        hp.lr[grp] = hyper_dev[grp];
-        hp.wd[grp] = hyper_dev[4 + grp];
-    }
-    if (step_dev) {  // step counter lives in device memory (hipGraph replay): bias correction computed here
-        const double st = (double)step_dev[0];
-        // the betas in double, as the host path has them: both paths then produce the same step size bit for bit (with the
-        // float betas the step differed by 8e-6 relative, enough to flip a few dozen bf16 shadow roundings per step)
-        const double bc1 = 1.0 - pow(beta1d, st), bc2 = 1.0 - pow(beta2d, st);
-        hp.step_size[grp] = (float)((double)hp.lr[grp] * sqrt(bc2) / bc1);
-    }
-    const size_t i = (size_t)blockIdx.x * 1024 + threadIdx.x * 4;
-    f32x4 pv = *(f32x4*)(p + i), mv = *(f32x4*)(m + i), vv = *(f32x4*)(v + i);
-    const f32x4 gv = *(const f32x4*)(g + i);
-    const float lr = hp.lr[grp], wd = hp.wd[grp], ss = hp.step_size[grp];
+    adamw_chunk<4>(p, g, m, v, shadow, chunk_group, [&](int grp) {
+        if (hyper_dev) {  // lr[4] | wd[4] in device memory: a captured launch follows the LR schedule without re-capture
+            hp.lr[grp] = hyper_dev[grp];
+            hp.wd[grp] = hyper_dev[4 + grp];
+        }
+        if (step_dev) {  // step counter lives in device memory (hipGraph replay): bias correction computed here
+            const double st = (double)step_dev[0];
+            // the betas in double, as the host path has them: both paths then produce the same step size bit for bit (with the
+            // float betas the step differed by 8e-6 relative, enough to flip a few dozen bf16 shadow roundings per step)
+            const double bc1 = 1.0 - pow(beta1d, st), bc2 = 1.0 - pow(beta2d, st);
+            hp.step_size[grp] = (float)((double)hp.lr[grp] * sqrt(bc2) / bc1);
+        }
+        const float lr = hp.lr[grp], wd = hp.wd[grp], ss = hp.step_size[grp];
+        return [=](f32x4& pv, f32x4& mv, f32x4& vv, const f32x4& gv) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float gg = gv[e] * grad_scale;
-        mv[e] = beta1 * mv[e] + omb1 * gg;
-        vv[e] = beta2 * vv[e] + omb2 * gg * gg;
-        pv[e] -= ss * mv[e] / (sqrtf(vv[e]) + eps);
-        if (wd > 0.f) pv[e] -= lr * wd * pv[e];
-    }
-    *(f32x4*)(p + i) = pv;
-    *(f32x4*)(m + i) = mv;
-    *(f32x4*)(v + i) = vv;
-    if (shadow) *(bf16x4*)(shadow + i) = (bf16x4){(bf16)pv[0], (bf16)pv[1], (bf16)pv[2], (bf16)pv[3]};
+            for (int e = 0; e < 4; ++e) {
+                const float gg = gv[e] * grad_scale;
+                mv[e] = beta1 * mv[e] + omb1 * gg;
+                vv[e] = beta2 * vv[e] + omb2 * gg * gg;
+                pv[e] -= ss * mv[e] / (sqrtf(vv[e]) + eps);
+                if (wd > 0.f) pv[e] -= lr * wd * pv[e];
+            }
+        };
+    });
 }
 
 extern "C" int tvts_adamw_hf(float* p, const float* g, float* m, float* v, void* shadow_bf16,
@@ -66,6 +82,55 @@ extern "C" int tvts_adamw_hf(float* p, const float* g, float* m, float* v, void*
     }
     hipLaunchKernelGGL(adamw_kernel, dim3(nchunks), dim3(256), 0, stream, p, g, m, v, (bf16*)shadow_bf16, chunk_group, hp,
                        (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, grad_scale, step_dev, hyper_dev, beta1, beta2);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
+// ---- torch.optim.AdamW, multi-tensor (the v1 fine-tuning step)
+// The optimizer run_class_finetuning.py builds through optim_factory.create_optimizer (opt "adamw") over the layer-decay parameter
+// groups (28 of them on ViT-B).  Per element, in torch's order (torch/optim/adamw.py, single-tensor form):
+//     p  *= 1 - lr wd                                   (the factor formed in double, rounded once)
+//     m   = b1 m + (1 - b1) g
+//     v   = b2 v + (1 - b2) g g
+//     p  -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)  (lr / bc1 and sqrt(bc2) formed in double, rounded once each)
+// with bc1 = 1 - b1^t, bc2 = 1 - b2^t in double from the double betas; t = step_dev[0] when given, else the host's `step` -- the
+// same device code either way, so both give the same bits.  g = stored gradient * grad_scale * norm_coef[1] (the clip coefficient
+// tvts_grad_sumsq left in device memory; no coefficient when norm_coef is null).  hyper_dev: lr[64] | wd[64] in device memory.
+// Chunk table as tvts_adamw_hf (1024 elements per chunk, one group byte each); a chunk of group >= 64 (255 = frozen) keeps every bit.
+__global__ __launch_bounds__(256) void adamw_torch_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, bf16* __restrict__ shadow,
+                                                          const unsigned char* __restrict__ chunk_group,
+                                                          const float* __restrict__ hyper_dev, int step,
+                                                          const int* __restrict__ step_dev, double beta1d, double beta2d, float beta1,
+                                                          float beta2, float omb1, float omb2, float eps, float grad_scale,
+                                                          const float* __restrict__ norm_coef) {
+#pragma clang fp contract(off)  // (lexical: it holds inside both lambdas; adamw_kernel has none and keeps its contractions)
+    adamw_chunk<64>(p, g, m, v, shadow, chunk_group, [&](int grp) {
+        const float lr = hyper_dev[grp], wd = hyper_dev[64 + grp];
+        const double st = (double)(step_dev ? step_dev[0] : step);
+        const double bc1 = 1.0 - pow(beta1d, st), bc2 = 1.0 - pow(beta2d, st);
+        const float decay = (float)(1.0 - (double)lr * (double)wd);
+        const float ss = (float)((double)lr / bc1), rs = (float)sqrt(bc2);
+        const float gs = norm_coef ? grad_scale * norm_coef[1] : grad_scale;
+        return [=](f32x4& pv, f32x4& mv, f32x4& vv, const f32x4& gv) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float gg = gv[e] * gs;
+                pv[e] *= decay;
+                mv[e] = beta1 * mv[e] + omb1 * gg;
+                vv[e] = beta2 * vv[e] + omb2 * gg * gg;
+                pv[e] -= ss * mv[e] / (sqrtf(vv[e]) / rs + eps);
+            }
+        };
+    });
+}
+extern "C" int tvts_adamw_torch(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group,
+                                int nchunks, const float* hyper_dev, int step, const int* step_dev, double beta1, double beta2,
+                                double eps, float grad_scale, const float* norm_coef, hipStream_t stream) {
+    if (!p || !g || !m || !v || !chunk_group || !hyper_dev || nchunks <= 0 || (step <= 0 && !step_dev)) return TVTS_EINVAL;
+    hipLaunchKernelGGL(adamw_torch_kernel, dim3(nchunks), dim3(256), 0, stream, p, g, m, v, (bf16*)shadow_bf16, chunk_group,
+                       hyper_dev, step, step_dev, beta1, beta2, (float)beta1, (float)beta2, (float)(1.0 - beta1),
+                       (float)(1.0 - beta2), (float)eps, grad_scale, norm_coef);
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;
 }
@@ -200,12 +265,10 @@ __global__ __launch_bounds__(256) void amax_kernel(const T* __restrict__ x, long
 #pragma unroll
             for (int e = 0; e < N; ++e) m = fmaxf(m, fabsf((float)v[e]));
         }
-    m = wave_max(m);
     __shared__ float wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
+    m = block_max_256(m, wm);
     if (threadIdx.x == 0)  // one atomic per block (every wave hammering the single address serialises the whole kernel)
-        atomicMax((unsigned*)amax, __float_as_uint(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]))));  // non-negative floats order like their bits
+        atomicMax((unsigned*)amax, __float_as_uint(m));  // non-negative floats order like their bits
 }
 template <typename T>
 __global__ __launch_bounds__(256) void quant_fp8_kernel(const T* __restrict__ x, long ld, int rows, int cols,
@@ -222,15 +285,8 @@ __global__ __launch_bounds__(256) void quant_fp8_kernel(const T* __restrict__ x,
             const V v = *(const V*)(x + r * ld + c);
             int pk[N / 4];
 #pragma unroll
-            for (int h = 0; h < N / 4; ++h) {
-                float f[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) f[e] = fminf(fmaxf((float)v[h * 4 + e] * inv, -448.0f), 448.0f);
-                int p = 0;
-                p = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], p, false);
-                p = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], p, true);
-                pk[h] = p;
-            }
+            for (int h = 0; h < N / 4; ++h)
+                pk[h] = pack4_e4m3((float)v[h * 4], (float)v[h * 4 + 1], (float)v[h * 4 + 2], (float)v[h * 4 + 3], inv);
             if (N == 8) *(long*)(out + r * ldo + c) = ((long)(unsigned)pk[N / 4 - 1] << 32) | (unsigned)pk[0];
             else *(int*)(out + r * ldo + c) = pk[0];
         }
@@ -278,17 +334,9 @@ __global__ __launch_bounds__(256) void q8_multi_amax_kernel(const Q8Desc* __rest
         const f32x4 v = *(const f32x4*)(d.w + i * 4);
         m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
     }
-    m = wave_max(m);
     __shared__ float wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicMax((unsigned*)d.amax, __float_as_uint(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]))));
-}
-__device__ __forceinline__ int pack4_e4m3(float a, float b, float c, float e, float inv) {
-    int p = 0;
-    p = __builtin_amdgcn_cvt_pk_fp8_f32(fminf(fmaxf(a * inv, -448.0f), 448.0f), fminf(fmaxf(b * inv, -448.0f), 448.0f), p, false);
-    p = __builtin_amdgcn_cvt_pk_fp8_f32(fminf(fmaxf(c * inv, -448.0f), 448.0f), fminf(fmaxf(e * inv, -448.0f), 448.0f), p, true);
-    return p;
+    m = block_max_256(m, wm);
+    if (threadIdx.x == 0) atomicMax((unsigned*)d.amax, __float_as_uint(m));
 }
 __global__ __launch_bounds__(256) void q8_multi_quant_kernel(const Q8Desc* __restrict__ tab) {
     const Q8Desc d = tab[blockIdx.y];
@@ -355,18 +403,9 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16* __restr
         if (lane == 0 && row_scale) row_scale[r] = scale;
         unsigned char* orow = out + r * ldo;
         auto emit = [&](const bf16x8& u, int c) {
-            int pk[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                float f[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) f[e] = fminf(fmaxf((float)u[h * 4 + e] * inv, -448.0f), 448.0f);
-                int q = 0;
-                q = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], q, false);
-                q = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], q, true);
-                pk[h] = q;
-            }
-            *(long*)(orow + c) = ((long)(unsigned)pk[1] << 32) | (unsigned)pk[0];
+            const int lo = pack4_e4m3((float)u[0], (float)u[1], (float)u[2], (float)u[3], inv);
+            const int hi = pack4_e4m3((float)u[4], (float)u[5], (float)u[6], (float)u[7], inv);
+            *(long*)(orow + c) = ((long)(unsigned)hi << 32) | (unsigned)lo;
         };
         if (in_regs) {
 #pragma unroll

@@ -14,6 +14,7 @@ One step: EngineV1.finetune_forward (all patches, stochastic depth from a counte
 `head`), tvts_soft_ce (soft targets as a host-side Mixup produces them, or labels with smoothing), EngineV1.finetune_backward,
 and on every update_freq-th call tvts_grad_sumsq (global norm + clip coefficient, left on the device), tvts_adamw_torch and a
 fill-kernel zero of the gradients.  Nothing in the step synchronises with the host; the returned values are device tensors.
+The optimizer, FusedTorchAdamW, lives in tvts_amd/optim.py beside FusedHFAdamW (one shared base) and is re-exported here.
 
 OUT OF SCOPE (not built here): mixup / cutmix and the augmentation stack (the host data pipeline: pass their soft targets in),
 ``ModelEma``, the fp16 loss scaler (the engine is bf16 with fp32 accumulation: there is no loss scale), DeepSpeed, the multi-GPU
@@ -24,9 +25,9 @@ from __future__ import annotations
 import torch
 
 from .. import hip as K
-from ..engine import CH, ParamStore
+from ..optim import FusedTorchAdamW  # noqa: F401  (re-exported)
 
-MAX_GROUPS = 64
+MAX_GROUPS = FusedTorchAdamW.MAX_GROUPS
 
 
 # ---------------------------------------------------------------------------------------------- parameter groups
@@ -74,105 +75,6 @@ def param_groups(model, weight_decay, layer_decay=1.0, skip_list=None, trainable
         g["params"].append(p)
         g["param_names"].append(name)
     return list(groups.values())
-
-
-# ---------------------------------------------------------------------------------------------- optimizer
-class FusedTorchAdamW(torch.optim.Optimizer):
-    """``torch.optim.AdamW`` arithmetic (decay first, p *= 1 - lr wd; bias corrections bc1 = 1 - b1^t, bc2 = 1 - b2^t;
-    p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps)) as ONE launch over the flat store, for up to 64 parameter groups -- the 28
-    layer-decay groups of ViT-B.  ``state[p] = {step, exp_avg, exp_avg_sq}`` (views of the flat moments) keeps the torch
-    checkpoint layout.  lr / weight_decay of the groups travel as a device table (sync_hyper(), called by step()); betas / eps are
-    shared by all groups.  ``norm_coef`` (set by FinetuneStep): the device buffer whose second element scales every gradient --
-    the clip coefficient of tvts_grad_sumsq."""
-
-    def __init__(self, params, store: ParamStore, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, model=None):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        if len(self.param_groups) > MAX_GROUPS:
-            raise ValueError(f"the fused kernel supports up to {MAX_GROUPS} parameter groups")
-        self.store, self.model = store, model
-        dev = store.device
-        if store.m is None:
-            store.m = torch.zeros_like(store.flat)
-            store.v = torch.zeros_like(store.flat)
-        ptr2name = {store.p(n).data_ptr(): n for n in store.shapes}
-        table = torch.full((store.total // CH,), 255, dtype=torch.uint8)
-        for gi, group in enumerate(self.param_groups):
-            for p in group["params"]:
-                name = ptr2name.get(p.data_ptr())
-                if name is None:
-                    raise ValueError("FusedTorchAdamW only handles parameters of the flat store")
-                o, n = store.off[name], p.numel()
-                table[o // CH:(o + n + CH - 1) // CH] = gi
-                self.state[p] = dict(step=0, exp_avg=store.m[o:o + n].view(p.shape), exp_avg_sq=store.v[o:o + n].view(p.shape))
-        self.chunk_group = table.to(dev)
-        self.global_step = 0
-        self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.hyper_dev = torch.zeros(2 * MAX_GROUPS, dtype=torch.float32, device=dev)  # lr[64] | wd[64]
-        self._hyper_host = None
-        self.grad_scale = 1.0
-        self.norm_coef = None
-
-    def _hyper(self):
-        b1, b2 = self.param_groups[0]["betas"]
-        eps = self.param_groups[0]["eps"]
-        for g in self.param_groups[1:]:
-            if tuple(g["betas"]) != (b1, b2) or g["eps"] != eps:
-                raise ValueError("FusedTorchAdamW needs the same betas / eps in every parameter group (lr and weight_decay may differ)")
-        pad = [0.0] * (MAX_GROUPS - len(self.param_groups))
-        return b1, b2, eps, [float(g["lr"]) for g in self.param_groups] + pad, [float(g["weight_decay"]) for g in self.param_groups] + pad
-
-    def sync_hyper(self):
-        """upload lr / weight_decay of the groups to the device table (skipped when nothing changed)"""
-        *_, lr, wd = self._hyper()
-        if self._hyper_host != (lr, wd):
-            self.hyper_dev.copy_(torch.tensor(lr + wd, dtype=torch.float32))
-            self._hyper_host = (lr, wd)
-
-    def zero_grad(self, set_to_none: bool = False):
-        K.zero_(self.store.grad)
-
-    def state_dict(self):
-        st = int(self.step_dev.item())
-        self.global_step = max(self.global_step, st)
-        for s in self.state.values():
-            s["step"] = self.global_step
-        return super().state_dict()
-
-    @torch.no_grad()
-    def step(self, closure=None, device_step: bool = False):
-        """device_step=True: the step counter the kernel reads lives in device memory (same bits as the host counter)"""
-        b1, b2, eps, _, _ = self._hyper()
-        self.sync_hyper()
-        self.global_step += 1
-        if device_step:
-            self.step_dev.add_(1)
-        else:
-            self.step_dev.fill_(self.global_step)
-        st = self.store
-        K.adamw_torch(st.flat, st.grad, st.m, st.v, st.shadow, self.chunk_group, self.hyper_dev, self.global_step, b1, b2, eps,
-                      self.grad_scale, step_dev=self.step_dev if device_step else None, norm_coef=self.norm_coef)
-        st.refresh_shadows(cast=False)
-        if self.model is not None:
-            self.model.mark_shadows_fresh()
-        if not device_step:
-            for s in self.state.values():
-                s["step"] = self.global_step
-
-    def load_state_dict(self, state_dict):
-        """accepts the torch layout: state keyed by the running parameter index"""
-        for g, sg in zip(self.param_groups, state_dict["param_groups"]):
-            for k, v in sg.items():
-                if k != "params":
-                    g[k] = v
-            for p, idx in zip(g["params"], sg["params"]):
-                s = state_dict["state"].get(idx)
-                if s is None:
-                    continue
-                self.state[p]["exp_avg"].copy_(s["exp_avg"])
-                self.state[p]["exp_avg_sq"].copy_(s["exp_avg_sq"])
-                self.state[p]["step"] = int(s["step"])
-                self.global_step = max(self.global_step, int(s["step"]))
-        self.step_dev.fill_(self.global_step)
 
 
 # ---------------------------------------------------------------------------------------------- the step

@@ -1061,21 +1061,38 @@ def v2v_ranks(sims, q0, labels, ranks=None, N=None):
     return ranks
 
 
+def _adamw_bytes(chunk_group, ngroups):
+    """30 B per element of every chunk that steps (group byte < ngroups): p, m, v read + written (24), g read (4), bf16 shadow
+    written (2)"""
+    assert chunk_group.dtype == torch.uint8
+    return lambda: 30.0 * 1024 * float((chunk_group < ngroups).sum())
+
+
 def adamw_hf(p, g, m, v, shadow, chunk_group, lr4, wd4, step, beta1=0.9, beta2=0.999, eps=1e-6, grad_scale=1.0,
              step_dev=None, hyper_dev=None):
     lib = _lib.load()
     lr = (ctypes.c_float * 4)(*lr4)
     wd = (ctypes.c_float * 4)(*wd4)
-    # 30 B per element of every chunk that steps: p, m, v read + written (24), g read (4), bf16 shadow written (2)
-    with _hbm("adamw", lambda: 30.0 * 1024 * float((chunk_group >= 0).sum()) if chunk_group.dtype != torch.uint8
-              else 30.0 * 1024 * float((chunk_group < 255).sum())):
+    with _hbm("adamw", _adamw_bytes(chunk_group, 255)):
         rc = (lib.tvts_adamw_hf(_p(p), _p(g), _p(m), _p(v), _p(shadow), _p(chunk_group), chunk_group.numel(),
                            ctypes.cast(lr, ctypes.c_void_p), ctypes.cast(wd, ctypes.c_void_p), step, _p(step_dev), _p(hyper_dev), beta1, beta2, eps,
                            grad_scale, _stream()))
     _chk(rc, "tvts_adamw_hf")
 
 
-# ---- v1 fine-tuning step (finetune.hip)
+def adamw_torch(p, g, m, v, shadow, chunk_group, hyper_dev, step, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, step_dev=None,
+                norm_coef=None):
+    """one torch.optim.AdamW step over the flat buffers; hyper_dev: device fp32 lr[64] | wd[64]"""
+    n = chunk_group.numel()
+    assert hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= 128
+    assert all(t.numel() >= n * 1024 for t in (p, g, m, v)) and (shadow is None or shadow.numel() >= n * 1024)
+    with _hbm("adamw", _adamw_bytes(chunk_group, 64)):
+        rc = _lib.load().tvts_adamw_torch(_p(p), _p(g), _p(m), _p(v), _p(shadow), _p(chunk_group), n, _p(hyper_dev), int(step),
+                                          _p(step_dev), beta1, beta2, eps, grad_scale, _p(norm_coef), _stream())
+    _chk(rc, "tvts_adamw_torch")
+
+
+# ---- v1 fine-tuning step (finetune.hip; its optimizer launch, adamw_torch, is above beside adamw_hf)
 def drop_path_table(seed, p_sites, scale, *, site_base=0):
     """scale [nsites, B] fp32 = the stochastic-depth draw of one step: 1 / (1 - p) for a kept sample, 0 for a dropped one, exactly
     1.0 where p_sites[s] == 0.  seed: int64 device scalar; p_sites: fp32 device [nsites]."""
@@ -1121,18 +1138,6 @@ def grad_sumsq(g, chunk_group, partial, norm_coef, *, max_norm=0.0, grad_scale=1
     assert partial.dtype == torch.float32 and partial.numel() >= n and norm_coef.dtype == torch.float32 and norm_coef.numel() >= 2
     _chk(_lib.load().tvts_grad_sumsq(_p(g), _p(chunk_group), n, _p(partial), float(max_norm or 0.0), float(grad_scale), _p(norm_coef),
                                      _stream()), "tvts_grad_sumsq")
-
-
-def adamw_torch(p, g, m, v, shadow, chunk_group, hyper_dev, step, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, step_dev=None,
-                norm_coef=None):
-    """one torch.optim.AdamW step over the flat buffers; hyper_dev: device fp32 lr[64] | wd[64]"""
-    n = chunk_group.numel()
-    assert hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= 128 and chunk_group.dtype == torch.uint8
-    assert all(t.numel() >= n * 1024 for t in (p, g, m, v)) and (shadow is None or shadow.numel() >= n * 1024)
-    with _hbm("adamw", lambda: 30.0 * 1024 * float((chunk_group < 64).sum())):
-        rc = _lib.load().tvts_adamw_torch(_p(p), _p(g), _p(m), _p(v), _p(shadow), _p(chunk_group), n, _p(hyper_dev), int(step),
-                                          _p(step_dev), beta1, beta2, eps, grad_scale, _p(norm_coef), _stream())
-    _chk(rc, "tvts_adamw_torch")
 
 
 def cast_f32_bf16(src, dst):

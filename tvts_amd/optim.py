@@ -1,9 +1,12 @@
-"""Fused multi-tensor AdamW with Hugging Face semantics over the flat parameter store.
+"""Fused multi-tensor AdamW over the flat parameter store: ``step()`` is ONE kernel launch over the flat buffers.
 
-Replaces ``transformers.AdamW(params=optimizer_grouped_parameters)`` built at
+``_FlatAdamW`` holds what the two optimizers share (chunk table, moments, state views, device table, step counters, checkpoints).
+
+``FusedHFAdamW`` replaces ``transformers.AdamW(params=optimizer_grouped_parameters)`` built at
 v2/train_dist_TVTSv2_ViT_B_16.py:118-125 (defaults betas (0.9, 0.999), eps 1e-6, correct_bias=True).
-It is a ``torch.optim.Optimizer`` so param_groups / state_dict keep the reference checkpoint layout
-(``state[p] = {step, exp_avg, exp_avg_sq}``), but ``step()`` is ONE kernel launch over the flat buffers.
+``FusedTorchAdamW`` is ``torch.optim.AdamW`` (eps 1e-8) for the v1 fine-tuning step (downstream/finetune_v1.py).
+Both are ``torch.optim.Optimizer``s, so param_groups / state_dict keep the reference checkpoint layout
+(``state[p] = {step, exp_avg, exp_avg_sq}``, views of the flat moments).
 
 Gradient handling follows the reference's pinned torch 1.11 ``zero_grad()`` (grads zeroed, not set to
 None): every trainable tensor is updated every step, tensors that received no gradient see g = 0.
@@ -16,15 +19,17 @@ from . import hip as K
 from .engine import CH, ParamStore
 
 
-class FusedHFAdamW(torch.optim.Optimizer):
-    def __init__(self, params, store: ParamStore, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0,
-                 correct_bias=True, model=None):
-        if not correct_bias:
-            raise NotImplementedError("correct_bias=False is not built")
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias)
+class _FlatAdamW(torch.optim.Optimizer):
+    """What the fused optimizers share: the moments on the ParamStore, the 1024-element chunk table (group per chunk, 255 = frozen),
+    the ``state[p]`` views, the lr / weight_decay device table and the host / device step counters.  A subclass sets MAX_GROUPS
+    (the width of its kernel's table) and launches its kernel in step()."""
+    MAX_GROUPS = 0
+
+    def __init__(self, params, defaults, store: ParamStore, model=None):
         super().__init__(params, defaults)
-        if len(self.param_groups) > 4:
-            raise ValueError("the fused kernel supports up to 4 parameter groups (the reference uses 4)")
+        self._cls = type(self).__name__
+        if len(self.param_groups) > self.MAX_GROUPS:
+            raise ValueError(f"the fused kernel supports up to {self.MAX_GROUPS} parameter groups")
         self.store, self.model = store, model
         dev = store.device
         if store.m is None:
@@ -32,47 +37,39 @@ class FusedHFAdamW(torch.optim.Optimizer):
             store.v = torch.zeros_like(store.flat)
         ptr2name = {store.p(n).data_ptr(): n for n in store.shapes}
         table = torch.full((store.total // CH,), 255, dtype=torch.uint8)
-        self._names = []
         for gi, group in enumerate(self.param_groups):
-            names = []
             for p in group["params"]:
                 name = ptr2name.get(p.data_ptr())
                 if name is None:
-                    raise ValueError("FusedHFAdamW only handles parameters of the flat store")
-                names.append(name)
+                    raise ValueError(f"{self._cls} only handles parameters of the flat store")
                 o, n = store.off[name], p.numel()
                 table[o // CH:(o + n + CH - 1) // CH] = gi
-                o2 = store.off[name]
-                self.state[p] = dict(step=0, exp_avg=store.m[o2:o2 + n].view(p.shape), exp_avg_sq=store.v[o2:o2 + n].view(p.shape))
-            self._names.append(names)
+                self.state[p] = dict(step=0, exp_avg=store.m[o:o + n].view(p.shape), exp_avg_sq=store.v[o:o + n].view(p.shape))
         self.chunk_group = table.to(dev)
         self.global_step = 0
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.hyper_dev = torch.zeros(8, dtype=torch.float32, device=dev)  # lr[4] | wd[4] for captured launches
+        self.hyper_dev = torch.zeros(2 * self.MAX_GROUPS, dtype=torch.float32, device=dev)  # lr[MAX_GROUPS] | wd[MAX_GROUPS]
         self._hyper_host = None
         self.grad_scale = 1.0
-        self._ranged = None      # (hyper-parameters, device_step, [chunk ranges done]) between begin_ranges() and step()
-        self._opt_stream = None
 
     def _hyper(self):
         b1, b2 = self.param_groups[0]["betas"]
         eps = self.param_groups[0]["eps"]
         for g in self.param_groups[1:]:  # one kernel launch covers every group: these three cannot differ per group
             if tuple(g["betas"]) != (b1, b2) or g["eps"] != eps:
-                raise ValueError("FusedHFAdamW needs the same betas / eps in every parameter group (lr and weight_decay may differ)")
-        n = len(self.param_groups)
-        lr4 = [float(g["lr"]) for g in self.param_groups] + [0.0] * (4 - n)
-        wd4 = [float(g["weight_decay"]) for g in self.param_groups] + [0.0] * (4 - n)
-        return b1, b2, eps, lr4, wd4
+                raise ValueError(f"{self._cls} needs the same betas / eps in every parameter group (lr and weight_decay may differ)")
+        pad = [0.0] * (self.MAX_GROUPS - len(self.param_groups))
+        return (b1, b2, eps, [float(g["lr"]) for g in self.param_groups] + pad,
+                [float(g["weight_decay"]) for g in self.param_groups] + pad)
 
     def sync_hyper(self):
-        """Upload lr / weight_decay of the parameter groups to the device table read by captured (device_step) launches.
-        step() calls it; when a captured hipGraph is REPLAYED, call it after changing param_groups (an LR schedule) -- the
-        replay then uses the new values without re-capture.  The copy is skipped when nothing changed."""
-        *_, lr4, wd4 = self._hyper()
-        if self._hyper_host != (lr4, wd4):
-            self.hyper_dev.copy_(torch.tensor(lr4 + wd4, dtype=torch.float32), non_blocking=False)
-            self._hyper_host = (lr4, wd4)
+        """Upload lr / weight_decay of the parameter groups to the device table.  When a captured hipGraph is REPLAYED, call it
+        after changing param_groups (an LR schedule) -- the replay then uses the new values without re-capture.  The copy is
+        skipped when nothing changed."""
+        *_, lr, wd = self._hyper()
+        if self._hyper_host != (lr, wd):
+            self.hyper_dev.copy_(torch.tensor(lr + wd, dtype=torch.float32), non_blocking=False)
+            self._hyper_host = (lr, wd)
 
     def _sync_step_from_device(self):
         """Under hipGraph replay the host counters only advance at capture time: re-read the device counter."""
@@ -91,18 +88,58 @@ class FusedHFAdamW(torch.optim.Optimizer):
 
     def _begin(self, device_step: bool):
         """counters of a new optimizer step (once per step, in front of its first launch)"""
-        b1, b2, eps, lr4, wd4 = self._hyper()
+        b1, b2, eps, lr, wd = self._hyper()
         capturing = torch.cuda.is_current_stream_capturing()
         if device_step and not capturing:
             self.sync_hyper()  # (a host -> device copy: not capturable; the caller syncs before capture / replay)
-        elif device_step and self._hyper_host != (lr4, wd4):
-            raise RuntimeError("FusedHFAdamW: call sync_hyper() (or run one eager device_step) before capturing the step")
+        elif device_step and self._hyper_host != (lr, wd):
+            raise RuntimeError(f"{self._cls}: call sync_hyper() (or run one eager device_step) before capturing the step")
         self.global_step += 1
         if device_step:
             self.step_dev.add_(1)
         else:
             self.step_dev.fill_(self.global_step)  # keeps the device counter in step when eager and captured steps mix
-        return b1, b2, eps, lr4, wd4
+        return b1, b2, eps, lr, wd
+
+    def _finish(self, device_step: bool, transposed: bool = True):
+        """behind the step's last launch: the shadows the kernel does not write, and the per-parameter step fields"""
+        self.store.refresh_shadows(cast=False, transposed=transposed)
+        if self.model is not None:
+            self.model.mark_shadows_fresh()
+        if not device_step:
+            for st in self.state.values():
+                st["step"] = self.global_step
+
+    def load_state_dict(self, state_dict):
+        """Accepts the HF-AdamW / torch layout: state keyed by the running parameter index."""
+        sd_groups, sd_state = state_dict["param_groups"], state_dict["state"]
+        for g, sg in zip(self.param_groups, sd_groups):
+            for k, v in sg.items():
+                if k != "params":
+                    g[k] = v
+            for p, idx in zip(g["params"], sg["params"]):
+                st = sd_state.get(idx)
+                if st is None:
+                    continue
+                self.state[p]["exp_avg"].copy_(st["exp_avg"])
+                self.state[p]["exp_avg_sq"].copy_(st["exp_avg_sq"])
+                self.state[p]["step"] = int(st["step"])
+                self.global_step = max(self.global_step, int(st["step"]))
+        self.step_dev.fill_(self.global_step)
+
+
+class FusedHFAdamW(_FlatAdamW):
+    """``transformers.AdamW`` arithmetic for up to 4 parameter groups (the reference uses 4).  The device table is lr[4] | wd[4];
+    the kernel reads it only together with the device step counter (captured launches)."""
+    MAX_GROUPS = 4
+
+    def __init__(self, params, store: ParamStore, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0,
+                 correct_bias=True, model=None):
+        if not correct_bias:
+            raise NotImplementedError("correct_bias=False is not built")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias), store, model)
+        self._ranged = None      # (hyper-parameters, device_step, [chunk ranges done]) between begin_ranges() and step()
+        self._opt_stream = None
 
     def _launch(self, lo: int, hi: int, hp, device_step: bool):
         """the update of the chunks [lo, hi) of the flat buffers + the transposed shadows of the weights inside them"""
@@ -124,7 +161,7 @@ class FusedHFAdamW(torch.optim.Optimizer):
             K.adamw_hf(self.store.flat, self.store.grad, self.store.m, self.store.v, self.store.shadow, self.chunk_group,
                        hp[3], hp[4], self.global_step, hp[0], hp[1], hp[2], self.grad_scale, step_dev=self.step_dev if device_step else None,
                        hyper_dev=self.hyper_dev if device_step else None)
-            self.store.refresh_shadows(cast=False)
+            self._finish(device_step)
         else:
             hp, dstep, done = self._ranged
             self._ranged = None
@@ -136,12 +173,7 @@ class FusedHFAdamW(torch.optim.Optimizer):
                 if lo > pos:
                     self._launch(pos, lo, hp, dstep)
                 pos = max(pos, hi)
-            self.store.refresh_shadows(cast=False, transposed=False)  # what is not per-range: K-padded conv weight, e4m3 copies
-        if self.model is not None:
-            self.model.mark_shadows_fresh()
-        if not device_step:
-            for st in self.state.values():
-                st["step"] = self.global_step
+            self._finish(device_step, transposed=False)  # what is not per-range: K-padded conv weight, e4m3 copies
 
     # ---- the update range by range, beside the backward (round 5).  The hand-written backward reports every parameter range whose
     # gradient is final (Engine._ready -> param_ready); its update -- HBM-bound, 30 B per parameter -- then runs on a stream of its
@@ -166,19 +198,25 @@ class FusedHFAdamW(torch.optim.Optimizer):
             self._launch(lo, hi, hp, dstep)
         done.append((lo, hi))
 
-    def load_state_dict(self, state_dict):
-        """Accepts the HF-AdamW / torch layout: state keyed by the running parameter index."""
-        sd_groups, sd_state = state_dict["param_groups"], state_dict["state"]
-        for g, sg in zip(self.param_groups, sd_groups):
-            for k, v in sg.items():
-                if k != "params":
-                    g[k] = v
-            for p, idx in zip(g["params"], sg["params"]):
-                st = sd_state.get(idx)
-                if st is None:
-                    continue
-                self.state[p]["exp_avg"].copy_(st["exp_avg"])
-                self.state[p]["exp_avg_sq"].copy_(st["exp_avg_sq"])
-                self.state[p]["step"] = int(st["step"])
-                self.global_step = max(self.global_step, int(st["step"]))
-        self.step_dev.fill_(self.global_step)
+
+class FusedTorchAdamW(_FlatAdamW):
+    """``torch.optim.AdamW`` arithmetic (decay first, p *= 1 - lr wd; bias corrections bc1 = 1 - b1^t, bc2 = 1 - b2^t;
+    p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps)) as ONE launch over the flat store, for up to 64 parameter groups -- the 28
+    layer-decay groups of ViT-B (v1 fine-tuning, downstream/finetune_v1.py).  lr / weight_decay of the groups travel as the device
+    table lr[64] | wd[64], which the kernel always reads: step() uploads it on every call.  ``norm_coef`` (set by FinetuneStep):
+    the device buffer whose second element scales every gradient -- the clip coefficient of tvts_grad_sumsq."""
+    MAX_GROUPS = 64
+
+    def __init__(self, params, store: ParamStore, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, model=None):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), store, model)
+        self.norm_coef = None
+
+    @torch.no_grad()
+    def step(self, closure=None, device_step: bool = False):
+        """device_step=True: the step counter the kernel reads lives in device memory (same bits as the host counter)"""
+        self.sync_hyper()
+        b1, b2, eps, _, _ = self._begin(device_step)
+        st = self.store
+        K.adamw_torch(st.flat, st.grad, st.m, st.v, st.shadow, self.chunk_group, self.hyper_dev, self.global_step, b1, b2, eps,
+                      self.grad_scale, step_dev=self.step_dev if device_step else None, norm_coef=self.norm_coef)
+        self._finish(device_step)
