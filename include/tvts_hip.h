@@ -444,6 +444,28 @@ int tvts_patch_gather_tube_cm(const float* video, const int* keep, int B, int tu
 int tvts_patch_gather_tube_u8(const unsigned char* frames, int H0, int W0, const int* crop, const int* keep, int B, int tubes,
                               int tubelet, int n, int img, int patch, const float* mean3, const float* std3, void* out, int ldo,
                               hipStream_t stream);
+/* Mixup / CutMix of the v1 fine-tuning recipe (v1/downstream/mixup.py:152-200 `_mix_elem` / `_mix_pair` / `_mix_batch`, applied as
+ * `samples, targets = mixup_fn(samples, targets)` at v1/downstream/engine_for_finetuning.py:58-59) fused into the channel-major
+ * gather: tvts_patch_gather_tube_cm with the mix applied per element in front of the bf16 rounding.  The step's draw is a
+ * per-sample table in DEVICE memory: mix_i int32 [B, 6] = (partner, mode, yl, yh, xl, xh), mode 0 none / 1 mixup / 2 cutmix / 3
+ * pair-mode cutmix (below), the box half-open in image coordinates behind the crop; mix_f fp32 [B, 2] = (lam, one_minus_lam), both rounded by the host.
+ * mode 0: the own value, bits untouched; mode 1: fadd_rn(fmul_rn(own, lam), fmul_rn(partner, one_minus_lam)) (two rounded
+ * products, then the sum: mixup.py:198-199, never an FMA); mode 2: the partner's value inside the box of every channel and frame
+ * (mixup.py:163,196), the own value outside; mode 3: what `_mix_pair` does to a 5-D clip batch -- `x[i][:, yl:yh, xl:xh]`
+ * (mixup.py:180-181) slices a [C, T, H, W] clip by (frame, row): the partner's value in the frames [yl, yh) (cut at T) and the rows
+ * [xl, xh) of every channel, whole rows; the own value elsewhere.  One table serves the reference's batch / pair / elem modes.  video and out 16-byte
+ * aligned, otherwise the conditions of tvts_patch_gather_tube_cm.  The table is DEVICE data and is not checked here (like crop): the
+ * caller keeps 0 <= partner < B, mode in {0, 1, 2, 3} and 0 <= lo <= hi <= img; a partner outside [0, B) leaves that sample's rows
+ * unwritten. */
+int tvts_patch_gather_tube_cm_mix(const float* video, const int* keep, const int* mix_i, const float* mix_f, int B, int tubes,
+                                  int tubelet, int n, int img, int patch, void* out, int ldo, hipStream_t stream);
+/* the same mix (v1/downstream/mixup.py:152-200) for uint8 frames: each of the two samples is cropped with ITS OWN crop offset and
+ * normalised as tvts_patch_gather_tube_u8 does, the normalised fp32 values are mixed as above and rounded to bf16 -- the bytes
+ * equal tvts_patch_gather_tube_cm_mix's on host-cropped, host-normalised frames.  out 16-byte aligned; crop and the table are
+ * DEVICE data and are not checked. */
+int tvts_patch_gather_tube_u8_mix(const unsigned char* frames, int H0, int W0, const int* crop, const int* keep, const int* mix_i,
+                                  const float* mix_f, int B, int tubes, int tubelet, int n, int img, int patch, const float* mean3,
+                                  const float* std3, void* out, int ldo, hipStream_t stream);
 int tvts_text_embed(const int* ids, int ld_ids, int N, int L, const float* emb, const float* pos, int Wt, float* x, int ldx,
                     hipStream_t stream);
 /* ---- PACKED variable-length captions (the forward-only text encoder of the SSv2 multiple-choice models,
@@ -545,6 +567,14 @@ int tvts_drop_path_rows(const float* y, long ldy, long rows, int cols, int S, co
  * sum_c t - t); hits (optional) = #{b : argmax x == argmax t} (engine_for_finetuning.py:104).  ws: fp32 [2 B] scratch. */
 int tvts_soft_ce(const float* logits, long ld, int B, int C, const float* soft_targets, long ldt, const int* labels,
                  float smoothing, float scale, float* loss_acc, float* dlogits, long ldd, int* hits, float* ws, hipStream_t stream);
+/* mixup_target (v1/downstream/mixup.py:18-23) over the mix table of tvts_patch_gather_tube_cm_mix: out fp32 [B, C] (ldo >= C, a
+ * wider leading dimension is left untouched), t[b, c] = fadd_rn(fmul_rn(y1, lam), fmul_rn(y2, one_minus_lam)) with y1 / y2 the on /
+ * off value for labels[b] / labels[partner[b]]; off = smoothing / C and on = 1 - smoothing + off are computed in double and rounded to
+ * fp32 as torch.full does.  Mode-0 rows take lam = 1, one_minus_lam = 0 and still run the arithmetic (the reference computes
+ * y1 * 1. + y2 * 0.).  labels int32 [B] and the table are DEVICE data and are not checked; a partner outside [0, B) leaves its row
+ * unwritten.  The result feeds tvts_soft_ce(soft_targets = ...). */
+int tvts_mix_targets(const int* labels, const int* mix_i, const float* mix_f, int B, int C, double smoothing, float* out, long ldo,
+                     hipStream_t stream);
 /* torch.nn.utils.clip_grad_norm_ as v1/downstream/utils.py:366 calls it, without the host round trip: two-stage fixed-order sum of
  * squares over the 1024-element chunks of g whose chunk_group != 255 (partial: fp32 [nchunks] scratch), norm_coef[0] = norm =
  * |grad_scale| sqrt(sum), norm_coef[1] = coef = min(1, max_norm / (norm + 1e-6)), 1 when max_norm <= 0 (clipping off). */

@@ -172,6 +172,134 @@ extern "C" int tvts_patch_gather_tube_u8(const unsigned char* frames, int H0, in
     return TVTS_OK;
 }
 
+// Mixup / CutMix of the v1 fine-tuning recipe (v1/downstream/mixup.py:152-200, applied at engine_for_finetuning.py:58-59) fused
+// into the two gathers the fine-tuning step uses.  The step's draw arrives as a per-sample table in device memory:
+//     mix_i int32 [B, 6] = (partner, mode, yl, yh, xl, xh)     mode 0 none, 1 mixup, 2 cutmix; the box in image coordinates
+//                                                              behind the crop, half-open
+//     mix_f fp32  [B, 2] = (lam, one_minus_lam)                both rounded by the host
+// mode 0: the sample's own value, its bits untouched (mixup.py:159,176,191 skip lam == 1: no x * 1 + y * 0).
+// mode 1: fadd_rn(fmul_rn(v_self, lam), fmul_rn(v_partner, one_minus_lam)) -- two fp32 products, then the fp32 sum, as
+//         `x.mul_(lam).add_(x.flip(0).mul_(1. - lam))` (:198-199); never an FMA.
+// mode 2: the partner's value inside [yl, yh) x [xl, xh) of every channel and frame (:163,196), the own value outside.
+// mode 3: cutmix as the reference's PAIR mode runs it on 5-D clips: `x[i][:, yl:yh, xl:xh]` (:180-181) is written for [C, H, W]
+//         pictures, and on a clip [C, T, H, W] its two slices land on (frame, row): the partner's value in the frames [yl, yh) (cut
+//         at T, as a slice is) and the rows [xl, xh) of every channel, over the whole row width; the own value elsewhere.
+// The select is per element (a thread's 8-pixel group may be cut by xl / xh anywhere); the partner is loaded only by the threads
+// that hold an element needing it.  A partner outside [0, B) leaves the sample's rows unwritten (nothing is read for it).
+struct MixRow { int partner, mode, yl, yh, xl, xh; float lam, oml; };
+__device__ __forceinline__ MixRow mix_row(const int* __restrict__ mix_i, const float* __restrict__ mix_f, int b) {
+    const int* mi = mix_i + 6 * (size_t)b;
+    return MixRow{mi[0], mi[1], mi[2], mi[3], mi[4], mi[5], mix_f[2 * (size_t)b], mix_f[2 * (size_t)b + 1]};
+}
+// does the 8-pixel group at frame f, (y, x .. x + 7) need the partner's values?
+__device__ __forceinline__ bool mix_needs_partner(const MixRow& m, int f, int y, int x) {
+    return m.mode == 1 || (m.mode == 2 && y >= m.yl && y < m.yh && x < m.xh && x + 8 > m.xl) ||
+           (m.mode == 3 && f >= m.yl && f < m.yh && y >= m.xl && y < m.xh);
+}
+__device__ __forceinline__ void mix_apply8(const MixRow& m, int x, float* v, const float* w) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        if (m.mode == 1) v[e] = __fadd_rn(__fmul_rn(v[e], m.lam), __fmul_rn(w[e], m.oml));
+        else if (m.mode == 3 || (x + e >= m.xl && x + e < m.xh)) v[e] = w[e];
+    }
+}
+__global__ __launch_bounds__(256) void patch_gather_tube_cm_mix_kernel(const float* __restrict__ video, const int* __restrict__ keep,
+                                                                       const int* __restrict__ mix_i, const float* __restrict__ mix_f,
+                                                                       int B, int tubes, int tb, int n, int img, int p,
+                                                                       bf16* __restrict__ out, int ldo) {
+    const int pp = p * p, K = 3 * tb * pp;
+    const int row = blockIdx.x;  // (b, tube, i)
+    const int i = row % n, tu = (row / n) % tubes, b = row / (n * tubes);
+    const int g = img / p;
+    const int pi = keep[(size_t)(b * tubes + tu) * n + i];
+    const int gy = pi / g, gx = pi % g;
+    const int T = tubes * tb;
+    const MixRow m = mix_row(mix_i, mix_f, b);
+    if ((unsigned)m.partner >= (unsigned)B) return;
+    const size_t clip = (size_t)3 * T * img * img;
+    for (int c8 = threadIdx.x * 8; c8 < K; c8 += 256 * 8) {
+        const int ch = c8 / (tb * pp), r1 = c8 % (tb * pp), t = r1 / pp, rem = r1 % pp, py = rem / p, px = rem % p;  // px % 8 == 0
+        const int y = gy * p + py, x = gx * p + px, f = tu * tb + t;
+        const size_t in = (((size_t)ch * T + f) * img + y) * img + x;  // inside one clip
+        const float* src = video + (size_t)b * clip + in;
+        const f32x4 a = *(const f32x4*)src, c = *(const f32x4*)(src + 4);
+        float v[8] = {a[0], a[1], a[2], a[3], c[0], c[1], c[2], c[3]};
+        if (mix_needs_partner(m, f, y, x)) {
+            const float* ps = video + (size_t)m.partner * clip + in;
+            const f32x4 pa = *(const f32x4*)ps, pc = *(const f32x4*)(ps + 4);
+            const float w[8] = {pa[0], pa[1], pa[2], pa[3], pc[0], pc[1], pc[2], pc[3]};
+            mix_apply8(m, x, v, w);
+        }
+        bf16x8 o = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3], (bf16)v[4], (bf16)v[5], (bf16)v[6], (bf16)v[7]};
+        *(bf16x8*)(out + (size_t)row * ldo + c8) = o;
+    }
+}
+extern "C" int tvts_patch_gather_tube_cm_mix(const float* video, const int* keep, const int* mix_i, const float* mix_f, int B,
+                                             int tubes, int tubelet, int n, int img, int patch, void* out, int ldo,
+                                             hipStream_t stream) {
+    if (!video || !keep || !mix_i || !mix_f || !out || B <= 0 || tubes <= 0 || tubelet <= 0 || n <= 0 || patch <= 0 || img <= 0 ||
+        img % patch || patch % 8 || ldo % 8 || ldo < 3 * tubelet * patch * patch || ((size_t)video % 16) || ((size_t)out % 16))
+        return TVTS_EINVAL;
+    hipLaunchKernelGGL(patch_gather_tube_cm_mix_kernel, dim3(B * tubes * n), dim3(256), 0, stream, video, keep, mix_i, mix_f, B, tubes,
+                       tubelet, n, img, patch, (bf16*)out, ldo);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+// uint8 frames: each of the two samples is cropped with ITS OWN offset and normalised by the expression of
+// patch_gather_tube_u8_kernel, then mixed as above and rounded to bf16: the bytes equal the fp32 kernel's on host-cropped,
+// host-normalised frames.
+__global__ __launch_bounds__(256) void patch_gather_tube_u8_mix_kernel(const unsigned char* __restrict__ frames, int H0, int W0,
+                                                                       const int* __restrict__ crop, const int* __restrict__ keep,
+                                                                       const int* __restrict__ mix_i, const float* __restrict__ mix_f,
+                                                                       int B, int tubes, int tb, int n, int img, int p, float m0,
+                                                                       float m1, float m2, float s0, float s1, float s2,
+                                                                       bf16* __restrict__ out, int ldo) {
+    const int pp = p * p, K = 3 * tb * pp;
+    const int row = blockIdx.x;  // (b, tube, i)
+    const int i = row % n, tu = (row / n) % tubes, b = row / (n * tubes);
+    const int g = img / p;
+    const int pi = keep[(size_t)(b * tubes + tu) * n + i];
+    const int gy = pi / g, gx = pi % g;
+    const int T = tubes * tb;
+    const MixRow m = mix_row(mix_i, mix_f, b);
+    if ((unsigned)m.partner >= (unsigned)B) return;
+    const int dy = H0 - img, dx = W0 - img;
+    const int yc = (dy >> 1) + ((dy & 1) & (dy >> 1)), xc = (dx >> 1) + ((dx & 1) & (dx >> 1));
+    const int y0 = crop ? crop[2 * b] : yc, x0 = crop ? crop[2 * b + 1] : xc;
+    const int py0 = crop ? crop[2 * m.partner] : yc, px0 = crop ? crop[2 * m.partner + 1] : xc;
+    for (int c8 = threadIdx.x * 8; c8 < K; c8 += 256 * 8) {
+        const int ch = c8 / (tb * pp), r1 = c8 % (tb * pp), t = r1 / pp, rem = r1 % pp, py = rem / p, px = rem % p;  // px % 8 == 0
+        const int y = gy * p + py, x = gx * p + px, f = tu * tb + t;
+        const unsigned char* src = frames + (((size_t)(b * T + f) * H0 + y0 + y) * W0 + x0 + x) * 3 + ch;
+        const float mean = ch == 0 ? m0 : ch == 1 ? m1 : m2, sd = ch == 0 ? s0 : ch == 1 ? s1 : s2;
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = ((float)src[3 * e] / 255.0f - mean) / sd;
+        if (mix_needs_partner(m, f, y, x)) {
+            const unsigned char* ps = frames + (((size_t)(m.partner * T + f) * H0 + py0 + y) * W0 + px0 + x) * 3 + ch;
+            float w[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) w[e] = ((float)ps[3 * e] / 255.0f - mean) / sd;
+            mix_apply8(m, x, v, w);
+        }
+        bf16x8 o = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3], (bf16)v[4], (bf16)v[5], (bf16)v[6], (bf16)v[7]};
+        *(bf16x8*)(out + (size_t)row * ldo + c8) = o;
+    }
+}
+extern "C" int tvts_patch_gather_tube_u8_mix(const unsigned char* frames, int H0, int W0, const int* crop, const int* keep,
+                                             const int* mix_i, const float* mix_f, int B, int tubes, int tubelet, int n, int img,
+                                             int patch, const float* mean3, const float* std3, void* out, int ldo,
+                                             hipStream_t stream) {
+    if (!frames || !keep || !mix_i || !mix_f || !out || !mean3 || !std3 || B <= 0 || tubes <= 0 || tubelet <= 0 || n <= 0 || patch <= 0 ||
+        img <= 0 || img % patch || patch % 8 || H0 < img || W0 < img || ldo % 8 || ldo < 3 * tubelet * patch * patch || ((size_t)out % 16))
+        return TVTS_EINVAL;
+    hipLaunchKernelGGL(patch_gather_tube_u8_mix_kernel, dim3(B * tubes * n), dim3(256), 0, stream, frames, H0, W0, crop, keep, mix_i,
+                       mix_f, B, tubes, tubelet, n, img, patch, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (bf16*)out,
+                       ldo);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
 // uint8 wire format: the frames arrive as the decoder leaves them -- uint8, H x W x 3 interleaved, already
 // resized on the host -- and the rest of the reference's transform chain runs here, fused into the tube-mask gather:
 // crop (video_transform.CenterCrop / RandomCrop = an offset per sample), ClipToTensor (float32 / 255) and Normalize

@@ -4,6 +4,7 @@
 //   tvts_drop_path_table   the step's stochastic-depth draw: one keep / drop decision per (branch, sample)
 //   tvts_drop_path_rows    out = residual + scale[sample] * y (forward) / dy_branch = scale[sample] * d_out (backward)
 //   tvts_soft_ce           soft-target / label-smoothing cross entropy on [B, C] logits: loss, dlogits, top-1 hit count
+//   tvts_mix_targets       the soft targets of a Mixup / CutMix step from labels and the step's mix table
 //   tvts_grad_sumsq        global gradient norm over the trainable chunks of the flat gradient buffer + the clip coefficient,
 //                          both left in device memory
 // (the step's optimizer, tvts_adamw_torch, is in optim.hip beside tvts_adamw_hf: the two share one chunk frame)
@@ -188,6 +189,34 @@ extern "C" int tvts_soft_ce(const float* logits, long ld, int B, int C, const fl
     hipLaunchKernelGGL(soft_ce_rows_kernel, dim3(B), dim3(256), 0, stream, logits, ld, B, C, soft_targets, ldt, labels, smoothing,
                        scale, dlogits, ldd, ws);
     hipLaunchKernelGGL(soft_ce_finish_kernel, dim3(1), dim3(256), 0, stream, ws, B, scale, loss_acc, hits);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- Mixup / CutMix soft targets
+// mixup_target (v1/downstream/mixup.py:18-23) over the step's mix table (embed.hip, patch_gather_tube_cm_mix_kernel):
+//   t[b, c] = fadd_rn(fmul_rn(y1, lam), fmul_rn(y2, one_minus_lam)),  y1 = on / off for labels[b], y2 = on / off for labels[partner[b]]
+// on / off arrive rounded to fp32 (torch.full of the double values).  A mode-0 row takes lam = 1, one_minus_lam = 0 and still
+// runs the arithmetic (the reference computes y1 * 1. + y2 * 0. there).  A partner outside [0, B) leaves its row unwritten.
+__global__ __launch_bounds__(256) void mix_targets_kernel(const int* __restrict__ labels, const int* __restrict__ mix_i,
+                                                          const float* __restrict__ mix_f, int B, int C, float on, float off,
+                                                          float* __restrict__ out, long ldo) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)B * C) return;
+    const int b = (int)(idx / C), c = (int)(idx % C);
+    const int partner = mix_i[6 * (size_t)b], mode = mix_i[6 * (size_t)b + 1];
+    if ((unsigned)partner >= (unsigned)B) return;
+    const float lam = mode == 0 ? 1.0f : mix_f[2 * (size_t)b], oml = mode == 0 ? 0.0f : mix_f[2 * (size_t)b + 1];
+    const float y1 = c == labels[b] ? on : off, y2 = c == labels[partner] ? on : off;
+    out[(long)b * ldo + c] = __fadd_rn(__fmul_rn(y1, lam), __fmul_rn(y2, oml));
+}
+extern "C" int tvts_mix_targets(const int* labels, const int* mix_i, const float* mix_f, int B, int C, double smoothing, float* out,
+                                long ldo, hipStream_t stream) {
+    if (!labels || !mix_i || !mix_f || !out || B <= 0 || C <= 0 || ldo < C || !(smoothing >= 0.0 && smoothing < 1.0)) return TVTS_EINVAL;
+    const double off = smoothing / (double)C, on = 1.0 - smoothing + off;  // mixup.py:19-20, in double as Python computes them
+    const long n = (long)B * C;
+    hipLaunchKernelGGL(mix_targets_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, labels, mix_i, mix_f, B, C,
+                       (float)on, (float)off, out, ldo);
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;
 }

@@ -10,18 +10,33 @@ v1/downstream/run_class_finetuning.py / run_class_linear.py (engine_for_finetuni
             g["lr"] = lr_schedule[it] * g["lr_scale"]
         out = step.step(samples, targets)                                          # loss, logits, grad_norm, class_acc
 
+Mixup / CutMix (run_class_finetuning.py:408-416, engine_for_finetuning.py:58-59; on in the default recipe):
+
+    mixup_fn = Mixup(mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, mode="batch", label_smoothing=0.1,
+                     num_classes=174)                                              # v1/downstream/mixup.py:97-112
+    plan = mixup_fn.draw(B, img)                                                   # host: the reference's np.random calls, in order
+    out = step.step(samples, labels, mix=plan)                                     # fp32 [B, 3, T, H, W] or uint8 [B, T, H0, W0, 3]
+
+The plan is a per-sample table (partner, mode, box, lam, 1 - lam); the tubelet gather mixes the two clips element by element in
+front of its bf16 rounding (tvts_patch_gather_tube_cm_mix / _u8_mix: uint8 clips are cropped and normalised first, then mixed, in
+the reference's arithmetic order) and tvts_mix_targets builds the soft targets from the labels.  No mixed clip is materialised.
+
 One step: EngineV1.finetune_forward (all patches, stochastic depth from a counter-based per-step table, `norm` at the CLS rows,
-`head`), tvts_soft_ce (soft targets as a host-side Mixup produces them, or labels with smoothing), EngineV1.finetune_backward,
+`head`), tvts_soft_ce (soft targets -- passed in, or built by tvts_mix_targets from a plan --, or labels with smoothing),
+EngineV1.finetune_backward,
 and on every update_freq-th call tvts_grad_sumsq (global norm + clip coefficient, left on the device), tvts_adamw_torch and a
 fill-kernel zero of the gradients.  Nothing in the step synchronises with the host; the returned values are device tensors.
 The optimizer, FusedTorchAdamW, lives in tvts_amd/optim.py beside FusedHFAdamW (one shared base) and is re-exported here.
 
-OUT OF SCOPE (not built here): mixup / cutmix and the augmentation stack (the host data pipeline: pass their soft targets in),
-``ModelEma``, the fp16 loss scaler (the engine is bf16 with fp32 accumulation: there is no loss scale), DeepSpeed, the multi-GPU
+OUT OF SCOPE (not built here): random erasing and the rest of the per-sample augmentation stack (the host data pipeline),
+``FastCollateMixup`` (the uint8-rounding variant: the reference scripts do not use it), ``ModelEma``, the fp16 loss scaler (the engine is bf16 with fp32 accumulation: there is no loss scale), DeepSpeed, the multi-GPU
 gradient exchange for this step (the backward keeps its Engine._ready calls so that one can hook in), and hipGraph capture of it.
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
+import numpy as np
 import torch
 
 from .. import hip as K
@@ -77,6 +92,118 @@ def param_groups(model, weight_decay, layer_decay=1.0, skip_list=None, trainable
     return list(groups.values())
 
 
+# ---------------------------------------------------------------------------------------------- Mixup / CutMix
+class MixPlan(NamedTuple):
+    """one step's draw, on the host: mix_i int32 [B, 6] = (partner, mode, yl, yh, xl, xh) with mode 0 none / 1 mixup / 2 cutmix /
+    3 pair-mode cutmix, mix_f float32 [B, 2] = (lam, one_minus_lam), and the label smoothing of the soft targets.
+    Mode 3: `_mix_pair` pastes `x[i][:, yl:yh, xl:xh]` (mixup.py:180-181), written for [C, H, W] pictures; on the [C, T, H, W] clips
+    of this recipe the two slices land on (frame, row), and that is what the reference trains on in pair mode: the box (drawn
+    for the picture, lam corrected for it) cuts the frames [yl, yh) and the rows [xl, xh), over the whole width."""
+    mix_i: np.ndarray
+    mix_f: np.ndarray
+    smoothing: float
+
+
+class Mixup:
+    """v1/downstream/mixup.py:83-211 (timm's Mixup) split in two: ``draw`` makes the reference's random draws on the host and
+    returns them as a MixPlan; the mixing itself runs inside the step's gather (FinetuneStep.step(..., mix=plan)).  Constructor
+    keywords, defaults and ``mixup_enabled`` as the reference class (:97-112)."""
+
+    def __init__(self, mixup_alpha=1., cutmix_alpha=0., cutmix_minmax=None, prob=1.0, switch_prob=0.5, mode='batch', correct_lam=True,
+                 label_smoothing=0.1, num_classes=1000):
+        if cutmix_minmax is not None:
+            if len(cutmix_minmax) != 2:
+                raise ValueError("cutmix_minmax: (min, max)")
+            cutmix_alpha = 1.0  # (:102-105: min / max boxes do not use the alpha, the class forces it on)
+        if mode not in ("batch", "pair", "elem"):
+            raise ValueError("mode: 'batch', 'pair' or 'elem'")
+        self.mixup_alpha, self.cutmix_alpha, self.cutmix_minmax = mixup_alpha, cutmix_alpha, cutmix_minmax
+        self.mix_prob, self.switch_prob, self.label_smoothing, self.num_classes = prob, switch_prob, label_smoothing, num_classes
+        self.mode, self.correct_lam, self.mixup_enabled = mode, correct_lam, True
+
+    # the draws below call the GLOBAL np.random in the reference's order (a script seeded the same way draws the same plan), and
+    # keep the reference's number types: float64 / Python scalars in batch mode, float32 array elements in pair / elem mode
+    def _lam_mix(self, size):
+        """-> (lam_mix, use_cutmix) of _params_per_batch (:138-148, size None) / _params_per_elem (:118-130)"""
+        both = self.mixup_alpha > 0. and self.cutmix_alpha > 0.
+        if not both and not self.mixup_alpha > 0. and not self.cutmix_alpha > 0.:
+            raise ValueError("one of mixup_alpha > 0, cutmix_alpha > 0, cutmix_minmax must be set")
+        if size is None:
+            cut = bool(np.random.rand() < self.switch_prob) if both else not self.mixup_alpha > 0.
+            alpha = self.cutmix_alpha if cut else self.mixup_alpha
+            return np.random.beta(alpha, alpha), cut
+        if both:  # both betas are drawn for every element, the cutmix one first
+            cut = np.random.rand(size) < self.switch_prob
+            lam_c = np.random.beta(self.cutmix_alpha, self.cutmix_alpha, size=size)
+            lam_m = np.random.beta(self.mixup_alpha, self.mixup_alpha, size=size)
+            return np.where(cut, lam_c, lam_m), cut
+        alpha = self.mixup_alpha if self.mixup_alpha > 0. else self.cutmix_alpha
+        return np.random.beta(alpha, alpha, size=size), np.full(size, not self.mixup_alpha > 0., dtype=bool)
+
+    def _box(self, img, lam):
+        """cutmix_bbox_and_lam (:70-80) on an img x img picture -> ((yl, yh, xl, xh), lam)"""
+        if self.cutmix_minmax is not None:  # rand_bbox_minmax (:60-66)
+            lo, hi = int(img * self.cutmix_minmax[0]), int(img * self.cutmix_minmax[1])
+            cut_h = np.random.randint(lo, hi)
+            cut_w = np.random.randint(lo, hi)
+            yl = np.random.randint(0, img - cut_h)
+            xl = np.random.randint(0, img - cut_w)
+            yh, xh = yl + cut_h, xl + cut_w
+        else:                               # rand_bbox (:36-45), margin 0; `ratio` keeps lam's type (float32 in pair / elem mode)
+            ratio = np.sqrt(1 - lam)
+            cut = int(img * ratio)
+            cy = np.random.randint(0, img)
+            cx = np.random.randint(0, img)
+            yl, yh = np.clip(cy - cut // 2, 0, img), np.clip(cy + cut // 2, 0, img)
+            xl, xh = np.clip(cx - cut // 2, 0, img), np.clip(cx + cut // 2, 0, img)
+        if self.correct_lam or self.cutmix_minmax is not None:
+            lam = 1. - ((yh - yl) * (xh - xl)) / float(img * img)
+        return (int(yl), int(yh), int(xl), int(xh)), lam
+
+    def draw(self, B, img):
+        """the parameters of one step for B clips of img x img pixels -> MixPlan.  Odd B: ValueError (the reference asserts, :203)"""
+        if B % 2:
+            raise ValueError("Mixup needs an even batch size")
+        mix_i = np.zeros((B, 6), dtype=np.int32)
+        mix_i[:, 0] = B - 1 - np.arange(B)  # every mode mixes sample i with sample B - 1 - i (flip(0), :157,174,196)
+        mix_f = np.empty((B, 2), dtype=np.float32)
+        mix_f[:, 0], mix_f[:, 1] = 1.0, 0.0
+        if self.mode == "batch":  # _mix_batch (:189-200): one draw for all; lam a double, 1 - lam taken in double
+            lam, cut = 1., False
+            if self.mixup_enabled and np.random.rand() < self.mix_prob:
+                lam, cut = self._lam_mix(None)
+                lam = float(lam)
+            if lam != 1.:
+                box = (0, 0, 0, 0)
+                if cut:
+                    box, lam = self._box(img, lam)
+                mix_i[:, 1], mix_i[:, 2:] = 2 if cut else 1, box
+                mix_f[:, 0], mix_f[:, 1] = np.float32(lam), np.float32(1. - lam)
+            return MixPlan(mix_i, mix_f, float(self.label_smoothing))
+        # _mix_elem (:152-167) / _mix_pair (:169-187): lam lives in a float32 array, 1 - lam is taken in float32
+        n = B // 2 if self.mode == "pair" else B
+        lam_batch, cut = np.ones(n, dtype=np.float32), np.zeros(n, dtype=bool)
+        if self.mixup_enabled:
+            lam_mix, cut = self._lam_mix(n)
+            lam_batch = np.where(np.random.rand(n) < self.mix_prob, lam_mix.astype(np.float32), lam_batch)
+        for i in range(n):
+            lam = lam_batch[i]
+            if lam == 1.:
+                continue
+            rows = (i, B - 1 - i) if self.mode == "pair" else (i,)
+            if cut[i]:
+                box, lam = self._box(img, lam)
+                lam_batch[i] = lam
+                for r in rows:
+                    mix_i[r, 1], mix_i[r, 2:] = 3 if self.mode == "pair" else 2, box
+            else:
+                for r in rows:
+                    mix_i[r, 1] = 1
+            for r in rows:
+                mix_f[r, 0], mix_f[r, 1] = lam_batch[i], np.float32(1) - lam_batch[i]
+        return MixPlan(mix_i, mix_f, float(self.label_smoothing))
+
+
 # ---------------------------------------------------------------------------------------------- the step
 class FinetuneStep:
     """train_one_epoch's loop body (engine_for_finetuning.py:55-123) without DeepSpeed / loss scaler.  ``trainable="head"`` is
@@ -111,9 +238,25 @@ class FinetuneStep:
             raise ValueError(f"targets: int64 labels [{B}] or soft targets [{B}, {C}], got {tuple(targets.shape)}")
         return dict(soft_targets=targets.to(dev, torch.float32).contiguous())  # (a Mixup has applied the smoothing already)
 
+    def _mixed_targets(self, targets, mix, B, C, img, dev):
+        """the device table of a MixPlan and the soft targets tvts_mix_targets builds from the labels -> (table, soft_ce keywords)"""
+        if targets.dim() != 1 or targets.is_floating_point() or targets.numel() != B:
+            raise ValueError(f"with a mix plan the targets are integer labels [{B}]")
+        if int(targets.min()) < 0 or int(targets.max()) >= C:
+            raise IndexError(f"labels must lie in [0, {C})")
+        if not (0.0 <= mix.smoothing < 1.0):
+            raise ValueError("mix plan: 0 <= smoothing < 1")
+        table = K.mix_table(mix.mix_i, mix.mix_f, B=B, img=img, device=dev)
+        soft = self.model.engine._f("ft.mix_targets", (B, C))
+        # (the plan's smoothing, not self.smoothing: with a mixup_fn the script's criterion is SoftTargetCrossEntropy, :421-423)
+        K.mix_targets(targets.to(dev, torch.int32).contiguous(), table, soft, smoothing=mix.smoothing)
+        return table, dict(soft_targets=soft)
+
     @torch.no_grad()
-    def step(self, samples, targets):
-        """samples: fp32 [B, 3, T, H, W] or uint8 [B, T, H0, W0, 3]; targets: int64 labels [B] or soft [B, C].
+    def step(self, samples, targets, mix=None):
+        """samples: fp32 [B, 3, T, H, W] or uint8 [B, T, H0, W0, 3]; targets: int64 labels [B] or soft [B, C].  mix: a MixPlan
+        (Mixup.draw) -- targets are then integer labels, the clips are mixed inside the gather and the soft targets built on the
+        device with the plan's label smoothing; None: no mixing.
         -> dict(loss, logits, grad_norm, class_acc): device tensors; loss is the unscaled loss of this call (:70), grad_norm the
         global norm before clipping on a call that updates, else None."""
         m, eng, st = self.model, self.model.engine, self.model.store
@@ -131,9 +274,12 @@ class FinetuneStep:
         if T == 0 or T % a["tubelet"] or T > a["num_frames"]:
             raise ValueError(f"clips of {T} frames: need a multiple of {a['tubelet']}, at most {a['num_frames']}")
         B, C = v.shape[0], m.num_classes
-        tk = self._targets(targets, B, C, dev)
+        if mix is None:
+            table, tk = None, self._targets(targets, B, C, dev)
+        else:
+            table, tk = self._mixed_targets(targets, mix, B, C, a["image"], dev)
         m._fresh_shadows()
-        logits = eng.finetune_forward(v, B, T // a["tubelet"], channel_major=cm)
+        logits = eng.finetune_forward(v, B, T // a["tubelet"], channel_major=cm, mix=table)
         dlogits, ws = eng._f("ft.dlogits", (B, C)), eng._f("ft.ce_ws", (2 * B,))
         K.zero_(self.loss_cell)
         K.soft_ce(logits, self.loss_cell, ws, scale=1.0 / self.update_freq, dlogits=dlogits, hits=self.hits, **tk)

@@ -888,6 +888,65 @@ def patch_gather_tube_u8(frames, keep, out, *, B, tubes, tubelet, n, img, patch,
                                        patch, m3, s3, _p(out), _ld(out), _stream()), "tvts_patch_gather_tube_u8")
 
 
+def check_mix_plan(mix_i, mix_f, *, B, img):
+    """the host-side check of a Mixup / CutMix plan (the C entry points take the table as unchecked device data): mix_i integer
+    [B, 6] = (partner, mode, yl, yh, xl, xh), mix_f float [B, 2] = (lam, one_minus_lam) -> (int32, float32) numpy arrays.
+    ValueError for a partner outside [0, B), a mode outside {0, 1, 2, 3} or a box that is not 0 <= lo <= hi <= img."""
+    import numpy as np
+    mi, mf = np.asarray(mix_i), np.asarray(mix_f)
+    if mi.shape != (B, 6) or mi.dtype.kind not in "iu" or mf.shape != (B, 2) or mf.dtype.kind != "f":
+        raise ValueError(f"mix plan: integer mix_i [{B}, 6] and float mix_f [{B}, 2], got {mi.dtype} {mi.shape} / {mf.dtype} {mf.shape}")
+    mi = mi.astype(np.int64)
+    if ((mi[:, 0] < 0) | (mi[:, 0] >= B)).any():
+        raise ValueError(f"mix plan: partner outside [0, {B})")
+    if ((mi[:, 1] < 0) | (mi[:, 1] > 3)).any():
+        raise ValueError("mix plan: mode must be 0 (none), 1 (mixup), 2 (cutmix) or 3 (pair-mode cutmix: the box over frames x rows)")
+    for lo, hi, ax in ((2, 3, "y"), (4, 5, "x")):
+        if ((mi[:, lo] < 0) | (mi[:, lo] > mi[:, hi]) | (mi[:, hi] > img)).any():
+            raise ValueError(f"mix plan: box needs 0 <= {ax}l <= {ax}h <= {img}")
+    if not np.isfinite(mf).all():
+        raise ValueError("mix plan: lam / one_minus_lam must be finite")
+    return np.ascontiguousarray(mi, dtype=np.int32), np.ascontiguousarray(mf, dtype=np.float32)
+
+
+def mix_table(mix_i, mix_f, *, B, img, device="cuda"):
+    """check_mix_plan, then the upload -> (mix_i int32 [B, 6], mix_f fp32 [B, 2]) on the device, as the _mix kernels read them"""
+    mi, mf = check_mix_plan(mix_i, mix_f, B=B, img=img)
+    return torch.from_numpy(mi).to(device), torch.from_numpy(mf).to(device)
+
+
+def _mix_dev(mix, B):
+    mi, mf = mix
+    assert mi.dtype == torch.int32 and mi.is_contiguous() and tuple(mi.shape) == (B, 6), "mix_i: int32 [B, 6] from mix_table()"
+    assert mf.dtype == torch.float32 and mf.is_contiguous() and tuple(mf.shape) == (B, 2), "mix_f: fp32 [B, 2] from mix_table()"
+    return mi, mf
+
+
+def patch_gather_tube_mix(video, keep, out, mix, *, B, tubes, tubelet, n, img, patch):
+    """patch_gather_tube(channel_major=True) with Mixup / CutMix applied per element in front of the bf16 rounding; mix: the device
+    table of mix_table()"""
+    mi, mf = _mix_dev(mix, B)
+    assert video.dtype == torch.float32 and keep.dtype == torch.int32
+    assert video.is_contiguous() and tuple(video.shape) == (B, 3, tubes * tubelet, img, img) and tuple(keep.shape) == (B, tubes, n)
+    assert keep.is_contiguous() and out.dtype == torch.bfloat16
+    _chk(_lib.load().tvts_patch_gather_tube_cm_mix(_p(video), _p(keep), _p(mi), _p(mf), B, tubes, tubelet, n, img, patch, _p(out),
+                                                   _ld(out), _stream()), "tvts_patch_gather_tube_cm_mix")
+
+
+def patch_gather_tube_u8_mix(frames, keep, out, mix, *, B, tubes, tubelet, n, img, patch, crop=None, mean=IMAGENET_MEAN,
+                             std=IMAGENET_STD):
+    """patch_gather_tube_u8 with Mixup / CutMix: both samples cropped (each by its own offset) and normalised, then mixed"""
+    mi, mf = _mix_dev(mix, B)
+    assert frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() == 5 and frames.shape[-1] == 3
+    assert frames.shape[0] == B and frames.shape[1] == tubes * tubelet
+    assert keep.dtype == torch.int32 and keep.is_contiguous() and tuple(keep.shape) == (B, tubes, n) and out.dtype == torch.bfloat16
+    assert crop is None or (crop.dtype == torch.int32 and crop.is_contiguous() and tuple(crop.shape) == (B, 2))
+    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    _chk(_lib.load().tvts_patch_gather_tube_u8_mix(_p(frames), frames.shape[2], frames.shape[3], _p(crop), _p(keep), _p(mi), _p(mf), B,
+                                                   tubes, tubelet, n, img, patch, m3, s3, _p(out), _ld(out), _stream()),
+         "tvts_patch_gather_tube_u8_mix")
+
+
 def text_embed(ids, emb, pos, x, *, N, L):
     lib = _lib.load()
     assert ids.dtype == torch.int32
@@ -1128,6 +1187,16 @@ def soft_ce(logits, loss_acc, ws, *, soft_targets=None, labels=None, smoothing=0
     _chk(_lib.load().tvts_soft_ce(_p(logits), _ld(logits), B, C, _p(soft_targets), _ld(soft_targets) if soft_targets is not None else 0,
                                   _p(labels), float(smoothing), float(scale), _p(loss_acc), _p(dlogits),
                                   _ld(dlogits) if dlogits is not None else 0, _p(hits), _p(ws), _stream()), "tvts_soft_ce")
+
+
+def mix_targets(labels, mix, out, *, smoothing=0.0):
+    """out fp32 [B, C] = the soft targets of a Mixup / CutMix step (mixup_target): labels int32 [B], mix the device table of
+    mix_table(); feeds soft_ce(soft_targets=out)"""
+    B, C = out.shape
+    mi, mf = _mix_dev(mix, B)
+    assert labels.dtype == torch.int32 and labels.numel() == B and labels.is_contiguous() and out.dtype == torch.float32
+    _chk(_lib.load().tvts_mix_targets(_p(labels), _p(mi), _p(mf), B, C, float(smoothing), _p(out), _ld(out), _stream()),
+         "tvts_mix_targets")
 
 
 def grad_sumsq(g, chunk_group, partial, norm_coef, *, max_norm=0.0, grad_scale=1.0):
