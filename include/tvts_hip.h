@@ -466,6 +466,39 @@ int tvts_patch_gather_tube_cm_mix(const float* video, const int* keep, const int
 int tvts_patch_gather_tube_u8_mix(const unsigned char* frames, int H0, int W0, const int* crop, const int* keep, const int* mix_i,
                                   const float* mix_f, int B, int tubes, int tubelet, int n, int img, int patch, const float* mean3,
                                   const float* std3, void* out, int ldo, hipStream_t stream);
+/* The per-sample augmentation of the v1 fine-tuning recipe behind RandAugment (v1/downstream/ssv2.py:186-227) fused into the uint8
+ * gather: Normalize, `random_resized_crop` (v1/downstream/video_transforms.py:499-573: `_get_param_spatial_crop`, then torch's
+ * bilinear `interpolate(..., align_corners=False)` of the crop to img x img), `horizontal_flip` (video_transforms.py:156-177),
+ * `RandomErasing._erase_cube` (v1/downstream/random_erasing.py:109-149), then the mix of tvts_patch_gather_tube_u8_mix.  frames
+ * uint8 [Bs, T, H0, W0, 3]; H0, W0 >= 1 (source frames may be smaller than img).  The draw is a per-sample table in DEVICE memory:
+ *   aug_i int32 [B, 16] = (src, top, left, h, w, flip, emode, etop, eleft, eh, ew, key_lo, key_hi, 0, 0, 0)
+ * src: the source clip in [0, Bs) -- several samples may name one clip (the two views of `--num_sample 2`,
+ * v1/downstream/utils.py `multiple_samples_collate`); [top, top + h) x [left, left + w): the crop in the source frame, 1 <= h <= H0,
+ * 1 <= w <= W0; flip 0 / 1: the resized picture mirrored in x; emode 0 none / 1 const (zeros) / 2 rand (one normal per frame and
+ * channel) / 3 pixel (one normal per frame, channel and pixel); [etop, etop + eh) x [eleft, eleft + ew): the erase box in OUTPUT
+ * coordinates, the same in every frame; key = key_lo | key_hi << 32: the sample's noise key.
+ * Output element (b, c, f, y, x), in this order:
+ *   taps   sy = (float)h / (float)img, s = max(sy * (y + 0.5f) - 0.5f, 0), y0 = (int)s, y1 = min(y0 + 1, h - 1) (the crop's edge, not
+ *          the frame's), ly = s - y0; the same in x with w, x replaced by img - 1 - x first under flip.  fp32, every operation rounded.
+ *   values the four taps of frame src * T + f at (top + y., left + x.), each (u / 255.0f - mean) / std as tvts_patch_gather_tube_u8
+ *   blend  (1 - ly) * ((1 - lx) * a + lx * b) + ly * ((1 - lx) * c + lx * d), every product and sum rounded to fp32 (no FMA).  With
+ *          h == w == img, flip == 0, emode == 0 every l is 0 and the bits are tvts_patch_gather_tube_u8's with crop = (top, left).
+ *   erase  inside the box: const 0.0f; pixel z(key, ((f * 3 + c) * img + y) * img + x); rand z(key + 0xD1B54A32D192ED03, f * 3 + c).  The
+ *          index is in output coordinates: a pixel's noise depends on neither keep, the patch size nor the thread that holds it.
+ *   mix    (mix_i / mix_f given) mix_apply of tvts_patch_gather_tube_cm_mix over this value and the partner's, the partner taken
+ *          through ITS OWN crop, flip and erase; then ONE rounding to bf16.
+ * z(key, idx): r = mix(key + idx * 0x9E3779B97F4A7C15) with the splitmix64 finaliser of the dropout masks above; u1 = ((r >> 32) + 1)
+ * * 2^-32 in (0, 1], u2 = (r & 0xffffffff) * 2^-32, z = sqrtf(-2 logf(u1)) * cosf(2 pi u2), the accurate library functions, ln u1
+ * taken as log1pf(u1 - 1) where u1 is within 2^-8 of 1 (an fp32 u1 has lost ln u1 there): within 2e-5 of the rule evaluated in
+ * float64, which is its definition.  The reference draws this noise from
+ * torch's CPU generator (random_erasing.py:11-24 `_get_pixels`); that stream is not reproduced.
+ * Returns -22 for a NULL among frames / keep / aug_i / out / mean3 / std3, exactly one of mix_i / mix_f NULL, Bs <= 0, H0 or W0 <= 0,
+ * the shape conditions of tvts_patch_gather_tube_u8_mix (without H0, W0 >= img) and out not 16-byte aligned.  The tables are DEVICE
+ * data and are not checked: the caller keeps every column in range (tvts_amd.hip.aug_table does); a src outside [0, Bs) -- the
+ * sample's own or, under a mix, its partner's -- leaves that sample's rows unwritten and reads nothing. */
+int tvts_patch_gather_tube_u8_aug(const unsigned char* frames, int Bs, int H0, int W0, const int* keep, const int* aug_i,
+                                  const int* mix_i, const float* mix_f, int B, int tubes, int tubelet, int n, int img, int patch,
+                                  const float* mean3, const float* std3, void* out, int ldo, hipStream_t stream);
 int tvts_text_embed(const int* ids, int ld_ids, int N, int L, const float* emb, const float* pos, int Wt, float* x, int ldx,
                     hipStream_t stream);
 /* ---- PACKED variable-length captions (the forward-only text encoder of the SSv2 multiple-choice models,

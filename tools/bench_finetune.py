@@ -17,7 +17,21 @@ seed, trainable = "all" only:
             soft targets.  The clip is mixed IN PLACE step after step, as the reference mixes the loader's batch: the values drift
             towards the batch mean, the work per step does not change.
     device  step(clip, labels, mix=plan): the mix inside the gather, tvts_mix_targets.
---u8: uint8 frames [B, T, 224, 224, 3] instead of the fp32 clip (with --mixup torch there is nothing to compare: refused)."""
+--u8: uint8 frames [B, T, 224, 224, 3] instead of the fp32 clip (with --mixup torch there is nothing to compare: refused).
+
+--aug {off,torch,device} (default off) with --num-sample N: the per-sample augmentation behind RandAugment (ssv2.py:186-227: random-
+resized crop, flip off as for SSv2, random erasing 0.25 / pixel), one plan per step drawn on the host from a fixed seed for
+B / N decoded clips of 256 x 320 and N views each, integer labels, trainable = "all" only.  Both settings start from HOST memory
+every step, as a loader's batch does (pinned buffers), so the upload is inside the timed step:
+    torch   the reference's torch operations on the host's normalised fp32 source clips -- slice, interpolate(bilinear), flip,
+            normal_() into the erase box -- written into a pinned fp32 [B, 3, T, 224, 224] buffer, the step taking that clip.
+            A second timed loop ships the already augmented pinned clip (upload + step only: a loader whose workers hide the
+            augmentation); the host operations' own clock is reported too (they overlap the previous step's device work, so
+            their time cannot be subtracted from the first figure).
+    device  step(frames_u8, labels, aug=plan): the uint8 source frames [B / N, T, 256, 320, 3] and the plan are shipped, the gather
+            does the rest.
+--mixup device / torch may be combined with the --aug setting of the same name.  With --u8 (--aug off) or --aug device the
+gather's own time is measured too: device events around 50 launches of the step's gather on the step's shapes, in a pass of its own."""
 import argparse
 import json
 import os
@@ -58,6 +72,117 @@ def torch_mix(x, labels, plan, classes):
     return y1 * lam + y2 * oml
 
 
+SRC = (256, 320)  # the decoded clip in front of the crop (short side 256, ssv2.py:147)
+
+
+def torch_aug(src, plan, img, buf):
+    """the reference's torch operations (video_transforms.py:567-573,177; random_erasing.py:138-148) with the plan's numbers, on
+    the host: src fp32 [Bs, 3, T, H0, W0] normalised -> buf fp32 [B, 3, T, img, img] (pinned)"""
+    for b, row in enumerate(plan.aug_i):
+        s_, i, j, h, w, flip, emode, et, el, eh, ew = (int(v) for v in row[:11])
+        x = torch.nn.functional.interpolate(src[s_][:, :, i:i + h, j:j + w], size=(img, img), mode="bilinear", align_corners=False)
+        if flip:
+            x = x.flip((-1))
+        if emode:
+            for t in range(x.shape[1]):
+                x[:, t, et:et + eh, el:el + ew] = torch.empty((3, eh, ew)).normal_()
+        buf[b].copy_(x)
+    return buf
+
+
+def gather_us(fn, reps=50):
+    """device events around `reps` launches of the step's gather (all patches kept) -> microseconds per launch"""
+    fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return 1e3 * e0.elapsed_time(e1) / reps
+
+
+def run_aug(args, targets):
+    """--aug torch / device -> the result dict of trainable = "all" """
+    import random
+
+    import numpy as np
+    from tvts_amd import hip as K
+    from tvts_amd.downstream.finetune_v1 import Augment, Mixup
+    m, step, ngroups = make("all", args)
+    img, T, B, Bs = KW["img_size"], KW["num_frames"], args.batch, args.batch // args.num_sample
+    random.seed(0)
+    np.random.seed(0)
+    aug = Augment(img, hflip=0.0, reprob=0.25, remode="pixel", recount=1, num_sample=args.num_sample)
+    mixup = Mixup(mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, mode="batch", label_smoothing=0.1, num_classes=args.classes)
+    g = torch.Generator().manual_seed(1)
+    frames = torch.randint(0, 256, (Bs, T, SRC[0], SRC[1], 3), generator=g, dtype=torch.uint8).pin_memory()
+    host = dict(s=0.0)
+    if args.aug == "device":
+        def one():
+            plan = aug.draw(Bs, *SRC)
+            return step.step(frames, targets, aug=plan, mix=mixup.draw(B, img) if args.mixup == "device" else None)
+    else:
+        mean, std = torch.tensor(K.IMAGENET_MEAN).view(1, 1, 1, 1, 3), torch.tensor(K.IMAGENET_STD).view(1, 1, 1, 1, 3)
+        src = ((frames.float() / 255.0 - mean) / std).permute(0, 4, 1, 2, 3).contiguous()
+        buf = torch.empty(B, 3, T, img, img).pin_memory()
+
+        def one():
+            t0 = time.perf_counter()
+            clip = torch_aug(src, aug.draw(Bs, *SRC), img, buf)
+            host["s"] += time.perf_counter() - t0
+            if args.mixup == "torch":
+                clip = clip.cuda()
+                return step.step(clip, torch_mix(clip, targets, mixup.draw(B, img), args.classes))
+            return step.step(clip, targets)
+    for _ in range(args.warmup):
+        out = one()
+    torch.cuda.synchronize()
+    host["s"] = 0.0
+    t0 = time.perf_counter()
+    for _ in range(args.iters):
+        out = one()
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / args.iters
+    res = {"step ms": 1e3 * dt, "clips/s": B / dt, "parameter groups": ngroups, "last loss": float(out["loss"]),
+           "upload bytes/step": (frames if args.aug == "device" else buf).numel() * (1 if args.aug == "device" else 4)}
+    if args.aug == "torch":
+        res["host augment ms/step"] = 1e3 * host["s"] / args.iters
+        if args.mixup == "off":  # upload + step only, from the pinned buffer the last step left
+            for _ in range(args.warmup):
+                step.step(buf, targets)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.iters):
+                step.step(buf, targets)
+            torch.cuda.synchronize()
+            dt = (time.perf_counter() - t0) / args.iters
+            res.update({"step ms, augmented clip ready on the host": 1e3 * dt, "clips/s, augmented clip ready on the host": B / dt})
+    else:
+        a, eng = m.engine.arch, m.engine
+        tubes, ppf, kc = T // a["tubelet"], (img // a["patch"]) ** 2, 3 * a["tubelet"] * a["patch"] ** 2
+        keep = torch.arange(ppf, dtype=torch.int32, device="cuda").repeat(B, tubes, 1).contiguous()
+        cols = torch.empty(B * tubes * ppf, kc, dtype=torch.bfloat16, device="cuda")
+        plan = aug.draw(Bs, *SRC)
+        table, fr = K.aug_table(plan.aug_i, Bs=Bs, H0=SRC[0], W0=SRC[1], img=img), frames.cuda()
+        kw = dict(B=B, tubes=tubes, tubelet=a["tubelet"], n=ppf, img=img, patch=a["patch"])
+        crop_bytes = int(sum(int(r[3]) * int(r[4]) for r in plan.aug_i)) * 3 * T
+        res.update({"gather us (events, 50 launches)": gather_us(lambda: K.patch_gather_tube_u8_aug(fr, keep, cols, table, None, **kw)),
+                    "gather bytes (crop source + 2 B per output element)": crop_bytes + 2 * cols.numel()})
+        ident = plan.aug_i.copy()
+        ident[:, 1:11] = (16, 48, img, img, 0, 0, 0, 0, 0, 0)
+        table = K.aug_table(ident, Bs=Bs, H0=SRC[0], W0=SRC[1], img=img)
+        res["gather us, identity crops, no erase"] = gather_us(lambda: K.patch_gather_tube_u8_aug(fr, keep, cols, table, None, **kw))
+        crop = torch.tensor([[16, 48]] * Bs, dtype=torch.int32, device="cuda")
+        kw["B"], keep, cols = Bs, keep[:Bs].contiguous(), cols[:Bs * tubes * ppf]
+        res["plain u8 gather us on the source clips (B / N samples)"] = gather_us(
+            lambda: K.patch_gather_tube_u8(fr, keep, cols, crop=crop, **kw))
+    del m, step
+    torch.cuda.empty_cache()
+    return res
+
+
 def run(trainable, args, clip, targets):
     from tvts_amd import hip as K
     m, step, ngroups = make(trainable, args)
@@ -95,6 +220,14 @@ def run(trainable, args, clip, targets):
             K.HBM_PROFILE = None
         res.update({"drop_path_rows launches/step": n / reps, "drop_path_rows ms/step (events)": ms / reps,
                     "drop_path_rows share of the step": ms / reps / (1e3 * dt)})
+    if trainable == "all" and clip.dtype == torch.uint8:  # the uint8 gather's own time, on the step's shapes
+        a, B = m.engine.arch, clip.shape[0]
+        tubes, ppf, kc = clip.shape[1] // a["tubelet"], (a["image"] // a["patch"]) ** 2, 3 * a["tubelet"] * a["patch"] ** 2
+        keep = torch.arange(ppf, dtype=torch.int32, device="cuda").repeat(B, tubes, 1).contiguous()
+        cols = torch.empty(B * tubes * ppf, kc, dtype=torch.bfloat16, device="cuda")
+        res["gather us (events, 50 launches)"] = gather_us(lambda: K.patch_gather_tube_u8(
+            clip, keep, cols, B=B, tubes=tubes, tubelet=a["tubelet"], n=ppf, img=a["image"], patch=a["patch"]))
+        res["gather bytes (source + 2 B per output element)"] = clip.numel() + 2 * cols.numel()
     del m, step
     torch.cuda.empty_cache()
     return res
@@ -109,7 +242,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--mixup", choices=("off", "torch", "device"), default="off")
     ap.add_argument("--u8", action="store_true", help="uint8 frames [B, T, H, W, 3] instead of the fp32 clip")
+    ap.add_argument("--aug", choices=("off", "torch", "device"), default="off")
+    ap.add_argument("--num-sample", type=int, default=1, help="views per decoded clip (--num_sample of the script)")
     args = ap.parse_args()
+    if args.aug != "off" and (args.u8 or args.mixup not in ("off", args.aug)):
+        raise SystemExit("--aug torch / device: without --u8 (the setting says what is shipped), --mixup off or the same setting")
+    if args.num_sample < 1 or args.batch % args.num_sample or (args.aug == "off" and args.num_sample != 1):
+        raise SystemExit("--num-sample: a divisor of --batch, with --aug torch / device")
     if args.u8 and args.mixup == "torch":
         raise SystemExit("--u8 --mixup torch: the reference mixes normalised fp32 clips, there is no torch form on uint8 frames")
     if args.mixup != "off" and args.batch % 2:
@@ -128,6 +267,13 @@ def main():
     if args.mixup != "off":
         targets = torch.randint(0, args.classes, (args.batch,), generator=g)  # (host labels, as a loader hands them over)
         out["mixup"] = args.mixup
+    if args.aug != "off":
+        out.update({"aug": args.aug, "num_sample": args.num_sample, "source": "%d x %d" % SRC})
+        if args.mixup == "off":
+            targets = torch.randint(0, args.classes, (args.batch,), generator=g)
+        out["trainable=all"] = run_aug(args, targets)
+        print(json.dumps(out), flush=True)
+        return
     for trainable in ("all", "head") if args.mixup == "off" else ("all",):
         out["trainable=" + trainable] = run(trainable, args, clip, targets)
     print(json.dumps(out), flush=True)

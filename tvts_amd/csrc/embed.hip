@@ -300,6 +300,142 @@ extern "C" int tvts_patch_gather_tube_u8_mix(const unsigned char* frames, int H0
     return TVTS_OK;
 }
 
+// The per-sample augmentation of the v1 fine-tuning recipe behind RandAugment (v1/downstream/ssv2.py:186-227), fused into the uint8
+// gather: Normalize, random_resized_crop (video_transforms.py:541-573: a crop of the source frame resized to img x img by
+// torch's bilinear interpolate, align_corners=False), horizontal_flip (:156-177), RandomErasing in cube mode
+// (random_erasing.py:109-149), then the mix above.  The step's draw arrives as a per-sample table in device memory:
+//     aug_i int32 [B, 16] = (src, top, left, h, w, flip, emode, etop, eleft, eh, ew, key_lo, key_hi, 0, 0, 0)
+// src: the source clip in [0, Bs) (several samples may read one clip: --num_sample); the crop [top, top + h) x [left, left + w) of
+// the source frame; flip mirrors the resized picture in x; the erase box [etop, etop + eh) x [eleft, eleft + ew) in OUTPUT
+// coordinates, the same in every frame, emode 0 none / 1 zeros / 2 one normal per (frame, channel) / 3 one per (frame, channel,
+// pixel); key: the sample's 64-bit noise key.  Per output element, in the reference's order:
+//   taps   sy = (float)h / (float)img, src = max(sy * (y + 0.5f) - 0.5f, 0), y0 = (int)src, y1 = min(y0 + 1, h - 1) (the CROP's
+//          edge), ly = src - y0; the same in x with w, for x' = flip ? img - 1 - x : x.  Products and differences are rounded
+//          one by one (no FMA), as the expression is written.
+//   values the four taps of frame src * T + f, each normalised by patch_gather_tube_u8_kernel's expression
+//   blend  (1 - ly) * ((1 - lx) * a + lx * b) + ly * ((1 - lx) * c + lx * d), every product and sum rounded; with h == w == img all
+//          l are 0 and the value is tap a, bit for bit
+//   erase  inside the box: 0 / z(key + AUG_RAND_STREAM, f * 3 + c) / z(key, ((f * 3 + c) * img + y) * img + x), x and y of the OUTPUT
+//   mix    mix_apply8 over this value and the partner's, the partner formed through ITS OWN table row
+// z(key, idx): r = the splitmix64 finaliser (attention.hip::drop_keep) of key + idx * 0x9E3779B97F4A7C15; u1 = ((r >> 32) + 1) * 2^-32
+// in (0, 1], u2 = (r & 0xffffffff) * 2^-32; z = sqrtf(-2 logf(u1)) * cosf(2 pi u2) (Box-Muller, the accurate library functions;
+// ln u1 through log1pf where u1 is within 2^-8 of 1).  The float64 form of this rule is the definition (tests/v1_aug_ref.noise).
+// The y taps and weights are formed once per 8-pixel row piece; a piece reads at most two source rows.
+#define AUG_RAND_STREAM 0xD1B54A32D192ED03ull
+struct AugRow { int src, top, left, h, w, flip, emode, etop, eleft, eh, ew; unsigned long long key; };
+__device__ __forceinline__ AugRow aug_row(const int* __restrict__ aug_i, int b) {
+    const int* a = aug_i + 16 * (size_t)b;
+    return AugRow{a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10],
+                  (unsigned long long)(unsigned)a[11] | ((unsigned long long)(unsigned)a[12] << 32)};
+}
+__device__ __forceinline__ float aug_noise(unsigned long long key, unsigned long long idx) {
+    unsigned long long z = key + idx * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    // ln u1: an fp32 u1 within 2^-8 of 1 has lost the bits that ln u1 = -(1 - u1) - ... consists of (z would be off by up to 2e-4
+    // there); 1 - u1 = k * 2^-32 with k < 2^24 is exact in fp32, so that range takes log1pf(-(1 - u1))
+    const unsigned hi = (unsigned)(z >> 32), k = 0xFFFFFFFFu - hi;  // u1 = (hi + 1) * 2^-32 = 1 - k * 2^-32
+    const float ln_u1 = k < (1u << 24) ? log1pf(-(float)k * 2.3283064365386963e-10f) : logf(((float)hi + 1.0f) * 2.3283064365386963e-10f);
+    const float u2 = (float)(unsigned)z * 2.3283064365386963e-10f;
+    return sqrtf(-2.0f * ln_u1) * cosf(6.283185307179586f * u2);
+}
+// torch's area_pixel_compute_source_index + guard_index_and_lambda for one output coordinate -> (i0, i1, lambda1)
+__device__ __forceinline__ void aug_tap(float scale, int o, int size, int& i0, int& i1, float& l) {
+    const float s = fmaxf(__fsub_rn(__fmul_rn(scale, (float)o + 0.5f), 0.5f), 0.f);
+    i0 = min((int)s, size - 1);
+    i1 = min(i0 + 1, size - 1);
+    l = fminf(fmaxf(__fsub_rn(s, (float)i0), 0.f), 1.f);
+}
+// the 8 augmented values of sample row `a` at channel ch, frame f, output pixels (y, x .. x + 7), before the mix
+// norm: the channel's 256 normalised values (u / 255.0f - mean) / sd, which the block forms once in LDS -- the uint8 gather's own
+// expression, so the same bits, at one pair of divisions per (block, channel, byte value) instead of four pairs per element
+__device__ __forceinline__ void aug_eval8(const unsigned char* __restrict__ frames, int H0, int W0, int T, const AugRow& a, int img,
+                                          int ch, int f, int y, int x, const float* norm, float* v) {
+    int y0, y1;
+    float ly;
+    aug_tap((float)a.h / (float)img, y, a.h, y0, y1, ly);
+    const float sx = (float)a.w / (float)img, hy = __fsub_rn(1.0f, ly);
+    const unsigned char* r0 = frames + (((size_t)(a.src * T + f) * H0 + a.top + y0) * W0 + a.left) * 3 + ch;
+    const unsigned char* r1 = r0 + (size_t)(y1 - y0) * W0 * 3;
+    const bool erow = a.emode != 0 && y >= a.etop && y < a.etop + a.eh;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int xo = x + e;
+        if (erow && xo >= a.eleft && xo < a.eleft + a.ew) {
+            const unsigned long long fc = (unsigned long long)(f * 3 + ch);
+            v[e] = a.emode == 1 ? 0.0f
+                 : a.emode == 2 ? aug_noise(a.key + AUG_RAND_STREAM, fc)
+                                : aug_noise(a.key, (fc * img + y) * img + xo);
+            continue;
+        }
+        int x0, x1;
+        float lx;
+        aug_tap(sx, a.flip ? img - 1 - xo : xo, a.w, x0, x1, lx);
+        const float hx = __fsub_rn(1.0f, lx);
+        const float p00 = norm[r0[3 * x0]], p01 = norm[r0[3 * x1]], p10 = norm[r1[3 * x0]], p11 = norm[r1[3 * x1]];
+        const float up = __fadd_rn(__fmul_rn(hx, p00), __fmul_rn(lx, p01)), dn = __fadd_rn(__fmul_rn(hx, p10), __fmul_rn(lx, p11));
+        v[e] = __fadd_rn(__fmul_rn(hy, up), __fmul_rn(ly, dn));
+    }
+}
+__global__ __launch_bounds__(256) void patch_gather_tube_u8_aug_kernel(const unsigned char* __restrict__ frames, int Bs, int H0, int W0,
+                                                                       const int* __restrict__ keep, const int* __restrict__ aug_i,
+                                                                       const int* __restrict__ mix_i, const float* __restrict__ mix_f,
+                                                                       int B, int tubes, int tb, int n, int img, int p, float m0,
+                                                                       float m1, float m2, float s0, float s1, float s2,
+                                                                       bf16* __restrict__ out, int ldo) {
+    const int pp = p * p, K = 3 * tb * pp;
+    const int row = blockIdx.x;  // (b, tube, i)
+    const int i = row % n, tu = (row / n) % tubes, b = row / (n * tubes);
+    const int g = img / p;
+    const int pi = keep[(size_t)(b * tubes + tu) * n + i];
+    const int gy = pi / g, gx = pi % g;
+    const int T = tubes * tb;
+    const AugRow a = aug_row(aug_i, b);
+    if ((unsigned)a.src >= (unsigned)Bs) return;
+    MixRow m = {b, 0, 0, 0, 0, 0, 1.0f, 0.0f};
+    AugRow pa = a;
+    if (mix_i) {
+        m = mix_row(mix_i, mix_f, b);
+        if ((unsigned)m.partner >= (unsigned)B) return;
+        pa = aug_row(aug_i, m.partner);
+        if ((unsigned)pa.src >= (unsigned)Bs) return;
+    }
+    __shared__ float norm[3][256];  // (the returns above are block-uniform: every thread of a block that stays reaches the barrier)
+    for (int ch = 0; ch < 3; ++ch) {
+        const float mean = ch == 0 ? m0 : ch == 1 ? m1 : m2, sd = ch == 0 ? s0 : ch == 1 ? s1 : s2;
+        norm[ch][threadIdx.x] = ((float)threadIdx.x / 255.0f - mean) / sd;
+    }
+    __syncthreads();
+    for (int c8 = threadIdx.x * 8; c8 < K; c8 += 256 * 8) {
+        const int ch = c8 / (tb * pp), r1 = c8 % (tb * pp), t = r1 / pp, rem = r1 % pp, py = rem / p, px = rem % p;  // px % 8 == 0
+        const int y = gy * p + py, x = gx * p + px, f = tu * tb + t;
+        float v[8];
+        aug_eval8(frames, H0, W0, T, a, img, ch, f, y, x, norm[ch], v);
+        if (mix_needs_partner(m, f, y, x)) {
+            float w[8];
+            aug_eval8(frames, H0, W0, T, pa, img, ch, f, y, x, norm[ch], w);
+            mix_apply8(m, x, v, w);
+        }
+        bf16x8 o = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3], (bf16)v[4], (bf16)v[5], (bf16)v[6], (bf16)v[7]};
+        *(bf16x8*)(out + (size_t)row * ldo + c8) = o;
+    }
+}
+extern "C" int tvts_patch_gather_tube_u8_aug(const unsigned char* frames, int Bs, int H0, int W0, const int* keep, const int* aug_i,
+                                             const int* mix_i, const float* mix_f, int B, int tubes, int tubelet, int n, int img,
+                                             int patch, const float* mean3, const float* std3, void* out, int ldo,
+                                             hipStream_t stream) {
+    if (!frames || !keep || !aug_i || !out || !mean3 || !std3 || (!mix_i) != (!mix_f) || Bs <= 0 || H0 <= 0 || W0 <= 0 || B <= 0 ||
+        tubes <= 0 || tubelet <= 0 || n <= 0 || patch <= 0 || img <= 0 || img % patch || patch % 8 || ldo % 8 ||
+        ldo < 3 * tubelet * patch * patch || ((size_t)out % 16))
+        return TVTS_EINVAL;
+    hipLaunchKernelGGL(patch_gather_tube_u8_aug_kernel, dim3(B * tubes * n), dim3(256), 0, stream, frames, Bs, H0, W0, keep, aug_i, mix_i,
+                       mix_f, B, tubes, tubelet, n, img, patch, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (bf16*)out,
+                       ldo);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
 // uint8 wire format: the frames arrive as the decoder leaves them -- uint8, H x W x 3 interleaved, already
 // resized on the host -- and the rest of the reference's transform chain runs here, fused into the tube-mask gather:
 // crop (video_transform.CenterCrop / RandomCrop = an offset per sample), ClipToTensor (float32 / 255) and Normalize

@@ -28,12 +28,26 @@ and on every update_freq-th call tvts_grad_sumsq (global norm + clip coefficient
 fill-kernel zero of the gradients.  Nothing in the step synchronises with the host; the returned values are device tensors.
 The optimizer, FusedTorchAdamW, lives in tvts_amd/optim.py beside FusedHFAdamW (one shared base) and is re-exported here.
 
-OUT OF SCOPE (not built here): random erasing and the rest of the per-sample augmentation stack (the host data pipeline),
+The per-sample augmentation behind RandAugment (ssv2.py:186-227: Normalize, random-resized crop, flip, random erasing; on in the
+default recipe, with --num_sample 2 views per clip):
+
+    aug_fn = Augment(224, hflip=0.0, reprob=0.25, remode="pixel", recount=1, num_sample=2)   # ssv2.py:196-222
+    plan = aug_fn.draw(Bs, H0, W0)                                                 # host: the reference's random / np.random calls
+    out = step.step(frames_u8, labels.repeat_interleave(2), mix=mixup_fn.draw(len(plan), img), aug=plan)   # uint8 [Bs, T, H0, W0, 3]
+
+The plan is a per-sample table (source clip, crop, flip, erase box, noise key); tvts_patch_gather_tube_u8_aug forms every element
+from its four bilinear taps of the uint8 source frame, erases, mixes and rounds once.  No augmented clip is materialised, and
+the views of one clip read the same uploaded frames.  The erase noise is a counter-based normal, not torch's CPU stream.
+
+OUT OF SCOPE (not built here): RandAugment itself (uint8 PIL frames at source size, the host data pipeline), --recount > 1,
+``motion_shift`` (random_resized_crop_with_shift), the reference's torch noise stream,
 ``FastCollateMixup`` (the uint8-rounding variant: the reference scripts do not use it), ``ModelEma``, the fp16 loss scaler (the engine is bf16 with fp32 accumulation: there is no loss scale), DeepSpeed, the multi-GPU
 gradient exchange for this step (the backward keeps its Engine._ready calls so that one can hook in), and hipGraph capture of it.
 """
 from __future__ import annotations
 
+import math
+import random
 from typing import NamedTuple
 
 import numpy as np
@@ -204,6 +218,122 @@ class Mixup:
         return MixPlan(mix_i, mix_f, float(self.label_smoothing))
 
 
+# ---------------------------------------------------------------------------------------------- crop, flip, random erasing
+_M64 = (1 << 64) - 1
+EMODE = {"const": 1, "rand": 2, "pixel": 3}
+
+
+def splitmix64(x: int) -> int:
+    """the first output of a splitmix64 generator seeded with x: the finaliser of the device's counter-based generator
+    (attention.hip::drop_keep) applied to x + 0x9E3779B97F4A7C15"""
+    z = (x + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+class AugPlan:
+    """one step's per-sample augmentation draw, on the host: aug_i int32 [B, 16] = (src, top, left, h, w, flip, emode, etop, eleft,
+    eh, ew, key_lo, key_hi, 0, 0, 0), the table of tvts_patch_gather_tube_u8_aug (include/tvts_hip.h).  len(plan) = B."""
+
+    def __init__(self, aug_i):
+        self.aug_i = aug_i
+
+    def __len__(self):
+        return int(self.aug_i.shape[0])
+
+
+class Augment:
+    """What v1/downstream/ssv2.py:196-227 draws per sample behind RandAugment, split from what it computes: ``draw`` makes the
+    reference's calls on the reference's generators (Python ``random`` and the global ``np.random``) in its order and with its
+    number types, and returns them as an AugPlan; Normalize, the bilinear resize of the crop, the flip and the erase run inside
+    the step's gather (FinetuneStep.step(frames_u8, targets, aug=plan)).  hflip: the flip probability, 0 = no flip and no draw
+    (ssv2.py:208 passes random_horizontal_flip=False for SSv2; the other data sets flip with 0.5).  reprob / remode / recount:
+    --reprob / --remode / --recount; reprob 0 builds no RandomErasing and draws nothing (ssv2.py:38-40).  num_sample: --num_sample,
+    the views per decoded clip, collated as neighbours (utils.multiple_samples_collate): sample s * num_sample + k is view k of
+    source clip s.  noise_seed: the erase noise is NOT torch's CPU stream (random_erasing.py:11-24) but a counter-based normal
+    keyed per sample, key = splitmix64(noise_seed) + the number of samples drawn before it; the key never touches ``random`` /
+    ``np.random``, so the reference's draw sequence is not shifted."""
+
+    def __init__(self, input_size, scale=(0.08, 1.0), ratio=(0.75, 1.3333), hflip=0.0, reprob=0.25, remode="pixel", recount=1,
+                 num_sample=1, noise_seed=0):
+        if recount != 1:
+            # (the script passes num_splits=args.recount, ssv2.py:220: recount > 1 would also leave the first T // recount frames clean)
+            raise ValueError("recount != 1 is not built (one erase box per sample)")
+        if remode not in EMODE:
+            raise ValueError("remode: 'const', 'rand' or 'pixel'")
+        if input_size < 1 or num_sample < 1:
+            raise ValueError("input_size >= 1 and num_sample >= 1")
+        self.input_size, self.scale, self.ratio, self.hflip = int(input_size), tuple(scale), tuple(ratio), float(hflip)
+        self.reprob, self.remode, self.recount, self.num_sample = reprob, remode, recount, int(num_sample)
+        # RandomErasing's defaults (random_erasing.py:46-64): min_area 0.02, max_area 1/3, min_aspect 0.3, max_aspect 1 / 0.3
+        self.min_area, self.max_area = 0.02, 1 / 3
+        self.log_aspect_ratio = (math.log(0.3), math.log(1 / 0.3))
+        self.noise_key, self.drawn = splitmix64(int(noise_seed) & _M64), 0
+
+    def _crop(self, height, width):
+        """_get_param_spatial_crop (video_transforms.py:499-538; log_scale=True, switch_hw=False) -> (i, j, h, w)"""
+        scale, ratio = self.scale, self.ratio
+        for _ in range(10):
+            area = height * width
+            target_area = random.uniform(*scale) * area
+            log_ratio = (math.log(ratio[0]), math.log(ratio[1]))
+            aspect_ratio = math.exp(random.uniform(*log_ratio))
+            w = int(round(math.sqrt(target_area * aspect_ratio)))
+            h = int(round(math.sqrt(target_area / aspect_ratio)))
+            np.random.uniform()  # (:517 `np.random.uniform() < 0.5 and switch_hw`: drawn on every try, never used)
+            if 0 < w <= width and 0 < h <= height:
+                i = random.randint(0, height - h)
+                j = random.randint(0, width - w)
+                return i, j, h, w
+        in_ratio = float(width) / float(height)  # the central fallback
+        if in_ratio < min(ratio):
+            w = width
+            h = int(round(w / min(ratio)))
+        elif in_ratio > max(ratio):
+            h = height
+            w = int(round(h * max(ratio)))
+        else:
+            w, h = width, height
+        return (height - h) // 2, (width - w) // 2, h, w
+
+    def _erase(self, img_h, img_w):
+        """RandomErasing._erase_cube (random_erasing.py:109-149) with count 1 -> (top, left, h, w) or None"""
+        if random.random() > self.reprob:
+            return None
+        area = img_h * img_w
+        for _ in range(100):
+            target_area = random.uniform(self.min_area, self.max_area) * area / 1
+            aspect_ratio = math.exp(random.uniform(*self.log_aspect_ratio))
+            h = int(round(math.sqrt(target_area * aspect_ratio)))
+            w = int(round(math.sqrt(target_area / aspect_ratio)))
+            if w < img_w and h < img_h:
+                top = random.randint(0, img_h - h)
+                left = random.randint(0, img_w - w)
+                return top, left, h, w
+        return None
+
+    def draw(self, Bs, H0, W0):
+        """the parameters of one step for Bs decoded clips of H0 x W0 pixels -> AugPlan for B = Bs * num_sample samples"""
+        if Bs < 1 or H0 < 1 or W0 < 1:
+            raise ValueError("Bs, H0, W0 >= 1")
+        img = self.input_size
+        aug_i = np.zeros((Bs * self.num_sample, 16), dtype=np.int32)
+        for b in range(Bs * self.num_sample):
+            row = aug_i[b]
+            row[0] = b // self.num_sample
+            row[1:5] = self._crop(H0, W0)
+            if self.hflip > 0:
+                row[5] = int(np.random.uniform() < self.hflip)  # horizontal_flip (video_transforms.py:176)
+            box = self._erase(img, img) if self.reprob > 0 else None
+            if box is not None and box[2] > 0 and box[3] > 0:
+                row[6], row[7:11] = EMODE[self.remode], box
+            key = (self.noise_key + self.drawn) & _M64
+            self.drawn += 1
+            row[11:13] = np.array([key & 0xFFFFFFFF, key >> 32], dtype=np.uint32).view(np.int32)
+        return AugPlan(aug_i)
+
+
 # ---------------------------------------------------------------------------------------------- the step
 class FinetuneStep:
     """train_one_epoch's loop body (engine_for_finetuning.py:55-123) without DeepSpeed / loss scaler.  ``trainable="head"`` is
@@ -253,17 +383,24 @@ class FinetuneStep:
         return table, dict(soft_targets=soft)
 
     @torch.no_grad()
-    def step(self, samples, targets, mix=None):
+    def step(self, samples, targets, mix=None, aug=None):
         """samples: fp32 [B, 3, T, H, W] or uint8 [B, T, H0, W0, 3]; targets: int64 labels [B] or soft [B, C].  mix: a MixPlan
         (Mixup.draw) -- targets are then integer labels, the clips are mixed inside the gather and the soft targets built on the
-        device with the plan's label smoothing; None: no mixing.
+        device with the plan's label smoothing; None: no mixing.  aug: an AugPlan (Augment.draw) -- samples are then the uint8
+        SOURCE frames [Bs, T, H0, W0, 3] (any H0, W0 >= 1), the step has B = len(aug) samples, each cropped, resized, flipped and
+        erased inside the gather from the source clip its row names; targets has B entries (the caller repeats the labels as the
+        collate does) and a MixPlan is drawn for B; None: uint8 clips take the centre crop, as before.
         -> dict(loss, logits, grad_norm, class_acc): device tensors; loss is the unscaled loss of this call (:70), grad_norm the
         global norm before clipping on a call that updates, else None."""
         m, eng, st = self.model, self.model.engine, self.model.store
         a, dev = eng.arch, st.device
         if samples.dim() != 5:
             raise ValueError(f"samples: expected a 5-D clip batch, got {tuple(samples.shape)}")
-        if samples.dtype == torch.uint8:
+        if aug is not None:
+            if samples.dtype != torch.uint8 or samples.shape[-1] != 3 or min(samples.shape[:4]) < 1:
+                raise ValueError("with an augmentation plan the samples are uint8 source frames [Bs, T, H0, W0, 3]")
+            v, T, cm = samples.to(dev).contiguous(), samples.shape[1], False
+        elif samples.dtype == torch.uint8:
             if samples.shape[-1] != 3 or samples.shape[2] < a["image"] or samples.shape[3] < a["image"]:
                 raise ValueError(f"uint8 samples must be [B, T, H, W, 3] with H, W >= {a['image']}")
             v, T, cm = samples.to(dev).contiguous(), samples.shape[1], False
@@ -273,13 +410,14 @@ class FinetuneStep:
             v, T, cm = samples.to(dev, torch.float32).contiguous(), samples.shape[2], True
         if T == 0 or T % a["tubelet"] or T > a["num_frames"]:
             raise ValueError(f"clips of {T} frames: need a multiple of {a['tubelet']}, at most {a['num_frames']}")
-        B, C = v.shape[0], m.num_classes
+        B, C = v.shape[0] if aug is None else len(aug), m.num_classes
+        atab = None if aug is None else K.aug_table(aug.aug_i, Bs=v.shape[0], H0=v.shape[2], W0=v.shape[3], img=a["image"], device=dev)
         if mix is None:
             table, tk = None, self._targets(targets, B, C, dev)
         else:
             table, tk = self._mixed_targets(targets, mix, B, C, a["image"], dev)
         m._fresh_shadows()
-        logits = eng.finetune_forward(v, B, T // a["tubelet"], channel_major=cm, mix=table)
+        logits = eng.finetune_forward(v, B, T // a["tubelet"], channel_major=cm, mix=table, aug=atab)
         dlogits, ws = eng._f("ft.dlogits", (B, C)), eng._f("ft.ce_ws", (2 * B,))
         K.zero_(self.loss_cell)
         K.soft_ce(logits, self.loss_cell, ws, scale=1.0 / self.update_freq, dlogits=dlogits, hits=self.hits, **tk)

@@ -220,15 +220,21 @@ class EngineV1(Engine):
                          P.g("text_model.embeddings.position_embeddings.weight"), N=N, L=L, tok_sort=tok_sort)
 
     # ------------------------------------------------------------------ tubelet ViT with joint attention
-    def _vit_embed_v1(self, video, keep, B, tubes, tag, crop=None, channel_major=False, mix=None):
+    def _vit_embed_v1(self, video, keep, B, tubes, tag, crop=None, channel_major=False, mix=None, aug=None):
         """tubelet gather over the kept patches (fp32 clips, channel-major ones, or uint8 frames with their crop) -> patch GEMM ->
         token assembly: the tokens [B * S, W] fp32 in front of the first block.  mix: the device table of hip.mix_table() -- Mixup /
-        CutMix applied inside the gather (channel-major fp32 clips and uint8 frames: the layouts the fine-tuning step takes)"""
+        CutMix applied inside the gather (channel-major fp32 clips and uint8 frames: the layouts the fine-tuning step takes).
+        aug: the device table of hip.aug_table() for B samples -- random-resized crop, flip and random erasing inside the gather, uint8
+        source frames [Bs, T, H0, W0, 3] only (every sample names its source clip; crop is not used), the mix applied behind it"""
         a, P, w = self.arch, self.P, self._w
         W, p, tb, n = a["width"], a["patch"], a["tubelet"], keep.shape[2]
         M, Mp = B * (1 + tubes * n), B * tubes * n
         cols = w(tag, ".im2col", "im2col", (Mp, P.conv_k))
-        if mix is not None:
+        if aug is not None:
+            if video.dtype != torch.uint8:
+                raise ValueError("an augmentation table needs uint8 frames [Bs, T, H0, W0, 3] (fp32 clips are augmented by their producer)")
+            K.patch_gather_tube_u8_aug(video, keep, cols, aug, mix, B=B, tubes=tubes, tubelet=tb, n=n, img=a["image"], patch=p)
+        elif mix is not None:
             if video.dtype == torch.uint8:
                 K.patch_gather_tube_u8_mix(video, keep, cols, mix, B=B, tubes=tubes, tubelet=tb, n=n, img=a["image"], patch=p, crop=crop)
             elif channel_major:
@@ -313,10 +319,11 @@ class EngineV1(Engine):
         K.drop_path_table(self.drop_seed, ent, table, site_base=self.FT_SITE_BASE)
         return table
 
-    def finetune_forward(self, video, B, tubes, channel_major=True, crop=None, mix=None):
+    def finetune_forward(self, video, B, tubes, channel_major=True, crop=None, mix=None, aug=None):
         """-> logits [B, C] fp32 (a named tensor of the step).  video on the device: fp32 [B, 3, T, H, W] (channel_major, the
         downstream layout), fp32 [B, T, 3, H, W], or uint8 [B, T, H0, W0, 3] with crop int32 [B, 2] (None: centre).  mix: the
-        device table of hip.mix_table(), Mixup / CutMix inside the gather (engine_for_finetuning.py:58-59)."""
+        device table of hip.mix_table(), Mixup / CutMix inside the gather (engine_for_finetuning.py:58-59).  aug: the device table of
+        hip.aug_table() for B samples over uint8 source frames [Bs, T, H0, W0, 3] (ssv2.py:186-227 inside the gather)."""
         a = self.arch
         W, hv, C, depth = a["width"], a["heads"], a["head_classes"], a["layers"]
         ppf = (a["image"] // a["patch"]) ** 2
@@ -329,7 +336,7 @@ class EngineV1(Engine):
             keep = self.buf[("ft.keep", B, tubes)] = torch.arange(ppf, dtype=torch.int32, device=self.dev).repeat(B, tubes, 1).contiguous()
             self.buf[("ft.cls_rows", B, S)] = (torch.arange(B, device=self.dev) * S).to(torch.int32)
         cls_rows = self.buf[("ft.cls_rows", B, S)]
-        tok = self._vit_embed_v1(video, keep, B, tubes, "ft", crop, channel_major, mix)
+        tok = self._vit_embed_v1(video, keep, B, tubes, "ft", crop, channel_major, mix, aug)
         dp = None if table is None else (table, S)
         x = self._blocks_fwd("video_model.blocks.", _VIT_NAMES, tok, "ft", depth, hv, "gelu", 1e-6,
                              lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hv, S=S, causal=False, head_dim=W // hv),

@@ -947,6 +947,58 @@ def patch_gather_tube_u8_mix(frames, keep, out, mix, *, B, tubes, tubelet, n, im
          "tvts_patch_gather_tube_u8_mix")
 
 
+def check_aug_plan(aug_i, *, Bs, H0, W0, img):
+    """the host-side check of an augmentation plan (the C entry point takes the table as unchecked device data): aug_i integer
+    [B, 16] = (src, top, left, h, w, flip, emode, etop, eleft, eh, ew, key_lo, key_hi, 0, 0, 0) -> int32 numpy array.
+    ValueError for a src outside [0, Bs), a crop that is not 1 <= h, 1 <= w inside the H0 x W0 frame, a flip outside {0, 1}, an
+    emode outside 0-3, an erase box outside the img x img picture, or a nonzero reserved column."""
+    import numpy as np
+    ai = np.asarray(aug_i)
+    if ai.ndim != 2 or ai.shape[0] < 1 or ai.shape[1] != 16 or ai.dtype.kind not in "iu":
+        raise ValueError(f"aug plan: integer aug_i [B, 16], got {ai.dtype} {ai.shape}")
+    ai = ai.astype(np.int64)
+    if ((ai[:, 11:13] < -(1 << 31)) | (ai[:, 11:13] >= (1 << 32))).any():
+        raise ValueError("aug plan: key_lo / key_hi are 32-bit words")
+    ai[:, 11:13] = ai[:, 11:13].astype(np.uint32).astype(np.int32)  # (unsigned words are stored by their bits)
+    if ((ai[:, 0] < 0) | (ai[:, 0] >= Bs)).any():
+        raise ValueError(f"aug plan: src outside [0, {Bs})")
+    for lo, ext, size, ax in ((1, 3, H0, "top / h"), (2, 4, W0, "left / w")):
+        if ((ai[:, ext] < 1) | (ai[:, lo] < 0) | (ai[:, lo] + ai[:, ext] > size)).any():
+            raise ValueError(f"aug plan: crop ({ax}) needs 1 <= extent, 0 <= offset and offset + extent <= {size}")
+    if ((ai[:, 5] < 0) | (ai[:, 5] > 1)).any():
+        raise ValueError("aug plan: flip must be 0 or 1")
+    if ((ai[:, 6] < 0) | (ai[:, 6] > 3)).any():
+        raise ValueError("aug plan: emode must be 0 (none), 1 (const), 2 (rand) or 3 (pixel)")
+    for lo, ext, ax in ((7, 9, "etop / eh"), (8, 10, "eleft / ew")):
+        if ((ai[:, ext] < 0) | (ai[:, lo] < 0) | (ai[:, lo] + ai[:, ext] > img)).any():
+            raise ValueError(f"aug plan: erase box ({ax}) needs 0 <= offset, 0 <= extent and offset + extent <= {img}")
+    if ai[:, 13:].any():
+        raise ValueError("aug plan: columns 13-15 are reserved and must be 0")
+    return np.ascontiguousarray(ai, dtype=np.int32)
+
+
+def aug_table(aug_i, *, Bs, H0, W0, img, device="cuda"):
+    """check_aug_plan, then the upload -> aug_i int32 [B, 16] on the device, as tvts_patch_gather_tube_u8_aug reads it"""
+    return torch.from_numpy(check_aug_plan(aug_i, Bs=Bs, H0=H0, W0=W0, img=img)).to(device)
+
+
+def patch_gather_tube_u8_aug(frames, keep, out, aug, mix=None, *, B, tubes, tubelet, n, img, patch, mean=IMAGENET_MEAN,
+                             std=IMAGENET_STD):
+    """v1 tubelet im2col with the per-sample augmentation fused in: frames uint8 [Bs, T, H0, W0, 3] on the device (any H0, W0 >= 1),
+    aug the device table of aug_table() for B samples (each names its source clip) -- Normalize, random-resized crop (bilinear),
+    flip, random erasing --, mix (optional) the device table of mix_table() for the same B samples, applied behind the erase;
+    keep int32 [B, tubes, n] -> out bf16 [B*tubes*n, 3*tubelet*patch^2]"""
+    assert frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() == 5 and frames.shape[-1] == 3
+    assert frames.shape[1] == tubes * tubelet
+    assert aug.dtype == torch.int32 and aug.is_contiguous() and tuple(aug.shape) == (B, 16), "aug: int32 [B, 16] from aug_table()"
+    assert keep.dtype == torch.int32 and keep.is_contiguous() and tuple(keep.shape) == (B, tubes, n) and out.dtype == torch.bfloat16
+    mi, mf = _mix_dev(mix, B) if mix is not None else (None, None)
+    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    _chk(_lib.load().tvts_patch_gather_tube_u8_aug(_p(frames), frames.shape[0], frames.shape[2], frames.shape[3], _p(keep), _p(aug),
+                                                   _p(mi), _p(mf), B, tubes, tubelet, n, img, patch, m3, s3, _p(out), _ld(out),
+                                                   _stream()), "tvts_patch_gather_tube_u8_aug")
+
+
 def text_embed(ids, emb, pos, x, *, N, L):
     lib = _lib.load()
     assert ids.dtype == torch.int32
