@@ -499,6 +499,22 @@ int tvts_patch_gather_tube_u8_mix(const unsigned char* frames, int H0, int W0, c
 int tvts_patch_gather_tube_u8_aug(const unsigned char* frames, int Bs, int H0, int W0, const int* keep, const int* aug_i,
                                   const int* mix_i, const float* mix_f, int B, int tubes, int tubelet, int n, int img, int patch,
                                   const float* mean3, const float* std3, void* out, int ldo, hipStream_t stream);
+/* The test views of v1/downstream/ssv2.py:132-164 (mode 'test') formed inside the uint8 tubelet gather: every sample is a strided run
+ * of frames of a source clip, cropped at an offset -- `buffer[temporal_start::2, spatial_start:spatial_start + short_side_size]` --
+ * so the test_num_segment x test_num_crop views of a video read ONE uploaded clip.  frames uint8 [Bs, Tsrc, H0, W0, 3]; the views are
+ * a per-sample table in DEVICE memory:
+ *   view_i int32 [B, 8] = (src, t0, tstep, top, left, 0, 0, 0)
+ * frame f (0 <= f < tubes * tubelet) of sample b is frame t0 + f * tstep of source clip src, cropped to [top, top + img) x [left,
+ * left + img); several samples may name one clip.  Every element is bf16((u / 255.0f - mean) / std), the operations and order of
+ * tvts_patch_gather_tube_u8: the bytes equal that kernel's on the host-sliced clip frames[src, t0::tstep][:T, top:top + img,
+ * left:left + img].  No resampling: the short-side Resize in front of the slicing (ssv2.py:147) is the host's, beside decoding.
+ * Returns -22 for a NULL among frames / view_i / keep / out / mean3 / std3, Bs, Tsrc, H0 or W0 <= 0, the shape conditions of
+ * tvts_patch_gather_tube_u8 (H0, W0 >= img among them) and out not 16-byte aligned.  The table is DEVICE data and is not checked: the
+ * caller keeps t0 + (T - 1) * tstep < Tsrc and the crop inside the frame (tvts_amd.hip.view_table does); a src outside [0, Bs) leaves
+ * that sample's rows unwritten and reads nothing. */
+int tvts_patch_gather_tube_u8_view(const unsigned char* frames, int Bs, int Tsrc, int H0, int W0, const int* view_i, const int* keep,
+                                   int B, int tubes, int tubelet, int n, int img, int patch, const float* mean3, const float* std3,
+                                   void* out, int ldo, hipStream_t stream);
 int tvts_text_embed(const int* ids, int ld_ids, int N, int L, const float* emb, const float* pos, int Wt, float* x, int ldx,
                     hipStream_t stream);
 /* ---- PACKED variable-length captions (the forward-only text encoder of the SSv2 multiple-choice models,
@@ -608,6 +624,29 @@ int tvts_soft_ce(const float* logits, long ld, int B, int C, const float* soft_t
  * unwritten.  The result feeds tvts_soft_ce(soft_targets = ...). */
 int tvts_mix_targets(const int* labels, const int* mix_i, const float* mix_f, int B, int C, double smoothing, float* out, long ldo,
                      hipStream_t stream);
+/* ---- evaluation of the fine-tuned classifier (v1/downstream/engine_for_finetuning.py:142-285: validation_one_epoch, final_test, merge) */
+/* The rank of the label's logit among a row's logits: x fp32 [R, C] (ld >= C), labels int32 [R] -> ranks int32 [R],
+ *   rank[r] = #{c : x[r, c] > x[r, label]} + #{c < label : x[r, c] == x[r, label]}
+ * exact integers; ties resolve towards the lower class index, so rank == 0 is np.argmax(x[r]) == label and `rank < k` is the top-k hit of
+ * utils.accuracy (engine_for_finetuning.py:163,210) and of compute_video (:278-280): one launch serves Acc@1 and Acc@5.  Comparisons
+ * with a NaN are false: a NaN logit outranks nothing (and a NaN at the label is outranked by nothing: rank 0).  labels are DEVICE data
+ * and are not checked by the host; a label outside [0, C) reads nothing and gets rank C (a miss at every k). */
+int tvts_class_ranks(const float* x, long ld, int R, int C, const int* labels, int* ranks, hipStream_t stream);
+/* merge / compute_video (:231-285) on the device.  view_logits fp32 [N, V, C] (dense), seen uint8 [N, V] -> sum fp32 [N, C] (lds >= C)
+ * and count int32 [N]: sum[n, c] = the fp32 sum of view_logits[n, v, c] over the views with seen[n, v] != 0, taken in the order
+ * v = 0 .. V - 1 from +0.0f, every add rounded; no atomics: two runs give the same bits.  count[n] = the number of seen views.
+ * compute_video takes the MEAN (:277); a mean and a sum rank identically (one positive divisor per video), so the division is left
+ * out and the result feeds tvts_class_ranks as it is.  A video without a seen view gets a zero row and count 0: the caller leaves it
+ * out of the average, as merge leaves out a video whose compute_video returns None (:265-268). */
+int tvts_view_sum(const float* view_logits, const unsigned char* seen, int N, int V, int C, float* sum, long lds, int* count,
+                  hipStream_t stream);
+/* One batch of view logits into the buffers tvts_view_sum reads: row b of logits fp32 [B, C] (ld >= C) goes to view slot slot[b] =
+ * video * V + view of view_logits fp32 [N * V, C], seen[slot] is set to 1 and video_labels[video] to labels[b].  merge keeps the FIRST
+ * line of a (video, chunk, split) and skips the later ones (:251-252): a row whose slot is seen already, or named by an earlier row of
+ * this batch, is dropped -- decided on the device from `seen`, without a host round trip.  slot / labels are DEVICE data; a slot
+ * outside [0, N * V) drops its row. */
+int tvts_view_store(const float* logits, long ld, int B, int C, const int* slot, const int* labels, int N, int V, float* view_logits,
+                    unsigned char* seen, int* video_labels, hipStream_t stream);
 /* torch.nn.utils.clip_grad_norm_ as v1/downstream/utils.py:366 calls it, without the host round trip: two-stage fixed-order sum of
  * squares over the 1024-element chunks of g whose chunk_group != 255 (partial: fp32 [nchunks] scratch), norm_coef[0] = norm =
  * |grad_scale| sqrt(sum), norm_coef[1] = coef = min(1, max_norm / (norm + 1e-6)), 1 when max_norm <= 0 (clipping off). */

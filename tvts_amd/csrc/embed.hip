@@ -172,6 +172,52 @@ extern "C" int tvts_patch_gather_tube_u8(const unsigned char* frames, int H0, in
     return TVTS_OK;
 }
 
+// The test views of the fine-tuning scripts (v1/downstream/ssv2.py:132-164) inside the same gather: sample b is the frames t0, t0 +
+// tstep, ... of source clip src, cropped at (top, left) -- `buffer[temporal_start::2, spatial_start:spatial_start + short_side_size]`
+// -- read from a per-sample table in device memory, view_i int32 [B, 8] = (src, t0, tstep, top, left, 0, 0, 0).  Only the source
+// address differs from patch_gather_tube_u8_kernel: the element expression is that kernel's, so the bytes equal its bytes on the
+// host-sliced clip.  The views of one video read one uploaded clip.  A src outside [0, Bs) leaves the sample's rows unwritten.
+__global__ __launch_bounds__(256) void patch_gather_tube_u8_view_kernel(const unsigned char* __restrict__ frames, int Bs, int Tsrc, int H0,
+                                                                        int W0, const int* __restrict__ view_i, const int* __restrict__ keep,
+                                                                        int B, int tubes, int tb, int n, int img, int p, float m0,
+                                                                        float m1, float m2, float s0, float s1, float s2,
+                                                                        bf16* __restrict__ out, int ldo) {
+    const int pp = p * p, K = 3 * tb * pp;
+    const int row = blockIdx.x;  // (b, tube, i)
+    const int i = row % n, tu = (row / n) % tubes, b = row / (n * tubes);
+    const int g = img / p;
+    const int pi = keep[(size_t)(b * tubes + tu) * n + i];
+    const int gy = pi / g, gx = pi % g;
+    const int* v = view_i + 8 * (size_t)b;
+    const int src = v[0], t0 = v[1], tstep = v[2], y0 = v[3], x0 = v[4];
+    if ((unsigned)src >= (unsigned)Bs) return;
+    for (int c8 = threadIdx.x * 8; c8 < K; c8 += 256 * 8) {
+        const int ch = c8 / (tb * pp), r1 = c8 % (tb * pp), t = r1 / pp, rem = r1 % pp, py = rem / p, px = rem % p;  // px % 8 == 0
+        const size_t fr = (size_t)src * Tsrc + t0 + (size_t)(tu * tb + t) * tstep;
+        const unsigned char* s = frames + ((fr * H0 + y0 + gy * p + py) * W0 + x0 + gx * p + px) * 3 + ch;
+        const float mean = ch == 0 ? m0 : ch == 1 ? m1 : m2, sd = ch == 0 ? s0 : ch == 1 ? s1 : s2;
+        bf16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float u = (float)s[3 * e];
+            o[e] = (bf16)((u / 255.0f - mean) / sd);
+        }
+        *(bf16x8*)(out + (size_t)row * ldo + c8) = o;
+    }
+}
+extern "C" int tvts_patch_gather_tube_u8_view(const unsigned char* frames, int Bs, int Tsrc, int H0, int W0, const int* view_i,
+                                              const int* keep, int B, int tubes, int tubelet, int n, int img, int patch,
+                                              const float* mean3, const float* std3, void* out, int ldo, hipStream_t stream) {
+    if (!frames || !view_i || !keep || !out || !mean3 || !std3 || Bs <= 0 || Tsrc <= 0 || H0 <= 0 || W0 <= 0 || B <= 0 || tubes <= 0 ||
+        tubelet <= 0 || n <= 0 || patch <= 0 || img <= 0 || img % patch || patch % 8 || H0 < img || W0 < img || ldo % 8 ||
+        ldo < 3 * tubelet * patch * patch || ((size_t)out % 16))
+        return TVTS_EINVAL;
+    hipLaunchKernelGGL(patch_gather_tube_u8_view_kernel, dim3(B * tubes * n), dim3(256), 0, stream, frames, Bs, Tsrc, H0, W0, view_i, keep,
+                       B, tubes, tubelet, n, img, patch, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (bf16*)out, ldo);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
 // Mixup / CutMix of the v1 fine-tuning recipe (v1/downstream/mixup.py:152-200, applied at engine_for_finetuning.py:58-59) fused
 // into the two gathers the fine-tuning step uses.  The step's draw arrives as a per-sample table in device memory:
 //     mix_i int32 [B, 6] = (partner, mode, yl, yh, xl, xh)     mode 0 none, 1 mixup, 2 cutmix; the box in image coordinates

@@ -264,3 +264,97 @@ extern "C" int tvts_grad_sumsq(const float* g, const unsigned char* chunk_group,
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- evaluation: ranks, view merge
+// validation_one_epoch / final_test / merge of v1/downstream/engine_for_finetuning.py:142-285 (tvts_amd/downstream/evaluate_v1.py).
+__device__ __forceinline__ int block_isum_256(int v, int* sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+// One block per row: rank = #{c : x_c > x_label} + #{c < label : x_c == x_label}, integer counts (exact at any C).  `rank < k` is the
+// top-k hit with ties resolved towards the lower class index, so rank 0 is np.argmax == label.  Every comparison with a NaN is false.
+__global__ __launch_bounds__(256) void class_ranks_kernel(const float* __restrict__ x, long ld, int C, const int* __restrict__ labels,
+                                                          int* __restrict__ ranks) {
+    __shared__ int sh[4];
+    const int r = blockIdx.x, lab = labels[r];
+    if ((unsigned)lab >= (unsigned)C) {  // (uniform per block) nothing is read for a label outside the row
+        if (threadIdx.x == 0) ranks[r] = C;
+        return;
+    }
+    const float* xr = x + (long)r * ld;
+    const float xl = xr[lab];
+    int cnt = 0;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const float v = xr[c];
+        cnt += (v > xl) || (v == xl && c < lab);
+    }
+    cnt = block_isum_256(cnt, sh);
+    if (threadIdx.x == 0) ranks[r] = cnt;
+}
+extern "C" int tvts_class_ranks(const float* x, long ld, int R, int C, const int* labels, int* ranks, hipStream_t stream) {
+    if (!x || !labels || !ranks || R <= 0 || C <= 0 || ld < C) return TVTS_EINVAL;
+    hipLaunchKernelGGL(class_ranks_kernel, dim3(R), dim3(256), 0, stream, x, ld, C, labels, ranks);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
+// compute_video's `np.mean(feat, axis=0)` (:277) as a SUM: one thread per (video, class) adds the seen views in the order v = 0 .. V - 1
+// from +0.0f, every add rounded -- the order is the definition, so the bits repeat.  The division by the count is left out: it does not
+// change the order of a video's classes, which is all that argmax and top-5 membership read.
+__global__ __launch_bounds__(256) void view_sum_kernel(const float* __restrict__ vl, const unsigned char* __restrict__ seen, int N, int V,
+                                                       int C, float* __restrict__ sum, long lds, int* __restrict__ count) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)N * C) return;
+    const int nv = (int)(idx / C), c = (int)(idx % C);
+    float s = 0.0f;
+    int k = 0;
+    for (int v = 0; v < V; ++v)
+        if (seen[(size_t)nv * V + v]) {
+            s = __fadd_rn(s, vl[((size_t)nv * V + v) * C + c]);
+            ++k;
+        }
+    sum[(long)nv * lds + c] = s;
+    if (c == 0) count[nv] = k;
+}
+extern "C" int tvts_view_sum(const float* view_logits, const unsigned char* seen, int N, int V, int C, float* sum, long lds, int* count,
+                             hipStream_t stream) {
+    if (!view_logits || !seen || !sum || !count || N <= 0 || V <= 0 || C <= 0 || lds < C || (long)N * V >= (1L << 31)) return TVTS_EINVAL;
+    const long n = (long)N * C;
+    if ((n + 255) / 256 >= (1L << 31)) return TVTS_EINVAL;
+    hipLaunchKernelGGL(view_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, view_logits, seen, N, V, C, sum, lds, count);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
+// One block per row of a batch's logits: the row lands in its view slot unless the slot is seen already or an earlier row of the batch
+// names it (merge keeps the first line of a (video, chunk, split), :251-252).  Every thread reads seen[slot] in front of the barrier
+// and thread 0 sets it behind it; a later row with the same slot is dropped by the earlier-row rule whichever value it reads.
+// Rows of one video carry one label: whichever of them writes video_labels[video] last writes the same value.
+__global__ __launch_bounds__(256) void view_store_kernel(const float* __restrict__ logits, long ld, int C, const int* __restrict__ slot,
+                                                         const int* __restrict__ labels, int nslots, int V, float* __restrict__ vl,
+                                                         unsigned char* __restrict__ seen, int* __restrict__ video_labels) {
+    const int b = blockIdx.x, s = slot[b];
+    if ((unsigned)s >= (unsigned)nslots) return;  // (uniform per block)
+    int dup = seen[s] != 0;
+    for (int j = threadIdx.x; j < b; j += 256) dup |= slot[j] == s;
+    if (__syncthreads_or(dup)) return;
+    for (int c = threadIdx.x; c < C; c += 256) vl[(size_t)s * C + c] = logits[(long)b * ld + c];
+    if (threadIdx.x == 0) {
+        seen[s] = 1;
+        video_labels[s / V] = labels[b];
+    }
+}
+extern "C" int tvts_view_store(const float* logits, long ld, int B, int C, const int* slot, const int* labels, int N, int V,
+                               float* view_logits, unsigned char* seen, int* video_labels, hipStream_t stream) {
+    if (!logits || !slot || !labels || !view_logits || !seen || !video_labels || B <= 0 || C <= 0 || ld < C || N <= 0 || V <= 0 ||
+        (long)N * V >= (1L << 31))
+        return TVTS_EINVAL;
+    hipLaunchKernelGGL(view_store_kernel, dim3(B), dim3(256), 0, stream, logits, ld, C, slot, labels, N * V, V, view_logits, seen,
+                       video_labels);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}

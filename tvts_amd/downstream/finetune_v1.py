@@ -43,6 +43,8 @@ OUT OF SCOPE (not built here): RandAugment itself (uint8 PIL frames at source si
 ``motion_shift`` (random_resized_crop_with_shift), the reference's torch noise stream,
 ``FastCollateMixup`` (the uint8-rounding variant: the reference scripts do not use it), ``ModelEma``, the fp16 loss scaler (the engine is bf16 with fp32 accumulation: there is no loss scale), DeepSpeed, the multi-GPU
 gradient exchange for this step (the backward keeps its Engine._ready calls so that one can hook in), and hipGraph capture of it.
+The scripts' other half -- validation_one_epoch after every epoch, final_test over the test views and merge
+(engine_for_finetuning.py:142-285) -- is tvts_amd/downstream/evaluate_v1.py.
 """
 from __future__ import annotations
 

@@ -150,12 +150,35 @@ class VisionTransformer(nn.Module):
         feat, _ = _encode_video_v1(self.engine, x, None, channel_major=True, project=False)
         return feat.clone()
 
-    @torch.no_grad()
-    def forward(self, x):
-        feat = self.forward_features(x)
+    def _head(self, feat):
         if self.num_classes == 0:
             return feat
         B, W, C = feat.shape[0], self.embed_dim, self.num_classes
         logits = torch.empty(B, C, dtype=torch.float32, device=feat.device)
         K.gemm_small(feat, self.store.p("head.weight"), logits, M=B, N=C, K=W, sa=(W, 1), sb=(1, W), bias=self.store.p("head.bias"))
         return logits
+
+    @torch.no_grad()
+    def forward(self, x):
+        return self._head(self.forward_features(x))
+
+    @torch.no_grad()
+    def forward_views(self, frames, view_i, T):
+        """forward() over test views cut from uint8 SOURCE clips on the device (v1/downstream/ssv2.py:132-164): frames uint8
+        [Bs, Tsrc, H0, W0, 3], view_i integer [B, 8] = (src, t0, tstep, top, left, 0, 0, 0) on the host (hip.view_table checks it), T the
+        frames per view.  Sample b is frames[src, t0::tstep][:T, top:top + img, left:left + img], normalised inside the gather: the
+        result is forward() on those B uint8 clips, bit for bit, from one upload of the source clips.  -> [B, num_classes] (or the
+        features [B, embed_dim] without a head).  tvts_amd.downstream.evaluate_v1.final_test(views=...) is the caller."""
+        a, dev = self.arch, self.engine.dev
+        if frames.dim() != 5 or frames.dtype != torch.uint8 or frames.shape[-1] != 3:
+            raise ValueError(f"frames: uint8 source clips [Bs, Tsrc, H0, W0, 3], got {frames.dtype} {tuple(frames.shape)}")
+        tb = a["tubelet"]
+        if T < 1 or T % tb or T > a["num_frames"]:
+            raise ValueError(f"views of {T} frames: need a multiple of {tb}, at most {a['num_frames']}")
+        v = frames.to(dev).contiguous()
+        table = K.view_table(view_i, Bs=v.shape[0], Tsrc=v.shape[1], H0=v.shape[2], W0=v.shape[3], T=T, img=a["image"], device=dev)
+        B, tubes, ppf = table.shape[0], T // tb, self.patches_per_frame
+        keep = torch.arange(ppf, dtype=torch.int32, device=dev).repeat(B, tubes, 1).contiguous()
+        self._fresh_shadows()
+        feat, _ = self.engine.encode_video(v, keep, B, tubes, project=False, view=table)
+        return self._head(feat.clone())

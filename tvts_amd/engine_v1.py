@@ -220,17 +220,23 @@ class EngineV1(Engine):
                          P.g("text_model.embeddings.position_embeddings.weight"), N=N, L=L, tok_sort=tok_sort)
 
     # ------------------------------------------------------------------ tubelet ViT with joint attention
-    def _vit_embed_v1(self, video, keep, B, tubes, tag, crop=None, channel_major=False, mix=None, aug=None):
+    def _vit_embed_v1(self, video, keep, B, tubes, tag, crop=None, channel_major=False, mix=None, aug=None, view=None):
         """tubelet gather over the kept patches (fp32 clips, channel-major ones, or uint8 frames with their crop) -> patch GEMM ->
         token assembly: the tokens [B * S, W] fp32 in front of the first block.  mix: the device table of hip.mix_table() -- Mixup /
         CutMix applied inside the gather (channel-major fp32 clips and uint8 frames: the layouts the fine-tuning step takes).
         aug: the device table of hip.aug_table() for B samples -- random-resized crop, flip and random erasing inside the gather, uint8
-        source frames [Bs, T, H0, W0, 3] only (every sample names its source clip; crop is not used), the mix applied behind it"""
+        source frames [Bs, T, H0, W0, 3] only (every sample names its source clip; crop is not used), the mix applied behind it.
+        view: the device table of hip.view_table() for B samples -- the test views of ssv2.py:132-164 (a strided run of frames of a source
+        clip, cropped at an offset) formed inside the gather, uint8 source clips [Bs, Tsrc, H0, W0, 3] only; no crop, mix or aug with it"""
         a, P, w = self.arch, self.P, self._w
         W, p, tb, n = a["width"], a["patch"], a["tubelet"], keep.shape[2]
         M, Mp = B * (1 + tubes * n), B * tubes * n
         cols = w(tag, ".im2col", "im2col", (Mp, P.conv_k))
-        if aug is not None:
+        if view is not None:
+            if video.dtype != torch.uint8 or crop is not None or mix is not None or aug is not None:
+                raise ValueError("a view table needs uint8 source clips [Bs, Tsrc, H0, W0, 3] and takes no crop, mix or aug beside it")
+            K.patch_gather_tube_u8_view(video, keep, cols, view, B=B, tubes=tubes, tubelet=tb, n=n, img=a["image"], patch=p)
+        elif aug is not None:
             if video.dtype != torch.uint8:
                 raise ValueError("an augmentation table needs uint8 frames [Bs, T, H0, W0, 3] (fp32 clips are augmented by their producer)")
             K.patch_gather_tube_u8_aug(video, keep, cols, aug, mix, B=B, tubes=tubes, tubelet=tb, n=n, img=a["image"], patch=p)
@@ -449,17 +455,19 @@ class EngineV1(Engine):
     # inference call, and an encoder call between two training steps must not shift the step's mask sequence.
     # (_advance_drop_seed is text_forward_v1's alone, and with tag None _pln_fwd / _text_tower_v1 do not look at _drop_active.)
     # Base-class refusal (_inf_check) stays for encode_text_packed: there is no packed DistilBERT pass.
-    def encode_video(self, video, keep, B, tubes, crop=None, channel_major=False, project=True):
+    def encode_video(self, video, keep, B, tubes, crop=None, channel_major=False, project=True, view=None):
         """-> (feat [B, W] fp32 = the normed CLS token, emb [B, E] = vid_proj(feat)).  Both are encoder workspaces: the next
         encoder call overwrites them.  project=False returns emb = None (a store without vid_proj: the downstream class).
         video, on the device: fp32 [B, T, 3, H, W]; fp32 [B, 3, T, H, W] with channel_major (the layout of the v1 downstream
         classes); or uint8 [B, T, H0, W0, 3].  keep: int32 [B, tubes, n].
         crop (uint8 only): int32 [B, 2] (top, left) inside the frame, None = centre crop.  It is an argument of the engine alone:
-        TVTS.encode_video and the downstream class always take the centre crop."""
+        TVTS.encode_video and the downstream class always take the centre crop.
+        view (uint8 only): the device table of hip.view_table() for B samples over source clips [Bs, Tsrc, H0, W0, 3] -- B test views of
+        tubes * tubelet frames each, formed inside the gather (downstream/evaluate_v1.py); None: the path above, launch for launch."""
         a, f32 = self.arch, torch.float32
         W, E, hv = a["width"], a["embed"], a["heads"]
         S = 1 + tubes * keep.shape[2]
-        tok = self._vit_embed_v1(video, keep, B, tubes, None, crop, channel_major)
+        tok = self._vit_embed_v1(video, keep, B, tubes, None, crop, channel_major, view=view)
         x_c = self._blocks_fwd(
             "video_model.blocks.", _VIT_NAMES, tok, None, a["layers"], hv, "gelu", 1e-6,
             lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hv, S=S, causal=False, head_dim=W // hv),

@@ -999,6 +999,49 @@ def patch_gather_tube_u8_aug(frames, keep, out, aug, mix=None, *, B, tubes, tube
                                                    _stream()), "tvts_patch_gather_tube_u8_aug")
 
 
+def check_view_plan(view_i, *, Bs, Tsrc, H0, W0, T, img):
+    """the host-side check of a test-view table (the C entry point takes it as unchecked device data): view_i integer [B, 8] =
+    (src, t0, tstep, top, left, 0, 0, 0) -> int32 numpy array.  ValueError for a src outside [0, Bs), t0 < 0, tstep < 1, a last frame
+    t0 + (T - 1) * tstep outside the Tsrc frames of the clip, a crop that leaves the H0 x W0 frame, or a nonzero reserved column."""
+    import numpy as np
+    vi = np.asarray(view_i)
+    if vi.ndim != 2 or vi.shape[0] < 1 or vi.shape[1] != 8 or vi.dtype.kind not in "iu":
+        raise ValueError(f"view plan: integer view_i [B, 8], got {vi.dtype} {vi.shape}")
+    if T < 1 or H0 < img or W0 < img:
+        raise ValueError(f"view plan: T >= 1 and source frames of at least {img} x {img}, got T = {T}, {H0} x {W0}")
+    vi = vi.astype(np.int64)
+    if ((vi[:, 0] < 0) | (vi[:, 0] >= Bs)).any():
+        raise ValueError(f"view plan: src outside [0, {Bs})")
+    if (vi[:, 1] < 0).any() or (vi[:, 2] < 1).any():
+        raise ValueError("view plan: t0 >= 0 and tstep >= 1")
+    if (vi[:, 1] + (T - 1) * vi[:, 2] >= Tsrc).any():
+        raise ValueError(f"view plan: t0 + (T - 1) * tstep must stay below Tsrc = {Tsrc} (T = {T})")
+    for col, size, ax in ((3, H0, "top"), (4, W0, "left")):
+        if ((vi[:, col] < 0) | (vi[:, col] + img > size)).any():
+            raise ValueError(f"view plan: crop needs 0 <= {ax} and {ax} + {img} <= {size}")
+    if vi[:, 5:].any():
+        raise ValueError("view plan: columns 5-7 are reserved and must be 0")
+    return np.ascontiguousarray(vi, dtype=np.int32)
+
+
+def view_table(view_i, *, Bs, Tsrc, H0, W0, T, img, device="cuda"):
+    """check_view_plan, then the upload -> view_i int32 [B, 8] on the device, as tvts_patch_gather_tube_u8_view reads it"""
+    return torch.from_numpy(check_view_plan(view_i, Bs=Bs, Tsrc=Tsrc, H0=H0, W0=W0, T=T, img=img)).to(device)
+
+
+def patch_gather_tube_u8_view(frames, keep, out, view, *, B, tubes, tubelet, n, img, patch, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """v1 tubelet im2col of the test views of uint8 source clips: frames uint8 [Bs, Tsrc, H0, W0, 3] on the device, view the device
+    table of view_table() for B samples (each names its source clip, its first frame, the frame stride and the crop offset);
+    keep int32 [B, tubes, n] -> out bf16 [B*tubes*n, 3*tubelet*patch^2], the bytes of patch_gather_tube_u8 on the host-sliced clips"""
+    assert frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() == 5 and frames.shape[-1] == 3
+    assert view.dtype == torch.int32 and view.is_contiguous() and tuple(view.shape) == (B, 8), "view: int32 [B, 8] from view_table()"
+    assert keep.dtype == torch.int32 and keep.is_contiguous() and tuple(keep.shape) == (B, tubes, n) and out.dtype == torch.bfloat16
+    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    _chk(_lib.load().tvts_patch_gather_tube_u8_view(_p(frames), frames.shape[0], frames.shape[1], frames.shape[2], frames.shape[3],
+                                                    _p(view), _p(keep), B, tubes, tubelet, n, img, patch, m3, s3, _p(out), _ld(out),
+                                                    _stream()), "tvts_patch_gather_tube_u8_view")
+
+
 def text_embed(ids, emb, pos, x, *, N, L):
     lib = _lib.load()
     assert ids.dtype == torch.int32
@@ -1249,6 +1292,46 @@ def mix_targets(labels, mix, out, *, smoothing=0.0):
     assert labels.dtype == torch.int32 and labels.numel() == B and labels.is_contiguous() and out.dtype == torch.float32
     _chk(_lib.load().tvts_mix_targets(_p(labels), _p(mi), _p(mf), B, C, float(smoothing), _p(out), _ld(out), _stream()),
          "tvts_mix_targets")
+
+
+def class_ranks(x, labels, ranks=None):
+    """ranks int32 [R] of the label's logit in every row of x fp32 [R, C] (row stride >= C): the number of classes that score
+    higher, plus the equal ones with a lower index -- `ranks < k` is the top-k hit, `ranks == 0` is argmax == label.  labels int32
+    [R] on the device; the caller has checked them on the host (a label outside [0, C) gets rank C)."""
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    R, C = x.shape
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == R
+    if ranks is None:
+        ranks = torch.empty(R, dtype=torch.int32, device=x.device)
+    assert ranks.dtype == torch.int32 and ranks.is_contiguous() and ranks.numel() >= R
+    _chk(_lib.load().tvts_class_ranks(_p(x), x.stride(0), R, C, _p(labels), _p(ranks), _stream()), "tvts_class_ranks")
+    return ranks
+
+
+def view_sum(view_logits, seen, out, count):
+    """out fp32 [N, C] = the sum of the seen views of view_logits fp32 [N, V, C] in the order v = 0 .. V - 1 (seen uint8 [N, V]),
+    count int32 [N] = the number of seen views; a video without one gets a zero row"""
+    N, V, C = view_logits.shape
+    assert view_logits.dtype == torch.float32 and view_logits.is_contiguous()
+    assert seen.dtype == torch.uint8 and seen.is_contiguous() and tuple(seen.shape) == (N, V)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (N, C) and out.stride(1) == 1
+    assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() == N
+    _chk(_lib.load().tvts_view_sum(_p(view_logits), _p(seen), N, V, C, _p(out), out.stride(0), _p(count), _stream()), "tvts_view_sum")
+
+
+def view_store(logits, slot, labels, view_logits, seen, video_labels):
+    """the rows of logits fp32 [B, C] into their view slots (slot int32 [B] = video * V + view) of view_logits fp32 [N, V, C]; a
+    slot that is seen already, or named by an earlier row of the batch, keeps what it has.  labels int32 [B] -> video_labels [N]."""
+    N, V, C = view_logits.shape
+    B = logits.shape[0]
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] == C and logits.stride(1) == 1
+    assert view_logits.dtype == torch.float32 and view_logits.is_contiguous()
+    assert seen.dtype == torch.uint8 and seen.is_contiguous() and tuple(seen.shape) == (N, V)
+    for t in (slot, labels):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == B
+    assert video_labels.dtype == torch.int32 and video_labels.is_contiguous() and video_labels.numel() == N
+    _chk(_lib.load().tvts_view_store(_p(logits), logits.stride(0), B, C, _p(slot), _p(labels), N, V, _p(view_logits), _p(seen),
+                                     _p(video_labels), _stream()), "tvts_view_store")
 
 
 def grad_sumsq(g, chunk_group, partial, norm_coef, *, max_norm=0.0, grad_scale=1.0):
