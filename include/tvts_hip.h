@@ -196,7 +196,13 @@ int tvts_rows_linear_fp8(const void* A8, long lda, const float* row_scale, const
  * ld >= N, X / out not null, workspace_elems >= 0, else -22 */
 int tvts_colsum_bf16(const void* X, int ld, int M, int N, float* out, float* workspace, long workspace_elems, hipStream_t stream);
 
-/* ---- LayerNorm (norm.hip): video_encoder_ViT_B_16.py:79-85 (eps 1e-5), sort_transformer.py:99 (eps 1e-6) */
+/* ---- LayerNorm (norm.hip): video_encoder_ViT_B_16.py:79-85 (eps 1e-5), sort_transformer.py:99 (eps 1e-6)
+ * Refused with -22, by every entry point below, before anything is launched: M <= 0; W <= 0, W % 4, W > 1280; a leading dimension of
+ * a matrix that is given (x, y, q8, dy, res1, res2, dx, dx_bf16) that is not a multiple of 4 or is shorter than the row (ld < W: rows
+ * would overlap); an absent optional matrix passes ld = 0.  x, gamma, beta must not be NULL, nor dy, mean, rstd in the backward forms
+ * (the forward's mean / rstd outputs are optional); tvts_layernorm_fwd needs y.  dgamma and dbeta are given together or not at all;
+ * workspace_elems >= 0.  bf16 x takes no fp32 y, no fp32 dy and no fp32 res1; q8 needs row_scale or tscale; res2 needs res1 in the
+ * fp8 and cls backward forms; cls_period > 0 and M % cls_period == 0. */
 int tvts_layernorm_fwd(const void* x, int ldx, int x_bf16, const int* rows, const float* gamma, const float* beta, float eps, int M,
                        int W, void* y, int ldy, int y_f32, float* mean, float* rstd, hipStream_t stream);
 /* the same, additionally writing the bf16 output as OCP e4m3 bytes q8[M, W] (ldq bytes per row) with one scale per row
@@ -232,7 +238,9 @@ int tvts_layernorm_fwd_cls(const void* x, int ldx, const float* cls_x, int cls_p
 /* Backward on the hybrid stream: bf16 dy, bf16 x, every row; res1_bf16 (optional) the bf16 stream gradient, res2_bf16 (optional, with
  * res1) a bf16 side branch; dx_bf16 required.  Rows r % cls_period == 0: input from cls_x (optional), stream gradient from cls_res1
  * (optional, fp32 [M / cls_period, W]) instead of res1's row, result ALSO to cls_dx (optional, fp32) -- the CLS token's gradient chain
- * never passes through a bf16 rounding.  q8 .. amax_acc optional, as in tvts_layernorm_bwd_fp8. */
+ * never passes through a bf16 rounding.  q8 .. amax_acc optional, as in tvts_layernorm_bwd_fp8; amax_acc receives the maximum of the
+ * dx_bf16 that is left behind: what the plain launch forms on the CLS rows from the stream's own rows, and the CLS launch replaces, is
+ * kept out of it. */
 int tvts_layernorm_bwd_cls(const void* dy, int lddy, const void* x, int ldx, const float* cls_x, const float* cls_res1, float* cls_dx,
                            int cls_period, const float* mean, const float* rstd, const float* gamma, const void* res1_bf16, int ldr,
                            const void* res2_bf16, int ldr2, int M, int W, void* dx_bf16, int lddxb, void* q8, int ldq, float* row_scale,

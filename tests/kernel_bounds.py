@@ -390,6 +390,32 @@ def ln_bwd_check(dy, x, mean, rstd, gamma, *, dx=None, dx_bf16=None, res1=None, 
     return worst
 
 
+def ln_cols_check(dy, x, mean, rstd, dgamma, dbeta, dgamma0, dbeta0, *, what):
+    """dgamma / dbeta of a LayerNorm backward over a FEW THOUSAND rows at most, every column within a derived summation bound
+    (ln_bwd_check's col_tol is calibrated for 150 720 rows, where a worst-case bound exceeds the sums themselves).
+
+    dbeta[c] = dbeta0[c] + sum_r dy[r, c]: the addends are exact, so sum_bound with n = M addends in any order (a wave's running
+    sum, four waves through LDS, per-block partials or atomics, the reduce kernel's groups, `+=`).
+    dgamma[c] = dgamma0[c] + sum_r dy[r, c] xhat[r, c]: each addend is fl(dy fl(xhat)) with xhat formed as in ln_bwd_check
+    (|err| <= e_x = 3u (|xhat| + |x| rstd)), i.e. off by at most |dy| e_x + u |dy xhat| before it is summed:
+
+        |got - ref| <= gamma_{M+8} (sum |dy xhat| + |dgamma0|) + (1 + gamma_{M+8}) sum |dy| e_x.
+
+    -> {"dgamma": worst |err| / bound, "dbeta": ...}"""
+    M = x.shape[0]
+    xc, dyc = x.double(), dy.double()
+    mu, rs = mean[:M].double()[:, None], rstd[:M].double()[:, None]
+    xh = (xc - mu) * rs
+    e_x = 3 * U32 * (xh.abs() + xc.abs() * rs)
+    gk = _gamma(M + 8)
+    ref_g = (dyc * xh).sum(0) + dgamma0.double()
+    bound_g = gk * ((dyc * xh).abs().sum(0) + dgamma0.double().abs()) + (1 + gk) * (dyc.abs() * e_x).sum(0) + 1e-45
+    ref_b = dyc.sum(0) + dbeta0.double()
+    bound_b = sum_bound(dyc.abs().sum(0), M, init=dbeta0)
+    return {"dgamma": assert_within(dgamma, ref_g, bound_g, f"{what}: dgamma (per column)"),
+            "dbeta": assert_within(dbeta, ref_b, bound_b, f"{what}: dbeta (per column)")}
+
+
 # ------------------------------------------------------------------------------------------------ attention references
 # per (row, head) relative L2 of the error beyond the bf16 rounding of each output value (rows_rel with out_dtype), calibrated on
 # the MI355X.  Worst measured over the short-sequence and divided tests: out 2.25e-3, dq 3.81e-3, dk 3.24e-3, dv 3.15e-3; each tol

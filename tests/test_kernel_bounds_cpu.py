@@ -726,3 +726,55 @@ def test_edge_mistakes_are_rejected_at_every_edge_shape():
         ref, bound = p.double().sum(0) + cs0.double(), KB.sum_bound(p.double().abs().sum(0), M, init=cs0)
         fails(lambda: KB.assert_within(cs0 + p[:M - 1].float().sum(0), ref, bound, "colsum"), "outside the bound")
         fails(lambda: KB.assert_within(cs0 + p.float().sum(0) + p[M - 1].float(), ref, bound, "colsum"), "outside the bound")  # ... or the tail row twice
+
+
+# ------------------------------------------------------------------------------------------------ LayerNorm at width and row edges
+import ln_cases as LC  # noqa: E402
+
+LN_EDGE_W = (260, 1028)  # a 4-column tail behind one full column group and behind four (IT = 2, 5)
+
+
+def test_layernorm_fp32_emulation_passes_the_edge_checks():
+    """the checks of tests/test_layernorm_edges_gpu.py (ln_cases.fwd_case / bwd_case: ln_fwd_check, ln_bwd_check, the derived
+    column bound ln_cols_check, the e4m3 references, guards, poison outside the listed rows) run on an fp32 torch emulation of
+    the kernels -- two-pass mean / variance, fp32 accumulation -- with the special rows, and pass with every ratio <= 1"""
+    K = LC.Emulation()
+    for W in LN_EDGE_W:
+        for name in ("f32_bf16", "f32_f32", "f32_q8rows", "f32_q8tensor", "bf16_4col", "cls_4col_q8rows"):
+            f = LC.FWD_BY_NAME[name]
+            assert LC.fwd_case(K, "cpu", f, 7, W, 4 if f["x"] == LC.F32 else 0, 0, seed=W, period=7 if f["cls"] else 0) <= 1.0
+        assert LC.fwd_case(K, "cpu", LC.FWD_BY_NAME["f32_f32"], 6, W, 0, 4, seed=W, gathered=True, extra=3) <= 1.0
+        assert LC.fwd_case(K, "cpu", LC.FWD_BY_NAME["f32_q8rows"], 5, W, 0, 4, seed=W, zero_beta=True) <= 1.0
+        for f in LC.FORMS + [LC.FORM_F32_RES12, LC.FORM_ALL_BF16]:
+            w, cols = LC.bwd_case(K, "cpu", f, 10, W, 0, 4, seed=W + 1, period=5 if f["cls"] else 0)
+            assert w <= 1.0 and max(cols.values()) <= 1.0, (f["name"], w, cols)
+        for M in LC.M_REDUCE[:4]:
+            w, cols = LC.bwd_case(K, "cpu", LC.FORM_F32_RES12, M, 68, 0, 0, seed=M, workspace=False)
+            assert w <= 1.0 and max(cols.values()) <= 1.0, (M, w, cols)
+
+
+def test_layernorm_edge_mistakes_are_rejected():
+    """what a kernel gets wrong at a width or row edge, built into the emulation: each is rejected by the check that is there for it,
+    at both widths"""
+    fwd, fwd_q, fwd_t = (LC.FWD_BY_NAME[n] for n in ("f32_bf16", "f32_q8rows", "f32_q8tensor"))
+    bwd = LC.FORM_F32_RES12
+    bwd_q, bwd_t = (LC.BWD_BY_NAME[f"bwd_fp8-x32-dy16-r1no-r2no-both-q8{m}"] for m in ("rows", "tensor"))
+    for W in LN_EDGE_W:
+        def f(form, mistake, **kw):
+            return lambda: LC.fwd_case(LC.Emulation(mistake), "cpu", form, 7, W, 4, 0, seed=W, **kw)
+
+        def b(form, mistake, **kw):
+            return lambda: LC.bwd_case(LC.Emulation(mistake), "cpu", form, 7, W, 4, 0, seed=W, **kw)
+
+        f(fwd, None)(); b(bwd, None)(); b(bwd_q, None)()                          # (the same calls without a mistake pass)
+        fails(f(fwd, "var_tail"), "outside the bound", "(row 0")                   # the variance without the last four columns
+        fails(f(fwd_q, "var_tail"), "outside the bound")
+        fails(b(bwd, "c12_tail"), "dx", "outside the bound", "(row 0")             # c1 / c2 without them
+        fails(f(fwd_q, "amax_tail"), "row scales")                                 # the amax without the tail group
+        fails(f(fwd_t, "amax_tail"), "amax")
+        fails(b(bwd_q, "amax_tail"), "row scales")
+        fails(b(bwd_t, "amax_tail"), "amax")
+        fails(b(bwd, "dgamma_tail"), "dgamma (per column)", f"(row {W - 4}, col 0)")   # dgamma missing the last block's tail
+        fails(f(fwd, "row_late"), "outside the bound", "non-finite", "(row 6")     # a row's result one row late
+        fails(f(fwd, "row_late", extra=2), "outside the bound", "(row 6")          # ... into a row past M (poison, not a guard)
+        fails(b(bwd, "row_late"), "outside the bound", "(row 6")

@@ -506,7 +506,8 @@ def test_layernorm_on_the_hybrid_stream(K, W, period, q8):
     m0, r0 = torch.empty_like(mean), torch.empty_like(rstd)
     K.layernorm_fwd(x_dev, g, b, 1e-5, y0, m0, r0)
     other = torch.ones(M, dtype=torch.bool); other[cls_rows] = False
-    if not q8 and W % 8 == 0:  # (the fused-copy form is the 4-column kernel: same values, another summation order)
+    if not q8 and W % 8 == 0:  # (bits only without the e4m3 copy; with it these widths run the 8-column Q8 kernel, ln_fwd8_kernel<NP, true, true>,
+        # not a 4-column one: held to the gate below here, per element in tests/test_layernorm_edges_gpu.py)
         assert torch.equal(y[other.to(DEV)].view(torch.int16), y0[other.to(DEV)].view(torch.int16))
     else:
         assert float((y[other.to(DEV)].float() - y0[other.to(DEV)].float()).abs().max()) <= 2.0 ** -7 * float(y0.float().abs().max())

@@ -332,12 +332,20 @@ static void launch_ln_fwd8_q8(hipStream_t stream, const bf16* x, int ldx, const 
 #undef LN8_CASE
 }
 static inline bool ln8_ok(int W, int ld_a, int ld_b) { return W % 8 == 0 && W <= 1536 && ld_a % 8 == 0 && ld_b % 8 == 0; }
+// host validation shared by the entry points: a matrix that is given has rows of at least W elements (a shorter pitch makes rows overlap:
+// silently wrong results, or accesses past the buffer) in whole 4-element groups; dgamma and dbeta come together or not at all (the
+// kernel accumulates both behind one test)
+static inline bool ln_ld_bad(const void* p, int ld, int W) { return p && (ld % 4 || ld < W); }
+static inline bool ln_grads_bad(const float* dgamma, const float* dbeta, long workspace_elems) {
+    return (dgamma == nullptr) != (dbeta == nullptr) || workspace_elems < 0;
+}
 
 // LayerNorm forward that also emits the e4m3 copy of its bf16 output with per-row scales (see Q8 above)
 extern "C" int tvts_layernorm_fwd_fp8(const void* x, int ldx, int x_bf16, const int* rows, const float* gamma, const float* beta,
                                       float eps, int M, int W, void* y, int ldy, void* q8, int ldq, float* row_scale,
                                       const float* tscale, float* amax_acc, float* mean, float* rstd, hipStream_t stream) {
     if (M <= 0 || W <= 0 || W % 4 || W > 256 * LN_MAX_IT || ldx % 4 || ldy % 4 || ldq % 4 || !q8 || (!row_scale && !tscale)) return TVTS_EINVAL;
+    if (!x || !gamma || !beta || ldx < W || ln_ld_bad(y, ldy, W) || ldq < W) return TVTS_EINVAL;
     if (!y && !(x_bf16 && ln8_ok(W, ldx, 8) && ldq % 8 == 0)) return TVTS_EINVAL;  // e4m3-only: the 8-column bf16-row form
     int blocks = ceil_div(M, 4);
     if (blocks > 2048) blocks = 2048;
@@ -356,6 +364,7 @@ extern "C" int tvts_layernorm_fwd(const void* x, int ldx, int x_bf16, const int*
                                   float eps, int M, int W, void* y, int ldy, int y_f32, float* mean, float* rstd,
                                   hipStream_t stream) {
     if (M <= 0 || W <= 0 || W % 4 || W > 256 * LN_MAX_IT || ldx % 4 || ldy % 4 || (x_bf16 && y_f32)) return TVTS_EINVAL;
+    if (!x || !gamma || !beta || !y || ldx < W || ldy < W) return TVTS_EINVAL;
     int blocks = ceil_div(M, 4);
     if (blocks > 2048) blocks = 2048;  // 8 blocks x 4 waves per CU, two rows in flight per wave
     const int it = ceil_div(W, 256);
@@ -376,6 +385,7 @@ extern "C" int tvts_layernorm_fwd_cls(const void* x, int ldx, const float* cls_x
                                       const float* tscale, float* amax_acc, float* mean, float* rstd, hipStream_t stream) {
     if (M <= 0 || W <= 0 || W % 4 || W > 256 * LN_MAX_IT || ldx % 4 || ldy % 4 || !cls_x || cls_period <= 0 || M % cls_period) return TVTS_EINVAL;
     if (q8 && (ldq % 4 || (!row_scale && !tscale))) return TVTS_EINVAL;
+    if (!x || !gamma || !beta || ldx < W || ln_ld_bad(y, ldy, W) || ln_ld_bad(q8, ldq, W)) return TVTS_EINVAL;
     if (!y && !(q8 && ln8_ok(W, ldx, 8) && ldq % 8 == 0)) return TVTS_EINVAL;  // e4m3-only: the 8-column form
     int blocks = ceil_div(M, 4);
     if (blocks > 2048) blocks = 2048;
@@ -540,7 +550,10 @@ __global__ __launch_bounds__(256, (ln_bwd_per_cu<TDY, IT, R1, R2, TX, TR1>())) v
         }
         if (Q8) {  // second sweep over the kept copy or the recomputed outputs
             am = wave_max(am);
-            run_amax = fmaxf(run_amax, am);
+            // the plain launch of tvts_layernorm_bwd_cls (cls_period given, not CLS): its results on the CLS rows are replaced by the
+            // CLS launch behind it and were formed from the stream's own rows there -- they are no part of the tensor whose maximum
+            // amax_acc collects
+            if (CLS || cls_period == 0 || r % cls_period != 0) run_amax = fmaxf(run_amax, am);
             const float scale = q8_scale(tscale, am);
             const float inv = 1.0f / scale;
 #pragma unroll
@@ -656,6 +669,8 @@ extern "C" int tvts_layernorm_bwd(const void* dy, int lddy, int dy_f32, const vo
     if ((res1_ && ldr % 4) || (res2_bf16 && ldr2 % 4)) return TVTS_EINVAL;
     const bf16* res2 = (const bf16*)res2_bf16;
     if (dx_bf16 && lddxb % 4) return TVTS_EINVAL;
+    if (!dy || !x_ || !mean || !rstd || !gamma || lddy < W || ldx < W || ln_grads_bad(dgamma, dbeta, workspace_elems)) return TVTS_EINVAL;
+    if (ln_ld_bad(res1_, ldr, W) || ln_ld_bad(res2_bf16, ldr2, W) || ln_ld_bad(dx, lddx, W) || ln_ld_bad(dx_bf16, lddxb, W)) return TVTS_EINVAL;
     if (x_bf16) {  // bf16 input: a side-branch value (ln_1's time residual) or the bf16 residual stream of the space-time blocks:
         // bf16 dy; no residual, or a bf16 res1 (+ the bf16 side branch res2)
         if (dy_f32 || (res1_ && !res1_bf16)) return TVTS_EINVAL;
@@ -702,6 +717,8 @@ extern "C" int tvts_layernorm_bwd_fp8(const void* dy, int lddy, const void* x_, 
     if (M <= 0 || W <= 0 || W % 4 || W > 256 * LN_MAX_IT || ldx % 4 || lddy % 4 || !dx_bf16 || lddxb % 4 || !q8 || ldq % 4 || (!row_scale && !tscale))
         return TVTS_EINVAL;
     if ((dx && lddx % 4) || (res1_ && ldr % 4) || (res2_bf16 && ldr2 % 4)) return TVTS_EINVAL;
+    if (!dy || !x_ || !mean || !rstd || !gamma || lddy < W || ldx < W || lddxb < W || ldq < W || ln_grads_bad(dgamma, dbeta, workspace_elems)) return TVTS_EINVAL;
+    if (ln_ld_bad(res1_, ldr, W) || ln_ld_bad(res2_bf16, ldr2, W) || ln_ld_bad(dx, lddx, W)) return TVTS_EINVAL;
     const bf16* res2 = (const bf16*)res2_bf16;
     const int it = ceil_div(W, 256);
 #define Q8_ARGS it, M, stream, (const bf16*)dy, lddy, x, ldx, (const int*)nullptr, mean, rstd, gamma, res1, res2, ldr2, ldr, W, dx, lddx, (bf16*)dx_bf16, lddxb, dgamma, dbeta, workspace, workspace_elems, (unsigned char*)q8, ldq, row_scale, tscale, amax_acc
@@ -743,13 +760,15 @@ extern "C" int tvts_layernorm_bwd_cls(const void* dy, int lddy, const void* x_, 
     if (M <= 0 || W <= 0 || W % 4 || W > 256 * LN_MAX_IT || ldx % 4 || lddy % 4 || !dx_bf16 || lddxb % 4) return TVTS_EINVAL;
     if (cls_period <= 0 || M % cls_period || (cls_res1 && !res1_bf16) || (res2_bf16 && !res1_bf16)) return TVTS_EINVAL;
     if ((res1_bf16 && ldr % 4) || (res2_bf16 && ldr2 % 4) || (q8 && (ldq % 4 || (!row_scale && !tscale)))) return TVTS_EINVAL;
+    if (!dy || !x_ || !mean || !rstd || !gamma || lddy < W || ldx < W || lddxb < W || ln_grads_bad(dgamma, dbeta, workspace_elems)) return TVTS_EINVAL;
+    if (ln_ld_bad(res1_bf16, ldr, W) || ln_ld_bad(res2_bf16, ldr2, W) || ln_ld_bad(q8, ldq, W)) return TVTS_EINVAL;
     const bf16* x = (const bf16*)x_;
     const bf16* res1 = (const bf16*)res1_bf16;
     const bf16* res2 = (const bf16*)res2_bf16;
     const int it = ceil_div(W, 256);
-#define CLS_ARGS(c) it, M, stream, (const bf16*)dy, lddy, x, ldx, (const int*)nullptr, mean, rstd, gamma, res1, res2, ldr2, ldr, W, (float*)nullptr, 0, (bf16*)dx_bf16, lddxb, dgamma, dbeta, workspace, workspace_elems, (unsigned char*)q8, ldq, row_scale, tscale, amax_acc, c ? cls_x : nullptr, c ? cls_res1 : nullptr, c ? cls_dx : nullptr, c ? cls_period : 0
+#define CLS_ARGS(c) it, M, stream, (const bf16*)dy, lddy, x, ldx, (const int*)nullptr, mean, rstd, gamma, res1, res2, ldr2, ldr, W, (float*)nullptr, 0, (bf16*)dx_bf16, lddxb, dgamma, dbeta, workspace, workspace_elems, (unsigned char*)q8, ldq, row_scale, tscale, amax_acc, c ? cls_x : nullptr, c ? cls_res1 : nullptr, c ? cls_dx : nullptr, cls_period
     // every row through the plain bf16-stream kernel (the CLS rows' results there come from the stream's bf16 rows: close, and
-    // replaced below), then the CLS rows alone from the fp32 side arrays
+    // replaced below; it is told cls_period only to keep them out of amax_acc), then the CLS rows alone from the fp32 side arrays
     if (q8) {
         if (res1 && res2) { launch_ln_bwd<bf16, true, true, bf16, true, bf16>(CLS_ARGS(0)); launch_ln_bwd<bf16, true, true, bf16, true, bf16, true>(CLS_ARGS(1)); }
         else if (res1) { launch_ln_bwd<bf16, true, false, bf16, true, bf16>(CLS_ARGS(0)); launch_ln_bwd<bf16, true, false, bf16, true, bf16, true>(CLS_ARGS(1)); }
