@@ -353,6 +353,24 @@ int tvts_attn_fwd_packed(const void* qkv, int ld, const int* seq_start, int N, i
                          hipStream_t stream);
 int tvts_attn_fwd_packed_last(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, void* out, int ldo,
                               hipStream_t stream);
+/* Training on packed captions.  _lse: the two entries above (same kernels, the same bits in out) that also store the log2-domain
+ * log-sum-exp lse2[row * heads + h] of every packed row they compute (every row of a valid sequence; the N last rows for _last) --
+ * layout and units of tvts_attn_fwd / tvts_attn_delta for a [rows = M, heads] problem.
+ * tvts_attn_bwd_packed: delta[row * heads + h] = rowsum(dO o O), P = exp2(s * scale2 - lse2), dS = P o (dP - delta), and dQ | dK | dV
+ * into the three thirds of dqkv bf16 [M, 3 * heads * 64].  A wave owns a (sequence, head) group (the forward's tile classes and
+ * guard) and writes all its rows in all three thirds: no atomics, no prior zeroing, run-to-run the same bits; a sequence with a
+ * malformed descriptor is skipped whole (nothing read or written).  _last: backward of the one-query form -- dQ at each sequence's
+ * last row, dK / dV at every row, and the dQ third of the other rows of a valid sequence ZEROED BY THE KERNEL; dO, O, lse2 are read
+ * and delta is written at the last rows only.  -22: as the forward, or dO / O / lse2 / delta / dqkv NULL, lddo or lddq no multiple of 8. */
+int tvts_attn_fwd_packed_lse(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, void* out, int ldo,
+                             float* lse2, hipStream_t stream);
+int tvts_attn_fwd_packed_last_lse(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, void* out,
+                                  int ldo, float* lse2, hipStream_t stream);
+int tvts_attn_bwd_packed(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, const void* dO, int lddo,
+                         const void* O, int ldo, const float* lse2, float* delta, void* dqkv, int lddq, hipStream_t stream);
+int tvts_attn_bwd_packed_last(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, const void* dO,
+                              int lddo, const void* O, int ldo, const float* lse2, float* delta, void* dqkv, int lddq,
+                              hipStream_t stream);
 int tvts_attn80_fwd_len(const void* qkv, int ld, int B, int heads, int S, const int* kv_len, void* out, int ldo, float* lse2,
                         hipStream_t stream);
 int tvts_attn80_bwd_len(const void* qkv, int ld, int B, int heads, int S, const int* kv_len, const void* dO, int lddo,
@@ -540,6 +558,13 @@ int tvts_text_embed_packed(const int* ids, const int* seq_start, int N, int M, c
  * block (list the long ones first: every caption's start / end token makes a run of N rows) */
 int tvts_text_embed_bwd(const float* dx, int ldx, const int* ids, int ld_ids, int N, int L, int Wt, float* demb, float* dpos,
                         const int* order, const int* seg, hipStream_t stream);
+/* the same for packed captions (ids int32[M], seq_start int32[N + 1]), ordered sums only: demb[id] += the rows of a run of tok_order /
+ * tok_seg (the plan of tvts_text_embed_bwd over the flat ids, M + 1 starts), dpos[l] += the rows pos_order[pos_seg[l] .. pos_seg[l + 1])
+ * in that order (rows sorted stably by r - seq_start[seq(r)], context + 1 starts).  An id outside [0, vocab) or a position outside
+ * [0, context) adds nothing. */
+int tvts_text_embed_bwd_packed(const float* dx, int ldx, const int* ids, const int* seq_start, int N, int M, int Wt, int vocab,
+                               int context, float* demb, float* dpos, const int* tok_order, const int* tok_seg, const int* pos_order,
+                               const int* pos_seg, hipStream_t stream);
 int tvts_text_mean(const float* t, int NT, int B, int E, float* mean, float* before, hipStream_t stream);
 int tvts_text_mean_bwd(const float* dmean, int NT, int B, int E, float* dt, hipStream_t stream);
 int tvts_sort_assemble(const float* tok, int ldt, int B, int S, int off, int Sv, const float* text, int NT,

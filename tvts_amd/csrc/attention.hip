@@ -2977,6 +2977,7 @@ extern "C" int ABI(fwd_divided_q8)(int mode, const void* qkv, int ld, int B, int
 }
 
 #if TVTS_DH == 64
-// packed variable-length causal attention (forward-only text encoder): tvts_attn_fwd_packed, tvts_attn_fwd_packed_last
+// packed variable-length causal attention: tvts_attn_fwd_packed(_last)(_lse) of the forward-only text encoder and of the packed
+// training step, tvts_attn_bwd_packed(_last)
 #include "attention_packed.h"
 #endif

@@ -1,4 +1,4 @@
-// Causal self-attention over PACKED variable-length sequences, forward-only, head dim 64 (included by attention.hip).
+// Causal self-attention over PACKED variable-length sequences, forward and backward, head dim 64 (included by attention.hip).
 //
 // The SSv2 multiple-choice scripts push C x B ragged captions through the CLIP text tower (v2/downstream/
 // zero_ssv2_mc_TVTSv2_ViT_B_16.py:60-88, "174 x B x 77"); rows behind a caption's EOT token cannot reach the row the model reads
@@ -15,6 +15,11 @@
 // contiguous range of one class would avoid the scan but needs the class boundaries on the host (the descriptor lives on the device).
 // A group is also skipped when its descriptor is out of range (rows outside [0, M), length < 1 or > 80): nothing is read or written
 // for it, so a malformed seq_start cannot leave the buffers.
+//
+// Training (the packed text tower of the step): the _lse entries are the same kernels and also store the log2-domain
+// log-sum-exp per (packed row, head), lse2[row * heads + h], the layout of the FULL kernels for a [rows = M, heads] problem.
+// attn_bwd_packed_kernel keeps the forward's ownership -- a wave per (sequence, head) group, the same tile classes, the same guard --
+// so one wave writes a group's rows of all three thirds of dqkv: no atomics, no cross-wave reduction, run-to-run the same bits.
 #pragma once
 
 namespace NS_DH {
@@ -24,9 +29,10 @@ __device__ __forceinline__ int packed_tile_class(int m) {
     return t <= 3 ? t : (t <= 5 ? 5 : 0);
 }
 
-template <int MT>
+template <int MT, bool LSE = false>
 __global__ __launch_bounds__(256) void attn_fwd_packed_kernel(const bf16* __restrict__ qkv, int ld, const int* __restrict__ seq_start,
-                                                              int N, int M, int heads, float scale2, bf16* __restrict__ out, int ldo) {
+                                                              int N, int M, int heads, float scale2, bf16* __restrict__ out, int ldo,
+                                                              float* __restrict__ lse2) {
     extern __shared__ __attribute__((aligned(16))) char smem[];  // per wave: V tile | output-staging patch
     constexpr int RA = MT * 16, TB = RA * VSTRIDE, NU = (MT + 1) / 2;
     constexpr int WB = TB + 1024;
@@ -137,6 +143,7 @@ __global__ __launch_bounds__(256) void attn_fwd_packed_kernel(const bf16* __rest
             store_tile_rows(opatch, on, lane, [&](int rr) -> bf16* {
                 const int j = qt * 16 + rr;
                 return j < m ? out + (size_t)(s0 + j) * ldo + hcol : nullptr; });
+            if (LSE && qj < m && gq == 0) lse2[(size_t)(s0 + qj) * heads + gid % heads] = mx + log2f(l);
         }
         gid = gnext;
     }
@@ -146,7 +153,8 @@ __global__ __launch_bounds__(256) void attn_fwd_packed_kernel(const bf16* __rest
 // v2/CLIP/clip/model.py:343-354), over all keys of the sequence.  A wave per (sequence, head): lanes over the keys for the scores
 // (fp32 dot products, up to two keys per lane), lanes over the 64 head columns for P V; probabilities stay fp32.  Writes that row only.
 __global__ __launch_bounds__(256) void attn_fwd_packed_last_kernel(const bf16* __restrict__ qkv, int ld, const int* __restrict__ seq_start,
-                                                                   int N, int M, int heads, float scale2, bf16* __restrict__ out, int ldo) {
+                                                                   int N, int M, int heads, float scale2, bf16* __restrict__ out, int ldo,
+                                                                   float* __restrict__ lse2) {
     const int lane = threadIdx.x & 63;
     const int gid = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (gid >= N * heads) return;
@@ -183,6 +191,268 @@ __global__ __launch_bounds__(256) void attn_fwd_packed_last_kernel(const bf16* _
         o = __builtin_fmaf(p, (float)vcol[(size_t)j * ld], o);
     }
     out[(size_t)(s1 - 1) * ldo + h * DH + lane] = (bf16)(o / l);
+    if (lse2 && lane == 0) lse2[(size_t)(s1 - 1) * heads + h] = mx + log2f(l);
+}
+
+// ---- backward of attn_fwd_packed_kernel: delta = rowsum(dO o O), then P = exp2(s * scale2 - lse2) from the stored log-sum-exp,
+// dS = P o (dP - delta), dQ = scale dS K (phase A), dK = scale dS^T Q and dV = P^T dO (phase B).  The data flow is
+// attn_bwd_seq_fused_kernel's: the group's Q | K | V | dO rows are staged once into wave-private row-major LDS tiles; the k-contiguous
+// operands (the score and dP products) are 16-byte row reads, the transposed ones (K^T, Q^T, dO^T under dS and P) ds_read_tr16_b64 of
+// the same tiles (VSTRIDE 160 keeps both conflict-free).  Key tiles above the diagonal are never multiplied: phase A stops at the
+// query tile, phase B starts at the key tile.  Rows m .. RA - 1 of the tiles are zeros, so neither stale LDS nor a neighbouring
+// sequence's rows can reach a product.  The 1 / 2 / 3-tile classes run two waves a block with the next group's rows in flight in
+// registers; the 5-tile class holds 52 KiB of tiles a wave -- one wave a block, three blocks a CU, no prefetch (its registers go to
+// the six score tiles of a query tile).
+template <int MT>
+__global__ __launch_bounds__(MT <= 3 ? 128 : 64) void attn_bwd_packed_kernel(
+    const bf16* __restrict__ qkv, int ld, const int* __restrict__ seq_start, int N, int M, int heads, float scale2, float scale,
+    const bf16* __restrict__ dO, int lddo, const bf16* __restrict__ O, int ldo, const float* __restrict__ lse2,
+    float* __restrict__ delta, bf16* __restrict__ dqkv, int lddq) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int WV = MT <= 3 ? 2 : 1;
+    constexpr int RA = MT * 16, TB = RA * VSTRIDE, NU = (MT + 1) / 2;
+    constexpr int WB = 4 * TB + 2 * RA * 4 + 1024;  // one wave's region: Q | K | V | dO tiles, lse and delta of the rows, output patch
+    constexpr int PT = RA * NCH / 64;
+    constexpr bool PF = MT <= 3;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    char* base = smem + wave * WB;
+    char* Qs = base;
+    char* Ks = Qs + TB;
+    char* Vs = Ks + TB;
+    char* Ds = Vs + TB;
+    float* st_lse = (float*)(Ds + TB);
+    float* st_dl = st_lse + RA;
+    char* opatch = (char*)(st_dl + RA);
+    const int gq = lane >> 4, li = lane & 15;
+    const int W = heads * DH, groups = N * heads, stride = gridDim.x * WV;
+
+    auto next = [&](int gid) {
+        for (; gid < groups; gid += stride) {
+            const int s = gid / heads, s0 = seq_start[s], s1 = seq_start[s + 1];
+            if (s0 >= 0 && s1 <= M && s1 > s0 && packed_tile_class(s1 - s0) == MT) break;
+        }
+        return gid;
+    };
+    bf16x8 stg[4][PT], ost[PT];
+    float lse_pf[2] = {0.f, 0.f};
+    int s0n = 0, mn = 1;
+    auto issue = [&](int gid) {
+        const int s = gid / heads, h = gid % heads;
+        s0n = seq_start[s];
+        mn = seq_start[s + 1] - s0n;
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            const bf16* src = (t == 3 ? dO : t == 4 ? O : qkv + t * W) + h * DH;
+            const int ldt = t == 3 ? lddo : t == 4 ? ldo : ld;
+#pragma unroll
+            for (int i = 0; i < PT; ++i) {
+                const int cc = lane + 64 * i, row = cc / NCH, ch = cc % NCH;
+                bf16x8 v;
+                if (PF) v = row < mn ? ldg8(src + (size_t)(s0n + row) * ldt + ch * 8) : zero8();
+                else v = sel8(row < mn, ldg8(src + (size_t)(s0n + (row < mn ? row : mn - 1)) * ldt + ch * 8));  // (see sel8)
+                if (t == 4) ost[i] = v; else stg[t][i] = v;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < (MT == 5 ? 2 : 1); ++k)
+            lse_pf[k] = lane + 64 * k < mn ? lse2[(size_t)(s0n + lane + 64 * k) * heads + h] : 0.f;
+    };
+    int gid = next(blockIdx.x * WV + wave);
+    if (PF && gid < groups) issue(gid);
+    while (gid < groups) {
+        if (!PF) issue(gid);
+        const int s0 = s0n, m = mn, h = gid % heads, hcol = h * DH;
+        // registers -> this wave's LDS tiles (rows m .. RA - 1 arrive as zeros); delta of every row on the way
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < PT; ++i) {
+                const int cc = lane + 64 * i, row = cc / NCH, ch = cc % NCH;
+                *(bf16x8*)(base + t * TB + row * VSTRIDE + ch * 16) = stg[t][i];
+            }
+#pragma unroll
+        for (int i = 0; i < PT; ++i) {
+            const int row = (lane + 64 * i) / NCH;
+            float p = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) p = __builtin_fmaf((float)stg[3][i][e], (float)ost[i][e], p);
+            p += __shfl_xor(p, 1, 64);
+            p += __shfl_xor(p, 2, 64);
+            p += __shfl_xor(p, 4, 64);
+            if ((lane & (NCH - 1)) == 0) {
+                st_dl[row] = p;
+                if (row < m) delta[(size_t)(s0 + row) * heads + h] = p;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < (MT == 5 ? 2 : 1); ++k)
+            if (lane + 64 * k < RA) st_lse[lane + 64 * k] = lse_pf[k];
+        const int gnext = next(gid + stride);
+        if (PF && gnext < groups) issue(gnext);
+
+        // ---- phase A: dQ of a query tile over the key tiles up to the diagonal
+#pragma unroll
+        for (int qt = 0; qt < MT; ++qt) {
+            if (qt * 16 >= m) continue;  // (wave-uniform; only the 5-tile class has a tile without rows)
+            const int qj = qt * 16 + li;
+            bf16x8 qf[KS], dof[KS];
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) { qf[ks] = frag_row(Qs, qj, ks, gq); dof[ks] = frag_row(Ds, qj, ks, gq); }
+            const float lse = st_lse[qj], dlt = st_dl[qj];
+            f32x4 dS[2 * NU];
+#pragma unroll
+            for (int t = 0; t < 2 * NU; ++t) {
+                dS[t] = (f32x4){0, 0, 0, 0};
+                if (t <= qt) {
+                    f32x4 sc = {0, 0, 0, 0}, dp = {0, 0, 0, 0};
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) {
+                        sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row(Ks, t * 16 + li, ks, gq), qf[ks], sc, 0, 0, 0);
+                        dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row(Vs, t * 16 + li, ks, gq), dof[ks], dp, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int key = t * 16 + gq * 4 + e;
+                        const bool ok = key < m && key <= qj && qj < m;
+                        const float pp = ok ? __builtin_amdgcn_exp2f(sc[e] * scale2 - lse) : 0.f;
+                        dS[t][e] = ok ? pp * (dp[e] - dlt) * scale : 0.f;
+                    }
+                }
+            }
+            f32x4 acc[DT];
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) acc[dt] = (f32x4){0, 0, 0, 0};
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+                if (2 * u > qt) continue;
+                bf16x8 dsf;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) dsf[j] = (bf16)dS[2 * u + (j >> 2)][j & 3];
+#pragma unroll
+                for (int dt = 0; dt < DT; ++dt)
+                    acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_T_lim<true>(Ks, u, dt, lane, RA), dsf, acc[dt], 0, 0, 0);
+            }
+            store_tile_rows(opatch, acc, lane, [&](int rr) -> bf16* {
+                const int j = qt * 16 + rr;
+                return j < m ? dqkv + (size_t)(s0 + j) * lddq + hcol : nullptr; });
+        }
+
+        // ---- phase B: dK / dV of a key tile over the query tiles from the diagonal down
+#pragma unroll
+        for (int kt = 0; kt < MT; ++kt) {
+            if (kt * 16 >= m) continue;
+            const int kj = kt * 16 + li;
+            bf16x8 kb[KS], vb[KS];
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) { kb[ks] = frag_row(Ks, kj, ks, gq); vb[ks] = frag_row(Vs, kj, ks, gq); }
+            f32x4 dv[DT], dk[DT];
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) { dv[dt] = (f32x4){0, 0, 0, 0}; dk[dt] = (f32x4){0, 0, 0, 0}; }
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+                if (2 * u + 1 < kt) continue;     // both query tiles of this k-step lie above the diagonal
+                if (u * 32 >= m) continue;        // ... or behind the last row (wave-uniform)
+                bf16x8 pf, dsf;
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const int tile = 2 * u + t;
+                    if (tile < MT && tile >= kt) {
+                        f32x4 sc = {0, 0, 0, 0}, dp = {0, 0, 0, 0};
+#pragma unroll
+                        for (int ks = 0; ks < KS; ++ks) {
+                            sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row(Qs, tile * 16 + li, ks, gq), kb[ks], sc, 0, 0, 0);
+                            dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row(Ds, tile * 16 + li, ks, gq), vb[ks], dp, 0, 0, 0);
+                        }
+                        const f32x4 l4 = *(const f32x4*)(st_lse + tile * 16 + gq * 4);
+                        const f32x4 d4 = *(const f32x4*)(st_dl + tile * 16 + gq * 4);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const int qi = tile * 16 + gq * 4 + e;
+                            const bool ok = qi < m && kj <= qi;
+                            const float pp = ok ? __builtin_amdgcn_exp2f(sc[e] * scale2 - l4[e]) : 0.f;
+                            pf[t * 4 + e] = (bf16)pp;
+                            dsf[t * 4 + e] = (bf16)(ok ? pp * (dp[e] - d4[e]) * scale : 0.f);
+                        }
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) { pf[t * 4 + e] = (bf16)0.f; dsf[t * 4 + e] = (bf16)0.f; }
+                    }
+                }
+#pragma unroll
+                for (int dt = 0; dt < DT; ++dt) {
+                    dv[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_T_lim<true>(Ds, u, dt, lane, RA), pf, dv[dt], 0, 0, 0);
+                    dk[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_T_lim<true>(Qs, u, dt, lane, RA), dsf, dk[dt], 0, 0, 0);
+                }
+            }
+            auto krowp = [&](int third) {
+                return [&, third](int rr) -> bf16* {
+                    const int j = kt * 16 + rr;
+                    return j < m ? dqkv + (size_t)(s0 + j) * lddq + third * W + hcol : nullptr; };
+            };
+            store_tile_rows(opatch, dk, lane, krowp(1));
+            store_tile_rows(opatch, dv, lane, krowp(2));
+        }
+        gid = gnext;
+    }
+}
+
+// ---- backward of attn_fwd_packed_last_kernel: the one query of a sequence sits at its last row.  fp32 throughout, a wave per
+// (sequence, head): lanes over the keys for P and dS (up to two keys per lane), then lanes over the 64 head columns for
+// dQ = scale sum_j dS_j K_j (summed in key order), dK_j = scale dS_j q and dV_j = P_j dO.  Every row of the sequence is written in all
+// three thirds: the dQ third of the rows that are no query is zeroed HERE (not by the caller), so a skipped sequence stays untouched.
+__global__ __launch_bounds__(256) void attn_bwd_packed_last_kernel(
+    const bf16* __restrict__ qkv, int ld, const int* __restrict__ seq_start, int N, int M, int heads, float scale2, float scale,
+    const bf16* __restrict__ dO, int lddo, const bf16* __restrict__ O, int ldo, const float* __restrict__ lse2,
+    float* __restrict__ delta, bf16* __restrict__ dqkv, int lddq) {
+    const int lane = threadIdx.x & 63;
+    const int gid = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gid >= N * heads) return;
+    const int s = gid / heads, h = gid % heads, W = heads * DH;
+    const int s0 = seq_start[s], s1 = seq_start[s + 1], m = s1 - s0;
+    if (s0 < 0 || s1 > M || m < 1 || m > 80) return;
+    const bf16* base = qkv + (size_t)s0 * ld + h * DH;
+    const size_t last = (size_t)(s1 - 1);
+    const float lse = lse2[last * heads + h];
+    const float do_d = (float)dO[last * lddo + h * DH + lane], q_d = (float)base[(size_t)(m - 1) * ld + lane];
+    const float dlt = wave_sum(do_d * (float)O[last * ldo + h * DH + lane]);
+    if (lane == 0) delta[last * heads + h] = dlt;
+    bf16x8 q[NCH], go[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        q[c] = ldg8(base + (size_t)(m - 1) * ld + c * 8);
+        go[c] = ldg8(dO + last * lddo + h * DH + c * 8);
+    }
+    float p[2], ds[2];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        const int j = lane + 64 * kk;
+        float dot = 0.f, dp = 0.f;
+        if (j < m) {
+            const bf16* kr = base + (size_t)j * ld + W;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                const bf16x8 kv = ldg8(kr + c * 8), vv = ldg8(kr + W + c * 8);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    dot = __builtin_fmaf((float)q[c][e], (float)kv[e], dot);
+                    dp = __builtin_fmaf((float)go[c][e], (float)vv[e], dp);
+                }
+            }
+        }
+        p[kk] = j < m ? __builtin_amdgcn_exp2f(dot * scale2 - lse) : 0.f;
+        ds[kk] = p[kk] * (dp - dlt) * scale;
+    }
+    float dq = 0.f;
+    bf16* drow = dqkv + (size_t)s0 * lddq + h * DH + lane;
+    for (int j = 0; j < m; ++j) {
+        const float pj = __shfl(j < 64 ? p[0] : p[1], j & 63, 64), dsj = __shfl(j < 64 ? ds[0] : ds[1], j & 63, 64);
+        dq = __builtin_fmaf(dsj, (float)base[(size_t)j * ld + W + lane], dq);
+        bf16* r = drow + (size_t)j * lddq;
+        if (j < m - 1) r[0] = (bf16)0.f;
+        r[W] = (bf16)(dsj * q_d);
+        r[2 * W] = (bf16)(pj * do_d);
+    }
+    drow[(size_t)(m - 1) * lddq] = (bf16)dq;
 }
 
 }  // namespace NS_DH
@@ -193,16 +463,20 @@ static int packed_args_ok(const void* qkv, int ld, const int* seq_start, int N, 
     return TVTS_OK;
 }
 
-extern "C" int tvts_attn_fwd_packed(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, void* out,
-                                    int ldo, hipStream_t stream) {
-    const int rc = packed_args_ok(qkv, ld, seq_start, N, M, heads, max_len, out, ldo);
-    if (rc) return rc;
+static int packed_fwd(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, void* out, int ldo, float* lse2,
+                      hipStream_t stream) {
     const float scale2 = 1.4426950408889634f / sqrtf((float)DH);
     const int groups = N * heads;
     const int blocks = ceil_div(groups, 4) < 1536 ? ceil_div(groups, 4) : 1536;
 #define PACKED_LAUNCH(MT)                                                                                                      \
-    hipLaunchKernelGGL((attn_fwd_packed_kernel<MT>), dim3(blocks), dim3(256), 4 * (MT * 16 * VSTRIDE + 1024), stream,           \
-                       (const bf16*)qkv, ld, seq_start, N, M, heads, scale2, (bf16*)out, ldo)
+    do {                                                                                                                       \
+        if (lse2)                                                                                                              \
+            hipLaunchKernelGGL((attn_fwd_packed_kernel<MT, true>), dim3(blocks), dim3(256), 4 * (MT * 16 * VSTRIDE + 1024),    \
+                               stream, (const bf16*)qkv, ld, seq_start, N, M, heads, scale2, (bf16*)out, ldo, lse2);           \
+        else                                                                                                                   \
+            hipLaunchKernelGGL((attn_fwd_packed_kernel<MT, false>), dim3(blocks), dim3(256), 4 * (MT * 16 * VSTRIDE + 1024),   \
+                               stream, (const bf16*)qkv, ld, seq_start, N, M, heads, scale2, (bf16*)out, ldo, (float*)nullptr);\
+    } while (0)
     PACKED_LAUNCH(1);
     if (max_len > 16) PACKED_LAUNCH(2);
     if (max_len > 32) PACKED_LAUNCH(3);
@@ -212,13 +486,82 @@ extern "C" int tvts_attn_fwd_packed(const void* qkv, int ld, const int* seq_star
     return TVTS_OK;
 }
 
+extern "C" int tvts_attn_fwd_packed(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, void* out,
+                                    int ldo, hipStream_t stream) {
+    const int rc = packed_args_ok(qkv, ld, seq_start, N, M, heads, max_len, out, ldo);
+    return rc ? rc : packed_fwd(qkv, ld, seq_start, N, M, heads, max_len, out, ldo, nullptr, stream);
+}
+
+extern "C" int tvts_attn_fwd_packed_lse(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, void* out,
+                                        int ldo, float* lse2, hipStream_t stream) {
+    const int rc = packed_args_ok(qkv, ld, seq_start, N, M, heads, max_len, out, ldo);
+    if (rc || !lse2) return TVTS_EINVAL;
+    return packed_fwd(qkv, ld, seq_start, N, M, heads, max_len, out, ldo, lse2, stream);
+}
+
+static int packed_fwd_last(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, void* out, int ldo, float* lse2,
+                           hipStream_t stream) {
+    const float scale2 = 1.4426950408889634f / sqrtf((float)DH);
+    hipLaunchKernelGGL(attn_fwd_packed_last_kernel, dim3(ceil_div(N * heads, 4)), dim3(256), 0, stream, (const bf16*)qkv, ld,
+                       seq_start, N, M, heads, scale2, (bf16*)out, ldo, lse2);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
 extern "C" int tvts_attn_fwd_packed_last(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len,
                                          void* out, int ldo, hipStream_t stream) {
     const int rc = packed_args_ok(qkv, ld, seq_start, N, M, heads, max_len, out, ldo);
+    return rc ? rc : packed_fwd_last(qkv, ld, seq_start, N, M, heads, out, ldo, nullptr, stream);
+}
+
+extern "C" int tvts_attn_fwd_packed_last_lse(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len,
+                                             void* out, int ldo, float* lse2, hipStream_t stream) {
+    const int rc = packed_args_ok(qkv, ld, seq_start, N, M, heads, max_len, out, ldo);
+    if (rc || !lse2) return TVTS_EINVAL;
+    return packed_fwd_last(qkv, ld, seq_start, N, M, heads, out, ldo, lse2, stream);
+}
+
+static int packed_bwd_args_ok(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, const void* dO,
+                              int lddo, const void* O, int ldo, const float* lse2, const float* delta, const void* dqkv, int lddq) {
+    const int rc = packed_args_ok(qkv, ld, seq_start, N, M, heads, max_len, O, ldo);
     if (rc) return rc;
-    const float scale2 = 1.4426950408889634f / sqrtf((float)DH);
-    hipLaunchKernelGGL(attn_fwd_packed_last_kernel, dim3(ceil_div(N * heads, 4)), dim3(256), 0, stream, (const bf16*)qkv, ld,
-                       seq_start, N, M, heads, scale2, (bf16*)out, ldo);
+    if (!dO || !lse2 || !delta || !dqkv || lddo % 8 || lddq % 8 || lddo < heads * DH || lddq < 3 * heads * DH) return TVTS_EINVAL;
+    return TVTS_OK;
+}
+
+extern "C" int tvts_attn_bwd_packed(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, const void* dO,
+                                    int lddo, const void* O, int ldo, const float* lse2, float* delta, void* dqkv, int lddq,
+                                    hipStream_t stream) {
+    const int rc = packed_bwd_args_ok(qkv, ld, seq_start, N, M, heads, max_len, dO, lddo, O, ldo, lse2, delta, dqkv, lddq);
+    if (rc) return rc;
+    const float scale = 1.0f / sqrtf((float)DH), scale2 = 1.4426950408889634f * scale;
+    const int groups = N * heads;
+#define PACKED_LAUNCH(MT)                                                                                                      \
+    do {                                                                                                                       \
+        constexpr int WV = MT <= 3 ? 2 : 1, WB = 4 * MT * 16 * VSTRIDE + 2 * MT * 16 * 4 + 1024;                               \
+        const int blocks = ceil_div(groups, WV) < 2048 ? ceil_div(groups, WV) : 2048;                                          \
+        hipLaunchKernelGGL((attn_bwd_packed_kernel<MT>), dim3(blocks), dim3(64 * WV), WV * WB, stream, (const bf16*)qkv, ld,   \
+                           seq_start, N, M, heads, scale2, scale, (const bf16*)dO, lddo, (const bf16*)O, ldo, lse2, delta,     \
+                           (bf16*)dqkv, lddq);                                                                                 \
+    } while (0)
+    PACKED_LAUNCH(1);
+    if (max_len > 16) PACKED_LAUNCH(2);
+    if (max_len > 32) PACKED_LAUNCH(3);
+    if (max_len > 48) PACKED_LAUNCH(5);
+#undef PACKED_LAUNCH
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
+extern "C" int tvts_attn_bwd_packed_last(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len,
+                                         const void* dO, int lddo, const void* O, int ldo, const float* lse2, float* delta, void* dqkv,
+                                         int lddq, hipStream_t stream) {
+    const int rc = packed_bwd_args_ok(qkv, ld, seq_start, N, M, heads, max_len, dO, lddo, O, ldo, lse2, delta, dqkv, lddq);
+    if (rc) return rc;
+    const float scale = 1.0f / sqrtf((float)DH), scale2 = 1.4426950408889634f * scale;
+    hipLaunchKernelGGL(attn_bwd_packed_last_kernel, dim3(ceil_div(N * heads, 4)), dim3(256), 0, stream, (const bf16*)qkv, ld,
+                       seq_start, N, M, heads, scale2, scale, (const bf16*)dO, lddo, (const bf16*)O, ldo, lse2, delta, (bf16*)dqkv,
+                       lddq);
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;
 }

@@ -855,13 +855,14 @@ __global__ __launch_bounds__(1024) void text_pos_bwd_kernel(const float* __restr
 #define TOK_LONG_SLOTS 64
 __global__ __launch_bounds__(256) void text_tok_bwd_kernel(const float* __restrict__ dx, int ldx, const int* __restrict__ ids,
                                                            int ld_ids, int L, int Wt, const int* __restrict__ order,
-                                                           const int* __restrict__ seg, float* __restrict__ demb) {
+                                                           const int* __restrict__ seg, float* __restrict__ demb, int vocab) {
     __shared__ f32x4 part[256];
     const int lo = seg[blockIdx.x], hi = seg[blockIdx.x + 1];
     if (lo >= hi) return;
     if (hi - lo > TOK_LONG_RUN && blockIdx.x < TOK_LONG_SLOTS) return;  // text_tok_long_bwd_kernel's
     const int row0 = order[lo];
     const int id = ids[(size_t)(row0 / L) * ld_ids + row0 % L];
+    if ((unsigned)id >= (unsigned)vocab) return;  // (block-uniform; the packed form's guard, INT_MAX in the rectangular one)
     const int cpt = Wt / 4 < 256 ? Wt / 4 : 256;  // column-threads per group
     const int G = 256 / cpt, grp = threadIdx.x / cpt, ct = threadIdx.x % cpt;
     for (int c0 = 0; c0 < Wt; c0 += cpt * 4) {
@@ -899,12 +900,13 @@ __global__ __launch_bounds__(256) void text_tok_bwd_kernel(const float* __restri
 // a thread four columns, sixteen rows in flight per thread, the groups combined in group order
 __global__ __launch_bounds__(256) void text_tok_long_bwd_kernel(const float* __restrict__ dx, int ldx, const int* __restrict__ ids,
                                                                 int ld_ids, int L, int Wt, const int* __restrict__ order,
-                                                                const int* __restrict__ seg, float* __restrict__ demb) {
+                                                                const int* __restrict__ seg, float* __restrict__ demb, int vocab) {
     __shared__ f32x4 part[256];
     const int lo = seg[blockIdx.x], hi = seg[blockIdx.x + 1];
     if (hi - lo <= TOK_LONG_RUN) return;
     const int row0 = order[lo];
     const int id = ids[(size_t)(row0 / L) * ld_ids + row0 % L];
+    if ((unsigned)id >= (unsigned)vocab) return;
     const int grp = threadIdx.x >> 4, c = blockIdx.y * 64 + (threadIdx.x & 15) * 4;
     f32x4 a = {0.f, 0.f, 0.f, 0.f};
     if (c < Wt) {
@@ -935,13 +937,63 @@ extern "C" int tvts_text_embed_bwd(const float* dx, int ldx, const int* ids, int
                                    float* dpos, const int* order, const int* seg, hipStream_t stream) {
     if (order != nullptr && seg != nullptr && Wt % 4 == 0 && ldx % 4 == 0) {
         hipLaunchKernelGGL(text_pos_bwd_kernel, dim3(ceil_div(Wt, 64), L), dim3(1024), 0, stream, dx, ldx, N, L, Wt, dpos);
-        hipLaunchKernelGGL(text_tok_bwd_kernel, dim3(N * L), dim3(256), 0, stream, dx, ldx, ids, ld_ids, L, Wt, order, seg, demb);
+        hipLaunchKernelGGL(text_tok_bwd_kernel, dim3(N * L), dim3(256), 0, stream, dx, ldx, ids, ld_ids, L, Wt, order, seg, demb, 0x7fffffff);
         const int slots = N * L < TOK_LONG_SLOTS ? N * L : TOK_LONG_SLOTS;
         hipLaunchKernelGGL(text_tok_long_bwd_kernel, dim3(slots, ceil_div(Wt, 64)), dim3(256), 0, stream, dx, ldx, ids, ld_ids, L, Wt,
-                           order, seg, demb);
+                           order, seg, demb, 0x7fffffff);
     } else {
         hipLaunchKernelGGL(text_embed_bwd_kernel, dim3(N * L), dim3(256), 0, stream, dx, ldx, ids, ld_ids, N, L, Wt, demb, dpos);
     }
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
+// the same for PACKED captions (ids int32 [M], seq_start as for tvts_text_embed_packed): ordered sums only.  Tokens: the two kernels
+// above read a flat ids as one caption of M tokens (row -> ids[row]); an id outside [0, vocab) writes nothing.  Positions: the caller
+// hands over the rows sorted stably by their position inside their caption (`pos_order`) and the context + 1 starts of the runs of
+// equal position (`pos_seg`); a block per (64 columns, position) adds its rows -- 16 thread groups, each in row order, combined in
+// group order.  A row that does not sit at the block's position according to seq_start is not added (a plan that does not belong to
+// the descriptor cannot put a gradient into another position's row).
+__global__ __launch_bounds__(1024) void text_pos_bwd_packed_kernel(const float* __restrict__ dx, int ldx, const int* __restrict__ seq_start,
+                                                                   int N, int M, int Wt, const int* __restrict__ pos_order,
+                                                                   const int* __restrict__ pos_seg, float* __restrict__ dpos) {
+    __shared__ float acc[16][64];
+    const int l = blockIdx.y, c = blockIdx.x * 64 + (threadIdx.x & 63), grp = threadIdx.x >> 6;
+    const int lo = pos_seg[l], hi = pos_seg[l + 1];
+    if (lo >= hi || lo < 0 || hi > M) return;  // (block-uniform)
+    float s = 0.f;
+    if (c < Wt)
+        for (int k = lo + grp; k < hi; k += 16) {
+            const int r = pos_order[k];
+            if (r < 0 || r >= M) continue;
+            int a = 0, b = N;
+            while (b - a > 1) {
+                const int mid = (a + b) >> 1;
+                if (seq_start[mid] <= r) a = mid; else b = mid;
+            }
+            if (r - seq_start[a] == l) s += dx[(size_t)r * ldx + c];
+        }
+    acc[grp][threadIdx.x & 63] = s;
+    __syncthreads();
+    if (grp == 0 && c < Wt) {
+        float t = 0.f;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) t += acc[g][threadIdx.x];
+        dpos[(size_t)l * Wt + c] += t;
+    }
+}
+extern "C" int tvts_text_embed_bwd_packed(const float* dx, int ldx, const int* ids, const int* seq_start, int N, int M, int Wt, int vocab,
+                                          int context, float* demb, float* dpos, const int* tok_order, const int* tok_seg,
+                                          const int* pos_order, const int* pos_seg, hipStream_t stream) {
+    if (!dx || !ids || !seq_start || !demb || !dpos || !tok_order || !tok_seg || !pos_order || !pos_seg || N <= 0 || M <= 0 ||
+        vocab <= 0 || context <= 0 || Wt <= 0 || Wt % 4 || ldx % 4 || ldx < Wt)
+        return TVTS_EINVAL;
+    hipLaunchKernelGGL(text_pos_bwd_packed_kernel, dim3(ceil_div(Wt, 64), context), dim3(1024), 0, stream, dx, ldx, seq_start, N, M, Wt,
+                       pos_order, pos_seg, dpos);
+    hipLaunchKernelGGL(text_tok_bwd_kernel, dim3(M), dim3(256), 0, stream, dx, ldx, ids, M, M, Wt, tok_order, tok_seg, demb, vocab);
+    const int slots = M < TOK_LONG_SLOTS ? M : TOK_LONG_SLOTS;
+    hipLaunchKernelGGL(text_tok_long_bwd_kernel, dim3(slots, ceil_div(Wt, 64)), dim3(256), 0, stream, dx, ldx, ids, M, M, Wt, tok_order,
+                       tok_seg, demb, vocab);
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;
 }

@@ -190,6 +190,17 @@ class Engine:
         self.sort_used_rows_only = bool(a.get("sort_used_rows_only", True))  # last sort block on the rows the head reads (sort_forward)
         self.text_used_rows_only = bool(a.get("text_used_rows_only", a.get("sort_used_rows_only", True)))  # last text block: EOT rows
         self.has_sort_head = bool(a.get("sort_head", True))
+        # the training step's text tower over PACKED captions (opt-in): M = sum L_i token rows instead of N * max L_i
+        tp = a.get("text_packed")
+        if tp is None and a.get("family") != "v1" and os.environ.get("TVTS_TEXT_PACKED"):  # (the reference entrypoint builds no arch dict)
+            tp = os.environ["TVTS_TEXT_PACKED"] != "0"
+        self.text_packed = bool(tp)
+        if self.text_packed:
+            if a.get("family") == "v1":
+                raise ValueError("text_packed: the v1 text tower masks padded keys, it is not causal -- rows behind a caption's end "
+                                 "are no dead rows there")
+            if self.dh_text != 64:
+                raise NotImplementedError("text_packed: the packed attention kernels are built for head dim 64")
         # Precision of the space-time blocks' residual stream (round 3).  Every consumer but the residual adds themselves reads
         # these tensors as bf16 anyway (LayerNorm outputs and GEMM operands are bf16): fp32 buys exact accumulation along the
         # 12 / 32 blocks, at 2.1 GB per block of HBM traffic in the forward + saved activations and 1.4 GB in the backward chain
@@ -791,8 +802,20 @@ class Engine:
         pos = (eot_rows - torch.arange(eot_rows.numel(), device=eot_rows.device, dtype=torch.int32) * L).contiguous()
         return None, pos
 
-    def text_forward(self, ids_dev, eot_rows, N, L, eot_index=None):
-        """eot_index: Engine.eot_index(eot_rows, L) kept by the caller (prepare_batch); made here when absent (eager use only)."""
+    def text_forward(self, ids_dev, eot_rows, N, L, eot_index=None, packed=None):
+        """eot_index: Engine.eot_index(eot_rows, L) kept by the caller (prepare_batch); made here when absent (eager use only).
+        packed: the batch of prepare_batch under arch["text_packed"] (its seq_start, M, max_len) -- ids_dev is then int32 [M], every
+        caption cut behind its EOT token, eot_rows = seq_start[1:] - 1, and the tower runs over those M rows.  M is whatever the
+        captions add up to, odd and prime included: the GEMMs of the text blocks take any row count and any contraction length (their
+        tile tails are masked), so the packed buffers carry no padding rows."""
+        if packed is not None:
+            ht, ss, ml = self.arch["text_heads"], packed["seq_start"], packed["max_len"]
+            return self._text_tower(
+                lambda x: K.text_embed_packed(ids_dev, ss, self.P.p("text_token_embedding.weight"),
+                                              self.P.p("text_positional_embedding"), x, N=N),
+                lambda qkv, att, lse: K.attn_fwd_packed(qkv, ss, att, N=N, heads=ht, max_len=ml, lse2=lse),
+                lambda qkv, att, lse: K.attn_fwd_packed(qkv, ss, att, N=N, heads=ht, max_len=ml, last_only=True, lse2=lse),
+                eot_rows, N, packed["M"], "txt")
         t, self._text_eot = self._text_padded(ids_dev, eot_rows, N, L, eot_index, "txt")  # (the backward takes the positions from here)
         return t
 
@@ -826,7 +849,9 @@ class Engine:
         K.gemm_small(lnf, self.P.p("text_projection"), t, M=N, N=a["embed"], K=Wt, sa=(Wt, 1), sb=(a["embed"], 1))
         return t
 
-    def text_backward(self, dt, ids_dev, eot_rows, N, L, tok_sort=None):
+    def text_backward(self, dt, ids_dev, eot_rows, N, L, tok_sort=None, packed=None):
+        """packed: as text_forward (the same batch); tok_sort is then the plan over the packed ids and packed["pos_sort"] the
+        position plan of tvts_text_embed_bwd_packed."""
         a = self.arch
         Wt, E = a["text_width"], a["embed"]
         lnf = self.buf["txt.lnf"]
@@ -834,18 +859,25 @@ class Engine:
             K.gemm_small(lnf, dt, self.P.g("text_projection"), M=Wt, N=E, K=N, sa=(1, Wt), sb=(E, 1), accumulate=True)
         dlnf = self._f("txt.dlnf", (N, Wt))
         K.gemm_small(dt, self.P.p("text_projection"), dlnf, M=N, N=Wt, K=E, sa=(E, 1), sb=(1, E))
-        packed = self.text_used_rows_only  # the gradient of the last block's output exists at the EOT rows only: [N, Wt]
-        dx, dxb = self._head_ln_bwd(dlnf, "text_ln_final", "txt", "txt.lnf", a["text_layers"], eot_rows, packed)
+        used = self.text_used_rows_only  # the gradient of the last block's output exists at the EOT rows only: [N, Wt]
+        dx, dxb = self._head_ln_bwd(dlnf, "text_ln_final", "txt", "txt.lnf", a["text_layers"], eot_rows, used)
         ht, hd = a["text_heads"], self.dh_text
-        pos = self._text_eot[1] if packed else None  # the forward's tensor (the batch's when it came through prepare_batch)
-        dx = self._blocks_bwd(
-            "text_model.resblocks.", _TEXT_NAMES, "txt", a["text_layers"], dx, dxb, ht, a["act"],
-            lambda qkv, *t: K.attn_bwd("full", qkv, *t, B=N, heads=ht, S=L, causal=True, head_dim=hd),
-            eot_rows if packed else None,
-            lambda qkv, *t: K.attn_bwd_rowq(qkv, pos, *t, B=N, heads=ht, S=L, head_dim=hd))
+        if packed is not None:
+            ss, ml = packed["seq_start"], packed["max_len"]
+            attn_bwd = lambda qkv, *t: K.attn_bwd_packed(qkv, ss, *t, N=N, heads=ht, max_len=ml)  # noqa: E731
+            attn_bwd_last = lambda qkv, *t: K.attn_bwd_packed(qkv, ss, *t, N=N, heads=ht, max_len=ml, last_only=True)  # noqa: E731
+        else:
+            pos = self._text_eot[1] if used else None  # the forward's tensor (the batch's when it came through prepare_batch)
+            attn_bwd = lambda qkv, *t: K.attn_bwd("full", qkv, *t, B=N, heads=ht, S=L, causal=True, head_dim=hd)  # noqa: E731
+            attn_bwd_last = lambda qkv, *t: K.attn_bwd_rowq(qkv, pos, *t, B=N, heads=ht, S=L, head_dim=hd)  # noqa: E731
+        dx = self._blocks_bwd("text_model.resblocks.", _TEXT_NAMES, "txt", a["text_layers"], dx, dxb, ht, a["act"], attn_bwd,
+                              eot_rows if used else None, attn_bwd_last)
         if self.requires_grad["text_token_embedding.weight"] or self.requires_grad["text_positional_embedding"]:
-            K.text_embed_bwd(dx, ids_dev, self.P.g("text_token_embedding.weight"), self.P.g("text_positional_embedding"),
-                             N=N, L=L, tok_sort=tok_sort)
+            demb, dpos = self.P.g("text_token_embedding.weight"), self.P.g("text_positional_embedding")
+            if packed is not None:
+                K.text_embed_bwd_packed(dx, ids_dev, ss, demb, dpos, N=N, tok_sort=tok_sort, pos_sort=packed["pos_sort"])
+            else:
+                K.text_embed_bwd(dx, ids_dev, demb, dpos, N=N, L=L, tok_sort=tok_sort)
 
     # ------------------------------------------------------------------ video tower
     def _attn_q8(self, M, W, name, T, n, persistent=False, consumer=None):
@@ -1262,12 +1294,16 @@ class Engine:
         L = int(eot.max()) + 1
         N = ids_cpu.shape[0]
         NT = N // B
+        pk = K.pack_captions(ids_cpu, a["context"]) if self.text_packed else None  # (captions stay in batch order: rows i * B + b)
         # every small index tensor of the batch is made on the HOST and travels in one asynchronous copy (_stage_small): no copy of
         # this function is ordered behind the compute stream's running step, so the host prepares batch t + 1 while step t computes
-        small = {"eot_rows": (torch.arange(N) * L + eot).to(torch.int32), "eot_pos": eot.to(torch.int32),
-                 "ids": ids_cpu[:, :L].to(torch.int32).contiguous()}
-        # rows sorted by token id: the token-embedding gradient is then an ordered sum per id instead of a scatter of atomics
-        small["tok_order"], small["tok_seg"] = K.token_sort(ids_cpu[:, :L])
+        if pk is None:
+            small = {"eot_rows": (torch.arange(N) * L + eot).to(torch.int32), "eot_pos": eot.to(torch.int32),
+                     "ids": ids_cpu[:, :L].to(torch.int32).contiguous()}
+            # rows sorted by token id: the token-embedding gradient is then an ordered sum per id instead of a scatter of atomics
+            small["tok_order"], small["tok_seg"] = K.token_sort(ids_cpu[:, :L])
+        else:  # the packed descriptors instead of the rectangle's: ids [M], seq_start, the EOT rows and the two sort plans
+            small = {k: pk[k] for k in ("eot_rows", "ids", "seq_start", "tok_order", "tok_seg", "pos_order", "pos_seg")}
         keep = None
         if "keep_ind" not in data:
             # device-drawn tube mask: data["mask_seed"] + the global number of the batch's first sample
@@ -1302,9 +1338,12 @@ class Engine:
         d = self._stage_small(small)
         if keep is None:
             keep = d["keep"]
-        return dict(video=video, crop=d.get("crop", crop), resize=resize, ids=d["ids"], tok_sort=(d["tok_order"], d["tok_seg"]),
-                    eot_rows=d["eot_rows"], eot_index=(None, d["eot_pos"]), keep=keep, B=B, T=T, N=N, NT=NT, L=L, n=n, S=S,
-                    sort_rows=d["sort_rows"], vid_rows=d["vid_rows"], labels=d.get("labels"))
+        pb = dict(video=video, crop=d.get("crop", crop), resize=resize, ids=d["ids"], tok_sort=(d["tok_order"], d["tok_seg"]),
+                  eot_rows=d["eot_rows"], eot_index=(None, d["eot_pos"]) if pk is None else None, keep=keep, B=B, T=T, N=N, NT=NT, L=L,
+                  n=n, S=S, sort_rows=d["sort_rows"], vid_rows=d["vid_rows"], labels=d.get("labels"))
+        if pk is not None:
+            pb.update(M=int(pk["ids"].numel()), seq_start=d["seq_start"], max_len=pk["max_len"], pos_sort=(d["pos_order"], d["pos_seg"]))
+        return pb
 
     STAGE_SLOTS = 4
 
@@ -1364,7 +1403,8 @@ class Engine:
         text_emb = self._f("mdl.text_emb", (B, E))
         text_before = self._f("mdl.text_before", (B, NT, E))
         with self._text_lane():  # (the text tower beside the ViT when self.text_side, in line otherwise)
-            t = self.text_forward(pb["ids"], pb["eot_rows"], N, L, eot_index=pb.get("eot_index"))
+            t = self.text_forward(pb["ids"], pb["eot_rows"], N, L, eot_index=pb.get("eot_index"),
+                                  packed=pb if pb.get("seq_start") is not None else None)
             K.text_mean(t, text_emb, text_before, NT=NT, B=B)
         out, pooled = self.video_forward(pb["video"], pb["keep"], B, T, vid_rows=pb["vid_rows"])
         if pooled is None:
@@ -1428,7 +1468,8 @@ class Engine:
             dt = self._f("mdl.dt", (N, E))
             with self._text_lane():  # beside the sort head's and the ViT's backward when self.text_side; joined at the end
                 K.text_mean_bwd(d_text, dt, NT=NT, B=B)
-                self.text_backward(dt, pb["ids"], pb["eot_rows"], N, L, tok_sort=pb.get("tok_sort"))
+                self.text_backward(dt, pb["ids"], pb["eot_rows"], N, L, tok_sort=pb.get("tok_sort"),
+                                   packed=pb if pb.get("seq_start") is not None else None)
                 if self.text_side and (self.grad_ready is not None or self.param_ready is not None):
                     text_ready_at_join = True
                 else:

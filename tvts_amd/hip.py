@@ -722,16 +722,37 @@ def attn_fwd_first(qkv, kv_len, out, lse2, *, B, heads, S, head_dim=64):
          "tvts_attn_fwd_first")
 
 
-def attn_fwd_packed(qkv, seq_start, out, *, N, heads, max_len, last_only=False):
+def attn_fwd_packed(qkv, seq_start, out, *, N, heads, max_len, last_only=False, lse2=None):
     """causal attention inside each sequence of a packed batch (seq_start int32 [N + 1], rows seq_start[i] .. seq_start[i + 1] - 1),
-    head dim 64, forward-only.  last_only: one query per sequence at its last row; only those N rows of out are written."""
+    head dim 64.  last_only: one query per sequence at its last row; only those N rows of out are written.  lse2 (fp32 [M, heads]):
+    the training entries -- the same kernels and the same bits in out, and the log-sum-exp of every row they compute stored for
+    attn_bwd_packed."""
     lib = _lib.load()
     assert seq_start.dtype == torch.int32 and seq_start.numel() == N + 1
     M = qkv.shape[0]
     assert out.shape[0] == M
-    fn = lib.tvts_attn_fwd_packed_last if last_only else lib.tvts_attn_fwd_packed
-    _chk(fn(_p(qkv), _ld(qkv), _p(seq_start), N, M, heads, max_len, _p(out), _ld(out), _stream()),
-         "tvts_attn_fwd_packed_last" if last_only else "tvts_attn_fwd_packed")
+    name = "tvts_attn_fwd_packed" + ("_last" if last_only else "") + ("_lse" if lse2 is not None else "")
+    args = (_p(qkv), _ld(qkv), _p(seq_start), N, M, heads, max_len, _p(out), _ld(out))
+    if lse2 is not None:
+        assert lse2.dtype == torch.float32 and lse2.is_contiguous() and lse2.numel() >= M * heads
+        args += (_p(lse2),)
+    _chk(getattr(lib, name)(*args, _stream()), name)
+
+
+def attn_bwd_packed(qkv, seq_start, dO, O, lse2, delta, dqkv, *, N, heads, max_len, last_only=False):
+    """backward of attn_fwd_packed(..., lse2=...) into dqkv bf16 [M, 3W] (contiguous or a row-major view with a wider leading
+    dimension, a multiple of 8): every row of a valid sequence is written in all three thirds, so dqkv needs no zeroing -- with
+    last_only the KERNEL zeroes the dQ third of the rows that are no sequence's last one (no _zero_rows here).  delta fp32 [M, heads] is
+    written on the way.  One wave owns a (sequence, head) group: no atomics, two runs give the same bits."""
+    lib = _lib.load()
+    assert seq_start.dtype == torch.int32 and seq_start.numel() == N + 1
+    M = qkv.shape[0]
+    assert dO.shape[0] == M and O.shape[0] == M and dqkv.shape[0] == M
+    assert lse2 is None or (lse2.dtype == torch.float32 and lse2.numel() >= M * heads)
+    assert delta is None or (delta.dtype == torch.float32 and delta.numel() >= M * heads)
+    name = "tvts_attn_bwd_packed_last" if last_only else "tvts_attn_bwd_packed"
+    _chk(getattr(lib, name)(_p(qkv), _ld(qkv), _p(seq_start), N, M, heads, max_len, _p(dO), _ld(dO), _p(O), _ld(O), _p(lse2), _p(delta),
+                            _p(dqkv), _ld(dqkv), _stream()), name)
 
 
 def attn_bwd_rowq(qkv, qpos, dO, O, lse2, delta, dqkv, *, B, heads, S, head_dim=64):
@@ -1092,6 +1113,47 @@ def text_embed_bwd(dx, ids, demb, dpos, *, N, L, tok_sort=None):
         assert order.dtype == torch.int32 and seg.dtype == torch.int32 and order.numel() == N * L and seg.numel() == N * L + 1
     _chk(lib.tvts_text_embed_bwd(_p(dx), _ld(dx), _p(ids), ids.stride(0), N, L, dx.shape[1], _p(demb), _p(dpos),
                                  _p(order), _p(seg), _stream()), "tvts_text_embed_bwd")
+
+
+def pack_captions(ids_cpu, context=None):
+    """The host half of the packed text tower: [N, L] token ids (a host tensor; the EOT token is each row's largest id,
+    CLIP/clip/model.py:343-354) -> the descriptors of the packed batch, all host tensors, no device access:
+    ids int32 [M] (caption i's tokens up to and including its EOT, captions in the given order), seq_start int32 [N + 1],
+    eot_rows int32 [N] (= seq_start[1:] - 1), max_len (int), tok_order / tok_seg (token_sort of the packed ids) and
+    pos_order int32 [M] / pos_seg int32 [context + 1]: the rows sorted stably by their position inside their caption and the starts
+    of the runs of equal position (context: the rows of the positional table, default L)."""
+    import numpy as np
+    assert ids_cpu.dim() == 2 and ids_cpu.shape[0] > 0 and ids_cpu.shape[1] > 0 and not ids_cpu.is_cuda
+    a = ids_cpu.numpy()
+    N, L = a.shape
+    context = L if context is None else int(context)
+    lens = a.argmax(axis=1).astype(np.int64) + 1
+    if int(lens.max()) > context:
+        raise ValueError(f"a caption of {int(lens.max())} tokens does not fit the context of {context}")
+    seq_start = np.zeros(N + 1, dtype=np.int64)
+    np.cumsum(lens, out=seq_start[1:])
+    M = int(seq_start[N])
+    pos = np.arange(M, dtype=np.int64) - np.repeat(seq_start[:-1], lens)
+    ids = a[np.repeat(np.arange(N), lens), pos].astype(np.int32)
+    pos_seg = np.zeros(context + 1, dtype=np.int64)
+    np.cumsum(np.bincount(pos, minlength=context), out=pos_seg[1:])
+    tok_order, tok_seg = token_sort(torch.from_numpy(ids))
+    i32 = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32))  # noqa: E731
+    return dict(ids=torch.from_numpy(ids), seq_start=i32(seq_start), eot_rows=i32(seq_start[1:] - 1), max_len=int(lens.max()),
+                tok_order=tok_order, tok_seg=tok_seg, pos_order=i32(np.argsort(pos, kind="stable")), pos_seg=i32(pos_seg))
+
+
+def text_embed_bwd_packed(dx, ids, seq_start, demb, dpos, *, N, tok_sort, pos_sort):
+    """demb[ids[r]] += dx[r], dpos[r - seq_start[seq(r)]] += dx[r] over the M packed rows as ordered sums (no atomic form):
+    tok_sort = (tok_order, tok_seg), pos_sort = (pos_order, pos_seg) device tensors of pack_captions()."""
+    lib = _lib.load()
+    M = ids.numel()
+    (to, ts), (po, ps) = tok_sort, pos_sort
+    assert ids.dtype == torch.int32 and seq_start.dtype == torch.int32 and seq_start.numel() == N + 1 and dx.shape[0] >= M
+    assert all(t.dtype == torch.int32 for t in (to, ts, po, ps))
+    assert to.numel() == M and ts.numel() == M + 1 and po.numel() == M and ps.numel() == dpos.shape[0] + 1
+    _chk(lib.tvts_text_embed_bwd_packed(_p(dx), _ld(dx), _p(ids), _p(seq_start), N, M, dx.shape[1], demb.shape[0], dpos.shape[0],
+                                        _p(demb), _p(dpos), _p(to), _p(ts), _p(po), _p(ps), _stream()), "tvts_text_embed_bwd_packed")
 
 
 def text_mean(t, mean, before, *, NT, B):

@@ -209,6 +209,10 @@ class GraphReplay:
         m._sync_requires_grad()
         pb = r.eng.prepare_batch(data)
         labels = r._labels(data, pb)
+        if pb.get("seq_start") is not None:
+            # packed captions (arch["text_packed"]): M and max_len change with every batch, a graph would never be replayed -- eager
+            self.eager += 1
+            return r.run(pb, labels, device_step=True)
         sig = (_signature(pb), None if labels is None else tuple(labels.shape), bool(m.training),
                hash(tuple(r.eng.requires_grad.values())) if hasattr(r.eng, "requires_grad") else None)
         ent = self.cache.get(sig)
