@@ -451,52 +451,57 @@ int tvts_vit_assemble(const float* patch, int ldp, const float* cls, const float
 int tvts_vit_assemble_bwd(const float* dtok, int ldt, const int* keep, int keep_per_frame, int B, int T, int n, int W,
                           void* dpatch, int ldp, float* dcls, float* dpos, int n_pos, float* dtemporal, float* workspace,
                           long workspace_elems, hipStream_t stream);
-/* v1 (TVTS) Conv3d tubelet embedding as im2col over the kept patches of every tube (v1/model/video_encoder.py:78-99,199-206):
- * video fp32 [B, tubes * tubelet, 3, img, img], keep int32 [B, tubes, n] -> bf16 rows [B * tubes * n, 3 * tubelet * patch^2]
- * in the Conv3d weight's (c, t, py, px) column order; patch % 8 == 0 */
+/* ---- v1 (TVTS) Conv3d tubelet embedding as im2col over the kept patches of every tube (v1/model/video_encoder.py:78-99,199-206):
+ * keep int32 [B, tubes, n] -> bf16 rows [B * tubes * n, 3 * tubelet * patch^2] in the Conv3d weight's (c, t, py, px) column order.
+ * The seven entry points below are ONE kernel frame (embed.hip: tube_gather_kernel -- row and column decode, keep lookup, the
+ * optional mix, the bf16 rounding and the store) over four source policies (fp32 clip, uint8 crop, uint8 view, uint8 augmentation), so
+ * every "same bits as" statement below holds by construction: the forms named share the frame, and the uint8 forms share one
+ * normalise expression, bf16((u / 255.0f - mean) / std) with the operations and their order those of tvts_patch_gather_u8 -- the
+ * bytes of the fp32 forms on host-normalised frames.
+ * All seven return -22 for: a NULL source / keep / out (and mean3 / std3, HOST arrays, in the uint8 forms; and the form's table);
+ * B, tubes, tubelet, n, patch or img <= 0; img % patch; patch % 8; ldo % 8 or ldo < 3 * tubelet * patch^2 (a wider leading dimension
+ * is left untouched); out not 16-byte aligned; an fp32 video not 16-byte aligned; H0 < img or W0 < img where a crop of img x img is
+ * cut from the frames (all uint8 forms but _aug).  crop and the tables are DEVICE data and are not checked: the caller keeps them in
+ * range (tvts_amd.hip.mix_table / aug_table / view_table do); a crop outside the frame reads outside the frames.
+ * video fp32 [B, tubes * tubelet, 3, img, img]: */
 int tvts_patch_gather_tube(const float* video, const int* keep, int B, int tubes, int tubelet, int n, int img, int patch,
                            void* out, int ldo, hipStream_t stream);
-/* the same gather for CHANNEL-MAJOR fp32 clips [B, 3, tubes * tubelet, img, img], the layout the v1 downstream classes take
- * (v1/downstream/video_encoder_zero.py:91-96,177: forward_features hands x to the Conv3d as it comes); ldo % 8 == 0 and
- * ldo >= 3 * tubelet * patch^2 here and in the uint8 form (a wider leading dimension is left untouched) */
+/* CHANNEL-MAJOR fp32 clips [B, 3, tubes * tubelet, img, img], the layout the v1 downstream classes take
+ * (v1/downstream/video_encoder_zero.py:91-96,177: forward_features hands x to the Conv3d as it comes): the same frame and load, so
+ * the bytes of tvts_patch_gather_tube on the permuted clip */
 int tvts_patch_gather_tube_cm(const float* video, const int* keep, int B, int tubes, int tubelet, int n, int img, int patch,
                               void* out, int ldo, hipStream_t stream);
-/* ... and for uint8 frames [B, tubes * tubelet, H0, W0, 3]: crop (device [B,2] (top, left), or NULL for the centre crop with the
- * round-half-to-even offsets of tvts_patch_gather_u8) + ClipToTensor + Normalize of the v1 downstream pipeline
- * (v1/downstream/ssv2.py:61-63) fused into the tubelet gather: out = bf16((u / 255.0f - mean) / std), the operations and their order
- * those of tvts_patch_gather_u8, so the bytes equal tvts_patch_gather_tube's on host-normalised frames.  mean3 / std3 are HOST
- * arrays; patch % 8 == 0, img > 0, H0 >= img, W0 >= img.  crop is DEVICE data and is not checked: the caller keeps
- * 0 <= top <= H0 - img and 0 <= left <= W0 - img for every sample (a crop outside reads outside the frames) */
+/* uint8 frames [B, tubes * tubelet, H0, W0, 3]: crop (device [B,2] (top, left), 0 <= top <= H0 - img and 0 <= left <= W0 - img, or
+ * NULL for the centre crop with the round-half-to-even offsets of tvts_patch_gather_u8) + ClipToTensor + Normalize of the v1
+ * downstream pipeline (v1/downstream/ssv2.py:61-63) fused into the gather */
 int tvts_patch_gather_tube_u8(const unsigned char* frames, int H0, int W0, const int* crop, const int* keep, int B, int tubes,
                               int tubelet, int n, int img, int patch, const float* mean3, const float* std3, void* out, int ldo,
                               hipStream_t stream);
 /* Mixup / CutMix of the v1 fine-tuning recipe (v1/downstream/mixup.py:152-200 `_mix_elem` / `_mix_pair` / `_mix_batch`, applied as
- * `samples, targets = mixup_fn(samples, targets)` at v1/downstream/engine_for_finetuning.py:58-59) fused into the channel-major
- * gather: tvts_patch_gather_tube_cm with the mix applied per element in front of the bf16 rounding.  The step's draw is a
- * per-sample table in DEVICE memory: mix_i int32 [B, 6] = (partner, mode, yl, yh, xl, xh), mode 0 none / 1 mixup / 2 cutmix / 3
- * pair-mode cutmix (below), the box half-open in image coordinates behind the crop; mix_f fp32 [B, 2] = (lam, one_minus_lam), both rounded by the host.
+ * `samples, targets = mixup_fn(samples, targets)` at v1/downstream/engine_for_finetuning.py:58-59) applied by the frame per element in
+ * front of the bf16 rounding, here over tvts_patch_gather_tube_cm's source.  The step's draw is a per-sample table in DEVICE memory:
+ * mix_i int32 [B, 6] = (partner, mode, yl, yh, xl, xh), mode 0 none / 1 mixup / 2 cutmix / 3 pair-mode cutmix (below), the box
+ * half-open in image coordinates behind the crop, 0 <= lo <= hi <= img; mix_f fp32 [B, 2] = (lam, one_minus_lam), both rounded by the host.
  * mode 0: the own value, bits untouched; mode 1: fadd_rn(fmul_rn(own, lam), fmul_rn(partner, one_minus_lam)) (two rounded
  * products, then the sum: mixup.py:198-199, never an FMA); mode 2: the partner's value inside the box of every channel and frame
  * (mixup.py:163,196), the own value outside; mode 3: what `_mix_pair` does to a 5-D clip batch -- `x[i][:, yl:yh, xl:xh]`
  * (mixup.py:180-181) slices a [C, T, H, W] clip by (frame, row): the partner's value in the frames [yl, yh) (cut at T) and the rows
- * [xl, xh) of every channel, whole rows; the own value elsewhere.  One table serves the reference's batch / pair / elem modes.  video and out 16-byte
- * aligned, otherwise the conditions of tvts_patch_gather_tube_cm.  The table is DEVICE data and is not checked here (like crop): the
- * caller keeps 0 <= partner < B, mode in {0, 1, 2, 3} and 0 <= lo <= hi <= img; a partner outside [0, B) leaves that sample's rows
- * unwritten. */
+ * [xl, xh) of every channel, whole rows; the own value elsewhere.  One table serves the reference's batch / pair / elem modes.
+ * A partner outside [0, B) leaves that sample's rows unwritten. */
 int tvts_patch_gather_tube_cm_mix(const float* video, const int* keep, const int* mix_i, const float* mix_f, int B, int tubes,
                                   int tubelet, int n, int img, int patch, void* out, int ldo, hipStream_t stream);
-/* the same mix (v1/downstream/mixup.py:152-200) for uint8 frames: each of the two samples is cropped with ITS OWN crop offset and
- * normalised as tvts_patch_gather_tube_u8 does, the normalised fp32 values are mixed as above and rounded to bf16 -- the bytes
- * equal tvts_patch_gather_tube_cm_mix's on host-cropped, host-normalised frames.  out 16-byte aligned; crop and the table are
- * DEVICE data and are not checked. */
+/* the same mix over tvts_patch_gather_tube_u8's source: each of the two samples is cropped with ITS OWN crop offset and normalised,
+ * the normalised fp32 values are mixed and rounded to bf16 -- the bytes of tvts_patch_gather_tube_cm_mix on host-cropped,
+ * host-normalised frames */
 int tvts_patch_gather_tube_u8_mix(const unsigned char* frames, int H0, int W0, const int* crop, const int* keep, const int* mix_i,
                                   const float* mix_f, int B, int tubes, int tubelet, int n, int img, int patch, const float* mean3,
                                   const float* std3, void* out, int ldo, hipStream_t stream);
-/* The per-sample augmentation of the v1 fine-tuning recipe behind RandAugment (v1/downstream/ssv2.py:186-227) fused into the uint8
- * gather: Normalize, `random_resized_crop` (v1/downstream/video_transforms.py:499-573: `_get_param_spatial_crop`, then torch's
+/* The per-sample augmentation of the v1 fine-tuning recipe behind RandAugment (v1/downstream/ssv2.py:186-227) as the frame's source:
+ * Normalize, `random_resized_crop` (v1/downstream/video_transforms.py:499-573: `_get_param_spatial_crop`, then torch's
  * bilinear `interpolate(..., align_corners=False)` of the crop to img x img), `horizontal_flip` (video_transforms.py:156-177),
- * `RandomErasing._erase_cube` (v1/downstream/random_erasing.py:109-149), then the mix of tvts_patch_gather_tube_u8_mix.  frames
- * uint8 [Bs, T, H0, W0, 3]; H0, W0 >= 1 (source frames may be smaller than img).  The draw is a per-sample table in DEVICE memory:
+ * `RandomErasing._erase_cube` (v1/downstream/random_erasing.py:109-149), then the frame's mix (mix_i / mix_f both given or both
+ * NULL).  frames uint8 [Bs, T, H0, W0, 3], Bs >= 1; H0, W0 >= 1 (source frames may be smaller than img).  The draw is a per-sample
+ * table in DEVICE memory:
  *   aug_i int32 [B, 16] = (src, top, left, h, w, flip, emode, etop, eleft, eh, ew, key_lo, key_hi, 0, 0, 0)
  * src: the source clip in [0, Bs) -- several samples may name one clip (the two views of `--num_sample 2`,
  * v1/downstream/utils.py `multiple_samples_collate`); [top, top + h) x [left, left + w): the crop in the source frame, 1 <= h <= H0,
@@ -506,38 +511,32 @@ int tvts_patch_gather_tube_u8_mix(const unsigned char* frames, int H0, int W0, c
  * Output element (b, c, f, y, x), in this order:
  *   taps   sy = (float)h / (float)img, s = max(sy * (y + 0.5f) - 0.5f, 0), y0 = (int)s, y1 = min(y0 + 1, h - 1) (the crop's edge, not
  *          the frame's), ly = s - y0; the same in x with w, x replaced by img - 1 - x first under flip.  fp32, every operation rounded.
- *   values the four taps of frame src * T + f at (top + y., left + x.), each (u / 255.0f - mean) / std as tvts_patch_gather_tube_u8
+ *   values the four taps of frame src * T + f at (top + y., left + x.), each normalised by the shared expression
  *   blend  (1 - ly) * ((1 - lx) * a + lx * b) + ly * ((1 - lx) * c + lx * d), every product and sum rounded to fp32 (no FMA).  With
  *          h == w == img, flip == 0, emode == 0 every l is 0 and the bits are tvts_patch_gather_tube_u8's with crop = (top, left).
  *   erase  inside the box: const 0.0f; pixel z(key, ((f * 3 + c) * img + y) * img + x); rand z(key + 0xD1B54A32D192ED03, f * 3 + c).  The
  *          index is in output coordinates: a pixel's noise depends on neither keep, the patch size nor the thread that holds it.
- *   mix    (mix_i / mix_f given) mix_apply of tvts_patch_gather_tube_cm_mix over this value and the partner's, the partner taken
- *          through ITS OWN crop, flip and erase; then ONE rounding to bf16.
+ *   mix    the frame's mix over this value and the partner's, the partner taken through ITS OWN crop, flip and erase; then ONE
+ *          rounding to bf16.
  * z(key, idx): r = mix(key + idx * 0x9E3779B97F4A7C15) with the splitmix64 finaliser of the dropout masks above; u1 = ((r >> 32) + 1)
  * * 2^-32 in (0, 1], u2 = (r & 0xffffffff) * 2^-32, z = sqrtf(-2 logf(u1)) * cosf(2 pi u2), the accurate library functions, ln u1
  * taken as log1pf(u1 - 1) where u1 is within 2^-8 of 1 (an fp32 u1 has lost ln u1 there): within 2e-5 of the rule evaluated in
  * float64, which is its definition.  The reference draws this noise from
  * torch's CPU generator (random_erasing.py:11-24 `_get_pixels`); that stream is not reproduced.
- * Returns -22 for a NULL among frames / keep / aug_i / out / mean3 / std3, exactly one of mix_i / mix_f NULL, Bs <= 0, H0 or W0 <= 0,
- * the shape conditions of tvts_patch_gather_tube_u8_mix (without H0, W0 >= img) and out not 16-byte aligned.  The tables are DEVICE
- * data and are not checked: the caller keeps every column in range (tvts_amd.hip.aug_table does); a src outside [0, Bs) -- the
- * sample's own or, under a mix, its partner's -- leaves that sample's rows unwritten and reads nothing. */
+ * A src outside [0, Bs) -- the sample's own or, under a mix, its partner's -- leaves that sample's rows unwritten and reads nothing. */
 int tvts_patch_gather_tube_u8_aug(const unsigned char* frames, int Bs, int H0, int W0, const int* keep, const int* aug_i,
                                   const int* mix_i, const float* mix_f, int B, int tubes, int tubelet, int n, int img, int patch,
                                   const float* mean3, const float* std3, void* out, int ldo, hipStream_t stream);
-/* The test views of v1/downstream/ssv2.py:132-164 (mode 'test') formed inside the uint8 tubelet gather: every sample is a strided run
- * of frames of a source clip, cropped at an offset -- `buffer[temporal_start::2, spatial_start:spatial_start + short_side_size]` --
- * so the test_num_segment x test_num_crop views of a video read ONE uploaded clip.  frames uint8 [Bs, Tsrc, H0, W0, 3]; the views are
- * a per-sample table in DEVICE memory:
+/* The test views of v1/downstream/ssv2.py:132-164 (mode 'test') as the frame's source: every sample is a strided run of frames of
+ * a source clip, cropped at an offset -- `buffer[temporal_start::2, spatial_start:spatial_start + short_side_size]` -- so the
+ * test_num_segment x test_num_crop views of a video read ONE uploaded clip.  frames uint8 [Bs, Tsrc, H0, W0, 3], Bs, Tsrc >= 1; the
+ * views are a per-sample table in DEVICE memory:
  *   view_i int32 [B, 8] = (src, t0, tstep, top, left, 0, 0, 0)
- * frame f (0 <= f < tubes * tubelet) of sample b is frame t0 + f * tstep of source clip src, cropped to [top, top + img) x [left,
- * left + img); several samples may name one clip.  Every element is bf16((u / 255.0f - mean) / std), the operations and order of
- * tvts_patch_gather_tube_u8: the bytes equal that kernel's on the host-sliced clip frames[src, t0::tstep][:T, top:top + img,
- * left:left + img].  No resampling: the short-side Resize in front of the slicing (ssv2.py:147) is the host's, beside decoding.
- * Returns -22 for a NULL among frames / view_i / keep / out / mean3 / std3, Bs, Tsrc, H0 or W0 <= 0, the shape conditions of
- * tvts_patch_gather_tube_u8 (H0, W0 >= img among them) and out not 16-byte aligned.  The table is DEVICE data and is not checked: the
- * caller keeps t0 + (T - 1) * tstep < Tsrc and the crop inside the frame (tvts_amd.hip.view_table does); a src outside [0, Bs) leaves
- * that sample's rows unwritten and reads nothing. */
+ * frame f (0 <= f < tubes * tubelet) of sample b is frame t0 + f * tstep < Tsrc of source clip src, cropped to [top, top + img) x
+ * [left, left + img); several samples may name one clip.  Only the source address differs from tvts_patch_gather_tube_u8: the bytes
+ * equal its bytes on the host-sliced clip frames[src, t0::tstep][:T, top:top + img, left:left + img].  No resampling: the short-side
+ * Resize in front of the slicing (ssv2.py:147) is the host's, beside decoding.  A src outside [0, Bs) leaves that sample's rows
+ * unwritten and reads nothing. */
 int tvts_patch_gather_tube_u8_view(const unsigned char* frames, int Bs, int Tsrc, int H0, int W0, const int* view_i, const int* keep,
                                    int B, int tubes, int tubelet, int n, int img, int patch, const float* mean3, const float* std3,
                                    void* out, int ldo, hipStream_t stream);

@@ -64,6 +64,18 @@ def test_tube_gathers_refuse_bad_arguments(lib):
     assert cm(0, 16, 3 * 2 * 256) == -22               # img <= 0 (0 % patch == 0 would pass the divisibility test)
     assert cm(-32, 16, 3 * 2 * 256) == -22
     assert cm(32, 16, 3 * 2 * 256, video=None) == -22
+    # the 16-byte conditions of the shared frame (the bf16x8 store of every form, the f32x4 loads of the fp32 forms) and the NULL
+    # pointers of tvts_patch_gather_tube; everything else about these calls is valid
+    room = ctypes.create_string_buffer(96)
+    at = lambda off: ctypes.c_void_p(((ctypes.addressof(room) + 15) & ~15) + off)  # noqa: E731
+    assert lib.tvts_patch_gather_tube_u8(_buf(), 40, 40, None, _buf(), 2, 3, 2, 4, 32, 16, m3, s3, at(8), 3 * 2 * 256, None) == -22
+    assert lib.tvts_patch_gather_tube_cm(at(0), _buf(), 2, 3, 2, 4, 32, 16, at(8), 3 * 2 * 256, None) == -22
+    assert lib.tvts_patch_gather_tube_cm(at(4), _buf(), 2, 3, 2, 4, 32, 16, at(0), 3 * 2 * 256, None) == -22
+    tube = lambda video=at(0), keep=_buf(), out=at(0), ldo=3 * 2 * 256: lib.tvts_patch_gather_tube(  # noqa: E731
+        video, keep, 2, 3, 2, 4, 32, 16, out, ldo, None)
+    assert tube(video=None) == -22 and tube(keep=None) == -22 and tube(out=None) == -22
+    assert tube(video=at(4)) == -22 and tube(out=at(8)) == -22
+    assert tube(ldo=3 * 2 * 256 + 4) == -22 and tube(ldo=3 * 2 * 256 - 8) == -22
 
 
 def test_v2v_ranks_refuses_bad_arguments(lib):

@@ -13,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 import kernel_bounds as KB  # noqa: E402
 import v1_downstream_synth as S  # noqa: E402
+from v1_gather_ref import MEAN, STD, im2col_ref as _im2col_ref, normalise_u8  # noqa: E402
 from oracle import tvts_v1_oracle as V  # noqa: E402  (checker only)
 
 DEV = "cuda:0"
@@ -20,7 +21,6 @@ ARGS = types.SimpleNamespace(local_rank=0, rank=0, world_size=1)
 HEADS = 3  # an odd count: a wrong head-column stride cannot land on another head's slice of the same row
 BF16 = torch.bfloat16
 NAN = float("nan")
-MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 
 
 @pytest.fixture(scope="module")
@@ -105,14 +105,6 @@ def test_attn_fwd_len_without_lse_gives_the_same_bits(K, S):
 
 
 # ------------------------------------------------------------------------------------------------ 2. tubelet gathers
-def _im2col_ref(video, keep, tb, p):
-    """video fp32 [B, T, 3, img, img], keep int64 [B, tubes, n] -> [B * tubes * n, 3 * tb * p * p] in (c, t, py, px) order"""
-    B, T, _, img, _ = video.shape
-    tubes, g = T // tb, img // p
-    x = video.reshape(B, tubes, tb, 3, g, p, g, p).permute(0, 1, 4, 6, 3, 2, 5, 7).reshape(B, tubes, g * g, -1)
-    return torch.gather(x, 2, keep[..., None].expand(-1, -1, -1, x.shape[-1])).reshape(B * tubes * keep.shape[2], -1)
-
-
 @pytest.mark.parametrize("full", [False, True])
 @pytest.mark.parametrize("p", [16, 8])
 def test_tube_gathers_bit_exact(K, p, full):
@@ -126,12 +118,11 @@ def test_tube_gathers_bit_exact(K, p, full):
     keep = torch.stack([torch.stack([torch.randperm(ppf, generator=g)[:n] for _ in range(tubes)]) for _ in range(B)])
     assert n == 1 or any(not torch.equal(keep[b, t], keep[b, t].sort().values) for b in range(B) for t in range(tubes))
     keep_d = keep.to(torch.int32).to(DEV)
-    mean, std = torch.tensor(MEAN).view(1, 1, 1, 1, 3), torch.tensor(STD).view(1, 1, 1, 1, 3)
     Kc, M = 3 * tb * p * p, B * tubes * n
     for name, crop in (("centre", None), ("corners", [[0, 0], [H0 - img, W0 - img]])):
         offs = [[2, 4]] * B if crop is None else crop
         cut = torch.stack([frames[b, :, y:y + img, x:x + img] for b, (y, x) in enumerate(offs)])
-        video = ((cut.float() / 255 - mean) / std).permute(0, 1, 4, 2, 3).contiguous()  # ClipToTensor + Normalize, [B, T, 3, H, W]
+        video = normalise_u8(cut).permute(0, 1, 4, 2, 3).contiguous()  # ClipToTensor + Normalize, [B, T, 3, H, W]
         want = _im2col_ref(video, keep, tb, p).bfloat16()
         what = f"tube gather[p {p}, n {n}, crop {name}]"
         crop_d = None if crop is None else torch.tensor(crop, dtype=torch.int32, device=DEV)

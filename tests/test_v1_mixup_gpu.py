@@ -265,6 +265,17 @@ def test_einval_for_each_refused_argument(K):
             args = dict(base)
             args[key] = val
             assert fn(*args.values(), st) == EINVAL, (fn.__name__, key, val)
+    # the unmixed forms of the same frame: the alignment conditions, and the NULL pointers of tvts_patch_gather_tube (nothing is
+    # read before the refusal, so the channel-major clip stands in for a frame-major one)
+    plain, plain_u8 = ({k: v for k, v in d.items() if k not in ("mix_i", "mix_f")} for d in (cm, u8))
+    for fn, base, bad in ((lib.tvts_patch_gather_tube, plain, [("video", None), ("keep", None), ("out", None), ("video", _ptr(clip, 4)),
+                                                               ("out", _ptr(out, 8))]),
+                          (lib.tvts_patch_gather_tube_cm, plain, [("video", _ptr(clip, 4)), ("out", _ptr(out, 8))]),
+                          (lib.tvts_patch_gather_tube_u8, plain_u8, [("out", _ptr(out, 8))])):
+        for key, val in bad:
+            args = dict(base)
+            args[key] = val
+            assert fn(*args.values(), st) == EINVAL, (fn.__name__, key, val)
     lab = torch.zeros(B, dtype=torch.int32, device=DEV)
     tout = torch.full((B + 1, 16), NAN, dtype=F32, device=DEV)
     mt = dict(labels=_ptr(lab), mix_i=_ptr(mi), mix_f=_ptr(mf), B=B, C=5, smoothing=0.1, out=_ptr(tout), ldo=16)

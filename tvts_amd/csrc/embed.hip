@@ -3,6 +3,9 @@
 //  tvts_patch_gather        kept patches of every frame -> bf16 im2col rows [B*T*n, 3*p*p] in conv-weight order
 //                           (v2/model/video_encoder_ViT_B_16.py:180-184 + tube-mask gather :201-215; only kept
 //                           patches are embedded -- output-equivalent)
+//  tvts_patch_gather_tube*  the v1 tubelet (Conv3d) form of the same im2col: seven entry points -- fp32 clips frame- or channel-major,
+//                           uint8 frames behind a crop, test views, random-resized crop / flip / erase, each of the fine-tuning
+//                           forms with Mixup / CutMix -- over ONE kernel frame (tube_gather_kernel) and four source policies
 //  tvts_vit_assemble(+_bwd) CLS + patch embedding + spatial/temporal position (:185-198) -> tokens [B*S, W]
 //  tvts_text_embed(+_bwd)   token embedding gather + positional add (model_dist_TVTSv2_ViT_B_16.py:98-100)
 //  tvts_text_mean(+_bwd)    clip-major captions [NT*B,E] -> mean over NT and the [B,NT,E] copy for the sort head (:69-76)
@@ -65,161 +68,29 @@ extern "C" int tvts_patch_gather(const float* video, const int* keep, int B, int
     return TVTS_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- v1 tubelet gathers
 // v1 (TVTS) tubelet embedding: Conv3d(3, W, kernel = stride = (tb, p, p)) over [B, C, T, H, W] (v1/model/video_encoder.py:78-99)
 // as an im2col product over the KEPT patches of every tube only.  Row (b, tube, i) = patch keep[b, tube, i] of tube `tube`,
 // columns in the Conv3d weight's (c, t, py, px) order: K = 3 * tb * p * p.  keep differs from tube to tube here
-// (v1/data_loader/YTTemporal_dataset.py:211-215); video arrives as [B, T, 3, H, W] (the model permutes it itself, :179).
-__global__ __launch_bounds__(256) void patch_gather_tube_kernel(const float* __restrict__ video, const int* __restrict__ keep,
-                                                                int B, int tubes, int tb, int n, int img, int p,
-                                                                bf16* __restrict__ out, int ldo) {
-    const int pp = p * p, K = 3 * tb * pp;
-    const int row = blockIdx.x;  // (b, tube, i)
-    const int i = row % n, tu = (row / n) % tubes, b = row / (n * tubes);
-    const int g = img / p;
-    const int pi = keep[(size_t)(b * tubes + tu) * n + i];
-    const int gy = pi / g, gx = pi % g;
-    const int T = tubes * tb;
-    for (int c8 = threadIdx.x * 8; c8 < K; c8 += 256 * 8) {
-        const int ch = c8 / (tb * pp), r1 = c8 % (tb * pp), t = r1 / pp, rem = r1 % pp, py = rem / p, px = rem % p;  // px % 8 == 0
-        const float* src = video + ((((size_t)(b * T + tu * tb + t) * 3 + ch) * img + gy * p + py) * img + gx * p + px);
-        const f32x4 a = *(const f32x4*)src, c = *(const f32x4*)(src + 4);
-        bf16x8 o = {(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], (bf16)c[0], (bf16)c[1], (bf16)c[2], (bf16)c[3]};
-        *(bf16x8*)(out + (size_t)row * ldo + c8) = o;
-    }
-}
-extern "C" int tvts_patch_gather_tube(const float* video, const int* keep, int B, int tubes, int tubelet, int n, int img,
-                                      int patch, void* out, int ldo, hipStream_t stream) {
-    if (B <= 0 || tubes <= 0 || tubelet <= 0 || n <= 0 || patch <= 0 || img % patch || patch % 8 || ldo != 3 * tubelet * patch * patch)
-        return TVTS_EINVAL;
-    hipLaunchKernelGGL(patch_gather_tube_kernel, dim3(B * tubes * n), dim3(256), 0, stream, video, keep, B, tubes, tubelet, n, img,
-                       patch, (bf16*)out, ldo);
-    TVTS_LAUNCH_CHECK();
-    return TVTS_OK;
-}
-
-// The same gather for CHANNEL-MAJOR clips [B, 3, T, H, W], the layout the v1 downstream classes take (their forward hands x to the
-// Conv3d as it comes, v1/downstream/video_encoder_zero.py:91-96,177): only the source address differs from the kernel above.
-__global__ __launch_bounds__(256) void patch_gather_tube_cm_kernel(const float* __restrict__ video, const int* __restrict__ keep,
-                                                                   int B, int tubes, int tb, int n, int img, int p,
-                                                                   bf16* __restrict__ out, int ldo) {
-    const int pp = p * p, K = 3 * tb * pp;
-    const int row = blockIdx.x;  // (b, tube, i)
-    const int i = row % n, tu = (row / n) % tubes, b = row / (n * tubes);
-    const int g = img / p;
-    const int pi = keep[(size_t)(b * tubes + tu) * n + i];
-    const int gy = pi / g, gx = pi % g;
-    const int T = tubes * tb;
-    for (int c8 = threadIdx.x * 8; c8 < K; c8 += 256 * 8) {
-        const int ch = c8 / (tb * pp), r1 = c8 % (tb * pp), t = r1 / pp, rem = r1 % pp, py = rem / p, px = rem % p;  // px % 8 == 0
-        const float* src = video + ((((size_t)(b * 3 + ch) * T + tu * tb + t) * img + gy * p + py) * img + gx * p + px);
-        const f32x4 a = *(const f32x4*)src, c = *(const f32x4*)(src + 4);
-        bf16x8 o = {(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], (bf16)c[0], (bf16)c[1], (bf16)c[2], (bf16)c[3]};
-        *(bf16x8*)(out + (size_t)row * ldo + c8) = o;
-    }
-}
-extern "C" int tvts_patch_gather_tube_cm(const float* video, const int* keep, int B, int tubes, int tubelet, int n, int img,
-                                         int patch, void* out, int ldo, hipStream_t stream) {
-    if (!video || !keep || !out || B <= 0 || tubes <= 0 || tubelet <= 0 || n <= 0 || patch <= 0 || img <= 0 || img % patch || patch % 8 ||
-        ldo % 8 || ldo < 3 * tubelet * patch * patch)
-        return TVTS_EINVAL;
-    hipLaunchKernelGGL(patch_gather_tube_cm_kernel, dim3(B * tubes * n), dim3(256), 0, stream, video, keep, B, tubes, tubelet, n,
-                       img, patch, (bf16*)out, ldo);
-    TVTS_LAUNCH_CHECK();
-    return TVTS_OK;
-}
-
-// ... and for the uint8 wire format: frames uint8 [B, T, H0, W0, 3] as the decoder leaves them, crop (an offset per sample, or the
-// centre crop with the round-half-to-even offsets of patch_gather_u8_kernel below), ClipToTensor (/ 255) and Normalize
-// ((v - mean) / std) of v1/downstream/ssv2.py:61-63 fused into the tubelet gather.  The operations and their order are those of
-// patch_gather_u8_kernel, so the bytes equal the fp32 kernel's on host-normalised frames.  A thread converts 8 neighbouring px
-// (24 interleaved source bytes apart by 3) and stores them as one 16-byte row piece.
-__global__ __launch_bounds__(256) void patch_gather_tube_u8_kernel(const unsigned char* __restrict__ frames, int H0, int W0,
-                                                                   const int* __restrict__ crop, const int* __restrict__ keep,
-                                                                   int B, int tubes, int tb, int n, int img, int p, float m0,
-                                                                   float m1, float m2, float s0, float s1, float s2,
-                                                                   bf16* __restrict__ out, int ldo) {
-    const int pp = p * p, K = 3 * tb * pp;
-    const int row = blockIdx.x;  // (b, tube, i)
-    const int i = row % n, tu = (row / n) % tubes, b = row / (n * tubes);
-    const int g = img / p;
-    const int pi = keep[(size_t)(b * tubes + tu) * n + i];
-    const int gy = pi / g, gx = pi % g;
-    const int T = tubes * tb;
-    const int dy = H0 - img, dx = W0 - img;
-    const int y0 = crop ? crop[2 * b] : (dy >> 1) + ((dy & 1) & (dy >> 1)), x0 = crop ? crop[2 * b + 1] : (dx >> 1) + ((dx & 1) & (dx >> 1));
-    for (int c8 = threadIdx.x * 8; c8 < K; c8 += 256 * 8) {
-        const int ch = c8 / (tb * pp), r1 = c8 % (tb * pp), t = r1 / pp, rem = r1 % pp, py = rem / p, px = rem % p;  // px % 8 == 0
-        const unsigned char* src = frames + (((size_t)(b * T + tu * tb + t) * H0 + y0 + gy * p + py) * W0 + x0 + gx * p + px) * 3 + ch;
-        const float mean = ch == 0 ? m0 : ch == 1 ? m1 : m2, sd = ch == 0 ? s0 : ch == 1 ? s1 : s2;
-        bf16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float u = (float)src[3 * e];
-            o[e] = (bf16)((u / 255.0f - mean) / sd);
-        }
-        *(bf16x8*)(out + (size_t)row * ldo + c8) = o;
-    }
-}
-extern "C" int tvts_patch_gather_tube_u8(const unsigned char* frames, int H0, int W0, const int* crop, const int* keep, int B,
-                                         int tubes, int tubelet, int n, int img, int patch, const float* mean3, const float* std3,
-                                         void* out, int ldo, hipStream_t stream) {
-    if (!frames || !keep || !out || !mean3 || !std3 || B <= 0 || tubes <= 0 || tubelet <= 0 || n <= 0 || patch <= 0 || img <= 0 || img % patch ||
-        patch % 8 || H0 < img || W0 < img || ldo % 8 || ldo < 3 * tubelet * patch * patch)
-        return TVTS_EINVAL;
-    hipLaunchKernelGGL(patch_gather_tube_u8_kernel, dim3(B * tubes * n), dim3(256), 0, stream, frames, H0, W0, crop, keep, B, tubes,
-                       tubelet, n, img, patch, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (bf16*)out, ldo);
-    TVTS_LAUNCH_CHECK();
-    return TVTS_OK;
-}
-
-// The test views of the fine-tuning scripts (v1/downstream/ssv2.py:132-164) inside the same gather: sample b is the frames t0, t0 +
-// tstep, ... of source clip src, cropped at (top, left) -- `buffer[temporal_start::2, spatial_start:spatial_start + short_side_size]`
-// -- read from a per-sample table in device memory, view_i int32 [B, 8] = (src, t0, tstep, top, left, 0, 0, 0).  Only the source
-// address differs from patch_gather_tube_u8_kernel: the element expression is that kernel's, so the bytes equal its bytes on the
-// host-sliced clip.  The views of one video read one uploaded clip.  A src outside [0, Bs) leaves the sample's rows unwritten.
-__global__ __launch_bounds__(256) void patch_gather_tube_u8_view_kernel(const unsigned char* __restrict__ frames, int Bs, int Tsrc, int H0,
-                                                                        int W0, const int* __restrict__ view_i, const int* __restrict__ keep,
-                                                                        int B, int tubes, int tb, int n, int img, int p, float m0,
-                                                                        float m1, float m2, float s0, float s1, float s2,
-                                                                        bf16* __restrict__ out, int ldo) {
-    const int pp = p * p, K = 3 * tb * pp;
-    const int row = blockIdx.x;  // (b, tube, i)
-    const int i = row % n, tu = (row / n) % tubes, b = row / (n * tubes);
-    const int g = img / p;
-    const int pi = keep[(size_t)(b * tubes + tu) * n + i];
-    const int gy = pi / g, gx = pi % g;
-    const int* v = view_i + 8 * (size_t)b;
-    const int src = v[0], t0 = v[1], tstep = v[2], y0 = v[3], x0 = v[4];
-    if ((unsigned)src >= (unsigned)Bs) return;
-    for (int c8 = threadIdx.x * 8; c8 < K; c8 += 256 * 8) {
-        const int ch = c8 / (tb * pp), r1 = c8 % (tb * pp), t = r1 / pp, rem = r1 % pp, py = rem / p, px = rem % p;  // px % 8 == 0
-        const size_t fr = (size_t)src * Tsrc + t0 + (size_t)(tu * tb + t) * tstep;
-        const unsigned char* s = frames + ((fr * H0 + y0 + gy * p + py) * W0 + x0 + gx * p + px) * 3 + ch;
-        const float mean = ch == 0 ? m0 : ch == 1 ? m1 : m2, sd = ch == 0 ? s0 : ch == 1 ? s1 : s2;
-        bf16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float u = (float)s[3 * e];
-            o[e] = (bf16)((u / 255.0f - mean) / sd);
-        }
-        *(bf16x8*)(out + (size_t)row * ldo + c8) = o;
-    }
-}
-extern "C" int tvts_patch_gather_tube_u8_view(const unsigned char* frames, int Bs, int Tsrc, int H0, int W0, const int* view_i,
-                                              const int* keep, int B, int tubes, int tubelet, int n, int img, int patch,
-                                              const float* mean3, const float* std3, void* out, int ldo, hipStream_t stream) {
-    if (!frames || !view_i || !keep || !out || !mean3 || !std3 || Bs <= 0 || Tsrc <= 0 || H0 <= 0 || W0 <= 0 || B <= 0 || tubes <= 0 ||
-        tubelet <= 0 || n <= 0 || patch <= 0 || img <= 0 || img % patch || patch % 8 || H0 < img || W0 < img || ldo % 8 ||
-        ldo < 3 * tubelet * patch * patch || ((size_t)out % 16))
-        return TVTS_EINVAL;
-    hipLaunchKernelGGL(patch_gather_tube_u8_view_kernel, dim3(B * tubes * n), dim3(256), 0, stream, frames, Bs, Tsrc, H0, W0, view_i, keep,
-                       B, tubes, tubelet, n, img, patch, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (bf16*)out, ldo);
-    TVTS_LAUNCH_CHECK();
-    return TVTS_OK;
-}
+// (v1/data_loader/YTTemporal_dataset.py:211-215).
+//
+// ONE kernel frame, tube_gather_kernel<Src, MIX>, owns what every form shares: the (b, tube, i) row decode, the keep lookup, the
+// column decode, the optional Mixup / CutMix, the bf16 rounding and the 16-byte store.  What differs between the seven entry points
+// is a SOURCE POLICY, a struct passed by value that holds its pointers and geometry and provides
+//     bool resolve(b, Sample&)                 the sample's source; false leaves the sample's rows unwritten (block-uniform)
+//     Block prologue()                         once per block behind the resolves: what the block's loads share (the uint8 policies'
+//                                              normalisation constants; the aug policy's LDS table, behind a barrier)
+//     void load8(Block, Sample, ch, f, y, x, v[8])   the fp32 values of channel ch, frame f, pixels (y, x .. x + 7) of the img x img clip
+// Policies: F32Clip<CM> (fp32 clips, frame- or channel-major), U8Crop (uint8 frames behind a crop offset), U8View (uint8 test views),
+// U8Aug (uint8 random-resized crop, flip and erase).  Two forms that share a policy's load8 share its bits by construction.
+// A policy's operations reach its fields through `this`, i.e. as loads from the kernel's arguments, and a select between two such
+// loads (the channel's mean; a centre-crop offset against crop[b]) is compiled into ONE load through a selected address -- a vector
+// load inside the column loop where a v_cndmask on two scalar registers belongs (+4 % on the uint8 forms).  So what load8 selects
+// between travels BY VALUE, in the Block, and no policy selects between a field and a table entry.
+struct TubeRows { const int* keep; int B, tubes, tb, n, img, p; bf16* out; int ldo; };
 
 // Mixup / CutMix of the v1 fine-tuning recipe (v1/downstream/mixup.py:152-200, applied at engine_for_finetuning.py:58-59) fused
-// into the two gathers the fine-tuning step uses.  The step's draw arrives as a per-sample table in device memory:
+// into the gather.  The step's draw arrives as a per-sample table in device memory:
 //     mix_i int32 [B, 6] = (partner, mode, yl, yh, xl, xh)     mode 0 none, 1 mixup, 2 cutmix; the box in image coordinates
 //                                                              behind the crop, half-open
 //     mix_f fp32  [B, 2] = (lam, one_minus_lam)                both rounded by the host
@@ -231,7 +102,8 @@ extern "C" int tvts_patch_gather_tube_u8_view(const unsigned char* frames, int B
 //         pictures, and on a clip [C, T, H, W] its two slices land on (frame, row): the partner's value in the frames [yl, yh) (cut
 //         at T, as a slice is) and the rows [xl, xh) of every channel, over the whole row width; the own value elsewhere.
 // The select is per element (a thread's 8-pixel group may be cut by xl / xh anywhere); the partner is loaded only by the threads
-// that hold an element needing it.  A partner outside [0, B) leaves the sample's rows unwritten (nothing is read for it).
+// that hold an element needing it, through the policy's own resolve (a uint8 partner takes ITS OWN crop, an augmented one ITS OWN
+// table row).  A partner outside [0, B) leaves the sample's rows unwritten (nothing is read for it).
 struct MixRow { int partner, mode, yl, yh, xl, xh; float lam, oml; };
 __device__ __forceinline__ MixRow mix_row(const int* __restrict__ mix_i, const float* __restrict__ mix_f, int b) {
     const int* mi = mix_i + 6 * (size_t)b;
@@ -249,107 +121,126 @@ __device__ __forceinline__ void mix_apply8(const MixRow& m, int x, float* v, con
         else if (m.mode == 3 || (x + e >= m.xl && x + e < m.xh)) v[e] = w[e];
     }
 }
-__global__ __launch_bounds__(256) void patch_gather_tube_cm_mix_kernel(const float* __restrict__ video, const int* __restrict__ keep,
-                                                                       const int* __restrict__ mix_i, const float* __restrict__ mix_f,
-                                                                       int B, int tubes, int tb, int n, int img, int p,
-                                                                       bf16* __restrict__ out, int ldo) {
-    const int pp = p * p, K = 3 * tb * pp;
+
+template <class Src, bool MIX>
+__global__ __launch_bounds__(256) void tube_gather_kernel(const Src src, const TubeRows r, const int* __restrict__ mix_i,
+                                                          const float* __restrict__ mix_f) {
+    const int tb = r.tb, p = r.p, pp = p * p, K = 3 * tb * pp;
     const int row = blockIdx.x;  // (b, tube, i)
-    const int i = row % n, tu = (row / n) % tubes, b = row / (n * tubes);
-    const int g = img / p;
-    const int pi = keep[(size_t)(b * tubes + tu) * n + i];
+    const int i = row % r.n, tu = (row / r.n) % r.tubes, b = row / (r.n * r.tubes);
+    const int g = r.img / p;
+    const int pi = r.keep[(size_t)(b * r.tubes + tu) * r.n + i];
     const int gy = pi / g, gx = pi % g;
-    const int T = tubes * tb;
-    const MixRow m = mix_row(mix_i, mix_f, b);
-    if ((unsigned)m.partner >= (unsigned)B) return;
-    const size_t clip = (size_t)3 * T * img * img;
-    for (int c8 = threadIdx.x * 8; c8 < K; c8 += 256 * 8) {
-        const int ch = c8 / (tb * pp), r1 = c8 % (tb * pp), t = r1 / pp, rem = r1 % pp, py = rem / p, px = rem % p;  // px % 8 == 0
-        const int y = gy * p + py, x = gx * p + px, f = tu * tb + t;
-        const size_t in = (((size_t)ch * T + f) * img + y) * img + x;  // inside one clip
-        const float* src = video + (size_t)b * clip + in;
-        const f32x4 a = *(const f32x4*)src, c = *(const f32x4*)(src + 4);
-        float v[8] = {a[0], a[1], a[2], a[3], c[0], c[1], c[2], c[3]};
-        if (mix_needs_partner(m, f, y, x)) {
-            const float* ps = video + (size_t)m.partner * clip + in;
-            const f32x4 pa = *(const f32x4*)ps, pc = *(const f32x4*)(ps + 4);
-            const float w[8] = {pa[0], pa[1], pa[2], pa[3], pc[0], pc[1], pc[2], pc[3]};
-            mix_apply8(m, x, v, w);
-        }
-        bf16x8 o = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3], (bf16)v[4], (bf16)v[5], (bf16)v[6], (bf16)v[7]};
-        *(bf16x8*)(out + (size_t)row * ldo + c8) = o;
+    typename Src::Sample s, ps;
+    if (!src.resolve(b, s)) return;
+    MixRow m;
+    if constexpr (MIX) {
+        m = mix_row(mix_i, mix_f, b);
+        if ((unsigned)m.partner >= (unsigned)r.B) return;
+        if (!src.resolve(m.partner, ps)) return;
     }
-}
-extern "C" int tvts_patch_gather_tube_cm_mix(const float* video, const int* keep, const int* mix_i, const float* mix_f, int B,
-                                             int tubes, int tubelet, int n, int img, int patch, void* out, int ldo,
-                                             hipStream_t stream) {
-    if (!video || !keep || !mix_i || !mix_f || !out || B <= 0 || tubes <= 0 || tubelet <= 0 || n <= 0 || patch <= 0 || img <= 0 ||
-        img % patch || patch % 8 || ldo % 8 || ldo < 3 * tubelet * patch * patch || ((size_t)video % 16) || ((size_t)out % 16))
-        return TVTS_EINVAL;
-    hipLaunchKernelGGL(patch_gather_tube_cm_mix_kernel, dim3(B * tubes * n), dim3(256), 0, stream, video, keep, mix_i, mix_f, B, tubes,
-                       tubelet, n, img, patch, (bf16*)out, ldo);
-    TVTS_LAUNCH_CHECK();
-    return TVTS_OK;
-}
-// uint8 frames: each of the two samples is cropped with ITS OWN offset and normalised by the expression of
-// patch_gather_tube_u8_kernel, then mixed as above and rounded to bf16: the bytes equal the fp32 kernel's on host-cropped,
-// host-normalised frames.
-__global__ __launch_bounds__(256) void patch_gather_tube_u8_mix_kernel(const unsigned char* __restrict__ frames, int H0, int W0,
-                                                                       const int* __restrict__ crop, const int* __restrict__ keep,
-                                                                       const int* __restrict__ mix_i, const float* __restrict__ mix_f,
-                                                                       int B, int tubes, int tb, int n, int img, int p, float m0,
-                                                                       float m1, float m2, float s0, float s1, float s2,
-                                                                       bf16* __restrict__ out, int ldo) {
-    const int pp = p * p, K = 3 * tb * pp;
-    const int row = blockIdx.x;  // (b, tube, i)
-    const int i = row % n, tu = (row / n) % tubes, b = row / (n * tubes);
-    const int g = img / p;
-    const int pi = keep[(size_t)(b * tubes + tu) * n + i];
-    const int gy = pi / g, gx = pi % g;
-    const int T = tubes * tb;
-    const MixRow m = mix_row(mix_i, mix_f, b);
-    if ((unsigned)m.partner >= (unsigned)B) return;
-    const int dy = H0 - img, dx = W0 - img;
-    const int yc = (dy >> 1) + ((dy & 1) & (dy >> 1)), xc = (dx >> 1) + ((dx & 1) & (dx >> 1));
-    const int y0 = crop ? crop[2 * b] : yc, x0 = crop ? crop[2 * b + 1] : xc;
-    const int py0 = crop ? crop[2 * m.partner] : yc, px0 = crop ? crop[2 * m.partner + 1] : xc;
+    const typename Src::Block blk = src.prologue();  // (the returns above are block-uniform: a barrier in here is reached by all)
     for (int c8 = threadIdx.x * 8; c8 < K; c8 += 256 * 8) {
         const int ch = c8 / (tb * pp), r1 = c8 % (tb * pp), t = r1 / pp, rem = r1 % pp, py = rem / p, px = rem % p;  // px % 8 == 0
         const int y = gy * p + py, x = gx * p + px, f = tu * tb + t;
-        const unsigned char* src = frames + (((size_t)(b * T + f) * H0 + y0 + y) * W0 + x0 + x) * 3 + ch;
-        const float mean = ch == 0 ? m0 : ch == 1 ? m1 : m2, sd = ch == 0 ? s0 : ch == 1 ? s1 : s2;
         float v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = ((float)src[3 * e] / 255.0f - mean) / sd;
-        if (mix_needs_partner(m, f, y, x)) {
-            const unsigned char* ps = frames + (((size_t)(m.partner * T + f) * H0 + py0 + y) * W0 + px0 + x) * 3 + ch;
-            float w[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) w[e] = ((float)ps[3 * e] / 255.0f - mean) / sd;
-            mix_apply8(m, x, v, w);
+        src.load8(blk, s, ch, f, y, x, v);
+        if constexpr (MIX) {
+            if (mix_needs_partner(m, f, y, x)) {
+                float w[8];
+                src.load8(blk, ps, ch, f, y, x, w);
+                mix_apply8(m, x, v, w);
+            }
         }
         bf16x8 o = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3], (bf16)v[4], (bf16)v[5], (bf16)v[6], (bf16)v[7]};
-        *(bf16x8*)(out + (size_t)row * ldo + c8) = o;
+        *(bf16x8*)(r.out + (size_t)row * r.ldo + c8) = o;
     }
-}
-extern "C" int tvts_patch_gather_tube_u8_mix(const unsigned char* frames, int H0, int W0, const int* crop, const int* keep,
-                                             const int* mix_i, const float* mix_f, int B, int tubes, int tubelet, int n, int img,
-                                             int patch, const float* mean3, const float* std3, void* out, int ldo,
-                                             hipStream_t stream) {
-    if (!frames || !keep || !mix_i || !mix_f || !out || !mean3 || !std3 || B <= 0 || tubes <= 0 || tubelet <= 0 || n <= 0 || patch <= 0 ||
-        img <= 0 || img % patch || patch % 8 || H0 < img || W0 < img || ldo % 8 || ldo < 3 * tubelet * patch * patch || ((size_t)out % 16))
-        return TVTS_EINVAL;
-    hipLaunchKernelGGL(patch_gather_tube_u8_mix_kernel, dim3(B * tubes * n), dim3(256), 0, stream, frames, H0, W0, crop, keep, mix_i,
-                       mix_f, B, tubes, tubelet, n, img, patch, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (bf16*)out,
-                       ldo);
-    TVTS_LAUNCH_CHECK();
-    return TVTS_OK;
 }
 
-// The per-sample augmentation of the v1 fine-tuning recipe behind RandAugment (v1/downstream/ssv2.py:186-227), fused into the uint8
-// gather: Normalize, random_resized_crop (video_transforms.py:541-573: a crop of the source frame resized to img x img by
-// torch's bilinear interpolate, align_corners=False), horizontal_flip (:156-177), RandomErasing in cube mode
-// (random_erasing.py:109-149), then the mix above.  The step's draw arrives as a per-sample table in device memory:
+// fp32 clips: frame-major [B, T, 3, img, img], as the pretrain model gets them (it permutes itself, v1/model/video_encoder.py:179),
+// or (CM) channel-major [B, 3, T, img, img], the layout the v1 downstream classes take (their forward hands x to the Conv3d as it
+// comes, v1/downstream/video_encoder_zero.py:91-96,177).  Two 16-byte loads per 8 pixels; the values pass through untouched.
+template <bool CM>
+struct F32Clip {
+    const float* video;
+    int T, img;
+    typedef int Sample;  // the clip's index
+    __device__ __forceinline__ bool resolve(int b, Sample& s) const {
+        s = b;
+        return true;
+    }
+    struct Block {};
+    __device__ __forceinline__ Block prologue() const { return Block{}; }
+    __device__ __forceinline__ void load8(Block, Sample s, int ch, int f, int y, int x, float* v) const {
+        const float* src = video + (((size_t)(CM ? (s * 3 + ch) * T + f : (s * T + f) * 3 + ch) * img + y) * img + x);
+        const f32x4 a = *(const f32x4*)src, c = *(const f32x4*)(src + 4);
+        v[0] = a[0], v[1] = a[1], v[2] = a[2], v[3] = a[3], v[4] = c[0], v[5] = c[1], v[6] = c[2], v[7] = c[3];
+    }
+};
+
+// The uint8 wire format: frames uint8 [., ., H0, W0, 3] as the decoder leaves them; ClipToTensor (/ 255) and Normalize
+// ((v - mean) / std) of v1/downstream/ssv2.py:61-63 run here.  u8_norm is THE normalise expression of every uint8 form: the
+// operations and their order are those of patch_gather_u8_kernel below, so the bytes equal the fp32 policy's on host-normalised
+// frames.  load8 converts 8 neighbouring px (24 interleaved source bytes apart by 3) of frame fr at (y, x) of the source picture.
+struct U8Norm { float m0, m1, m2, s0, s1, s2; };
+__device__ __forceinline__ float u8_norm(const U8Norm n, float u, int ch) {
+    const float mean = ch == 0 ? n.m0 : ch == 1 ? n.m1 : n.m2, sd = ch == 0 ? n.s0 : ch == 1 ? n.s1 : n.s2;
+    return (u / 255.0f - mean) / sd;
+}
+struct U8Frames {
+    const unsigned char* frames;
+    int H0, W0;
+    U8Norm nrm;
+    typedef U8Norm Block;
+    __device__ __forceinline__ Block prologue() const { return nrm; }
+    __device__ __forceinline__ void load8(const U8Norm n, size_t fr, int ch, int y, int x, float* v) const {
+        const unsigned char* src = frames + ((fr * H0 + y) * W0 + x) * 3 + ch;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = u8_norm(n, (float)src[3 * e], ch);
+    }
+};
+// the centre crop of a margin d = H0 - img: d / 2 rounded half to even (the offsets of patch_gather_u8_kernel)
+static inline int centre_crop_offset(int d) { return (d >> 1) + ((d & 1) & (d >> 1)); }
+
+// uint8 clips [B, T, H0, W0, 3] behind a crop: an offset per sample (crop int32 [B, 2] = (top, left), device data; y0 = x0 = 0), or
+// the centre crop (crop NULL; y0, x0 the offsets, which the host forms).  Under a mix each of the two samples is cropped with ITS
+// OWN offset.
+struct U8Crop : U8Frames {
+    const int* crop;
+    int T, y0, x0;
+    struct Sample { int f0, y0, x0; };
+    __device__ __forceinline__ bool resolve(int b, Sample& s) const {
+        s = Sample{b * T, y0 + (crop ? crop[2 * b] : 0), x0 + (crop ? crop[2 * b + 1] : 0)};
+        return true;
+    }
+    __device__ __forceinline__ void load8(const U8Norm n, const Sample& s, int ch, int f, int y, int x, float* v) const {
+        U8Frames::load8(n, (size_t)(s.f0 + f), ch, s.y0 + y, s.x0 + x, v);
+    }
+};
+
+// The test views of the fine-tuning scripts (v1/downstream/ssv2.py:132-164): sample b is the frames t0, t0 + tstep, ... of source
+// clip src of frames [Bs, Tsrc, H0, W0, 3], cropped at (top, left) -- `buffer[temporal_start::2, spatial_start:spatial_start +
+// short_side_size]` -- read from a per-sample table in device memory, view_i int32 [B, 8] = (src, t0, tstep, top, left, 0, 0, 0).
+// Only the source address differs from U8Crop: the bytes equal that form's on the host-sliced clip.  The views of one video read
+// one uploaded clip.  A src outside [0, Bs) leaves the sample's rows unwritten.
+struct U8View : U8Frames {
+    const int* view_i;
+    int Bs, Tsrc;
+    struct Sample { size_t f0; int tstep, y0, x0; };
+    __device__ __forceinline__ bool resolve(int b, Sample& s) const {
+        const int* v = view_i + 8 * (size_t)b;
+        s = Sample{(size_t)v[0] * Tsrc + v[1], v[2], v[3], v[4]};
+        return (unsigned)v[0] < (unsigned)Bs;
+    }
+    __device__ __forceinline__ void load8(const U8Norm n, const Sample& s, int ch, int f, int y, int x, float* v) const {
+        U8Frames::load8(n, s.f0 + (size_t)f * s.tstep, ch, s.y0 + y, s.x0 + x, v);
+    }
+};
+
+// The per-sample augmentation of the v1 fine-tuning recipe behind RandAugment (v1/downstream/ssv2.py:186-227): Normalize,
+// random_resized_crop (video_transforms.py:541-573: a crop of the source frame resized to img x img by torch's bilinear
+// interpolate, align_corners=False), horizontal_flip (:156-177), RandomErasing in cube mode (random_erasing.py:109-149), then the
+// frame's mix.  The step's draw arrives as a per-sample table in device memory:
 //     aug_i int32 [B, 16] = (src, top, left, h, w, flip, emode, etop, eleft, eh, ew, key_lo, key_hi, 0, 0, 0)
 // src: the source clip in [0, Bs) (several samples may read one clip: --num_sample); the crop [top, top + h) x [left, left + w) of
 // the source frame; flip mirrors the resized picture in x; the erase box [etop, etop + eh) x [eleft, eleft + ew) in OUTPUT
@@ -358,15 +249,16 @@ extern "C" int tvts_patch_gather_tube_u8_mix(const unsigned char* frames, int H0
 //   taps   sy = (float)h / (float)img, src = max(sy * (y + 0.5f) - 0.5f, 0), y0 = (int)src, y1 = min(y0 + 1, h - 1) (the CROP's
 //          edge), ly = src - y0; the same in x with w, for x' = flip ? img - 1 - x : x.  Products and differences are rounded
 //          one by one (no FMA), as the expression is written.
-//   values the four taps of frame src * T + f, each normalised by patch_gather_tube_u8_kernel's expression
+//   values the four taps of frame src * T + f, each normalised by u8_norm
 //   blend  (1 - ly) * ((1 - lx) * a + lx * b) + ly * ((1 - lx) * c + lx * d), every product and sum rounded; with h == w == img all
 //          l are 0 and the value is tap a, bit for bit
 //   erase  inside the box: 0 / z(key + AUG_RAND_STREAM, f * 3 + c) / z(key, ((f * 3 + c) * img + y) * img + x), x and y of the OUTPUT
-//   mix    mix_apply8 over this value and the partner's, the partner formed through ITS OWN table row
+//   mix    the frame's mix_apply8 over this value and the partner's, the partner formed through ITS OWN table row
 // z(key, idx): r = the splitmix64 finaliser (attention.hip::drop_keep) of key + idx * 0x9E3779B97F4A7C15; u1 = ((r >> 32) + 1) * 2^-32
 // in (0, 1], u2 = (r & 0xffffffff) * 2^-32; z = sqrtf(-2 logf(u1)) * cosf(2 pi u2) (Box-Muller, the accurate library functions;
 // ln u1 through log1pf where u1 is within 2^-8 of 1).  The float64 form of this rule is the definition (tests/v1_aug_ref.noise).
-// The y taps and weights are formed once per 8-pixel row piece; a piece reads at most two source rows.
+// The y taps and weights are formed once per 8-pixel row piece; a piece reads at most two source rows.  A src outside [0, Bs) -- the
+// sample's own or its partner's -- leaves the sample's rows unwritten.
 #define AUG_RAND_STREAM 0xD1B54A32D192ED03ull
 struct AugRow { int src, top, left, h, w, flip, emode, etop, eleft, eh, ew; unsigned long long key; };
 __device__ __forceinline__ AugRow aug_row(const int* __restrict__ aug_i, int b) {
@@ -393,94 +285,131 @@ __device__ __forceinline__ void aug_tap(float scale, int o, int size, int& i0, i
     i1 = min(i0 + 1, size - 1);
     l = fminf(fmaxf(__fsub_rn(s, (float)i0), 0.f), 1.f);
 }
-// the 8 augmented values of sample row `a` at channel ch, frame f, output pixels (y, x .. x + 7), before the mix
-// norm: the channel's 256 normalised values (u / 255.0f - mean) / sd, which the block forms once in LDS -- the uint8 gather's own
-// expression, so the same bits, at one pair of divisions per (block, channel, byte value) instead of four pairs per element
-__device__ __forceinline__ void aug_eval8(const unsigned char* __restrict__ frames, int H0, int W0, int T, const AugRow& a, int img,
-                                          int ch, int f, int y, int x, const float* norm, float* v) {
-    int y0, y1;
-    float ly;
-    aug_tap((float)a.h / (float)img, y, a.h, y0, y1, ly);
-    const float sx = (float)a.w / (float)img, hy = __fsub_rn(1.0f, ly);
-    const unsigned char* r0 = frames + (((size_t)(a.src * T + f) * H0 + a.top + y0) * W0 + a.left) * 3 + ch;
-    const unsigned char* r1 = r0 + (size_t)(y1 - y0) * W0 * 3;
-    const bool erow = a.emode != 0 && y >= a.etop && y < a.etop + a.eh;
+// uint8 source clips [Bs, T, H0, W0, 3] (any H0, W0 >= 1).  Block: the 256 normalised values of every channel, which the block forms
+// once in LDS -- u8_norm itself, so the same bits, at one pair of divisions per (block, channel, byte value) instead of four
+// pairs per element.
+struct U8Aug : U8Frames {
+    const int* aug_i;
+    int Bs, T, img;
+    typedef AugRow Sample;
+    typedef const float (*Block)[256];
+    __device__ __forceinline__ bool resolve(int b, Sample& a) const {
+        a = aug_row(aug_i, b);
+        return (unsigned)a.src < (unsigned)Bs;
+    }
+    __device__ __forceinline__ Block prologue() const {
+        __shared__ float lds[3][256];
+        for (int ch = 0; ch < 3; ++ch) lds[ch][threadIdx.x] = u8_norm(nrm, (float)threadIdx.x, ch);
+        __syncthreads();
+        return lds;
+    }
+    __device__ __forceinline__ void load8(Block table, const AugRow& a, int ch, int f, int y, int x, float* v) const {
+        const float* norm = table[ch];
+        int y0, y1;
+        float ly;
+        aug_tap((float)a.h / (float)img, y, a.h, y0, y1, ly);
+        const float sx = (float)a.w / (float)img, hy = __fsub_rn(1.0f, ly);
+        const unsigned char* r0 = frames + (((size_t)(a.src * T + f) * H0 + a.top + y0) * W0 + a.left) * 3 + ch;
+        const unsigned char* r1 = r0 + (size_t)(y1 - y0) * W0 * 3;
+        const bool erow = a.emode != 0 && y >= a.etop && y < a.etop + a.eh;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int xo = x + e;
-        if (erow && xo >= a.eleft && xo < a.eleft + a.ew) {
-            const unsigned long long fc = (unsigned long long)(f * 3 + ch);
-            v[e] = a.emode == 1 ? 0.0f
-                 : a.emode == 2 ? aug_noise(a.key + AUG_RAND_STREAM, fc)
-                                : aug_noise(a.key, (fc * img + y) * img + xo);
-            continue;
+        for (int e = 0; e < 8; ++e) {
+            const int xo = x + e;
+            if (erow && xo >= a.eleft && xo < a.eleft + a.ew) {
+                const unsigned long long fc = (unsigned long long)(f * 3 + ch);
+                v[e] = a.emode == 1 ? 0.0f
+                     : a.emode == 2 ? aug_noise(a.key + AUG_RAND_STREAM, fc)
+                                    : aug_noise(a.key, (fc * img + y) * img + xo);
+                continue;
+            }
+            int x0, x1;
+            float lx;
+            aug_tap(sx, a.flip ? img - 1 - xo : xo, a.w, x0, x1, lx);
+            const float hx = __fsub_rn(1.0f, lx);
+            const float p00 = norm[r0[3 * x0]], p01 = norm[r0[3 * x1]], p10 = norm[r1[3 * x0]], p11 = norm[r1[3 * x1]];
+            const float up = __fadd_rn(__fmul_rn(hx, p00), __fmul_rn(lx, p01)), dn = __fadd_rn(__fmul_rn(hx, p10), __fmul_rn(lx, p11));
+            v[e] = __fadd_rn(__fmul_rn(hy, up), __fmul_rn(ly, dn));
         }
-        int x0, x1;
-        float lx;
-        aug_tap(sx, a.flip ? img - 1 - xo : xo, a.w, x0, x1, lx);
-        const float hx = __fsub_rn(1.0f, lx);
-        const float p00 = norm[r0[3 * x0]], p01 = norm[r0[3 * x1]], p10 = norm[r1[3 * x0]], p11 = norm[r1[3 * x1]];
-        const float up = __fadd_rn(__fmul_rn(hx, p00), __fmul_rn(lx, p01)), dn = __fadd_rn(__fmul_rn(hx, p10), __fmul_rn(lx, p11));
-        v[e] = __fadd_rn(__fmul_rn(hy, up), __fmul_rn(ly, dn));
     }
+};
+
+// ---- the seven entry points: one shared argument check, the policy, one shared launch
+// what every form refuses: a NULL source / keep / out, a non-positive size, img % patch, patch % 8 (a thread's 8 pixels lie in one
+// patch row), ldo % 8 or ldo < K, out not 16-byte aligned (the bf16x8 store), the source not aligned to src_align bytes (16 for the
+// f32x4 loads of the fp32 clips)
+static bool tube_rows_ok(const void* src, size_t src_align, const TubeRows& r) {
+    return src && r.keep && r.out && r.B > 0 && r.tubes > 0 && r.tb > 0 && r.n > 0 && r.p > 0 && r.img > 0 && r.img % r.p == 0 &&
+           r.p % 8 == 0 && r.ldo % 8 == 0 && r.ldo >= 3 * r.tb * r.p * r.p && (size_t)r.out % 16 == 0 && (size_t)src % src_align == 0;
 }
-__global__ __launch_bounds__(256) void patch_gather_tube_u8_aug_kernel(const unsigned char* __restrict__ frames, int Bs, int H0, int W0,
-                                                                       const int* __restrict__ keep, const int* __restrict__ aug_i,
-                                                                       const int* __restrict__ mix_i, const float* __restrict__ mix_f,
-                                                                       int B, int tubes, int tb, int n, int img, int p, float m0,
-                                                                       float m1, float m2, float s0, float s1, float s2,
-                                                                       bf16* __restrict__ out, int ldo) {
-    const int pp = p * p, K = 3 * tb * pp;
-    const int row = blockIdx.x;  // (b, tube, i)
-    const int i = row % n, tu = (row / n) % tubes, b = row / (n * tubes);
-    const int g = img / p;
-    const int pi = keep[(size_t)(b * tubes + tu) * n + i];
-    const int gy = pi / g, gx = pi % g;
-    const int T = tubes * tb;
-    const AugRow a = aug_row(aug_i, b);
-    if ((unsigned)a.src >= (unsigned)Bs) return;
-    MixRow m = {b, 0, 0, 0, 0, 0, 1.0f, 0.0f};
-    AugRow pa = a;
-    if (mix_i) {
-        m = mix_row(mix_i, mix_f, b);
-        if ((unsigned)m.partner >= (unsigned)B) return;
-        pa = aug_row(aug_i, m.partner);
-        if ((unsigned)pa.src >= (unsigned)Bs) return;
-    }
-    __shared__ float norm[3][256];  // (the returns above are block-uniform: every thread of a block that stays reaches the barrier)
-    for (int ch = 0; ch < 3; ++ch) {
-        const float mean = ch == 0 ? m0 : ch == 1 ? m1 : m2, sd = ch == 0 ? s0 : ch == 1 ? s1 : s2;
-        norm[ch][threadIdx.x] = ((float)threadIdx.x / 255.0f - mean) / sd;
-    }
-    __syncthreads();
-    for (int c8 = threadIdx.x * 8; c8 < K; c8 += 256 * 8) {
-        const int ch = c8 / (tb * pp), r1 = c8 % (tb * pp), t = r1 / pp, rem = r1 % pp, py = rem / p, px = rem % p;  // px % 8 == 0
-        const int y = gy * p + py, x = gx * p + px, f = tu * tb + t;
-        float v[8];
-        aug_eval8(frames, H0, W0, T, a, img, ch, f, y, x, norm[ch], v);
-        if (mix_needs_partner(m, f, y, x)) {
-            float w[8];
-            aug_eval8(frames, H0, W0, T, pa, img, ch, f, y, x, norm[ch], w);
-            mix_apply8(m, x, v, w);
-        }
-        bf16x8 o = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3], (bf16)v[4], (bf16)v[5], (bf16)v[6], (bf16)v[7]};
-        *(bf16x8*)(out + (size_t)row * ldo + c8) = o;
-    }
+// ... and every uint8 form: NULL mean3 / std3 (host arrays), source frames below min_side (img where a crop of img x img is cut
+// from them, 1 where the crop is resized)
+static bool u8_frames_ok(const float* mean3, const float* std3, int H0, int W0, int min_side) {
+    return mean3 && std3 && H0 >= min_side && W0 >= min_side;
+}
+static U8Frames u8_frames(const unsigned char* frames, int H0, int W0, const float* mean3, const float* std3) {
+    return U8Frames{frames, H0, W0, U8Norm{mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]}};
+}
+static U8Crop u8_crop(const unsigned char* frames, int H0, int W0, const float* mean3, const float* std3, const int* crop, int T, int img) {
+    return U8Crop{u8_frames(frames, H0, W0, mean3, std3), crop, T, crop ? 0 : centre_crop_offset(H0 - img), crop ? 0 : centre_crop_offset(W0 - img)};
+}
+template <bool MIX, class Src>
+static int tube_launch(const Src& src, const TubeRows& r, const int* mix_i, const float* mix_f, hipStream_t stream) {
+    hipLaunchKernelGGL((tube_gather_kernel<Src, MIX>), dim3(r.B * r.tubes * r.n), dim3(256), 0, stream, src, r, mix_i, mix_f);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
+extern "C" int tvts_patch_gather_tube(const float* video, const int* keep, int B, int tubes, int tubelet, int n, int img,
+                                      int patch, void* out, int ldo, hipStream_t stream) {
+    const TubeRows r{keep, B, tubes, tubelet, n, img, patch, (bf16*)out, ldo};
+    if (!tube_rows_ok(video, 16, r)) return TVTS_EINVAL;
+    return tube_launch<false>(F32Clip<false>{video, tubes * tubelet, img}, r, nullptr, nullptr, stream);
+}
+extern "C" int tvts_patch_gather_tube_cm(const float* video, const int* keep, int B, int tubes, int tubelet, int n, int img,
+                                         int patch, void* out, int ldo, hipStream_t stream) {
+    const TubeRows r{keep, B, tubes, tubelet, n, img, patch, (bf16*)out, ldo};
+    if (!tube_rows_ok(video, 16, r)) return TVTS_EINVAL;
+    return tube_launch<false>(F32Clip<true>{video, tubes * tubelet, img}, r, nullptr, nullptr, stream);
+}
+extern "C" int tvts_patch_gather_tube_cm_mix(const float* video, const int* keep, const int* mix_i, const float* mix_f, int B,
+                                             int tubes, int tubelet, int n, int img, int patch, void* out, int ldo,
+                                             hipStream_t stream) {
+    const TubeRows r{keep, B, tubes, tubelet, n, img, patch, (bf16*)out, ldo};
+    if (!tube_rows_ok(video, 16, r) || !mix_i || !mix_f) return TVTS_EINVAL;
+    return tube_launch<true>(F32Clip<true>{video, tubes * tubelet, img}, r, mix_i, mix_f, stream);
+}
+extern "C" int tvts_patch_gather_tube_u8(const unsigned char* frames, int H0, int W0, const int* crop, const int* keep, int B,
+                                         int tubes, int tubelet, int n, int img, int patch, const float* mean3, const float* std3,
+                                         void* out, int ldo, hipStream_t stream) {
+    const TubeRows r{keep, B, tubes, tubelet, n, img, patch, (bf16*)out, ldo};
+    if (!tube_rows_ok(frames, 1, r) || !u8_frames_ok(mean3, std3, H0, W0, img)) return TVTS_EINVAL;
+    return tube_launch<false>(u8_crop(frames, H0, W0, mean3, std3, crop, tubes * tubelet, img), r, nullptr, nullptr, stream);
+}
+extern "C" int tvts_patch_gather_tube_u8_mix(const unsigned char* frames, int H0, int W0, const int* crop, const int* keep,
+                                             const int* mix_i, const float* mix_f, int B, int tubes, int tubelet, int n, int img,
+                                             int patch, const float* mean3, const float* std3, void* out, int ldo,
+                                             hipStream_t stream) {
+    const TubeRows r{keep, B, tubes, tubelet, n, img, patch, (bf16*)out, ldo};
+    if (!tube_rows_ok(frames, 1, r) || !u8_frames_ok(mean3, std3, H0, W0, img) || !mix_i || !mix_f) return TVTS_EINVAL;
+    return tube_launch<true>(u8_crop(frames, H0, W0, mean3, std3, crop, tubes * tubelet, img), r, mix_i, mix_f, stream);
+}
+extern "C" int tvts_patch_gather_tube_u8_view(const unsigned char* frames, int Bs, int Tsrc, int H0, int W0, const int* view_i,
+                                              const int* keep, int B, int tubes, int tubelet, int n, int img, int patch,
+                                              const float* mean3, const float* std3, void* out, int ldo, hipStream_t stream) {
+    const TubeRows r{keep, B, tubes, tubelet, n, img, patch, (bf16*)out, ldo};
+    if (!tube_rows_ok(frames, 1, r) || !u8_frames_ok(mean3, std3, H0, W0, img) || !view_i || Bs <= 0 || Tsrc <= 0) return TVTS_EINVAL;
+    return tube_launch<false>(U8View{u8_frames(frames, H0, W0, mean3, std3), view_i, Bs, Tsrc}, r, nullptr, nullptr, stream);
 }
 extern "C" int tvts_patch_gather_tube_u8_aug(const unsigned char* frames, int Bs, int H0, int W0, const int* keep, const int* aug_i,
                                              const int* mix_i, const float* mix_f, int B, int tubes, int tubelet, int n, int img,
                                              int patch, const float* mean3, const float* std3, void* out, int ldo,
                                              hipStream_t stream) {
-    if (!frames || !keep || !aug_i || !out || !mean3 || !std3 || (!mix_i) != (!mix_f) || Bs <= 0 || H0 <= 0 || W0 <= 0 || B <= 0 ||
-        tubes <= 0 || tubelet <= 0 || n <= 0 || patch <= 0 || img <= 0 || img % patch || patch % 8 || ldo % 8 ||
-        ldo < 3 * tubelet * patch * patch || ((size_t)out % 16))
-        return TVTS_EINVAL;
-    hipLaunchKernelGGL(patch_gather_tube_u8_aug_kernel, dim3(B * tubes * n), dim3(256), 0, stream, frames, Bs, H0, W0, keep, aug_i, mix_i,
-                       mix_f, B, tubes, tubelet, n, img, patch, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (bf16*)out,
-                       ldo);
-    TVTS_LAUNCH_CHECK();
-    return TVTS_OK;
+    const TubeRows r{keep, B, tubes, tubelet, n, img, patch, (bf16*)out, ldo};
+    if (!tube_rows_ok(frames, 1, r) || !u8_frames_ok(mean3, std3, H0, W0, 1) || !aug_i || Bs <= 0 || (!mix_i) != (!mix_f)) return TVTS_EINVAL;
+    const U8Aug src{u8_frames(frames, H0, W0, mean3, std3), aug_i, Bs, tubes * tubelet, img};
+    return mix_i ? tube_launch<true>(src, r, mix_i, mix_f, stream) : tube_launch<false>(src, r, nullptr, nullptr, stream);
 }
+
 
 // uint8 wire format: the frames arrive as the decoder leaves them -- uint8, H x W x 3 interleaved, already
 // resized on the host -- and the rest of the reference's transform chain runs here, fused into the tube-mask gather:

@@ -194,7 +194,7 @@ extern "C" int tvts_soft_ce(const float* logits, long ld, int B, int C, const fl
 }
 
 // ---------------------------------------------------------------------------------------------- Mixup / CutMix soft targets
-// mixup_target (v1/downstream/mixup.py:18-23) over the step's mix table (embed.hip, patch_gather_tube_cm_mix_kernel):
+// mixup_target (v1/downstream/mixup.py:18-23) over the step's mix table (embed.hip, MixRow of tube_gather_kernel):
 //   t[b, c] = fadd_rn(fmul_rn(y1, lam), fmul_rn(y2, one_minus_lam)),  y1 = on / off for labels[b], y2 = on / off for labels[partner[b]]
 // on / off arrive rounded to fp32 (torch.full of the double values).  A mode-0 row takes lam = 1, one_minus_lam = 0 and still
 // runs the arithmetic (the reference computes y1 * 1. + y2 * 0. there).  A partner outside [0, B) leaves its row unwritten.

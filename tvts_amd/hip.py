@@ -882,16 +882,43 @@ def vit_assemble_bwd(dtok, keep, dpatch, dcls, dpos, dtemporal, *, B, T, n):
          "tvts_vit_assemble_bwd")
 
 
+# ---- the v1 tubelet gathers (embed.hip: one kernel frame over four source policies).  What their wrappers check, stated once:
+def _tube_rows(keep, out, *, B, tubes, n):
+    assert keep.dtype == torch.int32 and keep.is_contiguous() and tuple(keep.shape) == (B, tubes, n), "keep: int32 [B, tubes, n]"
+    assert out.dtype == torch.bfloat16
+
+
+def _cm_clip(video, *, B, T, img):
+    assert video.dtype == torch.float32 and video.is_contiguous() and tuple(video.shape) == (B, 3, T, img, img)
+
+
+def _u8_clips(frames, T=None, B=None):
+    """uint8 clips [B, T, H0, W0, 3] as the decoder leaves them, contiguous -> (B, T, H0, W0)"""
+    assert frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() == 5 and frames.shape[-1] == 3
+    assert (B is None or frames.shape[0] == B) and (T is None or frames.shape[1] == T)
+    return frames.shape[:4]
+
+
+def _crop_dev(crop, B):
+    assert crop is None or (crop.dtype == torch.int32 and crop.is_contiguous() and tuple(crop.shape) == (B, 2))
+    return _p(crop)
+
+
+def _norm3(mean, std):
+    return (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+
+
 def patch_gather_tube(video, keep, out, *, B, tubes, tubelet, n, img, patch, channel_major=False):
     """v1 tubelet im2col: video fp32 [B, T, 3, img, img] (channel_major: [B, 3, T, img, img], the layout of the v1 downstream
     classes), keep int32 [B, tubes, n] -> out bf16 [B*tubes*n, 3*tubelet*patch^2]"""
     lib = _lib.load()
-    assert video.dtype == torch.float32 and keep.dtype == torch.int32 and keep.dim() == 3
+    _tube_rows(keep, out, B=B, tubes=tubes, n=n)
     if channel_major:
-        assert video.is_contiguous() and tuple(video.shape) == (B, 3, tubes * tubelet, img, img) and tuple(keep.shape) == (B, tubes, n)
+        _cm_clip(video, B=B, T=tubes * tubelet, img=img)
         _chk(lib.tvts_patch_gather_tube_cm(_p(video), _p(keep), B, tubes, tubelet, n, img, patch, _p(out), _ld(out), _stream()),
              "tvts_patch_gather_tube_cm")
         return
+    assert video.dtype == torch.float32
     _chk(lib.tvts_patch_gather_tube(_p(video), _p(keep), B, tubes, tubelet, n, img, patch, _p(out), _ld(out), _stream()),
          "tvts_patch_gather_tube")
 
@@ -899,14 +926,10 @@ def patch_gather_tube(video, keep, out, *, B, tubes, tubelet, n, img, patch, cha
 def patch_gather_tube_u8(frames, keep, out, *, B, tubes, tubelet, n, img, patch, crop=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """v1 tubelet im2col from uint8 frames [B, T, H0, W0, 3] on the device: crop (int32 [B, 2] (top, left), None = centre crop),
     / 255 and Normalize fused into the gather; keep int32 [B, tubes, n] -> out bf16 [B*tubes*n, 3*tubelet*patch^2]"""
-    lib = _lib.load()
-    assert frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() == 5 and frames.shape[-1] == 3
-    assert frames.shape[0] == B and frames.shape[1] == tubes * tubelet
-    assert keep.dtype == torch.int32 and keep.is_contiguous() and tuple(keep.shape) == (B, tubes, n)
-    assert crop is None or (crop.dtype == torch.int32 and crop.is_contiguous() and tuple(crop.shape) == (B, 2))
-    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
-    _chk(lib.tvts_patch_gather_tube_u8(_p(frames), frames.shape[2], frames.shape[3], _p(crop), _p(keep), B, tubes, tubelet, n, img,
-                                       patch, m3, s3, _p(out), _ld(out), _stream()), "tvts_patch_gather_tube_u8")
+    _, _, H0, W0 = _u8_clips(frames, T=tubes * tubelet, B=B)
+    _tube_rows(keep, out, B=B, tubes=tubes, n=n)
+    _chk(_lib.load().tvts_patch_gather_tube_u8(_p(frames), H0, W0, _crop_dev(crop, B), _p(keep), B, tubes, tubelet, n, img, patch,
+                                               *_norm3(mean, std), _p(out), _ld(out), _stream()), "tvts_patch_gather_tube_u8")
 
 
 def check_mix_plan(mix_i, mix_f, *, B, img):
@@ -947,9 +970,8 @@ def patch_gather_tube_mix(video, keep, out, mix, *, B, tubes, tubelet, n, img, p
     """patch_gather_tube(channel_major=True) with Mixup / CutMix applied per element in front of the bf16 rounding; mix: the device
     table of mix_table()"""
     mi, mf = _mix_dev(mix, B)
-    assert video.dtype == torch.float32 and keep.dtype == torch.int32
-    assert video.is_contiguous() and tuple(video.shape) == (B, 3, tubes * tubelet, img, img) and tuple(keep.shape) == (B, tubes, n)
-    assert keep.is_contiguous() and out.dtype == torch.bfloat16
+    _cm_clip(video, B=B, T=tubes * tubelet, img=img)
+    _tube_rows(keep, out, B=B, tubes=tubes, n=n)
     _chk(_lib.load().tvts_patch_gather_tube_cm_mix(_p(video), _p(keep), _p(mi), _p(mf), B, tubes, tubelet, n, img, patch, _p(out),
                                                    _ld(out), _stream()), "tvts_patch_gather_tube_cm_mix")
 
@@ -958,13 +980,10 @@ def patch_gather_tube_u8_mix(frames, keep, out, mix, *, B, tubes, tubelet, n, im
                              std=IMAGENET_STD):
     """patch_gather_tube_u8 with Mixup / CutMix: both samples cropped (each by its own offset) and normalised, then mixed"""
     mi, mf = _mix_dev(mix, B)
-    assert frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() == 5 and frames.shape[-1] == 3
-    assert frames.shape[0] == B and frames.shape[1] == tubes * tubelet
-    assert keep.dtype == torch.int32 and keep.is_contiguous() and tuple(keep.shape) == (B, tubes, n) and out.dtype == torch.bfloat16
-    assert crop is None or (crop.dtype == torch.int32 and crop.is_contiguous() and tuple(crop.shape) == (B, 2))
-    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
-    _chk(_lib.load().tvts_patch_gather_tube_u8_mix(_p(frames), frames.shape[2], frames.shape[3], _p(crop), _p(keep), _p(mi), _p(mf), B,
-                                                   tubes, tubelet, n, img, patch, m3, s3, _p(out), _ld(out), _stream()),
+    _, _, H0, W0 = _u8_clips(frames, T=tubes * tubelet, B=B)
+    _tube_rows(keep, out, B=B, tubes=tubes, n=n)
+    _chk(_lib.load().tvts_patch_gather_tube_u8_mix(_p(frames), H0, W0, _crop_dev(crop, B), _p(keep), _p(mi), _p(mf), B, tubes, tubelet,
+                                                   n, img, patch, *_norm3(mean, std), _p(out), _ld(out), _stream()),
          "tvts_patch_gather_tube_u8_mix")
 
 
@@ -1009,15 +1028,13 @@ def patch_gather_tube_u8_aug(frames, keep, out, aug, mix=None, *, B, tubes, tube
     aug the device table of aug_table() for B samples (each names its source clip) -- Normalize, random-resized crop (bilinear),
     flip, random erasing --, mix (optional) the device table of mix_table() for the same B samples, applied behind the erase;
     keep int32 [B, tubes, n] -> out bf16 [B*tubes*n, 3*tubelet*patch^2]"""
-    assert frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() == 5 and frames.shape[-1] == 3
-    assert frames.shape[1] == tubes * tubelet
+    Bs, _, H0, W0 = _u8_clips(frames, T=tubes * tubelet)
     assert aug.dtype == torch.int32 and aug.is_contiguous() and tuple(aug.shape) == (B, 16), "aug: int32 [B, 16] from aug_table()"
-    assert keep.dtype == torch.int32 and keep.is_contiguous() and tuple(keep.shape) == (B, tubes, n) and out.dtype == torch.bfloat16
+    _tube_rows(keep, out, B=B, tubes=tubes, n=n)
     mi, mf = _mix_dev(mix, B) if mix is not None else (None, None)
-    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
-    _chk(_lib.load().tvts_patch_gather_tube_u8_aug(_p(frames), frames.shape[0], frames.shape[2], frames.shape[3], _p(keep), _p(aug),
-                                                   _p(mi), _p(mf), B, tubes, tubelet, n, img, patch, m3, s3, _p(out), _ld(out),
-                                                   _stream()), "tvts_patch_gather_tube_u8_aug")
+    _chk(_lib.load().tvts_patch_gather_tube_u8_aug(_p(frames), Bs, H0, W0, _p(keep), _p(aug), _p(mi), _p(mf), B, tubes, tubelet, n, img,
+                                                   patch, *_norm3(mean, std), _p(out), _ld(out), _stream()),
+         "tvts_patch_gather_tube_u8_aug")
 
 
 def check_view_plan(view_i, *, Bs, Tsrc, H0, W0, T, img):
@@ -1054,13 +1071,11 @@ def patch_gather_tube_u8_view(frames, keep, out, view, *, B, tubes, tubelet, n, 
     """v1 tubelet im2col of the test views of uint8 source clips: frames uint8 [Bs, Tsrc, H0, W0, 3] on the device, view the device
     table of view_table() for B samples (each names its source clip, its first frame, the frame stride and the crop offset);
     keep int32 [B, tubes, n] -> out bf16 [B*tubes*n, 3*tubelet*patch^2], the bytes of patch_gather_tube_u8 on the host-sliced clips"""
-    assert frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() == 5 and frames.shape[-1] == 3
+    Bs, Tsrc, H0, W0 = _u8_clips(frames)
     assert view.dtype == torch.int32 and view.is_contiguous() and tuple(view.shape) == (B, 8), "view: int32 [B, 8] from view_table()"
-    assert keep.dtype == torch.int32 and keep.is_contiguous() and tuple(keep.shape) == (B, tubes, n) and out.dtype == torch.bfloat16
-    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
-    _chk(_lib.load().tvts_patch_gather_tube_u8_view(_p(frames), frames.shape[0], frames.shape[1], frames.shape[2], frames.shape[3],
-                                                    _p(view), _p(keep), B, tubes, tubelet, n, img, patch, m3, s3, _p(out), _ld(out),
-                                                    _stream()), "tvts_patch_gather_tube_u8_view")
+    _tube_rows(keep, out, B=B, tubes=tubes, n=n)
+    _chk(_lib.load().tvts_patch_gather_tube_u8_view(_p(frames), Bs, Tsrc, H0, W0, _p(view), _p(keep), B, tubes, tubelet, n, img, patch,
+                                                    *_norm3(mean, std), _p(out), _ld(out), _stream()), "tvts_patch_gather_tube_u8_view")
 
 
 def text_embed(ids, emb, pos, x, *, N, L):
