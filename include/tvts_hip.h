@@ -540,6 +540,42 @@ int tvts_patch_gather_tube_u8_aug(const unsigned char* frames, int Bs, int H0, i
 int tvts_patch_gather_tube_u8_view(const unsigned char* frames, int Bs, int Tsrc, int H0, int W0, const int* view_i, const int* keep,
                                    int B, int tubes, int tubelet, int n, int img, int patch, const float* mean3, const float* std3,
                                    void* out, int ldo, hipStream_t stream);
+/* ---- RandAugment of the v1 fine-tuning recipe (v1/downstream/rand_augment.py applied at v1/downstream/ssv2.py:174-184, --aa
+ * rand-m7-n4-mstd0.5-inc1) on uint8 frames at source size, in front of the augmentation gather above, with the bytes PIL gives.
+ * work uint8 [Bs + 2 * B, T, H0, W0, 3]: the Bs uploaded source clips, then two regions of B views each.  B = Bs * num_sample views;
+ * view b belongs to source clip b / num_sample.  The draw is a per-view table of L <= 8 layers in DEVICE memory, the active ops of a
+ * view compacted to the front of its row (tvts_amd.hip.check_randaug_plan checks it; here it is unchecked device data):
+ *   ra_i int32   [B, L, 4] = (op, resample, iarg, 0)           ra_d float64 [B, L, 8] = (a, b, c, d, e, f, factor, 0)
+ * op 0 none, 1 AutoContrast, 2 Equalize, 3 Invert, 4 Solarize(iarg = threshold, 0..256), 5 SolarizeAdd(iarg = add), 6 Posterize(iarg
+ * = bits kept, 0..7), 7 Color, 8 Contrast, 9 Brightness, 10 Sharpness (7-10: factor), 11 Affine (a..f, resample 2 bilinear / 3
+ * bicubic -- PIL's constants: ShearX / ShearY / TranslateXRel / TranslateYRel / Rotate all arrive as the six coefficients PIL's
+ * Image.transform hands its C code).  One call handles ONE layer: layer j reads view b from clip b / num_sample (j = 0) or from
+ * clip Bs + ((j - 1) & 1) * B + b, and writes clip Bs + (j & 1) * B + b -- only for a view whose op in layer j is 1..11.  A view with
+ * k active ops therefore ends in its source clip (k = 0), the first region (k odd) or the second (k even, k > 0); nothing is copied.
+ * Arithmetic (no product-sum of it is contracted into an FMA), c = channel:
+ *   3-6    a 256-entry table: 255 - i; i < thr ? i : 255 - i; i < 128 ? min(255, i + add) : i; i & ~(2^(8 - bits) - 1)
+ *   1      per frame and channel, lo / hi the first / last nonzero histogram bin: hi <= lo the identity, else scale = 255.0 / (hi -
+ *          lo), off = -lo * scale, table[i] = clamp((int)(i * scale + off), 0, 255), in double
+ *   2      per frame and channel: one nonzero bin or fewer the identity; step = (N - the last nonzero count) / 255 (integers), 0 the
+ *          identity; n = step / 2, then for i = 0 .. 255: table[i] = min(n / step, 255), n += h[i]
+ *   7-10   t = (float)d + factor * ((float)i - (float)d) in float, the result (int)t for 0 <= factor <= 1, else t clamped to [0, 255]
+ *          first; d = 0 (Brightness); L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 (Color); the constant (int)(mean(L) + 0.5),
+ *          the mean the exact sum of the L histogram over the pixel count in double (Contrast); the 3 x 3 filter (1 1 1 / 1 5 1 /
+ *          1 1 1) / 13 in float -- 0.5f, then += the three products of the row below, of the row itself, of the row above, each
+ *          summed left to right; clamped and truncated; the frame's one-pixel border unfiltered (Sharpness)
+ *   11     xin = a * (x + 0.5) + b * (y + 0.5) + c, yin the same with d, e, f, in double; outside [0, W0) x [0, H0): 128; else both
+ *          - 0.5, floor, fractions dx, dy, tap coordinates clamped to the frame; bilinear v1 = p00 + (p01 - p00) * dx, v2 the same
+ *          one row down, (int)(v1 + (v2 - v1) * dy); bicubic 4 x 4 taps, rows first, each p1 + d * (p2 + d * (p3 + d * p4)) with
+ *          p1 = v2, p2 = -v1 + v3, p3 = 2 * (v1 - v2) + v3 - v4, p4 = -v1 + v2 - v3 + v4; 0 for v <= 0, 255 for v >= 255, else (int)v
+ * tvts_randaug_hist: hist uint32 [B, T, 4 (R, G, B, L), 256] of the frames layer `layer` reads, for the views whose op there is 1, 2
+ * or 8 (the rest stays 0); zeroed on the stream first; integer atomics, so independent of order.  tvts_randaug_apply: hist may be
+ * NULL when no view's op in the layer is 1, 2 or 8 (such a view is then left unwritten).
+ * Both return -22 for a NULL work / ra_i (/ ra_d; / hist in _hist), Bs, B, num_sample, T <= 0, B != Bs * num_sample, B or T > 65535,
+ * H0 < 3 or W0 < 3, L outside [1, 8], layer outside [0, L). */
+int tvts_randaug_hist(const unsigned char* work, int Bs, int B, int num_sample, int T, int H0, int W0, int layer, int L,
+                      const int* ra_i, unsigned int* hist, hipStream_t stream);
+int tvts_randaug_apply(unsigned char* work, int Bs, int B, int num_sample, int T, int H0, int W0, int layer, int L, const int* ra_i,
+                       const double* ra_d, const unsigned int* hist, hipStream_t stream);
 int tvts_text_embed(const int* ids, int ld_ids, int N, int L, const float* emb, const float* pos, int Wt, float* x, int ldx,
                     hipStream_t stream);
 /* ---- PACKED variable-length captions (the forward-only text encoder of the SSv2 multiple-choice models,

@@ -30,6 +30,14 @@ every step, as a loader's batch does (pinned buffers), so the upload is inside t
             their time cannot be subtracted from the first figure).
     device  step(frames_u8, labels, aug=plan): the uint8 source frames [B / N, T, 256, 320, 3] and the plan are shipped, the gather
             does the rest.
+--randaug {off,device,host} (default off; with --aug device): RandAugment rand-m7-n4-mstd0.5-inc1, bicubic, in front of the crop
+(ssv2.py:174-184), drawn on the host per view from the same fixed seed:
+    device  Augment(..., randaug=...): the plan carries the ops, the step runs them on the uploaded source frames
+            (tvts_randaug_hist / tvts_randaug_apply) and the views of a clip still share ONE upload.  The launches' own time is
+            measured too, by op class (point, blend, statistics, sharpness, bilinear, bicubic): device events around 20 launches
+            of a one-layer plan in which every view has an op of that class, on the step's shapes.
+    host    the same ops by PIL on the host, per view and frame, in front of the step; every view is then a uint8 clip of its own
+            and is uploaded separately (B clips instead of B / N).  PIL's own clock is reported.  Without PIL: says so and skips.
 --mixup device / torch may be combined with the --aug setting of the same name.  With --u8 (--aug off) or --aug device the
 gather's own time is measured too: device events around 50 launches of the step's gather on the step's shapes, in a pass of its own."""
 import argparse
@@ -90,6 +98,60 @@ def torch_aug(src, plan, img, buf):
     return buf
 
 
+RANDAUG = "rand-m7-n4-mstd0.5-inc1"
+RA_CLASSES = {"point (invert)": ("invert", None), "blend (color)": ("color", 1.63), "statistics (autocontrast)": ("auto_contrast", None),
+              "statistics (equalize)": ("equalize", None), "sharpness": ("sharpness", 1.63), "bilinear (rotate)": ("rotate", 21.0),
+              "bicubic (rotate)": ("rotate", 21.0)}
+
+
+def pil_op(im, fn, arg, resample):
+    """one RandAugment op of a plan's record on a PIL image, as PIL's own calls"""
+    from PIL import Image, ImageEnhance, ImageOps
+    fill = dict(fillcolor=(128, 128, 128), resample=resample)
+    if fn == "auto_contrast":
+        return ImageOps.autocontrast(im)
+    if fn == "equalize":
+        return ImageOps.equalize(im)
+    if fn == "invert":
+        return ImageOps.invert(im)
+    if fn == "solarize":
+        return ImageOps.solarize(im, arg)
+    if fn == "solarize_add":
+        return im.point([min(255, i + arg) if i < 128 else i for i in range(256)] * 3)
+    if fn == "posterize":
+        return im if arg >= 8 else ImageOps.posterize(im, arg)
+    if fn in ("color", "contrast", "brightness", "sharpness"):
+        return getattr(ImageEnhance, fn.capitalize())(im).enhance(arg)
+    if fn == "rotate":
+        return im.rotate(arg, **fill)
+    w, h = im.size
+    data = {"shear_x": (1, arg, 0, 0, 1, 0), "shear_y": (1, 0, 0, arg, 1, 0), "translate_x_rel": (1, 0, arg * w, 0, 1, 0),
+            "translate_y_rel": (1, 0, 0, 0, 1, arg * h)}[fn]
+    return im.transform(im.size, Image.AFFINE, data, **fill)
+
+
+def randaug_class_us(frames, Bs, B, ns, reps=20):
+    """device events around the hist and apply launches of one-layer plans, every view an op of one class -> {class: us}"""
+    from tvts_amd import hip as K
+    from tvts_amd.downstream.finetune_v1 import ra_plan, ra_row
+    work = torch.empty((Bs + 2 * B,) + tuple(frames.shape[1:]), dtype=torch.uint8, device="cuda")
+    work[:Bs].copy_(frames)
+    H0, W0 = frames.shape[2], frames.shape[3]
+    hist = torch.empty((B, frames.shape[1], 4, 256), dtype=torch.int32, device="cuda")
+    lib, p, st = K._lib.load(), K._p, K._stream
+    out = {}
+    for name, (fn, arg) in RA_CLASSES.items():
+        row = ra_row(fn, arg, 2 if "bilinear" in name else 3, H0, W0)
+        plan = ra_plan([([row], [])] * B, 1, ns)
+        t = K.RandaugTable(plan.ra_i, plan.ra_d, Bs=Bs, num_sample=ns)
+        a = (p(work), Bs, B, ns, frames.shape[1], H0, W0, 0, 1, p(t.ra_i))
+        if t.stats[0]:
+            out[name + ": hist us"] = gather_us(lambda: lib.tvts_randaug_hist(*a, p(hist), st()), reps)
+        out[name + ": apply us"] = gather_us(lambda: lib.tvts_randaug_apply(*a, p(t.ra_d), p(hist) if t.stats[0] else None, st()), reps)
+    out["bytes read + written per apply launch"] = 2 * B * frames[0].numel()
+    return out
+
+
 def gather_us(fn, reps=50):
     """device events around `reps` launches of the step's gather (all patches kept) -> microseconds per launch"""
     fn()
@@ -109,17 +171,36 @@ def run_aug(args, targets):
 
     import numpy as np
     from tvts_amd import hip as K
-    from tvts_amd.downstream.finetune_v1 import Augment, Mixup
+    from tvts_amd.downstream.finetune_v1 import AugPlan, Augment, Mixup, RandAugment
     m, step, ngroups = make("all", args)
     img, T, B, Bs = KW["img_size"], KW["num_frames"], args.batch, args.batch // args.num_sample
     random.seed(0)
     np.random.seed(0)
-    aug = Augment(img, hflip=0.0, reprob=0.25, remode="pixel", recount=1, num_sample=args.num_sample)
+    aug = Augment(img, hflip=0.0, reprob=0.25, remode="pixel", recount=1, num_sample=args.num_sample,
+                  randaug=None if args.randaug == "off" else RandAugment(RANDAUG, interpolation="bicubic", input_size=img))
     mixup = Mixup(mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, mode="batch", label_smoothing=0.1, num_classes=args.classes)
     g = torch.Generator().manual_seed(1)
     frames = torch.randint(0, 256, (Bs, T, SRC[0], SRC[1], 3), generator=g, dtype=torch.uint8).pin_memory()
     host = dict(s=0.0)
-    if args.aug == "device":
+    if args.randaug == "host":
+        from PIL import Image
+        views = torch.empty((B, T, SRC[0], SRC[1], 3), dtype=torch.uint8).pin_memory()
+        src_np, views_np = frames.numpy(), views.numpy()
+
+        def one():
+            plan = aug.draw(Bs, *SRC)
+            t0 = time.perf_counter()
+            for b, ops in enumerate(plan.ra.ops):
+                for t in range(T):
+                    im = Image.fromarray(src_np[b // args.num_sample, t])
+                    for fn, arg, rs in ops:
+                        im = pil_op(im, fn, arg, rs)
+                    views_np[b, t] = np.asarray(im)
+            host["s"] += time.perf_counter() - t0
+            own = plan.aug_i.copy()
+            own[:, 0] = np.arange(B)  # every view is a source clip of its own
+            return step.step(views, targets, aug=AugPlan(own), mix=mixup.draw(B, img) if args.mixup == "device" else None)
+    elif args.aug == "device":
         def one():
             plan = aug.draw(Bs, *SRC)
             return step.step(frames, targets, aug=plan, mix=mixup.draw(B, img) if args.mixup == "device" else None)
@@ -147,6 +228,10 @@ def run_aug(args, targets):
     dt = (time.perf_counter() - t0) / args.iters
     res = {"step ms": 1e3 * dt, "clips/s": B / dt, "parameter groups": ngroups, "last loss": float(out["loss"]),
            "upload bytes/step": (frames if args.aug == "device" else buf).numel() * (1 if args.aug == "device" else 4)}
+    if args.randaug == "host":
+        res.update({"upload bytes/step": views.numel(), "host RandAugment (PIL) ms/step": 1e3 * host["s"] / args.iters})
+    if args.randaug == "device":
+        res["randaug launches by op class (events, 20 launches)"] = randaug_class_us(frames, Bs, B, args.num_sample)
     if args.aug == "torch":
         res["host augment ms/step"] = 1e3 * host["s"] / args.iters
         if args.mixup == "off":  # upload + step only, from the pinned buffer the last step left
@@ -164,7 +249,7 @@ def run_aug(args, targets):
         tubes, ppf, kc = T // a["tubelet"], (img // a["patch"]) ** 2, 3 * a["tubelet"] * a["patch"] ** 2
         keep = torch.arange(ppf, dtype=torch.int32, device="cuda").repeat(B, tubes, 1).contiguous()
         cols = torch.empty(B * tubes * ppf, kc, dtype=torch.bfloat16, device="cuda")
-        plan = aug.draw(Bs, *SRC)
+        plan = Augment(img, hflip=0.0, reprob=0.25, remode="pixel", recount=1, num_sample=args.num_sample).draw(Bs, *SRC)
         table, fr = K.aug_table(plan.aug_i, Bs=Bs, H0=SRC[0], W0=SRC[1], img=img), frames.cuda()
         kw = dict(B=B, tubes=tubes, tubelet=a["tubelet"], n=ppf, img=img, patch=a["patch"])
         crop_bytes = int(sum(int(r[3]) * int(r[4]) for r in plan.aug_i)) * 3 * T
@@ -244,7 +329,16 @@ def main():
     ap.add_argument("--u8", action="store_true", help="uint8 frames [B, T, H, W, 3] instead of the fp32 clip")
     ap.add_argument("--aug", choices=("off", "torch", "device"), default="off")
     ap.add_argument("--num-sample", type=int, default=1, help="views per decoded clip (--num_sample of the script)")
+    ap.add_argument("--randaug", choices=("off", "device", "host"), default="off", help="RandAugment in front of the crop (--aug device)")
     args = ap.parse_args()
+    if args.randaug != "off" and args.aug != "device":
+        raise SystemExit("--randaug device / host: with --aug device (the rest of the augmentation stays on the device)")
+    if args.randaug == "host":
+        try:
+            import PIL  # noqa: F401
+        except ImportError:
+            print("--randaug host: PIL is not importable here; skipped (NOT MEASURED)", flush=True)
+            return
     if args.aug != "off" and (args.u8 or args.mixup not in ("off", args.aug)):
         raise SystemExit("--aug torch / device: without --u8 (the setting says what is shipped), --mixup off or the same setting")
     if args.num_sample < 1 or args.batch % args.num_sample or (args.aug == "off" and args.num_sample != 1):
@@ -269,6 +363,8 @@ def main():
         out["mixup"] = args.mixup
     if args.aug != "off":
         out.update({"aug": args.aug, "num_sample": args.num_sample, "source": "%d x %d" % SRC})
+        if args.randaug != "off":
+            out["randaug"] = "%s (%s, bicubic)" % (args.randaug, RANDAUG)
         if args.mixup == "off":
             targets = torch.randint(0, args.classes, (args.batch,), generator=g)
         out["trainable=all"] = run_aug(args, targets)

@@ -39,7 +39,20 @@ The plan is a per-sample table (source clip, crop, flip, erase box, noise key); 
 from its four bilinear taps of the uint8 source frame, erases, mixes and rounds once.  No augmented clip is materialised, and
 the views of one clip read the same uploaded frames.  The erase noise is a counter-based normal, not torch's CPU stream.
 
-OUT OF SCOPE (not built here): RandAugment itself (uint8 PIL frames at source size, the host data pipeline), --recount > 1,
+RandAugment in front of all of it (ssv2.py:174-184, --aa rand-m7-n4-mstd0.5-inc1 in the default recipe; rand_augment.py):
+
+    ra_fn = RandAugment("rand-m7-n4-mstd0.5-inc1", interpolation="bicubic", input_size=224)   # video_transforms.create_random_augment
+    aug_fn = Augment(224, ..., num_sample=2, randaug=ra_fn)                        # per view: the RandAugment draws, then crop / flip / erase
+    out = step.step(frames_u8, labels.repeat_interleave(2), mix=..., aug=aug_fn.draw(Bs, H0, W0))
+
+The draw makes the reference's calls on ``np.random`` and ``random`` in its order and does the level arithmetic in Python doubles;
+the plan carries, per view, the active ops as finished coefficients (RAPlan).  The step uploads the source clips ONCE into the head
+of a work tensor [Bs + 2 * B, T, H0, W0, 3] and runs the layers over its two view regions (tvts_randaug_hist / tvts_randaug_apply,
+one launch pair per layer, csrc/randaug.hip) with the bytes PIL gives -- every op, bilinear and bicubic -- then points the
+plan's source column at the clip each view ended in, so the gather above reads the augmented views unchanged.
+
+OUT OF SCOPE (not built here): RandAugment's per-frame ``"random"`` interpolation and TranslateX / TranslateY (abs) (neither list of
+rand_augment_transform holds them), --recount > 1,
 ``motion_shift`` (random_resized_crop_with_shift), the reference's torch noise stream,
 ``FastCollateMixup`` (the uint8-rounding variant: the reference scripts do not use it), ``ModelEma``, the fp16 loss scaler (the engine is bf16 with fp32 accumulation: there is no loss scale), DeepSpeed, the multi-GPU
 gradient exchange for this step (the backward keeps its Engine._ready calls so that one can hook in), and hipGraph capture of it.
@@ -50,6 +63,7 @@ from __future__ import annotations
 
 import math
 import random
+import re
 from typing import NamedTuple
 
 import numpy as np
@@ -220,6 +234,198 @@ class Mixup:
         return MixPlan(mix_i, mix_f, float(self.label_smoothing))
 
 
+# ---------------------------------------------------------------------------------------------- RandAugment: the draw
+# op codes of the plan's ra_i column 0, as tvts_randaug_apply reads them (include/tvts_hip.h)
+(RA_NONE, RA_AUTOCONTRAST, RA_EQUALIZE, RA_INVERT, RA_SOLARIZE, RA_SOLARIZE_ADD, RA_POSTERIZE, RA_COLOR, RA_CONTRAST, RA_BRIGHTNESS,
+ RA_SHARPNESS, RA_AFFINE) = range(12)
+RA_STATS = (RA_AUTOCONTRAST, RA_EQUALIZE, RA_CONTRAST)  # the ops that read the frame's histograms (tvts_randaug_hist)
+RA_MAX_LAYERS = 8
+RA_BILINEAR, RA_BICUBIC = 2, 3  # PIL's Image.BILINEAR / Image.BICUBIC
+_RA_MAX_LEVEL = 10.0
+# rand_augment.py:385-420: the op of every slot as (reference function, level rule, level rule under `inc`)
+_RA_OPS = (("auto_contrast", None, None), ("equalize", None, None), ("invert", None, None), ("rotate", "rotate", "rotate"),
+           ("posterize", "posterize", "posterize_inc"), ("solarize", "solarize", "solarize_inc"),
+           ("solarize_add", "solarize_add", "solarize_add"), ("color", "enhance", "enhance_inc"),
+           ("contrast", "enhance", "enhance_inc"), ("brightness", "enhance", "enhance_inc"), ("sharpness", "enhance", "enhance_inc"),
+           ("shear_x", "shear", "shear"), ("shear_y", "shear", "shear"), ("translate_x_rel", "translate_rel", "translate_rel"),
+           ("translate_y_rel", "translate_rel", "translate_rel"))
+# _RAND_CHOICE_WEIGHTS_0 (:425-441) in the order of _RAND_TRANSFORMS, the list _select_rand_weights indexes whatever list is in use
+_RA_WEIGHTS_0 = (0.025, 0.005, 0, 0.3, 0, 0.005, 0.005, 0.025, 0.005, 0.005, 0.025, 0.2, 0.2, 0.1, 0.1)
+_RA_BLEND = {"color": RA_COLOR, "contrast": RA_CONTRAST, "brightness": RA_BRIGHTNESS, "sharpness": RA_SHARPNESS}
+
+
+def _negate(v):
+    """_randomly_negate (:195-197)"""
+    return -v if random.random() > 0.5 else v
+
+
+def _ra_level(rule, level):
+    """LEVEL_TO_ARG (:200-306) in the reference's Python doubles -> the one argument the op function receives"""
+    if rule == "rotate":
+        return _negate((level / _RA_MAX_LEVEL) * 30.0)
+    if rule == "enhance":
+        return (level / _RA_MAX_LEVEL) * 1.8 + 0.1
+    if rule == "enhance_inc":
+        return 1.0 + _negate((level / _RA_MAX_LEVEL) * 0.9)
+    if rule == "shear":
+        return _negate((level / _RA_MAX_LEVEL) * 0.3)
+    if rule == "translate_rel":
+        return _negate((level / _RA_MAX_LEVEL) * 0.45)
+    if rule == "posterize":
+        return int((level / _RA_MAX_LEVEL) * 4)
+    if rule == "posterize_inc":
+        return 4 - int((level / _RA_MAX_LEVEL) * 4)
+    if rule == "solarize":
+        return int((level / _RA_MAX_LEVEL) * 256)
+    if rule == "solarize_inc":
+        return 256 - int((level / _RA_MAX_LEVEL) * 256)
+    if rule == "solarize_add":
+        return int((level / _RA_MAX_LEVEL) * 110)
+    raise ValueError(rule)
+
+
+def ra_row(fn, arg, resample, H0, W0):
+    """one op of the reference -- the NAME_TO_OP function `fn` (:64-192) called with `arg` and `resample` on H0 x W0 frames -- as a
+    plan row: ((op, resample, iarg, 0), (a, b, c, d, e, f, factor, 0)).  The coefficients are what PIL hands its C code: the AFFINE
+    data of Image.transform as they are, the matrix of Image.rotate (angle % 360, -radians, cos / sin rounded to 15 places, the
+    centre (W0 / 2, H0 / 2) carried through), the enhancers' factor.  An op that PIL returns unchanged (posterize to 8 bits or
+    more) is op 0."""
+    ri, rd = [RA_NONE, 0, 0, 0], [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
+    if fn in ("auto_contrast", "equalize", "invert"):
+        ri[0] = {"auto_contrast": RA_AUTOCONTRAST, "equalize": RA_EQUALIZE, "invert": RA_INVERT}[fn]
+    elif fn in ("solarize", "solarize_add", "posterize"):
+        if int(arg) != arg:
+            raise ValueError(f"{fn}: an integer argument")
+        if fn == "posterize" and arg >= 8:
+            return tuple(ri), tuple(rd)
+        if not (0 <= arg <= 256):
+            raise ValueError(f"{fn}: argument outside [0, 256]")
+        ri[0], ri[2] = {"solarize": RA_SOLARIZE, "solarize_add": RA_SOLARIZE_ADD, "posterize": RA_POSTERIZE}[fn], int(arg)
+    elif fn in _RA_BLEND:
+        ri[0], rd[6] = _RA_BLEND[fn], float(arg)
+    elif fn in ("shear_x", "shear_y", "translate_x_rel", "translate_y_rel", "rotate"):
+        if resample not in (RA_BILINEAR, RA_BICUBIC):
+            raise ValueError("resample: 2 (bilinear) or 3 (bicubic)")
+        ri[0], ri[1] = RA_AFFINE, resample
+        if fn == "shear_x":
+            rd[1] = float(arg)
+        elif fn == "shear_y":
+            rd[3] = float(arg)
+        elif fn == "translate_x_rel":
+            rd[2] = float(arg * W0)
+        elif fn == "translate_y_rel":
+            rd[5] = float(arg * H0)
+        else:  # Image.rotate(degrees, resample, fillcolor): no expand, centre and translate left at their defaults
+            angle = -math.radians(arg % 360.0)
+            cx, cy = W0 / 2.0, H0 / 2.0
+            a, b = round(math.cos(angle), 15), round(math.sin(angle), 15)
+            d, e = round(-math.sin(angle), 15), round(math.cos(angle), 15)
+            c = a * -cx + b * -cy + 0.0
+            f = d * -cx + e * -cy + 0.0
+            rd[:6] = a, b, c + cx, d, e, f + cy
+    else:
+        raise ValueError(f"RandAugment op {fn!r}")
+    if not all(math.isfinite(v) for v in rd):
+        raise ValueError(f"{fn}: a coefficient that is not finite")
+    return tuple(ri), tuple(rd)
+
+
+class RAPlan(NamedTuple):
+    """one step's RandAugment draw, on the host.  The ACTIVE ops of every view, compacted to the front of its row:
+    ra_i int32 [B, L, 4] = (op code, resample, integer argument, 0), op 0 = none; ra_d float64 [B, L, 8] = (affine a..f, blend
+    factor, 0); num_sample views per source clip; ops: per view, every op the reference called, as (function name, argument or
+    None, resample) -- the record the tests compare, not read by the step."""
+    ra_i: np.ndarray
+    ra_d: np.ndarray
+    num_sample: int
+    ops: list
+
+
+class RandAugment:
+    """rand_augment_transform / AugmentOp.__call__ / RandAugment.__call__ (rand_augment.py:337-531, built by create_random_augment,
+    video_transforms.py:621-654, for ssv2.py:174-184) as draws only: ``draw_view`` makes the reference's calls on the global
+    ``np.random`` and ``random`` in its order and returns the ops it would run; the ops themselves run on the device
+    (tvts_randaug_hist / tvts_randaug_apply, FinetuneStep.step(..., aug=plan)).  config_str: --aa, e.g. "rand-m7-n4-mstd0.5-inc1".
+    ``inc0`` selects the increasing list like ``inc1``: the reference tests bool("0") (:515).  ``w0`` weights the choice by
+    _RAND_CHOICE_WEIGHTS_0 in the order of the non-increasing names and draws without replacement (:470-475).  interpolation:
+    --train_interpolation, "bilinear" or "bicubic"; "random" (a resample drawn per frame and op, :50-55) is not built.  input_size
+    only sets translate_const, which no op of the two lists reads."""
+
+    def __init__(self, config_str, interpolation="bicubic", input_size=224):
+        if interpolation == "random":
+            raise ValueError("interpolation 'random' (a resample drawn per frame and op) is not built")
+        if interpolation not in ("bilinear", "bicubic"):
+            raise ValueError("interpolation: 'bilinear' or 'bicubic'")
+        config = str(config_str).split("-")
+        if not str(config_str).startswith("rand") or config[0] != "rand":
+            raise ValueError("config_str: 'rand-...' (e.g. rand-m7-n4-mstd0.5-inc1)")
+        self.resample = RA_BILINEAR if interpolation == "bilinear" else RA_BICUBIC
+        self.magnitude, self.num_layers, self.magnitude_std, self.increasing, weight_idx = _RA_MAX_LEVEL, 2, 0, False, None
+        std_set = False
+        for c in config[1:]:
+            cs = re.split(r"(\d.*)", c)
+            if len(cs) < 2:
+                continue
+            key, val = cs[:2]
+            if key == "mstd":
+                if not std_set:  # (hparams.setdefault: the first one holds)
+                    self.magnitude_std, std_set = float(val), True
+            elif key == "inc":
+                if bool(val):
+                    self.increasing = True
+            elif key == "m":
+                self.magnitude = int(val)
+            elif key == "n":
+                self.num_layers = int(val)
+            elif key == "w":
+                weight_idx = int(val)
+        if not (1 <= self.num_layers <= RA_MAX_LAYERS):
+            raise ValueError(f"n: 1 to {RA_MAX_LAYERS} layers")
+        if weight_idx not in (None, 0):
+            raise ValueError("w: only weight set 0 exists")
+        self.input_size = input_size
+        self.weights = None
+        if weight_idx is not None:  # _select_rand_weights (:444-450)
+            probs = [w for w in _RA_WEIGHTS_0]
+            self.weights = probs / np.sum(probs)
+
+    def draw_view(self, H0, W0):
+        """the draws of one RandAugment.__call__ -> (rows, ops): the plan rows of the active ops, in order, and the record"""
+        if H0 < 3 or W0 < 3:
+            raise ValueError("RandAugment needs frames of at least 3 x 3")
+        picks = np.random.choice(len(_RA_OPS), self.num_layers, replace=self.weights is None, p=self.weights)
+        rows, ops = [], []
+        for k in picks:
+            fn, rule, rule_inc = _RA_OPS[int(k)]
+            if random.random() > 0.5:  # AugmentOp.__call__ (:365): prob 0.5 for every op
+                continue
+            magnitude = self.magnitude
+            if self.magnitude_std and self.magnitude_std > 0:
+                magnitude = random.gauss(magnitude, self.magnitude_std)
+            magnitude = min(_RA_MAX_LEVEL, max(0, magnitude))
+            rule = rule_inc if self.increasing else rule
+            arg = None if rule is None else _ra_level(rule, magnitude)
+            ops.append((fn, arg, self.resample))
+            ri, rd = ra_row(fn, arg, self.resample, H0, W0)
+            if ri[0] != RA_NONE:
+                rows.append((ri, rd))
+        return rows, ops
+
+    def draw(self, B, H0, W0, num_sample=1):
+        """B views of H0 x W0 frames, nothing drawn between them -> RAPlan"""
+        return ra_plan([self.draw_view(H0, W0) for _ in range(B)], self.num_layers, num_sample)
+
+
+def ra_plan(views, L, num_sample):
+    """[(rows, ops)] per view -> RAPlan with L layers"""
+    ra_i, ra_d = np.zeros((len(views), L, 4), dtype=np.int32), np.zeros((len(views), L, 8), dtype=np.float64)
+    ra_d[:, :, 0] = ra_d[:, :, 4] = 1.0
+    for b, (rows, _) in enumerate(views):
+        for j, (ri, rd) in enumerate(rows):
+            ra_i[b, j], ra_d[b, j] = ri, rd
+    return RAPlan(ra_i, ra_d, int(num_sample), [ops for _, ops in views])
+
+
 # ---------------------------------------------------------------------------------------------- crop, flip, random erasing
 _M64 = (1 << 64) - 1
 EMODE = {"const": 1, "rand": 2, "pixel": 3}
@@ -236,10 +442,11 @@ def splitmix64(x: int) -> int:
 
 class AugPlan:
     """one step's per-sample augmentation draw, on the host: aug_i int32 [B, 16] = (src, top, left, h, w, flip, emode, etop, eleft,
-    eh, ew, key_lo, key_hi, 0, 0, 0), the table of tvts_patch_gather_tube_u8_aug (include/tvts_hip.h).  len(plan) = B."""
+    eh, ew, key_lo, key_hi, 0, 0, 0), the table of tvts_patch_gather_tube_u8_aug (include/tvts_hip.h).  len(plan) = B.
+    ra: the RAPlan of the same B views (Augment(..., randaug=...)), or None: no RandAugment in front of the crop."""
 
-    def __init__(self, aug_i):
-        self.aug_i = aug_i
+    def __init__(self, aug_i, ra=None):
+        self.aug_i, self.ra = aug_i, ra
 
     def __len__(self):
         return int(self.aug_i.shape[0])
@@ -255,10 +462,11 @@ class Augment:
     the views per decoded clip, collated as neighbours (utils.multiple_samples_collate): sample s * num_sample + k is view k of
     source clip s.  noise_seed: the erase noise is NOT torch's CPU stream (random_erasing.py:11-24) but a counter-based normal
     keyed per sample, key = splitmix64(noise_seed) + the number of samples drawn before it; the key never touches ``random`` /
-    ``np.random``, so the reference's draw sequence is not shifted."""
+    ``np.random``, so the reference's draw sequence is not shifted.  randaug: a RandAugment, or None -- every view then draws
+    its RandAugment ops first (ssv2.py:174-184 runs in front of the crop), then the crop, flip and erase."""
 
     def __init__(self, input_size, scale=(0.08, 1.0), ratio=(0.75, 1.3333), hflip=0.0, reprob=0.25, remode="pixel", recount=1,
-                 num_sample=1, noise_seed=0):
+                 num_sample=1, noise_seed=0, randaug=None):
         if recount != 1:
             # (the script passes num_splits=args.recount, ssv2.py:220: recount > 1 would also leave the first T // recount frames clean)
             raise ValueError("recount != 1 is not built (one erase box per sample)")
@@ -272,6 +480,7 @@ class Augment:
         self.min_area, self.max_area = 0.02, 1 / 3
         self.log_aspect_ratio = (math.log(0.3), math.log(1 / 0.3))
         self.noise_key, self.drawn = splitmix64(int(noise_seed) & _M64), 0
+        self.randaug = randaug
 
     def _crop(self, height, width):
         """_get_param_spatial_crop (video_transforms.py:499-538; log_scale=True, switch_hw=False) -> (i, j, h, w)"""
@@ -321,8 +530,11 @@ class Augment:
             raise ValueError("Bs, H0, W0 >= 1")
         img = self.input_size
         aug_i = np.zeros((Bs * self.num_sample, 16), dtype=np.int32)
+        views = []
         for b in range(Bs * self.num_sample):
             row = aug_i[b]
+            if self.randaug is not None:
+                views.append(self.randaug.draw_view(H0, W0))
             row[0] = b // self.num_sample
             row[1:5] = self._crop(H0, W0)
             if self.hflip > 0:
@@ -333,7 +545,7 @@ class Augment:
             key = (self.noise_key + self.drawn) & _M64
             self.drawn += 1
             row[11:13] = np.array([key & 0xFFFFFFFF, key >> 32], dtype=np.uint32).view(np.int32)
-        return AugPlan(aug_i)
+        return AugPlan(aug_i, None if self.randaug is None else ra_plan(views, self.randaug.num_layers, self.num_sample))
 
 
 # ---------------------------------------------------------------------------------------------- the step
@@ -384,6 +596,29 @@ class FinetuneStep:
         K.mix_targets(targets.to(dev, torch.int32).contiguous(), table, soft, smoothing=mix.smoothing)
         return table, dict(soft_targets=soft)
 
+    def _randaug(self, samples, aug, dev):
+        """RandAugment in front of the gather: the source clips are uploaded ONCE into the head of a work tensor [Bs + 2 * B, T, H0,
+        W0, 3], the layers run over its two view regions (hip.randaug_u8), and the plan's source column is rewritten to the clip
+        every view ended in -- the gather then reads the augmented views like any source clips -> (work tensor, device aug table)"""
+        Bs, T, H0, W0 = samples.shape[:4]
+        B, ra = len(aug), aug.ra
+        if ra.num_sample < 1 or B != Bs * ra.num_sample or ra.ra_i.shape[0] != B:
+            raise ValueError(f"RandAugment plan: {ra.ra_i.shape[0]} views of {ra.num_sample} per clip for {Bs} clips, {B} samples")
+        src = np.asarray(aug.aug_i)[:, 0]
+        if (src != np.arange(B) // ra.num_sample).any():
+            raise ValueError("with RandAugment, sample b is a view of source clip b // num_sample")
+        table = K.RandaugTable(ra.ra_i, ra.ra_d, Bs=Bs, num_sample=ra.num_sample, device=dev)
+        shape = (Bs + 2 * B, T, H0, W0, 3)
+        if getattr(self, "_ra_work", None) is None or tuple(self._ra_work.shape) != shape:
+            self._ra_work = torch.empty(shape, dtype=torch.uint8, device=dev)
+            self._ra_hist = torch.empty((B, T, 4, 256), dtype=torch.int32, device=dev)
+        work = self._ra_work
+        work[:Bs].copy_(samples)
+        rows = K.randaug_u8(work, table, self._ra_hist)
+        aug_i = np.array(aug.aug_i, dtype=np.int64)
+        aug_i[:, 0] = rows
+        return work, K.aug_table(aug_i, Bs=Bs + 2 * B, H0=H0, W0=W0, img=self.model.engine.arch["image"], device=dev)
+
     @torch.no_grad()
     def step(self, samples, targets, mix=None, aug=None):
         """samples: fp32 [B, 3, T, H, W] or uint8 [B, T, H0, W0, 3]; targets: int64 labels [B] or soft [B, C].  mix: a MixPlan
@@ -391,7 +626,8 @@ class FinetuneStep:
         device with the plan's label smoothing; None: no mixing.  aug: an AugPlan (Augment.draw) -- samples are then the uint8
         SOURCE frames [Bs, T, H0, W0, 3] (any H0, W0 >= 1), the step has B = len(aug) samples, each cropped, resized, flipped and
         erased inside the gather from the source clip its row names; targets has B entries (the caller repeats the labels as the
-        collate does) and a MixPlan is drawn for B; None: uint8 clips take the centre crop, as before.
+        collate does) and a MixPlan is drawn for B; None: uint8 clips take the centre crop, as before.  A plan that carries a
+        RandAugment draw (Augment(..., randaug=...)) runs its ops on the device first, on the uploaded source frames (H0, W0 >= 3).
         -> dict(loss, logits, grad_norm, class_acc): device tensors; loss is the unscaled loss of this call (:70), grad_norm the
         global norm before clipping on a call that updates, else None."""
         m, eng, st = self.model, self.model.engine, self.model.store
@@ -401,7 +637,8 @@ class FinetuneStep:
         if aug is not None:
             if samples.dtype != torch.uint8 or samples.shape[-1] != 3 or min(samples.shape[:4]) < 1:
                 raise ValueError("with an augmentation plan the samples are uint8 source frames [Bs, T, H0, W0, 3]")
-            v, T, cm = samples.to(dev).contiguous(), samples.shape[1], False
+            # (a RandAugment plan uploads the clips into its work tensor instead: _randaug below)
+            v, T, cm = samples if aug.ra is not None else samples.to(dev).contiguous(), samples.shape[1], False
         elif samples.dtype == torch.uint8:
             if samples.shape[-1] != 3 or samples.shape[2] < a["image"] or samples.shape[3] < a["image"]:
                 raise ValueError(f"uint8 samples must be [B, T, H, W, 3] with H, W >= {a['image']}")
@@ -413,7 +650,10 @@ class FinetuneStep:
         if T == 0 or T % a["tubelet"] or T > a["num_frames"]:
             raise ValueError(f"clips of {T} frames: need a multiple of {a['tubelet']}, at most {a['num_frames']}")
         B, C = v.shape[0] if aug is None else len(aug), m.num_classes
-        atab = None if aug is None else K.aug_table(aug.aug_i, Bs=v.shape[0], H0=v.shape[2], W0=v.shape[3], img=a["image"], device=dev)
+        if aug is not None and aug.ra is not None:
+            v, atab = self._randaug(samples, aug, dev)
+        else:
+            atab = None if aug is None else K.aug_table(aug.aug_i, Bs=v.shape[0], H0=v.shape[2], W0=v.shape[3], img=a["image"], device=dev)
         if mix is None:
             table, tk = None, self._targets(targets, B, C, dev)
         else:

@@ -1037,6 +1037,93 @@ def patch_gather_tube_u8_aug(frames, keep, out, aug, mix=None, *, B, tubes, tube
          "tvts_patch_gather_tube_u8_aug")
 
 
+RA_MAX_LAYERS = 8
+_RA_STATS, _RA_INT, _RA_BLEND, _RA_AFFINE = (1, 2, 8), (4, 5, 6), (7, 8, 9, 10), 11
+
+
+def check_randaug_plan(ra_i, ra_d, *, B):
+    """the host-side check of a RandAugment plan (the C entry points take the tables as unchecked device data): ra_i integer
+    [B, L, 4] = (op, resample, iarg, 0), ra_d float [B, L, 8] = (a, b, c, d, e, f, factor, 0) -> (int32, float64) numpy arrays.
+    ValueError for L outside [1, 8], an op outside 0-11, an active op behind an empty slot (the ops of a view are compacted to the
+    front), a resample that is not 2 (bilinear) / 3 (bicubic) on an affine op or not 0 elsewhere, a threshold / add outside
+    [0, 256] or a posterize outside [0, 7], a nonzero iarg elsewhere, a coefficient that is not finite, or a nonzero reserved column."""
+    import numpy as np
+    ri, rd = np.asarray(ra_i), np.asarray(ra_d)
+    if ri.ndim != 3 or ri.shape[0] != B or ri.shape[2] != 4 or ri.dtype.kind not in "iu" or not (1 <= ri.shape[1] <= RA_MAX_LAYERS):
+        raise ValueError(f"randaug plan: integer ra_i [{B}, L <= {RA_MAX_LAYERS}, 4], got {ri.dtype} {ri.shape}")
+    if rd.shape != ri.shape[:2] + (8,) or rd.dtype.kind != "f":
+        raise ValueError(f"randaug plan: float ra_d {ri.shape[:2] + (8,)}, got {rd.dtype} {rd.shape}")
+    ri = ri.astype(np.int64)
+    op, rs, ia = ri[..., 0], ri[..., 1], ri[..., 2]
+    if ((op < 0) | (op > _RA_AFFINE)).any():
+        raise ValueError(f"randaug plan: op outside [0, {_RA_AFFINE}]")
+    if ((op[:, :-1] == 0) & (op[:, 1:] != 0)).any():
+        raise ValueError("randaug plan: the active ops of a view must be compacted to the front of its row")
+    aff = op == _RA_AFFINE
+    if (aff & (rs != 2) & (rs != 3)).any() or (~aff & (rs != 0)).any():
+        raise ValueError("randaug plan: resample 2 (bilinear) or 3 (bicubic) on an affine op, 0 elsewhere")
+    intop = np.isin(op, _RA_INT)
+    if (intop & ((ia < 0) | (ia > 256))).any() or ((op == 6) & (ia > 7)).any() or (~intop & (ia != 0)).any():
+        raise ValueError("randaug plan: iarg in [0, 256] for solarize / solarize-add, [0, 7] for posterize, 0 elsewhere")
+    if ri[..., 3].any() or rd[..., 7].any():
+        raise ValueError("randaug plan: the last column of ra_i and of ra_d is reserved and must be 0")
+    if not np.isfinite(rd).all():
+        raise ValueError("randaug plan: coefficients must be finite")
+    return np.ascontiguousarray(ri, dtype=np.int32), np.ascontiguousarray(rd, dtype=np.float64)
+
+
+def randaug_rows(ra_i, *, Bs, num_sample):
+    """the clip of the work tensor [Bs + 2 * B, ...] every view of a (checked, compacted) plan ends in: its source clip with no
+    active op, the first view region with an odd number of them, the second with an even number -> int32 [B]"""
+    import numpy as np
+    B = Bs * num_sample
+    k = (np.asarray(ra_i)[:, :, 0] != 0).sum(axis=1)
+    return np.where(k == 0, np.arange(B) // num_sample, Bs + np.where(k % 2 == 1, 0, B) + np.arange(B)).astype(np.int32)
+
+
+class RandaugTable:
+    """a checked RandAugment plan on the device, with what the host needs to launch its layers: ra_i / ra_d the device tables,
+    L the layers, stats[j] / active[j] whether some view's op in layer j needs frame statistics / is an op at all, rows[b] the
+    clip of the work tensor [Bs + 2 * B, ...] view b ends in (include/tvts_hip.h)"""
+
+    def __init__(self, ra_i, ra_d, *, Bs, num_sample, device="cuda"):
+        import numpy as np
+        B = Bs * num_sample
+        if Bs < 1 or num_sample < 1:
+            raise ValueError("randaug plan: Bs >= 1 and num_sample >= 1")
+        ri, rd = check_randaug_plan(ra_i, ra_d, B=B)
+        self.Bs, self.B, self.num_sample, self.L = Bs, B, num_sample, ri.shape[1]
+        self.stats = [bool(np.isin(ri[:, j, 0], _RA_STATS).any()) for j in range(self.L)]
+        self.active = [bool((ri[:, j, 0] != 0).any()) for j in range(self.L)]
+        self.rows = randaug_rows(ri, Bs=Bs, num_sample=num_sample)
+        self.ra_i, self.ra_d = torch.from_numpy(ri).to(device), torch.from_numpy(rd).to(device)
+
+
+def randaug_u8(work, table, hist=None):
+    """RandAugment on the device: work uint8 [Bs + 2 * B, T, H0, W0, 3] with the source clips in its first Bs rows, table a
+    RandaugTable; runs the layers (tvts_randaug_hist only for a layer where some view's op needs statistics, tvts_randaug_apply only
+    while some view is still active) on the current stream, nothing synchronises with the host.  View b ends in work[table.rows[b]].
+    hist: optional uint32 (int32 storage) scratch [B, T, 4, 256]; allocated when a layer needs it and none is given."""
+    n, T, H0, W0 = _u8_clips(work)
+    Bs, B, ns, L = table.Bs, table.B, table.num_sample, table.L
+    assert n == Bs + 2 * B, "work: [Bs + 2 * B, T, H0, W0, 3]"
+    if H0 < 3 or W0 < 3:
+        raise ValueError("RandAugment needs frames of at least 3 x 3")
+    if any(table.stats):
+        if hist is None:
+            hist = torch.empty((B, T, 4, 256), dtype=torch.int32, device=work.device)
+        assert hist.dtype == torch.int32 and hist.is_contiguous() and hist.numel() >= B * T * 1024
+    lib = _lib.load()
+    for j in range(L):
+        if not table.active[j]:
+            break
+        if table.stats[j]:
+            _chk(lib.tvts_randaug_hist(_p(work), Bs, B, ns, T, H0, W0, j, L, _p(table.ra_i), _p(hist), _stream()), "tvts_randaug_hist")
+        _chk(lib.tvts_randaug_apply(_p(work), Bs, B, ns, T, H0, W0, j, L, _p(table.ra_i), _p(table.ra_d),
+                                    _p(hist) if table.stats[j] else None, _stream()), "tvts_randaug_apply")
+    return table.rows
+
+
 def check_view_plan(view_i, *, Bs, Tsrc, H0, W0, T, img):
     """the host-side check of a test-view table (the C entry point takes it as unchecked device data): view_i integer [B, 8] =
     (src, t0, tstep, top, left, 0, 0, 0) -> int32 numpy array.  ValueError for a src outside [0, Bs), t0 < 0, tstep < 1, a last frame
