@@ -154,7 +154,10 @@ int tvts_gemm_tn_fp8(const void* P8, int ldp, const void* Q8, int ldq, int M, in
  * product whatever the contraction length, which only a long contraction's fp32-accumulation bound covers: contractions shorter
  * than 512 -- K of tvts_gemm_nt_fp8 / _fp8_gate, M of tvts_gemm_tn_fp8 -- run with the e4m3 values decoded to bf16 in registers
  * (exact) on the bf16 MFMA, whichever main loop `opts` names) */
-/* per-tensor fp8 quantisation: amax[0] = max |x| ; q = rne(x * 448 / amax) as e4m3, scale_out[0] = amax / 448 */
+/* per-tensor fp8 quantisation: amax[0] = max |x| ; q = rne(x * 448 / amax) as e4m3, scale_out[0] = amax / 448.
+ * Refused with -22 before any launch (here, in tvts_quant_fp8_rows, tvts_quant_fp8_multi and tvts_fp8_update_scales): rows / cols /
+ * n <= 0, cols % 8 (bf16) or % 4 (fp32), ld off a 16-byte multiple, ldo % 8, ld or ldo < cols with more than one row, a null x / out /
+ * amax / table / scale, and tvts_quant_fp8_rows with neither row_scale nor tscale */
 int tvts_amax(const void* x, int is_f32, long ld, int rows, int cols, float* amax, hipStream_t stream);
 int tvts_quant_fp8(const void* x, int is_f32, long ld, int rows, int cols, const float* amax, void* out, long ldo,
                    float* scale_out, hipStream_t stream);

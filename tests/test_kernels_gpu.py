@@ -1083,17 +1083,15 @@ def _e4m3(x):
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 def test_fp8_quantisation(K, dtype):
-    """per-tensor e4m3 (OCP) quantisation: bit patterns of torch.float8_e4m3fn on x * 448 / amax."""
+    """per-tensor e4m3 (OCP) quantisation: scale == fl32(amax / 448), and the bytes are exactly those of the independent encoder
+    (tests/fp8_cases.py) on x * fl32(1 / scale) with the scale the kernel returned -- the kernel multiplies by that reciprocal in
+    fp32, so nothing is left to a tie."""
     x = (rnd(300, 256, seed=51) * 3).to(dtype)
     x[5, 7] = -17.0
     q, scale = K.quantize_fp8(x.to(DEV))
-    s = float(x.float().abs().max()) / 448.0
-    assert abs(float(scale) - s) < 1e-7 * s
-    want = _e4m3(x.float() * (1.0 / torch.tensor(s, dtype=torch.float32)))
-    got = q.cpu().view(torch.float8_e4m3fn)
-    diff = (got.float() - want.float()).abs()
-    # identical except where x / scale sits within rounding of a tie (the kernel multiplies by 1 / scale in fp32)
-    assert float((diff > 0).float().mean()) < 2e-3 and float((diff / want.float().abs().clamp_min(1e-3)).max()) <= 0.13
+    assert float(scale) == FC.scale_of(float(x.double().abs().max())), float(scale)
+    KB.assert_equal_bits(q.cpu(), FC.encode_e4m3(x, FC.inv_of(float(scale))), "quantize_fp8 bytes")
+    assert torch.equal(q.cpu(), _e4m3(x.float() * torch.tensor(FC.inv_of(float(scale)), dtype=torch.float32)).view(torch.uint8))
     # a strided view (columns of a wider matrix)
     wide = torch.zeros(300, 512, dtype=dtype, device=DEV)
     wide[:, 128:384] = x.to(DEV)
@@ -1530,6 +1528,7 @@ def test_two_threads_call_different_shapes_and_options_concurrently(K):
 # with NaN / 0xFF guard rows and columns around what a kernel writes.  Each prints its worst |err| / bound ("BOUND" lines).
 import kernel_bounds as KB  # noqa: E402
 import gemm_cases as GC  # noqa: E402  (the form loops, shared with tests/test_gemm_edges_gpu.py)
+import fp8_cases as FC  # noqa: E402  (the independent e4m3 encoder)
 
 
 # forms a parametrised shape must take (the shapes test_gemm_nt_streamk / test_gemm_nt_ring_gives_the_bits_of_the_128_kernel /

@@ -742,6 +742,55 @@ def test_fp8_wgrad_path(gpu, h14):
     assert torch.equal(g3, store.grad)                             # identical scales, identical steps: identical bits
 
 
+def test_fp8_q8_only_forms_change_no_bit_of_the_step(gpu):
+    """arch["fp8_q8_only"] (the default with fp8_wgrad): the fused attention kernels, the LayerNorms and the MLP GEMMs write the e4m3
+    copy INSTEAD of the bf16 result.  H/14-style small model, the same calibration step and the same second step, once with
+    fp8_q8_only=False and once with the default.
+
+    The attention and LayerNorm only-forms encode the same bf16 values as their storing forms, so with them alone the step is bit
+    for bit the one without (ve, te, every gradient).  The GEMM only-form (store_out=False) cannot be: it quantises the fp32 result
+    where the storing form quantises its bf16 rounding, which moves a value across an e4m3 code boundary now and then
+    (tests/test_fp8_copies_gpu.py::test_gemm_epilogue_copy_is_the_encoder_on_the_stored_result holds each byte to that statement).
+    No arch flag switches the GEMM only-form off by itself, so the bit-equal run hands the default engine the `_q8_out` answer of
+    an engine without epilogue copies; the run with the GEMM only-form on is held to the gates test_fp8_wgrad_path sets for two
+    e4m3 steps that differ in where they round (its difference is a part of the e4m3 rounding noise those gates allow)."""
+    from tvts_amd import arch as A
+    mk = lambda **kw: A.small_arch_h(width=640, heads=8, fp8_wgrad=True, **kw)  # noqa: E731
+
+    def two_steps(m, batch):
+        engine_step(m, batch)
+        m.engine.end_step()
+        assert m.engine._f8_tensor_mode
+        _, _, te, ve, _, store = engine_step(m, batch)
+        return te, ve, store.grad.clone()
+
+    m0, oarch, P = build(arch=mk(fp8_q8_only=False), seed=4)
+    batch = O.synth_batch(oarch, B=4, T=3, seed=6, caption_len=11)
+    assert not m0.engine.fp8_q8_only and not m0.arch.get("fp8_epilogue_copies")
+    te0, ve0, g0 = two_steps(m0, batch)
+    m1, _, _ = build(arch=mk(), seed=4)
+    assert m1.engine.fp8_q8_only
+    m1.engine._q8_out = lambda *a, **kw: ({}, None)   # no epilogue copies: the attention and LayerNorm only-forms remain
+    only_calls = []
+    from tvts_amd import hip as K
+    fwd, bwd, ln = K.attn_fwd_divided, K.attn_bwd, K.layernorm_fwd
+    try:  # (count the only-form launches: the comparison below means nothing if none ran)
+        K.attn_fwd_divided = lambda *a, **kw: (only_calls.append("fwd") if kw.get("q8_only") else None, fwd(*a, **kw))[1]
+        K.attn_bwd = lambda *a, **kw: (only_calls.append("bwd") if kw.get("q8_only") else None, bwd(*a, **kw))[1]
+        K.layernorm_fwd = lambda x, g, b, eps, y, *a, **kw: (only_calls.append("ln") if y is None else None, ln(x, g, b, eps, y, *a, **kw))[1]
+        te1, ve1, g1 = two_steps(m1, batch)
+    finally:
+        K.attn_fwd_divided, K.attn_bwd, K.layernorm_fwd = fwd, bwd, ln
+    assert {"fwd", "bwd", "ln"} <= set(only_calls), set(only_calls)
+    assert torch.equal(te1, te0) and torch.equal(ve1, ve0) and torch.equal(g1, g0)
+    m2, _, _ = build(arch=mk(), seed=4)                # the default as it runs: the GEMM only-form too
+    te2, ve2, g2 = two_steps(m2, batch)
+    assert m2.engine._x8_only, "no GEMM ran in its only-output form"
+    assert torch.equal(te2, te0) or min_cos(te2, te0) > 0.9995
+    cos = float(torch.nn.functional.cosine_similarity(g0.double().flatten(), g2.double().flatten(), dim=0))
+    assert min_cos(ve2, ve0) > 0.999 and cos > 0.99 and abs(float(g2.double().norm()) / float(g0.double().norm()) - 1) < 0.03, (min_cos(ve2, ve0), cos)
+
+
 def test_b16_config2_against_reference_golden(gpu, golden):
     """The headline architecture (BASELINE config 2's model): the real TVTSv2_B_16 class ran in the build container at
     B=2, T=4 with tube mask 0.5 (98 of 196 patches kept: the fused SPACE / TIME attention kernels' shapes)."""

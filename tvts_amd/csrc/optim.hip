@@ -293,7 +293,8 @@ __global__ __launch_bounds__(256) void quant_fp8_kernel(const T* __restrict__ x,
 }
 static __global__ void zero1_kernel(float* p) { *p = 0.f; }
 extern "C" int tvts_amax(const void* x, int is_f32, long ld, int rows, int cols, float* amax, hipStream_t stream) {
-    if (rows <= 0 || cols <= 0 || cols % (is_f32 ? 4 : 8) || ld % (is_f32 ? 4 : 8)) return TVTS_EINVAL;
+    if (rows <= 0 || cols <= 0 || cols % (is_f32 ? 4 : 8) || ld % (is_f32 ? 4 : 8) || !x || !amax) return TVTS_EINVAL;
+    if (rows > 1 && ld < cols) return TVTS_EINVAL;  // overlapping rows
     hipLaunchKernelGGL(zero1_kernel, dim3(1), dim3(1), 0, stream, amax);  // a kernel, not a memset node (see attention.hip)
     const int blocks = rows < 1024 ? rows : 1024;
     if (is_f32) hipLaunchKernelGGL(amax_kernel<float>, dim3(blocks), dim3(256), 0, stream, (const float*)x, ld, rows, cols, amax);
@@ -303,7 +304,8 @@ extern "C" int tvts_amax(const void* x, int is_f32, long ld, int rows, int cols,
 }
 extern "C" int tvts_quant_fp8(const void* x, int is_f32, long ld, int rows, int cols, const float* amax, void* out, long ldo,
                               float* scale_out, hipStream_t stream) {
-    if (rows <= 0 || cols <= 0 || cols % (is_f32 ? 4 : 8) || ldo % 8 || ld % (is_f32 ? 4 : 8)) return TVTS_EINVAL;
+    if (rows <= 0 || cols <= 0 || cols % (is_f32 ? 4 : 8) || ldo % 8 || ld % (is_f32 ? 4 : 8) || !x || !amax || !out) return TVTS_EINVAL;
+    if (rows > 1 && (ld < cols || ldo < cols)) return TVTS_EINVAL;  // overlapping rows
     const int blocks = rows < 2048 ? rows : 2048;
     if (is_f32) hipLaunchKernelGGL(quant_fp8_kernel<float>, dim3(blocks), dim3(256), 0, stream, (const float*)x, ld, rows, cols, amax,
                                    (unsigned char*)out, ldo, scale_out);
@@ -441,6 +443,7 @@ extern "C" int tvts_fp8_update_scales(float* amax, float* scale, int n, hipStrea
 extern "C" int tvts_quant_fp8_rows(const void* x, long ld, int rows, int cols, void* out, long ldo, float* row_scale,
                                    const float* tscale, float* amax_acc, hipStream_t stream) {
     if (rows <= 0 || cols <= 0 || cols % 8 || ld % 8 || ldo % 8 || !x || !out || (!row_scale && !tscale)) return TVTS_EINVAL;
+    if (rows > 1 && (ld < cols || ldo < cols)) return TVTS_EINVAL;  // overlapping rows
     const long want = ((long)rows + 3) / 4;
     const int blocks = (int)(want < 8192 ? want : 8192);
     hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3(blocks), dim3(256), 0, stream, (const bf16*)x, ld, rows, cols,
