@@ -39,7 +39,16 @@ every step, as a loader's batch does (pinned buffers), so the upload is inside t
     host    the same ops by PIL on the host, per view and frame, in front of the step; every view is then a uint8 clip of its own
             and is uploaded separately (B clips instead of B / N).  PIL's own clock is reported.  Without PIL: says so and skips.
 --mixup device / torch may be combined with the --aug setting of the same name.  With --u8 (--aug off) or --aug device the
-gather's own time is measured too: device events around 50 launches of the step's gather on the step's shapes, in a pass of its own."""
+gather's own time is measured too: device events around 50 launches of the step's gather on the step's shapes, in a pass of its own.
+
+--gpus N: the data-parallel step, one process per GPU -- `python -m torch.distributed.run --nproc-per-node N tools/bench_finetune.py
+--gpus N --batch 8 --num-sample 2` (N = 1 also runs as a plain process, without a process group).  Every rank runs the default
+recipe's step on its own --batch samples (--aug device, --mixup device, --randaug device; per-rank draws seeded seed + rank as the
+script does) twice in the same process: FinetuneStep with the gradient exchange, and FinetuneStep(data_parallel=False).  Rank 0
+prints one JSON line: clips/s per node (N * batch over the slowest rank's step), bytes_sent per rank and updating step, both step
+times and the share of the step the exchange costs, and whether the replicas' checksums agree after the run.  --payload bf16
+halves the bytes.  --one-gpu: every rank on GPU 0 over gloo (the form of tools/dist_finetune_smoke.py) -- bytes_sent and the
+checksum agreement only; its times say nothing about scaling and the line says so."""
 import argparse
 import json
 import os
@@ -52,7 +61,7 @@ import torch  # noqa: E402
 KW = dict(img_size=224, patch_size=16, embed_dim=768, depth=12, num_heads=12, num_frames=16, tubelet_size=2)
 
 
-def make(trainable, args):
+def make(trainable, args, **step_kw):
     from tvts_amd.downstream.finetune_v1 import FinetuneStep, FusedTorchAdamW, param_groups
     from tvts_amd.downstream.video_encoder_v1 import VisionTransformer
     m = VisionTransformer(num_classes=args.classes, drop_path_rate=args.drop_path, init_seed=1, **KW)
@@ -60,7 +69,7 @@ def make(trainable, args):
     opt = FusedTorchAdamW(groups, m.store, lr=1e-3, model=m)
     for g in opt.param_groups:
         g["lr"] = 1e-4 * g["lr_scale"]
-    return m, FinetuneStep(m, opt, clip_grad=5.0, trainable=trainable), len(groups)
+    return m, FinetuneStep(m, opt, clip_grad=5.0, trainable=trainable, **step_kw), len(groups)
 
 
 def torch_mix(x, labels, plan, classes):
@@ -318,8 +327,80 @@ def run(trainable, args, clip, targets):
     return res
 
 
+def run_dist(args):
+    """--gpus N -> one JSON line on rank 0 (see the module docstring)"""
+    import random
+
+    import numpy as np
+    import torch.distributed as dist
+    from tvts_amd import dist as D
+    from tvts_amd.downstream.finetune_v1 import Augment, Mixup, RandAugment
+    launched = "WORLD_SIZE" in os.environ
+    if args.gpus > 1 and not launched:
+        raise SystemExit(f"--gpus {args.gpus}: run under `python -m torch.distributed.run --nproc-per-node {args.gpus}`")
+    if launched:
+        if int(os.environ["WORLD_SIZE"]) != args.gpus:
+            raise SystemExit(f"--gpus {args.gpus} under a launcher with WORLD_SIZE={os.environ['WORLD_SIZE']}")
+        torch.cuda.set_device(0 if args.one_gpu else int(os.environ.get("LOCAL_RANK", "0")))
+        dist.init_process_group("gloo" if args.one_gpu else "nccl")
+    W, rank = D.world()
+    dev = torch.cuda.current_device()
+    img, T, B, Bs = KW["img_size"], KW["num_frames"], args.batch, args.batch // args.num_sample
+    frames = torch.randint(0, 256, (Bs, T, SRC[0], SRC[1], 3), generator=torch.Generator().manual_seed(1 + rank), dtype=torch.uint8).pin_memory()
+    labels = torch.randint(0, args.classes, (B,), generator=torch.Generator().manual_seed(100 + rank))
+    res = {}
+    for name, dp in (("exchange", None), ("data_parallel=False", False)):
+        random.seed(rank)
+        np.random.seed(rank)
+        aug = Augment(img, hflip=0.0, reprob=0.25, remode="pixel", recount=1, num_sample=args.num_sample,
+                      randaug=RandAugment(RANDAUG, interpolation="bicubic", input_size=img))
+        mixup = Mixup(mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, mode="batch", label_smoothing=0.1, num_classes=args.classes)
+        m, step, _ = make("all", args, data_parallel=dp, payload=args.payload)
+
+        def one():
+            return step.step(frames, labels, aug=aug.draw(Bs, *SRC), mix=mixup.draw(B, img))
+        for _ in range(args.warmup):
+            one()
+        torch.cuda.synchronize()
+        if W > 1:
+            dist.barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.iters):
+            out = one()
+        torch.cuda.synchronize()
+        res[name] = dict(ms=1e3 * (time.perf_counter() - t0) / args.iters, bytes=step.bytes_sent, loss=float(out["loss"]),
+                         checksum=int(step.replicas_checksum()) if dp is None else 0)
+        del m, step
+        torch.cuda.empty_cache()
+    ex, loc = res["exchange"], res["data_parallel=False"]
+    # (the checksum travels as two 31-bit halves: gather_rows sums in float64-exact integers either way, this keeps it readable)
+    row = torch.tensor([ex["ms"], loc["ms"], float(ex["bytes"]), float(ex["checksum"] & 0x7FFFFFFF), float((ex["checksum"] >> 31) & 0x7FFFFFFF)],
+                       dtype=torch.float64)
+    rows = D.gather_rows(row)
+    if W > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+    if rank != 0:
+        return
+    slow_ex, slow_loc = float(rows[:, 0].max()), float(rows[:, 1].max())
+    out = {"what": "v1 FinetuneStep across ranks, ViT-B/16, 16 frames at 224, default recipe (aug, RandAugment, Mixup on the device)",
+           "gpus": W, "batch per rank": B, "num_sample": args.num_sample, "payload": args.payload or os.environ.get("TVTS_GRAD_PAYLOAD", "fp32"),
+           "transport": D.transport() if W > 1 else "none", "backend": ("gloo, every rank on GPU 0" if args.one_gpu else "nccl") if W > 1 else "none",
+           "iters": args.iters, "warmup": args.warmup, "device": torch.cuda.get_device_name(dev),
+           "step ms with the exchange (slowest rank)": slow_ex, "step ms, data_parallel=False (slowest rank)": slow_loc,
+           "exchange share of the step": (slow_ex - slow_loc) / slow_ex, "clips/s per node": W * B / (1e-3 * slow_ex),
+           "bytes_sent per rank and step": int(rows[0, 2]), "step ms by rank": [round(float(v), 3) for v in rows[:, 0]],
+           "replicas' checksums agree": bool((rows[:, 3:] == rows[0, 3:]).all()), "last loss (rank 0)": ex["loss"]}
+    if args.one_gpu and W > 1:
+        out["scaling"] = "NOT MEASURED: the ranks share one GPU (times above are not a scaling figure)"
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=0, help="the data-parallel step on N ranks (under torch.distributed.run); see the docstring")
+    ap.add_argument("--one-gpu", action="store_true", help="with --gpus N: every rank on GPU 0 over gloo (bytes and correctness only)")
+    ap.add_argument("--payload", choices=("fp32", "bf16"), default=None, help="with --gpus N: the gradients' format on the links")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--classes", type=int, default=174)
     ap.add_argument("--drop-path", type=float, default=0.1)
@@ -331,6 +412,12 @@ def main():
     ap.add_argument("--num-sample", type=int, default=1, help="views per decoded clip (--num_sample of the script)")
     ap.add_argument("--randaug", choices=("off", "device", "host"), default="off", help="RandAugment in front of the crop (--aug device)")
     args = ap.parse_args()
+    if args.gpus:
+        if args.gpus < 1 or args.batch % 2 or args.num_sample < 1 or args.batch % args.num_sample:
+            raise SystemExit("--gpus N >= 1, an even --batch (Mixup) and --num-sample a divisor of it")
+        if not torch.cuda.is_available():
+            raise SystemExit("bench_finetune.py measures on the GPU; there is none here (NOT MEASURED)")
+        return run_dist(args)
     if args.randaug != "off" and args.aug != "device":
         raise SystemExit("--randaug device / host: with --aug device (the rest of the augmentation stays on the device)")
     if args.randaug == "host":

@@ -60,6 +60,43 @@ def local_rows(grad_all: torch.Tensor, B: int) -> torch.Tensor:
     return grad_all[B * r:B * (r + 1)]
 
 
+# ------------------------------------------------------------------------------------------------ small host-side exchanges
+def _small_device() -> torch.device:
+    """where the tensor of a small bookkeeping collective lives: device memory under nccl (RCCL moves nothing else), else the host"""
+    if dist.get_backend() == "nccl":
+        return torch.device("cuda", torch.cuda.current_device())
+    return torch.device("cpu")
+
+
+def gather_rows(row: torch.Tensor) -> torch.Tensor:
+    """every rank's `row` (a host tensor, same shape and dtype on every rank) -> host tensor [W, *row.shape], rank r in row r.
+    ONE all-reduce (SUM) of a [W, ...] table in which a rank fills its own row: every rank receives the same bits, and whoever
+    sums the rows afterwards does so in rank order on every rank alike.  W == 1: no collective."""
+    W, r = world()
+    table = torch.zeros((W,) + tuple(row.shape), dtype=row.dtype)
+    table[r] = row
+    if W > 1:
+        t = table.to(_small_device())
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        table = t.cpu()
+    return table
+
+
+def agree(signature: bytes, what: str):
+    """checksum agreement: every rank hands in the bytes that describe its configuration; differing bytes raise RuntimeError on
+    EVERY rank (all of them see all checksums), so no rank walks on into a collective the others never enter."""
+    import hashlib
+    W, r = world()
+    if W == 1:
+        return
+    # 48 bits of the digest: exact in the int64 SUM of gather_rows whatever the other rows hold (they are zero)
+    mine = int.from_bytes(hashlib.sha256(signature).digest()[:6], "little")
+    sums = gather_rows(torch.tensor([mine], dtype=torch.int64)).view(-1).tolist()
+    if any(s != sums[0] for s in sums):
+        raise RuntimeError(f"{what} differs between the ranks (rank {r} of {W}; checksums by rank: "
+                           + ", ".join(f"{s:012x}" for s in sums) + ")")
+
+
 # ------------------------------------------------------------------------------------------------ native transport
 class NativeComm:
     """ctypes binding of libtvts_comm.so (include/tvts_comm.h); the unique id travels over the torch.distributed group

@@ -22,11 +22,21 @@ takes the mean (:277): mean and sum rank identically, the division is left out. 
 (np.argmax's rule; the reference's top-5 `np.argsort(-feat)[:5]` leaves the order of equal logits to the sort).
 ``merge(eval_path, num_tasks)`` is the host drop-in that reads the per-rank files, for multi-process runs.
 
+Several ranks (one process per GPU, torch.distributed initialised).  ``validation_one_epoch(loader, model, sync=None)``: after the
+local loop ONE float64 all-reduce carries every rank's [sum acc1_b n_b, sum acc5_b n_b, sum n_b, sum loss_b, batches]
+(dist.gather_rows: a [W, 5] table in which a rank fills its own row, so every rank sums the rows in rank order and returns the same
+bits) and ``merge_meters`` -- a host function, per-rank tuples in, dict out -- does what
+``SmoothedValue.synchronize_between_processes`` followed by ``global_avg`` does (utils.py:49-60): acc1 / acc5 weighted by sample
+count over all ranks, loss the plain mean over all batches of all ranks.  A rank whose loader gave no batch is refused on every
+rank.  ``ViewMerger.gather()``: merge without the files -- every rank contributes its seen slots (compact logits, labels, the
+host keys (video id, chunk, split)), every rank rebuilds the union by ``add``-ing the contributions in rank order, and
+tvts_view_store's first-line-wins rule resolves DistributedSampler's padding duplicates as the reference does with rank 0's file
+read first; the caller runs ``merger.gather().result()``.  The per-rank file + ``merge`` path works as before.
+
 Logits are the engine's fp32 (bf16 operands, fp32 accumulation).  The reference runs the model under fp16 autocast (:159,198): its
 logits, and the loss computed from them, carry fp16 rounding that is not reproduced here.
 
-OUT OF SCOPE (not built here): ``synchronize_between_processes`` (one process per call; several ranks write their own files and
-``merge`` reads them), decoding, the short-side resize in front of the views (cv2 / PIL work on the host beside decoding, as
+OUT OF SCOPE (not built here): decoding, the short-side resize in front of the views (cv2 / PIL work on the host beside decoding, as
 RandAugment is for training), the fp16 autocast rounding of the logits, and ``ModelEma`` (the scripts only save it and never
 evaluate it).
 """
@@ -37,6 +47,7 @@ import os
 import numpy as np
 import torch
 
+from .. import dist as D
 from .. import hip as K
 
 
@@ -76,26 +87,84 @@ class _Scores:
         self.ranks.append(K.class_ranks(logits, labels_dev))
         self.sizes.append(B)
 
-    def result(self):
-        """-> ({"loss", "acc1", "acc5"}, (acc1, acc5) of the last batch); the one synchronisation of the loop"""
-        if not self.sizes:
-            raise ValueError("the data loader gave no batch")
+    def _read(self):
+        """-> (loss per batch in double, top-1 hits per batch, top-5 hits per batch); the one synchronisation of the loop"""
         loss = torch.cat(self.loss).cpu().numpy().astype(np.float64)
         ranks = torch.cat(self.ranks).cpu().numpy()
         ends = np.cumsum(self.sizes)
         h1 = [int((ranks[e - n:e] < 1).sum()) for e, n in zip(ends, self.sizes)]
         h5 = [int((ranks[e - n:e] < 5).sum()) for e, n in zip(ends, self.sizes)]
+        return loss, h1, h5
+
+    def result(self):
+        """-> ({"loss", "acc1", "acc5"}, (acc1, acc5) of the last batch); the one synchronisation of the loop"""
+        if not self.sizes:
+            raise ValueError("the data loader gave no batch")
+        loss, h1, h5 = self._read()
         last = tuple(float(np.float32(h[-1]) * np.float32(100.0 / self.sizes[-1])) for h in (h1, h5))
         return dict(loss=float(loss.mean()), acc1=_meter_avg(h1, self.sizes), acc5=_meter_avg(h5, self.sizes)), last
 
+    def totals(self):
+        """this rank's meters as meter_totals() states them; a rank without a batch gives five zeros (it still has to enter the
+        exchange, where merge_meters refuses it on every rank)"""
+        if not self.sizes:
+            return (0.0, 0.0, 0.0, 0.0, 0.0)
+        loss, h1, h5 = self._read()
+        return meter_totals(h1, h5, self.sizes, loss)
+
+
+def meter_totals(h1, h5, sizes, loss):
+    """one rank's SmoothedValue state after its loop, as (sum acc1_b n_b, sum acc5_b n_b, sum n_b, sum loss_b, batches): acc_b is
+    the batch's fp32 percentage hits * (100 / n) (utils.accuracy), `total += value * n` and `count += n` run in Python doubles
+    (utils.py:33-36); the loss meter counts every batch once"""
+    a1 = sum(float(np.float32(h) * np.float32(100.0 / n)) * n for h, n in zip(h1, sizes))
+    a5 = sum(float(np.float32(h) * np.float32(100.0 / n)) * n for h, n in zip(h5, sizes))
+    return (a1, a5, float(sum(sizes)), float(sum(float(v) for v in loss)), float(len(sizes)))
+
+
+def merge_meters(per_rank):
+    """SmoothedValue.synchronize_between_processes followed by global_avg (utils.py:49-60,76-78) on the host: per_rank is one
+    meter_totals() tuple per rank, in rank order -> {"loss", "acc1", "acc5"}.  count and total are summed over the ranks in
+    double, in rank order; acc1 / acc5 = total / count with count the SAMPLES of all ranks, loss = total / count with count the
+    BATCHES of all ranks.  A rank without a batch is refused, as the single-process loop refuses an empty loader (in the
+    reference that rank has no meter to synchronise and fails alone)."""
+    rows = [tuple(float(v) for v in r) for r in per_rank]
+    if not rows or any(len(r) != 5 for r in rows):
+        raise ValueError("per_rank: one (sum acc1 n, sum acc5 n, sum n, sum loss, batches) tuple per rank")
+    empty = [i for i, r in enumerate(rows) if r[4] <= 0 or r[2] <= 0]
+    if empty:
+        raise ValueError(f"the data loader gave no batch on rank {empty[0]}")
+    tot = [0.0] * 5
+    for r in rows:
+        tot = [t + v for t, v in zip(tot, r)]
+    return dict(loss=tot[3] / tot[4], acc1=tot[0] / tot[2], acc5=tot[1] / tot[2])
+
+
+def sync_meters(totals):
+    """this rank's meter_totals() -> the merged {"loss", "acc1", "acc5"}, the same on every rank: ONE float64 all-reduce carries the
+    five numbers of every rank (dist.gather_rows), merge_meters does the arithmetic"""
+    return merge_meters(D.gather_rows(torch.tensor([float(v) for v in totals], dtype=torch.float64)).tolist())
+
+
+def _use_ranks(sync):
+    """sync None: on with more than one rank.  True without a process group is refused"""
+    if sync and not (D.dist.is_available() and D.dist.is_initialized()):
+        raise RuntimeError("sync=True needs an initialised torch.distributed process group")
+    return D.world()[0] > 1 and (sync is None or bool(sync))
+
 
 @torch.no_grad()
-def validation_one_epoch(data_loader, model, device=None):
+def validation_one_epoch(data_loader, model, device=None, sync=None):
     """engine_for_finetuning.py:142-174 -> {"loss", "acc1", "acc5"} (the reference's keys).  A batch is (videos, target, ...):
     videos fp32 [B, 3, T, H, W] or uint8 [B, T, H0, W0, 3] (centre crop and normalisation on the device), target integer [B].
     acc1 / acc5 in percent, weighted by batch size; loss the unweighted mean of the batch means (the reference's meters).  Nothing
     synchronises with the host until the loader is exhausted.  The logits are the engine's fp32: the reference computes them, and
-    the loss, under fp16 autocast.  device: accepted for the reference's signature; the model's device is used."""
+    the loss, under fp16 autocast.  device: accepted for the reference's signature; the model's device is used.
+    sync: None -- with more than one rank of torch.distributed the meters are merged over the ranks after the local loop
+    (`metric_logger.synchronize_between_processes()`, :170: sync_meters, one float64 all-reduce) and every rank returns the same
+    numbers -- acc1 / acc5 weighted by sample count over all ranks, loss the plain mean over all batches of all ranks; False --
+    this rank's own numbers."""
+    ranks = _use_ranks(sync)
     model.eval()
     sc = _Scores(model)
     for batch in data_loader:
@@ -104,6 +173,8 @@ def validation_one_epoch(data_loader, model, device=None):
         if logits.shape[0] != labels.numel():
             raise ValueError(f"{labels.numel()} labels for {logits.shape[0]} clips")
         sc.add(logits, labels.to(sc.dev))
+    if ranks:
+        return sync_meters(sc.totals())
     return sc.result()[0]
 
 
@@ -218,6 +289,43 @@ class ViewMerger:
                 raise ValueError(f"view (chunk {c}, split {s}) outside the {self.V // self.num_crop} x {self.num_crop} views of a video")
             slot[b] = self.index_of(vid) * self.V + c * self.num_crop + s
         K.view_store(logits, torch.from_numpy(slot).to(self.dev), labels_dev, self.view_logits, self.seen, self.labels)
+
+    def gather(self):
+        """-> a ViewMerger that holds the views of EVERY rank, the same on every rank: merge (:231-270) without the files.  Each rank
+        contributes only its seen slots -- compact logits [n_seen, C] and labels, and the host keys (video id, chunk, split) --
+        and every rank rebuilds the union by ``add``-ing the contributions in rank order 0 .. W - 1, so tvts_view_store applies
+        merge's rule unchanged: the first line of a (video, chunk, split) wins, rank 0's lines read first (the duplicates
+        DistributedSampler pads the last batch with resolve as in the reference).  Video rows are assigned from the gathered keys
+        in that order; the per-rank first-seen dictionaries differ and are not reused.  One rank: a copy of this merger's views."""
+        W, _ = D.world()
+        seen = self.seen.cpu().numpy().reshape(-1)
+        slots = np.flatnonzero(seen)
+        ids = {i: vid for vid, i in self.index.items()}
+        keys = [(ids[int(s) // self.V], (int(s) % self.V) // self.num_crop, (int(s) % self.V) % self.num_crop) for s in slots]
+        sl = torch.from_numpy(slots.astype(np.int64)).to(self.dev)
+        logits = self.view_logits.view(self.N * self.V, self.C).index_select(0, sl)
+        labels = self.labels.index_select(0, sl // self.V)
+        if W == 1:
+            parts = [(keys, logits, labels)]
+        else:
+            every = [None] * W
+            D.dist.all_gather_object(every, keys)
+            rows = max(1, max(len(k) for k in every))  # (every rank sends tensors of the longest contribution's size)
+            lg = torch.zeros(rows, self.C, dtype=torch.float32, device=self.dev)
+            lb = torch.zeros(rows, dtype=torch.int32, device=self.dev)
+            lg[:len(keys)].copy_(logits)
+            lb[:len(keys)].copy_(labels)
+            all_lg = [torch.empty_like(lg) for _ in range(W)]
+            all_lb = [torch.empty_like(lb) for _ in range(W)]
+            D.dist.all_gather(all_lg, lg)
+            D.dist.all_gather(all_lb, lb)
+            parts = [(k, a[:len(k)], b[:len(k)]) for k, a, b in zip(every, all_lg, all_lb)]
+        videos = {k[0] for ks, _, _ in parts for k in ks}
+        out = ViewMerger(max(1, len(videos)), self.V, self.C, self.dev, num_crop=self.num_crop)
+        for ks, lg, lb in parts:
+            if ks:
+                out.add(lg.contiguous(), lb.contiguous(), [k[0] for k in ks], [k[1] for k in ks], [k[2] for k in ks])
+        return out
 
     def result(self):
         """-> (top1 * 100, top5 * 100) over the videos that have a view, as merge returns them (:265-270)"""

@@ -51,17 +51,52 @@ of a work tensor [Bs + 2 * B, T, H0, W0, 3] and runs the layers over its two vie
 one launch pair per layer, csrc/randaug.hip) with the bytes PIL gives -- every op, bilinear and bicubic -- then points the
 plan's source column at the clip each view ended in, so the gather above reads the augmented views unchanged.
 
+Several GPUs (run_class_finetuning.py / run_class_linear.py wrap the model in DistributedDataParallel, :403-406 of the latter;
+train_one_epoch's non-DeepSpeed path, engine_for_finetuning.py:55-123): one process per GPU, torch.distributed initialised as the
+script does, and the same two lines -- no wrap.
+
+    step = FinetuneStep(model, opt, clip_grad=5.0, update_freq=1)                  # data_parallel=None: on with more than one rank
+    out = step.step(samples, targets, mix=..., aug=...)                            # this rank's shard; step.bytes_sent afterwards
+
+What replaces the wrap: at construction the ranks agree, by checksum, on the model size, `trainable`, update_freq, clip_grad, the
+payload and the optimizer's chunk / group table (a mismatch raises on EVERY rank, none is left inside a collective), then rank
+0's fp32 masters (store.flat) are broadcast and the bf16 shadows re-derived from them -- replicas start equal, as behind DDP's
+wrap-time broadcast.  Only the call that updates (calls % update_freq == 0) exchanges gradients: the reference all-reduces on
+every micro-step, and since the average of sums is the sum of averages, ONE exchange of the accumulated buffer is the same update
+with 1 / update_freq of the traffic.  On that call the engine's grad_ready hook is armed with dist.GradSync.reduce_range in front of
+finetune_backward and disarmed behind it, so the ranges travel (asynchronously, SUM) under the remaining backward: the head first,
+the blocks depth - 1 .. 0, then the embedding parameters and the final norm.  Frozen ranges never travel (Engine._ready hands over
+trainable runs only; with trainable="head" the whole exchange is the head's range) and a call that only accumulates issues no
+collective.  Then: GradSync.finish(), tvts_grad_sumsq with grad_scale = 1 / W, tvts_adamw_torch with the same grad_scale, the zero
+fill -- so grad_norm is the global norm of the AVERAGED gradient, what clip_grad_norm_ sees behind DDP (utils.py:366), and the clip
+coefficient is the same number on every rank.  `loss` and `class_acc` stay per-rank device tensors: the reference logs per-rank
+values too, and the script's MetricLogger does the epoch-end reduction on the host, unchanged.  payload="bf16" (or
+TVTS_GRAD_PAYLOAD=bf16, as for pretraining) sends the gradients as bf16, half the bytes; fp32 is the default and keeps the
+reference's fp32 all-reduce.  Both transports of dist.transport() carry it; the native one stays opt-in (TVTS_COMM=native).
+FinetuneStep.replicas_checksum() is a device int64 over the parameter bits: compare it across ranks to assert that the replicas
+are still equal.  With one rank (or data_parallel=False) nothing of this exists: no collective is created and the step is the
+single-process step bit for bit.
+
+Random draws across ranks.  Stochastic depth: every rank draws its own masks -- the engine's seed carries a per-rank offset
+(EngineV1._rank_offset), whether the process group exists when the model is built or is created afterwards (FinetuneStep adopts
+the rank at construction, EngineV1.adopt_rank).  Resume: ``model.engine.drop_seed_base()`` is the rank-independent part of the
+seed -- rank 0 writes it into the checkpoint, EVERY rank reads it back with ``set_drop_seed_base(base)`` and continues its own
+mask sequence (loading rank 0's seed verbatim would give all ranks rank 0's masks).  The host draws (Mixup.draw, Augment.draw,
+RandAugment) use the global ``random`` / ``np.random``, which the script seeds with ``args.seed + rank``
+(run_class_finetuning.py:230): they differ per rank as in the reference and need nothing here.
+
 OUT OF SCOPE (not built here): RandAugment's per-frame ``"random"`` interpolation and TranslateX / TranslateY (abs) (neither list of
 rand_augment_transform holds them), --recount > 1,
 ``motion_shift`` (random_resized_crop_with_shift), the reference's torch noise stream,
-``FastCollateMixup`` (the uint8-rounding variant: the reference scripts do not use it), ``ModelEma``, the fp16 loss scaler (the engine is bf16 with fp32 accumulation: there is no loss scale), DeepSpeed, the multi-GPU
-gradient exchange for this step (the backward keeps its Engine._ready calls so that one can hook in), and hipGraph capture of it.
+``FastCollateMixup`` (the uint8-rounding variant: the reference scripts do not use it), ``ModelEma``, the fp16 loss scaler (the engine is bf16 with fp32 accumulation: there is no loss scale), DeepSpeed,
+sharded optimizer state, synchronising the TRAINING meters (the script's MetricLogger), and hipGraph capture of the step.
 The scripts' other half -- validation_one_epoch after every epoch, final_test over the test views and merge
-(engine_for_finetuning.py:142-285) -- is tvts_amd/downstream/evaluate_v1.py.
+(engine_for_finetuning.py:142-285), both across ranks too -- is tvts_amd/downstream/evaluate_v1.py.
 """
 from __future__ import annotations
 
 import math
+import os
 import random
 import re
 from typing import NamedTuple
@@ -69,6 +104,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
+from .. import dist as D
 from .. import hip as K
 from ..optim import FusedTorchAdamW  # noqa: F401  (re-exported)
 
@@ -551,9 +587,18 @@ class Augment:
 # ---------------------------------------------------------------------------------------------- the step
 class FinetuneStep:
     """train_one_epoch's loop body (engine_for_finetuning.py:55-123) without DeepSpeed / loss scaler.  ``trainable="head"`` is
-    linear probing: the backward stops behind the head; build the optimizer from ``param_groups(..., trainable="head")``."""
+    linear probing: the backward stops behind the head; build the optimizer from ``param_groups(..., trainable="head")``.
+    With more than one rank of torch.distributed it is the data-parallel step (module docstring, "Several GPUs")."""
 
-    def __init__(self, model, optimizer: FusedTorchAdamW, clip_grad=None, update_freq=1, smoothing=0.0, trainable="all"):
+    def __init__(self, model, optimizer: FusedTorchAdamW, clip_grad=None, update_freq=1, smoothing=0.0, trainable="all",
+                 data_parallel=None, payload=None):
+        """data_parallel: None -- on when torch.distributed is initialised with more than one rank; False -- the single-process
+        step whatever the world size; True without a process group is refused.  payload: "fp32" (default) or "bf16", the number
+        format the gradients travel in; None reads TVTS_GRAD_PAYLOAD, as the pretraining step does."""
+        if payload not in (None, "fp32", "bf16"):
+            raise ValueError(f"payload {payload!r}: expected 'fp32' or 'bf16' (None: TVTS_GRAD_PAYLOAD, default fp32)")
+        if data_parallel and not (D.dist.is_available() and D.dist.is_initialized()):
+            raise RuntimeError("data_parallel=True needs an initialised torch.distributed process group")
         if model.num_classes <= 0:
             raise ValueError("FinetuneStep needs a model with a head (num_classes > 0)")
         if update_freq < 1 or not (0.0 <= smoothing < 1.0):
@@ -570,6 +615,36 @@ class FinetuneStep:
         self.loss_cell = torch.zeros(1, dtype=torch.float32, device=dev)
         self.hits = torch.zeros(1, dtype=torch.int32, device=dev)
         self.calls = 0
+        model.engine.adopt_rank()  # (a process group created after the model: the seed moves to this rank's mask sequence)
+        self.world = D.world()[0]
+        self.sync = None
+        if self.world > 1 and (data_parallel is None or data_parallel):
+            self._join(payload)
+
+    def _join(self, payload):
+        """what DistributedDataParallel does at wrap time: the ranks agree on what they are about to exchange, then take rank 0's
+        parameters.  The agreement comes first -- ranks that disagree (another model, another `trainable`, another group table)
+        all raise, none is left inside the broadcast."""
+        st, opt = self.model.store, self.opt
+        pay = payload or os.environ.get("TVTS_GRAD_PAYLOAD", "fp32")
+        sig = repr((int(st.flat.numel()), self.trainable, self.update_freq, self.clip_grad, pay, len(opt.param_groups),
+                    [float(g["weight_decay"]) for g in opt.param_groups])).encode() + opt.chunk_group.cpu().numpy().tobytes()
+        D.agree(sig, "FinetuneStep: the model size, `trainable`, update_freq, clip_grad, payload or the optimizer's chunk / group table")
+        D.dist.broadcast(st.flat, src=0)
+        st.refresh_shadows()
+        self.model.mark_shadows_fresh()
+        self.sync = D.GradSync(st.grad, payload=pay)
+
+    @property
+    def bytes_sent(self) -> int:
+        """the bytes this rank handed to the gradient exchange in the last call of step() (0: a call that only accumulated, or
+        the single-process step)"""
+        return 0 if self.sync is None else self.sync.bytes_sent
+
+    def replicas_checksum(self) -> torch.Tensor:
+        """device int64 scalar: the sum of the fp32 masters' bit patterns (store.flat read as int32, summed in int64).  Equal
+        replicas give equal sums; compare it across ranks (or against a checkpoint) instead of the parameters.  No host sync."""
+        return self.model.store.flat.view(torch.int32).sum(dtype=torch.int64)
 
     def _targets(self, targets, B, C, dev):
         if targets.dim() == 1 and not targets.is_floating_point():
@@ -629,7 +704,8 @@ class FinetuneStep:
         collate does) and a MixPlan is drawn for B; None: uint8 clips take the centre crop, as before.  A plan that carries a
         RandAugment draw (Augment(..., randaug=...)) runs its ops on the device first, on the uploaded source frames (H0, W0 >= 3).
         -> dict(loss, logits, grad_norm, class_acc): device tensors; loss is the unscaled loss of this call (:70), grad_norm the
-        global norm before clipping on a call that updates, else None."""
+        global norm before clipping on a call that updates, else None.  Across ranks loss / logits / class_acc are this rank's,
+        grad_norm is the norm of the gradient averaged over the ranks (the same value on every rank)."""
         m, eng, st = self.model, self.model.engine, self.model.store
         a, dev = eng.arch, st.device
         if samples.dim() != 5:
@@ -663,13 +739,28 @@ class FinetuneStep:
         dlogits, ws = eng._f("ft.dlogits", (B, C)), eng._f("ft.ce_ws", (2 * B,))
         K.zero_(self.loss_cell)
         K.soft_ce(logits, self.loss_cell, ws, scale=1.0 / self.update_freq, dlogits=dlogits, hits=self.hits, **tk)
-        eng.finetune_backward(dlogits, self.trainable)
+        updating = (self.calls + 1) % self.update_freq == 0
+        sync, hook = self.sync, eng.grad_ready
+        if sync is not None:
+            sync.bytes_sent = 0
+            if updating:  # the accumulated gradient travels once, range by range under the rest of this backward
+                eng.grad_ready = sync.reduce_range
+        try:
+            eng.finetune_backward(dlogits, self.trainable)
+        finally:
+            eng.grad_ready = hook
         self.calls += 1
         grad_norm = None
-        if self.calls % self.update_freq == 0:
-            K.grad_sumsq(st.grad, self.opt.chunk_group, self.partial, self.norm_coef, max_norm=self.clip_grad,
-                         grad_scale=self.opt.grad_scale)
-            self.opt.step()
+        if updating:
+            # behind the exchange the buffer holds the SUM over the ranks; 1 / W rides in the norm and in the update, so grad_norm
+            # is the norm of the averaged gradient and the clip coefficient is the same number on every rank
+            scale = self.opt.grad_scale if sync is None else self.opt.grad_scale * sync.finish()
+            K.grad_sumsq(st.grad, self.opt.chunk_group, self.partial, self.norm_coef, max_norm=self.clip_grad, grad_scale=scale)
+            kept, self.opt.grad_scale = self.opt.grad_scale, scale
+            try:
+                self.opt.step()
+            finally:
+                self.opt.grad_scale = kept
             K.zero_(st.grad)
             grad_norm = self.norm_coef[0].clone()
         return dict(loss=self.loss_cell[0] * float(self.update_freq), logits=logits.clone(), grad_norm=grad_norm,

@@ -42,7 +42,8 @@ class EngineV1(Engine):
         # every data-parallel rank draws its own masks, as the reference's ranks do (each seeds its own generator): the rank is mixed
         # into the seed with an odd 64-bit constant.  The seed is trainer state: Trainer_TVTS saves it with the checkpoint.
         from .dist import world
-        seed = (int(self.arch.get("dropout_seed", 0x1234ABCD)) + world()[1] * self.DROP_RANK_STRIDE) & ((1 << 64) - 1)
+        self._drop_rank = world()[1]  # the rank whose offset the seed carries (adopt_rank: a process group created afterwards)
+        seed = (int(self.arch.get("dropout_seed", 0x1234ABCD)) + self._drop_rank * self.DROP_RANK_STRIDE) & ((1 << 64) - 1)
         self.drop_seed = torch.tensor([seed - (1 << 64) if seed >= (1 << 63) else seed], dtype=torch.int64, device=self.dev)
         self._drop_active = 0.0
 
@@ -56,15 +57,23 @@ class EngineV1(Engine):
     def drop_seed_base(self) -> int:
         """the rank-independent part of the seed (configured seed + step advances, unsigned 64-bit): what a checkpoint stores --
         rank 0 writes the file, every rank reads it"""
-        from .dist import world
-        return ((int(self.drop_seed.item()) & ((1 << 64) - 1)) - self._rank_offset(world()[1])) & ((1 << 64) - 1)
+        return ((int(self.drop_seed.item()) & ((1 << 64) - 1)) - self._rank_offset(self._drop_rank)) & ((1 << 64) - 1)
 
     def set_drop_seed_base(self, base: int):
         """resume: this rank's seed = stored base + this rank's offset (mod 2^64), so that every rank continues ITS OWN mask
         sequence -- loading rank 0's seed verbatim would give all ranks the same masks"""
         from .dist import world
-        seed = ((int(base) & ((1 << 64) - 1)) + self._rank_offset(world()[1])) & ((1 << 64) - 1)
+        self._drop_rank = world()[1]
+        seed = ((int(base) & ((1 << 64) - 1)) + self._rank_offset(self._drop_rank)) & ((1 << 64) - 1)
         self.drop_seed.fill_(seed - (1 << 64) if seed >= (1 << 63) else seed)
+
+    def adopt_rank(self):
+        """The seed carries the offset of the rank this process had when the engine was built.  A process group that was created
+        AFTERWARDS gives the process another rank: move the seed to that rank's sequence (same base), or every rank would draw
+        rank 0's masks.  Nothing happens, and nothing is read back, when the rank is the one the seed already carries."""
+        from .dist import world
+        if world()[1] != self._drop_rank:
+            self.set_drop_seed_base(self.drop_seed_base())
 
     def _advance_drop_seed(self):
         """new masks for this step (a device op: a captured graph advances the seed on every replay)"""
