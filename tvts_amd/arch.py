@@ -252,3 +252,47 @@ def param_group_of(name: str, arch) -> int:
                 return -1
         return 2 + int(nd)
     return int(nd)
+
+
+# ---- activation recomputation of the video towers (DESIGN.md "Activation recomputation"); no device needed for any of this
+RECOMPUTE_MODES = ("none", "mlp", "block")
+
+
+def recompute_mode(value) -> str:
+    """What set_grad_checkpointing() and the `grad_checkpointing` entry of the reference's args take -> a mode of RECOMPUTE_MODES:
+    None / False -> "none", True -> "block" (the reference's switch checkpoints whole blocks, video_encoder_ViT_H_14.py:289-294),
+    a mode string -> itself.  ValueError for anything else, the unknown mode by name."""
+    if value is None or value is False:
+        return "none"
+    if value is True:
+        return "block"
+    if isinstance(value, str) and value in RECOMPUTE_MODES:
+        return value
+    raise ValueError(f"recompute mode {value!r}: expected one of {RECOMPUTE_MODES} (or a bool: True = 'block')")
+
+
+def check_recompute(arch, mode=None) -> str:
+    """The mode an engine over `arch` runs in (mode None: arch["recompute"], absent = "none"), validated: an unknown mode and any
+    mode but "none" together with the e4m3 options are refused by name -- the e4m3 operand copies live in persistent per-layer
+    buffers under per-tensor amax state, which a shared slot would overwrite and a second evaluation would record twice."""
+    mode = recompute_mode(arch.get("recompute") if mode is None else mode)
+    if mode != "none":
+        for key in ("fp8", "fp8_dgrad", "fp8_wgrad"):
+            if arch.get(key):
+                raise ValueError(f"recompute={mode!r} together with arch[{key!r}]: activation recomputation is built for the bf16 "
+                                 f"architectures only")
+    return mode
+
+
+def recompute_from_args(args, arch) -> str:
+    """The constructors' rule: an explicit arch["recompute"] wins, else the `grad_checkpointing` entry (bool or mode string) of the
+    reference's args -- a dict, or a namespace (also one that carries the dict as `.args`) -- else "none"."""
+    if arch.get("recompute") is not None:
+        return recompute_mode(arch["recompute"])
+    for src in (args, getattr(args, "args", None)):
+        if isinstance(src, dict):
+            if src.get("grad_checkpointing") is not None:
+                return recompute_mode(src["grad_checkpointing"])
+        elif src is not None and getattr(src, "grad_checkpointing", None) is not None:
+            return recompute_mode(getattr(src, "grad_checkpointing"))
+    return "none"

@@ -628,8 +628,9 @@ class FinetuneStep:
         st, opt = self.model.store, self.opt
         pay = payload or os.environ.get("TVTS_GRAD_PAYLOAD", "fp32")
         sig = repr((int(st.flat.numel()), self.trainable, self.update_freq, self.clip_grad, pay, len(opt.param_groups),
-                    [float(g["weight_decay"]) for g in opt.param_groups])).encode() + opt.chunk_group.cpu().numpy().tobytes()
-        D.agree(sig, "FinetuneStep: the model size, `trainable`, update_freq, clip_grad, payload or the optimizer's chunk / group table")
+                    [float(g["weight_decay"]) for g in opt.param_groups], self.model.engine.recompute)).encode() + opt.chunk_group.cpu().numpy().tobytes()
+        D.agree(sig, "FinetuneStep: the model size, `trainable`, update_freq, clip_grad, payload, the recomputation mode or the "
+                     "optimizer's chunk / group table")
         D.dist.broadcast(st.flat, src=0)
         st.refresh_shadows()
         self.model.mark_shadows_fresh()

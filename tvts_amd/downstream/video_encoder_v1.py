@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from .. import hip as K
-from ..arch import ARCH_V1
+from ..arch import ARCH_V1, recompute_mode
 from ..engine import ParamStore
 from ..engine_v1 import EngineV1
 from ..model._common import _require_gpu
@@ -43,7 +43,7 @@ def _norm_eps(norm_layer):
 class VisionTransformer(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=0, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4.,
                  qkv_bias=True, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0., norm_layer=None, num_frames=16,
-                 tubelet_size=2, representation_size=None, device_index=0, init_seed=0):
+                 tubelet_size=2, representation_size=None, device_index=0, init_seed=0, grad_checkpointing=False):
         super().__init__()
         if not qkv_bias:
             raise NotImplementedError("qkv_bias=False is not built (every shipped v1 checkpoint has the bias)")
@@ -67,7 +67,8 @@ class VisionTransformer(nn.Module):
         self.patches_per_frame = (img_size // patch_size) ** 2
         self.arch = dict(ARCH_V1, name="v1_video", image=int(img_size), patch=int(patch_size), tubelet=int(tubelet_size),
                          width=int(embed_dim), heads=int(num_heads), layers=int(depth), num_frames=int(num_frames),
-                         towers="video", head_classes=self.num_classes, sort_head=False)
+                         towers="video", head_classes=self.num_classes, sort_head=False,
+                         recompute=recompute_mode(grad_checkpointing))  # (FinetuneStep's backward; a bool or a mode string)
         dev = _require_gpu(device_index)
         self.store = ParamStore(self.arch, dev)
         self.engine = EngineV1(self.store)
@@ -130,6 +131,12 @@ class VisionTransformer(nn.Module):
         for n, _ in self.named_parameters():
             out[n] = self.engine.requires_grad[self.store_name(n)] = trainable == "all" or n.startswith("head.")
         return out
+
+    def set_grad_checkpointing(self, enable=True):
+        """activation recomputation in FinetuneStep's backward: True -- "block" (every block is evaluated again from its kept input,
+        drop-path table and all, instead of keeping what it saves), False -- "none", or a mode string ("none" / "mlp" / "block").
+        Same logits, loss, gradient norm and update, bit for bit.  May be called between steps; workspaces only grow."""
+        self.engine.set_recompute(recompute_mode(enable))
 
     def mark_shadows_fresh(self):
         """the fused optimizer rewrote the bf16 shadows together with the parameters"""

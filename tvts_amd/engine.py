@@ -25,7 +25,7 @@ import os
 import torch
 
 from . import hip as K
-from .arch import is_mfma_weight, n_keep, param_shapes, patches_per_frame
+from .arch import check_recompute, is_mfma_weight, n_keep, param_shapes, patches_per_frame
 
 CH = 1024  # flat-buffer alignment / optimizer chunk (elements)
 
@@ -275,6 +275,17 @@ class Engine:
         self._dy8_ready: Dict[str, tuple] = {}
         self._wg_stream = None
         self._wg_ws = None
+        # Activation recomputation of the VIDEO tower (DESIGN.md "Activation recomputation"): arch["recompute"] "none" | "mlp" | "block".
+        #   "block"  the forward keeps the residual stream behind every block (x<l>, xc<l>); every other tensor a block saves goes
+        #            into ONE slot shared by all blocks (two, by layer parity, beside the weight-gradient side stream), and the
+        #            backward re-runs block l's training forward from x<l> into the slot just before block l's backward;
+        #   "mlp"    everything is kept but the two [M, 4W] tensors of the MLP (act'(x) and the activation), which share one pair of
+        #            buffers; the backward re-runs fc1 from the kept ln2.
+        # The second evaluation launches the kernels of the first on the same operand bytes, so it leaves the same bits.
+        self.recompute = check_recompute(a)
+        self.recompute_count = 0                  # block (or fc1) re-evaluations of the last backward
+        self._rc_fwd: Dict[str, str] = {}         # tower tag -> the mode its last forward ran in (its backward follows that)
+        self._rc_held: Dict[str, int] = {}        # slot tag -> the block whose tensors it holds
         self.dev = store.device
         if self.dev.type == "cuda":
             K.warm_scratch(self.dev)
@@ -381,6 +392,29 @@ class Engine:
         if t is None:
             t = self.buf[("ones", n)] = torch.ones(n, dtype=torch.float32, device=self.dev)
         return t
+
+    def set_recompute(self, mode):
+        """switch the recomputation mode between steps (validated as at construction); buffers only grow, nothing is freed"""
+        self.recompute = self.arch["recompute"] = check_recompute(self.arch, mode)
+
+    def workspace_bytes(self) -> int:
+        """the bytes behind every named workspace: the grow-only allocations of _b, the fresh tensors in buf, and the encoders'"""
+        seen = {}
+        for t in list(self._back.values()) + list(self.buf.values()) + list(self._inf.values()):
+            st = t.untyped_storage()
+            seen[st.data_ptr()] = st.nbytes()
+        return sum(seen.values())
+
+    @staticmethod
+    def _rc_tags(tag, l, mode, parity=False):
+        """-> (tag of the tensors block l of tower `tag` saves, tag of its MLP pair h / a) under recomputation mode `mode`: the
+        block's own tag + "<l>", or the shared slot tag + ".rc" (parity: one slot per layer parity, for the side stream's weight
+        gradients of block l + 1, which still read their operands while block l is evaluated again)"""
+        own = f"{tag}{l}"
+        if mode == "none":
+            return own, own
+        slot = f"{tag}.rc{l % 2}" if parity else f"{tag}.rc"
+        return (slot, slot) if mode == "block" else (own, slot)
 
     def _row_starts(self, role, count, stride):
         """encoder workspace `role`: int32 [count], the first row of every sequence of `stride` rows (its CLS / [CLS] token)"""
@@ -666,12 +700,16 @@ class Engine:
     # (attn_fwd: a query-restricted kernel writing the used rows of `att`), the output projection, the residual, LayerNorm 2 and the
     # MLP are computed for the R used rows; backward: dQ for those rows, dK / dV -- and through them the gradient of every input
     # row -- dense.
-    def _block_fwd(self, pre, nm, x_in, x_out, tag, heads, act, eps, attn_fwd, rows=None, drop_path=None):
+    def _block_fwd(self, pre, nm, x_in, x_out, tag, heads, act, eps, attn_fwd, rows=None, drop_path=None, mtag=None, redo=False):
         """attn_fwd(qkv, att, lse): the attention call.  tag None: forward-only (lse None, no act'(x) side output; x_out may be x_in).
         -> x_out, or with `rows` the block output at those rows, packed [R, Wd] fp32 (x_out is not used).
         drop_path (dense training blocks only): (scale_attn [B], scale_mlp [B], rows per sample) -- stochastic depth: each branch's
-        projection, bias included, goes to an fp32 scratch and tvts_drop_path_rows forms residual + scale[sample] * branch."""
+        projection, bias included, goes to an fp32 scratch and tvts_drop_path_rows forms residual + scale[sample] * branch.
+        mtag: the tag of the MLP pair h / a where it is not the block's own (_rc_tags); redo: the backward's second evaluation --
+        stops behind fc1, the block's output is the kept stream."""
         assert drop_path is None or (rows is None and tag is not None)
+        mtag = mtag or tag
+        assert (mtag == tag and not redo) or (rows is None and tag is not None)
         w, f32 = self._w, torch.float32
         M, Wd = x_in.shape
         R = M if rows is None else rows.numel()
@@ -696,9 +734,11 @@ class Engine:
             K.drop_path_rows(y, drop_path[0], drop_path[2], residual=res, out=mid)
         ln2 = w(tag, ".ln2", "ln" if rows is None else "lnc", (R, Wd))
         self._ln(mid, pre + nm["ln2"], eps, ln2, tag and tag + ".ln2")
-        h = self._b(tag + ".h", (R, 4 * Wd)) if tag else None
-        a = w(tag, ".a", "h", (R, 4 * Wd))
+        h = self._b(mtag + ".h", (R, 4 * Wd)) if tag else None
+        a = w(mtag, ".a", "h", (R, 4 * Wd))
         self._lin(ln2, pre + nm["fc_w"], pre + nm["fc_b"], a, R, act=act, preact=h)
+        if redo:
+            return None
         if drop_path is None:
             self._lin(a, pre + nm["pj_w"], pre + nm["pj_b"], x_out, R, residual=mid)
         else:
@@ -706,20 +746,20 @@ class Engine:
             K.drop_path_rows(y, drop_path[1], drop_path[2], residual=mid, out=x_out)
         return x_out
 
-    def _block_bwd(self, pre, nm, x_in, dx, dxb, dx_in, dxb_in, tag, scr, heads, act, attn_bwd, rows=None, drop_path=None):
+    def _block_bwd(self, pre, nm, x_in, dx, dxb, dx_in, dxb_in, tag, scr, heads, act, attn_bwd, rows=None, drop_path=None, mtag=None):
         """dx / dxb: fp32 / bf16 gradient of the block output (with `rows`: at those R rows, packed); attn_bwd(qkv, datt, att, lse,
         delta, dqkv): the attention call.  Writes the gradient of every input row to dx_in / dxb_in.
         drop_path: as _block_fwd -- the gradient entering a branch is scale[sample] * (gradient of the sum), formed from the fp32
         gradient as the bf16 operand of _lin_bwd; the residual path keeps the unscaled gradient."""
         assert drop_path is None or rows is None
-        B_ = self.buf
+        B_, mtag = self.buf, mtag or tag
         M, Wd = x_in.shape
         R, r = (M, "") if rows is None else (rows.numel(), "_r")
         dh, dln_r = self._b(scr + ".dh" + r, (R, 4 * Wd)), self._b(scr + ".dln" + r, (R, Wd))
         if drop_path is not None:
             dxb = self._b(scr + ".dpb", (R, Wd))
             K.drop_path_rows(dx, drop_path[1], drop_path[2], out_bf16=dxb)
-        self._lin_bwd(dxb, B_[tag + ".a"], pre + nm["pj_w"], pre + nm["pj_b"], dh, R, gate_h=B_[tag + ".h"], gate_act=act)
+        self._lin_bwd(dxb, B_[mtag + ".a"], pre + nm["pj_w"], pre + nm["pj_b"], dh, R, gate_h=B_[mtag + ".h"], gate_act=act)
         self._lin_bwd(dh, B_[tag + ".ln2"], pre + nm["fc_w"], pre + nm["fc_b"], dln_r, R)
         dmid, dmidb = self._f(scr + ".dmid" + r, (R, Wd)), self._b(scr + ".dmidb" + r, (R, Wd))
         self._ln_bwd(dln_r, B_[tag + ".mid"], pre + nm["ln2"], tag + ".ln2", dmid, dx_bf16=dmidb, res1=dx)
@@ -742,17 +782,25 @@ class Engine:
         if rows is not None:
             K.rows_move("scatter_add", rows, full_f32=dx_in, full_bf16=dxb_in, packed_f32=dmid)
 
-    def _blocks_fwd(self, pre, nm, x, tag, depth, heads, act, eps, attn, rows=None, attn_rows=None, drop_path=None):
+    def _blocks_fwd(self, pre, nm, x, tag, depth, heads, act, eps, attn, rows=None, attn_rows=None, drop_path=None, recompute="none"):
         """x through the blocks pre + "0." ... of a pre-LN tower -> the stream behind the last block -- or, with `rows`, that
         block's output at those rows (packed; attn_rows: its attention call), for the caller's final LayerNorm and head.
         tag: block l keeps its tensors as tag + "l" + name and writes the stream tag + ".x<l + 1>"; None: forward-only, in place.
         drop_path: (scale table fp32 [2 * depth, B], rows per sample) of a stochastic-depth step, row 2 l for the attention branch of
-        block l and 2 l + 1 for its MLP branch (tvts_drop_path_table); None: no stochastic depth."""
+        block l and 2 l + 1 for its MLP branch (tvts_drop_path_table); None: no stochastic depth.
+        recompute (per CALL: the video towers pass the engine's mode, the text towers and the sort head nothing): "mlp" / "block" keep
+        the blocks' tensors in the shared slot of _rc_tags; _blocks_bwd evaluates them again."""
+        assert recompute == "none" or (tag is not None and rows is None)
+        if tag is not None:
+            self._rc_fwd[tag] = recompute
         for l in range(depth):
             used = rows if l == depth - 1 else None
             xo = None if used is not None else self._f(f"{tag}.x{l + 1}", x.shape) if tag else x
-            x = self._block_fwd(f"{pre}{l}.", nm, x, xo, tag and f"{tag}{l}", heads, act, eps, attn if used is None else attn_rows,
-                                rows=used, drop_path=self._dp_of(drop_path, l))
+            tg, tm = self._rc_tags(tag, l, recompute) if tag else (None, None)
+            x = self._block_fwd(f"{pre}{l}.", nm, x, xo, tg, heads, act, eps, attn if used is None else attn_rows,
+                                rows=used, drop_path=self._dp_of(drop_path, l), mtag=tm)
+            if recompute != "none":
+                self._rc_held[tm] = l
         return x
 
     @staticmethod
@@ -780,14 +828,29 @@ class Engine:
         return dx, dxb
 
     def _blocks_bwd(self, pre, nm, tag, depth, dx, dxb, heads, act, attn_bwd, rows=None, attn_bwd_rows=None, after=None,
-                    drop_path=None):
+                    drop_path=None, redo=None):
         """The backward of _blocks_fwd (drop_path: the forward's).  dx / dxb: fp32 / bf16 gradient of what it returned -> the fp32 gradient of its input x.
-        The blocks' input gradients alternate between tag + ".dxA|B" / ".dxbA|B" (_ab); after(l): called behind block l."""
+        The blocks' input gradients alternate between tag + ".dxA|B" / ".dxbA|B" (_ab); after(l): called behind block l.
+        redo: (eps, the forward's attention call) of a tower that may have run under a recomputation mode (_blocks_fwd): a block whose
+        tensors the shared slot no longer holds is evaluated again from its kept input ("block": up to fc1; "mlp": fc1 alone)
+        before its backward -- every launch of this stream that read the slot is queued in front of it."""
+        mode = self._rc_fwd.get(tag, "none")
+        assert mode == "none" or (redo is not None and rows is None)
         for l in reversed(range(depth)):
             x_in, nx, used = self.buf[f"{tag}.x{l}"], self._ab(depth, l), rows if l == depth - 1 else None
+            tg, tm = self._rc_tags(tag, l, mode)
+            if mode != "none" and self._rc_held.get(tm) != l:
+                if mode == "block":
+                    self._block_fwd(f"{pre}{l}.", nm, x_in, None, tg, heads, act, redo[0], redo[1], drop_path=self._dp_of(drop_path, l),
+                                    mtag=tm, redo=True)
+                else:
+                    self._lin(self.buf[tg + ".ln2"], f"{pre}{l}." + nm["fc_w"], f"{pre}{l}." + nm["fc_b"], self._b(tm + ".a", (x_in.shape[0], 4 * x_in.shape[1])),
+                              x_in.shape[0], act=act, preact=self._b(tm + ".h", (x_in.shape[0], 4 * x_in.shape[1])))
+                self._rc_held[tm] = l
+                self.recompute_count += 1
             dxi, dxbi = self._f(f"{tag}.dx{nx}", x_in.shape), self._b(f"{tag}.dxb{nx}", x_in.shape)
-            self._block_bwd(f"{pre}{l}.", nm, x_in, dx, dxb, dxi, dxbi, f"{tag}{l}", tag + ".s", heads, act,
-                            attn_bwd if used is None else attn_bwd_rows, rows=used, drop_path=self._dp_of(drop_path, l))
+            self._block_bwd(f"{pre}{l}.", nm, x_in, dx, dxb, dxi, dxbi, tg, tag + ".s", heads, act,
+                            attn_bwd if used is None else attn_bwd_rows, rows=used, drop_path=self._dp_of(drop_path, l), mtag=tm)
             dx, dxb = dxi, dxbi
             if after is not None:
                 after(l)
@@ -965,10 +1028,13 @@ class Engine:
         self._lin(ln1, pre + "attn.qkv.weight", pre + "attn.qkv.bias", qkv_s, M, a8=a8, fwd_only=fo)
         return qkv_s
 
-    def _vit_block(self, l, x, xc, tag, B, T, n):
-        """space-time block l on every row: (x, xc) -> the next (x, xc); forward-only (tag None) in place"""
+    def _vit_block(self, l, x, xc, tag, B, T, n, recompute="none", redo=False):
+        """space-time block l on every row: (x, xc) -> the next (x, xc); forward-only (tag None) in place.
+        recompute: the training step's mode -- the block's tensors go where _rc_tags says; redo: the backward's second evaluation,
+        which stops behind fc1 (the block's output is the kept stream)."""
         a, w = self.arch, self._w
-        pre, tg = f"video_model.transformer.resblocks.{l}.", tag and f"{tag}{l}"
+        pre = f"video_model.transformer.resblocks.{l}."
+        tg, tm = self._rc_tags(tag, l, recompute, parity=bool(self.wgrad_stream)) if tag else (None, None)
         W, M, S, fo = a["width"], x.shape[0], 1 + T * n, tag is None
         qkv_s = self._vit_block_head(pre, x, xc, tg, B, T, n)
         att_s, lse_s = w(tg, ".att_s", "att", (M, W)), (self._f(tg + ".lse_s", (M, a["heads"])) if tg else None)
@@ -981,9 +1047,13 @@ class Engine:
             self._cls_lin(att_s, S, pre + "attn.proj.weight", pre + "attn.proj.bias", xc, s_res_c, fwd_only=fo)
         ln2 = w(tg, ".ln2", "ln", (M, W))
         a8 = self._ln(s_res, pre + "ln_2", 1e-5, ln2, tg and tg + ".ln2", fp8_for=pre + "mlp.c_fc.weight", cls_x=s_res_c)
-        h, act = (self._b(tg + ".h", (M, 4 * W)) if tg else None), w(tg, ".a", "h", (M, 4 * W))
+        h, act = (self._b(tm + ".h", (M, 4 * W)) if tg else None), w(tm, ".a", "h", (M, 4 * W))
         self._lin(ln2, pre + "mlp.c_fc.weight", pre + "mlp.c_fc.bias", act, M, act=a["act"], preact=h, a8=a8,
                   q8_for=pre + "mlp.c_proj.weight", fwd_only=fo)
+        if recompute != "none":
+            self._rc_held[tm] = l
+        if redo:
+            return None, None
         xo = self._b(f"{tag}.x{l + 1}", (M, W), x.dtype) if tag else x  # (forward-only: x is dead)
         self._lin(act, pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", xo, M, residual=s_res, fwd_only=fo)
         if xc is not None:
@@ -1002,8 +1072,9 @@ class Engine:
         if vid_rows is None:
             vid_rows = (torch.arange(B, device=self.dev) * S).to(torch.int32)
         x, xc = self._vit_embed(video, keep_dev, B, T, vid_rows, self.ctx.get("crop"), self.ctx.get("resize"), "vit")
+        rc = self._rc_fwd["vit"] = self.recompute
         for l in range(a["layers"]):
-            x, xc = self._vit_block(l, x, xc, "vit", B, T, n)
+            x, xc = self._vit_block(l, x, xc, "vit", B, T, n, recompute=rc)
         out = self._f("vit.out", (M, E))
         if not self.pooled_tail:  # B models: ln_post on every token, all S projected rows feed the sort head
             lnp = self._b("vit.lnpost", (M, W))
@@ -1085,7 +1156,8 @@ class Engine:
         of the buffers those weight gradients read late; join(): called once all six are issued, before the block's input
         gradient is written."""
         a, B_ = self.arch, self.buf
-        pre, tg = f"video_model.transformer.resblocks.{l}.", f"vit{l}"
+        pre = f"video_model.transformer.resblocks.{l}."
+        tg, tm = self._rc_tags("vit", l, self._rc_fwd.get("vit", "none"), parity=bool(self.wgrad_stream))
         M, W = dxb.shape
         # the residual-stream gradient in bf16 (self.bf16_grad_stream, see __init__): measured alone +1.4 % (the three LayerNorm
         # backwards of a block move 3.2 instead of 4.6 GB) at 2.4x the error of the embedding-side gradients, which sit behind
@@ -1100,8 +1172,8 @@ class Engine:
         dqkv = self._b("vit.s.dqkv" + par, (M, 3 * W))
         dqkv_t = self._b("vit.s.dqkv_t" + par, (M, 3 * W)) if (wg["side"] or wg["defer"] is not None) else dqkv
         # (e4m3 input gradients: the LayerNorm backward that produces an output gradient also writes its e4m3 copy, d*8)
-        self._lin_bwd(dxb, B_[tg + ".a"], pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", dh, M, dy8=dxb8,
-                      q8_for=pre + "mlp.c_fc.weight", gate_h=B_[tg + ".h"], gate_act=a["act"], **wg)
+        self._lin_bwd(dxb, B_[tm + ".a"], pre + "mlp.c_proj.weight", pre + "mlp.c_proj.bias", dh, M, dy8=dxb8,
+                      q8_for=pre + "mlp.c_fc.weight", gate_h=B_[tm + ".h"], gate_act=a["act"], **wg)
         self._lin_bwd(dh, B_[tg + ".ln2"], pre + "mlp.c_fc.weight", pre + "mlp.c_fc.bias", dln, M, **wg)
         dsrc = self._f("vit.s.dsrc", (B, W)) if cls else None
         dsrb8 = self._ln_bwd(dln, B_[tg + ".s_res"], pre + "ln_2", tg + ".ln2", dsr, dx_bf16=dsrb, res1=dxb if lowp else dx,
@@ -1132,6 +1204,29 @@ class Engine:
                             cls_x=B_[f"vit.xc{l}"] if cls else None, cls_res1=dsrc, cls_dx=dxci)
         return dxi, dxbi, dxci, dxb8
 
+    def _vit_redo(self, l, B, T, n):
+        """Under a recomputation mode, in front of block l's backward: evaluate the block again unless its slot still holds it (the
+        forward's last writer).  "block": its training forward from the kept x<l> / xc<l>, up to fc1; "mlp": fc1 from the kept ln2.
+        The slot's earlier readers are queued in front of this on the current stream -- the grouped weight gradients of block l + 1
+        are launched inside that block's backward (join), and the side stream's readers of this parity's slot (block l + 2) were
+        joined there as well (video_backward)."""
+        mode = self._rc_fwd.get("vit", "none")
+        if mode == "none":
+            return
+        tg, tm = self._rc_tags("vit", l, mode, parity=bool(self.wgrad_stream))
+        if self._rc_held.get(tm) == l:
+            return
+        B_, a = self.buf, self.arch
+        if mode == "block":
+            self._vit_block(l, B_[f"vit.x{l}"], B_[f"vit.xc{l}"] if self.cls32 else None, "vit", B, T, n, recompute=mode, redo=True)
+        else:
+            pre, x = f"video_model.transformer.resblocks.{l}.", B_[f"vit.x{l}"]
+            M, W = x.shape
+            self._lin(B_[tg + ".ln2"], pre + "mlp.c_fc.weight", pre + "mlp.c_fc.bias", self._b(tm + ".a", (M, 4 * W)), M, act=a["act"],
+                      preact=self._b(tm + ".h", (M, 4 * W)))
+            self._rc_held[tm] = l
+        self.recompute_count += 1
+
     def _vit_embed_bwd(self, dx, keep_dev, B, T):
         """The backward of _vit_embed: ln_pre -> token assembly -> conv weight gradient; the embedding stage's gradients are final."""
         B_ = self.buf
@@ -1159,6 +1254,7 @@ class Engine:
         when there is no sorting loss); d_pooled: fp32 [B, E] grad of the pooled embedding (H/14 only)."""
         n = keep_dev.shape[1]
         M = B * (1 + T * n)
+        self.recompute_count = 0
         dx, dxb, dxc, dxb8 = self._vit_tail_bwd(dout_b, d_pooled, B, M)
         # the weight gradients of the blocks on the side stream: the output gradients they read (dh, dsrb, dqkv of the space and of
         # the time branch, dtrb, and the block's own dxb) then live in buffers of the layer's parity, and the chain joins the side
@@ -1184,6 +1280,7 @@ class Engine:
                         cur.wait_event(side_done.pop(l + 1))
                         self._ready(f"video_model.transformer.resblocks.{l + 1}.")
 
+            self._vit_redo(l, B, T, n)
             dx, dxb, dxc, dxb8 = self._vit_block_bwd(l, dx, dxb, dxc, dxb8, B, T, n, str(l % 2) if side else "",
                                                      dict(side=side, defer=defer), join)
             if not side:

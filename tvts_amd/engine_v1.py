@@ -275,7 +275,8 @@ class EngineV1(Engine):
         S = 1 + tubes * keep.shape[2]
         tok = self._vit_embed_v1(video, keep, B, tubes, "vit")
         x = self._blocks_fwd("video_model.blocks.", _VIT_NAMES, tok, "vit", a["layers"], hv, "gelu", 1e-6,
-                             lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hv, S=S, causal=False, head_dim=W // hv))
+                             lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hv, S=S, causal=False, head_dim=W // hv),
+                             recompute=self.recompute)
         out = self._f("vit.out", (B * S, W))
         self._ln(x, "video_model.norm", 1e-6, out, "vit.norm")
         cls = self._f("vit.cls", (B, W))
@@ -294,9 +295,12 @@ class EngineV1(Engine):
         dx, dxb = self._f("vit.dxA", (M, W)), self._b("vit.dxbA", (M, W))
         self._ln_bwd(dout_b, B_[f"vit.x{a['layers']}"], "video_model.norm", "vit.norm", dx, dx_bf16=dxb)
         hv = a["heads"]
+        self.recompute_count = 0
         dx = self._blocks_bwd("video_model.blocks.", _VIT_NAMES, "vit", a["layers"], dx, dxb, hv, "gelu",
                               lambda qkv, *t: K.attn_bwd("full", qkv, *t, B=B, heads=hv, S=S, causal=False, head_dim=W // hv),
-                              after=lambda l: self._ready(f"video_model.blocks.{l}."))
+                              after=lambda l: self._ready(f"video_model.blocks.{l}."),
+                              redo=(1e-6, lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hv, S=S, causal=False,
+                                                                           head_dim=W // hv)))
         dpatch = self._b("vit.dpatch", (Mp, W))
         K.vit_assemble_bwd(dx, keep, dpatch, P.g("video_model.cls_token").view(W), P.g("video_model.pos_embed").view(-1, W),
                            P.g("video_model.temporal_embed").view(-1, W), B=B, T=tubes, n=n)
@@ -355,7 +359,7 @@ class EngineV1(Engine):
         dp = None if table is None else (table, S)
         x = self._blocks_fwd("video_model.blocks.", _VIT_NAMES, tok, "ft", depth, hv, "gelu", 1e-6,
                              lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hv, S=S, causal=False, head_dim=W // hv),
-                             drop_path=dp)
+                             drop_path=dp, recompute=self.recompute)
         feat = self._f("ft.feat", (B, W))
         self._ln(x, "video_model.norm", 1e-6, feat, "ft.norm", rows=cls_rows)
         logits = self._f("ft.logits", (B, C))
@@ -370,6 +374,7 @@ class EngineV1(Engine):
             raise ValueError("trainable: 'all' or 'head'")
         a, c, P, B_ = self.arch, self.ft_ctx, self.P, self.buf
         B, S, tubes, W, hv, depth = c["B"], c["S"], c["tubes"], a["width"], a["heads"], a["layers"]
+        self.recompute_count = 0  # (trainable "head": the backward never reaches the blocks, nothing is evaluated again)
         dfeat = self._f("ft.dfeat", (B, W))
         self._head_lin_bwd(dlogits, B_["ft.feat"], "head.weight", "head.bias", dfeat, B)
         self._ready("head.")
@@ -378,7 +383,9 @@ class EngineV1(Engine):
         dx, dxb = self._head_ln_bwd(dfeat, "video_model.norm", "ft", "ft.norm", depth, c["cls_rows"], False)
         dx = self._blocks_bwd("video_model.blocks.", _VIT_NAMES, "ft", depth, dx, dxb, hv, "gelu",
                               lambda qkv, *t: K.attn_bwd("full", qkv, *t, B=B, heads=hv, S=S, causal=False, head_dim=W // hv),
-                              after=lambda l: self._ready(f"video_model.blocks.{l}."), drop_path=c["drop_path"])
+                              after=lambda l: self._ready(f"video_model.blocks.{l}."), drop_path=c["drop_path"],
+                              redo=(1e-6, lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hv, S=S, causal=False,
+                                                                           head_dim=W // hv)))
         n = c["keep"].shape[2]
         Mp = B * tubes * n
         dpatch = self._b("ft.dpatch", (Mp, W))

@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from .. import hip as K
-from ..arch import ARCHS, param_shapes
+from ..arch import ARCHS, param_shapes, recompute_from_args, recompute_mode
 from ..engine import Engine, LossHead, ParamStore
 
 
@@ -112,7 +112,7 @@ class TVTSv2Base(nn.Module):
     ENGINE = Engine
     INIT = staticmethod(reference_init_)
 
-    def __init__(self, args, load_checkpoint=None, arch=None, init_seed=0, pretrained=None):
+    def __init__(self, args, load_checkpoint=None, arch=None, init_seed=0, pretrained=None, grad_checkpointing=None):
         """``args`` / ``load_checkpoint``: the reference's constructor (model_dist_TVTSv2_ViT_B_16.py:11-14).
 
         ``pretrained`` -- what an empty ``load_checkpoint`` initialises from (ignored when a checkpoint is given, whose strict load
@@ -121,7 +121,12 @@ class TVTSv2Base(nn.Module):
                  of the kept packages (model/clip_init.py), an error if it cannot be loaded -- never a silent random start;
                  with an explicit ``arch`` dict (tests, benches, smoke) it means False;
           False  the constructor's random initialisation only (reference_init_);
-          a mapping / a path: a CLIP-layout state dict (full model: ``visual.*``, ``transformer.*``, ``token_embedding.weight``, ...)."""
+          a mapping / a path: a CLIP-layout state dict (full model: ``visual.*``, ``transformer.*``, ``token_embedding.weight``, ...).
+
+        ``grad_checkpointing`` -- activation recomputation of the video tower (set_grad_checkpointing): a bool or a mode string.  A
+        keyword here is an entry of the config's ``arch.args`` (parse_config_dist_multi.py:73-98 passes that dictionary as keywords),
+        so a trainer config switches it on without code; None reads ``args.grad_checkpointing`` instead; an explicit
+        ``arch["recompute"]`` wins over both."""
         super().__init__()
         self.args = args
         if pretrained is None and (arch is not None or self.ARCH_NAME is None or ARCHS[self.ARCH_NAME].get("family") == "v1"):
@@ -129,6 +134,8 @@ class TVTSv2Base(nn.Module):
         if isinstance(pretrained, str) and pretrained == "reference":  # (a subclass that builds its own arch dict asks for the reference's source)
             pretrained = None
         self.arch = dict(arch if arch is not None else ARCHS[self.ARCH_NAME])
+        self.arch["recompute"] = recompute_from_args(args if grad_checkpointing is None else {"grad_checkpointing": grad_checkpointing},
+                                                     self.arch)
         self.num_clips = 4
         self.n_trans = self.arch["n_trans"]
         dev = _require_gpu(getattr(args, "local_rank", 0))
@@ -224,6 +231,13 @@ class TVTSv2Base(nn.Module):
 
     def set_device(self, device):
         self.device = device
+
+    def set_grad_checkpointing(self, enable=True):
+        """The reference's switch (video_encoder_ViT_H_14.py:410) for the video tower of this model: True -- "block", the backward
+        evaluates every space-time block again from its kept input instead of keeping what the block saves; False -- "none"; a mode
+        string ("none" / "mlp" / "block") is taken as is.  Same losses, gradients and updates, bit for bit, in every mode.  May be
+        called between steps: workspaces only grow, nothing is freed.  Holds for the autograd path and for StepRunner alike."""
+        self.engine.set_recompute(recompute_mode(enable))
 
     def __str__(self):
         n = sum(int(np.prod(p.size())) for p in self.parameters() if p.requires_grad)

@@ -73,7 +73,7 @@ class TVTS(TVTSv2Base):
     INIT = staticmethod(reference_init_v1_)
 
     def __init__(self, args, video_params=None, text_params=None, projection_dim=256, load_checkpoint=None,
-                 projection="minimal", arch=None, init_seed=0):
+                 projection="minimal", arch=None, init_seed=0, grad_checkpointing=None):
         video_params = video_params or {}
         text_params = text_params or {"model": "distilbert-base-uncased", "pretrained": True}
         if arch is None:
@@ -85,7 +85,7 @@ class TVTS(TVTSv2Base):
                 raise NotImplementedError
             arch = dict(ARCH_V1, num_frames=video_params.get("num_frames", 16), embed=projection_dim)
         self.video_params, self.text_params = video_params, text_params
-        super().__init__(args, load_checkpoint=load_checkpoint, arch=arch, init_seed=init_seed)
+        super().__init__(args, load_checkpoint=load_checkpoint, arch=arch, init_seed=init_seed, grad_checkpointing=grad_checkpointing)
 
     def forward(self, data, return_embeds=True):
         self.engine.training = self.training  # dropout of the text tower in training mode only

@@ -214,7 +214,8 @@ class GraphReplay:
             self.eager += 1
             return r.run(pb, labels, device_step=True)
         sig = (_signature(pb), None if labels is None else tuple(labels.shape), bool(m.training),
-               hash(tuple(r.eng.requires_grad.values())) if hasattr(r.eng, "requires_grad") else None)
+               hash(tuple(r.eng.requires_grad.values())) if hasattr(r.eng, "requires_grad") else None,
+               getattr(r.eng, "recompute", "none"))  # (a graph holds the launches of the mode it was captured in)
         ent = self.cache.get(sig)
         if ent is None:
             if len(self.cache) >= self.MAX_SIGNATURES:
