@@ -12,8 +12,8 @@ import kernel_bounds as KB
 from gemm_cases import BF16, F32, I32, U8, Mat
 
 # ------------------------------------------------------------------------------------------------ the kernels' constants
-COLS4 = 64 * 4          # columns one trip of the 4-column kernels covers (ln_fwd_kernel, ln_bwd_kernel: IT = ceil(W / 256) trips)
-COLS8 = 64 * 8          # ... of the 8-column bf16-row forward (ln_fwd8_kernel: NP = ceil(W / 512))
+COLS4 = 64 * 4          # columns one trip of the 4-column kernels covers (ln_fwd_kernel<LnCols4<TX>, ...>, ln_bwd_kernel: G = IT = ceil(W / 256) trips)
+COLS8 = 64 * 8          # ... of the 8-column bf16-row forward (ln_fwd_kernel<LnCols8, ...>: G = ceil(W / 512))
 MAX_W = COLS4 * 5       # LN_MAX_IT
 WAVES = 4               # rows a block holds at a time
 FWD_BLOCKS = 2048       # cap of the forward grids: past 8192 rows a wave walks to a second row
@@ -45,7 +45,7 @@ W_REDUCE = [4, REDUCE_COLS + 4, 4 * REDUCE_COLS + 4]  # c < W cuts the first, th
 
 
 def ln8_ok(W, lda, ldb):
-    """the host's choice of the 8-column bf16-row forward (norm.hip)"""
+    """the host's choice of the 8-column bf16-row forward (ln_cols8 of norm.hip)"""
     return W % 8 == 0 and W <= 1536 and lda % 8 == 0 and ldb % 8 == 0
 
 
@@ -177,22 +177,22 @@ def _f(name, kernel, x, y, widths, q8=None, cls=False, has_y=True):
 
 
 FWD_FORMS = [
-    _f("f32_bf16", "ln_fwd_kernel<bf16, IT, float>", F32, BF16, "W_4COL"),
-    _f("f32_f32", "ln_fwd_kernel<float, IT, float>", F32, F32, "W_4COL"),
-    _f("bf16_8col", "ln_fwd8_kernel<NP, false>", BF16, BF16, "W_8COL"),
-    _f("bf16_4col", "ln_fwd_kernel<bf16, IT, bf16>", BF16, BF16, "W_BF16_4COL"),
-    _f("f32_q8rows", "ln_fwd_kernel<bf16, IT, float, Q8>", F32, BF16, "W_4COL", q8="rows"),
-    _f("f32_q8tensor", "ln_fwd_kernel<bf16, IT, float, Q8>", F32, BF16, "W_4COL", q8="tensor"),
-    _f("bf16_8col_q8rows", "ln_fwd8_kernel<NP, false, Q8>", BF16, BF16, "W_8COL", q8="rows"),
-    _f("bf16_8col_q8tensor", "ln_fwd8_kernel<NP, false, Q8>", BF16, BF16, "W_8COL", q8="tensor"),
-    _f("bf16_8col_q8only_rows", "ln_fwd8_kernel<NP, false, Q8>, y = NULL", BF16, BF16, "W_8COL", q8="rows", has_y=False),
-    _f("bf16_8col_q8only_tensor", "ln_fwd8_kernel<NP, false, Q8>, y = NULL", BF16, BF16, "W_8COL", q8="tensor", has_y=False),
-    _f("bf16_4col_q8rows", "ln_fwd_kernel<bf16, IT, bf16, Q8>", BF16, BF16, "W_BF16_4COL", q8="rows"),
-    _f("bf16_4col_q8tensor", "ln_fwd_kernel<bf16, IT, bf16, Q8>", BF16, BF16, "W_BF16_4COL", q8="tensor"),
-    _f("cls_8col", "ln_fwd8_kernel<NP, true>", BF16, BF16, "W_8COL", cls=True),
-    _f("cls_4col", "ln_fwd_kernel<bf16, IT, bf16, false, CLS>", BF16, BF16, "W_BF16_4COL", cls=True),
-    _f("cls_8col_q8rows", "ln_fwd8_kernel<NP, true, Q8>", BF16, BF16, "W_8COL", q8="rows", cls=True),
-    _f("cls_4col_q8rows", "ln_fwd_kernel<bf16, IT, bf16, Q8, CLS>", BF16, BF16, "W_BF16_4COL", q8="rows", cls=True),
+    _f("f32_bf16", "ln_fwd_kernel<LnCols4<float>, bf16, G>", F32, BF16, "W_4COL"),
+    _f("f32_f32", "ln_fwd_kernel<LnCols4<float>, float, G>", F32, F32, "W_4COL"),
+    _f("bf16_8col", "ln_fwd_kernel<LnCols8, bf16, G>", BF16, BF16, "W_8COL"),
+    _f("bf16_4col", "ln_fwd_kernel<LnCols4<bf16>, bf16, G>", BF16, BF16, "W_BF16_4COL"),
+    _f("f32_q8rows", "ln_fwd_kernel<LnCols4<float>, bf16, G, Q8>", F32, BF16, "W_4COL", q8="rows"),
+    _f("f32_q8tensor", "ln_fwd_kernel<LnCols4<float>, bf16, G, Q8>", F32, BF16, "W_4COL", q8="tensor"),
+    _f("bf16_8col_q8rows", "ln_fwd_kernel<LnCols8, bf16, G, Q8>", BF16, BF16, "W_8COL", q8="rows"),
+    _f("bf16_8col_q8tensor", "ln_fwd_kernel<LnCols8, bf16, G, Q8>", BF16, BF16, "W_8COL", q8="tensor"),
+    _f("bf16_8col_q8only_rows", "ln_fwd_kernel<LnCols8, bf16, G, Q8>, y = NULL", BF16, BF16, "W_8COL", q8="rows", has_y=False),
+    _f("bf16_8col_q8only_tensor", "ln_fwd_kernel<LnCols8, bf16, G, Q8>, y = NULL", BF16, BF16, "W_8COL", q8="tensor", has_y=False),
+    _f("bf16_4col_q8rows", "ln_fwd_kernel<LnCols4<bf16>, bf16, G, Q8>", BF16, BF16, "W_BF16_4COL", q8="rows"),
+    _f("bf16_4col_q8tensor", "ln_fwd_kernel<LnCols4<bf16>, bf16, G, Q8>", BF16, BF16, "W_BF16_4COL", q8="tensor"),
+    _f("cls_8col", "ln_fwd_kernel<LnCols8, bf16, G, false, CLS>", BF16, BF16, "W_8COL", cls=True),
+    _f("cls_4col", "ln_fwd_kernel<LnCols4<bf16>, bf16, G, false, CLS>", BF16, BF16, "W_BF16_4COL", cls=True),
+    _f("cls_8col_q8rows", "ln_fwd_kernel<LnCols8, bf16, G, Q8, CLS>", BF16, BF16, "W_8COL", q8="rows", cls=True),
+    _f("cls_4col_q8rows", "ln_fwd_kernel<LnCols4<bf16>, bf16, G, Q8, CLS>", BF16, BF16, "W_BF16_4COL", q8="rows", cls=True),
 ]
 FWD_BY_NAME = {f["name"]: f for f in FWD_FORMS}
 
@@ -273,7 +273,7 @@ def fwd_case(K, dev, form, M, W, ldx=0, ldy=0, *, seed=0, period=0, gathered=Fal
         kw["M"] = M
     # the kernel the case is written for
     expect8 = form["x"] == BF16 and ln8_ok(W, xin.stride(0), ldy)  # (y and q8 share the flavour ldy of their pitch)
-    assert expect8 == ("ln_fwd8" in form["kernel"]), (what, "reaches the 8-column kernel" if expect8 else "reaches the 4-column kernel")
+    assert expect8 == ("LnCols8" in form["kernel"]), (what, "reaches the 8-column kernel" if expect8 else "reaches the 4-column kernel")
     ybuf, y = out_mat(Mt, W, form["y"], dev, ldy)
     mean, rstd = out_vec(Mt, dev), out_vec(Mt, dev)
     q8 = form["q8"]

@@ -506,7 +506,7 @@ def test_layernorm_on_the_hybrid_stream(K, W, period, q8):
     m0, r0 = torch.empty_like(mean), torch.empty_like(rstd)
     K.layernorm_fwd(x_dev, g, b, 1e-5, y0, m0, r0)
     other = torch.ones(M, dtype=torch.bool); other[cls_rows] = False
-    if not q8 and W % 8 == 0:  # (bits only without the e4m3 copy; with it these widths run the 8-column Q8 kernel, ln_fwd8_kernel<NP, true, true>,
+    if not q8 and W % 8 == 0:  # (bits only without the e4m3 copy; with it these widths run the 8-column Q8 kernel, ln_fwd_kernel<LnCols8, bf16, G, true, true>,
         # not a 4-column one: held to the gate below here, per element in tests/test_layernorm_edges_gpu.py)
         assert torch.equal(y[other.to(DEV)].view(torch.int16), y0[other.to(DEV)].view(torch.int16))
     else:
@@ -1683,7 +1683,7 @@ def test_layernorm_at_the_step_sizes_within_the_bound(K, M, W, period):
     eps = 1e-5
     worst, cols = 0.0, {}
     mean, rstd = torch.full((M,), float("nan"), device=DEV), torch.full((M,), float("nan"), device=DEV)
-    for xin in (x, x.bfloat16()):  # the fp32 stream input, the bf16 input (ln_fwd8; bf16 rows have no fp32-output form)
+    for xin in (x, x.bfloat16()):  # the fp32 stream input, the bf16 input (the 8-column form; bf16 rows have no fp32-output form)
         for odt in ((torch.bfloat16, torch.float32) if xin.dtype == torch.float32 else (torch.bfloat16,)):
             buf, y = KB.guarded(M, W, odt, DEV)
             K.layernorm_fwd(xin, gamma, beta, eps, y, mean, rstd)
