@@ -730,6 +730,19 @@ int tvts_grad_sumsq(const float* g, const unsigned char* chunk_group, int nchunk
 int tvts_adamw_torch(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
                      const float* hyper_dev, int step, const int* step_dev, double beta1, double beta2, double eps,
                      float grad_scale, const float* norm_coef, hipStream_t stream);
+/* timm.utils.ModelEma as run_class_finetuning.py:345-352 builds it and engine_for_finetuning.py:84-85,97-98 updates it, per
+ * element: ema = fl(fl(ema * d32) + fl(o32 * p)) -- three roundings, no FMA -- with d32 = fp32(decay) and o32 = fp32(1.0 - decay),
+ * the difference formed in double on the host.  tvts_adamw_torch_ema: tvts_adamw_torch with the rule applied to the chunk's new p
+ * in the same pass (p, m, v and the shadow get the bits of tvts_adamw_torch); tvts_ema_update: the rule as a pass of its own.
+ * Both keep every bit of `ema` in a chunk that does not step (group >= 64, 255 = frozen).  Pointers 16-byte aligned (-22). */
+int tvts_adamw_torch_ema(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group,
+                         int nchunks, const float* hyper_dev, int step, const int* step_dev, double beta1, double beta2, double eps,
+                         float grad_scale, const float* norm_coef, float* ema, float d32, float o32, hipStream_t stream);
+int tvts_ema_update(float* ema, const float* p, const unsigned char* chunk_group, int nchunks, float d32, float o32,
+                    hipStream_t stream);
+/* a[i] <-> b[i] in place and shadow_bf16[i] = bf16(new a[i]) for i < n; n % 4 == 0, a and b disjoint and 16-byte aligned (-22).
+ * ModelEma.applied(): the masters and the average change places without a third buffer. */
+int tvts_swap_f32_shadow(float* a, float* b, void* shadow_bf16, long n, hipStream_t stream);
 
 /* ---- timing helper for bench.py: HIP events on the stream the kernels run on */
 int tvts_event_create(void** ev);

@@ -41,6 +41,12 @@ every step, as a loader's batch does (pinned buffers), so the upload is inside t
 --mixup device / torch may be combined with the --aug setting of the same name.  With --u8 (--aug off) or --aug device the
 gather's own time is measured too: device events around 50 launches of the step's gather on the step's shapes, in a pass of its own.
 
+--ema {off,fused,separate} (default off: the run and its output as before; without --mixup / --aug / --gpus): averaged weights,
+ModelEma(decay 0.9999).
+    fused     FinetuneStep(..., model_ema=ema): the average rides in the optimizer's launch (tvts_adamw_torch_ema, 38 B per element)
+    separate  the step without an average, then ema.update(model) behind every call, as the reference's loop does (one more
+              launch, tvts_ema_update, 12 B per element)
+
 --gpus N: the data-parallel step, one process per GPU -- `python -m torch.distributed.run --nproc-per-node N tools/bench_finetune.py
 --gpus N --batch 8 --num-sample 2` (N = 1 also runs as a plain process, without a process group).  Every rank runs the default
 recipe's step on its own --batch samples (--aug device, --mixup device, --randaug device; per-rank draws seeded seed + rank as the
@@ -69,6 +75,12 @@ def make(trainable, args, **step_kw):
     opt = FusedTorchAdamW(groups, m.store, lr=1e-3, model=m)
     for g in opt.param_groups:
         g["lr"] = 1e-4 * g["lr_scale"]
+    ema = getattr(args, "ema", "off")
+    if ema != "off":
+        from tvts_amd.downstream.finetune_v1 import ModelEma
+        args.model_ema = ModelEma(m, decay=0.9999)
+        if ema == "fused":
+            step_kw["model_ema"] = args.model_ema
     return m, FinetuneStep(m, opt, clip_grad=5.0, trainable=trainable, **step_kw), len(groups)
 
 
@@ -280,7 +292,12 @@ def run_aug(args, targets):
 def run(trainable, args, clip, targets):
     from tvts_amd import hip as K
     m, step, ngroups = make(trainable, args)
-    if args.mixup == "off":
+    if args.ema == "separate":
+        def one():
+            out = step.step(clip, targets)
+            args.model_ema.update(m)
+            return out
+    elif args.mixup == "off":
         one = lambda: step.step(clip, targets)
     else:
         import numpy as np
@@ -411,7 +428,10 @@ def main():
     ap.add_argument("--aug", choices=("off", "torch", "device"), default="off")
     ap.add_argument("--num-sample", type=int, default=1, help="views per decoded clip (--num_sample of the script)")
     ap.add_argument("--randaug", choices=("off", "device", "host"), default="off", help="RandAugment in front of the crop (--aug device)")
+    ap.add_argument("--ema", choices=("off", "fused", "separate"), default="off", help="ModelEma: in the optimizer's launch, or update() behind the step")
     args = ap.parse_args()
+    if args.ema != "off" and (args.gpus or args.mixup != "off" or args.aug != "off"):
+        raise SystemExit("--ema fused / separate: the plain step only (without --gpus, --mixup, --aug)")
     if args.gpus:
         if args.gpus < 1 or args.batch % 2 or args.num_sample < 1 or args.batch % args.num_sample:
             raise SystemExit("--gpus N >= 1, an even --batch (Mixup) and --num-sample a divisor of it")
@@ -445,6 +465,8 @@ def main():
     if args.u8:
         clip = torch.randint(0, 256, (args.batch, KW["num_frames"], KW["img_size"], KW["img_size"], 3), generator=g, dtype=torch.uint8).cuda()
         out["input"] = "uint8 frames"
+    if args.ema != "off":
+        out["ema"] = args.ema
     if args.mixup != "off":
         targets = torch.randint(0, args.classes, (args.batch,), generator=g)  # (host labels, as a loader hands them over)
         out["mixup"] = args.mixup

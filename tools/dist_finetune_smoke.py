@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Two data-parallel ranks of the v1 fine-tuning step and of the evaluation merges on ONE GPU (gloo moving device tensors, the
 pattern of tools/dist_smoke.py): FinetuneStep's gradient exchange, validation_one_epoch's meter merge and ViewMerger.gather.
-usage: python tools/dist_finetune_smoke.py [check ...]      (no argument: every check, in one pair of processes)
+usage: python tools/dist_finetune_smoke.py [--ema] [check ...]      (no argument: every check, in one pair of processes)
 checks: identical distinct replicas travel bf16 start mismatch seeds validation merge
+--ema: the check `ema` behind the named ones (alone when none is named; not part of "every check") -- a ModelEma made BEFORE the
+step object on ranks that start from different weights, both ranks' ModelEma.checksum() after _join and after two updating steps.
 The model is tests/v1_downstream_synth.TINY; the gates are the test suite's own (tests/kernel_bounds.py, check_grads of
 tests/test_v1_gpu.py), imported from tests/.  Prints DIST_FINETUNE_OK when every rank passed every check."""
 import math
@@ -14,6 +16,7 @@ import traceback
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHECKS = ("identical", "distinct", "replicas", "travel", "bf16", "start", "mismatch", "seeds", "validation", "merge")
+OPTIONAL = ("ema",)  # checks a flag asks for
 DEV, CLASSES, T, LR, WD, LAYER_DECAY, CH = "cuda:0", 5, 4, 1e-3, 0.05, 0.75, 1024
 SEED_BASE = 0x9A3C5F1B7E24D694
 
@@ -447,6 +450,44 @@ def check_merge(c):
     c.say("merge: gather() equals the single-process merger", g.result())
 
 
+# ================================================================================================ 9. averaged weights (--ema)
+def check_ema(c):
+    """rank r is built from init seed 11 + r and makes its ModelEma BEFORE the step object: behind _join every rank's average is a
+    bit copy of rank 0's masters, and it stays equal across the ranks over two updating steps on distinct shards (no exchange of
+    its own); ranks that disagree on the decay all raise"""
+    torch, F = c.torch, c.F
+    m = c.model(load=False, init_seed=11 + c.rank)
+    ema = F.ModelEma(m, decay=0.99)
+    first = [torch.zeros(1, dtype=torch.int64, device=DEV) for _ in range(c.world)]
+    c.dist.all_gather(first, ema.checksum().reshape(1))
+    assert int(first[0]) != int(first[1]), "the test's replicas start equal"
+    step, opt = c.stepper(m, clip_grad=1.0, model_ema=ema)
+    assert opt.ema is not None and opt.ema[0] is ema.flat
+    torch.cuda.synchronize()
+    cs, master = int(ema.checksum()), int(step.replicas_checksum())
+    c.say(f"EMA after _join: checksum {cs} master {master} built-from {int(first[c.rank])}")
+    c.all_equal(ema.checksum().reshape(1), "ModelEma.checksum() after _join")
+    c.bits(ema.flat, m.store.flat, "the average after _join against the broadcast masters")
+    assert cs == master == int(first[0]), (cs, master, int(first[0]))
+    for k in range(2):
+        out = step.step(c.clips(2, 950 + 10 * k + c.rank), c.labels(2, 960 + 10 * k + c.rank))
+        assert out["grad_norm"] is not None
+    torch.cuda.synchronize()
+    c.say(f"EMA after 2 updating steps: checksum {int(ema.checksum())} master {int(step.replicas_checksum())}")
+    c.all_equal(ema.checksum().reshape(1), "ModelEma.checksum() after two updating steps")
+    c.all_equal(ema.flat, "the average after two updating steps")
+    c.all_equal(m.store.flat, "the masters after two updating steps")
+    assert int(ema.checksum()) != cs and not torch.equal(ema.flat, m.store.flat)
+    m2 = c.model()
+    try:
+        c.stepper(m2, model_ema=F.ModelEma(m2, decay=0.99 if c.rank == 0 else 0.999))
+    except RuntimeError as e:
+        assert "differs between the ranks" in str(e) and "ModelEma" in str(e)
+        c.say("EMA_MISMATCH_RAISED")
+    else:
+        raise AssertionError("ranks with different ModelEma decays were accepted")
+
+
 # ================================================================================================ driver
 def worker(rank, world, port, checks, q):
     try:
@@ -475,8 +516,9 @@ def worker(rank, world, port, checks, q):
 
 
 def main(argv):
-    checks = argv or list(CHECKS)
-    bad = [n for n in checks if n not in CHECKS]
+    with_ema, argv = "--ema" in argv, [a for a in argv if a != "--ema"]
+    checks = argv + ["ema"] if with_ema else argv or list(CHECKS)
+    bad = [n for n in checks if n not in CHECKS + OPTIONAL]
     if bad:
         raise SystemExit(f"unknown check {bad}: one of {CHECKS}")
     world, port = 2, free_port()

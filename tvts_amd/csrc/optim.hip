@@ -7,29 +7,52 @@
 //                        byte table gives each chunk its parameter group (255 = frozen / padding).  The same pass
 //                        applies the data-parallel 1/world gradient scale and refreshes the bf16 weight shadow.
 //   tvts_adamw_torch     the same frame with torch.optim.AdamW arithmetic over up to 64 groups (the v1 fine-tuning step)
+//   tvts_adamw_torch_ema the same launch with timm's ModelEma rule applied to the new p while it is still in registers (one more
+//                        fp32 stream, 38 B per element); tvts_ema_update is the rule as a pass of its own (ModelEma.update)
+//   tvts_swap_f32_shadow in-place exchange of two fp32 buffers + the bf16 shadow of the first (evaluation from the average)
 //   tvts_cast_f32_bf16   shadow refresh when an external optimizer owned the update (drop-in path)
 //   tvts_transpose_bf16_batched   [N,K] -> [K,N] copies of every GEMM weight (dgrad operand), one launch
 //   tvts_pad_rows_bf16 / tvts_add_rows_f32   K-padding of the 14x14 patch-embedding weight and its wgrad (H/14)
 #include "common.h"
 
-// The frame of both AdamW kernels: one block per 1024-element chunk, four elements per lane.  `prologue(grp)` runs once the
+// timm.utils.ModelEma.update per element: ema_v * decay + (1. - decay) * model_v on fp32 tensors with a Python-float decay, i.e.
+// three roundings and no FMA, d32 = fp32(decay), o32 = fp32(1.0 - decay) with the difference formed in DOUBLE on the host (the
+// fp32 difference 1 - d32 is another number: 1.00016594e-4 instead of 9.99999975e-5 at decay 0.9999).
+__device__ __forceinline__ f32x4 ema_rule4(const f32x4& ev, const f32x4& pv, float d32, float o32) {
+#pragma clang fp contract(off)
+    f32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float a = ev[e] * d32, b = o32 * pv[e];
+        r[e] = a + b;
+    }
+    return r;
+}
+
+// The frame of the AdamW kernels: one block per 1024-element chunk, four elements per lane.  `prologue(grp)` runs once the
 // chunk is known to step (its group byte is below NGROUPS; a foreign group, 255 = frozen, keeps every bit) and returns the rule
-// that updates four elements of p / m / v from their gradients; the frame loads, stores and writes the bf16 shadow.
-template <int NGROUPS, typename Prologue>
+// that updates four elements of p / m / v from their gradients; the frame loads, stores and writes the bf16 shadow.  EMA: the
+// frame also carries the chunk's average through ema_rule4 from the final p (a compile-time choice: the instantiations without
+// an average are the code they were).
+template <int NGROUPS, bool EMA = false, typename Prologue>
 __device__ __forceinline__ void adamw_chunk(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                             float* __restrict__ v, bf16* __restrict__ shadow,
-                                            const unsigned char* __restrict__ chunk_group, Prologue prologue) {
+                                            const unsigned char* __restrict__ chunk_group, Prologue prologue,
+                                            float* __restrict__ ema = nullptr, float d32 = 0.f, float o32 = 0.f) {
     const int grp = chunk_group[blockIdx.x];
     if (grp >= NGROUPS) return;
     const auto update4 = prologue(grp);
     const size_t i = (size_t)blockIdx.x * 1024 + threadIdx.x * 4;
     f32x4 pv = *(f32x4*)(p + i), mv = *(f32x4*)(m + i), vv = *(f32x4*)(v + i);
     const f32x4 gv = *(const f32x4*)(g + i);
+    f32x4 ev;
+    if constexpr (EMA) ev = *(const f32x4*)(ema + i);
     update4(pv, mv, vv, gv);
     *(f32x4*)(p + i) = pv;
     *(f32x4*)(m + i) = mv;
     *(f32x4*)(v + i) = vv;
     if (shadow) *(bf16x4*)(shadow + i) = (bf16x4){(bf16)pv[0], (bf16)pv[1], (bf16)pv[2], (bf16)pv[3]};
+    if constexpr (EMA) *(f32x4*)(ema + i) = ema_rule4(ev, pv, d32, o32);
 }
 
 struct AdamGroups { float lr[4]; float wd[4]; float step_size[4]; };
@@ -97,15 +120,17 @@ extern "C" int tvts_adamw_hf(float* p, const float* g, float* m, float* v, void*
 // same device code either way, so both give the same bits.  g = stored gradient * grad_scale * norm_coef[1] (the clip coefficient
 // tvts_grad_sumsq left in device memory; no coefficient when norm_coef is null).  hyper_dev: lr[64] | wd[64] in device memory.
 // Chunk table as tvts_adamw_hf (1024 elements per chunk, one group byte each); a chunk of group >= 64 (255 = frozen) keeps every bit.
-__global__ __launch_bounds__(256) void adamw_torch_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                          float* __restrict__ v, bf16* __restrict__ shadow,
-                                                          const unsigned char* __restrict__ chunk_group,
-                                                          const float* __restrict__ hyper_dev, int step,
-                                                          const int* __restrict__ step_dev, double beta1d, double beta2d, float beta1,
-                                                          float beta2, float omb1, float omb2, float eps, float grad_scale,
-                                                          const float* __restrict__ norm_coef) {
+// (one body, two kernels: the kernel without an average keeps its name, its arguments and its code)
+template <bool EMA>
+__device__ __forceinline__ void adamw_torch_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                 float* __restrict__ v, bf16* __restrict__ shadow,
+                                                 const unsigned char* __restrict__ chunk_group,
+                                                 const float* __restrict__ hyper_dev, int step,
+                                                 const int* __restrict__ step_dev, double beta1d, double beta2d, float beta1,
+                                                 float beta2, float omb1, float omb2, float eps, float grad_scale,
+                                                 const float* __restrict__ norm_coef, float* __restrict__ ema, float d32, float o32) {
 #pragma clang fp contract(off)  // (lexical: it holds inside both lambdas; adamw_kernel has none and keeps its contractions)
-    adamw_chunk<64>(p, g, m, v, shadow, chunk_group, [&](int grp) {
+    adamw_chunk<64, EMA>(p, g, m, v, shadow, chunk_group, [&](int grp) {
         const float lr = hyper_dev[grp], wd = hyper_dev[64 + grp];
         const double st = (double)(step_dev ? step_dev[0] : step);
         const double bc1 = 1.0 - pow(beta1d, st), bc2 = 1.0 - pow(beta2d, st);
@@ -122,8 +147,30 @@ __global__ __launch_bounds__(256) void adamw_torch_kernel(float* __restrict__ p,
                 pv[e] -= ss * mv[e] / (sqrtf(vv[e]) / rs + eps);
             }
         };
-    });
+    }, ema, d32, o32);
 }
+__global__ __launch_bounds__(256) void adamw_torch_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, bf16* __restrict__ shadow,
+                                                          const unsigned char* __restrict__ chunk_group,
+                                                          const float* __restrict__ hyper_dev, int step,
+                                                          const int* __restrict__ step_dev, double beta1d, double beta2d, float beta1,
+                                                          float beta2, float omb1, float omb2, float eps, float grad_scale,
+                                                          const float* __restrict__ norm_coef) {
+    adamw_torch_body<false>(p, g, m, v, shadow, chunk_group, hyper_dev, step, step_dev, beta1d, beta2d, beta1, beta2, omb1, omb2, eps,
+                            grad_scale, norm_coef, nullptr, 0.f, 0.f);
+}
+__global__ __launch_bounds__(256) void adamw_torch_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                              float* __restrict__ v, bf16* __restrict__ shadow,
+                                                              const unsigned char* __restrict__ chunk_group,
+                                                              const float* __restrict__ hyper_dev, int step,
+                                                              const int* __restrict__ step_dev, double beta1d, double beta2d,
+                                                              float beta1, float beta2, float omb1, float omb2, float eps,
+                                                              float grad_scale, const float* __restrict__ norm_coef,
+                                                              float* __restrict__ ema, float d32, float o32) {
+    adamw_torch_body<true>(p, g, m, v, shadow, chunk_group, hyper_dev, step, step_dev, beta1d, beta2d, beta1, beta2, omb1, omb2, eps,
+                           grad_scale, norm_coef, ema, d32, o32);
+}
+static inline bool misaligned16(const void* q) { return ((uintptr_t)q & 15) != 0; }
 extern "C" int tvts_adamw_torch(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group,
                                 int nchunks, const float* hyper_dev, int step, const int* step_dev, double beta1, double beta2,
                                 double eps, float grad_scale, const float* norm_coef, hipStream_t stream) {
@@ -131,6 +178,58 @@ extern "C" int tvts_adamw_torch(float* p, const float* g, float* m, float* v, vo
     hipLaunchKernelGGL(adamw_torch_kernel, dim3(nchunks), dim3(256), 0, stream, p, g, m, v, (bf16*)shadow_bf16, chunk_group,
                        hyper_dev, step, step_dev, beta1, beta2, (float)beta1, (float)beta2, (float)(1.0 - beta1),
                        (float)(1.0 - beta2), (float)eps, grad_scale, norm_coef);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+extern "C" int tvts_adamw_torch_ema(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group,
+                                    int nchunks, const float* hyper_dev, int step, const int* step_dev, double beta1, double beta2,
+                                    double eps, float grad_scale, const float* norm_coef, float* ema, float d32, float o32,
+                                    hipStream_t stream) {
+    if (!p || !g || !m || !v || !ema || !chunk_group || !hyper_dev || nchunks <= 0 || (step <= 0 && !step_dev)) return TVTS_EINVAL;
+    if (misaligned16(p) || misaligned16(g) || misaligned16(m) || misaligned16(v) || misaligned16(ema) ||
+        ((uintptr_t)shadow_bf16 & 7)) return TVTS_EINVAL;
+    hipLaunchKernelGGL(adamw_torch_ema_kernel, dim3(nchunks), dim3(256), 0, stream, p, g, m, v, (bf16*)shadow_bf16, chunk_group,
+                       hyper_dev, step, step_dev, beta1, beta2, (float)beta1, (float)beta2, (float)(1.0 - beta1),
+                       (float)(1.0 - beta2), (float)eps, grad_scale, norm_coef, ema, d32, o32);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
+// ModelEma.update as a pass of its own (12 B per element): the chunk gate of tvts_adamw_torch (a chunk of group >= 64, 255 =
+// frozen / padding, keeps every bit of its average) and the rule of the fused launch.
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p,
+                                                         const unsigned char* __restrict__ chunk_group, float d32, float o32) {
+    if (chunk_group[blockIdx.x] >= 64) return;
+    const size_t i = (size_t)blockIdx.x * 1024 + threadIdx.x * 4;
+    *(f32x4*)(ema + i) = ema_rule4(*(const f32x4*)(ema + i), *(const f32x4*)(p + i), d32, o32);
+}
+extern "C" int tvts_ema_update(float* ema, const float* p, const unsigned char* chunk_group, int nchunks, float d32, float o32,
+                               hipStream_t stream) {
+    if (!ema || !p || !chunk_group || nchunks <= 0 || misaligned16(ema) || misaligned16(p)) return TVTS_EINVAL;
+    hipLaunchKernelGGL(ema_update_kernel, dim3(nchunks), dim3(256), 0, stream, ema, p, chunk_group, d32, o32);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
+// a[i] <-> b[i] in place, shadow[i] = bf16(new a[i]): the masters and the average change places for an evaluation, no third buffer.
+// Every element is read and written by one lane only, so the exchange needs no order between lanes.
+__global__ __launch_bounds__(256) void swap_shadow_kernel(float* __restrict__ a, float* __restrict__ b, bf16* __restrict__ shadow,
+                                                          size_t n4) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const f32x4 av = *(const f32x4*)(a + i * 4), bv = *(const f32x4*)(b + i * 4);
+        *(f32x4*)(a + i * 4) = bv;
+        *(f32x4*)(b + i * 4) = av;
+        *(bf16x4*)(shadow + i * 4) = (bf16x4){(bf16)bv[0], (bf16)bv[1], (bf16)bv[2], (bf16)bv[3]};
+    }
+}
+extern "C" int tvts_swap_f32_shadow(float* a, float* b, void* shadow_bf16, long n, hipStream_t stream) {
+    if (!a || !b || !shadow_bf16 || n <= 0 || n % 4 || misaligned16(a) || misaligned16(b) || ((uintptr_t)shadow_bf16 & 7))
+        return TVTS_EINVAL;
+    if (a < b ? a + n > b : b + n > a) return TVTS_EINVAL;  // overlapping buffers
+    const size_t n4 = (size_t)n / 4;
+    size_t blocks = (n4 + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(swap_shadow_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a, b, (bf16*)shadow_bf16, n4);
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;
 }

@@ -85,16 +85,35 @@ mask sequence (loading rank 0's seed verbatim would give all ranks rank 0's mask
 RandAugment) use the global ``random`` / ``np.random``, which the script seeds with ``args.seed + rank``
 (run_class_finetuning.py:230): they differ per rank as in the reference and need nothing here.
 
+Averaged weights (--model_ema, run_class_finetuning.py:55-58,345-352; engine_for_finetuning.py:84-85,97-98):
+
+    model_ema = ModelEma(model, decay=0.9999, device='', resume='')                # timm.utils.ModelEma's signature
+    step = FinetuneStep(model, opt, ..., model_ema=model_ema)                      # every updating call also carries the average
+    with model_ema.applied():                                                      # the model evaluates from the averaged weights
+        stats = validation_one_epoch(loader, model)
+    checkpoint["model_ema"] = model_ema.state_dict()                               # get_state_dict(model_ema), utils.py:419-440
+
+Not a second model: ONE fp32 buffer with the flat store's layout.  The rule is timm's expression ``ema * decay + (1. - decay) * p`` on
+fp32 tensors with a Python-float decay, bit for bit: ema' = fl(fl(ema * d32) + fl(o32 * p)), d32 = fp32(decay), o32 = fp32(1.0 -
+decay) with the difference formed in double (hip.ema_pair).  With a FinetuneStep it rides in the optimizer's launch
+(tvts_adamw_torch_ema, 38 instead of 30 B per trained element); ``update(model)`` is the same rule as a launch of its own
+(tvts_ema_update) for a loop that calls it the way the reference does.  A chunk the optimizer does not step (group byte 255: the
+whole tower under trainable="head", and padding) keeps every bit of its average, which is the parameter's value -- timm would let
+it drift.  ``applied()`` exchanges the masters and the average in place (tvts_swap_f32_shadow) and re-derives the
+shadows, on entry and again on exit: no second ParamStore, no second set of engine workspaces.
+
 OUT OF SCOPE (not built here): RandAugment's per-frame ``"random"`` interpolation and TranslateX / TranslateY (abs) (neither list of
 rand_augment_transform holds them), --recount > 1,
 ``motion_shift`` (random_resized_crop_with_shift), the reference's torch noise stream,
-``FastCollateMixup`` (the uint8-rounding variant: the reference scripts do not use it), ``ModelEma``, the fp16 loss scaler (the engine is bf16 with fp32 accumulation: there is no loss scale), DeepSpeed,
+``FastCollateMixup`` (the uint8-rounding variant: the reference scripts do not use it), ``ModelEma``'s ``device=`` (--model_ema_force_cpu)
+and ``resume=`` arguments, the fp16 loss scaler (the engine is bf16 with fp32 accumulation: there is no loss scale), DeepSpeed,
 sharded optimizer state, synchronising the TRAINING meters (the script's MetricLogger), and hipGraph capture of the step.
 The scripts' other half -- validation_one_epoch after every epoch, final_test over the test views and merge
 (engine_for_finetuning.py:142-285), both across ranks too -- is tvts_amd/downstream/evaluate_v1.py.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import random
@@ -106,6 +125,7 @@ import torch
 
 from .. import dist as D
 from .. import hip as K
+from ..engine import CH
 from ..optim import FusedTorchAdamW  # noqa: F401  (re-exported)
 
 MAX_GROUPS = FusedTorchAdamW.MAX_GROUPS
@@ -584,6 +604,112 @@ class Augment:
         return AugPlan(aug_i, None if self.randaug is None else ra_plan(views, self.randaug.num_layers, self.num_sample))
 
 
+# ---------------------------------------------------------------------------------------------- averaged weights
+class ModelEma:
+    """timm.utils.ModelEma (run_class_finetuning.py:345-352) over the flat store: ``flat`` is ONE fp32 buffer with the layout of
+    ``model.store.flat``, initialised as a bit copy of it.  Same constructor signature; a non-empty ``device`` (--model_ema_force_cpu)
+    and a non-empty ``resume`` (the scripts pass '') are not built and are refused.  Handed to ``FinetuneStep(..., model_ema=...)``
+    the average is updated inside the optimizer's launch on every updating call and the user does not call ``update``."""
+
+    def __init__(self, model, decay=0.9999, device='', resume=''):
+        if device:
+            raise NotImplementedError(f"ModelEma(device={device!r}): an average on another device (--model_ema_force_cpu) is not built")
+        if resume:
+            raise NotImplementedError(f"ModelEma(resume={resume!r}): loading a checkpoint file is not built; use load_state_dict")
+        decay = float(decay)
+        if not (0.0 <= decay <= 1.0):
+            raise ValueError(f"ModelEma(decay={decay!r}): expected a number in [0, 1]")
+        self.model, self.decay = model, decay
+        self.flat = model.store.flat.clone()
+        self.chunk_group = None  # FinetuneStep hands over its optimizer's chunk table; alone, the table follows set_trainable()
+        self._own_table = None
+        self._active = False
+
+    def _idle(self, what):
+        if self._active:
+            raise RuntimeError(f"ModelEma.{what} inside applied(): the masters and the average have changed places")
+
+    def _chunks(self):
+        """the chunk gate of update(): the optimizer's table when a FinetuneStep holds this average, else every chunk of a
+        parameter the engine marks trainable (model.set_trainable) as group 0, all others 255"""
+        if self.chunk_group is not None:
+            return self.chunk_group
+        st, flags = self.model.store, self.model.engine.requires_grad
+        key = tuple(bool(flags[n]) for n in st.shapes)
+        if self._own_table is None or self._own_table[0] != key:
+            table = torch.full((st.total // CH,), 255, dtype=torch.uint8)
+            for n, on in zip(st.shapes, key):
+                if on:
+                    o = st.off[n]
+                    table[o // CH:(o + st._n(n) + CH - 1) // CH] = 0
+            self._own_table = (key, table.to(st.device))
+        return self._own_table[1]
+
+    def reset(self):
+        """the average becomes a bit copy of the masters again (FinetuneStep._join, behind the start-up broadcast)"""
+        self._idle("reset")
+        self.flat.copy_(self.model.store.flat)
+
+    @torch.no_grad()
+    def update(self, model=None):
+        """ModelEma.update(model) as the reference's loop calls it (engine_for_finetuning.py:84-85,97-98): one launch of
+        tvts_ema_update over the trainable chunks"""
+        self._idle("update")
+        if model is not None and model is not self.model:
+            raise ValueError("ModelEma.update: the model this average was built from")
+        K.ema_update(self.flat, self.model.store.flat, self._chunks(), self.decay)
+
+    def _view(self, name):
+        st = self.model.store
+        o = st.off[name]
+        return self.flat[o:o + st._n(name)].view(st.shapes[name])
+
+    def state_dict(self):
+        """clones of the averaged tensors under model.state_dict()'s keys and shapes: what get_state_dict(model_ema) puts into the
+        checkpoint as `model_ema` (utils.py:419-440)"""
+        self._idle("state_dict")
+        return {k: self._view(self.model.store_name(k)).clone() for k in self.model.state_dict()}
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        self._idle("load_state_dict")
+        keys = list(self.model.state_dict())
+        if set(state_dict) != set(keys):
+            raise KeyError(f"ModelEma.load_state_dict: keys differ from the model's ({sorted(set(state_dict) ^ set(keys))[:4]} ...)")
+        for k in keys:
+            v, src = self._view(self.model.store_name(k)), state_dict[k]
+            if tuple(src.shape) != tuple(v.shape):
+                raise ValueError(f"ModelEma.load_state_dict: {k} has shape {tuple(src.shape)}, expected {tuple(v.shape)}")
+            v.copy_(src)
+
+    def checksum(self) -> torch.Tensor:
+        """device int64 scalar: the sum of the average's bit patterns, as FinetuneStep.replicas_checksum() for the masters"""
+        return self.flat.view(torch.int32).sum(dtype=torch.int64)
+
+    def _exchange(self):
+        st = self.model.store
+        K.swap_f32_shadow(st.flat, self.flat, st.shadow)
+        st.refresh_shadows(cast=False, transposed=True)
+        self.model.mark_shadows_fresh()
+
+    @contextlib.contextmanager
+    def applied(self):
+        """inside, the model evaluates from the averaged weights: model(x), forward_views, evaluate_v1.validation_one_epoch and
+        final_test run unchanged.  Entry and exit are the same in-place exchange of masters and average (+ the shadows); behind
+        it both hold their earlier bits, also when the body raised.  FinetuneStep.step, update, state_dict, load_state_dict and a
+        nested applied() raise RuntimeError while it is active."""
+        self._idle("applied")
+        if getattr(self.model, "_ema_applied", None) is not None:
+            raise RuntimeError("ModelEma.applied: another average is applied to this model")
+        self._exchange()
+        self._active, self.model._ema_applied = True, self
+        try:
+            yield self.model
+        finally:
+            self._active, self.model._ema_applied = False, None
+            self._exchange()
+
+
 # ---------------------------------------------------------------------------------------------- the step
 class FinetuneStep:
     """train_one_epoch's loop body (engine_for_finetuning.py:55-123) without DeepSpeed / loss scaler.  ``trainable="head"`` is
@@ -591,8 +717,10 @@ class FinetuneStep:
     With more than one rank of torch.distributed it is the data-parallel step (module docstring, "Several GPUs")."""
 
     def __init__(self, model, optimizer: FusedTorchAdamW, clip_grad=None, update_freq=1, smoothing=0.0, trainable="all",
-                 data_parallel=None, payload=None):
-        """data_parallel: None -- on when torch.distributed is initialised with more than one rank; False -- the single-process
+                 data_parallel=None, payload=None, model_ema=None):
+        """model_ema: a ModelEma of this model -- every call that updates then also updates the average, inside the optimizer's
+        launch (a call that only accumulates leaves it alone, as the reference's loop does); None: the step without an average.
+        data_parallel: None -- on when torch.distributed is initialised with more than one rank; False -- the single-process
         step whatever the world size; True without a process group is refused.  payload: "fp32" (default) or "bf16", the number
         format the gradients travel in; None reads TVTS_GRAD_PAYLOAD, as the pretraining step does."""
         if payload not in (None, "fp32", "bf16"):
@@ -611,6 +739,13 @@ class FinetuneStep:
         self.norm_coef = torch.zeros(2, dtype=torch.float32, device=dev)
         self.norm_coef[1] = 1.0
         optimizer.norm_coef = self.norm_coef
+        self.model_ema = model_ema
+        if model_ema is not None:
+            if model_ema.model is not model:
+                raise ValueError("model_ema: a ModelEma built from this step's model")
+            model_ema._idle("a FinetuneStep built")
+            model_ema.chunk_group = optimizer.chunk_group
+            optimizer.ema = (model_ema.flat, model_ema.decay)
         self.partial = torch.zeros(optimizer.chunk_group.numel(), dtype=torch.float32, device=dev)
         self.loss_cell = torch.zeros(1, dtype=torch.float32, device=dev)
         self.hits = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -629,11 +764,15 @@ class FinetuneStep:
         pay = payload or os.environ.get("TVTS_GRAD_PAYLOAD", "fp32")
         sig = repr((int(st.flat.numel()), self.trainable, self.update_freq, self.clip_grad, pay, len(opt.param_groups),
                     [float(g["weight_decay"]) for g in opt.param_groups], self.model.engine.recompute)).encode() + opt.chunk_group.cpu().numpy().tobytes()
-        D.agree(sig, "FinetuneStep: the model size, `trainable`, update_freq, clip_grad, payload, the recomputation mode or the "
-                     "optimizer's chunk / group table")
+        if self.model_ema is not None:  # (appended only with an average: without one the signature is the bytes it was)
+            sig += repr(("model_ema", self.model_ema.decay)).encode()
+        D.agree(sig, "FinetuneStep: the model size, `trainable`, update_freq, clip_grad, payload, the recomputation mode, the "
+                     "ModelEma (present or not, its decay) or the optimizer's chunk / group table")
         D.dist.broadcast(st.flat, src=0)
         st.refresh_shadows()
         self.model.mark_shadows_fresh()
+        if self.model_ema is not None:  # an average made before the process group holds this rank's pre-broadcast weights
+            self.model_ema.reset()
         self.sync = D.GradSync(st.grad, payload=pay)
 
     @property
@@ -709,6 +848,8 @@ class FinetuneStep:
         grad_norm is the norm of the gradient averaged over the ranks (the same value on every rank)."""
         m, eng, st = self.model, self.model.engine, self.model.store
         a, dev = eng.arch, st.device
+        if getattr(m, "_ema_applied", None) is not None:
+            raise RuntimeError("FinetuneStep.step inside ModelEma.applied(): the masters hold the averaged weights")
         if samples.dim() != 5:
             raise ValueError(f"samples: expected a 5-D clip batch, got {tuple(samples.shape)}")
         if aug is not None:

@@ -1398,16 +1398,62 @@ def adamw_hf(p, g, m, v, shadow, chunk_group, lr4, wd4, step, beta1=0.9, beta2=0
     _chk(rc, "tvts_adamw_hf")
 
 
+def ema_pair(decay):
+    """(d32, o32) of timm's ModelEma rule ``ema * decay + (1. - decay) * p`` on fp32 tensors with a Python-float decay, as Python
+    floats that hold fp32 values: d32 = fp32(decay), o32 = fp32(1.0 - decay) with the difference formed in DOUBLE and rounded once
+    (fp32(1) - d32 is another number: 1.00016594e-4 instead of 9.99999975e-5 at decay 0.9999)"""
+    decay = float(decay)
+    if not (0.0 <= decay <= 1.0):
+        raise ValueError(f"decay {decay!r}: expected a number in [0, 1]")
+    return ctypes.c_float(decay).value, ctypes.c_float(1.0 - decay).value  # (the C cast: round to nearest even, once each)
+
+
 def adamw_torch(p, g, m, v, shadow, chunk_group, hyper_dev, step, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, step_dev=None,
-                norm_coef=None):
-    """one torch.optim.AdamW step over the flat buffers; hyper_dev: device fp32 lr[64] | wd[64]"""
+                norm_coef=None, ema=None, ema_decay=None):
+    """one torch.optim.AdamW step over the flat buffers; hyper_dev: device fp32 lr[64] | wd[64].  ema (fp32, the layout of p) with
+    ema_decay: the same pass applies ModelEma's rule to the new p (tvts_adamw_torch_ema, 38 B per element); None: the launch of
+    before."""
     n = chunk_group.numel()
     assert hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= 128
     assert all(t.numel() >= n * 1024 for t in (p, g, m, v)) and (shadow is None or shadow.numel() >= n * 1024)
-    with _hbm("adamw", _adamw_bytes(chunk_group, 64)):
-        rc = _lib.load().tvts_adamw_torch(_p(p), _p(g), _p(m), _p(v), _p(shadow), _p(chunk_group), n, _p(hyper_dev), int(step),
-                                          _p(step_dev), beta1, beta2, eps, grad_scale, _p(norm_coef), _stream())
-    _chk(rc, "tvts_adamw_torch")
+    if ema is None:
+        if ema_decay is not None:
+            raise ValueError("ema_decay without ema")
+        with _hbm("adamw", _adamw_bytes(chunk_group, 64)):
+            rc = _lib.load().tvts_adamw_torch(_p(p), _p(g), _p(m), _p(v), _p(shadow), _p(chunk_group), n, _p(hyper_dev), int(step),
+                                              _p(step_dev), beta1, beta2, eps, grad_scale, _p(norm_coef), _stream())
+        _chk(rc, "tvts_adamw_torch")
+        return
+    if ema_decay is None:
+        raise ValueError("ema needs ema_decay")
+    d32, o32 = ema_pair(ema_decay)
+    assert ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() >= n * 1024 and ema.device == p.device
+    with _hbm("adamw", lambda: 38.0 * 1024 * float((chunk_group < 64).sum())):
+        rc = _lib.load().tvts_adamw_torch_ema(_p(p), _p(g), _p(m), _p(v), _p(shadow), _p(chunk_group), n, _p(hyper_dev), int(step),
+                                              _p(step_dev), beta1, beta2, eps, grad_scale, _p(norm_coef), _p(ema), d32, o32, _stream())
+    _chk(rc, "tvts_adamw_torch_ema")
+
+
+def ema_update(ema, p, chunk_group, decay):
+    """ModelEma.update as a pass of its own: ema = fl(fl(ema * d32) + fl(o32 * p)) on every 1024-element chunk whose group byte is
+    below 64; a chunk of another group (255 = frozen / padding) keeps every bit of ema.  12 B per element."""
+    n = chunk_group.numel()
+    d32, o32 = ema_pair(decay)
+    assert chunk_group.dtype == torch.uint8 and ema.dtype == torch.float32 and p.dtype == torch.float32
+    assert ema.is_contiguous() and p.is_contiguous() and ema.numel() >= n * 1024 and p.numel() >= n * 1024
+    with _hbm("ema", lambda: 12.0 * 1024 * float((chunk_group < 64).sum())):
+        rc = _lib.load().tvts_ema_update(_p(ema), _p(p), _p(chunk_group), n, d32, o32, _stream())
+    _chk(rc, "tvts_ema_update")
+
+
+def swap_f32_shadow(a, b, shadow):
+    """a <-> b in place (fp32, equal sizes, a multiple of 4 elements) and shadow = bf16(new a); no temporary buffer"""
+    assert a.dtype == torch.float32 and b.dtype == torch.float32 and shadow.dtype == torch.bfloat16
+    assert a.is_contiguous() and b.is_contiguous() and shadow.is_contiguous()
+    assert a.numel() == b.numel() and shadow.numel() >= a.numel() and a.device == b.device == shadow.device
+    with _hbm("ema", 18.0 * a.numel()):
+        rc = _lib.load().tvts_swap_f32_shadow(_p(a), _p(b), _p(shadow), a.numel(), _stream())
+    _chk(rc, "tvts_swap_f32_shadow")
 
 
 # ---- v1 fine-tuning step (finetune.hip; its optimizer launch, adamw_torch, is above beside adamw_hf)

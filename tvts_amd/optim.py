@@ -204,12 +204,15 @@ class FusedTorchAdamW(_FlatAdamW):
     p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps)) as ONE launch over the flat store, for up to 64 parameter groups -- the 28
     layer-decay groups of ViT-B (v1 fine-tuning, downstream/finetune_v1.py).  lr / weight_decay of the groups travel as the device
     table lr[64] | wd[64], which the kernel always reads: step() uploads it on every call.  ``norm_coef`` (set by FinetuneStep):
-    the device buffer whose second element scales every gradient -- the clip coefficient of tvts_grad_sumsq."""
+    the device buffer whose second element scales every gradient -- the clip coefficient of tvts_grad_sumsq.  ``ema`` (set by
+    FinetuneStep from its ModelEma): (fp32 buffer with the flat store's layout, decay) -- the launch then also carries the
+    averaged weights (tvts_adamw_torch_ema); None: the launch without an average."""
     MAX_GROUPS = 64
 
     def __init__(self, params, store: ParamStore, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, model=None):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), store, model)
         self.norm_coef = None
+        self.ema = None
 
     @torch.no_grad()
     def step(self, closure=None, device_step: bool = False):
@@ -217,6 +220,7 @@ class FusedTorchAdamW(_FlatAdamW):
         self.sync_hyper()
         b1, b2, eps, _, _ = self._begin(device_step)
         st = self.store
+        ema = {} if self.ema is None else dict(ema=self.ema[0], ema_decay=self.ema[1])
         K.adamw_torch(st.flat, st.grad, st.m, st.v, st.shadow, self.chunk_group, self.hyper_dev, self.global_step, b1, b2, eps,
-                      self.grad_scale, step_dev=self.step_dev if device_step else None, norm_coef=self.norm_coef)
+                      self.grad_scale, step_dev=self.step_dev if device_step else None, norm_coef=self.norm_coef, **ema)
         self._finish(device_step)
