@@ -740,6 +740,23 @@ int tvts_adamw_torch_ema(float* p, const float* g, float* m, float* v, void* sha
                          float grad_scale, const float* norm_coef, float* ema, float d32, float o32, hipStream_t stream);
 int tvts_ema_update(float* ema, const float* p, const unsigned char* chunk_group, int nchunks, float d32, float o32,
                     hipStream_t stream);
+/* torch.optim.SGD as optim_factory.py:121-126 builds it for v1/scripts/linear_ssv2.sh (--opt sgd --lr 0.1 --momentum 0.9
+ * --weight_decay 1e-9: "sgd" / "nesterov" with nesterov=True, "momentum" without), single-tensor form of torch/optim/sgd.py with
+ * dampening 0, bit for bit -- every add(x, alpha=a) there is one fused multiply-add:
+ *   gg = g * gs; d = wd != 0 ? fmaf(wd, p, gg) : gg; momentum != 0: buf = first update ? d : fl(mu * buf) + d,
+ *   d = nesterov ? fmaf(mu, buf, d) : buf; p = fmaf(-lr, d, p); shadow = bf16(p).
+ * lr, wd per group from hyper_dev (device fp32 lr[64] | wd[64]), mu = fp32(momentum), gs = grad_scale * norm_coef[1] (norm_coef
+ * optional).  First update: `step` (or step_dev[0] when given: same device code, same bits) == 1; buf is then written, not read.
+ * momentum == 0: buf is neither read nor written and may be null.  Chunk table as tvts_adamw_torch: a chunk of group >= 64 (255 =
+ * frozen) keeps every bit of p, buf, the shadow and the average.  tvts_sgd_torch_ema: the same launch with ModelEma's rule applied
+ * to the new p (p, buf and the shadow get the bits of tvts_sgd_torch).  -22: a null pointer, nchunks <= 0, step <= 0 without
+ * step_dev, nesterov with momentum == 0, a pointer that is not 16-byte aligned (shadow: 8). */
+int tvts_sgd_torch(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
+                   const float* hyper_dev, int step, const int* step_dev, double momentum, int nesterov, float grad_scale,
+                   const float* norm_coef, hipStream_t stream);
+int tvts_sgd_torch_ema(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
+                       const float* hyper_dev, int step, const int* step_dev, double momentum, int nesterov, float grad_scale,
+                       const float* norm_coef, float* ema, float d32, float o32, hipStream_t stream);
 /* a[i] <-> b[i] in place and shadow_bf16[i] = bf16(new a[i]) for i < n; n % 4 == 0, a and b disjoint and 16-byte aligned (-22).
  * ModelEma.applied(): the masters and the average change places without a third buffer. */
 int tvts_swap_f32_shadow(float* a, float* b, void* shadow_bf16, long n, hipStream_t stream);

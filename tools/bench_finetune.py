@@ -47,6 +47,13 @@ ModelEma(decay 0.9999).
     separate  the step without an average, then ema.update(model) behind every call, as the reference's loop does (one more
               launch, tvts_ema_update, 12 B per element)
 
+--opt {adamw,sgd} (default adamw: the run and its output as before; without --mixup / --aug / --gpus / --ema).  sgd: the linear-probe
+script's optimizer, FusedTorchSGD (torch.optim.SGD, momentum 0.9, Nesterov: tvts_sgd_torch, 22 B per trained element against
+AdamW's 30), beside FusedTorchAdamW in the SAME process: three rounds, each timing trainable = "all" and "head" under AdamW and
+then under SGD (probe: lr 0.1, weight_decay 1e-9 as v1/scripts/linear_ssv2.sh; fine-tuning: lr 1e-3 x layer scale, weight_decay
+0.05).  The line's "summary" gives, per setting, the SGD step over the AdamW step of the same round beside the spread of the
+AdamW rounds (max / min - 1): a difference inside that spread is not a measured difference.
+
 --gpus N: the data-parallel step, one process per GPU -- `python -m torch.distributed.run --nproc-per-node N tools/bench_finetune.py
 --gpus N --batch 8 --num-sample 2` (N = 1 also runs as a plain process, without a process group).  Every rank runs the default
 recipe's step on its own --batch samples (--aug device, --mixup device, --randaug device; per-rank draws seeded seed + rank as the
@@ -71,10 +78,17 @@ def make(trainable, args, **step_kw):
     from tvts_amd.downstream.finetune_v1 import FinetuneStep, FusedTorchAdamW, param_groups
     from tvts_amd.downstream.video_encoder_v1 import VisionTransformer
     m = VisionTransformer(num_classes=args.classes, drop_path_rate=args.drop_path, init_seed=1, **KW)
-    groups = param_groups(m, 0.05, 0.75, trainable=trainable)
-    opt = FusedTorchAdamW(groups, m.store, lr=1e-3, model=m)
+    if getattr(args, "opt_kind", "adamw") == "sgd":
+        from tvts_amd.downstream.finetune_v1 import FusedTorchSGD
+        lr, wd = (0.1, 1e-9) if trainable == "head" else (1e-3, 0.05)
+        groups = param_groups(m, wd, 0.75, trainable=trainable)
+        opt = FusedTorchSGD(groups, m.store, lr=lr, momentum=0.9, nesterov=True, model=m)
+    else:
+        lr = 1e-4
+        groups = param_groups(m, 0.05, 0.75, trainable=trainable)
+        opt = FusedTorchAdamW(groups, m.store, lr=1e-3, model=m)
     for g in opt.param_groups:
-        g["lr"] = 1e-4 * g["lr_scale"]
+        g["lr"] = lr * g["lr_scale"]
     ema = getattr(args, "ema", "off")
     if ema != "off":
         from tvts_amd.downstream.finetune_v1 import ModelEma
@@ -318,7 +332,7 @@ def run(trainable, args, clip, targets):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.iters
     res = {"step ms": 1e3 * dt, "clips/s": args.batch / dt, "parameter groups": ngroups, "last loss": float(out["loss"])}
-    if trainable == "all" and args.mixup == "off":  # the instrumented pass: events around every HBM-bound launch, the drop-path family summed
+    if trainable == "all" and args.mixup == "off" and args.opt == "adamw":  # the instrumented pass: events around every HBM-bound launch, the drop-path family summed
         reps = max(2, args.iters // 4)
         K.HBM_PROFILE = []
         try:
@@ -429,7 +443,10 @@ def main():
     ap.add_argument("--num-sample", type=int, default=1, help="views per decoded clip (--num_sample of the script)")
     ap.add_argument("--randaug", choices=("off", "device", "host"), default="off", help="RandAugment in front of the crop (--aug device)")
     ap.add_argument("--ema", choices=("off", "fused", "separate"), default="off", help="ModelEma: in the optimizer's launch, or update() behind the step")
+    ap.add_argument("--opt", choices=("adamw", "sgd"), default="adamw", help="sgd: FusedTorchSGD beside FusedTorchAdamW in the same run, three rounds")
     args = ap.parse_args()
+    if args.opt != "adamw" and (args.gpus or args.mixup != "off" or args.aug != "off" or args.ema != "off" or args.u8):
+        raise SystemExit("--opt sgd: the plain step only (without --gpus, --mixup, --aug, --ema, --u8)")
     if args.ema != "off" and (args.gpus or args.mixup != "off" or args.aug != "off"):
         raise SystemExit("--ema fused / separate: the plain step only (without --gpus, --mixup, --aug)")
     if args.gpus:
@@ -477,6 +494,26 @@ def main():
         if args.mixup == "off":
             targets = torch.randint(0, args.classes, (args.batch,), generator=g)
         out["trainable=all"] = run_aug(args, targets)
+        print(json.dumps(out), flush=True)
+        return
+    if args.opt == "sgd":
+        rounds = []
+        for _ in range(3):
+            rnd = {}
+            for kind in ("adamw", "sgd"):
+                args.opt_kind = kind
+                rnd[kind] = {"trainable=" + t: run(t, args, clip, targets) for t in ("all", "head")}
+            rounds.append(rnd)
+        out["optimizers"] = {"adamw": "FusedTorchAdamW (tvts_adamw_torch)", "sgd": "FusedTorchSGD momentum 0.9 nesterov (tvts_sgd_torch)"}
+        out["rounds"] = rounds
+        summary = {}
+        for t in ("trainable=all", "trainable=head"):
+            adam = [r["adamw"][t]["step ms"] for r in rounds]
+            sgd = [r["sgd"][t]["step ms"] for r in rounds]
+            summary[t] = {"adamw step ms by round": adam, "sgd step ms by round": sgd,
+                          "sgd / adamw by round": [b / a for a, b in zip(adam, sgd)],
+                          "spread of the adamw rounds (max / min - 1)": max(adam) / min(adam) - 1.0}
+        out["summary"] = summary
         print(json.dumps(out), flush=True)
         return
     for trainable in ("all", "head") if args.mixup == "off" else ("all",):

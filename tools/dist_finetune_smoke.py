@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Two data-parallel ranks of the v1 fine-tuning step and of the evaluation merges on ONE GPU (gloo moving device tensors, the
 pattern of tools/dist_smoke.py): FinetuneStep's gradient exchange, validation_one_epoch's meter merge and ViewMerger.gather.
-usage: python tools/dist_finetune_smoke.py [--ema] [check ...]      (no argument: every check, in one pair of processes)
+usage: python tools/dist_finetune_smoke.py [--ema] [--opt {adamw,sgd}] [check ...]      (no argument: every check, in one pair of processes)
 checks: identical distinct replicas travel bf16 start mismatch seeds validation merge
+--opt sgd: the same checks with FusedTorchSGD (lr 0.1, momentum 0.9, Nesterov: torch.optim.SGD as the linear-probe script builds it)
+in place of FusedTorchAdamW -- all but `bf16`, whose bound is derived for AdamW's first step -- and the check `optimizers` behind
+them: a rank built with AdamW beside a rank built with SGD, both raise.
 --ema: the check `ema` behind the named ones (alone when none is named; not part of "every check") -- a ModelEma made BEFORE the
 step object on ranks that start from different weights, both ranks' ModelEma.checksum() after _join and after two updating steps.
 The model is tests/v1_downstream_synth.TINY; the gates are the test suite's own (tests/kernel_bounds.py, check_grads of
@@ -16,7 +19,9 @@ import traceback
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHECKS = ("identical", "distinct", "replicas", "travel", "bf16", "start", "mismatch", "seeds", "validation", "merge")
-OPTIONAL = ("ema",)  # checks a flag asks for
+OPTIONAL = ("ema", "optimizers")  # checks a flag asks for
+ADAMW_ONLY = ("bf16",)  # (its bound is AdamW's first step)
+SGD_LR, SGD_MOMENTUM = 0.1, 0.9
 DEV, CLASSES, T, LR, WD, LAYER_DECAY, CH = "cuda:0", 5, 4, 1e-3, 0.05, 0.75, 1024
 SEED_BASE = 0x9A3C5F1B7E24D694
 
@@ -30,7 +35,7 @@ def free_port():
 class Ctx:
     """what every check of one rank shares: the modules, the rank, a model that was built BEFORE the process group existed"""
 
-    def __init__(self, rank, world, early):
+    def __init__(self, rank, world, early, opt="adamw"):
         import numpy as np
         import torch
         import torch.distributed as dist
@@ -41,7 +46,7 @@ class Ctx:
         from tvts_amd.downstream import evaluate_v1 as E
         from tvts_amd.downstream import finetune_v1 as F
         self.np, self.torch, self.dist, self.KB, self.S, self.K, self.E, self.F = np, torch, dist, KB, S, K, E, F
-        self.rank, self.world, self.early = rank, world, early
+        self.rank, self.world, self.early, self.opt = rank, world, early, opt
         self.sd = S.synth_state(S.TINY, 61, CLASSES)
 
     # ---- builders
@@ -52,11 +57,15 @@ class Ctx:
             m.load_state_dict(self.sd, strict=True)
         return m
 
-    def stepper(self, m, trainable="all", **kw):
+    def stepper(self, m, trainable="all", opt=None, **kw):
         F = self.F
-        opt = F.FusedTorchAdamW(F.param_groups(m, WD, LAYER_DECAY, trainable=trainable), m.store, lr=LR, model=m)
+        groups = F.param_groups(m, WD, LAYER_DECAY, trainable=trainable)
+        if (opt or self.opt) == "sgd":
+            lr, opt = SGD_LR, F.FusedTorchSGD(groups, m.store, lr=SGD_LR, momentum=SGD_MOMENTUM, nesterov=True, model=m)
+        else:
+            lr, opt = LR, F.FusedTorchAdamW(groups, m.store, lr=LR, model=m)
         for g in opt.param_groups:
-            g["lr"] = LR * g["lr_scale"]
+            g["lr"] = lr * g["lr_scale"]
         return F.FinetuneStep(m, opt, trainable=trainable, **kw), opt
 
     def clips(self, B, seed):
@@ -94,7 +103,8 @@ class Ctx:
 
 def state_of(m):
     st = m.store
-    return dict(flat=st.flat.clone(), m=st.m.clone(), v=st.v.clone(), shadow=st.shadow.clone())
+    # (SGD keeps no second state buffer: store.v does not exist then)
+    return {k: t.clone() for k, t in (("flat", st.flat), ("m", st.m), ("v", st.v), ("shadow", st.shadow)) if t is not None}
 
 
 def bitsum(c, t):
@@ -212,9 +222,10 @@ def check_replicas(c):
         c.dist.all_gather(tabs, m.engine.buf["ft.dp_table"].contiguous())
         differ = differ or not torch.equal(tabs[0], tabs[1])
     assert differ, "both ranks drew the same stochastic-depth masks in every step"
-    sums = torch.stack([step.replicas_checksum(), bitsum(c, m.store.m), bitsum(c, m.store.v)])
+    sums = torch.stack([step.replicas_checksum()] + [bitsum(c, t) for t in (m.store.m, m.store.v) if t is not None])
     assert sums.dtype == torch.int64 and sums.is_cuda
-    c.all_equal(sums, "replicas_checksum and the checksums of exp_avg / exp_avg_sq after 3 steps")
+    assert sums.numel() == (2 if c.opt == "sgd" else 3)
+    c.all_equal(sums, "replicas_checksum and the checksums of the optimizer's state buffers after 3 steps")
     c.all_equal(m.store.flat, "the parameters after 3 steps")
     assert int(step.replicas_checksum()) != int(bitsum(c, c.model().store.flat))
     c.say("replicas: parameters and moments equal on both ranks after 3 steps, masks differ")
@@ -488,8 +499,31 @@ def check_ema(c):
         raise AssertionError("ranks with different ModelEma decays were accepted")
 
 
+# ================================================================================================ 10. optimizers (--opt sgd)
+def check_optimizers(c):
+    """rank 0 built with FusedTorchAdamW, rank 1 with FusedTorchSGD over the same groups: both raise from the agreement, neither
+    is left in a collective; two ranks with SGD that differ in `nesterov` raise too"""
+    F = c.F
+    for what in ("kind", "nesterov"):
+        m = c.model()
+        try:
+            if what == "kind":
+                c.stepper(m, opt="adamw" if c.rank == 0 else "sgd")
+            else:
+                opt = F.FusedTorchSGD(F.param_groups(m, WD, LAYER_DECAY), m.store, lr=SGD_LR, momentum=SGD_MOMENTUM, nesterov=c.rank == 0, model=m)
+                F.FinetuneStep(m, opt)
+        except RuntimeError as e:
+            assert "differs between the ranks" in str(e) and "the optimizer's kind" in str(e), str(e)
+            c.say(f"OPTIMIZER_MISMATCH_RAISED ({what})")
+        else:
+            raise AssertionError(f"ranks with different optimizers ({what}) were accepted")
+    t = c.torch.ones(1, device=DEV)
+    c.dist.all_reduce(t)  # the group is still usable
+    assert float(t) == c.world
+
+
 # ================================================================================================ driver
-def worker(rank, world, port, checks, q):
+def worker(rank, world, port, checks, q, opt="adamw"):
     try:
         sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
         os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
@@ -503,7 +537,7 @@ def worker(rank, world, port, checks, q):
             early = VisionTransformer(num_classes=CLASSES, drop_path_rate=0.1, **S.TINY)
             early.load_state_dict(S.synth_state(S.TINY, 61, CLASSES), strict=True)
         dist.init_process_group("gloo", rank=rank, world_size=world)
-        c = Ctx(rank, world, early)
+        c = Ctx(rank, world, early, opt)
         for name in checks:
             globals()["check_" + name](c)
             torch.cuda.synchronize()
@@ -517,14 +551,23 @@ def worker(rank, world, port, checks, q):
 
 def main(argv):
     with_ema, argv = "--ema" in argv, [a for a in argv if a != "--ema"]
-    checks = argv + ["ema"] if with_ema else argv or list(CHECKS)
+    opt = "adamw"
+    if "--opt" in argv:
+        i = argv.index("--opt")
+        if i + 1 >= len(argv) or argv[i + 1] not in ("adamw", "sgd"):
+            raise SystemExit("--opt adamw | sgd")
+        opt, argv = argv[i + 1], argv[:i] + argv[i + 2:]
+    every = list(CHECKS) if opt == "adamw" else [n for n in CHECKS if n not in ADAMW_ONLY] + ["optimizers"]
+    checks = argv + ["ema"] if with_ema else argv or every
     bad = [n for n in checks if n not in CHECKS + OPTIONAL]
     if bad:
         raise SystemExit(f"unknown check {bad}: one of {CHECKS}")
+    if opt == "sgd" and any(n in ADAMW_ONLY for n in checks):
+        raise SystemExit(f"--opt sgd: {ADAMW_ONLY} hold AdamW to a bound of its own and do not run under SGD")
     world, port = 2, free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=worker, args=(r, world, port, checks, q)) for r in range(world)]
+    procs = [ctx.Process(target=worker, args=(r, world, port, checks, q, opt)) for r in range(world)]
     for p in procs:
         p.start()
     import queue

@@ -9,6 +9,8 @@
 //   tvts_adamw_torch     the same frame with torch.optim.AdamW arithmetic over up to 64 groups (the v1 fine-tuning step)
 //   tvts_adamw_torch_ema the same launch with timm's ModelEma rule applied to the new p while it is still in registers (one more
 //                        fp32 stream, 38 B per element); tvts_ema_update is the rule as a pass of its own (ModelEma.update)
+//   tvts_sgd_torch       torch.optim.SGD (momentum, Nesterov) in the same chunk frame with ONE state stream, bit for bit (the v1 linear
+//                        probe, 22 B per element); tvts_sgd_torch_ema carries the average as tvts_adamw_torch_ema does
 //   tvts_swap_f32_shadow in-place exchange of two fp32 buffers + the bf16 shadow of the first (evaluation from the average)
 //   tvts_cast_f32_bf16   shadow refresh when an external optimizer owned the update (drop-in path)
 //   tvts_transpose_bf16_batched   [N,K] -> [K,N] copies of every GEMM weight (dgrad operand), one launch
@@ -209,6 +211,101 @@ extern "C" int tvts_ema_update(float* ema, const float* p, const unsigned char* 
     hipLaunchKernelGGL(ema_update_kernel, dim3(nchunks), dim3(256), 0, stream, ema, p, chunk_group, d32, o32);
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;
+}
+
+// ---- torch.optim.SGD, multi-tensor (the v1 linear probe: v1/scripts/linear_ssv2.sh, --opt sgd --lr 0.1 --momentum 0.9)
+// The optimizer optim_factory.create_optimizer builds for "sgd" / "nesterov" (nesterov=True) and "momentum" (optim_factory.py:121-126),
+// in the single-tensor form of torch/optim/sgd.py with dampening 0.  Every add(x, alpha=a) of that form is ONE fused multiply-add in
+// ATen, so per element (fmaf = one rounding; lr, wd, mu the fp32 roundings of the group's lr / weight_decay and of momentum):
+//     gg = g * gs                                    gs as tvts_adamw_torch forms it
+//     d  = wd != 0 ? fmaf(wd, p, gg) : gg            d_p.add(param, alpha=weight_decay)
+//     mu != 0:  buf = first update ? d : fl(mu * buf) + d      clone(d_p) -- the bits of d -- / buf.mul_(mu).add_(d_p): two roundings
+//               d   = nesterov ? fmaf(mu, buf, d) : buf
+//     p  = fmaf(-lr, d, p)                           param.add_(d_p, alpha=-lr)
+// The step counter (step_dev[0] when given, else `step`: the same device code) only says whether this is the first update, t == 1:
+// buf is then written and not read.  MOM = false (momentum 0): buf is neither read nor written.  A sibling of adamw_chunk with one
+// state stream instead of two: the same chunk gate, the same 16-byte accesses, the shadow and the average as there.
+template <bool MOM, bool EMA>
+__device__ __forceinline__ void sgd_torch_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                               bf16* __restrict__ shadow, const unsigned char* __restrict__ chunk_group,
+                                               const float* __restrict__ hyper_dev, int step, const int* __restrict__ step_dev,
+                                               float mu, int nesterov, float grad_scale, const float* __restrict__ norm_coef,
+                                               float* __restrict__ ema, float d32, float o32) {
+#pragma clang fp contract(off)  // (the FMAs below are explicit calls; fl(mu * buf) + d must stay two roundings)
+    const int grp = chunk_group[blockIdx.x];
+    if (grp >= 64) return;
+    const float lr = hyper_dev[grp], wd = hyper_dev[64 + grp];
+    const bool first = (step_dev ? step_dev[0] : step) == 1;
+    const float gs = norm_coef ? grad_scale * norm_coef[1] : grad_scale;
+    const float nlr = -lr;
+    const size_t i = (size_t)blockIdx.x * 1024 + threadIdx.x * 4;
+    f32x4 pv = *(f32x4*)(p + i), bv, ev;
+    const f32x4 gv = *(const f32x4*)(g + i);
+    if constexpr (MOM) {
+        if (!first) bv = *(const f32x4*)(buf + i);
+    }
+    if constexpr (EMA) ev = *(const f32x4*)(ema + i);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float gg = gv[e] * gs;
+        float d = wd != 0.f ? __builtin_fmaf(wd, pv[e], gg) : gg;
+        if constexpr (MOM) {
+            float b = d;
+            if (!first) {
+                const float mb = mu * bv[e];
+                b = mb + d;
+            }
+            bv[e] = b;
+            d = nesterov ? __builtin_fmaf(mu, b, d) : b;
+        }
+        pv[e] = __builtin_fmaf(nlr, d, pv[e]);
+    }
+    *(f32x4*)(p + i) = pv;
+    if constexpr (MOM) *(f32x4*)(buf + i) = bv;
+    if (shadow) *(bf16x4*)(shadow + i) = (bf16x4){(bf16)pv[0], (bf16)pv[1], (bf16)pv[2], (bf16)pv[3]};
+    if constexpr (EMA) *(f32x4*)(ema + i) = ema_rule4(ev, pv, d32, o32);
+}
+template <bool MOM, bool EMA>
+__global__ __launch_bounds__(256) void sgd_torch_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                        bf16* __restrict__ shadow, const unsigned char* __restrict__ chunk_group,
+                                                        const float* __restrict__ hyper_dev, int step,
+                                                        const int* __restrict__ step_dev, float mu, int nesterov, float grad_scale,
+                                                        const float* __restrict__ norm_coef, float* __restrict__ ema, float d32,
+                                                        float o32) {
+    sgd_torch_body<MOM, EMA>(p, g, buf, shadow, chunk_group, hyper_dev, step, step_dev, mu, nesterov, grad_scale, norm_coef, ema, d32,
+                             o32);
+}
+template <bool EMA>
+static int sgd_torch_launch(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
+                            const float* hyper_dev, int step, const int* step_dev, double momentum, int nesterov, float grad_scale,
+                            const float* norm_coef, float* ema, float d32, float o32, hipStream_t stream) {
+    const float mu = (float)momentum;
+    const bool mom = mu != 0.f;
+    if (!p || !g || (mom && !buf) || (EMA && !ema) || !chunk_group || !hyper_dev || nchunks <= 0 || (step <= 0 && !step_dev))
+        return TVTS_EINVAL;
+    if (nesterov && !mom) return TVTS_EINVAL;  // torch: "Nesterov momentum requires a momentum and zero dampening"
+    if (misaligned16(p) || misaligned16(g) || (mom && misaligned16(buf)) || (EMA && misaligned16(ema)) ||
+        ((uintptr_t)shadow_bf16 & 7)) return TVTS_EINVAL;
+    if (mom)
+        hipLaunchKernelGGL((sgd_torch_kernel<true, EMA>), dim3(nchunks), dim3(256), 0, stream, p, g, buf, (bf16*)shadow_bf16,
+                           chunk_group, hyper_dev, step, step_dev, mu, nesterov ? 1 : 0, grad_scale, norm_coef, ema, d32, o32);
+    else
+        hipLaunchKernelGGL((sgd_torch_kernel<false, EMA>), dim3(nchunks), dim3(256), 0, stream, p, g, buf, (bf16*)shadow_bf16,
+                           chunk_group, hyper_dev, step, step_dev, mu, 0, grad_scale, norm_coef, ema, d32, o32);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+extern "C" int tvts_sgd_torch(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
+                              const float* hyper_dev, int step, const int* step_dev, double momentum, int nesterov, float grad_scale,
+                              const float* norm_coef, hipStream_t stream) {
+    return sgd_torch_launch<false>(p, g, buf, shadow_bf16, chunk_group, nchunks, hyper_dev, step, step_dev, momentum, nesterov,
+                                   grad_scale, norm_coef, nullptr, 0.f, 0.f, stream);
+}
+extern "C" int tvts_sgd_torch_ema(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group,
+                                  int nchunks, const float* hyper_dev, int step, const int* step_dev, double momentum, int nesterov,
+                                  float grad_scale, const float* norm_coef, float* ema, float d32, float o32, hipStream_t stream) {
+    return sgd_torch_launch<true>(p, g, buf, shadow_bf16, chunk_group, nchunks, hyper_dev, step, step_dev, momentum, nesterov,
+                                  grad_scale, norm_coef, ema, d32, o32, stream);
 }
 
 // a[i] <-> b[i] in place, shadow[i] = bf16(new a[i]): the masters and the average change places for an evaluation, no third buffer.

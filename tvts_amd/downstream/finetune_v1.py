@@ -28,6 +28,19 @@ and on every update_freq-th call tvts_grad_sumsq (global norm + clip coefficient
 fill-kernel zero of the gradients.  Nothing in the step synchronises with the host; the returned values are device tensors.
 The optimizer, FusedTorchAdamW, lives in tvts_amd/optim.py beside FusedHFAdamW (one shared base) and is re-exported here.
 
+Linear probing with the script's optimizer (v1/scripts/linear_ssv2.sh: --opt sgd --lr 0.1 --momentum 0.9 --weight_decay 1e-9;
+run_class_linear.py:342-346 leaves the head trainable, optim_factory.py:121-126 maps `sgd` / `nesterov` to
+torch.optim.SGD(momentum=args.momentum, nesterov=True) and `momentum` to the same without Nesterov):
+
+    args = Namespace(opt="sgd", lr=0.1, momentum=0.9, weight_decay=1e-9, opt_eps=None, opt_betas=None)
+    opt = create_optimizer(args, model, trainable="head")                          # -> FusedTorchSGD over param_groups(..., "head")
+    step = FinetuneStep(model, opt, update_freq=1, trainable="head")
+    out = step.step(samples, targets)
+
+FusedTorchSGD (tvts_amd/optim.py) is torch.optim.SGD's single-tensor arithmetic bit for bit -- every add(x, alpha=a) of it is one
+fused multiply-add -- as one launch over the flat store (tvts_sgd_torch; with a ModelEma, tvts_sgd_torch_ema): 22 B per trained
+element with momentum against AdamW's 30.  Its state is torch's (``momentum_buffer``), so checkpoints travel both ways.
+
 The per-sample augmentation behind RandAugment (ssv2.py:186-227: Normalize, random-resized crop, flip, random erasing; on in the
 default recipe, with --num_sample 2 views per clip):
 
@@ -126,7 +139,7 @@ import torch
 from .. import dist as D
 from .. import hip as K
 from ..engine import CH
-from ..optim import FusedTorchAdamW  # noqa: F401  (re-exported)
+from ..optim import FusedTorchAdamW, FusedTorchSGD  # noqa: F401  (re-exported)
 
 MAX_GROUPS = FusedTorchAdamW.MAX_GROUPS
 
@@ -173,6 +186,87 @@ def param_groups(model, weight_decay, layer_decay=1.0, skip_list=None, trainable
         if g is None:
             g = groups[gname] = dict(name=gname, weight_decay=0.0 if no_decay else weight_decay, params=[], param_names=[],
                                      lr_scale=scale)
+        g["params"].append(p)
+        g["param_names"].append(name)
+    return list(groups.values())
+
+
+class LayerDecayValueAssigner:
+    """optim_factory.LayerDecayValueAssigner (:40-48): get_layer_id / get_scale are what the scripts hand to create_optimizer as
+    get_num_layer / get_layer_scale (run_class_finetuning.py:369-378)"""
+
+    def __init__(self, values):
+        self.values = values
+
+    def get_scale(self, layer_id):
+        return self.values[layer_id]
+
+    def get_layer_id(self, var_name):
+        return num_layer_for_vit(var_name, len(self.values))
+
+
+_BUILT_OPTS = "adamw; sgd / nesterov (torch.optim.SGD with Nesterov momentum); momentum (torch.optim.SGD without)"
+
+
+def create_optimizer(args, model, get_num_layer=None, get_layer_scale=None, filter_bias_and_bn=True, skip_list=None, trainable="all"):
+    """optim_factory.create_optimizer (:93-178) for the optimizers the shipped scripts select: ``adamw`` -> FusedTorchAdamW, ``sgd`` /
+    ``nesterov`` -> FusedTorchSGD(momentum=args.momentum, nesterov=True), ``momentum`` -> the same without Nesterov (:121-130); as
+    there the name is lower-cased and only what follows its last ``_`` selects.  With args.weight_decay and filter_bias_and_bn
+    the groups carry the decay (``param_groups``: get_parameter_groups with get_num_layer / get_layer_scale, a
+    LayerDecayValueAssigner's bound methods or None) and the optimizer's own weight_decay is 0 (:96-103); else all trainable
+    parameters form one group.  opt_eps is dropped for SGD (:122,125); opt_betas with an SGD name is refused (torch.optim.SGD would
+    raise on the keyword).  Every other name -- and a ``lookahead_`` prefix -- raises NotImplementedError.  trainable: as
+    ``param_groups`` ("head": the parameters run_class_linear.py leaves trainable)."""
+    opt_lower = args.opt.lower()
+    weight_decay = args.weight_decay
+    flags = model.set_trainable(trainable)
+    if weight_decay and filter_bias_and_bn:
+        parameters = _factory_groups(model, weight_decay, skip_list, get_num_layer, get_layer_scale, trainable)
+        weight_decay = 0.
+    else:
+        parameters = [p for n, p in model.named_parameters() if flags[n]]
+    opt_args = dict(lr=args.lr, weight_decay=weight_decay)
+    if getattr(args, "opt_eps", None) is not None:
+        opt_args["eps"] = args.opt_eps
+    if getattr(args, "opt_betas", None) is not None:
+        opt_args["betas"] = args.opt_betas
+    opt_split = opt_lower.split("_")
+    opt_lower = opt_split[-1]
+    if len(opt_split) > 1:
+        raise NotImplementedError(f"create_optimizer(opt={args.opt!r}): prefixes (lookahead_) are not built; built: {_BUILT_OPTS}")
+    if opt_lower in ("sgd", "nesterov", "momentum"):
+        opt_args.pop("eps", None)
+        if "betas" in opt_args:
+            raise TypeError(f"create_optimizer(opt={args.opt!r}): opt_betas with an SGD optimizer (torch.optim.SGD has no betas)")
+        return FusedTorchSGD(parameters, model.store, momentum=args.momentum, nesterov=opt_lower != "momentum", model=model, **opt_args)
+    if opt_lower == "adamw":
+        if "betas" in opt_args:
+            opt_args["betas"] = tuple(opt_args["betas"])
+        return FusedTorchAdamW(parameters, model.store, model=model, **opt_args)
+    raise NotImplementedError(f"create_optimizer(opt={args.opt!r}) is not built; built: {_BUILT_OPTS}")
+
+
+def _factory_groups(model, weight_decay, skip_list, get_num_layer, get_layer_scale, trainable):
+    """get_parameter_groups (:51-90) as create_optimizer calls it: ``param_groups`` without the two callables (groups ``decay`` /
+    ``no_decay``, lr_scale 1); with them the same rule name by name, layer ids and scales from the callables (a
+    LayerDecayValueAssigner's give the groups of ``param_groups(..., layer_decay)``)"""
+    if get_num_layer is None and get_layer_scale is None:
+        return param_groups(model, weight_decay, 1.0, skip_list=skip_list, trainable=trainable)
+    flags = model.set_trainable(trainable)
+    skip = model.no_weight_decay() if skip_list is None else skip_list
+    groups = {}
+    for name, p in model.named_parameters():
+        if not flags[name]:
+            continue
+        no_decay = p.dim() == 1 or name.endswith(".bias") or name in skip
+        gname, lid = "no_decay" if no_decay else "decay", None
+        if get_num_layer is not None:
+            lid = get_num_layer(name)
+            gname = "layer_%d_%s" % (lid, gname)
+        g = groups.get(gname)
+        if g is None:
+            scale = get_layer_scale(lid) if get_layer_scale is not None else 1.
+            g = groups[gname] = dict(name=gname, weight_decay=0.0 if no_decay else weight_decay, params=[], param_names=[], lr_scale=scale)
         g["params"].append(p)
         g["param_names"].append(name)
     return list(groups.values())
@@ -713,10 +807,11 @@ class ModelEma:
 # ---------------------------------------------------------------------------------------------- the step
 class FinetuneStep:
     """train_one_epoch's loop body (engine_for_finetuning.py:55-123) without DeepSpeed / loss scaler.  ``trainable="head"`` is
-    linear probing: the backward stops behind the head; build the optimizer from ``param_groups(..., trainable="head")``.
+    linear probing: the backward stops behind the head; build the optimizer from ``param_groups(..., trainable="head")`` or
+    ``create_optimizer(args, model, trainable="head")``.  optimizer: FusedTorchAdamW or FusedTorchSGD (the script's probe).
     With more than one rank of torch.distributed it is the data-parallel step (module docstring, "Several GPUs")."""
 
-    def __init__(self, model, optimizer: FusedTorchAdamW, clip_grad=None, update_freq=1, smoothing=0.0, trainable="all",
+    def __init__(self, model, optimizer: "FusedTorchAdamW | FusedTorchSGD", clip_grad=None, update_freq=1, smoothing=0.0, trainable="all",
                  data_parallel=None, payload=None, model_ema=None):
         """model_ema: a ModelEma of this model -- every call that updates then also updates the average, inside the optimizer's
         launch (a call that only accumulates leaves it alone, as the reference's loop does); None: the step without an average.
@@ -766,8 +861,11 @@ class FinetuneStep:
                     [float(g["weight_decay"]) for g in opt.param_groups], self.model.engine.recompute)).encode() + opt.chunk_group.cpu().numpy().tobytes()
         if self.model_ema is not None:  # (appended only with an average: without one the signature is the bytes it was)
             sig += repr(("model_ema", self.model_ema.decay)).encode()
+        if not isinstance(opt, FusedTorchAdamW):  # (appended only for another optimizer: with AdamW the signature is the bytes it was)
+            g0 = opt.param_groups[0]
+            sig += repr((type(opt).__name__, float(g0.get("momentum", 0)), bool(g0.get("nesterov", False)))).encode()
         D.agree(sig, "FinetuneStep: the model size, `trainable`, update_freq, clip_grad, payload, the recomputation mode, the "
-                     "ModelEma (present or not, its decay) or the optimizer's chunk / group table")
+                     "ModelEma (present or not, its decay), the optimizer's kind (its momentum, nesterov) or the optimizer's chunk / group table")
         D.dist.broadcast(st.flat, src=0)
         st.refresh_shadows()
         self.model.mark_shadows_fresh()

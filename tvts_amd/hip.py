@@ -1434,6 +1434,33 @@ def adamw_torch(p, g, m, v, shadow, chunk_group, hyper_dev, step, beta1=0.9, bet
     _chk(rc, "tvts_adamw_torch_ema")
 
 
+def sgd_torch(p, g, buf, shadow, chunk_group, hyper_dev, step, momentum=0.0, nesterov=False, grad_scale=1.0, step_dev=None,
+              norm_coef=None, ema=None, ema_decay=None):
+    """one torch.optim.SGD step (dampening 0) over the flat buffers, bit for bit; hyper_dev: device fp32 lr[64] | wd[64].  buf: the
+    momentum buffer (None with momentum 0: not touched); step == 1 (or step_dev[0] == 1) is the first update, which writes buf
+    without reading it.  ema / ema_decay as adamw_torch (tvts_sgd_torch_ema).  Bytes per stepped element: p 8, g 4, shadow 2,
+    buf 8 (4 on the first update, 0 without momentum), the average 8."""
+    n = chunk_group.numel()
+    assert chunk_group.dtype == torch.uint8
+    assert hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= 128
+    mom = ctypes.c_float(float(momentum)).value != 0.0
+    assert all(t.dtype == torch.float32 and t.numel() >= n * 1024 for t in (p, g) + ((buf,) if buf is not None else ()))
+    assert shadow is None or shadow.numel() >= n * 1024
+    if (ema is None) != (ema_decay is None):
+        raise ValueError("ema_decay without ema" if ema is None else "ema needs ema_decay")
+    per = 14.0 + (8.0 if mom else 0.0) + (0.0 if ema is None else 8.0)
+    args = (_p(p), _p(g), _p(buf), _p(shadow), _p(chunk_group), n, _p(hyper_dev), int(step), _p(step_dev), float(momentum),
+            1 if nesterov else 0, grad_scale, _p(norm_coef))
+    with _hbm("sgd", lambda: per * 1024 * float((chunk_group < 64).sum())):
+        if ema is None:
+            name, rc = "tvts_sgd_torch", _lib.load().tvts_sgd_torch(*args, _stream())
+        else:
+            d32, o32 = ema_pair(ema_decay)
+            assert ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() >= n * 1024 and ema.device == p.device
+            name, rc = "tvts_sgd_torch_ema", _lib.load().tvts_sgd_torch_ema(*args, _p(ema), d32, o32, _stream())
+    _chk(rc, name)
+
+
 def ema_update(ema, p, chunk_group, decay):
     """ModelEma.update as a pass of its own: ema = fl(fl(ema * d32) + fl(o32 * p)) on every 1024-element chunk whose group byte is
     below 64; a chunk of another group (255 = frozen / padding) keeps every bit of ema.  12 B per element."""

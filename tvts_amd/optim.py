@@ -1,12 +1,14 @@
-"""Fused multi-tensor AdamW over the flat parameter store: ``step()`` is ONE kernel launch over the flat buffers.
+"""Fused multi-tensor optimizers over the flat parameter store: ``step()`` is ONE kernel launch over the flat buffers.
 
-``_FlatAdamW`` holds what the two optimizers share (chunk table, moments, state views, device table, step counters, checkpoints).
+``_FlatOptimizer`` holds what all of them share (chunk table, lr / weight_decay device table, step counters, ``_begin`` /
+``_finish``, the shadow refresh); ``_FlatAdamW`` adds what the two AdamWs share (moments, state views, checkpoints).
 
 ``FusedHFAdamW`` replaces ``transformers.AdamW(params=optimizer_grouped_parameters)`` built at
 v2/train_dist_TVTSv2_ViT_B_16.py:118-125 (defaults betas (0.9, 0.999), eps 1e-6, correct_bias=True).
 ``FusedTorchAdamW`` is ``torch.optim.AdamW`` (eps 1e-8) for the v1 fine-tuning step (downstream/finetune_v1.py).
-Both are ``torch.optim.Optimizer``s, so param_groups / state_dict keep the reference checkpoint layout
-(``state[p] = {step, exp_avg, exp_avg_sq}``, views of the flat moments).
+``FusedTorchSGD`` is ``torch.optim.SGD`` (momentum, Nesterov) for the v1 linear probe (v1/scripts/linear_ssv2.sh), bit for bit.
+All are ``torch.optim.Optimizer``s, so param_groups / state_dict keep the reference checkpoint layout
+(AdamW: ``state[p] = {step, exp_avg, exp_avg_sq}``, SGD: ``state[p] = {momentum_buffer}``; views of the flat state buffers).
 
 Gradient handling follows the reference's pinned torch 1.11 ``zero_grad()`` (grads zeroed, not set to
 None): every trainable tensor is updated every step, tensors that received no gradient see g = 0.
@@ -19,10 +21,10 @@ from . import hip as K
 from .engine import CH, ParamStore
 
 
-class _FlatAdamW(torch.optim.Optimizer):
-    """What the fused optimizers share: the moments on the ParamStore, the 1024-element chunk table (group per chunk, 255 = frozen),
-    the ``state[p]`` views, the lr / weight_decay device table and the host / device step counters.  A subclass sets MAX_GROUPS
-    (the width of its kernel's table) and launches its kernel in step()."""
+class _FlatOptimizer(torch.optim.Optimizer):
+    """What the fused optimizers share: the 1024-element chunk table (group per chunk, 255 = frozen), the lr / weight_decay device
+    table and the host / device step counters.  A subclass sets MAX_GROUPS (the width of its kernel's table), allocates its state
+    on the ParamStore (_alloc_state, _init_param), names its per-launch constants (_hyper) and launches its kernel in step()."""
     MAX_GROUPS = 0
 
     def __init__(self, params, defaults, store: ParamStore, model=None):
@@ -32,9 +34,7 @@ class _FlatAdamW(torch.optim.Optimizer):
             raise ValueError(f"the fused kernel supports up to {self.MAX_GROUPS} parameter groups")
         self.store, self.model = store, model
         dev = store.device
-        if store.m is None:
-            store.m = torch.zeros_like(store.flat)
-            store.v = torch.zeros_like(store.flat)
+        self._alloc_state()
         ptr2name = {store.p(n).data_ptr(): n for n in store.shapes}
         table = torch.full((store.total // CH,), 255, dtype=torch.uint8)
         for gi, group in enumerate(self.param_groups):
@@ -44,7 +44,7 @@ class _FlatAdamW(torch.optim.Optimizer):
                     raise ValueError(f"{self._cls} only handles parameters of the flat store")
                 o, n = store.off[name], p.numel()
                 table[o // CH:(o + n + CH - 1) // CH] = gi
-                self.state[p] = dict(step=0, exp_avg=store.m[o:o + n].view(p.shape), exp_avg_sq=store.v[o:o + n].view(p.shape))
+                self._init_param(p, o, n)
         self.chunk_group = table.to(dev)
         self.global_step = 0
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -52,15 +52,21 @@ class _FlatAdamW(torch.optim.Optimizer):
         self._hyper_host = None
         self.grad_scale = 1.0
 
+    def _alloc_state(self):
+        """the flat state buffers this optimizer keeps on the store"""
+        raise NotImplementedError
+
+    def _init_param(self, p, o, n):
+        """state[p] of the parameter at elements [o, o + n) of the flat store"""
+        raise NotImplementedError
+
     def _hyper(self):
-        b1, b2 = self.param_groups[0]["betas"]
-        eps = self.param_groups[0]["eps"]
-        for g in self.param_groups[1:]:  # one kernel launch covers every group: these three cannot differ per group
-            if tuple(g["betas"]) != (b1, b2) or g["eps"] != eps:
-                raise ValueError(f"{self._cls} needs the same betas / eps in every parameter group (lr and weight_decay may differ)")
+        """-> (the per-launch constants ..., lr per group, weight_decay per group), both lists padded to MAX_GROUPS"""
+        raise NotImplementedError
+
+    def _lr_wd(self):
         pad = [0.0] * (self.MAX_GROUPS - len(self.param_groups))
-        return (b1, b2, eps, [float(g["lr"]) for g in self.param_groups] + pad,
-                [float(g["weight_decay"]) for g in self.param_groups] + pad)
+        return [float(g["lr"]) for g in self.param_groups] + pad, [float(g["weight_decay"]) for g in self.param_groups] + pad
 
     def sync_hyper(self):
         """Upload lr / weight_decay of the parameter groups to the device table.  When a captured hipGraph is REPLAYED, call it
@@ -70,6 +76,54 @@ class _FlatAdamW(torch.optim.Optimizer):
         if self._hyper_host != (lr, wd):
             self.hyper_dev.copy_(torch.tensor(lr + wd, dtype=torch.float32), non_blocking=False)
             self._hyper_host = (lr, wd)
+
+    def zero_grad(self, set_to_none: bool = False):
+        K.zero_(self.store.grad)
+
+    def _begin(self, device_step: bool):
+        """counters of a new optimizer step (once per step, in front of its first launch) -> _hyper()"""
+        hp = self._hyper()
+        lr, wd = hp[-2:]
+        capturing = torch.cuda.is_current_stream_capturing()
+        if device_step and not capturing:
+            self.sync_hyper()  # (a host -> device copy: not capturable; the caller syncs before capture / replay)
+        elif device_step and self._hyper_host != (lr, wd):
+            raise RuntimeError(f"{self._cls}: call sync_hyper() (or run one eager device_step) before capturing the step")
+        self.global_step += 1
+        if device_step:
+            self.step_dev.add_(1)
+        else:
+            self.step_dev.fill_(self.global_step)  # keeps the device counter in step when eager and captured steps mix
+        return hp
+
+    def _finish(self, device_step: bool, transposed: bool = True):
+        """behind the step's last launch: the shadows the kernel does not write"""
+        self.store.refresh_shadows(cast=False, transposed=transposed)
+        if self.model is not None:
+            self.model.mark_shadows_fresh()
+
+
+class _FlatAdamW(_FlatOptimizer):
+    """What the fused AdamWs share: the moments on the ParamStore, the ``state[p]`` views with their step fields, checkpoints."""
+
+    def _alloc_state(self):
+        store = self.store
+        if store.m is None:
+            store.m = torch.zeros_like(store.flat)
+        if store.v is None:
+            store.v = torch.zeros_like(store.flat)
+
+    def _init_param(self, p, o, n):
+        store = self.store
+        self.state[p] = dict(step=0, exp_avg=store.m[o:o + n].view(p.shape), exp_avg_sq=store.v[o:o + n].view(p.shape))
+
+    def _hyper(self):
+        b1, b2 = self.param_groups[0]["betas"]
+        eps = self.param_groups[0]["eps"]
+        for g in self.param_groups[1:]:  # one kernel launch covers every group: these three cannot differ per group
+            if tuple(g["betas"]) != (b1, b2) or g["eps"] != eps:
+                raise ValueError(f"{self._cls} needs the same betas / eps in every parameter group (lr and weight_decay may differ)")
+        return (b1, b2, eps, *self._lr_wd())
 
     def _sync_step_from_device(self):
         """Under hipGraph replay the host counters only advance at capture time: re-read the device counter."""
@@ -83,29 +137,9 @@ class _FlatAdamW(torch.optim.Optimizer):
         self._sync_step_from_device()
         return super().state_dict()
 
-    def zero_grad(self, set_to_none: bool = False):
-        K.zero_(self.store.grad)
-
-    def _begin(self, device_step: bool):
-        """counters of a new optimizer step (once per step, in front of its first launch)"""
-        b1, b2, eps, lr, wd = self._hyper()
-        capturing = torch.cuda.is_current_stream_capturing()
-        if device_step and not capturing:
-            self.sync_hyper()  # (a host -> device copy: not capturable; the caller syncs before capture / replay)
-        elif device_step and self._hyper_host != (lr, wd):
-            raise RuntimeError(f"{self._cls}: call sync_hyper() (or run one eager device_step) before capturing the step")
-        self.global_step += 1
-        if device_step:
-            self.step_dev.add_(1)
-        else:
-            self.step_dev.fill_(self.global_step)  # keeps the device counter in step when eager and captured steps mix
-        return b1, b2, eps, lr, wd
-
     def _finish(self, device_step: bool, transposed: bool = True):
-        """behind the step's last launch: the shadows the kernel does not write, and the per-parameter step fields"""
-        self.store.refresh_shadows(cast=False, transposed=transposed)
-        if self.model is not None:
-            self.model.mark_shadows_fresh()
+        """the shadows, and the per-parameter step fields"""
+        super()._finish(device_step, transposed)
         if not device_step:
             for st in self.state.values():
                 st["step"] = self.global_step
@@ -224,3 +258,123 @@ class FusedTorchAdamW(_FlatAdamW):
         K.adamw_torch(st.flat, st.grad, st.m, st.v, st.shadow, self.chunk_group, self.hyper_dev, self.global_step, b1, b2, eps,
                       self.grad_scale, step_dev=self.step_dev if device_step else None, norm_coef=self.norm_coef, **ema)
         self._finish(device_step)
+
+
+class FusedTorchSGD(_FlatOptimizer):
+    """``torch.optim.SGD`` (single-tensor form, dampening 0) as ONE launch over the flat store, bit for bit, for up to 64 parameter
+    groups: the optimizer optim_factory.create_optimizer builds for ``sgd`` / ``nesterov`` (nesterov=True) and ``momentum``
+    (optim_factory.py:121-126) -- v1/scripts/linear_ssv2.sh trains the probe with ``--opt sgd --lr 0.1 --momentum 0.9
+    --weight_decay 1e-9``.  Constructor as torch's; refused: dampening != 0, maximize, foreach=True, fused=True, differentiable,
+    and nesterov without momentum (torch refuses that too).  lr / weight_decay travel per group in the device table lr[64] |
+    wd[64]; momentum / nesterov / dampening are one value per launch and must agree across the groups.  The momentum buffer is
+    ``store.m`` (no ``store.v``; with momentum 0 no state at all), ``state[p] = {"momentum_buffer": view of store.m}`` once the
+    first update has run, as torch fills it.  The first update (buf = d, the bits of d) is decided for the whole store by the step
+    counter: under this project's zero-gradient convention every trainable tensor is updated every step, so torch's per-parameter
+    ``buf is None`` is the same rule.  ``norm_coef`` / ``ema`` / ``grad_scale`` as FusedTorchAdamW (the average: tvts_sgd_torch_ema)."""
+    MAX_GROUPS = 64
+
+    def __init__(self, params, store: ParamStore, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *,
+                 maximize=False, foreach=None, differentiable=False, fused=None, model=None):
+        if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
+            raise ValueError(f"FusedTorchSGD: lr {lr}, momentum {momentum} and weight_decay {weight_decay} must not be negative")
+        for what, bad in (("dampening != 0", dampening != 0), ("maximize=True", bool(maximize)), ("foreach=True", bool(foreach)),
+                          ("fused=True", bool(fused)), ("differentiable=True", bool(differentiable))):
+            if bad:
+                raise NotImplementedError(f"FusedTorchSGD({what}) is not built")
+        if nesterov and momentum <= 0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                        maximize=maximize, foreach=foreach, differentiable=differentiable, fused=fused)
+        super().__init__(params, defaults, store, model)
+        self._hyper()
+        self.norm_coef = None
+        self.ema = None
+
+    def _alloc_state(self):
+        if self.defaults["momentum"] != 0 and self.store.m is None:
+            self.store.m = torch.zeros_like(self.store.flat)
+
+    def _init_param(self, p, o, n):
+        pass  # (torch.optim.SGD has no state in front of its first update)
+
+    def _buffers(self):
+        """state[p] = {"momentum_buffer": view of store.m} for every parameter, as torch holds it behind an update"""
+        st = self.store
+        if self.defaults["momentum"] == 0 or len(self.state):
+            return
+        ptr2name = {st.p(n).data_ptr(): n for n in st.shapes}
+        for group in self.param_groups:
+            for p in group["params"]:
+                o = st.off[ptr2name[p.data_ptr()]]
+                self.state[p] = dict(momentum_buffer=st.m[o:o + p.numel()].view(p.shape))
+
+    def _hyper(self):
+        g0 = self.param_groups[0]
+        mu, nes = float(g0["momentum"]), bool(g0["nesterov"])
+        for g in self.param_groups:  # one kernel launch covers every group: these cannot differ per group
+            if float(g["momentum"]) != mu or bool(g["nesterov"]) != nes:
+                raise ValueError(f"{self._cls} needs the same momentum / nesterov in every parameter group (lr and weight_decay may differ)")
+            if g["dampening"] != 0 or g["maximize"] or g["foreach"] or g["fused"] or g["differentiable"]:
+                raise NotImplementedError(f"{self._cls}: dampening / maximize / foreach / fused / differentiable are not built")
+        if (mu != 0) != (self.defaults["momentum"] != 0):
+            raise ValueError(f"{self._cls}: momentum cannot be switched on or off after construction (the buffer is allocated there)")
+        if nes and mu <= 0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        return (mu, nes, *self._lr_wd())
+
+    @torch.no_grad()
+    def step(self, closure=None, device_step: bool = False):
+        """device_step=True: the step counter the kernel reads lives in device memory (same bits as the host counter)"""
+        self.sync_hyper()
+        mu, nes, _, _ = self._begin(device_step)
+        st = self.store
+        ema = {} if self.ema is None else dict(ema=self.ema[0], ema_decay=self.ema[1])
+        K.sgd_torch(st.flat, st.grad, st.m if mu != 0 else None, st.shadow, self.chunk_group, self.hyper_dev, self.global_step,
+                    momentum=mu, nesterov=nes, grad_scale=self.grad_scale, step_dev=self.step_dev if device_step else None,
+                    norm_coef=self.norm_coef, **ema)
+        self._buffers()
+        self._finish(device_step)
+
+    def state_dict(self):
+        st = int(self.step_dev.item())  # (under hipGraph replay the host counter only advances at capture time)
+        if st > self.global_step:
+            self.global_step = st
+        if self.global_step > 0:
+            self._buffers()
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        """Accepts torch.optim.SGD's layout, state keyed by the running parameter index.  Buffers present: the next update is not
+        a first one; an empty state: it is.  Some parameters with and some without a buffer: ValueError (the first-update rule
+        is one decision for the whole store)."""
+        sd_groups, sd_state = state_dict["param_groups"], state_dict["state"]
+        if len(sd_groups) != len(self.param_groups) or any(len(g["params"]) != len(sg["params"])
+                                                           for g, sg in zip(self.param_groups, sd_groups)):
+            raise ValueError("loaded state dict has other parameter groups than this optimizer")
+        pairs = [(p, sd_state.get(idx)) for g, sg in zip(self.param_groups, sd_groups) for p, idx in zip(g["params"], sg["params"])]
+        have = [s is not None and s.get("momentum_buffer") is not None for _, s in pairs]
+        if any(have) and not all(have):
+            raise ValueError(f"{self._cls}.load_state_dict: {sum(have)} of {len(have)} parameters carry a momentum_buffer; all or none")
+        kept = [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]
+        for g, sg in zip(self.param_groups, sd_groups):
+            for k, v in sg.items():
+                if k != "params":
+                    g[k] = v
+        try:
+            mu = self._hyper()[0]
+            if any(have) and mu == 0:
+                raise ValueError(f"{self._cls}.load_state_dict: momentum buffers for an optimizer with momentum 0")
+        except Exception:
+            for g, k in zip(self.param_groups, kept):
+                g.update(k)
+            raise
+        if any(have):
+            self.state.clear()
+            self._buffers()
+            for p, s in pairs:
+                self.state[p]["momentum_buffer"].copy_(s["momentum_buffer"])
+            self.global_step = max(self.global_step, 1)
+        else:
+            self.state.clear()
+            self.global_step = 0
+        self.step_dev.fill_(self.global_step)
