@@ -757,6 +757,21 @@ int tvts_sgd_torch(float* p, const float* g, float* buf, void* shadow_bf16, cons
 int tvts_sgd_torch_ema(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
                        const float* hyper_dev, int step, const int* step_dev, double momentum, int nesterov, float grad_scale,
                        const float* norm_coef, float* ema, float d32, float o32, hipStream_t stream);
+/* The overflow guard of the v1 fine-tuning step (GradScaler's "skip the update on inf / NaN", decided on the device):
+ * tvts_adamw_torch[_ema] / tvts_sgd_torch[_ema] whose update happens only when norm_coef[0] -- the global norm tvts_grad_sumsq left
+ * in device memory, formed over the trainable chunks -- is finite.  Finite: step_dev[0] += 1 first, then the unguarded update with
+ * that step count, bit for bit.  Not finite: every bit of p, m, v (buf), the shadow and the average is kept, step_dev[0] stays and
+ * the device int64 skipped[0] += 1.  The step counter lives on the device only (no `step` argument); norm_coef is required;
+ * ema == null: the launch without an average.  -22: a null pointer (shadow, ema and -- with momentum 0 -- buf may be null),
+ * nchunks <= 0, nesterov with momentum == 0, p / g / m / v / buf / ema not 16-byte aligned, shadow / skipped not 8, step_dev /
+ * norm_coef not 4. */
+int tvts_adamw_torch_guard(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group,
+                           int nchunks, const float* hyper_dev, int* step_dev, double beta1, double beta2, double eps,
+                           float grad_scale, const float* norm_coef, long* skipped, float* ema, float d32, float o32,
+                           hipStream_t stream);
+int tvts_sgd_torch_guard(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
+                         const float* hyper_dev, int* step_dev, double momentum, int nesterov, float grad_scale,
+                         const float* norm_coef, long* skipped, float* ema, float d32, float o32, hipStream_t stream);
 /* a[i] <-> b[i] in place and shadow_bf16[i] = bf16(new a[i]) for i < n; n % 4 == 0, a and b disjoint and 16-byte aligned (-22).
  * ModelEma.applied(): the masters and the average change places without a third buffer. */
 int tvts_swap_f32_shadow(float* a, float* b, void* shadow_bf16, long n, hipStream_t stream);

@@ -54,6 +54,12 @@ then under SGD (probe: lr 0.1, weight_decay 1e-9 as v1/scripts/linear_ssv2.sh; f
 0.05).  The line's "summary" gives, per setting, the SGD step over the AdamW step of the same round beside the spread of the
 AdamW rounds (max / min - 1): a difference inside that spread is not a measured difference.
 
+--guard {off,on,both} (default off: the run and its output as before; the plain step only).  on: FinetuneStep(skip_nonfinite=True),
+the overflow guard (tvts_adamw_torch_guard: one more single-lane launch, one uniform load and a branch per chunk).  both: the
+guarded beside the unguarded step in the SAME process, three rounds, each timing trainable = "all" and "head" without and then
+with the guard; the line's "summary" gives the guarded step over the unguarded step of the same round beside the spread of the
+unguarded rounds (max / min - 1): a difference inside that spread is not a measured difference.
+
 --gpus N: the data-parallel step, one process per GPU -- `python -m torch.distributed.run --nproc-per-node N tools/bench_finetune.py
 --gpus N --batch 8 --num-sample 2` (N = 1 also runs as a plain process, without a process group).  Every rank runs the default
 recipe's step on its own --batch samples (--aug device, --mixup device, --randaug device; per-rank draws seeded seed + rank as the
@@ -95,6 +101,8 @@ def make(trainable, args, **step_kw):
         args.model_ema = ModelEma(m, decay=0.9999)
         if ema == "fused":
             step_kw["model_ema"] = args.model_ema
+    if getattr(args, "guard_on", False):
+        step_kw["skip_nonfinite"] = True
     return m, FinetuneStep(m, opt, clip_grad=5.0, trainable=trainable, **step_kw), len(groups)
 
 
@@ -444,7 +452,11 @@ def main():
     ap.add_argument("--randaug", choices=("off", "device", "host"), default="off", help="RandAugment in front of the crop (--aug device)")
     ap.add_argument("--ema", choices=("off", "fused", "separate"), default="off", help="ModelEma: in the optimizer's launch, or update() behind the step")
     ap.add_argument("--opt", choices=("adamw", "sgd"), default="adamw", help="sgd: FusedTorchSGD beside FusedTorchAdamW in the same run, three rounds")
+    ap.add_argument("--guard", choices=("off", "on", "both"), default="off", help="skip_nonfinite: on, or both: guarded beside unguarded, three rounds")
     args = ap.parse_args()
+    if args.guard != "off" and (args.gpus or args.mixup != "off" or args.aug != "off" or args.ema != "off" or args.u8 or args.opt != "adamw"):
+        raise SystemExit("--guard on / both: the plain step only (without --gpus, --mixup, --aug, --ema, --u8, --opt sgd)")
+    args.guard_on = args.guard == "on"
     if args.opt != "adamw" and (args.gpus or args.mixup != "off" or args.aug != "off" or args.ema != "off" or args.u8):
         raise SystemExit("--opt sgd: the plain step only (without --gpus, --mixup, --aug, --ema, --u8)")
     if args.ema != "off" and (args.gpus or args.mixup != "off" or args.aug != "off"):
@@ -516,6 +528,28 @@ def main():
         out["summary"] = summary
         print(json.dumps(out), flush=True)
         return
+    if args.guard == "both":
+        rounds = []
+        for _ in range(3):
+            rnd = {}
+            for kind in ("off", "on"):
+                args.guard_on = kind == "on"
+                rnd[kind] = {"trainable=" + t: run(t, args, clip, targets) for t in ("all", "head")}
+            rounds.append(rnd)
+        out["guard"] = {"off": "FinetuneStep (tvts_adamw_torch)", "on": "FinetuneStep(skip_nonfinite=True) (tvts_adamw_torch_guard)"}
+        out["rounds"] = rounds
+        summary = {}
+        for t in ("trainable=all", "trainable=head"):
+            off = [r["off"][t]["step ms"] for r in rounds]
+            on = [r["on"][t]["step ms"] for r in rounds]
+            summary[t] = {"unguarded step ms by round": off, "guarded step ms by round": on,
+                          "guarded / unguarded by round": [b / a for a, b in zip(off, on)],
+                          "spread of the unguarded rounds (max / min - 1)": max(off) / min(off) - 1.0}
+        out["summary"] = summary
+        print(json.dumps(out), flush=True)
+        return
+    if args.guard == "on":
+        out["guard"] = "on"
     for trainable in ("all", "head") if args.mixup == "off" else ("all",):
         out["trainable=" + trainable] = run(trainable, args, clip, targets)
     print(json.dumps(out), flush=True)

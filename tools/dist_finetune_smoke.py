@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Two data-parallel ranks of the v1 fine-tuning step and of the evaluation merges on ONE GPU (gloo moving device tensors, the
 pattern of tools/dist_smoke.py): FinetuneStep's gradient exchange, validation_one_epoch's meter merge and ViewMerger.gather.
-usage: python tools/dist_finetune_smoke.py [--ema] [--opt {adamw,sgd}] [check ...]      (no argument: every check, in one pair of processes)
+usage: python tools/dist_finetune_smoke.py [--ema] [--guard] [--opt {adamw,sgd}] [check ...]      (no argument: every check, in one pair of processes)
 checks: identical distinct replicas travel bf16 start mismatch seeds validation merge
 --opt sgd: the same checks with FusedTorchSGD (lr 0.1, momentum 0.9, Nesterov: torch.optim.SGD as the linear-probe script builds it)
 in place of FusedTorchAdamW -- all but `bf16`, whose bound is derived for AdamW's first step -- and the check `optimizers` behind
 them: a rank built with AdamW beside a rank built with SGD, both raise.
 --ema: the check `ema` behind the named ones (alone when none is named; not part of "every check") -- a ModelEma made BEFORE the
 step object on ranks that start from different weights, both ranks' ModelEma.checksum() after _join and after two updating steps.
+--guard: the check `guard` behind the named ones (alone when none is named; not part of "every check") -- FinetuneStep(
+skip_nonfinite=True) on both ranks, a NaN pixel in rank 1's shard only on call 2 of 3: both ranks skip that update, count it, and
+hold equal, finite replicas after every call; a guarded rank beside an unguarded one raises on both.
 The model is tests/v1_downstream_synth.TINY; the gates are the test suite's own (tests/kernel_bounds.py, check_grads of
 tests/test_v1_gpu.py), imported from tests/.  Prints DIST_FINETUNE_OK when every rank passed every check."""
 import math
@@ -19,7 +22,7 @@ import traceback
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHECKS = ("identical", "distinct", "replicas", "travel", "bf16", "start", "mismatch", "seeds", "validation", "merge")
-OPTIONAL = ("ema", "optimizers")  # checks a flag asks for
+OPTIONAL = ("ema", "optimizers", "guard")  # checks a flag asks for
 ADAMW_ONLY = ("bf16",)  # (its bound is AdamW's first step)
 SGD_LR, SGD_MOMENTUM = 0.1, 0.9
 DEV, CLASSES, T, LR, WD, LAYER_DECAY, CH = "cuda:0", 5, 4, 1e-3, 0.05, 0.75, 1024
@@ -522,6 +525,44 @@ def check_optimizers(c):
     assert float(t) == c.world
 
 
+# ================================================================================================ 11. the overflow guard (--guard)
+def check_guard(c):
+    """the decision is taken behind the all-reduce, so a NaN in ONE rank's shard skips the update on EVERY rank, with no
+    collective of its own; ranks that disagree about skip_nonfinite raise from the agreement"""
+    torch = c.torch
+    m = c.model()
+    step, opt = c.stepper(m, clip_grad=1.0, skip_nonfinite=True)
+    start = int(step.replicas_checksum())
+    sums = []
+    for k in range(3):
+        clip = c.clips(2, 700 + 10 * k + c.rank)
+        if k == 1 and c.rank == 1:
+            clip[0, 1, 2, 3, 4] = float("nan")
+        before = int(step.replicas_checksum())
+        out = step.step(clip, c.labels(2, 800 + 10 * k + c.rank))
+        c.all_equal(step.replicas_checksum().reshape(1), f"replicas_checksum after call {k + 1}")
+        c.all_equal(out["grad_norm"].reshape(1), f"grad_norm of call {k + 1}")
+        now = int(step.replicas_checksum())
+        assert math.isfinite(float(out["grad_norm"])) == (k != 1) and (now == before) == (k == 1), (k, float(out["grad_norm"]), now, before)
+        sums.append(now)
+    c.all_equal(step.skipped, "the skip counter")
+    state = torch.stack([bitsum(c, t) for t in (m.store.flat, m.store.m, m.store.v) if t is not None])
+    c.all_equal(state, "parameters and optimizer state after 3 calls")
+    assert bool(torch.isfinite(m.store.flat).all()) and bool(torch.isfinite(m.store.m).all()) and sums[-1] != start
+    assert int(step.skipped.item()) == 1 and int(opt.step_dev.item()) == 2
+    c.say(f"guard: skipped {int(step.skipped.item())}, replicas equal after every call, finite state at the end")
+    try:
+        c.stepper(c.model(), skip_nonfinite=c.rank == 0)
+    except RuntimeError as e:
+        assert "differs between the ranks" in str(e) and "skip_nonfinite" in str(e), str(e)
+        c.say("GUARD_MISMATCH_RAISED")
+    else:
+        raise AssertionError("a guarded rank beside an unguarded one was accepted")
+    t = torch.ones(1, device=DEV)
+    c.dist.all_reduce(t)  # the group is still usable
+    assert float(t) == c.world
+
+
 # ================================================================================================ driver
 def worker(rank, world, port, checks, q, opt="adamw"):
     try:
@@ -551,6 +592,7 @@ def worker(rank, world, port, checks, q, opt="adamw"):
 
 def main(argv):
     with_ema, argv = "--ema" in argv, [a for a in argv if a != "--ema"]
+    with_guard, argv = "--guard" in argv, [a for a in argv if a != "--guard"]
     opt = "adamw"
     if "--opt" in argv:
         i = argv.index("--opt")
@@ -559,6 +601,8 @@ def main(argv):
         opt, argv = argv[i + 1], argv[:i] + argv[i + 2:]
     every = list(CHECKS) if opt == "adamw" else [n for n in CHECKS if n not in ADAMW_ONLY] + ["optimizers"]
     checks = argv + ["ema"] if with_ema else argv or every
+    if with_guard:
+        checks = (argv + ["ema"] if with_ema else argv) + ["guard"]
     bad = [n for n in checks if n not in CHECKS + OPTIONAL]
     if bad:
         raise SystemExit(f"unknown check {bad}: one of {CHECKS}")

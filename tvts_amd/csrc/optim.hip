@@ -11,6 +11,9 @@
 //                        fp32 stream, 38 B per element); tvts_ema_update is the rule as a pass of its own (ModelEma.update)
 //   tvts_sgd_torch       torch.optim.SGD (momentum, Nesterov) in the same chunk frame with ONE state stream, bit for bit (the v1 linear
 //                        probe, 22 B per element); tvts_sgd_torch_ema carries the average as tvts_adamw_torch_ema does
+//   tvts_adamw_torch_guard / tvts_sgd_torch_guard   the four launches above under the overflow guard of the fine-tuning step: the update
+//                        happens only when the global gradient norm tvts_grad_sumsq left on the device is finite; else every bit of
+//                        p / m / v / shadow / average stays, the device step counter stays and a device counter of skips advances
 //   tvts_swap_f32_shadow in-place exchange of two fp32 buffers + the bf16 shadow of the first (evaluation from the average)
 //   tvts_cast_f32_bf16   shadow refresh when an external optimizer owned the update (drop-in path)
 //   tvts_transpose_bf16_batched   [N,K] -> [K,N] copies of every GEMM weight (dgrad operand), one launch
@@ -35,14 +38,21 @@ __device__ __forceinline__ f32x4 ema_rule4(const f32x4& ev, const f32x4& pv, flo
 // chunk is known to step (its group byte is below NGROUPS; a foreign group, 255 = frozen, keeps every bit) and returns the rule
 // that updates four elements of p / m / v from their gradients; the frame loads, stores and writes the bf16 shadow.  EMA: the
 // frame also carries the chunk's average through ema_rule4 from the final p (a compile-time choice: the instantiations without
-// an average are the code they were).
-template <int NGROUPS, bool EMA = false, typename Prologue>
+// an average are the code they were).  GUARD (compile time as well, tvts_adamw_torch_guard): the frame first tests the global
+// gradient norm `guard_norm[0]` -- one uniform load and one branch per block -- and a block that finds it not finite returns in
+// front of every load of p / m / v: the whole launch then keeps every bit of p, m, v, the shadow and the average.
+__device__ __forceinline__ bool finite_f32(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+template <int NGROUPS, bool EMA = false, bool GUARD = false, typename Prologue>
 __device__ __forceinline__ void adamw_chunk(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                             float* __restrict__ v, bf16* __restrict__ shadow,
                                             const unsigned char* __restrict__ chunk_group, Prologue prologue,
-                                            float* __restrict__ ema = nullptr, float d32 = 0.f, float o32 = 0.f) {
+                                            float* __restrict__ ema = nullptr, float d32 = 0.f, float o32 = 0.f,
+                                            const float* __restrict__ guard_norm = nullptr) {
     const int grp = chunk_group[blockIdx.x];
     if (grp >= NGROUPS) return;
+    if constexpr (GUARD) {
+        if (!finite_f32(guard_norm[0])) return;
+    }
     const auto update4 = prologue(grp);
     const size_t i = (size_t)blockIdx.x * 1024 + threadIdx.x * 4;
     f32x4 pv = *(f32x4*)(p + i), mv = *(f32x4*)(m + i), vv = *(f32x4*)(v + i);
@@ -123,7 +133,7 @@ extern "C" int tvts_adamw_hf(float* p, const float* g, float* m, float* v, void*
 // tvts_grad_sumsq left in device memory; no coefficient when norm_coef is null).  hyper_dev: lr[64] | wd[64] in device memory.
 // Chunk table as tvts_adamw_hf (1024 elements per chunk, one group byte each); a chunk of group >= 64 (255 = frozen) keeps every bit.
 // (one body, two kernels: the kernel without an average keeps its name, its arguments and its code)
-template <bool EMA>
+template <bool EMA, bool GUARD = false>
 __device__ __forceinline__ void adamw_torch_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                  float* __restrict__ v, bf16* __restrict__ shadow,
                                                  const unsigned char* __restrict__ chunk_group,
@@ -132,7 +142,7 @@ __device__ __forceinline__ void adamw_torch_body(float* __restrict__ p, const fl
                                                  float beta2, float omb1, float omb2, float eps, float grad_scale,
                                                  const float* __restrict__ norm_coef, float* __restrict__ ema, float d32, float o32) {
 #pragma clang fp contract(off)  // (lexical: it holds inside both lambdas; adamw_kernel has none and keeps its contractions)
-    adamw_chunk<64, EMA>(p, g, m, v, shadow, chunk_group, [&](int grp) {
+    adamw_chunk<64, EMA, GUARD>(p, g, m, v, shadow, chunk_group, [&](int grp) {
         const float lr = hyper_dev[grp], wd = hyper_dev[64 + grp];
         const double st = (double)(step_dev ? step_dev[0] : step);
         const double bc1 = 1.0 - pow(beta1d, st), bc2 = 1.0 - pow(beta2d, st);
@@ -149,7 +159,7 @@ __device__ __forceinline__ void adamw_torch_body(float* __restrict__ p, const fl
                 pv[e] -= ss * mv[e] / (sqrtf(vv[e]) / rs + eps);
             }
         };
-    }, ema, d32, o32);
+    }, ema, d32, o32, norm_coef);
 }
 __global__ __launch_bounds__(256) void adamw_torch_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                           float* __restrict__ v, bf16* __restrict__ shadow,
@@ -197,6 +207,51 @@ extern "C" int tvts_adamw_torch_ema(float* p, const float* g, float* m, float* v
     return TVTS_OK;
 }
 
+// ---- the overflow guard of the v1 fine-tuning step (FinetuneStep(skip_nonfinite=True)): GradScaler's "skip the update on inf / NaN"
+// decided on the device.  The decision is isfinite(norm_coef[0]), the global norm tvts_grad_sumsq left in device memory.  Two
+// launches: guard_advance_kernel (one lane) advances step_dev[0] on a finite norm and skipped[0] otherwise, then the guarded
+// instantiation of the chunk frame runs -- with the step counter it would have had unguarded, or returning in every block.  A skipped
+// call leaves step_dev where it was: the bias corrections and SGD's first-update rule go on as if step() had not been called.
+__global__ void guard_advance_kernel(const float* __restrict__ norm_coef, int* __restrict__ step_dev, long* __restrict__ skipped) {
+    if (finite_f32(norm_coef[0])) step_dev[0] += 1;
+    else skipped[0] += 1;
+}
+template <bool EMA>
+__global__ __launch_bounds__(256) void adamw_torch_guard_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                float* __restrict__ v, bf16* __restrict__ shadow,
+                                                                const unsigned char* __restrict__ chunk_group,
+                                                                const float* __restrict__ hyper_dev, const int* __restrict__ step_dev,
+                                                                double beta1d, double beta2d, float beta1, float beta2, float omb1,
+                                                                float omb2, float eps, float grad_scale,
+                                                                const float* __restrict__ norm_coef, float* __restrict__ ema, float d32,
+                                                                float o32) {
+    adamw_torch_body<EMA, true>(p, g, m, v, shadow, chunk_group, hyper_dev, 0, step_dev, beta1d, beta2d, beta1, beta2, omb1, omb2, eps,
+                                grad_scale, norm_coef, ema, d32, o32);
+}
+static inline bool guard_args_bad(const int* step_dev, const float* norm_coef, const long* skipped) {
+    return !step_dev || !norm_coef || !skipped || ((uintptr_t)step_dev & 3) || ((uintptr_t)norm_coef & 3) || ((uintptr_t)skipped & 7);
+}
+extern "C" int tvts_adamw_torch_guard(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group,
+                                      int nchunks, const float* hyper_dev, int* step_dev, double beta1, double beta2, double eps,
+                                      float grad_scale, const float* norm_coef, long* skipped, float* ema, float d32, float o32,
+                                      hipStream_t stream) {
+    if (!p || !g || !m || !v || !chunk_group || !hyper_dev || nchunks <= 0 || guard_args_bad(step_dev, norm_coef, skipped))
+        return TVTS_EINVAL;
+    if (misaligned16(p) || misaligned16(g) || misaligned16(m) || misaligned16(v) || misaligned16(ema) ||
+        ((uintptr_t)shadow_bf16 & 7)) return TVTS_EINVAL;
+    hipLaunchKernelGGL(guard_advance_kernel, dim3(1), dim3(1), 0, stream, norm_coef, step_dev, skipped);
+    if (ema)
+        hipLaunchKernelGGL(adamw_torch_guard_kernel<true>, dim3(nchunks), dim3(256), 0, stream, p, g, m, v, (bf16*)shadow_bf16,
+                           chunk_group, hyper_dev, step_dev, beta1, beta2, (float)beta1, (float)beta2, (float)(1.0 - beta1),
+                           (float)(1.0 - beta2), (float)eps, grad_scale, norm_coef, ema, d32, o32);
+    else
+        hipLaunchKernelGGL(adamw_torch_guard_kernel<false>, dim3(nchunks), dim3(256), 0, stream, p, g, m, v, (bf16*)shadow_bf16,
+                           chunk_group, hyper_dev, step_dev, beta1, beta2, (float)beta1, (float)beta2, (float)(1.0 - beta1),
+                           (float)(1.0 - beta2), (float)eps, grad_scale, norm_coef, nullptr, 0.f, 0.f);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
 // ModelEma.update as a pass of its own (12 B per element): the chunk gate of tvts_adamw_torch (a chunk of group >= 64, 255 =
 // frozen / padding, keeps every bit of its average) and the rule of the fused launch.
 __global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p,
@@ -225,7 +280,7 @@ extern "C" int tvts_ema_update(float* ema, const float* p, const unsigned char* 
 // The step counter (step_dev[0] when given, else `step`: the same device code) only says whether this is the first update, t == 1:
 // buf is then written and not read.  MOM = false (momentum 0): buf is neither read nor written.  A sibling of adamw_chunk with one
 // state stream instead of two: the same chunk gate, the same 16-byte accesses, the shadow and the average as there.
-template <bool MOM, bool EMA>
+template <bool MOM, bool EMA, bool GUARD = false>
 __device__ __forceinline__ void sgd_torch_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
                                                bf16* __restrict__ shadow, const unsigned char* __restrict__ chunk_group,
                                                const float* __restrict__ hyper_dev, int step, const int* __restrict__ step_dev,
@@ -234,6 +289,9 @@ __device__ __forceinline__ void sgd_torch_body(float* __restrict__ p, const floa
 #pragma clang fp contract(off)  // (the FMAs below are explicit calls; fl(mu * buf) + d must stay two roundings)
     const int grp = chunk_group[blockIdx.x];
     if (grp >= 64) return;
+    if constexpr (GUARD) {  // (as adamw_chunk: the norm's own pointer, one uniform load, in front of every load of p / buf)
+        if (!finite_f32(norm_coef[0])) return;
+    }
     const float lr = hyper_dev[grp], wd = hyper_dev[64 + grp];
     const bool first = (step_dev ? step_dev[0] : step) == 1;
     const float gs = norm_coef ? grad_scale * norm_coef[1] : grad_scale;
@@ -275,6 +333,16 @@ __global__ __launch_bounds__(256) void sgd_torch_kernel(float* __restrict__ p, c
     sgd_torch_body<MOM, EMA>(p, g, buf, shadow, chunk_group, hyper_dev, step, step_dev, mu, nesterov, grad_scale, norm_coef, ema, d32,
                              o32);
 }
+template <bool MOM, bool EMA>
+__global__ __launch_bounds__(256) void sgd_torch_guard_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                              bf16* __restrict__ shadow, const unsigned char* __restrict__ chunk_group,
+                                                              const float* __restrict__ hyper_dev, const int* __restrict__ step_dev,
+                                                              float mu, int nesterov, float grad_scale,
+                                                              const float* __restrict__ norm_coef, float* __restrict__ ema, float d32,
+                                                              float o32) {
+    sgd_torch_body<MOM, EMA, true>(p, g, buf, shadow, chunk_group, hyper_dev, 0, step_dev, mu, nesterov, grad_scale, norm_coef, ema,
+                                   d32, o32);
+}
 template <bool EMA>
 static int sgd_torch_launch(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
                             const float* hyper_dev, int step, const int* step_dev, double momentum, int nesterov, float grad_scale,
@@ -306,6 +374,34 @@ extern "C" int tvts_sgd_torch_ema(float* p, const float* g, float* buf, void* sh
                                   float grad_scale, const float* norm_coef, float* ema, float d32, float o32, hipStream_t stream) {
     return sgd_torch_launch<true>(p, g, buf, shadow_bf16, chunk_group, nchunks, hyper_dev, step, step_dev, momentum, nesterov,
                                   grad_scale, norm_coef, ema, d32, o32, stream);
+}
+// tvts_sgd_torch under the overflow guard (see tvts_adamw_torch_guard): guard_advance_kernel, then the guarded frame.  A skipped
+// call 1 leaves step_dev at 0, so the next call is the first update and writes the buffer without reading it.
+template <bool MOM, bool EMA>
+static void sgd_torch_guard_go(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
+                               const float* hyper_dev, const int* step_dev, float mu, int nesterov, float grad_scale,
+                               const float* norm_coef, float* ema, float d32, float o32, hipStream_t stream) {
+    hipLaunchKernelGGL((sgd_torch_guard_kernel<MOM, EMA>), dim3(nchunks), dim3(256), 0, stream, p, g, buf, (bf16*)shadow_bf16,
+                       chunk_group, hyper_dev, step_dev, mu, nesterov, grad_scale, norm_coef, ema, d32, o32);
+}
+extern "C" int tvts_sgd_torch_guard(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group,
+                                    int nchunks, const float* hyper_dev, int* step_dev, double momentum, int nesterov, float grad_scale,
+                                    const float* norm_coef, long* skipped, float* ema, float d32, float o32, hipStream_t stream) {
+    const float mu = (float)momentum;
+    const bool mom = mu != 0.f;
+    if (!p || !g || (mom && !buf) || !chunk_group || !hyper_dev || nchunks <= 0 || guard_args_bad(step_dev, norm_coef, skipped))
+        return TVTS_EINVAL;
+    if (nesterov && !mom) return TVTS_EINVAL;
+    if (misaligned16(p) || misaligned16(g) || (mom && misaligned16(buf)) || misaligned16(ema) || ((uintptr_t)shadow_bf16 & 7))
+        return TVTS_EINVAL;
+    hipLaunchKernelGGL(guard_advance_kernel, dim3(1), dim3(1), 0, stream, norm_coef, step_dev, skipped);
+    const int nes = nesterov ? 1 : 0;
+    if (mom && ema) sgd_torch_guard_go<true, true>(p, g, buf, shadow_bf16, chunk_group, nchunks, hyper_dev, step_dev, mu, nes, grad_scale, norm_coef, ema, d32, o32, stream);
+    else if (mom) sgd_torch_guard_go<true, false>(p, g, buf, shadow_bf16, chunk_group, nchunks, hyper_dev, step_dev, mu, nes, grad_scale, norm_coef, nullptr, 0.f, 0.f, stream);
+    else if (ema) sgd_torch_guard_go<false, true>(p, g, buf, shadow_bf16, chunk_group, nchunks, hyper_dev, step_dev, mu, 0, grad_scale, norm_coef, ema, d32, o32, stream);
+    else sgd_torch_guard_go<false, false>(p, g, buf, shadow_bf16, chunk_group, nchunks, hyper_dev, step_dev, mu, 0, grad_scale, norm_coef, nullptr, 0.f, 0.f, stream);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
 }
 
 // a[i] <-> b[i] in place, shadow[i] = bf16(new a[i]): the masters and the average change places for an evaluation, no third buffer.

@@ -115,12 +115,36 @@ whole tower under trainable="head", and padding) keeps every bit of its average,
 it drift.  ``applied()`` exchanges the masters and the average in place (tvts_swap_f32_shadow) and re-derives the
 shadows, on entry and again on exit: no second ParamStore, no second set of engine workspaces.
 
+The epoch loop (run_class_finetuning.py main(), engine_for_finetuning.py:22-137, utils.py:399-503) and the overflow guard:
+
+    step = FinetuneStep(model, opt, clip_grad=5.0, update_freq=1, model_ema=model_ema, skip_nonfinite=True)
+    lr_values = cosine_scheduler(args.lr, args.min_lr, args.epochs, n_per_epoch, warmup_epochs=args.warmup_epochs)
+    wd_values = cosine_scheduler(args.weight_decay, args.weight_decay_end, args.epochs, n_per_epoch)
+    auto_load_model(args, model, opt, model_ema=model_ema, step=step)              # args.auto_resume: the newest checkpoint-<n>.pth
+    for epoch in range(args.start_epoch, args.epochs):
+        stats = train_one_epoch(step, loader, epoch, mixup_fn=mixup_fn, aug_fn=aug_fn, start_steps=epoch * n_per_epoch,
+                                lr_schedule_values=lr_values, wd_schedule_values=wd_values,
+                                num_training_steps_per_epoch=n_per_epoch, on_nonfinite="skip")
+        save_model(args, epoch, model, opt, model_ema=model_ema, step=step)        # rank 0 writes, every rank calls
+
+skip_nonfinite=True is GradScaler's "skip the update on inf / NaN", decided on the device: an updating call whose global gradient
+norm (tvts_grad_sumsq's norm_coef[0]: over the trainable chunks, behind the all-reduce, 1 / W folded in) is not finite keeps every
+bit of the masters, the moments (the momentum buffer), the shadows and the average, leaves the optimizer's device step counter where
+it was and counts in ``step.skipped`` (device int64); the gradients are zeroed and grad_norm is returned as it is.  With a finite
+norm the update is the unguarded update bit for bit.  The guarded kernels (tvts_adamw_torch_guard / tvts_sgd_torch_guard) are the
+chunk frames with one uniform load of the norm and a branch per block in front of every load of p / m / v; a one-lane kernel in
+front of them advances the step counter or ``skipped``.  Every rank sees the same norm, so every rank decides alike and no
+collective is added.  train_one_epoch reads the step's device scalars in one transfer every print_freq micro-steps, not on each
+(the reference's loss.item()): on_nonfinite="stop" raises FloatingPointError at that readout, "skip" only counts.  Across ranks the
+epoch's meters are merged through one dist.gather_rows table (counts and totals summed: SmoothedValue.synchronize_between_processes
++ global_avg).
+
 OUT OF SCOPE (not built here): RandAugment's per-frame ``"random"`` interpolation and TranslateX / TranslateY (abs) (neither list of
 rand_augment_transform holds them), --recount > 1,
 ``motion_shift`` (random_resized_crop_with_shift), the reference's torch noise stream,
 ``FastCollateMixup`` (the uint8-rounding variant: the reference scripts do not use it), ``ModelEma``'s ``device=`` (--model_ema_force_cpu)
 and ``resume=`` arguments, the fp16 loss scaler (the engine is bf16 with fp32 accumulation: there is no loss scale), DeepSpeed,
-sharded optimizer state, synchronising the TRAINING meters (the script's MetricLogger), and hipGraph capture of the step.
+sharded optimizer state, and hipGraph capture of the step.
 The scripts' other half -- validation_one_epoch after every epoch, final_test over the test views and merge
 (engine_for_finetuning.py:142-285), both across ranks too -- is tvts_amd/downstream/evaluate_v1.py.
 """
@@ -812,8 +836,12 @@ class FinetuneStep:
     With more than one rank of torch.distributed it is the data-parallel step (module docstring, "Several GPUs")."""
 
     def __init__(self, model, optimizer: "FusedTorchAdamW | FusedTorchSGD", clip_grad=None, update_freq=1, smoothing=0.0, trainable="all",
-                 data_parallel=None, payload=None, model_ema=None):
-        """model_ema: a ModelEma of this model -- every call that updates then also updates the average, inside the optimizer's
+                 data_parallel=None, payload=None, model_ema=None, skip_nonfinite=False):
+        """skip_nonfinite: True -- every updating call decides ON THE DEVICE whether it updates: when the global gradient norm
+        (after the all-reduce, over the trainable chunks) is not finite, the masters, the optimizer state, the shadows and the
+        average keep every bit, the optimizer's device step counter stays and ``skipped`` counts one more (GradScaler's rule); the
+        gradients are zeroed and grad_norm is returned as the non-finite value it is.  False: the step without a guard.
+        model_ema: a ModelEma of this model -- every call that updates then also updates the average, inside the optimizer's
         launch (a call that only accumulates leaves it alone, as the reference's loop does); None: the step without an average.
         data_parallel: None -- on when torch.distributed is initialised with more than one rank; False -- the single-process
         step whatever the world size; True without a process group is refused.  payload: "fp32" (default) or "bf16", the number
@@ -834,6 +862,7 @@ class FinetuneStep:
         self.norm_coef = torch.zeros(2, dtype=torch.float32, device=dev)
         self.norm_coef[1] = 1.0
         optimizer.norm_coef = self.norm_coef
+        self.skip_nonfinite = bool(skip_nonfinite)
         self.model_ema = model_ema
         if model_ema is not None:
             if model_ema.model is not model:
@@ -864,8 +893,10 @@ class FinetuneStep:
         if not isinstance(opt, FusedTorchAdamW):  # (appended only for another optimizer: with AdamW the signature is the bytes it was)
             g0 = opt.param_groups[0]
             sig += repr((type(opt).__name__, float(g0.get("momentum", 0)), bool(g0.get("nesterov", False)))).encode()
+        if self.skip_nonfinite:  # (appended only with the guard: without it the signature is the bytes it was)
+            sig += repr(("skip_nonfinite", True)).encode()
         D.agree(sig, "FinetuneStep: the model size, `trainable`, update_freq, clip_grad, payload, the recomputation mode, the "
-                     "ModelEma (present or not, its decay), the optimizer's kind (its momentum, nesterov) or the optimizer's chunk / group table")
+                     "ModelEma (present or not, its decay), the optimizer's kind (its momentum, nesterov), skip_nonfinite or the optimizer's chunk / group table")
         D.dist.broadcast(st.flat, src=0)
         st.refresh_shadows()
         self.model.mark_shadows_fresh()
@@ -878,6 +909,11 @@ class FinetuneStep:
         """the bytes this rank handed to the gradient exchange in the last call of step() (0: a call that only accumulated, or
         the single-process step)"""
         return 0 if self.sync is None else self.sync.bytes_sent
+
+    @property
+    def skipped(self) -> torch.Tensor:
+        """device int64 [1]: the updating calls the overflow guard skipped so far (always 0 without skip_nonfinite)"""
+        return self.opt.skipped
 
     def replicas_checksum(self) -> torch.Tensor:
         """device int64 scalar: the sum of the fp32 masters' bit patterns (store.flat read as int32, summed in int64).  Equal
@@ -998,10 +1034,218 @@ class FinetuneStep:
             K.grad_sumsq(st.grad, self.opt.chunk_group, self.partial, self.norm_coef, max_norm=self.clip_grad, grad_scale=scale)
             kept, self.opt.grad_scale = self.opt.grad_scale, scale
             try:
-                self.opt.step()
+                if self.skip_nonfinite:
+                    self.opt.step(guard=True)
+                else:
+                    self.opt.step()
             finally:
                 self.opt.grad_scale = kept
             K.zero_(st.grad)
             grad_norm = self.norm_coef[0].clone()
         return dict(loss=self.loss_cell[0] * float(self.update_freq), logits=logits.clone(), grad_norm=grad_norm,
                     class_acc=self.hits[0].to(torch.float32) / B)
+
+
+# ---------------------------------------------------------------------------------------------- the epoch loop
+METERS = ("loss", "class_acc", "lr", "min_lr", "weight_decay", "grad_norm", "skipped")  # the row order of the rank-merged table
+
+
+def cosine_scheduler(base_value, final_value, epochs, niter_per_ep, warmup_epochs=0, start_warmup_value=0, warmup_steps=-1):
+    """utils.cosine_scheduler (utils.py:399-416) in its float64 arithmetic -> ndarray [epochs * niter_per_ep]: a linear warm-up
+    (np.linspace) over warmup_epochs * niter_per_ep iterations, or over warmup_steps when that is positive, then half a cosine
+    from base_value to final_value.  Its quirk is kept: the warm-up values are only built with warmup_epochs > 0, so warmup_steps
+    > 0 with warmup_epochs == 0 shortens the cosine part without adding a warm-up and fails the length assertion."""
+    warmup_schedule = np.array([])
+    warmup_iters = warmup_epochs * niter_per_ep
+    if warmup_steps > 0:
+        warmup_iters = warmup_steps
+    if warmup_epochs > 0:
+        warmup_schedule = np.linspace(start_warmup_value, base_value, warmup_iters)
+    iters = np.arange(epochs * niter_per_ep - warmup_iters)
+    schedule = np.array([final_value + 0.5 * (base_value - final_value) * (1 + math.cos(math.pi * i / (len(iters)))) for i in iters])
+    schedule = np.concatenate((warmup_schedule, schedule))
+    assert len(schedule) == epochs * niter_per_ep
+    return schedule
+
+
+def merge_train_meters(rows):
+    """per-rank tables [len(METERS), 2] of (count, total) -> {meter: global_avg}: counts and totals summed over the ranks, then
+    total / count, what SmoothedValue.synchronize_between_processes followed by global_avg does (utils.py:49-60,72-74).  A meter
+    nobody updated (class_acc under Mixup, weight_decay without a decayed group) is absent, as in the reference's dict."""
+    t = torch.as_tensor(rows, dtype=torch.float64).reshape(-1, len(METERS), 2).sum(0)
+    return {k: float(t[i, 1]) / int(t[i, 0]) for i, k in enumerate(METERS) if int(t[i, 0]) > 0}
+
+
+def train_one_epoch(step, data_loader, epoch, criterion=None, device=None, loss_scaler=None, mixup_fn=None, log_writer=None,
+                    start_steps=0, lr_schedule_values=None, wd_schedule_values=None, num_training_steps_per_epoch=None,
+                    update_freq=None, aug_fn=None, print_freq=10, on_nonfinite="stop"):
+    """engine_for_finetuning.train_one_epoch (:22-137) over a FinetuneStep, which already holds the model, the optimizer, max_norm
+    (clip_grad) and the ModelEma.  data_loader yields (samples, targets, ...); only the first two are read.  ``criterion``,
+    ``device`` and ``loss_scaler`` are accepted for the reference's call shape and IGNORED: the loss is the step's soft-target /
+    smoothed cross-entropy, the device is the model's, and there is no loss scale.  mixup_fn: a Mixup -- its draw is made per
+    micro-step and handed to the step as ``mix``; aug_fn: an Augment -- samples are then uint8 source frames and the targets are
+    repeated per view.  update_freq: None or the step's own value (another one is refused).
+
+    Kept from the reference: micro-steps beyond num_training_steps_per_epoch * update_freq are drawn from the loader and dropped;
+    ``it = start_steps + step``; the schedule assignment with the precedence of :47 -- with an lr schedule it runs on EVERY micro-
+    step (same ``it``), with a weight-decay schedule alone only on the first micro-step of an update; lr is scaled by the group's
+    lr_scale and only groups whose weight_decay is above 0 take the scheduled decay.  Returned: {meter: global_avg} under the
+    reference's names loss, class_acc (absent with a mixup_fn), lr, min_lr, weight_decay, grad_norm; instead of loss_scale the
+    dict carries ``skipped``, the guard's counter at the end of the epoch (cumulative, a state value as loss_scale was).
+
+    Changed: the host does not read the device on every micro-step.  The step's device scalars are kept and read in ONE transfer
+    whenever data_iter_step % print_freq == 0 (the reference's log_every rhythm) and once behind the last micro-step.  At that
+    readout on_nonfinite="stop" raises FloatingPointError naming the first iteration whose loss or gradient norm was not finite,
+    where the reference's sys.exit(1) would have fired; "skip" only counts, and leaves non-finite values out of the loss /
+    grad_norm meters.  With FinetuneStep(skip_nonfinite=True) the weights are intact either way; without it "skip" is refused in
+    front of the first micro-step (it would train on NaN).  Across ranks the meters are merged at the end of the epoch through
+    one dist.gather_rows table (merge_train_meters)."""
+    if on_nonfinite not in ("stop", "skip"):
+        raise ValueError(f"on_nonfinite {on_nonfinite!r}: expected 'stop' or 'skip'")
+    if on_nonfinite == "skip" and not getattr(step, "skip_nonfinite", False):
+        raise ValueError("on_nonfinite='skip' needs FinetuneStep(skip_nonfinite=True): without the guard a non-finite gradient "
+                         "is written into every weight and the loop would train on NaN")
+    if update_freq is None:
+        update_freq = step.update_freq
+    if int(update_freq) != step.update_freq:
+        raise ValueError(f"update_freq {update_freq}: the step was built with {step.update_freq}")
+    if print_freq < 1:
+        raise ValueError("print_freq >= 1")
+    if num_training_steps_per_epoch is None:
+        num_training_steps_per_epoch = len(data_loader) // update_freq
+    opt = step.opt
+    count, total = [0] * len(METERS), [0.0] * len(METERS)
+
+    def meter(name, value):
+        if value is not None:
+            i = METERS.index(name)
+            count[i] += 1
+            total[i] += value
+
+    pending = []  # (it, loss, class_acc or None, grad_norm or None, max lr, min lr, weight decay or None) of micro-steps not read yet
+
+    def readout():
+        """ONE device -> host transfer for everything pending (+ the skip counter); meters, log_writer, the non-finite rule"""
+        if not pending:
+            return 0
+        cells = [step.skipped.reshape(-1)[0].to(torch.float64)]
+        for _, loss, acc, gn, *_ in pending:
+            cells += [c.to(torch.float64) for c in (loss, acc, gn) if c is not None]
+        host = iter(torch.stack(cells).cpu().tolist())
+        skipped = int(next(host))
+        for it, loss, acc, gn, max_lr, min_lr, wd in pending:
+            loss = next(host)
+            acc = None if acc is None else next(host)
+            gn = None if gn is None else next(host)
+            bad = not math.isfinite(loss) or (gn is not None and not math.isfinite(gn))
+            if bad and on_nonfinite == "stop":
+                pending.clear()
+                what = f"Loss is {loss}" if not math.isfinite(loss) else f"Gradient norm is {gn}"
+                raise FloatingPointError(f"{what} at iteration {it} (epoch {epoch}), stopping training")
+            meter("loss", loss if math.isfinite(loss) else None)
+            meter("class_acc", acc)
+            meter("lr", max_lr)
+            meter("min_lr", min_lr)
+            meter("weight_decay", wd)
+            meter("grad_norm", gn if gn is None or math.isfinite(gn) else None)
+            if log_writer is not None:
+                log_writer.update(loss=loss, head="loss")
+                log_writer.update(class_acc=acc, head="loss")
+                log_writer.update(skipped=skipped, head="opt")
+                log_writer.update(lr=max_lr, head="opt")
+                log_writer.update(min_lr=min_lr, head="opt")
+                log_writer.update(weight_decay=wd, head="opt")
+                log_writer.update(grad_norm=gn, head="opt")
+                log_writer.set_step()
+        pending.clear()
+        return skipped
+
+    opt.zero_grad()
+    skipped = 0
+    for data_iter_step, batch in enumerate(data_loader):
+        it_step = data_iter_step // update_freq
+        if it_step >= num_training_steps_per_epoch:
+            continue
+        it = start_steps + it_step  # global training iteration
+        if lr_schedule_values is not None or wd_schedule_values is not None and data_iter_step % update_freq == 0:
+            for param_group in opt.param_groups:
+                if lr_schedule_values is not None:
+                    param_group["lr"] = lr_schedule_values[it] * param_group["lr_scale"]
+                if wd_schedule_values is not None and param_group["weight_decay"] > 0:
+                    param_group["weight_decay"] = wd_schedule_values[it]
+        samples, targets = batch[0], batch[1]
+        plan = None
+        if aug_fn is not None:
+            plan = aug_fn.draw(samples.shape[0], samples.shape[2], samples.shape[3])
+            targets = targets.repeat_interleave(aug_fn.num_sample)
+        mix = None
+        if mixup_fn is not None:
+            mix = mixup_fn.draw(samples.shape[0] if plan is None else len(plan), step.model.engine.arch["image"])
+        out = step.step(samples, targets, mix=mix, aug=plan)
+        min_lr, max_lr, wd = 10., 0., None
+        for group in opt.param_groups:
+            min_lr, max_lr = min(min_lr, group["lr"]), max(max_lr, group["lr"])
+            if group["weight_decay"] > 0:
+                wd = group["weight_decay"]
+        pending.append((it, out["loss"], None if mixup_fn is not None else out["class_acc"], out["grad_norm"], float(max_lr),
+                        float(min_lr), None if wd is None else float(wd)))
+        if data_iter_step % print_freq == 0:
+            skipped = readout()
+    if pending:
+        skipped = readout()
+    else:
+        skipped = int(step.skipped.reshape(-1)[0].item())
+    meter("skipped", skipped)
+    table = torch.tensor([[float(c), float(t)] for c, t in zip(count, total)], dtype=torch.float64)
+    return merge_train_meters(D.gather_rows(table))
+
+
+def save_model(args, epoch, model, optimizer, model_ema=None, step=None):
+    """utils.save_model (:419-440), the branch without DeepSpeed: ``args.output_dir/checkpoint-<epoch>.pth`` written by rank 0 with
+    the keys model, optimizer, epoch, args and -- with an average -- model_ema (ModelEma.state_dict(): get_state_dict(model_ema)).
+    No ``scaler`` key: there is no loss scale.  For an exact continuation of THIS engine the file also carries drop_seed_base (the
+    rank-independent part of the stochastic-depth seed, every rank reads it back) and, with a FinetuneStep, its ``calls`` and
+    ``skipped``.  optimizer.state_dict() reads the device step counter: behind skipped updates it reports the updates that
+    counted, and loads into torch.optim.AdamW / SGD.  Every rank calls it (the state dicts are formed on every rank alike)."""
+    to_save = {"model": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "optimizer": optimizer.state_dict(),
+               "epoch": epoch, "args": args, "drop_seed_base": int(model.engine.drop_seed_base())}
+    if model_ema is not None:
+        to_save["model_ema"] = {k: v.cpu() for k, v in model_ema.state_dict().items()}
+    if step is not None:
+        to_save["calls"], to_save["skipped"] = int(step.calls), int(step.skipped.reshape(-1)[0].item())
+    if D.world()[1] == 0:
+        os.makedirs(args.output_dir, exist_ok=True)
+        torch.save(to_save, os.path.join(args.output_dir, "checkpoint-%s.pth" % str(epoch)))
+
+
+def auto_load_model(args, model, optimizer, model_ema=None, step=None):
+    """utils.auto_load_model (:444-475), the branch without DeepSpeed, on EVERY rank: args.auto_resume with an empty args.resume
+    picks ``checkpoint-<n>.pth`` with the largest all-digit n in args.output_dir (checkpoint-best.pth is not one); then model,
+    optimizer (when the file has `optimizer` and `epoch`: args.start_epoch = epoch + 1), the average (when a model_ema is handed
+    in and the file has one), the stochastic-depth seed base and the step's ``calls`` / ``skipped`` are loaded.  URLs are refused:
+    this project has no network path.  The file is this project's own pickle (it holds ``args``) -- load only what you wrote."""
+    import glob
+    if args.auto_resume and len(args.resume) == 0:
+        latest_ckpt = -1
+        for ckpt in glob.glob(os.path.join(args.output_dir, "checkpoint-*.pth")):
+            t = ckpt.split("-")[-1].split(".")[0]
+            if t.isdigit():
+                latest_ckpt = max(int(t), latest_ckpt)
+        if latest_ckpt >= 0:
+            args.resume = os.path.join(args.output_dir, "checkpoint-%d.pth" % latest_ckpt)
+    if not args.resume:
+        return
+    if re.match(r"^[a-zA-Z][a-zA-Z0-9+.-]*://", args.resume):
+        raise ValueError(f"auto_load_model: {args.resume!r} is a URL; only local files are loaded")
+    checkpoint = torch.load(args.resume, map_location="cpu", weights_only=False)
+    model.load_state_dict(checkpoint["model"])
+    if "optimizer" in checkpoint and "epoch" in checkpoint:
+        optimizer.load_state_dict(checkpoint["optimizer"])
+        args.start_epoch = checkpoint["epoch"] + 1
+        if model_ema is not None and "model_ema" in checkpoint:
+            model_ema.load_state_dict(checkpoint["model_ema"])
+        if "drop_seed_base" in checkpoint:
+            model.engine.set_drop_seed_base(checkpoint["drop_seed_base"])
+        if step is not None:
+            step.calls = int(checkpoint.get("calls", 0))
+            step.skipped.fill_(int(checkpoint.get("skipped", 0)))

@@ -1461,6 +1461,53 @@ def sgd_torch(p, g, buf, shadow, chunk_group, hyper_dev, step, momentum=0.0, nes
     _chk(rc, name)
 
 
+def _guard_cells(step_dev, skipped, norm_coef):
+    assert step_dev.dtype == torch.int32 and step_dev.numel() >= 1 and skipped.dtype == torch.int64 and skipped.numel() >= 1
+    assert norm_coef.dtype == torch.float32 and norm_coef.numel() >= 2
+
+
+def adamw_torch_guard(p, g, m, v, shadow, chunk_group, hyper_dev, step_dev, skipped, norm_coef, beta1=0.9, beta2=0.999, eps=1e-8,
+                      grad_scale=1.0, ema=None, ema_decay=None):
+    """adamw_torch under the overflow guard (tvts_adamw_torch_guard): norm_coef[0] finite -- step_dev[0] += 1, then the update of
+    adamw_torch with that device step count, bit for bit; not finite -- p, m, v, the shadow and the average keep every bit, step_dev
+    stays, skipped[0] (device int64) += 1.  ema / ema_decay as adamw_torch."""
+    n = chunk_group.numel()
+    assert chunk_group.dtype == torch.uint8 and hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= 128
+    assert all(t.dtype == torch.float32 and t.numel() >= n * 1024 for t in (p, g, m, v)) and (shadow is None or shadow.numel() >= n * 1024)
+    _guard_cells(step_dev, skipped, norm_coef)
+    if (ema is None) != (ema_decay is None):
+        raise ValueError("ema_decay without ema" if ema is None else "ema needs ema_decay")
+    d32, o32 = (0.0, 0.0) if ema is None else ema_pair(ema_decay)
+    assert ema is None or (ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() >= n * 1024 and ema.device == p.device)
+    per = 30.0 if ema is None else 38.0  # (an upper bound: a skipped launch moves no parameter bytes)
+    with _hbm("adamw", lambda: per * 1024 * float((chunk_group < 64).sum())):
+        rc = _lib.load().tvts_adamw_torch_guard(_p(p), _p(g), _p(m), _p(v), _p(shadow), _p(chunk_group), n, _p(hyper_dev), _p(step_dev),
+                                                beta1, beta2, eps, grad_scale, _p(norm_coef), _p(skipped), _p(ema), d32, o32, _stream())
+    _chk(rc, "tvts_adamw_torch_guard")
+
+
+def sgd_torch_guard(p, g, buf, shadow, chunk_group, hyper_dev, step_dev, skipped, norm_coef, momentum=0.0, nesterov=False,
+                    grad_scale=1.0, ema=None, ema_decay=None):
+    """sgd_torch under the overflow guard (tvts_sgd_torch_guard), as adamw_torch_guard.  A skipped first call leaves step_dev at 0:
+    the next call is then the first update and writes buf without reading it."""
+    n = chunk_group.numel()
+    assert chunk_group.dtype == torch.uint8 and hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= 128
+    mom = ctypes.c_float(float(momentum)).value != 0.0
+    assert all(t.dtype == torch.float32 and t.numel() >= n * 1024 for t in (p, g) + ((buf,) if buf is not None else ()))
+    assert shadow is None or shadow.numel() >= n * 1024
+    _guard_cells(step_dev, skipped, norm_coef)
+    if (ema is None) != (ema_decay is None):
+        raise ValueError("ema_decay without ema" if ema is None else "ema needs ema_decay")
+    d32, o32 = (0.0, 0.0) if ema is None else ema_pair(ema_decay)
+    assert ema is None or (ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() >= n * 1024 and ema.device == p.device)
+    per = 14.0 + (8.0 if mom else 0.0) + (0.0 if ema is None else 8.0)
+    with _hbm("sgd", lambda: per * 1024 * float((chunk_group < 64).sum())):
+        rc = _lib.load().tvts_sgd_torch_guard(_p(p), _p(g), _p(buf), _p(shadow), _p(chunk_group), n, _p(hyper_dev), _p(step_dev),
+                                              float(momentum), 1 if nesterov else 0, grad_scale, _p(norm_coef), _p(skipped), _p(ema),
+                                              d32, o32, _stream())
+    _chk(rc, "tvts_sgd_torch_guard")
+
+
 def ema_update(ema, p, chunk_group, decay):
     """ModelEma.update as a pass of its own: ema = fl(fl(ema * d32) + fl(o32 * p)) on every 1024-element chunk whose group byte is
     below 64; a chunk of another group (255 = frozen / padding) keeps every bit of ema.  12 B per element."""

@@ -10,6 +10,11 @@ v2/train_dist_TVTSv2_ViT_B_16.py:118-125 (defaults betas (0.9, 0.999), eps 1e-6,
 All are ``torch.optim.Optimizer``s, so param_groups / state_dict keep the reference checkpoint layout
 (AdamW: ``state[p] = {step, exp_avg, exp_avg_sq}``, SGD: ``state[p] = {momentum_buffer}``; views of the flat state buffers).
 
+``FusedTorchAdamW.step(guard=True)`` / ``FusedTorchSGD.step(guard=True)`` are the same launches under the overflow guard
+(tvts_adamw_torch_guard / tvts_sgd_torch_guard): the kernel updates only when ``norm_coef[0]`` is finite, the step counter the
+kernels read lives on the device and advances there, ``skipped`` (device int64) counts the calls that did not update, and
+``state_dict()`` reports the device's step count.
+
 Gradient handling follows the reference's pinned torch 1.11 ``zero_grad()`` (grads zeroed, not set to
 None): every trainable tensor is updated every step, tensors that received no gradient see g = 0.
 """
@@ -48,6 +53,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self.chunk_group = table.to(dev)
         self.global_step = 0
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.skipped = torch.zeros(1, dtype=torch.int64, device=dev)  # updates the overflow guard skipped (step(guard=True))
+        self._guarded = False  # a guarded step has run since the host last read step_dev: global_step may lag behind it
         self.hyper_dev = torch.zeros(2 * self.MAX_GROUPS, dtype=torch.float32, device=dev)  # lr[MAX_GROUPS] | wd[MAX_GROUPS]
         self._hyper_host = None
         self.grad_scale = 1.0
@@ -89,12 +96,32 @@ class _FlatOptimizer(torch.optim.Optimizer):
             self.sync_hyper()  # (a host -> device copy: not capturable; the caller syncs before capture / replay)
         elif device_step and self._hyper_host != (lr, wd):
             raise RuntimeError(f"{self._cls}: call sync_hyper() (or run one eager device_step) before capturing the step")
+        if self._guarded:  # (guarded steps count on the device only: the host counter catches up before it is used again)
+            self._adopt_device_step()
         self.global_step += 1
         if device_step:
             self.step_dev.add_(1)
         else:
             self.step_dev.fill_(self.global_step)  # keeps the device counter in step when eager and captured steps mix
         return hp
+
+    def _begin_guard(self):
+        """a step under the overflow guard (step(guard=True)) -> _hyper().  The kernels decide on the device whether the step
+        counts: the launch itself advances step_dev or skipped, and the host counter is re-read from step_dev when somebody needs it
+        (state_dict, the next unguarded step) -- nothing here synchronises."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{self._cls}: step(guard=True) inside a stream capture is not built")
+        if self.norm_coef is None:
+            raise RuntimeError(f"{self._cls}: step(guard=True) needs norm_coef (the device norm of tvts_grad_sumsq; FinetuneStep sets it)")
+        hp = self._hyper()
+        self.sync_hyper()
+        self._guarded = True
+        return hp
+
+    def _adopt_device_step(self):
+        """the host counter takes the device's value (a host read): behind guarded steps the device alone knows how many counted"""
+        self.global_step = int(self.step_dev.item())
+        self._guarded = False
 
     def _finish(self, device_step: bool, transposed: bool = True):
         """behind the step's last launch: the shadows the kernel does not write"""
@@ -128,8 +155,8 @@ class _FlatAdamW(_FlatOptimizer):
     def _sync_step_from_device(self):
         """Under hipGraph replay the host counters only advance at capture time: re-read the device counter."""
         st = int(self.step_dev.item())
-        if st > self.global_step:
-            self.global_step = st
+        if st > self.global_step or self._guarded:
+            self.global_step, self._guarded = st, False
         for s in self.state.values():
             s["step"] = self.global_step
 
@@ -160,6 +187,7 @@ class _FlatAdamW(_FlatOptimizer):
                 self.state[p]["step"] = int(st["step"])
                 self.global_step = max(self.global_step, int(st["step"]))
         self.step_dev.fill_(self.global_step)
+        self._guarded = False
 
 
 class FusedHFAdamW(_FlatAdamW):
@@ -249,12 +277,20 @@ class FusedTorchAdamW(_FlatAdamW):
         self.ema = None
 
     @torch.no_grad()
-    def step(self, closure=None, device_step: bool = False):
-        """device_step=True: the step counter the kernel reads lives in device memory (same bits as the host counter)"""
-        self.sync_hyper()
-        b1, b2, eps, _, _ = self._begin(device_step)
+    def step(self, closure=None, device_step: bool = False, guard: bool = False):
+        """device_step=True: the step counter the kernel reads lives in device memory (same bits as the host counter).
+        guard=True (FinetuneStep(skip_nonfinite=True)): the update happens only when norm_coef[0] is finite, decided on the device
+        (tvts_adamw_torch_guard); a skipped call advances ``skipped`` instead of the device step counter."""
         st = self.store
         ema = {} if self.ema is None else dict(ema=self.ema[0], ema_decay=self.ema[1])
+        if guard:
+            b1, b2, eps, _, _ = self._begin_guard()
+            K.adamw_torch_guard(st.flat, st.grad, st.m, st.v, st.shadow, self.chunk_group, self.hyper_dev, self.step_dev, self.skipped,
+                                self.norm_coef, b1, b2, eps, self.grad_scale, **ema)
+            self._finish(True)
+            return
+        self.sync_hyper()
+        b1, b2, eps, _, _ = self._begin(device_step)
         K.adamw_torch(st.flat, st.grad, st.m, st.v, st.shadow, self.chunk_group, self.hyper_dev, self.global_step, b1, b2, eps,
                       self.grad_scale, step_dev=self.step_dev if device_step else None, norm_coef=self.norm_coef, **ema)
         self._finish(device_step)
@@ -323,12 +359,20 @@ class FusedTorchSGD(_FlatOptimizer):
         return (mu, nes, *self._lr_wd())
 
     @torch.no_grad()
-    def step(self, closure=None, device_step: bool = False):
-        """device_step=True: the step counter the kernel reads lives in device memory (same bits as the host counter)"""
-        self.sync_hyper()
-        mu, nes, _, _ = self._begin(device_step)
+    def step(self, closure=None, device_step: bool = False, guard: bool = False):
+        """device_step=True: the step counter the kernel reads lives in device memory (same bits as the host counter).
+        guard=True: as FusedTorchAdamW.step (tvts_sgd_torch_guard).  ``state[p]`` is then filled by state_dict(), which reads the
+        device counter: whether a first update has happened is the device's knowledge."""
         st = self.store
         ema = {} if self.ema is None else dict(ema=self.ema[0], ema_decay=self.ema[1])
+        if guard:
+            mu, nes, _, _ = self._begin_guard()
+            K.sgd_torch_guard(st.flat, st.grad, st.m if mu != 0 else None, st.shadow, self.chunk_group, self.hyper_dev, self.step_dev,
+                              self.skipped, self.norm_coef, momentum=mu, nesterov=nes, grad_scale=self.grad_scale, **ema)
+            self._finish(True)
+            return
+        self.sync_hyper()
+        mu, nes, _, _ = self._begin(device_step)
         K.sgd_torch(st.flat, st.grad, st.m if mu != 0 else None, st.shadow, self.chunk_group, self.hyper_dev, self.global_step,
                     momentum=mu, nesterov=nes, grad_scale=self.grad_scale, step_dev=self.step_dev if device_step else None,
                     norm_coef=self.norm_coef, **ema)
@@ -337,8 +381,8 @@ class FusedTorchSGD(_FlatOptimizer):
 
     def state_dict(self):
         st = int(self.step_dev.item())  # (under hipGraph replay the host counter only advances at capture time)
-        if st > self.global_step:
-            self.global_step = st
+        if st > self.global_step or self._guarded:
+            self.global_step, self._guarded = st, False
         if self.global_step > 0:
             self._buffers()
         return super().state_dict()
@@ -378,3 +422,4 @@ class FusedTorchSGD(_FlatOptimizer):
             self.state.clear()
             self.global_step = 0
         self.step_dev.fill_(self.global_step)
+        self._guarded = False
