@@ -723,55 +723,41 @@ int tvts_view_store(const float* logits, long ld, int B, int C, const int* slot,
  * |grad_scale| sqrt(sum), norm_coef[1] = coef = min(1, max_norm / (norm + 1e-6)), 1 when max_norm <= 0 (clipping off). */
 int tvts_grad_sumsq(const float* g, const unsigned char* chunk_group, int nchunks, float* partial, float max_norm,
                     float grad_scale, float* norm_coef, hipStream_t stream);
-/* torch.optim.AdamW as optim_factory.py:129-130 builds it over the layer-decay groups of optim_factory.py:51-90: p *= 1 - lr wd;
- * m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g g; p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps), bias corrections in double from
- * `step` or from step_dev[0] (same bits).  g = stored gradient * grad_scale * norm_coef[1] (norm_coef optional).  hyper_dev: device
- * fp32 lr[64] | wd[64]; chunk table as tvts_adamw_hf, groups 0..63, 255 = frozen (every bit kept); bf16 shadow in the same pass. */
+/* The two torch rules of the v1 downstream steps, one launch over the flat store each.  Common to both: hyper_dev is the device
+ * fp32 table lr[64] | wd[64]; chunk table as tvts_adamw_hf, groups 0..63, and a chunk of another group (255 = frozen) keeps every
+ * bit of p, the state, the shadow and the average; the bf16 shadow (optional) is written in the same pass; g = stored gradient *
+ * grad_scale * norm_coef[1] (norm_coef optional); the step count is `step`, or step_dev[0] when given (same device code, same bits).
+ * -22 from either: p, g or a state stream the launch touches null or not 16-byte aligned; chunk_group or hyper_dev null;
+ * nchunks <= 0; step <= 0 without step_dev; ema not 16-byte aligned, shadow / skipped not 8, step_dev / norm_coef not 4; under the
+ * guard step_dev or norm_coef null; nesterov with momentum == 0.
+ *
+ * torch.optim.AdamW as optim_factory.py:129-130 builds it over the layer-decay groups of optim_factory.py:51-90: p *= 1 - lr wd;
+ * m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g g; p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps), bias corrections in double. */
 int tvts_adamw_torch(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
-                     const float* hyper_dev, int step, const int* step_dev, double beta1, double beta2, double eps,
-                     float grad_scale, const float* norm_coef, hipStream_t stream);
-/* timm.utils.ModelEma as run_class_finetuning.py:345-352 builds it and engine_for_finetuning.py:84-85,97-98 updates it, per
- * element: ema = fl(fl(ema * d32) + fl(o32 * p)) -- three roundings, no FMA -- with d32 = fp32(decay) and o32 = fp32(1.0 - decay),
- * the difference formed in double on the host.  tvts_adamw_torch_ema: tvts_adamw_torch with the rule applied to the chunk's new p
- * in the same pass (p, m, v and the shadow get the bits of tvts_adamw_torch); tvts_ema_update: the rule as a pass of its own.
- * Both keep every bit of `ema` in a chunk that does not step (group >= 64, 255 = frozen).  Pointers 16-byte aligned (-22). */
-int tvts_adamw_torch_ema(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group,
-                         int nchunks, const float* hyper_dev, int step, const int* step_dev, double beta1, double beta2, double eps,
-                         float grad_scale, const float* norm_coef, float* ema, float d32, float o32, hipStream_t stream);
-int tvts_ema_update(float* ema, const float* p, const unsigned char* chunk_group, int nchunks, float d32, float o32,
-                    hipStream_t stream);
+                     const float* hyper_dev, int step, int* step_dev, double beta1, double beta2, double eps, float grad_scale,
+                     const float* norm_coef, float* ema, float d32, float o32, long* skipped, hipStream_t stream);
 /* torch.optim.SGD as optim_factory.py:121-126 builds it for v1/scripts/linear_ssv2.sh (--opt sgd --lr 0.1 --momentum 0.9
  * --weight_decay 1e-9: "sgd" / "nesterov" with nesterov=True, "momentum" without), single-tensor form of torch/optim/sgd.py with
  * dampening 0, bit for bit -- every add(x, alpha=a) there is one fused multiply-add:
  *   gg = g * gs; d = wd != 0 ? fmaf(wd, p, gg) : gg; momentum != 0: buf = first update ? d : fl(mu * buf) + d,
  *   d = nesterov ? fmaf(mu, buf, d) : buf; p = fmaf(-lr, d, p); shadow = bf16(p).
- * lr, wd per group from hyper_dev (device fp32 lr[64] | wd[64]), mu = fp32(momentum), gs = grad_scale * norm_coef[1] (norm_coef
- * optional).  First update: `step` (or step_dev[0] when given: same device code, same bits) == 1; buf is then written, not read.
- * momentum == 0: buf is neither read nor written and may be null.  Chunk table as tvts_adamw_torch: a chunk of group >= 64 (255 =
- * frozen) keeps every bit of p, buf, the shadow and the average.  tvts_sgd_torch_ema: the same launch with ModelEma's rule applied
- * to the new p (p, buf and the shadow get the bits of tvts_sgd_torch).  -22: a null pointer, nchunks <= 0, step <= 0 without
- * step_dev, nesterov with momentum == 0, a pointer that is not 16-byte aligned (shadow: 8). */
+ * mu = fp32(momentum).  First update: the step count == 1; buf is then written, not read.  momentum == 0: buf is neither read nor
+ * written and may be null. */
 int tvts_sgd_torch(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
-                   const float* hyper_dev, int step, const int* step_dev, double momentum, int nesterov, float grad_scale,
-                   const float* norm_coef, hipStream_t stream);
-int tvts_sgd_torch_ema(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
-                       const float* hyper_dev, int step, const int* step_dev, double momentum, int nesterov, float grad_scale,
-                       const float* norm_coef, float* ema, float d32, float o32, hipStream_t stream);
-/* The overflow guard of the v1 fine-tuning step (GradScaler's "skip the update on inf / NaN", decided on the device):
- * tvts_adamw_torch[_ema] / tvts_sgd_torch[_ema] whose update happens only when norm_coef[0] -- the global norm tvts_grad_sumsq left
- * in device memory, formed over the trainable chunks -- is finite.  Finite: step_dev[0] += 1 first, then the unguarded update with
- * that step count, bit for bit.  Not finite: every bit of p, m, v (buf), the shadow and the average is kept, step_dev[0] stays and
- * the device int64 skipped[0] += 1.  The step counter lives on the device only (no `step` argument); norm_coef is required;
- * ema == null: the launch without an average.  -22: a null pointer (shadow, ema and -- with momentum 0 -- buf may be null),
- * nchunks <= 0, nesterov with momentum == 0, p / g / m / v / buf / ema not 16-byte aligned, shadow / skipped not 8, step_dev /
- * norm_coef not 4. */
-int tvts_adamw_torch_guard(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group,
-                           int nchunks, const float* hyper_dev, int* step_dev, double beta1, double beta2, double eps,
-                           float grad_scale, const float* norm_coef, long* skipped, float* ema, float d32, float o32,
-                           hipStream_t stream);
-int tvts_sgd_torch_guard(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
-                         const float* hyper_dev, int* step_dev, double momentum, int nesterov, float grad_scale,
-                         const float* norm_coef, long* skipped, float* ema, float d32, float o32, hipStream_t stream);
+                   const float* hyper_dev, int step, int* step_dev, double momentum, int nesterov, float grad_scale,
+                   const float* norm_coef, float* ema, float d32, float o32, long* skipped, hipStream_t stream);
+/* The average (ema != null; null: none, d32 / o32 unused): timm.utils.ModelEma as run_class_finetuning.py:345-352 builds it and
+ * engine_for_finetuning.py:84-85,97-98 updates it, per element ema = fl(fl(ema * d32) + fl(o32 * p)) -- three roundings, no FMA --
+ * with d32 = fp32(decay) and o32 = fp32(1.0 - decay), the difference formed in double on the host.  The rule is applied to the
+ * chunk's new p in the same pass; p, the state and the shadow get the bits of the launch without an average.  tvts_ema_update is the
+ * rule as a pass of its own, with the same chunk gate (pointers 16-byte aligned, -22). */
+int tvts_ema_update(float* ema, const float* p, const unsigned char* chunk_group, int nchunks, float d32, float o32,
+                    hipStream_t stream);
+/* The guard (skipped != null; null: unguarded): the overflow guard of the v1 fine-tuning step, GradScaler's "skip the update on
+ * inf / NaN" decided on the device.  The update happens only when norm_coef[0] -- the global norm tvts_grad_sumsq left in device
+ * memory, formed over the trainable chunks -- is finite.  Finite: step_dev[0] += 1 first, then the unguarded update with that step
+ * count, bit for bit.  Not finite: every bit of p, the state, the shadow and the average is kept, step_dev[0] stays and the device
+ * int64 skipped[0] += 1.  The step counter lives on the device only: step_dev and norm_coef are required, `step` is ignored. */
 /* a[i] <-> b[i] in place and shadow_bf16[i] = bf16(new a[i]) for i < n; n % 4 == 0, a and b disjoint and 16-byte aligned (-22).
  * ModelEma.applied(): the masters and the average change places without a third buffer. */
 int tvts_swap_f32_shadow(float* a, float* b, void* shadow_bf16, long n, hipStream_t stream);

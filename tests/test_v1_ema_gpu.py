@@ -1,4 +1,4 @@
-"""ModelEma on the GPU (run with -m gpu): tvts_ema_update, tvts_adamw_torch_ema and tvts_swap_f32_shadow per element, and the
+"""ModelEma on the GPU (run with -m gpu): tvts_ema_update, tvts_adamw_torch with ema and tvts_swap_f32_shadow per element, and the
 class inside FinetuneStep -- everything bit equality against tests/v1_ema_ref.py (the numpy restatement of timm's rule, held to
 torch on the CPU by tests/test_v1_ema_cpu.py), a twin step without an average, or the state before.  Kernel tests: six chunks with
 the group bytes and the state construction of test_adamw_torch_per_element.  Step tests: tests/v1_downstream_synth.TINY, 7 classes,

@@ -1,6 +1,6 @@
 """The overflow guard of the v1 fine-tuning step and the epoch loop around it, on the GPU (run with -m gpu).
 
-1. the kernels: tvts_adamw_torch_guard / tvts_sgd_torch_guard against their unguarded siblings, bit for bit, with the norm a real
+1. the kernels: tvts_adamw_torch / tvts_sgd_torch with `skipped` (the guarded launch) against the unguarded launch, bit for bit, with the norm a real
    tvts_grad_sumsq left on the device (so a NaN inside a FROZEN chunk is seen not to skip), and every byte kept on a skipped launch;
 2. FinetuneStep(skip_nonfinite=True) against a real torch.optim.SGD / torch.optim.AdamW on the CPU whose step() is not called on
    the poisoned call, fed this project's own gradients (the construction of tests/test_v1_sgd_gpu.py);
@@ -102,7 +102,7 @@ def launch(K, variant, g, *, guard, step0):
     ema = dict(ema=views["e"], ema_decay=DECAY) if cfg["ema"] else {}
     if cfg["kind"] == "adamw":
         if guard:
-            K.adamw_torch_guard(views["p"], gv, views["m"], views["v"], views["sh"], cg, hyper, sd, sk, nc, grad_scale=0.5, **ema)
+            K.adamw_torch(views["p"], gv, views["m"], views["v"], views["sh"], cg, hyper, 0, grad_scale=0.5, step_dev=sd, norm_coef=nc, skipped=sk, **ema)
         else:
             sd += 1
             K.adamw_torch(views["p"], gv, views["m"], views["v"], views["sh"], cg, hyper, 0, grad_scale=0.5, step_dev=sd, norm_coef=nc, **ema)
@@ -110,7 +110,7 @@ def launch(K, variant, g, *, guard, step0):
         mom = dict(momentum=cfg["momentum"], nesterov=cfg["nesterov"])
         buf = views["m"] if cfg["momentum"] else None
         if guard:
-            K.sgd_torch_guard(views["p"], gv, buf, views["sh"], cg, hyper, sd, sk, nc, grad_scale=0.5, **mom, **ema)
+            K.sgd_torch(views["p"], gv, buf, views["sh"], cg, hyper, 0, grad_scale=0.5, step_dev=sd, norm_coef=nc, skipped=sk, **mom, **ema)
         else:
             sd += 1
             K.sgd_torch(views["p"], gv, buf, views["sh"], cg, hyper, 0, grad_scale=0.5, step_dev=sd, norm_coef=nc, **mom, **ema)
@@ -179,21 +179,28 @@ def test_guard_entry_points_refuse_with_einval(K):
 
     def call(kind, **o):
         a = dict(p=ptr(t["p"]), g=ptr(t["g"]), m=ptr(t["m"]), v=ptr(t["v"]), shadow=ptr(sh), chunk_group=ptr(grp), nchunks=2, hyper=ptr(hyper),
-                 step_dev=ptr(sdev), norm_coef=ptr(nc), skipped=ptr(skp), ema=ptr(t["ema"]), momentum=0.9, nesterov=1)
+                 step=0, step_dev=ptr(sdev), norm_coef=ptr(nc), skipped=ptr(skp), ema=ptr(t["ema"]), momentum=0.9, nesterov=1)
         a.update(o)
         if kind == "adamw":
-            return lib.tvts_adamw_torch_guard(a["p"], a["g"], a["m"], a["v"], a["shadow"], a["chunk_group"], a["nchunks"], a["hyper"],
-                                              a["step_dev"], 0.9, 0.999, 1e-8, 1.0, a["norm_coef"], a["skipped"], a["ema"], 0.5, 0.5, None)
-        return lib.tvts_sgd_torch_guard(a["p"], a["g"], a["m"], a["shadow"], a["chunk_group"], a["nchunks"], a["hyper"], a["step_dev"],
-                                        a["momentum"], a["nesterov"], 1.0, a["norm_coef"], a["skipped"], a["ema"], 0.5, 0.5, None)
+            return lib.tvts_adamw_torch(a["p"], a["g"], a["m"], a["v"], a["shadow"], a["chunk_group"], a["nchunks"], a["hyper"], a["step"],
+                                        a["step_dev"], 0.9, 0.999, 1e-8, 1.0, a["norm_coef"], a["ema"], 0.5, 0.5, a["skipped"], None)
+        return lib.tvts_sgd_torch(a["p"], a["g"], a["m"], a["shadow"], a["chunk_group"], a["nchunks"], a["hyper"], a["step"], a["step_dev"],
+                                  a["momentum"], a["nesterov"], 1.0, a["norm_coef"], a["ema"], 0.5, 0.5, a["skipped"], None)
+    # (skipped=None is the UNGUARDED launch: refused here because its step is 0 and the device counter goes with it)
     common = [dict(p=None), dict(g=None), dict(m=None), dict(chunk_group=None), dict(hyper=None), dict(step_dev=None), dict(norm_coef=None),
-              dict(skipped=None), dict(nchunks=0), dict(nchunks=-3), dict(p=ptr(t["p"], 4)), dict(g=ptr(t["g"], 8)), dict(m=ptr(t["m"], 4)),
+              dict(skipped=None, step_dev=None), dict(nchunks=0), dict(nchunks=-3), dict(p=ptr(t["p"], 4)), dict(g=ptr(t["g"], 8)), dict(m=ptr(t["m"], 4)),
               dict(ema=ptr(t["ema"], 4)), dict(shadow=ptr(sh, 2)), dict(shadow=ptr(sh, 4)), dict(skipped=ptr(skp, 4)), dict(step_dev=ptr(sdev, 2)),
               dict(norm_coef=ptr(nc, 2))]
     for o in common + [dict(v=None), dict(v=ptr(t["v"], 4))]:
         assert call("adamw", **o) == EINVAL, ("adamw", o)
     for o in common + [dict(momentum=0.0, nesterov=1)]:
         assert call("sgd", **o) == EINVAL, ("sgd", o)
+    # guarded without its cells, with a host step that would do unguarded; the unguarded tvts_adamw_torch refuses misalignment too
+    for o in (dict(step=1, step_dev=None), dict(step=1, norm_coef=None)):
+        for kind in ("adamw", "sgd"):
+            assert call(kind, **o) == EINVAL, (kind, o)
+    for o in (dict(p=ptr(t["p"], 4)), dict(shadow=ptr(sh, 2))):
+        assert call("adamw", step=1, skipped=None, ema=None, **o) == EINVAL, ("adamw unguarded", o)
     torch.cuda.synchronize()
     for k, x in t.items():
         assert bool((x == 1).all()), k

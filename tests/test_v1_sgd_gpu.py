@@ -1,4 +1,4 @@
-"""torch.optim.SGD for the v1 linear probe on the GPU (run with -m gpu): tvts_sgd_torch / tvts_sgd_torch_ema bit for bit against
+"""torch.optim.SGD for the v1 linear probe on the GPU (run with -m gpu): tvts_sgd_torch without and with `ema` bit for bit against
 tests/v1_sgd_ref.py (the numpy restatement with an exact FMA, held to torch on the CPU by tests/test_v1_sgd_cpu.py), FusedTorchSGD
 inside FinetuneStep against a real torch.optim.SGD(foreach=False) on the CPU fed with the engine's own gradients, checkpoints in
 both directions, gradient accumulation and create_optimizer.  Everything is bit equality: the rule is a chain of fp32 operations
@@ -196,7 +196,7 @@ def test_fused_average_is_the_plain_launch_plus_the_separate_pass(K, step, mode,
 
 # ================================================================================================ 3. refusals
 def test_entry_points_refuse_with_einval(K):
-    """every refusal of the two host entry points, through the library itself; nothing is launched and the operands keep their bits"""
+    """every refusal of the host entry point, without and with an average, through the library itself; nothing is launched and the operands keep their bits"""
     lib = K._lib.load()
     n = 2 * CH
     t = {k: torch.ones(n + 8, dtype=F32, device=DEV) for k in ("p", "g", "buf", "ema")}
@@ -214,16 +214,14 @@ def test_entry_points_refuse_with_einval(K):
         a.update(o)
         args = [a[k] for k in ("p", "g", "buf", "shadow", "chunk_group", "nchunks", "hyper", "step", "step_dev", "momentum", "nesterov",
                                "grad_scale", "norm_coef")]
-        if ema:
-            return lib.tvts_sgd_torch_ema(*args, a["e"], 0.5, 0.5, None)
-        return lib.tvts_sgd_torch(*args, None)
+        return lib.tvts_sgd_torch(*args, a["e"] if ema else None, 0.5, 0.5, None, None)
     cases = [dict(p=None), dict(g=None), dict(buf=None), dict(chunk_group=None), dict(hyper=None), dict(nchunks=0), dict(nchunks=-3),
              dict(step=0), dict(step=-1), dict(momentum=0.0, nesterov=1),
              dict(p=ptr(t["p"], 4)), dict(g=ptr(t["g"], 8)), dict(buf=ptr(t["buf"], 4)), dict(shadow=ptr(sh, 2)), dict(shadow=ptr(sh, 4))]
     for fused in (False, True):
         for o in cases:
             assert call(ema=fused, **o) == EINVAL, (fused, o)
-    assert call(ema=True, e=None) == EINVAL and call(ema=True, e=ptr(t["ema"], 4)) == EINVAL
+    assert call(ema=True, e=ptr(t["ema"], 4)) == EINVAL  # (a null ema is the launch without an average: the `fused=False` cases)
     torch.cuda.synchronize()
     for k, v in t.items():
         assert bool((v == 1).all()), k

@@ -63,7 +63,7 @@ def bits(a):
 
 
 def ema_ref_chunks(e, p, groups, decay):
-    """the chunk gate of tvts_ema_update / tvts_adamw_torch_ema: 1024-element chunk c follows the rule iff groups[c] < 64, else it
+    """the chunk gate of tvts_ema_update / tvts_adamw_torch with ema: 1024-element chunk c follows the rule iff groups[c] < 64, else it
     keeps every bit of e"""
     e, p = np.asarray(e, dtype=np.float32), np.asarray(p, dtype=np.float32)
     steps = np.repeat(np.asarray(groups).astype(np.int64) < 64, CH)

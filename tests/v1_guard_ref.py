@@ -1,4 +1,4 @@
-"""The overflow guard of the v1 fine-tuning step as a numpy restatement (tvts_adamw_torch_guard / tvts_sgd_torch_guard, csrc/optim.hip):
+"""The overflow guard of the v1 fine-tuning step as a numpy restatement (tvts_adamw_torch / tvts_sgd_torch with skipped, csrc/optim.hip):
 a sequence of updating calls in which a call whose global gradient norm is not finite keeps every bit of the parameters, the
 optimizer state and the average, does not advance the step counter, and counts one skip -- torch.cuda.amp.GradScaler's rule,
 ``optimizer.step()`` simply not called.  Built on the exact-arithmetic references: tests/v1_sgd_ref.sgd_ref (torch.optim.SGD bit
@@ -19,7 +19,7 @@ def norm_of(g, grad_scale=1.0):
 
 
 def adamw_ref(p, g, m, v, *, lr, wd, step, beta1=0.9, beta2=0.999, eps=1e-8):
-    """one update in the order of adamw_torch_body: p *= fl(1 - lr wd); m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g g;
+    """one update in the order of adamw_torch_kernel: p *= fl(1 - lr wd); m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g g;
     p -= fl(lr / bc1) m / (sqrt(v) / fl(sqrt(bc2)) + eps), every operation rounded to fp32, no FMA"""
     p, g, m, v = (np.asarray(x, dtype=F32) for x in (p, g, m, v))
     bc1, bc2 = 1.0 - beta1 ** step, 1.0 - beta2 ** step

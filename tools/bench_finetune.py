@@ -43,7 +43,7 @@ gather's own time is measured too: device events around 50 launches of the step'
 
 --ema {off,fused,separate} (default off: the run and its output as before; without --mixup / --aug / --gpus): averaged weights,
 ModelEma(decay 0.9999).
-    fused     FinetuneStep(..., model_ema=ema): the average rides in the optimizer's launch (tvts_adamw_torch_ema, 38 B per element)
+    fused     FinetuneStep(..., model_ema=ema): the average rides in the optimizer's launch (tvts_adamw_torch with ema, 38 B per element)
     separate  the step without an average, then ema.update(model) behind every call, as the reference's loop does (one more
               launch, tvts_ema_update, 12 B per element)
 
@@ -55,7 +55,7 @@ then under SGD (probe: lr 0.1, weight_decay 1e-9 as v1/scripts/linear_ssv2.sh; f
 AdamW rounds (max / min - 1): a difference inside that spread is not a measured difference.
 
 --guard {off,on,both} (default off: the run and its output as before; the plain step only).  on: FinetuneStep(skip_nonfinite=True),
-the overflow guard (tvts_adamw_torch_guard: one more single-lane launch, one uniform load and a branch per chunk).  both: the
+the overflow guard (tvts_adamw_torch with skipped: one more single-lane launch, one uniform load and a branch per chunk).  both: the
 guarded beside the unguarded step in the SAME process, three rounds, each timing trainable = "all" and "head" without and then
 with the guard; the line's "summary" gives the guarded step over the unguarded step of the same round beside the spread of the
 unguarded rounds (max / min - 1): a difference inside that spread is not a measured difference.
@@ -536,7 +536,7 @@ def main():
                 args.guard_on = kind == "on"
                 rnd[kind] = {"trainable=" + t: run(t, args, clip, targets) for t in ("all", "head")}
             rounds.append(rnd)
-        out["guard"] = {"off": "FinetuneStep (tvts_adamw_torch)", "on": "FinetuneStep(skip_nonfinite=True) (tvts_adamw_torch_guard)"}
+        out["guard"] = {"off": "FinetuneStep (tvts_adamw_torch)", "on": "FinetuneStep(skip_nonfinite=True) (tvts_adamw_torch with skipped)"}
         out["rounds"] = rounds
         summary = {}
         for t in ("trainable=all", "trainable=head"):

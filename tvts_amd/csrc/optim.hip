@@ -7,18 +7,22 @@
 //                        byte table gives each chunk its parameter group (255 = frozen / padding).  The same pass
 //                        applies the data-parallel 1/world gradient scale and refreshes the bf16 weight shadow.
 //   tvts_adamw_torch     the same frame with torch.optim.AdamW arithmetic over up to 64 groups (the v1 fine-tuning step)
-//   tvts_adamw_torch_ema the same launch with timm's ModelEma rule applied to the new p while it is still in registers (one more
-//                        fp32 stream, 38 B per element); tvts_ema_update is the rule as a pass of its own (ModelEma.update)
-//   tvts_sgd_torch       torch.optim.SGD (momentum, Nesterov) in the same chunk frame with ONE state stream, bit for bit (the v1 linear
-//                        probe, 22 B per element); tvts_sgd_torch_ema carries the average as tvts_adamw_torch_ema does
-//   tvts_adamw_torch_guard / tvts_sgd_torch_guard   the four launches above under the overflow guard of the fine-tuning step: the update
-//                        happens only when the global gradient norm tvts_grad_sumsq left on the device is finite; else every bit of
-//                        p / m / v / shadow / average stays, the device step counter stays and a device counter of skips advances
+//   tvts_sgd_torch       torch.optim.SGD (momentum, Nesterov) in the same frame with ONE state stream, bit for bit (the v1 linear
+//                        probe, 22 B per element)
+//                        Both take two optional parts as nullable pointers.  `ema`: the launch applies timm's ModelEma rule to the
+//                        new p while it is still in registers (one more fp32 stream, + 8 B per element); tvts_ema_update is the rule
+//                        as a pass of its own (ModelEma.update).  `skipped`: the launch runs under the overflow guard of the
+//                        fine-tuning step -- the update happens only when the global gradient norm tvts_grad_sumsq left on the
+//                        device is finite; else every bit of p / state / shadow / average stays, the device step counter stays
+//                        and the device counter `skipped` advances
 //   tvts_swap_f32_shadow in-place exchange of two fp32 buffers + the bf16 shadow of the first (evaluation from the average)
 //   tvts_cast_f32_bf16   shadow refresh when an external optimizer owned the update (drop-in path)
 //   tvts_transpose_bf16_batched   [N,K] -> [K,N] copies of every GEMM weight (dgrad operand), one launch
 //   tvts_pad_rows_bf16 / tvts_add_rows_f32   K-padding of the 14x14 patch-embedding weight and its wgrad (H/14)
 #include "common.h"
+
+#include <initializer_list>
+#include <type_traits>
 
 // timm.utils.ModelEma.update per element: ema_v * decay + (1. - decay) * model_v on fp32 tensors with a Python-float decay, i.e.
 // three roundings and no FMA, d32 = fp32(decay), o32 = fp32(1.0 - decay) with the difference formed in DOUBLE on the host (the
@@ -34,38 +38,65 @@ __device__ __forceinline__ f32x4 ema_rule4(const f32x4& ev, const f32x4& pv, flo
     return r;
 }
 
-// The frame of the AdamW kernels: one block per 1024-element chunk, four elements per lane.  `prologue(grp)` runs once the
-// chunk is known to step (its group byte is below NGROUPS; a foreign group, 255 = frozen, keeps every bit) and returns the rule
-// that updates four elements of p / m / v from their gradients; the frame loads, stores and writes the bf16 shadow.  EMA: the
-// frame also carries the chunk's average through ema_rule4 from the final p (a compile-time choice: the instantiations without
-// an average are the code they were).  GUARD (compile time as well, tvts_adamw_torch_guard): the frame first tests the global
-// gradient norm `guard_norm[0]` -- one uniform load and one branch per block -- and a block that finds it not finite returns in
-// front of every load of p / m / v: the whole launch then keeps every bit of p, m, v, the shadow and the average.
+// The frame of the optimizer kernels: one block per 1024-element chunk, four elements per lane, 16-byte accesses.  The frame owns
+// the group gate (a chunk whose group byte is not below NGROUPS -- a foreign group, 255 = frozen -- keeps every bit), the guard
+// test, the element index, the loads and stores of p and g, the bf16 shadow and the average.  `prologue(grp)` runs once the chunk is
+// known to step and returns the rule: the hyper-parameters of the group, and the rule's own state streams as
+//     load(i)  /  update4(pv, gv)  /  store(i)        (StateStreams below: two moments for the AdamWs, one buffer or none for SGD)
+// EMA: the frame also carries the chunk's average through ema_rule4 from the final p (a compile-time choice: an instantiation
+// without an average neither loads nor tests `ema`).  GUARD (compile time as well): the frame first tests the global gradient norm
+// `guard_norm[0]` -- one uniform load and one branch per block -- and a block that finds it not finite returns in front of every
+// load of p or state: the whole launch then keeps every bit of p, the state, the shadow and the average.
 __device__ __forceinline__ bool finite_f32(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-template <int NGROUPS, bool EMA = false, bool GUARD = false, typename Prologue>
-__device__ __forceinline__ void adamw_chunk(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                            float* __restrict__ v, bf16* __restrict__ shadow,
-                                            const unsigned char* __restrict__ chunk_group, Prologue prologue,
-                                            float* __restrict__ ema = nullptr, float d32 = 0.f, float o32 = 0.f,
-                                            const float* __restrict__ guard_norm = nullptr) {
+template <int NGROUPS, bool EMA, bool GUARD, typename Prologue>
+__device__ __forceinline__ void optim_chunk(float* __restrict__ p, const float* __restrict__ g, bf16* __restrict__ shadow,
+                                            const unsigned char* __restrict__ chunk_group, float* __restrict__ ema, float d32,
+                                            float o32, const float* __restrict__ guard_norm, Prologue prologue) {
     const int grp = chunk_group[blockIdx.x];
     if (grp >= NGROUPS) return;
     if constexpr (GUARD) {
         if (!finite_f32(guard_norm[0])) return;
     }
-    const auto update4 = prologue(grp);
+    auto rule = prologue(grp);
     const size_t i = (size_t)blockIdx.x * 1024 + threadIdx.x * 4;
-    f32x4 pv = *(f32x4*)(p + i), mv = *(f32x4*)(m + i), vv = *(f32x4*)(v + i);
+    f32x4 pv = *(f32x4*)(p + i);
     const f32x4 gv = *(const f32x4*)(g + i);
+    rule.load(i);  // (behind g: with the state in front of it the SGD instantiations with momentum took two more VGPRs)
     f32x4 ev;
     if constexpr (EMA) ev = *(const f32x4*)(ema + i);
-    update4(pv, mv, vv, gv);
+    rule.update4(pv, gv);
     *(f32x4*)(p + i) = pv;
-    *(f32x4*)(m + i) = mv;
-    *(f32x4*)(v + i) = vv;
+    rule.store(i);
     if (shadow) *(bf16x4*)(shadow + i) = (bf16x4){(bf16)pv[0], (bf16)pv[1], (bf16)pv[2], (bf16)pv[3]};
     if constexpr (EMA) *(f32x4*)(ema + i) = ema_rule4(ev, pv, d32, o32);
 }
+
+// A rule's N state streams (fp32, the layout of p) around its four-element update `u(pv, state..., gv)`.  skip_load: the streams
+// are written without being read (SGD's first update).
+template <int N, typename Update4>
+struct StateStreams {
+    float* s[N ? N : 1];
+    bool skip_load;
+    Update4 u;
+    f32x4 sv[N ? N : 1];
+    __device__ __forceinline__ void load(size_t i) {
+        if (skip_load) return;
+#pragma unroll
+        for (int k = 0; k < N; ++k) sv[k] = *(const f32x4*)(s[k] + i);
+    }
+    __device__ __forceinline__ void update4(f32x4& pv, const f32x4& gv) {
+        if constexpr (N == 2) u(pv, sv[0], sv[1], gv);
+        else u(pv, sv[0], gv);
+    }
+    __device__ __forceinline__ void store(size_t i) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) *(f32x4*)(s[k] + i) = sv[k];
+    }
+};
+template <typename U>
+__device__ __forceinline__ StateStreams<2, U> two_streams(float* m, float* v, U u) { return {{m, v}, false, u}; }
+template <bool MOM, typename U>
+__device__ __forceinline__ StateStreams<MOM ? 1 : 0, U> one_stream(float* buf, bool skip_load, U u) { return {{buf}, skip_load, u}; }
 
 struct AdamGroups { float lr[4]; float wd[4]; float step_size[4]; };
 
@@ -75,7 +106,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
                                                     float beta2, float omb1, float omb2, float eps, float grad_scale,
                                                     const int* __restrict__ step_dev, const float* __restrict__ hyper_dev,
                                                     double beta1d, double beta2d) {
-    adamw_chunk<4>(p, g, m, v, shadow, chunk_group, [&](int grp) {
+    optim_chunk<4, false, false>(p, g, shadow, chunk_group, nullptr, 0.f, 0.f, nullptr, [&](int grp) {
         if (hyper_dev) {  // lr[4] | wd[4] in device memory: a captured launch follows the LR schedule without re-capture
             hp.lr[grp] = hyper_dev[grp];
             hp.wd[grp] = hyper_dev[4 + grp];
@@ -88,7 +119,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
             hp.step_size[grp] = (float)((double)hp.lr[grp] * sqrt(bc2) / bc1);
         }
         const float lr = hp.lr[grp], wd = hp.wd[grp], ss = hp.step_size[grp];
-        return [=](f32x4& pv, f32x4& mv, f32x4& vv, const f32x4& gv) {
+        return two_streams(m, v, [=](f32x4& pv, f32x4& mv, f32x4& vv, const f32x4& gv) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float gg = gv[e] * grad_scale;
@@ -97,7 +128,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
                 pv[e] -= ss * mv[e] / (sqrtf(vv[e]) + eps);
                 if (wd > 0.f) pv[e] -= lr * wd * pv[e];
             }
-        };
+        });
     });
 }
 
@@ -121,6 +152,38 @@ extern "C" int tvts_adamw_hf(float* p, const float* g, float* m, float* v, void*
     return TVTS_OK;
 }
 
+// ---- what the two torch rules share on the host
+// The overflow guard of the v1 fine-tuning step (FinetuneStep(skip_nonfinite=True)): GradScaler's "skip the update on inf / NaN"
+// decided on the device.  The decision is isfinite(norm_coef[0]), the global norm tvts_grad_sumsq left in device memory.  Two
+// launches: guard_advance_kernel (one lane) advances step_dev[0] on a finite norm and skipped[0] otherwise, then the guarded
+// instantiation of the rule runs -- with the step counter it would have had unguarded, or returning in every block.  A skipped
+// call leaves step_dev where it was: the bias corrections and SGD's first-update rule go on as if step() had not been called.
+__global__ void guard_advance_kernel(const float* __restrict__ norm_coef, int* __restrict__ step_dev, long* __restrict__ skipped) {
+    if (finite_f32(norm_coef[0])) step_dev[0] += 1;
+    else skipped[0] += 1;
+}
+static inline bool misaligned16(const void* q) { return ((uintptr_t)q & 15) != 0; }
+// The refusals of tvts_adamw_torch / tvts_sgd_torch.  streams: p, g and the state streams the launch touches -- each present and
+// 16-byte aligned.  ema (null: no average), shadow (null: none) and norm_coef (null: no coefficient) are optional; skipped (null:
+// unguarded) makes step_dev and norm_coef required and the host `step` irrelevant.
+static bool torch_args_bad(std::initializer_list<const void*> streams, const float* ema, const void* shadow,
+                           const unsigned char* chunk_group, int nchunks, const float* hyper_dev, int step, const int* step_dev,
+                           const float* norm_coef, const long* skipped, bool momentum, int nesterov) {
+    for (const void* q : streams)
+        if (!q || misaligned16(q)) return true;
+    if (!chunk_group || !hyper_dev || nchunks <= 0) return true;
+    if (misaligned16(ema) || ((uintptr_t)shadow & 7) || ((uintptr_t)skipped & 7) || ((uintptr_t)step_dev & 3) || ((uintptr_t)norm_coef & 3))
+        return true;
+    if (skipped ? (!step_dev || !norm_coef) : (step <= 0 && !step_dev)) return true;
+    return nesterov && !momentum;  // torch: "Nesterov momentum requires a momentum and zero dampening"
+}
+// a run-time choice as a compile-time one: f(std::true_type) or f(std::false_type)
+template <typename F>
+static void with_bool(bool b, F f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
 // ---- torch.optim.AdamW, multi-tensor (the v1 fine-tuning step)
 // The optimizer run_class_finetuning.py builds through optim_factory.create_optimizer (opt "adamw") over the layer-decay parameter
 // groups (28 of them on ViT-B).  Per element, in torch's order (torch/optim/adamw.py, single-tensor form):
@@ -132,24 +195,24 @@ extern "C" int tvts_adamw_hf(float* p, const float* g, float* m, float* v, void*
 // same device code either way, so both give the same bits.  g = stored gradient * grad_scale * norm_coef[1] (the clip coefficient
 // tvts_grad_sumsq left in device memory; no coefficient when norm_coef is null).  hyper_dev: lr[64] | wd[64] in device memory.
 // Chunk table as tvts_adamw_hf (1024 elements per chunk, one group byte each); a chunk of group >= 64 (255 = frozen) keeps every bit.
-// (one body, two kernels: the kernel without an average keeps its name, its arguments and its code)
-template <bool EMA, bool GUARD = false>
-__device__ __forceinline__ void adamw_torch_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                 float* __restrict__ v, bf16* __restrict__ shadow,
-                                                 const unsigned char* __restrict__ chunk_group,
-                                                 const float* __restrict__ hyper_dev, int step,
-                                                 const int* __restrict__ step_dev, double beta1d, double beta2d, float beta1,
-                                                 float beta2, float omb1, float omb2, float eps, float grad_scale,
-                                                 const float* __restrict__ norm_coef, float* __restrict__ ema, float d32, float o32) {
+template <bool EMA, bool GUARD>
+__global__ __launch_bounds__(256) void adamw_torch_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, bf16* __restrict__ shadow,
+                                                          const unsigned char* __restrict__ chunk_group,
+                                                          const float* __restrict__ hyper_dev, int step,
+                                                          const int* __restrict__ step_dev, double beta1d, double beta2d, float beta1,
+                                                          float beta2, float omb1, float omb2, float eps, float grad_scale,
+                                                          const float* __restrict__ norm_coef, float* __restrict__ ema, float d32,
+                                                          float o32) {
 #pragma clang fp contract(off)  // (lexical: it holds inside both lambdas; adamw_kernel has none and keeps its contractions)
-    adamw_chunk<64, EMA, GUARD>(p, g, m, v, shadow, chunk_group, [&](int grp) {
+    optim_chunk<64, EMA, GUARD>(p, g, shadow, chunk_group, ema, d32, o32, norm_coef, [&](int grp) {
         const float lr = hyper_dev[grp], wd = hyper_dev[64 + grp];
         const double st = (double)(step_dev ? step_dev[0] : step);
         const double bc1 = 1.0 - pow(beta1d, st), bc2 = 1.0 - pow(beta2d, st);
         const float decay = (float)(1.0 - (double)lr * (double)wd);
         const float ss = (float)((double)lr / bc1), rs = (float)sqrt(bc2);
         const float gs = norm_coef ? grad_scale * norm_coef[1] : grad_scale;
-        return [=](f32x4& pv, f32x4& mv, f32x4& vv, const f32x4& gv) {
+        return two_streams(m, v, [=](f32x4& pv, f32x4& mv, f32x4& vv, const f32x4& gv) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float gg = gv[e] * gs;
@@ -158,96 +221,24 @@ __device__ __forceinline__ void adamw_torch_body(float* __restrict__ p, const fl
                 vv[e] = beta2 * vv[e] + omb2 * gg * gg;
                 pv[e] -= ss * mv[e] / (sqrtf(vv[e]) / rs + eps);
             }
-        };
-    }, ema, d32, o32, norm_coef);
+        });
+    });
 }
-__global__ __launch_bounds__(256) void adamw_torch_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                          float* __restrict__ v, bf16* __restrict__ shadow,
-                                                          const unsigned char* __restrict__ chunk_group,
-                                                          const float* __restrict__ hyper_dev, int step,
-                                                          const int* __restrict__ step_dev, double beta1d, double beta2d, float beta1,
-                                                          float beta2, float omb1, float omb2, float eps, float grad_scale,
-                                                          const float* __restrict__ norm_coef) {
-    adamw_torch_body<false>(p, g, m, v, shadow, chunk_group, hyper_dev, step, step_dev, beta1d, beta2d, beta1, beta2, omb1, omb2, eps,
-                            grad_scale, norm_coef, nullptr, 0.f, 0.f);
-}
-__global__ __launch_bounds__(256) void adamw_torch_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                              float* __restrict__ v, bf16* __restrict__ shadow,
-                                                              const unsigned char* __restrict__ chunk_group,
-                                                              const float* __restrict__ hyper_dev, int step,
-                                                              const int* __restrict__ step_dev, double beta1d, double beta2d,
-                                                              float beta1, float beta2, float omb1, float omb2, float eps,
-                                                              float grad_scale, const float* __restrict__ norm_coef,
-                                                              float* __restrict__ ema, float d32, float o32) {
-    adamw_torch_body<true>(p, g, m, v, shadow, chunk_group, hyper_dev, step, step_dev, beta1d, beta2d, beta1, beta2, omb1, omb2, eps,
-                           grad_scale, norm_coef, ema, d32, o32);
-}
-static inline bool misaligned16(const void* q) { return ((uintptr_t)q & 15) != 0; }
 extern "C" int tvts_adamw_torch(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group,
-                                int nchunks, const float* hyper_dev, int step, const int* step_dev, double beta1, double beta2,
-                                double eps, float grad_scale, const float* norm_coef, hipStream_t stream) {
-    if (!p || !g || !m || !v || !chunk_group || !hyper_dev || nchunks <= 0 || (step <= 0 && !step_dev)) return TVTS_EINVAL;
-    hipLaunchKernelGGL(adamw_torch_kernel, dim3(nchunks), dim3(256), 0, stream, p, g, m, v, (bf16*)shadow_bf16, chunk_group,
-                       hyper_dev, step, step_dev, beta1, beta2, (float)beta1, (float)beta2, (float)(1.0 - beta1),
-                       (float)(1.0 - beta2), (float)eps, grad_scale, norm_coef);
-    TVTS_LAUNCH_CHECK();
-    return TVTS_OK;
-}
-extern "C" int tvts_adamw_torch_ema(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group,
-                                    int nchunks, const float* hyper_dev, int step, const int* step_dev, double beta1, double beta2,
-                                    double eps, float grad_scale, const float* norm_coef, float* ema, float d32, float o32,
-                                    hipStream_t stream) {
-    if (!p || !g || !m || !v || !ema || !chunk_group || !hyper_dev || nchunks <= 0 || (step <= 0 && !step_dev)) return TVTS_EINVAL;
-    if (misaligned16(p) || misaligned16(g) || misaligned16(m) || misaligned16(v) || misaligned16(ema) ||
-        ((uintptr_t)shadow_bf16 & 7)) return TVTS_EINVAL;
-    hipLaunchKernelGGL(adamw_torch_ema_kernel, dim3(nchunks), dim3(256), 0, stream, p, g, m, v, (bf16*)shadow_bf16, chunk_group,
-                       hyper_dev, step, step_dev, beta1, beta2, (float)beta1, (float)beta2, (float)(1.0 - beta1),
-                       (float)(1.0 - beta2), (float)eps, grad_scale, norm_coef, ema, d32, o32);
-    TVTS_LAUNCH_CHECK();
-    return TVTS_OK;
-}
-
-// ---- the overflow guard of the v1 fine-tuning step (FinetuneStep(skip_nonfinite=True)): GradScaler's "skip the update on inf / NaN"
-// decided on the device.  The decision is isfinite(norm_coef[0]), the global norm tvts_grad_sumsq left in device memory.  Two
-// launches: guard_advance_kernel (one lane) advances step_dev[0] on a finite norm and skipped[0] otherwise, then the guarded
-// instantiation of the chunk frame runs -- with the step counter it would have had unguarded, or returning in every block.  A skipped
-// call leaves step_dev where it was: the bias corrections and SGD's first-update rule go on as if step() had not been called.
-__global__ void guard_advance_kernel(const float* __restrict__ norm_coef, int* __restrict__ step_dev, long* __restrict__ skipped) {
-    if (finite_f32(norm_coef[0])) step_dev[0] += 1;
-    else skipped[0] += 1;
-}
-template <bool EMA>
-__global__ __launch_bounds__(256) void adamw_torch_guard_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                                float* __restrict__ v, bf16* __restrict__ shadow,
-                                                                const unsigned char* __restrict__ chunk_group,
-                                                                const float* __restrict__ hyper_dev, const int* __restrict__ step_dev,
-                                                                double beta1d, double beta2d, float beta1, float beta2, float omb1,
-                                                                float omb2, float eps, float grad_scale,
-                                                                const float* __restrict__ norm_coef, float* __restrict__ ema, float d32,
-                                                                float o32) {
-    adamw_torch_body<EMA, true>(p, g, m, v, shadow, chunk_group, hyper_dev, 0, step_dev, beta1d, beta2d, beta1, beta2, omb1, omb2, eps,
-                                grad_scale, norm_coef, ema, d32, o32);
-}
-static inline bool guard_args_bad(const int* step_dev, const float* norm_coef, const long* skipped) {
-    return !step_dev || !norm_coef || !skipped || ((uintptr_t)step_dev & 3) || ((uintptr_t)norm_coef & 3) || ((uintptr_t)skipped & 7);
-}
-extern "C" int tvts_adamw_torch_guard(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group,
-                                      int nchunks, const float* hyper_dev, int* step_dev, double beta1, double beta2, double eps,
-                                      float grad_scale, const float* norm_coef, long* skipped, float* ema, float d32, float o32,
-                                      hipStream_t stream) {
-    if (!p || !g || !m || !v || !chunk_group || !hyper_dev || nchunks <= 0 || guard_args_bad(step_dev, norm_coef, skipped))
+                                int nchunks, const float* hyper_dev, int step, int* step_dev, double beta1, double beta2, double eps,
+                                float grad_scale, const float* norm_coef, float* ema, float d32, float o32, long* skipped,
+                                hipStream_t stream) {
+    if (torch_args_bad({p, g, m, v}, ema, shadow_bf16, chunk_group, nchunks, hyper_dev, step, step_dev, norm_coef, skipped, false, 0))
         return TVTS_EINVAL;
-    if (misaligned16(p) || misaligned16(g) || misaligned16(m) || misaligned16(v) || misaligned16(ema) ||
-        ((uintptr_t)shadow_bf16 & 7)) return TVTS_EINVAL;
-    hipLaunchKernelGGL(guard_advance_kernel, dim3(1), dim3(1), 0, stream, norm_coef, step_dev, skipped);
-    if (ema)
-        hipLaunchKernelGGL(adamw_torch_guard_kernel<true>, dim3(nchunks), dim3(256), 0, stream, p, g, m, v, (bf16*)shadow_bf16,
-                           chunk_group, hyper_dev, step_dev, beta1, beta2, (float)beta1, (float)beta2, (float)(1.0 - beta1),
-                           (float)(1.0 - beta2), (float)eps, grad_scale, norm_coef, ema, d32, o32);
-    else
-        hipLaunchKernelGGL(adamw_torch_guard_kernel<false>, dim3(nchunks), dim3(256), 0, stream, p, g, m, v, (bf16*)shadow_bf16,
-                           chunk_group, hyper_dev, step_dev, beta1, beta2, (float)beta1, (float)beta2, (float)(1.0 - beta1),
-                           (float)(1.0 - beta2), (float)eps, grad_scale, norm_coef, nullptr, 0.f, 0.f);
+    if (skipped) hipLaunchKernelGGL(guard_advance_kernel, dim3(1), dim3(1), 0, stream, norm_coef, step_dev, skipped);
+    with_bool(ema != nullptr, [&](auto E) {
+        with_bool(skipped != nullptr, [&](auto G) {
+            hipLaunchKernelGGL((adamw_torch_kernel<decltype(E)::value, decltype(G)::value>), dim3(nchunks), dim3(256), 0, stream, p, g,
+                               m, v, (bf16*)shadow_bf16, chunk_group, hyper_dev, step, step_dev, beta1, beta2, (float)beta1,
+                               (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, grad_scale, norm_coef, ema, d32,
+                               o32);
+        });
+    });
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;
 }
@@ -278,128 +269,58 @@ extern "C" int tvts_ema_update(float* ema, const float* p, const unsigned char* 
 //               d   = nesterov ? fmaf(mu, buf, d) : buf
 //     p  = fmaf(-lr, d, p)                           param.add_(d_p, alpha=-lr)
 // The step counter (step_dev[0] when given, else `step`: the same device code) only says whether this is the first update, t == 1:
-// buf is then written and not read.  MOM = false (momentum 0): buf is neither read nor written.  A sibling of adamw_chunk with one
-// state stream instead of two: the same chunk gate, the same 16-byte accesses, the shadow and the average as there.
-template <bool MOM, bool EMA, bool GUARD = false>
-__device__ __forceinline__ void sgd_torch_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                               bf16* __restrict__ shadow, const unsigned char* __restrict__ chunk_group,
-                                               const float* __restrict__ hyper_dev, int step, const int* __restrict__ step_dev,
-                                               float mu, int nesterov, float grad_scale, const float* __restrict__ norm_coef,
-                                               float* __restrict__ ema, float d32, float o32) {
-#pragma clang fp contract(off)  // (the FMAs below are explicit calls; fl(mu * buf) + d must stay two roundings)
-    const int grp = chunk_group[blockIdx.x];
-    if (grp >= 64) return;
-    if constexpr (GUARD) {  // (as adamw_chunk: the norm's own pointer, one uniform load, in front of every load of p / buf)
-        if (!finite_f32(norm_coef[0])) return;
-    }
-    const float lr = hyper_dev[grp], wd = hyper_dev[64 + grp];
-    const bool first = (step_dev ? step_dev[0] : step) == 1;
-    const float gs = norm_coef ? grad_scale * norm_coef[1] : grad_scale;
-    const float nlr = -lr;
-    const size_t i = (size_t)blockIdx.x * 1024 + threadIdx.x * 4;
-    f32x4 pv = *(f32x4*)(p + i), bv, ev;
-    const f32x4 gv = *(const f32x4*)(g + i);
-    if constexpr (MOM) {
-        if (!first) bv = *(const f32x4*)(buf + i);
-    }
-    if constexpr (EMA) ev = *(const f32x4*)(ema + i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float gg = gv[e] * gs;
-        float d = wd != 0.f ? __builtin_fmaf(wd, pv[e], gg) : gg;
-        if constexpr (MOM) {
-            float b = d;
-            if (!first) {
-                const float mb = mu * bv[e];
-                b = mb + d;
-            }
-            bv[e] = b;
-            d = nesterov ? __builtin_fmaf(mu, b, d) : b;
-        }
-        pv[e] = __builtin_fmaf(nlr, d, pv[e]);
-    }
-    *(f32x4*)(p + i) = pv;
-    if constexpr (MOM) *(f32x4*)(buf + i) = bv;
-    if (shadow) *(bf16x4*)(shadow + i) = (bf16x4){(bf16)pv[0], (bf16)pv[1], (bf16)pv[2], (bf16)pv[3]};
-    if constexpr (EMA) *(f32x4*)(ema + i) = ema_rule4(ev, pv, d32, o32);
-}
-template <bool MOM, bool EMA>
+// buf is then written and not read.  MOM = false (momentum 0): buf is neither read nor written.  Under the guard a skipped call 1
+// leaves step_dev at 0, so the next call is the first update.
+template <bool MOM, bool EMA, bool GUARD>
 __global__ __launch_bounds__(256) void sgd_torch_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
                                                         bf16* __restrict__ shadow, const unsigned char* __restrict__ chunk_group,
                                                         const float* __restrict__ hyper_dev, int step,
                                                         const int* __restrict__ step_dev, float mu, int nesterov, float grad_scale,
                                                         const float* __restrict__ norm_coef, float* __restrict__ ema, float d32,
                                                         float o32) {
-    sgd_torch_body<MOM, EMA>(p, g, buf, shadow, chunk_group, hyper_dev, step, step_dev, mu, nesterov, grad_scale, norm_coef, ema, d32,
-                             o32);
-}
-template <bool MOM, bool EMA>
-__global__ __launch_bounds__(256) void sgd_torch_guard_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                              bf16* __restrict__ shadow, const unsigned char* __restrict__ chunk_group,
-                                                              const float* __restrict__ hyper_dev, const int* __restrict__ step_dev,
-                                                              float mu, int nesterov, float grad_scale,
-                                                              const float* __restrict__ norm_coef, float* __restrict__ ema, float d32,
-                                                              float o32) {
-    sgd_torch_body<MOM, EMA, true>(p, g, buf, shadow, chunk_group, hyper_dev, 0, step_dev, mu, nesterov, grad_scale, norm_coef, ema,
-                                   d32, o32);
-}
-template <bool EMA>
-static int sgd_torch_launch(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
-                            const float* hyper_dev, int step, const int* step_dev, double momentum, int nesterov, float grad_scale,
-                            const float* norm_coef, float* ema, float d32, float o32, hipStream_t stream) {
-    const float mu = (float)momentum;
-    const bool mom = mu != 0.f;
-    if (!p || !g || (mom && !buf) || (EMA && !ema) || !chunk_group || !hyper_dev || nchunks <= 0 || (step <= 0 && !step_dev))
-        return TVTS_EINVAL;
-    if (nesterov && !mom) return TVTS_EINVAL;  // torch: "Nesterov momentum requires a momentum and zero dampening"
-    if (misaligned16(p) || misaligned16(g) || (mom && misaligned16(buf)) || (EMA && misaligned16(ema)) ||
-        ((uintptr_t)shadow_bf16 & 7)) return TVTS_EINVAL;
-    if (mom)
-        hipLaunchKernelGGL((sgd_torch_kernel<true, EMA>), dim3(nchunks), dim3(256), 0, stream, p, g, buf, (bf16*)shadow_bf16,
-                           chunk_group, hyper_dev, step, step_dev, mu, nesterov ? 1 : 0, grad_scale, norm_coef, ema, d32, o32);
-    else
-        hipLaunchKernelGGL((sgd_torch_kernel<false, EMA>), dim3(nchunks), dim3(256), 0, stream, p, g, buf, (bf16*)shadow_bf16,
-                           chunk_group, hyper_dev, step, step_dev, mu, 0, grad_scale, norm_coef, ema, d32, o32);
-    TVTS_LAUNCH_CHECK();
-    return TVTS_OK;
+#pragma clang fp contract(off)  // (the FMAs below are explicit calls; fl(mu * buf) + d must stay two roundings)
+    optim_chunk<64, EMA, GUARD>(p, g, shadow, chunk_group, ema, d32, o32, norm_coef, [&](int grp) {
+        const float lr = hyper_dev[grp], wd = hyper_dev[64 + grp];
+        const bool first = (step_dev ? step_dev[0] : step) == 1;
+        const float gs = norm_coef ? grad_scale * norm_coef[1] : grad_scale;
+        const float nlr = -lr;
+        return one_stream<MOM>(buf, first, [=](f32x4& pv, f32x4& bv, const f32x4& gv) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float gg = gv[e] * gs;
+                float d = wd != 0.f ? __builtin_fmaf(wd, pv[e], gg) : gg;
+                if constexpr (MOM) {
+                    float b = d;
+                    if (!first) {
+                        const float mb = mu * bv[e];
+                        b = mb + d;
+                    }
+                    bv[e] = b;
+                    d = nesterov ? __builtin_fmaf(mu, b, d) : b;
+                }
+                pv[e] = __builtin_fmaf(nlr, d, pv[e]);
+            }
+        });
+    });
 }
 extern "C" int tvts_sgd_torch(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
-                              const float* hyper_dev, int step, const int* step_dev, double momentum, int nesterov, float grad_scale,
-                              const float* norm_coef, hipStream_t stream) {
-    return sgd_torch_launch<false>(p, g, buf, shadow_bf16, chunk_group, nchunks, hyper_dev, step, step_dev, momentum, nesterov,
-                                   grad_scale, norm_coef, nullptr, 0.f, 0.f, stream);
-}
-extern "C" int tvts_sgd_torch_ema(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group,
-                                  int nchunks, const float* hyper_dev, int step, const int* step_dev, double momentum, int nesterov,
-                                  float grad_scale, const float* norm_coef, float* ema, float d32, float o32, hipStream_t stream) {
-    return sgd_torch_launch<true>(p, g, buf, shadow_bf16, chunk_group, nchunks, hyper_dev, step, step_dev, momentum, nesterov,
-                                  grad_scale, norm_coef, ema, d32, o32, stream);
-}
-// tvts_sgd_torch under the overflow guard (see tvts_adamw_torch_guard): guard_advance_kernel, then the guarded frame.  A skipped
-// call 1 leaves step_dev at 0, so the next call is the first update and writes the buffer without reading it.
-template <bool MOM, bool EMA>
-static void sgd_torch_guard_go(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group, int nchunks,
-                               const float* hyper_dev, const int* step_dev, float mu, int nesterov, float grad_scale,
-                               const float* norm_coef, float* ema, float d32, float o32, hipStream_t stream) {
-    hipLaunchKernelGGL((sgd_torch_guard_kernel<MOM, EMA>), dim3(nchunks), dim3(256), 0, stream, p, g, buf, (bf16*)shadow_bf16,
-                       chunk_group, hyper_dev, step_dev, mu, nesterov, grad_scale, norm_coef, ema, d32, o32);
-}
-extern "C" int tvts_sgd_torch_guard(float* p, const float* g, float* buf, void* shadow_bf16, const unsigned char* chunk_group,
-                                    int nchunks, const float* hyper_dev, int* step_dev, double momentum, int nesterov, float grad_scale,
-                                    const float* norm_coef, long* skipped, float* ema, float d32, float o32, hipStream_t stream) {
+                              const float* hyper_dev, int step, int* step_dev, double momentum, int nesterov, float grad_scale,
+                              const float* norm_coef, float* ema, float d32, float o32, long* skipped, hipStream_t stream) {
     const float mu = (float)momentum;
     const bool mom = mu != 0.f;
-    if (!p || !g || (mom && !buf) || !chunk_group || !hyper_dev || nchunks <= 0 || guard_args_bad(step_dev, norm_coef, skipped))
+    if (torch_args_bad({p, g, mom ? buf : p /* momentum 0: buf is no stream of this launch */}, ema, shadow_bf16, chunk_group, nchunks, hyper_dev, step, step_dev, norm_coef, skipped, mom,
+                       nesterov))
         return TVTS_EINVAL;
-    if (nesterov && !mom) return TVTS_EINVAL;
-    if (misaligned16(p) || misaligned16(g) || (mom && misaligned16(buf)) || misaligned16(ema) || ((uintptr_t)shadow_bf16 & 7))
-        return TVTS_EINVAL;
-    hipLaunchKernelGGL(guard_advance_kernel, dim3(1), dim3(1), 0, stream, norm_coef, step_dev, skipped);
-    const int nes = nesterov ? 1 : 0;
-    if (mom && ema) sgd_torch_guard_go<true, true>(p, g, buf, shadow_bf16, chunk_group, nchunks, hyper_dev, step_dev, mu, nes, grad_scale, norm_coef, ema, d32, o32, stream);
-    else if (mom) sgd_torch_guard_go<true, false>(p, g, buf, shadow_bf16, chunk_group, nchunks, hyper_dev, step_dev, mu, nes, grad_scale, norm_coef, nullptr, 0.f, 0.f, stream);
-    else if (ema) sgd_torch_guard_go<false, true>(p, g, buf, shadow_bf16, chunk_group, nchunks, hyper_dev, step_dev, mu, 0, grad_scale, norm_coef, ema, d32, o32, stream);
-    else sgd_torch_guard_go<false, false>(p, g, buf, shadow_bf16, chunk_group, nchunks, hyper_dev, step_dev, mu, 0, grad_scale, norm_coef, nullptr, 0.f, 0.f, stream);
+    if (skipped) hipLaunchKernelGGL(guard_advance_kernel, dim3(1), dim3(1), 0, stream, norm_coef, step_dev, skipped);
+    with_bool(mom, [&](auto M) {
+        with_bool(ema != nullptr, [&](auto E) {
+            with_bool(skipped != nullptr, [&](auto G) {
+                hipLaunchKernelGGL((sgd_torch_kernel<decltype(M)::value, decltype(E)::value, decltype(G)::value>), dim3(nchunks),
+                                   dim3(256), 0, stream, p, g, buf, (bf16*)shadow_bf16, chunk_group, hyper_dev, step, step_dev, mu,
+                                   nesterov ? 1 : 0, grad_scale, norm_coef, ema, d32, o32);
+            });
+        });
+    });
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;
 }

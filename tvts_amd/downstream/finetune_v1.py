@@ -38,7 +38,7 @@ torch.optim.SGD(momentum=args.momentum, nesterov=True) and `momentum` to the sam
     out = step.step(samples, targets)
 
 FusedTorchSGD (tvts_amd/optim.py) is torch.optim.SGD's single-tensor arithmetic bit for bit -- every add(x, alpha=a) of it is one
-fused multiply-add -- as one launch over the flat store (tvts_sgd_torch; with a ModelEma, tvts_sgd_torch_ema): 22 B per trained
+fused multiply-add -- as one launch over the flat store (tvts_sgd_torch; with a ModelEma, its ema argument): 22 B per trained
 element with momentum against AdamW's 30.  Its state is torch's (``momentum_buffer``), so checkpoints travel both ways.
 
 The per-sample augmentation behind RandAugment (ssv2.py:186-227: Normalize, random-resized crop, flip, random erasing; on in the
@@ -109,7 +109,7 @@ Averaged weights (--model_ema, run_class_finetuning.py:55-58,345-352; engine_for
 Not a second model: ONE fp32 buffer with the flat store's layout.  The rule is timm's expression ``ema * decay + (1. - decay) * p`` on
 fp32 tensors with a Python-float decay, bit for bit: ema' = fl(fl(ema * d32) + fl(o32 * p)), d32 = fp32(decay), o32 = fp32(1.0 -
 decay) with the difference formed in double (hip.ema_pair).  With a FinetuneStep it rides in the optimizer's launch
-(tvts_adamw_torch_ema, 38 instead of 30 B per trained element); ``update(model)`` is the same rule as a launch of its own
+(tvts_adamw_torch with ema, 38 instead of 30 B per trained element); ``update(model)`` is the same rule as a launch of its own
 (tvts_ema_update) for a loop that calls it the way the reference does.  A chunk the optimizer does not step (group byte 255: the
 whole tower under trainable="head", and padding) keeps every bit of its average, which is the parameter's value -- timm would let
 it drift.  ``applied()`` exchanges the masters and the average in place (tvts_swap_f32_shadow) and re-derives the
@@ -131,7 +131,7 @@ skip_nonfinite=True is GradScaler's "skip the update on inf / NaN", decided on t
 norm (tvts_grad_sumsq's norm_coef[0]: over the trainable chunks, behind the all-reduce, 1 / W folded in) is not finite keeps every
 bit of the masters, the moments (the momentum buffer), the shadows and the average, leaves the optimizer's device step counter where
 it was and counts in ``step.skipped`` (device int64); the gradients are zeroed and grad_norm is returned as it is.  With a finite
-norm the update is the unguarded update bit for bit.  The guarded kernels (tvts_adamw_torch_guard / tvts_sgd_torch_guard) are the
+norm the update is the unguarded update bit for bit.  The guarded launches (tvts_adamw_torch / tvts_sgd_torch with skipped) are the
 chunk frames with one uniform load of the norm and a branch per block in front of every load of p / m / v; a one-lane kernel in
 front of them advances the step counter or ``skipped``.  Every rank sees the same norm, so every rank decides alike and no
 collective is added.  train_one_epoch reads the step's device scalars in one transfer every print_freq micro-steps, not on each
@@ -192,27 +192,10 @@ def param_groups(model, weight_decay, layer_decay=1.0, skip_list=None, trainable
     ``layer_%d_no_decay``.  No decay: 1-D tensors, ``*.bias`` and the skip list (default: model.no_weight_decay()).  As in the
     script, layer ids are assigned only with layer_decay < 1 (:369-372); without, the groups are ``decay`` / ``no_decay`` with
     lr_scale 1.  trainable "head": the parameters run_class_linear.py leaves trainable (:342-346)."""
-    flags = model.set_trainable(trainable)
-    skip = model.no_weight_decay() if skip_list is None else skip_list
-    depth = model.arch["layers"]
-    scales = layer_scales(depth, layer_decay) if layer_decay < 1.0 else None
-    groups = {}
-    for name, p in model.named_parameters():
-        if not flags[name]:
-            continue  # frozen weights
-        no_decay = p.dim() == 1 or name.endswith(".bias") or name in skip
-        gname = "no_decay" if no_decay else "decay"
-        scale = 1.0
-        if scales is not None:
-            lid = num_layer_for_vit(name, len(scales))
-            gname, scale = "layer_%d_%s" % (lid, gname), scales[lid]
-        g = groups.get(gname)
-        if g is None:
-            g = groups[gname] = dict(name=gname, weight_decay=0.0 if no_decay else weight_decay, params=[], param_names=[],
-                                     lr_scale=scale)
-        g["params"].append(p)
-        g["param_names"].append(name)
-    return list(groups.values())
+    if not layer_decay < 1.0:
+        return _factory_groups(model, weight_decay, skip_list, None, None, trainable)
+    assigner = LayerDecayValueAssigner(layer_scales(model.arch["layers"], layer_decay))
+    return _factory_groups(model, weight_decay, skip_list, assigner.get_layer_id, assigner.get_scale, trainable)
 
 
 class LayerDecayValueAssigner:
@@ -271,17 +254,15 @@ def create_optimizer(args, model, get_num_layer=None, get_layer_scale=None, filt
 
 
 def _factory_groups(model, weight_decay, skip_list, get_num_layer, get_layer_scale, trainable):
-    """get_parameter_groups (:51-90) as create_optimizer calls it: ``param_groups`` without the two callables (groups ``decay`` /
-    ``no_decay``, lr_scale 1); with them the same rule name by name, layer ids and scales from the callables (a
+    """get_parameter_groups (:51-90) as create_optimizer calls it, the one builder of the groups: without the two callables the
+    groups are ``decay`` / ``no_decay`` with lr_scale 1; with them layer ids and scales come from the callables (a
     LayerDecayValueAssigner's give the groups of ``param_groups(..., layer_decay)``)"""
-    if get_num_layer is None and get_layer_scale is None:
-        return param_groups(model, weight_decay, 1.0, skip_list=skip_list, trainable=trainable)
     flags = model.set_trainable(trainable)
     skip = model.no_weight_decay() if skip_list is None else skip_list
     groups = {}
     for name, p in model.named_parameters():
         if not flags[name]:
-            continue
+            continue  # frozen weights
         no_decay = p.dim() == 1 or name.endswith(".bias") or name in skip
         gname, lid = "no_decay" if no_decay else "decay", None
         if get_num_layer is not None:

@@ -1408,104 +1408,58 @@ def ema_pair(decay):
     return ctypes.c_float(decay).value, ctypes.c_float(1.0 - decay).value  # (the C cast: round to nearest even, once each)
 
 
-def adamw_torch(p, g, m, v, shadow, chunk_group, hyper_dev, step, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, step_dev=None,
-                norm_coef=None, ema=None, ema_decay=None):
-    """one torch.optim.AdamW step over the flat buffers; hyper_dev: device fp32 lr[64] | wd[64].  ema (fp32, the layout of p) with
-    ema_decay: the same pass applies ModelEma's rule to the new p (tvts_adamw_torch_ema, 38 B per element); None: the launch of
-    before."""
+def _torch_rule(label, per, streams, shadow, chunk_group, hyper_dev, step_dev, norm_coef, ema, ema_decay, skipped):
+    """What adamw_torch and sgd_torch share: the buffer asserts, the ema / ema_decay pairing, the guard's cells and the traffic figure
+    (`per` bytes per stepped element without the average, which adds 8; under the guard an upper bound: a skipped launch moves no
+    parameter bytes) -> (the _hbm context of the launch, the entry point's trailing arguments ema, d32, o32, skipped, stream)"""
     n = chunk_group.numel()
-    assert hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= 128
-    assert all(t.numel() >= n * 1024 for t in (p, g, m, v)) and (shadow is None or shadow.numel() >= n * 1024)
-    if ema is None:
-        if ema_decay is not None:
-            raise ValueError("ema_decay without ema")
-        with _hbm("adamw", _adamw_bytes(chunk_group, 64)):
-            rc = _lib.load().tvts_adamw_torch(_p(p), _p(g), _p(m), _p(v), _p(shadow), _p(chunk_group), n, _p(hyper_dev), int(step),
-                                              _p(step_dev), beta1, beta2, eps, grad_scale, _p(norm_coef), _stream())
-        _chk(rc, "tvts_adamw_torch")
-        return
-    if ema_decay is None:
-        raise ValueError("ema needs ema_decay")
-    d32, o32 = ema_pair(ema_decay)
-    assert ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() >= n * 1024 and ema.device == p.device
-    with _hbm("adamw", lambda: 38.0 * 1024 * float((chunk_group < 64).sum())):
-        rc = _lib.load().tvts_adamw_torch_ema(_p(p), _p(g), _p(m), _p(v), _p(shadow), _p(chunk_group), n, _p(hyper_dev), int(step),
-                                              _p(step_dev), beta1, beta2, eps, grad_scale, _p(norm_coef), _p(ema), d32, o32, _stream())
-    _chk(rc, "tvts_adamw_torch_ema")
+    assert chunk_group.dtype == torch.uint8 and hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= 128
+    assert all(t.dtype == torch.float32 and t.numel() >= n * 1024 for t in streams) and (shadow is None or shadow.numel() >= n * 1024)
+    if (ema is None) != (ema_decay is None):
+        raise ValueError("ema_decay without ema" if ema is None else "ema needs ema_decay")
+    d32, o32 = (0.0, 0.0) if ema is None else ema_pair(ema_decay)
+    assert ema is None or (ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() >= n * 1024 and ema.device == streams[0].device)
+    if skipped is not None:
+        if step_dev is None or norm_coef is None:
+            raise ValueError("skipped (the guarded launch) needs step_dev and norm_coef")
+        _guard_cells(step_dev, skipped, norm_coef)
+    per += 0.0 if ema is None else 8.0
+    return _hbm(label, lambda: per * 1024 * float((chunk_group < 64).sum())), (_p(ema), d32, o32, _p(skipped), _stream())
+
+
+def adamw_torch(p, g, m, v, shadow, chunk_group, hyper_dev, step, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, step_dev=None,
+                norm_coef=None, ema=None, ema_decay=None, skipped=None):
+    """one torch.optim.AdamW step over the flat buffers (tvts_adamw_torch, 30 B per element); hyper_dev: device fp32 lr[64] | wd[64].
+    ema (fp32, the layout of p) with ema_decay: the same pass applies ModelEma's rule to the new p (38 B per element).  skipped
+    (device int64, with step_dev and norm_coef): the launch under the overflow guard -- norm_coef[0] finite: step_dev[0] += 1, then
+    the update with that device step count, bit for bit; not finite: p, m, v, the shadow and the average keep every bit, step_dev
+    stays, skipped[0] += 1.  `step` is then ignored."""
+    hbm, tail = _torch_rule("adamw", 30.0, (p, g, m, v), shadow, chunk_group, hyper_dev, step_dev, norm_coef, ema, ema_decay, skipped)
+    with hbm:
+        rc = _lib.load().tvts_adamw_torch(_p(p), _p(g), _p(m), _p(v), _p(shadow), _p(chunk_group), chunk_group.numel(), _p(hyper_dev),
+                                          int(step), _p(step_dev), beta1, beta2, eps, grad_scale, _p(norm_coef), *tail)
+    _chk(rc, "tvts_adamw_torch")
 
 
 def sgd_torch(p, g, buf, shadow, chunk_group, hyper_dev, step, momentum=0.0, nesterov=False, grad_scale=1.0, step_dev=None,
-              norm_coef=None, ema=None, ema_decay=None):
-    """one torch.optim.SGD step (dampening 0) over the flat buffers, bit for bit; hyper_dev: device fp32 lr[64] | wd[64].  buf: the
-    momentum buffer (None with momentum 0: not touched); step == 1 (or step_dev[0] == 1) is the first update, which writes buf
-    without reading it.  ema / ema_decay as adamw_torch (tvts_sgd_torch_ema).  Bytes per stepped element: p 8, g 4, shadow 2,
-    buf 8 (4 on the first update, 0 without momentum), the average 8."""
-    n = chunk_group.numel()
-    assert chunk_group.dtype == torch.uint8
-    assert hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= 128
+              norm_coef=None, ema=None, ema_decay=None, skipped=None):
+    """one torch.optim.SGD step (dampening 0) over the flat buffers, bit for bit (tvts_sgd_torch); hyper_dev: device fp32 lr[64] |
+    wd[64].  buf: the momentum buffer (None with momentum 0: not touched); step == 1 (or step_dev[0] == 1) is the first update,
+    which writes buf without reading it.  ema / ema_decay / skipped as adamw_torch; a skipped first call leaves step_dev at 0, so the
+    next call is then the first update.  Bytes per stepped element: p 8, g 4, shadow 2, buf 8 (4 on the first update, 0 without
+    momentum), the average 8."""
     mom = ctypes.c_float(float(momentum)).value != 0.0
-    assert all(t.dtype == torch.float32 and t.numel() >= n * 1024 for t in (p, g) + ((buf,) if buf is not None else ()))
-    assert shadow is None or shadow.numel() >= n * 1024
-    if (ema is None) != (ema_decay is None):
-        raise ValueError("ema_decay without ema" if ema is None else "ema needs ema_decay")
-    per = 14.0 + (8.0 if mom else 0.0) + (0.0 if ema is None else 8.0)
-    args = (_p(p), _p(g), _p(buf), _p(shadow), _p(chunk_group), n, _p(hyper_dev), int(step), _p(step_dev), float(momentum),
-            1 if nesterov else 0, grad_scale, _p(norm_coef))
-    with _hbm("sgd", lambda: per * 1024 * float((chunk_group < 64).sum())):
-        if ema is None:
-            name, rc = "tvts_sgd_torch", _lib.load().tvts_sgd_torch(*args, _stream())
-        else:
-            d32, o32 = ema_pair(ema_decay)
-            assert ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() >= n * 1024 and ema.device == p.device
-            name, rc = "tvts_sgd_torch_ema", _lib.load().tvts_sgd_torch_ema(*args, _p(ema), d32, o32, _stream())
-    _chk(rc, name)
+    hbm, tail = _torch_rule("sgd", 22.0 if mom else 14.0, (p, g) + ((buf,) if buf is not None else ()), shadow, chunk_group, hyper_dev,
+                            step_dev, norm_coef, ema, ema_decay, skipped)
+    with hbm:
+        rc = _lib.load().tvts_sgd_torch(_p(p), _p(g), _p(buf), _p(shadow), _p(chunk_group), chunk_group.numel(), _p(hyper_dev), int(step),
+                                        _p(step_dev), float(momentum), 1 if nesterov else 0, grad_scale, _p(norm_coef), *tail)
+    _chk(rc, "tvts_sgd_torch")
 
 
 def _guard_cells(step_dev, skipped, norm_coef):
     assert step_dev.dtype == torch.int32 and step_dev.numel() >= 1 and skipped.dtype == torch.int64 and skipped.numel() >= 1
     assert norm_coef.dtype == torch.float32 and norm_coef.numel() >= 2
-
-
-def adamw_torch_guard(p, g, m, v, shadow, chunk_group, hyper_dev, step_dev, skipped, norm_coef, beta1=0.9, beta2=0.999, eps=1e-8,
-                      grad_scale=1.0, ema=None, ema_decay=None):
-    """adamw_torch under the overflow guard (tvts_adamw_torch_guard): norm_coef[0] finite -- step_dev[0] += 1, then the update of
-    adamw_torch with that device step count, bit for bit; not finite -- p, m, v, the shadow and the average keep every bit, step_dev
-    stays, skipped[0] (device int64) += 1.  ema / ema_decay as adamw_torch."""
-    n = chunk_group.numel()
-    assert chunk_group.dtype == torch.uint8 and hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= 128
-    assert all(t.dtype == torch.float32 and t.numel() >= n * 1024 for t in (p, g, m, v)) and (shadow is None or shadow.numel() >= n * 1024)
-    _guard_cells(step_dev, skipped, norm_coef)
-    if (ema is None) != (ema_decay is None):
-        raise ValueError("ema_decay without ema" if ema is None else "ema needs ema_decay")
-    d32, o32 = (0.0, 0.0) if ema is None else ema_pair(ema_decay)
-    assert ema is None or (ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() >= n * 1024 and ema.device == p.device)
-    per = 30.0 if ema is None else 38.0  # (an upper bound: a skipped launch moves no parameter bytes)
-    with _hbm("adamw", lambda: per * 1024 * float((chunk_group < 64).sum())):
-        rc = _lib.load().tvts_adamw_torch_guard(_p(p), _p(g), _p(m), _p(v), _p(shadow), _p(chunk_group), n, _p(hyper_dev), _p(step_dev),
-                                                beta1, beta2, eps, grad_scale, _p(norm_coef), _p(skipped), _p(ema), d32, o32, _stream())
-    _chk(rc, "tvts_adamw_torch_guard")
-
-
-def sgd_torch_guard(p, g, buf, shadow, chunk_group, hyper_dev, step_dev, skipped, norm_coef, momentum=0.0, nesterov=False,
-                    grad_scale=1.0, ema=None, ema_decay=None):
-    """sgd_torch under the overflow guard (tvts_sgd_torch_guard), as adamw_torch_guard.  A skipped first call leaves step_dev at 0:
-    the next call is then the first update and writes buf without reading it."""
-    n = chunk_group.numel()
-    assert chunk_group.dtype == torch.uint8 and hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= 128
-    mom = ctypes.c_float(float(momentum)).value != 0.0
-    assert all(t.dtype == torch.float32 and t.numel() >= n * 1024 for t in (p, g) + ((buf,) if buf is not None else ()))
-    assert shadow is None or shadow.numel() >= n * 1024
-    _guard_cells(step_dev, skipped, norm_coef)
-    if (ema is None) != (ema_decay is None):
-        raise ValueError("ema_decay without ema" if ema is None else "ema needs ema_decay")
-    d32, o32 = (0.0, 0.0) if ema is None else ema_pair(ema_decay)
-    assert ema is None or (ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() >= n * 1024 and ema.device == p.device)
-    per = 14.0 + (8.0 if mom else 0.0) + (0.0 if ema is None else 8.0)
-    with _hbm("sgd", lambda: per * 1024 * float((chunk_group < 64).sum())):
-        rc = _lib.load().tvts_sgd_torch_guard(_p(p), _p(g), _p(buf), _p(shadow), _p(chunk_group), n, _p(hyper_dev), _p(step_dev),
-                                              float(momentum), 1 if nesterov else 0, grad_scale, _p(norm_coef), _p(skipped), _p(ema),
-                                              d32, o32, _stream())
-    _chk(rc, "tvts_sgd_torch_guard")
 
 
 def ema_update(ema, p, chunk_group, decay):

@@ -1,7 +1,8 @@
 """Fused multi-tensor optimizers over the flat parameter store: ``step()`` is ONE kernel launch over the flat buffers.
 
 ``_FlatOptimizer`` holds what all of them share (chunk table, lr / weight_decay device table, step counters, ``_begin`` /
-``_finish``, the shadow refresh); ``_FlatAdamW`` adds what the two AdamWs share (moments, state views, checkpoints).
+``_finish``, the shadow refresh); ``_FlatAdamW`` adds what the two AdamWs share (moments, state views, checkpoints), ``_TorchRule``
+what the two torch rules share (``norm_coef``, ``ema``, the body of ``step(closure, device_step, guard)``).
 
 ``FusedHFAdamW`` replaces ``transformers.AdamW(params=optimizer_grouped_parameters)`` built at
 v2/train_dist_TVTSv2_ViT_B_16.py:118-125 (defaults betas (0.9, 0.999), eps 1e-6, correct_bias=True).
@@ -11,7 +12,7 @@ All are ``torch.optim.Optimizer``s, so param_groups / state_dict keep the refere
 (AdamW: ``state[p] = {step, exp_avg, exp_avg_sq}``, SGD: ``state[p] = {momentum_buffer}``; views of the flat state buffers).
 
 ``FusedTorchAdamW.step(guard=True)`` / ``FusedTorchSGD.step(guard=True)`` are the same launches under the overflow guard
-(tvts_adamw_torch_guard / tvts_sgd_torch_guard): the kernel updates only when ``norm_coef[0]`` is finite, the step counter the
+(tvts_adamw_torch / tvts_sgd_torch with ``skipped``): the kernel updates only when ``norm_coef[0]`` is finite, the step counter the
 kernels read lives on the device and advances there, ``skipped`` (device int64) counts the calls that did not update, and
 ``state_dict()`` reports the device's step count.
 
@@ -103,19 +104,6 @@ class _FlatOptimizer(torch.optim.Optimizer):
             self.step_dev.add_(1)
         else:
             self.step_dev.fill_(self.global_step)  # keeps the device counter in step when eager and captured steps mix
-        return hp
-
-    def _begin_guard(self):
-        """a step under the overflow guard (step(guard=True)) -> _hyper().  The kernels decide on the device whether the step
-        counts: the launch itself advances step_dev or skipped, and the host counter is re-read from step_dev when somebody needs it
-        (state_dict, the next unguarded step) -- nothing here synchronises."""
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"{self._cls}: step(guard=True) inside a stream capture is not built")
-        if self.norm_coef is None:
-            raise RuntimeError(f"{self._cls}: step(guard=True) needs norm_coef (the device norm of tvts_grad_sumsq; FinetuneStep sets it)")
-        hp = self._hyper()
-        self.sync_hyper()
-        self._guarded = True
         return hp
 
     def _adopt_device_step(self):
@@ -261,42 +249,60 @@ class FusedHFAdamW(_FlatAdamW):
         done.append((lo, hi))
 
 
-class FusedTorchAdamW(_FlatAdamW):
-    """``torch.optim.AdamW`` arithmetic (decay first, p *= 1 - lr wd; bias corrections bc1 = 1 - b1^t, bc2 = 1 - b2^t;
-    p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps)) as ONE launch over the flat store, for up to 64 parameter groups -- the 28
-    layer-decay groups of ViT-B (v1 fine-tuning, downstream/finetune_v1.py).  lr / weight_decay of the groups travel as the device
-    table lr[64] | wd[64], which the kernel always reads: step() uploads it on every call.  ``norm_coef`` (set by FinetuneStep):
-    the device buffer whose second element scales every gradient -- the clip coefficient of tvts_grad_sumsq.  ``ema`` (set by
-    FinetuneStep from its ModelEma): (fp32 buffer with the flat store's layout, decay) -- the launch then also carries the
-    averaged weights (tvts_adamw_torch_ema); None: the launch without an average."""
+class _TorchRule:
+    """What the two torch rules (the v1 downstream steps) add to _FlatOptimizer: up to 64 parameter groups whose lr / weight_decay
+    travel as the device table lr[64] | wd[64], which the kernel always reads (step() uploads it on every call), and the optional
+    parts of the launch.  ``norm_coef`` (set by FinetuneStep): the device buffer whose second element scales every gradient -- the
+    clip coefficient of tvts_grad_sumsq.  ``ema`` (set by FinetuneStep from its ModelEma): (fp32 buffer with the flat store's
+    layout, decay) -- the launch then also carries the averaged weights; None: the launch without an average.  A subclass names
+    its buffers and its kernel in ``_launch(hp, step, **kw)``; kw is what the two kernels' wrappers have in common."""
     MAX_GROUPS = 64
+    norm_coef = None
+    ema = None
 
-    def __init__(self, params, store: ParamStore, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, model=None):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), store, model)
-        self.norm_coef = None
-        self.ema = None
+    def _begin_guard(self):
+        """a step under the overflow guard (step(guard=True)) -> _hyper().  The kernels decide on the device whether the step
+        counts: the launch itself advances step_dev or skipped, and the host counter is re-read from step_dev when somebody needs it
+        (state_dict, the next unguarded step) -- nothing here synchronises."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{self._cls}: step(guard=True) inside a stream capture is not built")
+        if self.norm_coef is None:
+            raise RuntimeError(f"{self._cls}: step(guard=True) needs norm_coef (the device norm of tvts_grad_sumsq; FinetuneStep sets it)")
+        hp = self._hyper()
+        self.sync_hyper()
+        self._guarded = True
+        return hp
 
     @torch.no_grad()
     def step(self, closure=None, device_step: bool = False, guard: bool = False):
         """device_step=True: the step counter the kernel reads lives in device memory (same bits as the host counter).
-        guard=True (FinetuneStep(skip_nonfinite=True)): the update happens only when norm_coef[0] is finite, decided on the device
-        (tvts_adamw_torch_guard); a skipped call advances ``skipped`` instead of the device step counter."""
-        st = self.store
-        ema = {} if self.ema is None else dict(ema=self.ema[0], ema_decay=self.ema[1])
+        guard=True (FinetuneStep(skip_nonfinite=True)): the update happens only when norm_coef[0] is finite, decided on the device;
+        a skipped call advances ``skipped`` instead of the device step counter."""
+        kw = dict(grad_scale=self.grad_scale, norm_coef=self.norm_coef)
+        if self.ema is not None:
+            kw.update(ema=self.ema[0], ema_decay=self.ema[1])
         if guard:
-            b1, b2, eps, _, _ = self._begin_guard()
-            K.adamw_torch_guard(st.flat, st.grad, st.m, st.v, st.shadow, self.chunk_group, self.hyper_dev, self.step_dev, self.skipped,
-                                self.norm_coef, b1, b2, eps, self.grad_scale, **ema)
-            self._finish(True)
-            return
-        self.sync_hyper()
-        b1, b2, eps, _, _ = self._begin(device_step)
-        K.adamw_torch(st.flat, st.grad, st.m, st.v, st.shadow, self.chunk_group, self.hyper_dev, self.global_step, b1, b2, eps,
-                      self.grad_scale, step_dev=self.step_dev if device_step else None, norm_coef=self.norm_coef, **ema)
-        self._finish(device_step)
+            self._launch(self._begin_guard(), 0, step_dev=self.step_dev, skipped=self.skipped, **kw)
+        else:
+            self.sync_hyper()
+            self._launch(self._begin(device_step), self.global_step, step_dev=self.step_dev if device_step else None, **kw)
+        self._finish(guard or device_step)
 
 
-class FusedTorchSGD(_FlatOptimizer):
+class FusedTorchAdamW(_TorchRule, _FlatAdamW):
+    """``torch.optim.AdamW`` arithmetic (decay first, p *= 1 - lr wd; bias corrections bc1 = 1 - b1^t, bc2 = 1 - b2^t;
+    p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps)) as ONE launch over the flat store (tvts_adamw_torch) -- the 28 layer-decay
+    groups of ViT-B (v1 fine-tuning, downstream/finetune_v1.py)."""
+
+    def __init__(self, params, store: ParamStore, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, model=None):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), store, model)
+
+    def _launch(self, hp, step, **kw):
+        st = self.store
+        K.adamw_torch(st.flat, st.grad, st.m, st.v, st.shadow, self.chunk_group, self.hyper_dev, step, *hp[:3], **kw)
+
+
+class FusedTorchSGD(_TorchRule, _FlatOptimizer):
     """``torch.optim.SGD`` (single-tensor form, dampening 0) as ONE launch over the flat store, bit for bit, for up to 64 parameter
     groups: the optimizer optim_factory.create_optimizer builds for ``sgd`` / ``nesterov`` (nesterov=True) and ``momentum``
     (optim_factory.py:121-126) -- v1/scripts/linear_ssv2.sh trains the probe with ``--opt sgd --lr 0.1 --momentum 0.9
@@ -306,8 +312,7 @@ class FusedTorchSGD(_FlatOptimizer):
     ``store.m`` (no ``store.v``; with momentum 0 no state at all), ``state[p] = {"momentum_buffer": view of store.m}`` once the
     first update has run, as torch fills it.  The first update (buf = d, the bits of d) is decided for the whole store by the step
     counter: under this project's zero-gradient convention every trainable tensor is updated every step, so torch's per-parameter
-    ``buf is None`` is the same rule.  ``norm_coef`` / ``ema`` / ``grad_scale`` as FusedTorchAdamW (the average: tvts_sgd_torch_ema)."""
-    MAX_GROUPS = 64
+    ``buf is None`` is the same rule.  ``norm_coef`` / ``ema`` / ``grad_scale`` as FusedTorchAdamW."""
 
     def __init__(self, params, store: ParamStore, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *,
                  maximize=False, foreach=None, differentiable=False, fused=None, model=None):
@@ -323,8 +328,6 @@ class FusedTorchSGD(_FlatOptimizer):
                         maximize=maximize, foreach=foreach, differentiable=differentiable, fused=fused)
         super().__init__(params, defaults, store, model)
         self._hyper()
-        self.norm_coef = None
-        self.ema = None
 
     def _alloc_state(self):
         if self.defaults["momentum"] != 0 and self.store.m is None:
@@ -358,26 +361,14 @@ class FusedTorchSGD(_FlatOptimizer):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         return (mu, nes, *self._lr_wd())
 
-    @torch.no_grad()
-    def step(self, closure=None, device_step: bool = False, guard: bool = False):
-        """device_step=True: the step counter the kernel reads lives in device memory (same bits as the host counter).
-        guard=True: as FusedTorchAdamW.step (tvts_sgd_torch_guard).  ``state[p]`` is then filled by state_dict(), which reads the
-        device counter: whether a first update has happened is the device's knowledge."""
+    def _launch(self, hp, step, **kw):
+        """Behind a guarded launch ``state[p]`` is filled by state_dict(), which reads the device counter: whether a first update
+        has happened is then the device's knowledge."""
         st = self.store
-        ema = {} if self.ema is None else dict(ema=self.ema[0], ema_decay=self.ema[1])
-        if guard:
-            mu, nes, _, _ = self._begin_guard()
-            K.sgd_torch_guard(st.flat, st.grad, st.m if mu != 0 else None, st.shadow, self.chunk_group, self.hyper_dev, self.step_dev,
-                              self.skipped, self.norm_coef, momentum=mu, nesterov=nes, grad_scale=self.grad_scale, **ema)
-            self._finish(True)
-            return
-        self.sync_hyper()
-        mu, nes, _, _ = self._begin(device_step)
-        K.sgd_torch(st.flat, st.grad, st.m if mu != 0 else None, st.shadow, self.chunk_group, self.hyper_dev, self.global_step,
-                    momentum=mu, nesterov=nes, grad_scale=self.grad_scale, step_dev=self.step_dev if device_step else None,
-                    norm_coef=self.norm_coef, **ema)
-        self._buffers()
-        self._finish(device_step)
+        K.sgd_torch(st.flat, st.grad, st.m if hp[0] != 0 else None, st.shadow, self.chunk_group, self.hyper_dev, step,
+                    momentum=hp[0], nesterov=hp[1], **kw)
+        if kw.get("skipped") is None:
+            self._buffers()
 
     def state_dict(self):
         st = int(self.step_dev.item())  # (under hipGraph replay the host counter only advances at capture time)
