@@ -177,6 +177,14 @@ int tvts_quant_fp8_rows(const void* x, long ld, int rows, int cols, void* out, l
  * next step's scales: scale[i] = amax[i] / 448 where amax[i] > 0, amax[i] = 0.  The same two arguments exist on the LayerNorm forms
  * below. */
 int tvts_fp8_update_scales(float* amax, float* scale, int n, hipStream_t stream);
+/* The update under the overflow guard of the pretraining step: a maximum that is not finite never becomes a scale.  Per slot:
+ * amax[i] finite and > 0: scale[i] = amax[i] / 448; anything else (0, -0, inf, NaN): scale[i] is kept.  A slot whose scale is then
+ * not finite and positive -- it has never had a usable maximum (the calibration step was the bad one), or the quotient underflowed
+ * -- is set to 1.0, the value the quantisers use at a zero scale, so no quantiser ever divides by 0, inf or NaN.  amax[i] = 0 in
+ * every case.  guard_norm (optional device scalar, 4-byte aligned): the step's global gradient norm (norm_coef[0] of
+ * tvts_grad_sumsq); when it is not finite -- a step the guarded optimizer skips -- every slot keeps its old scale (the 1.0 rule
+ * still applies), so the scales are those of the last step that counted.  -22: n <= 0, amax or scale null, guard_norm misaligned. */
+int tvts_fp8_update_scales_guarded(float* amax, float* scale, int n, const float* guard_norm, hipStream_t stream);
 /* strided fp32 matmul for the tiny products (text_projection model_dist..B_16.py:108, head sort_transformer.py:113,
  * sim_matrix model_dist..B_16.py:126): C[i,j] (+)= alpha * sum_k A[i*sai+k*sak] * B[k*sbk+j*sbj] + bias[j] */
 int tvts_gemm_small_f32(const float* A, long sai, long sak, const float* B, long sbk, long sbj, int M, int N, int K,
@@ -660,6 +668,19 @@ int tvts_v2v_ranks(const float* sims, long ld, int nq, int q0, int N, const int*
 int tvts_adamw_hf(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group,
                   int nchunks, const float* lr4, const float* wd4, int step, const int* step_dev, const float* hyper_dev,
                   double beta1, double beta2, double eps, float grad_scale, hipStream_t stream);
+/* The same rule for the pretraining step with gradient clipping and the overflow guard (StepRunner(clip_grad=, skip_nonfinite=)).
+ * The arguments of tvts_adamw_hf plus norm_coef (optional) and skipped (optional); step_dev is written under the guard.
+ * g = stored gradient * grad_scale * norm_coef[1], multiplied in that order (two fp32 roundings), norm_coef = what tvts_grad_sumsq left
+ * in device memory.  norm_coef null, or a coefficient of exactly 1.0f: the bits of tvts_adamw_hf.  skipped != null: the guard as
+ * described above tvts_swap_f32_shadow -- norm_coef[0] finite: step_dev[0] += 1 first, then the unguarded update with that count, bit
+ * for bit; not finite: every bit of p, m, v and the shadow is kept, step_dev[0] stays, skipped[0] += 1; `step` is ignored.
+ * -22: p, g, m or v null or not 16-byte aligned; chunk_group, lr4 or wd4 null; nchunks <= 0; shadow / skipped not 8-byte aligned,
+ * step_dev / norm_coef / hyper_dev not 4; step <= 0 without step_dev; hyper_dev without step_dev; under the guard step_dev or
+ * norm_coef null. */
+int tvts_adamw_hf_guarded(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group,
+                          int nchunks, const float* lr4, const float* wd4, int step, int* step_dev, const float* hyper_dev,
+                          double beta1, double beta2, double eps, float grad_scale, const float* norm_coef, long* skipped,
+                          hipStream_t stream);
 int tvts_cast_f32_bf16(const float* src, void* dst, long n, hipStream_t stream);
 int tvts_cast_bf16_f32(const void* src, float* dst, long n, hipStream_t stream);
 int tvts_transpose_bf16_batched(const void* src, void* dst, const void* tiles, int ntiles, hipStream_t stream);

@@ -94,6 +94,20 @@ def strip_data_parallel_prefix(state_dict: Mapping) -> Mapping:
     return state_dict
 
 
+def guard_config(trainer_cfg: Mapping):
+    """``config['trainer']['clip_grad']`` (a positive finite number: max_norm of the global-norm clip; absent or None: off) and
+    ``['skip_nonfinite']`` (bool: the overflow guard; absent: off) -> (clip_grad or None, skip_nonfinite).  Both are this
+    package's own optional keys; a value of another type is an error, not a default."""
+    clip, skip = trainer_cfg.get("clip_grad"), trainer_cfg.get("skip_nonfinite", False)
+    if clip is not None:
+        if isinstance(clip, bool) or not isinstance(clip, (int, float)) or not (0.0 < float(clip) < math.inf):
+            raise ValueError(f"config['trainer']['clip_grad'] must be a positive finite number (or absent), got {clip!r}")
+        clip = float(clip)
+    if not isinstance(skip, bool):
+        raise ValueError(f"config['trainer']['skip_nonfinite'] must be true or false (or absent), got {skip!r}")
+    return clip, skip
+
+
 class Multi_BaseTrainer_dist:
     CHECKPOINT_NAME = "checkpoint-epoch{}.pth"
     BEST_NAME = "model_best.pth"

@@ -6,6 +6,8 @@
 //                        One launch for all ~400 tensors: the flat buffers are cut into 1024-element chunks and a
 //                        byte table gives each chunk its parameter group (255 = frozen / padding).  The same pass
 //                        applies the data-parallel 1/world gradient scale and refreshes the bf16 weight shadow.
+//   tvts_adamw_hf_guarded   the same rule with the clip coefficient tvts_grad_sumsq left on the device and, optionally, under the
+//                        overflow guard described below (the pretraining step with clip_grad / skip_nonfinite)
 //   tvts_adamw_torch     the same frame with torch.optim.AdamW arithmetic over up to 64 groups (the v1 fine-tuning step)
 //   tvts_sgd_torch       torch.optim.SGD (momentum, Nesterov) in the same frame with ONE state stream, bit for bit (the v1 linear
 //                        probe, 22 B per element)
@@ -100,13 +102,18 @@ __device__ __forceinline__ StateStreams<MOM ? 1 : 0, U> one_stream(float* buf, b
 
 struct AdamGroups { float lr[4]; float wd[4]; float step_size[4]; };
 
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, bf16* __restrict__ shadow,
-                                                    const unsigned char* __restrict__ chunk_group, AdamGroups hp, float beta1,
-                                                    float beta2, float omb1, float omb2, float eps, float grad_scale,
-                                                    const int* __restrict__ step_dev, const float* __restrict__ hyper_dev,
-                                                    double beta1d, double beta2d) {
-    optim_chunk<4, false, false>(p, g, shadow, chunk_group, nullptr, 0.f, 0.f, nullptr, [&](int grp) {
+// The HF rule inside the chunk frame: what tvts_adamw_hf and tvts_adamw_hf_guarded share.  COEF: the gradient is also multiplied by
+// the clip coefficient norm_coef[1] (1 with a null norm_coef), AFTER grad_scale: g = fl(fl(stored g * grad_scale) * coef), the order
+// the header states for the torch rules' gradient; a coefficient of exactly 1.0f leaves the bits of the launch without one.  GUARD:
+// the frame tests norm_coef[0] in front of every load.
+template <bool COEF, bool GUARD>
+__device__ __forceinline__ void hf_chunk(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                         float* __restrict__ v, bf16* __restrict__ shadow,
+                                         const unsigned char* __restrict__ chunk_group, AdamGroups& hp, float beta1, float beta2,
+                                         float omb1, float omb2, float eps, float grad_scale, const int* __restrict__ step_dev,
+                                         const float* __restrict__ hyper_dev, double beta1d, double beta2d,
+                                         const float* __restrict__ norm_coef) {
+    optim_chunk<4, false, GUARD>(p, g, shadow, chunk_group, nullptr, 0.f, 0.f, norm_coef, [&](int grp) {
         if (hyper_dev) {  // lr[4] | wd[4] in device memory: a captured launch follows the LR schedule without re-capture
             hp.lr[grp] = hyper_dev[grp];
             hp.wd[grp] = hyper_dev[4 + grp];
@@ -119,10 +126,12 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
             hp.step_size[grp] = (float)((double)hp.lr[grp] * sqrt(bc2) / bc1);
         }
         const float lr = hp.lr[grp], wd = hp.wd[grp], ss = hp.step_size[grp];
+        const float coef = COEF && norm_coef ? norm_coef[1] : 1.f;
         return two_streams(m, v, [=](f32x4& pv, f32x4& mv, f32x4& vv, const f32x4& gv) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float gg = gv[e] * grad_scale;
+                float gg = gv[e] * grad_scale;
+                if constexpr (COEF) gg *= coef;
                 mv[e] = beta1 * mv[e] + omb1 * gg;
                 vv[e] = beta2 * vv[e] + omb2 * gg * gg;
                 pv[e] -= ss * mv[e] / (sqrtf(vv[e]) + eps);
@@ -132,12 +141,28 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     });
 }
 
-extern "C" int tvts_adamw_hf(float* p, const float* g, float* m, float* v, void* shadow_bf16,
-                             const unsigned char* chunk_group, int nchunks, const float* lr4, const float* wd4, int step,
-                             const int* step_dev, const float* hyper_dev, double beta1, double beta2, double eps,
-                             float grad_scale, hipStream_t stream) {
-    if (nchunks <= 0 || (step <= 0 && !step_dev)) return TVTS_EINVAL;
-    if (hyper_dev && !step_dev) return TVTS_EINVAL;  // the device table is only consulted together with the device step counter
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, bf16* __restrict__ shadow,
+                                                    const unsigned char* __restrict__ chunk_group, AdamGroups hp, float beta1,
+                                                    float beta2, float omb1, float omb2, float eps, float grad_scale,
+                                                    const int* __restrict__ step_dev, const float* __restrict__ hyper_dev,
+                                                    double beta1d, double beta2d) {
+    hf_chunk<false, false>(p, g, m, v, shadow, chunk_group, hp, beta1, beta2, omb1, omb2, eps, grad_scale, step_dev, hyper_dev, beta1d,
+                           beta2d, nullptr);
+}
+template <bool GUARD>
+__global__ __launch_bounds__(256) void adamw_hf_coef_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, bf16* __restrict__ shadow,
+                                                            const unsigned char* __restrict__ chunk_group, AdamGroups hp, float beta1,
+                                                            float beta2, float omb1, float omb2, float eps, float grad_scale,
+                                                            const int* __restrict__ step_dev, const float* __restrict__ hyper_dev,
+                                                            double beta1d, double beta2d, const float* __restrict__ norm_coef) {
+    hf_chunk<true, GUARD>(p, g, m, v, shadow, chunk_group, hp, beta1, beta2, omb1, omb2, eps, grad_scale, step_dev, hyper_dev, beta1d,
+                          beta2d, norm_coef);
+}
+
+// lr / wd of the four groups and the host's step sizes (the kernel forms its own when it reads the step counter from the device)
+static AdamGroups hf_groups(const float* lr4, const float* wd4, int step, double beta1, double beta2) {
     if (step <= 0) step = 1;
     AdamGroups hp;
     const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
@@ -146,6 +171,16 @@ extern "C" int tvts_adamw_hf(float* p, const float* g, float* m, float* v, void*
         hp.wd[i] = wd4[i];
         hp.step_size[i] = (float)((double)lr4[i] * sqrt(bc2) / bc1);
     }
+    return hp;
+}
+
+extern "C" int tvts_adamw_hf(float* p, const float* g, float* m, float* v, void* shadow_bf16,
+                             const unsigned char* chunk_group, int nchunks, const float* lr4, const float* wd4, int step,
+                             const int* step_dev, const float* hyper_dev, double beta1, double beta2, double eps,
+                             float grad_scale, hipStream_t stream) {
+    if (nchunks <= 0 || (step <= 0 && !step_dev)) return TVTS_EINVAL;
+    if (hyper_dev && !step_dev) return TVTS_EINVAL;  // the device table is only consulted together with the device step counter
+    const AdamGroups hp = hf_groups(lr4, wd4, step, beta1, beta2);
     hipLaunchKernelGGL(adamw_kernel, dim3(nchunks), dim3(256), 0, stream, p, g, m, v, (bf16*)shadow_bf16, chunk_group, hp,
                        (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, grad_scale, step_dev, hyper_dev, beta1, beta2);
     TVTS_LAUNCH_CHECK();
@@ -182,6 +217,34 @@ template <typename F>
 static void with_bool(bool b, F f) {
     if (b) f(std::true_type{});
     else f(std::false_type{});
+}
+
+// ---- the HF rule of the pretraining step with the clip coefficient and the guard (StepRunner(clip_grad=..., skip_nonfinite=True))
+// The arguments of tvts_adamw_hf, then norm_coef (null: no coefficient) and skipped (null: unguarded).  g = stored gradient *
+// grad_scale * norm_coef[1], multiplied in that order; norm_coef null or a coefficient of 1.0f: the bits of tvts_adamw_hf.  Under the
+// guard the counter kernel runs in front, the bias corrections come from step_dev[0] (the device code tvts_adamw_hf runs with a
+// step_dev: same bits) and `step` is ignored.  Refusals as the torch rules': p, g, m, v present and 16-byte aligned, and so on.
+extern "C" int tvts_adamw_hf_guarded(float* p, const float* g, float* m, float* v, void* shadow_bf16, const unsigned char* chunk_group,
+                                     int nchunks, const float* lr4, const float* wd4, int step, int* step_dev, const float* hyper_dev,
+                                     double beta1, double beta2, double eps, float grad_scale, const float* norm_coef, long* skipped,
+                                     hipStream_t stream) {
+    for (const void* q : {(const void*)p, (const void*)g, (const void*)m, (const void*)v})
+        if (!q || misaligned16(q)) return TVTS_EINVAL;
+    if (!chunk_group || !lr4 || !wd4 || nchunks <= 0) return TVTS_EINVAL;
+    if (((uintptr_t)shadow_bf16 & 7) || ((uintptr_t)skipped & 7) || ((uintptr_t)step_dev & 3) || ((uintptr_t)norm_coef & 3) ||
+        ((uintptr_t)hyper_dev & 3))
+        return TVTS_EINVAL;
+    if (skipped ? (!step_dev || !norm_coef) : (step <= 0 && !step_dev)) return TVTS_EINVAL;
+    if (hyper_dev && !step_dev) return TVTS_EINVAL;  // (as tvts_adamw_hf: the device table goes with the device step counter)
+    const AdamGroups hp = hf_groups(lr4, wd4, step, beta1, beta2);
+    if (skipped) hipLaunchKernelGGL(guard_advance_kernel, dim3(1), dim3(1), 0, stream, norm_coef, step_dev, skipped);
+    with_bool(skipped != nullptr, [&](auto G) {
+        hipLaunchKernelGGL(adamw_hf_coef_kernel<decltype(G)::value>, dim3(nchunks), dim3(256), 0, stream, p, g, m, v,
+                           (bf16*)shadow_bf16, chunk_group, hp, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
+                           (float)eps, grad_scale, (const int*)step_dev, hyper_dev, beta1, beta2, norm_coef);
+    });
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
 }
 
 // ---- torch.optim.AdamW, multi-tensor (the v1 fine-tuning step)
@@ -650,6 +713,29 @@ __global__ void fp8_update_scales_kernel(float* __restrict__ amax, float* __rest
 extern "C" int tvts_fp8_update_scales(float* amax, float* scale, int n, hipStream_t stream) {
     if (n <= 0 || !amax || !scale) return TVTS_EINVAL;
     hipLaunchKernelGGL(fp8_update_scales_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, stream, amax, scale, n);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+// The update under the overflow guard of the pretraining step (StepRunner(skip_nonfinite=True)): a maximum that is not finite never
+// becomes a scale.  Per slot: a finite amax > 0 gives scale = amax / 448, anything else (0, -0, inf, NaN) keeps the old scale; a
+// slot whose scale is then not finite and positive -- it has never had a usable maximum: the calibration step was the bad one, or
+// amax / 448 underflowed -- gets 1.0, the value q8_scale() quantises under at a zero scale; amax = 0 in every case.  guard_norm
+// (optional): the step's global gradient norm on the device; when it is not finite the step is one the optimizer skips, and every
+// slot keeps its old scale (the 1.0 rule still holds), so a skipped step leaves the scales of the step before it.
+__global__ void fp8_update_scales_guarded_kernel(float* __restrict__ amax, float* __restrict__ scale, int n,
+                                                 const float* __restrict__ guard_norm) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float a = amax[i];
+    float s = scale[i];
+    if (finite_f32(a) && a > 0.f && (!guard_norm || finite_f32(guard_norm[0]))) s = a / 448.0f;
+    if (!(finite_f32(s) && s > 0.f)) s = 1.0f;
+    scale[i] = s;
+    amax[i] = 0.f;
+}
+extern "C" int tvts_fp8_update_scales_guarded(float* amax, float* scale, int n, const float* guard_norm, hipStream_t stream) {
+    if (n <= 0 || !amax || !scale || ((uintptr_t)guard_norm & 3)) return TVTS_EINVAL;
+    hipLaunchKernelGGL(fp8_update_scales_guarded_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, stream, amax, scale, n, guard_norm);
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;
 }

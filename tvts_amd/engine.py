@@ -456,11 +456,17 @@ class Engine:
             assert i < self._f8_scale.numel(), "more e4m3 tensors than the scale table holds"
         return self._f8_scale[i:i + 1], self._f8_amax[i:i + 1]
 
-    def end_step(self):
+    def end_step(self, guard_norm=None):
         """Called once per optimisation step (StepRunner.run) after the backward: this step's amax values become the per-tensor
-        scales of the next step, and from the second step on the e4m3 copies are per-tensor and the weight gradients e4m3."""
+        scales of the next step, and from the second step on the e4m3 copies are per-tensor and the weight gradients e4m3.
+        guard_norm (StepRunner(skip_nonfinite=True): the device norm of the step's gradient): the guarded update -- a maximum that
+        is not finite never becomes a scale, a step whose norm is not finite keeps every scale, and a slot without a usable scale
+        (the calibration step was the bad one) gets 1.0 (tvts_fp8_update_scales_guarded)."""
         if self.fp8_wgrad and self._f8_scale is not None:
-            K.fp8_update_scales(self._f8_amax, self._f8_scale)
+            if guard_norm is not None:
+                K.fp8_update_scales_guarded(self._f8_amax, self._f8_scale, guard_norm)
+            else:
+                K.fp8_update_scales(self._f8_amax, self._f8_scale)
             self._f8_tensor_mode = True
 
     def _q8(self, M, W, name, persistent=False):

@@ -279,6 +279,16 @@ def fp8_update_scales(amax, scale):
     _chk(_lib.load().tvts_fp8_update_scales(_p(amax), _p(scale), amax.numel(), _stream()), "tvts_fp8_update_scales")
 
 
+def fp8_update_scales_guarded(amax, scale, guard_norm=None):
+    """fp8_update_scales under the overflow guard: only a finite amax[i] > 0 becomes a scale, every other slot keeps its scale; a
+    scale that is then not finite and positive becomes 1.0; amax[i] = 0.  guard_norm (device fp32, the global gradient norm): not
+    finite -- the step the optimizer skips -- keeps every scale."""
+    assert amax.dtype == scale.dtype == torch.float32 and amax.numel() == scale.numel()
+    assert guard_norm is None or (guard_norm.dtype == torch.float32 and guard_norm.numel() >= 1)
+    _chk(_lib.load().tvts_fp8_update_scales_guarded(_p(amax), _p(scale), amax.numel(), _p(guard_norm), _stream()),
+         "tvts_fp8_update_scales_guarded")
+
+
 def gemm_nt_fp8(a8, sa, b8, sb, out, *, bias=None, residual=None, act=None, preact=None, gate_h=None, gate_act=None, k32=None,
                 cus=None, q8out=None, q8_scale=None, q8_amax=None, store_out=True, side_deriv=False):
     """out[M,N] = act(sa*sb * (a8[M,K] @ b8[N,K]^T) + bias) [+ residual]; a8 / b8 uint8 e4m3 bit patterns; sb float32[1]; sa
@@ -1396,6 +1406,30 @@ def adamw_hf(p, g, m, v, shadow, chunk_group, lr4, wd4, step, beta1=0.9, beta2=0
                            ctypes.cast(lr, ctypes.c_void_p), ctypes.cast(wd, ctypes.c_void_p), step, _p(step_dev), _p(hyper_dev), beta1, beta2, eps,
                            grad_scale, _stream()))
     _chk(rc, "tvts_adamw_hf")
+
+
+def adamw_hf_guarded(p, g, m, v, shadow, chunk_group, lr4, wd4, step, beta1=0.9, beta2=0.999, eps=1e-6, grad_scale=1.0,
+                     step_dev=None, hyper_dev=None, norm_coef=None, skipped=None):
+    """adamw_hf for the pretraining step with clipping and the overflow guard (tvts_adamw_hf_guarded).  norm_coef (device fp32 [2],
+    what grad_sumsq left): g = stored g * grad_scale * norm_coef[1]; None, or a coefficient of 1.0: the bits of adamw_hf.  skipped
+    (device int64, with step_dev and norm_coef): the guard as adamw_torch describes it; `step` is then ignored."""
+    n = chunk_group.numel()
+    assert chunk_group.dtype == torch.uint8 and all(t.dtype == torch.float32 and t.numel() >= n * 1024 for t in (p, g, m, v))
+    assert shadow is None or (shadow.dtype == torch.bfloat16 and shadow.numel() >= n * 1024)
+    assert hyper_dev is None or (hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= 8)
+    assert norm_coef is None or (norm_coef.dtype == torch.float32 and norm_coef.numel() >= 2)
+    assert step_dev is None or (step_dev.dtype == torch.int32 and step_dev.numel() >= 1)
+    if skipped is not None:
+        if step_dev is None or norm_coef is None:
+            raise ValueError("skipped (the guarded launch) needs step_dev and norm_coef")
+        _guard_cells(step_dev, skipped, norm_coef)
+    lr = (ctypes.c_float * 4)(*lr4)
+    wd = (ctypes.c_float * 4)(*wd4)
+    with _hbm("adamw", _adamw_bytes(chunk_group, 255)):
+        rc = _lib.load().tvts_adamw_hf_guarded(_p(p), _p(g), _p(m), _p(v), _p(shadow), _p(chunk_group), n, ctypes.cast(lr, ctypes.c_void_p),
+                                               ctypes.cast(wd, ctypes.c_void_p), int(step), _p(step_dev), _p(hyper_dev), beta1, beta2, eps,
+                                               grad_scale, _p(norm_coef), _p(skipped), _stream())
+    _chk(rc, "tvts_adamw_hf_guarded")
 
 
 def ema_pair(decay):

@@ -1,8 +1,8 @@
 """Fused multi-tensor optimizers over the flat parameter store: ``step()`` is ONE kernel launch over the flat buffers.
 
 ``_FlatOptimizer`` holds what all of them share (chunk table, lr / weight_decay device table, step counters, ``_begin`` /
-``_finish``, the shadow refresh); ``_FlatAdamW`` adds what the two AdamWs share (moments, state views, checkpoints), ``_TorchRule``
-what the two torch rules share (``norm_coef``, ``ema``, the body of ``step(closure, device_step, guard)``).
+``_begin_guard`` / ``_finish``, ``norm_coef``, the shadow refresh); ``_FlatAdamW`` adds what the two AdamWs share (moments, state views,
+checkpoints), ``_TorchRule`` what the two torch rules share (``ema``, the body of ``step(closure, device_step, guard)``).
 
 ``FusedHFAdamW`` replaces ``transformers.AdamW(params=optimizer_grouped_parameters)`` built at
 v2/train_dist_TVTSv2_ViT_B_16.py:118-125 (defaults betas (0.9, 0.999), eps 1e-6, correct_bias=True).
@@ -14,7 +14,9 @@ All are ``torch.optim.Optimizer``s, so param_groups / state_dict keep the refere
 ``FusedTorchAdamW.step(guard=True)`` / ``FusedTorchSGD.step(guard=True)`` are the same launches under the overflow guard
 (tvts_adamw_torch / tvts_sgd_torch with ``skipped``): the kernel updates only when ``norm_coef[0]`` is finite, the step counter the
 kernels read lives on the device and advances there, ``skipped`` (device int64) counts the calls that did not update, and
-``state_dict()`` reports the device's step count.
+``state_dict()`` reports the device's step count.  ``FusedHFAdamW.step(guard=True)`` is the same for the pretraining step
+(tvts_adamw_hf_guarded; StepRunner(skip_nonfinite=True)), and with ``norm_coef`` set its launch multiplies the gradient by the clip
+coefficient (StepRunner(clip_grad=...)).
 
 Gradient handling follows the reference's pinned torch 1.11 ``zero_grad()`` (grads zeroed, not set to
 None): every trainable tensor is updated every step, tensors that received no gradient see g = 0.
@@ -32,6 +34,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
     table and the host / device step counters.  A subclass sets MAX_GROUPS (the width of its kernel's table), allocates its state
     on the ParamStore (_alloc_state, _init_param), names its per-launch constants (_hyper) and launches its kernel in step()."""
     MAX_GROUPS = 0
+    norm_coef = None  # set by the step that clips / guards: device fp32 [norm, clip coefficient] as tvts_grad_sumsq leaves them
+    _NORM_OWNER = "StepRunner(clip_grad / skip_nonfinite)"  # who sets norm_coef, for the message of a guarded step without one
 
     def __init__(self, params, defaults, store: ParamStore, model=None):
         super().__init__(params, defaults)
@@ -104,6 +108,19 @@ class _FlatOptimizer(torch.optim.Optimizer):
             self.step_dev.add_(1)
         else:
             self.step_dev.fill_(self.global_step)  # keeps the device counter in step when eager and captured steps mix
+        return hp
+
+    def _begin_guard(self):
+        """a step under the overflow guard (step(guard=True)) -> _hyper().  The kernels decide on the device whether the step
+        counts: the launch itself advances step_dev or skipped, and the host counter is re-read from step_dev when somebody needs it
+        (state_dict, the next unguarded step) -- nothing here synchronises."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{self._cls}: step(guard=True) inside a stream capture is not built")
+        if self.norm_coef is None:
+            raise RuntimeError(f"{self._cls}: step(guard=True) needs norm_coef (the device norm of tvts_grad_sumsq; {self._NORM_OWNER} sets it)")
+        hp = self._hyper()
+        self.sync_hyper()
+        self._guarded = True
         return hp
 
     def _adopt_device_step(self):
@@ -202,15 +219,31 @@ class FusedHFAdamW(_FlatAdamW):
         st.refresh_transposed(s, e)
 
     @torch.no_grad()
-    def step(self, closure=None, device_step: bool = False):
+    def step(self, closure=None, device_step: bool = False, guard: bool = False):
         """device_step=True keeps the step counter in device memory (hipGraph replay).  After begin_ranges() / step_range() calls
-        this finishes the step: the chunks no range has covered yet."""
+        this finishes the step: the chunks no range has covered yet.  With ``norm_coef`` set (StepRunner(clip_grad=...)) the launch
+        is tvts_adamw_hf_guarded, which multiplies every gradient by the clip coefficient norm_coef[1]; guard=True
+        (StepRunner(skip_nonfinite=True)) runs it under the overflow guard: the update happens only when norm_coef[0] is finite,
+        decided on the device, and a skipped call advances ``skipped`` instead of the device step counter."""
         nch = self.chunk_group.numel()
-        if self._ranged is None:
+        st = self.store
+        if guard:
+            if self._ranged is not None:
+                raise RuntimeError(f"{self._cls}: step(guard=True) cannot finish a ranged update (begin_ranges / step_range)")
+            hp = self._begin_guard()
+            K.adamw_hf_guarded(st.flat, st.grad, st.m, st.v, st.shadow, self.chunk_group, hp[3], hp[4], 0, hp[0], hp[1], hp[2],
+                               self.grad_scale, step_dev=self.step_dev, hyper_dev=self.hyper_dev, norm_coef=self.norm_coef,
+                               skipped=self.skipped)
+            self._finish(True)
+        elif self._ranged is None:
             hp = self._begin(device_step)
-            K.adamw_hf(self.store.flat, self.store.grad, self.store.m, self.store.v, self.store.shadow, self.chunk_group,
-                       hp[3], hp[4], self.global_step, hp[0], hp[1], hp[2], self.grad_scale, step_dev=self.step_dev if device_step else None,
-                       hyper_dev=self.hyper_dev if device_step else None)
+            dev = dict(step_dev=self.step_dev if device_step else None, hyper_dev=self.hyper_dev if device_step else None)
+            if self.norm_coef is not None:
+                K.adamw_hf_guarded(st.flat, st.grad, st.m, st.v, st.shadow, self.chunk_group, hp[3], hp[4], self.global_step, hp[0], hp[1],
+                                   hp[2], self.grad_scale, norm_coef=self.norm_coef, **dev)
+            else:
+                K.adamw_hf(st.flat, st.grad, st.m, st.v, st.shadow, self.chunk_group, hp[3], hp[4], self.global_step, hp[0], hp[1], hp[2],
+                           self.grad_scale, **dev)
             self._finish(device_step)
         else:
             hp, dstep, done = self._ranged
@@ -230,7 +263,12 @@ class FusedHFAdamW(_FlatAdamW):
     # own under the remaining backward instead of behind it: the layer's weights are not read again before the next forward.
     # begin_ranges() once per step in front of the backward, step_range(lo, hi) per finished range (elements of the flat buffers,
     # chunk-aligned as Engine.trainable_runs hands them out), step() afterwards for whatever no range covered.
-    def begin_ranges(self, device_step: bool = False):
+    def begin_ranges(self, device_step: bool = False, guard: bool = False):
+        if self.norm_coef is not None or guard:
+            # a range's update starts before the last gradient exists: neither the global norm nor the guard's decision is known then
+            raise RuntimeError(f"{self._cls}: ranged updates (begin_ranges / step_range) cannot be combined with "
+                               f"{'the overflow guard' if guard else 'gradient clipping (norm_coef)'}: the global gradient norm exists "
+                               "only behind the whole backward")
         self._ranged = (self._begin(device_step), device_step, [])
 
     def step_range(self, lo_elem: int, hi_elem: int, wait=None):
@@ -252,26 +290,13 @@ class FusedHFAdamW(_FlatAdamW):
 class _TorchRule:
     """What the two torch rules (the v1 downstream steps) add to _FlatOptimizer: up to 64 parameter groups whose lr / weight_decay
     travel as the device table lr[64] | wd[64], which the kernel always reads (step() uploads it on every call), and the optional
-    parts of the launch.  ``norm_coef`` (set by FinetuneStep): the device buffer whose second element scales every gradient -- the
-    clip coefficient of tvts_grad_sumsq.  ``ema`` (set by FinetuneStep from its ModelEma): (fp32 buffer with the flat store's
+    parts of the launch.  ``norm_coef`` (the base class's; set by FinetuneStep): the device buffer whose second element scales every
+    gradient -- the clip coefficient of tvts_grad_sumsq.  ``ema`` (set by FinetuneStep from its ModelEma): (fp32 buffer with the flat store's
     layout, decay) -- the launch then also carries the averaged weights; None: the launch without an average.  A subclass names
     its buffers and its kernel in ``_launch(hp, step, **kw)``; kw is what the two kernels' wrappers have in common."""
     MAX_GROUPS = 64
-    norm_coef = None
     ema = None
-
-    def _begin_guard(self):
-        """a step under the overflow guard (step(guard=True)) -> _hyper().  The kernels decide on the device whether the step
-        counts: the launch itself advances step_dev or skipped, and the host counter is re-read from step_dev when somebody needs it
-        (state_dict, the next unguarded step) -- nothing here synchronises."""
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"{self._cls}: step(guard=True) inside a stream capture is not built")
-        if self.norm_coef is None:
-            raise RuntimeError(f"{self._cls}: step(guard=True) needs norm_coef (the device norm of tvts_grad_sumsq; FinetuneStep sets it)")
-        hp = self._hyper()
-        self.sync_hyper()
-        self._guarded = True
-        return hp
+    _NORM_OWNER = "FinetuneStep"
 
     @torch.no_grad()
     def step(self, closure=None, device_step: bool = False, guard: bool = False):

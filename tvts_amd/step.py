@@ -2,6 +2,8 @@
 
 zero_grad -> model forward -> all-gather of embeddings -> sim_matrix + InfoNCE (+ 2*CE sorting loss) ->
 hand-written backward (gradients all-reduced range by range while it runs) -> fused HF-AdamW.
+Optional, both decided on the device: the global gradient norm with its clip coefficient in front of the update (clip_grad) and the
+overflow guard that skips a step whose norm is not finite (skip_nonfinite).
 """
 from __future__ import annotations
 
@@ -15,8 +17,33 @@ from . import hip as K
 from .engine import LossHead
 
 
+def guard_options(clip_grad, skip_nonfinite, *, fused: bool, ranged: bool, optimizer: str = "the optimizer"):
+    """The two options of StepRunner as it keeps them -> (clip_grad or None, skip_nonfinite), or the named refusal: a max_norm that
+    is not a positive finite number; either option with an optimizer that is not the fused one; either option together with the
+    ranged update."""
+    clip = float(clip_grad) if clip_grad else None
+    skip = bool(skip_nonfinite)
+    if clip is not None and not (0.0 < clip < float("inf")):
+        raise ValueError(f"StepRunner: clip_grad {clip_grad!r} must be a positive finite max_norm (None switches clipping off)")
+    what = " / ".join(n for n, on in (("clip_grad", clip is not None), ("skip_nonfinite", skip)) if on)
+    if what and not fused:
+        raise RuntimeError(f"StepRunner({what}) needs the fused optimizer (FusedHFAdamW): the norm, the coefficient and the "
+                           f"guard's decision stay on the device; got {optimizer}")
+    if what and ranged:
+        raise RuntimeError(f"StepRunner({what}) cannot be combined with adamw_ranges / TVTS_ADAMW_RANGES=1: a ranged update "
+                           "starts before the last gradient exists, the global gradient norm only behind the whole backward")
+    return clip, skip
+
+
 class StepRunner:
-    def __init__(self, model, optimizer, loss_head: Optional[LossHead] = None):
+    def __init__(self, model, optimizer, loss_head: Optional[LossHead] = None, clip_grad: Optional[float] = None,
+                 skip_nonfinite: bool = False):
+        """clip_grad (max_norm of torch.nn.utils.clip_grad_norm_ over the trainable tensors, None / 0: off) and skip_nonfinite (the
+        overflow guard: a step whose global gradient norm is not finite changes no bit of the weights, the moments, the shadows or
+        the e4m3 scales, and counts in ``skipped``) are both decided on the device: tvts_grad_sumsq behind the gradient exchange
+        leaves norm and coefficient in ``norm_coef``, FusedHFAdamW reads them there.  The norm is that of the AVERAGED gradient,
+        the number clip_grad_norm_ sees behind DDP, and every rank computes it from the same reduced buffer: no collective is
+        added.  With both off the step is launch for launch the one without these arguments."""
         self.model, self.opt = model, optimizer
         self.eng, self.store = model.engine, model.store
         self.head = loss_head or LossHead(self.store.device)
@@ -34,6 +61,24 @@ class StepRunner:
         # exchange diagnostics (bench.py at world > 1, eager launches only): event pairs on the compute stream around the two places where
         # it waits for a collective -- {"gather": [...], "allreduce": [...]} when switched on, None otherwise
         self.diag = None
+        self.clip_grad, self.skip_nonfinite = guard_options(clip_grad, skip_nonfinite, fused=self.fused and hasattr(optimizer, "begin_ranges"),
+                                                            ranged=self.ranged, optimizer=type(optimizer).__name__)
+        self.guarding = self.clip_grad is not None or self.skip_nonfinite
+        # every rank enters this, with or without the options: a rank that guards beside one that does not would skip alone
+        # (only where a process group exists: the check is a collective)
+        if D.dist.is_available() and D.dist.is_initialized():
+            D.agree(repr(("clip_grad", self.clip_grad, "skip_nonfinite", self.skip_nonfinite)).encode(),
+                    "StepRunner: clip_grad or skip_nonfinite")
+        if self.guarding:
+            dev = self.store.device
+            self.norm_coef = torch.zeros(2, dtype=torch.float32, device=dev)  # [global norm, clip coefficient] of the last step
+            self._partial = torch.zeros(optimizer.chunk_group.numel(), dtype=torch.float32, device=dev)
+            optimizer.norm_coef = self.norm_coef
+
+    @property
+    def skipped(self):
+        """the optimizer's device int64 counter of the steps the overflow guard skipped (never read on the host by the step)"""
+        return self.opt.skipped
 
     def _bracket(self, key, fn):
         """fn() between two events of the current stream when the diagnostics are on: the elapsed time is what the compute stream
@@ -118,9 +163,18 @@ class StepRunner:
             self.eng.backward(d_te, d_ve, dpred)
         finally:
             self.eng.param_ready = None
-        if hasattr(self.eng, "end_step"):
+        if hasattr(self.eng, "end_step") and not self.skip_nonfinite:
             self.eng.end_step()  # (e4m3 weight gradients: this step's amax values become the next step's per-tensor scales)
         scale = self._bracket("allreduce", self.sync.finish)
+        if self.guarding:
+            # the norm of the averaged gradient over the trainable chunks (frozen chunks carry group 255, the kernel's exclusion
+            # rule) and the coefficient: one more read of the gradient buffer, everything stays on the device
+            K.grad_sumsq(self.store.grad, self.opt.chunk_group, self._partial, self.norm_coef, max_norm=self.clip_grad, grad_scale=scale)
+            if self.skip_nonfinite and hasattr(self.eng, "end_step"):
+                self.eng.end_step(guard_norm=self.norm_coef)  # (behind the norm: a skipped step keeps the e4m3 scales as well)
+            self.opt.grad_scale = scale
+            self.opt.step(device_step=device_step, guard=self.skip_nonfinite)
+            return dict(loss1=loss1, loss2=loss2, grad_norm=self.norm_coef[0])
         if self.fused:
             self.opt.grad_scale = scale
             self.opt.step(device_step=device_step)
@@ -186,8 +240,10 @@ class GraphReplay:
     def __init__(self, runner: StepRunner):
         self.r = runner
         self.cache = {}
+        # (skip_nonfinite: the guarded optimizer launch refuses a stream capture, so such a runner steps eagerly; clip_grad alone is
+        # capturable -- the coefficient is a device scalar the replayed launches read)
         self.usable = (torch.cuda.is_available() and runner.fused and not runner.ranged and runner.sync.W == 1 and not runner.sync.native
-                       and os.environ.get("TVTS_TRAINER_GRAPH", "0") == "1")
+                       and not runner.skip_nonfinite and os.environ.get("TVTS_TRAINER_GRAPH", "0") == "1")
         self.replays = self.captures = self.eager = 0
 
     def step(self, data: dict):

@@ -17,6 +17,7 @@ import torch
 import torch.distributed as dist
 
 from ..base import Multi_BaseTrainer_dist
+from ..base.base_trainer import guard_config
 from ..model._common import sim_matrix  # noqa: F401  (the reference re-exports it at module scope)
 from ..step import GraphReplay, StepRunner
 
@@ -88,12 +89,13 @@ class _LazyLog:
 
     SLOTS = 64
 
-    def __init__(self, logger, fmt, device):
+    def __init__(self, logger, fmt, device, extra=0):
+        """extra: further device scalars per line (the gradient norm of a clipped / guarded step), formatted behind the three losses"""
         self.logger, self.fmt, self.q, self.i = logger, fmt, [], 0
         self.cuda = torch.cuda.is_available() and torch.device(device).type == "cuda"
-        self.host = torch.zeros(self.SLOTS, 2, dtype=torch.float32, pin_memory=self.cuda)
+        self.host = torch.zeros(self.SLOTS, 2 + extra, dtype=torch.float32, pin_memory=self.cuda)
 
-    def add(self, head, l1, l2):
+    def add(self, head, l1, l2, *extra):
         if len(self.q) >= self.SLOTS:
             self.flush(block=True)
         slot = self.host[self.i]
@@ -103,6 +105,8 @@ class _LazyLog:
             slot[1] = 0.0
         else:
             slot[1:2].copy_(l2.reshape(1), non_blocking=True)
+        for k, x in enumerate(extra):
+            slot[2 + k:3 + k].copy_(x.reshape(1), non_blocking=True)
         ev = None
         if self.cuda:
             ev = torch.cuda.Event()
@@ -115,13 +119,14 @@ class _LazyLog:
             if ev is not None:
                 ev.synchronize()
             a, b = np.float32(slot[0].item()), np.float32(slot[1].item())
-            self.logger.debug(self.fmt.format(*head, float(a), float(b), float(np.float32(a + b))))
+            self.logger.debug(self.fmt.format(*head, float(a), float(b), float(np.float32(a + b)), *(float(x) for x in slot[2:].tolist())))
 
 
 class _TrainerBase(Multi_BaseTrainer_dist):
     TRUNCATE = True
     CACHE_CAPTIONS = True
     LOG_LINE = "Train Epoch: {} dl{} {} Loss_ct: {:.6f} Loss_ce: {:.6f} Loss: {:.6f}"  # v2/trainer/trainer.py:505-512
+    LOG_GRAD_NORM = " grad_norm: {:.6f}"  # appended with clip_grad / skip_nonfinite: the norm of the step's averaged gradient
 
     def __init__(self, args, model, loss, metrics, optimizer, config, data_loader, valid_data_loader=None,
                  lr_scheduler=None, len_epoch=None, writer=None, visualizer=None, tokenizer=None,
@@ -154,12 +159,27 @@ class _TrainerBase(Multi_BaseTrainer_dist):
         self.base_lr = [g["lr"] for g in optimizer.param_groups]
         # the configured loss module's temperature drives the fused loss head (model/loss.py:11 NormSoftmaxLoss(temperature))
         from ..engine import LossHead
-        self.runner = StepRunner(model, optimizer, LossHead(model.store.device, temperature=float(getattr(loss, "temperature", 0.05))))
+        # config["trainer"]["clip_grad"] / ["skip_nonfinite"] (both optional, this package's own keys): gradient clipping by global norm
+        # and the overflow guard of the step, decided on the device.  Absent: the trainer without them, log text included.
+        clip_grad, skip_nonfinite = guard_config(config["trainer"])
+        self.runner = StepRunner(model, optimizer, LossHead(model.store.device, temperature=float(getattr(loss, "temperature", 0.05))),
+                                 clip_grad=clip_grad, skip_nonfinite=skip_nonfinite)
         # TVTS_TRAINER_GRAPH=1: batches of a repeating shape are replayed from a captured hipGraph (world 1, fused optimizer).  OPT-IN:
         # measured equal to slower than the eager loop once prepare_batch stopped synchronising (profiles/r06_bench_product_path*.txt:
         # 141.8 - 142.2 against 140.3 - 140.5 ms at 192 pairs, 16.4 against 15.7 - 16.0 ms at 12) -- the copy into the captured
         # buffers and the replay of a two-stream graph cost what the saved launches return
         self.replay = GraphReplay(self.runner)
+
+    # the guard's skip count travels with the checkpoint (under the package's own key; the reference's keys are untouched).  Resume
+    # runs inside the base constructor, in front of the StepRunner: the counter is the optimizer's
+    def _extra_state(self):
+        if getattr(self, "runner", None) is not None and self.runner.guarding:
+            return {"skipped": int(self.optimizer.skipped.item())}
+        return None
+
+    def _load_extra_state(self, state):
+        if state and "skipped" in state and hasattr(self.optimizer, "skipped"):
+            self.optimizer.skipped.fill_(int(state["skipped"]))
 
     def _adjust_learning_rate(self, optimizer, epoch, args):
         lr_rate = 1.0
@@ -191,7 +211,8 @@ class _TrainerBase(Multi_BaseTrainer_dist):
         for loader in self.data_loader:
             if hasattr(loader, "train_sampler") and loader.train_sampler is not None:
                 loader.train_sampler.set_epoch(epoch)
-        lazy = _LazyLog(self.logger, self.LOG_LINE, self.model.store.device)
+        guarding = self.runner.guarding
+        lazy = _LazyLog(self.logger, self.LOG_LINE + (self.LOG_GRAD_NORM if guarding else ""), self.model.store.device, extra=int(guarding))
         for batch_idx, data_li in enumerate(_lockstep(self.data_loader, self.len_epoch)):
             for dl_idx, data in enumerate(data_li):
                 out = self.replay.step(self._tokenize(data))
@@ -206,7 +227,8 @@ class _TrainerBase(Multi_BaseTrainer_dist):
                 else:
                     total_loss[dl_idx] += float(l1 if l2 is None else l1 + l2)
                 if log_now:
-                    lazy.add((epoch, dl_idx, self._progress(batch_idx, dl_idx)), l1, l2)
+                    # (grad_norm is one device scalar every step overwrites: the copy is ordered behind this step on its stream)
+                    lazy.add((epoch, dl_idx, self._progress(batch_idx, dl_idx)), l1, l2, *((out["grad_norm"],) if guarding else ()))
                 lazy.flush()
         lazy.flush(block=True)
             # max_samples_per_epoch is stored and never read by the reference's TVTSv2 trainers (trainer.py:93,387,681):
@@ -214,6 +236,8 @@ class _TrainerBase(Multi_BaseTrainer_dist):
         for dl_idx, row in enumerate(step_loss.cpu().tolist()):
             total_loss[dl_idx] += sum(row)  # the same per-step fp32 values the reference adds up as Python floats
         log = {f"loss_{dl_idx}": total_loss[dl_idx] / self.len_epoch for dl_idx in range(len(self.data_loader))}
+        if guarding:  # steps the overflow guard has skipped so far (read behind the epoch's losses: the host has waited already)
+            log["skipped"] = int(self.runner.skipped.item())
         if self.do_validation:
             val_log = self._valid_epoch(epoch)
             if self.args.rank == 0:
@@ -324,9 +348,13 @@ class Trainer_TVTS(_TrainerBase):
     # on EVERY rank -- the file (written by rank 0) holds the rank-independent part of the seed, each rank adds its own offset back
     def _extra_state(self):
         eng = self.model.engine
-        return {"drop_seed_base": eng.drop_seed_base()} if hasattr(eng, "drop_seed") else None
+        extra = dict(super()._extra_state() or {})
+        if hasattr(eng, "drop_seed"):
+            extra["drop_seed_base"] = eng.drop_seed_base()
+        return extra or None
 
     def _load_extra_state(self, state):
+        super()._load_extra_state(state)
         eng = self.model.engine
         if not state or not hasattr(eng, "drop_seed"):
             return
