@@ -108,6 +108,16 @@ def guard_config(trainer_cfg: Mapping):
     return clip, skip
 
 
+def micro_batch_config(trainer_cfg: Mapping) -> int:
+    """``config['trainer']['micro_batches']`` (an int >= 1; absent: 1, the unsplit step) -> StepRunner's micro_batches: every
+    batch the loaders deliver is stepped from that many chunks, with the contrastive loss over the whole batch.  This package's
+    own optional key; a value of another type is an error, not a default."""
+    n = trainer_cfg.get("micro_batches", 1)
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"config['trainer']['micro_batches'] must be an int >= 1 (or absent), got {n!r}")
+    return n
+
+
 class Multi_BaseTrainer_dist:
     CHECKPOINT_NAME = "checkpoint-epoch{}.pth"
     BEST_NAME = "model_best.pth"

@@ -1497,8 +1497,10 @@ class Engine:
             out[k] = devbuf[offs[k]:offs[k] + nb].view(t.dtype).view(t.shape)
         return out
 
-    def forward(self, pb: dict):
-        """-> (text_emb [B,E], video_emb [B,E], pred [B*NT, n_trans] | None); all fp32 workspace tensors."""
+    def forward(self, pb: dict, sort_head: bool = True):
+        """-> (text_emb [B,E], video_emb [B,E], pred [B*NT, n_trans] | None); all fp32 workspace tensors.
+        sort_head=False (the embedding pass of the micro-batched step): the same launches up to the two embeddings,
+        hence their bits; the sort head is left out and pred is None."""
         a = self.arch
         self.ctx = pb
         self._tick += 1  # (workspace: a buffer whose shape changes from here on belongs to a new step, see _b)
@@ -1518,7 +1520,7 @@ class Engine:
         self._text_join()
         if self.embeds_ready is not None:  # the embedding all-gather starts here and travels under the sort head's forward
             self.embeds_ready(text_emb, video_emb)
-        pred = self.sort_forward(out, text_before, B, S, NT) if (NT != 1 and self.has_sort_head) else None
+        pred = self.sort_forward(out, text_before, B, S, NT) if (NT != 1 and self.has_sort_head and sort_head) else None
         return text_emb, video_emb, pred
 
     class _TextLane:
@@ -1749,9 +1751,11 @@ class LossHead:
         K.l2norm_rows_bwd(dtn, tn, ti, dt)
         return loss, dv, dt
 
-    def sorting(self, pred, labels_i32, need_grad=True):
-        """2 * CrossEntropy (trainer.py:487-492) -> (loss2, dpred)."""
-        loss = self._f("loss2", (1,), zero=True)
+    def sorting(self, pred, labels_i32, need_grad=True, scale=2.0, add=False):
+        """2 * CrossEntropy (trainer.py:487-492) -> (loss2, dpred).  scale / add (the micro-batched step): the kernel means over the
+        rows it is given, so chunk k of n passes scale 2 / n, and add=True keeps the value the earlier chunks left in loss2 -- the
+        kernel adds to it, the n shares sum to the full batch's 2 * CE in chunk order."""
+        loss = self._f("loss2", (1,), zero=not add)
         dp = self._f("dpred", pred.shape) if need_grad else None
-        K.cross_entropy(pred, labels_i32, 2.0, dp, loss)
+        K.cross_entropy(pred, labels_i32, scale, dp, loss)
         return loss, dp

@@ -35,15 +35,87 @@ def guard_options(clip_grad, skip_nonfinite, *, fused: bool, ranged: bool, optim
     return clip, skip
 
 
+def micro_batch_option(micro_batches, *, fused: bool = True, ranged: bool = False, family=None, optimizer: str = "the optimizer") -> int:
+    """StepRunner's micro_batches as it keeps it (an int >= 1), or the named refusal: anything that is not such an int; and, for
+    n > 1, an optimizer that is not the fused one, the ranged update, the v1 engine."""
+    n = micro_batches
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"StepRunner: micro_batches {micro_batches!r} must be an int >= 1 (1: the unsplit step)")
+    if n == 1:
+        return n
+    if family == "v1":
+        raise NotImplementedError(f"StepRunner(micro_batches={n}) is not built for the v1 engine: its text dropout seed advances with "
+                                  "every forward, so a second forward does not reproduce the first, and it has no forward-only encoders")
+    if not fused:
+        raise RuntimeError(f"StepRunner(micro_batches={n}) needs the fused optimizer (FusedHFAdamW): one update behind the last "
+                           f"chunk's backward, the gradient scale folded into its launch; got {optimizer}")
+    if ranged:
+        raise RuntimeError(f"StepRunner(micro_batches={n}) cannot be combined with adamw_ranges / TVTS_ADAMW_RANGES=1: a ranged update "
+                           "starts before the last chunk's gradient exists")
+    return n
+
+
+# the per-clip fields of the reference batch dict, sliced by clip; "text" is transcript-major and handled apart
+_PER_CLIP = ("video", "keep_ind", "crop", "label")
+
+
+def split_batch(data: dict, n: int):
+    """The reference batch dict of B clips -> n dicts of b = B / n clips, chunk k holding the clips [k * b, (k + 1) * b).
+    text is TRANSCRIPT-major (row t * B + b, what prepare_batch and the model's reshape(NT, B, -1) read): chunk rows are
+    text.reshape(NT, B, L)[:, lo:hi], never a contiguous slice of rows.  video (fp32 or the uint8 wire format), keep_ind [B, n],
+    crop [B, 2] and label are sliced by clip; keep_ind [1, n] and resize are kept; a device-drawn mask keeps mask_seed and moves
+    sample_offset by lo (tvts_tube_mask numbers the samples globally); everything else (meta, ...) is carried through untouched."""
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"split_batch: n {n!r} must be an int >= 1")
+    video = data["video"]
+    if video.dim() < 4:
+        raise ValueError(f"split_batch: video {tuple(video.shape)} has no clip dimension")
+    B = int(video.shape[0])
+    if B % n:
+        raise ValueError(f"split_batch: micro_batches {n} does not divide the batch of {B} clips (unequal chunks are not built)")
+    b = B // n
+    text = data["text"]
+    if text.dim() != 2 or text.shape[0] == 0 or text.shape[0] % B:
+        raise ValueError(f"split_batch: text {tuple(text.shape)}: expected n_trans * {B} token rows (transcript-major)")
+    NT, L = text.shape[0] // B, text.shape[1]
+    for key in _PER_CLIP[1:]:
+        t = data.get(key)
+        if torch.is_tensor(t) and not (key == "keep_ind" and t.shape[0] == 1) and (t.dim() == 0 or t.shape[0] != B):
+            raise ValueError(f"split_batch: {key} {tuple(t.shape)} is not per clip (expected {B} rows)")
+    out = []
+    for k in range(n):
+        lo, hi = k * b, (k + 1) * b
+        d = {}
+        for key, val in data.items():
+            if key == "text":
+                d[key] = text.reshape(NT, B, L)[:, lo:hi].reshape(NT * b, L)
+            elif key in _PER_CLIP and torch.is_tensor(val) and not (key == "keep_ind" and val.shape[0] == 1):
+                d[key] = val[lo:hi]
+            elif key == "sample_offset":
+                continue
+            else:
+                d[key] = val
+        if "mask_seed" in data and "keep_ind" not in data:
+            d["sample_offset"] = int(data.get("sample_offset", 0)) + lo
+        elif "sample_offset" in data:
+            d["sample_offset"] = data["sample_offset"]
+        out.append(d)
+    return out
+
+
 class StepRunner:
     def __init__(self, model, optimizer, loss_head: Optional[LossHead] = None, clip_grad: Optional[float] = None,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, micro_batches: int = 1):
         """clip_grad (max_norm of torch.nn.utils.clip_grad_norm_ over the trainable tensors, None / 0: off) and skip_nonfinite (the
         overflow guard: a step whose global gradient norm is not finite changes no bit of the weights, the moments, the shadows or
         the e4m3 scales, and counts in ``skipped``) are both decided on the device: tvts_grad_sumsq behind the gradient exchange
         leaves norm and coefficient in ``norm_coef``, FusedHFAdamW reads them there.  The norm is that of the AVERAGED gradient,
         the number clip_grad_norm_ sees behind DDP, and every rank computes it from the same reduced buffer: no collective is
-        added.  With both off the step is launch for launch the one without these arguments."""
+        added.  With both off the step is launch for launch the one without these arguments.
+        micro_batches = n > 1: the step of a batch of B clips from n chunks of B / n, with the InfoNCE over the WHOLE
+        batch -- every chunk forward once for its [b, E] embeddings (two [B, E] caches), one gather + loss + dE over all rows, then
+        each chunk forward again and backward with its rows of dE into the same gradient buffer; one exchange, one update.  The
+        activations held are those of one chunk.  1: launch for launch the unsplit step."""
         self.model, self.opt = model, optimizer
         self.eng, self.store = model.engine, model.store
         self.head = loss_head or LossHead(self.store.device)
@@ -64,11 +136,18 @@ class StepRunner:
         self.clip_grad, self.skip_nonfinite = guard_options(clip_grad, skip_nonfinite, fused=self.fused and hasattr(optimizer, "begin_ranges"),
                                                             ranged=self.ranged, optimizer=type(optimizer).__name__)
         self.guarding = self.clip_grad is not None or self.skip_nonfinite
+        self.micro_batches = micro_batch_option(micro_batches, fused=self.fused, ranged=self.ranged, family=self.eng.arch.get("family"),
+                                                optimizer=type(optimizer).__name__)
+        self.micro_observer = None  # optional callback(k, text_emb, video_emb) behind chunk k's second forward (tests: cache identity)
+        self._emb_cache = None      # the two [B, E] fp32 embedding caches of the micro-batched step (text, video), grown on demand
         # every rank enters this, with or without the options: a rank that guards beside one that does not would skip alone
         # (only where a process group exists: the check is a collective)
         if D.dist.is_available() and D.dist.is_initialized():
             D.agree(repr(("clip_grad", self.clip_grad, "skip_nonfinite", self.skip_nonfinite)).encode(),
                     "StepRunner: clip_grad or skip_nonfinite")
+            # (a rank that splits beside one that does not would run the same collectives, but a chunk count is part of what the
+            # ranks must have in common: the batch each one hands over has to divide by it)
+            D.agree(repr(("micro_batches", self.micro_batches)).encode(), "StepRunner: micro_batches")
         if self.guarding:
             dev = self.store.device
             self.norm_coef = torch.zeros(2, dtype=torch.float32, device=dev)  # [global norm, clip coefficient] of the last step
@@ -131,6 +210,12 @@ class StepRunner:
             self.eng.training = bool(m.training)
         m._fresh_shadows()
         m._sync_requires_grad()
+        if self.micro_batches > 1:
+            if pb is not None:
+                raise ValueError("StepRunner(micro_batches > 1).step prepares its chunks itself: pass the batch dict, not a prepared batch")
+            chunks = split_batch(data, self.micro_batches)
+            pbs = [self.eng.prepare_batch(c) for c in chunks]  # once: both passes run on the same masks and index tables
+            return self.run_micro(pbs, [self._labels(c, p) for c, p in zip(chunks, pbs)], device_step)
         if pb is None:
             pb = self.eng.prepare_batch(data)
         return self.run(pb, self._labels(data, pb), device_step)
@@ -163,6 +248,59 @@ class StepRunner:
             self.eng.backward(d_te, d_ve, dpred)
         finally:
             self.eng.param_ready = None
+        return self._update(loss1, loss2, device_step)
+
+    def _caches(self, B, E):
+        c = self._emb_cache
+        if c is None or c[0].shape[0] < B or c[0].shape[1] != E:
+            c = self._emb_cache = tuple(torch.empty(B, E, dtype=torch.float32, device=self.store.device) for _ in range(2))
+        return c[0][:B], c[1][:B]
+
+    def run_micro(self, pbs, labels, device_step=False):
+        """The device-side part of the micro-batched step: pbs / labels are the chunks' prepared batches and sorting
+        labels, in clip order.  Pass 1 is the training forward without the sort head (the forward-only video encoder runs the last
+        block's CLS tail and the full-frame SPACE kernel of its own: not the training forward's bits), so its last chunk, run with
+        the sort head, is also pass 2's first forward."""
+        eng, n = self.eng, len(pbs)
+        b, E = pbs[0]["B"], eng.arch["embed"]
+        if any(p["B"] != b for p in pbs):
+            raise ValueError("StepRunner.run_micro: chunks of unequal size")
+        B = n * b
+        if self.sync.W > 1:
+            D._apply_cu_reservation(b * pbs[0]["S"])
+        self.sync.bytes_sent = 0
+        t_cache, v_cache = self._caches(B, E)
+        fwd = None
+        for k, pb in enumerate(pbs):  # pass 1: embeddings only (embeds_ready stays unarmed: the gather is of the whole batch's rows)
+            fwd = eng.forward(pb, sort_head=(k == n - 1))
+            t_cache[k * b:(k + 1) * b].copy_(fwd[0])
+            v_cache[k * b:(k + 1) * b].copy_(fwd[1])
+        self.gather.start(t_cache, v_cache)
+        vg, tg = self._bracket("gather", self.gather.result)
+        loss1, dv_all, dt_all = self.head.contrastive(vg, tg)
+        d_te, d_ve = D.local_rows(dt_all, B), D.local_rows(dv_all, B)
+        ready, eng.grad_ready = eng.grad_ready, None  # the range exchange is armed for the last backward only: an earlier
+        loss2 = None                                  # all-reduce would sum partial gradients in place
+        K.zero_(self.store.grad)
+        try:
+            for i, k in enumerate([n - 1] + list(range(n - 1))):  # pass 2, starting with the chunk whose forward is still held
+                pb = pbs[k]
+                te, ve, pred = fwd if i == 0 else eng.forward(pb)
+                if self.micro_observer is not None:
+                    self.micro_observer(k, te, ve)
+                dpred = None
+                if pred is not None:
+                    loss2, dpred = self.head.sorting(pred, labels[k], scale=2.0 / n, add=i > 0)
+                if i == n - 1:
+                    eng.grad_ready = ready
+                eng.backward(d_te[k * b:(k + 1) * b], d_ve[k * b:(k + 1) * b], dpred)
+        finally:
+            eng.grad_ready = ready
+        return self._update(loss1, loss2, device_step)
+
+    def _update(self, loss1, loss2, device_step):
+        """Behind the (last) backward, once per step: the e4m3 scales, the end of the gradient exchange, the norm when guarding, the
+        optimizer."""
         if hasattr(self.eng, "end_step") and not self.skip_nonfinite:
             self.eng.end_step()  # (e4m3 weight gradients: this step's amax values become the next step's per-tensor scales)
         scale = self._bracket("allreduce", self.sync.finish)
@@ -241,9 +379,10 @@ class GraphReplay:
         self.r = runner
         self.cache = {}
         # (skip_nonfinite: the guarded optimizer launch refuses a stream capture, so such a runner steps eagerly; clip_grad alone is
-        # capturable -- the coefficient is a device scalar the replayed launches read)
+        # capturable -- the coefficient is a device scalar the replayed launches read; micro_batches > 1: the micro-batched step has
+        # never been captured, such a runner steps eagerly as well)
         self.usable = (torch.cuda.is_available() and runner.fused and not runner.ranged and runner.sync.W == 1 and not runner.sync.native
-                       and not runner.skip_nonfinite and os.environ.get("TVTS_TRAINER_GRAPH", "0") == "1")
+                       and not runner.skip_nonfinite and runner.micro_batches == 1 and os.environ.get("TVTS_TRAINER_GRAPH", "0") == "1")
         self.replays = self.captures = self.eager = 0
 
     def step(self, data: dict):
@@ -271,7 +410,7 @@ class GraphReplay:
             return r.run(pb, labels, device_step=True)
         sig = (_signature(pb), None if labels is None else tuple(labels.shape), bool(m.training),
                hash(tuple(r.eng.requires_grad.values())) if hasattr(r.eng, "requires_grad") else None,
-               getattr(r.eng, "recompute", "none"))  # (a graph holds the launches of the mode it was captured in)
+               getattr(r.eng, "recompute", "none"), r.micro_batches)  # (a graph holds the launches of the mode it was captured in)
         ent = self.cache.get(sig)
         if ent is None:
             if len(self.cache) >= self.MAX_SIGNATURES:

@@ -17,7 +17,7 @@ import torch
 import torch.distributed as dist
 
 from ..base import Multi_BaseTrainer_dist
-from ..base.base_trainer import guard_config
+from ..base.base_trainer import guard_config, micro_batch_config
 from ..model._common import sim_matrix  # noqa: F401  (the reference re-exports it at module scope)
 from ..step import GraphReplay, StepRunner
 
@@ -162,8 +162,10 @@ class _TrainerBase(Multi_BaseTrainer_dist):
         # config["trainer"]["clip_grad"] / ["skip_nonfinite"] (both optional, this package's own keys): gradient clipping by global norm
         # and the overflow guard of the step, decided on the device.  Absent: the trainer without them, log text included.
         clip_grad, skip_nonfinite = guard_config(config["trainer"])
+        # config["trainer"]["micro_batches"] (optional, this package's own key): every batch stepped from that many chunks with the
+        # InfoNCE over the whole batch.  Absent / 1: the unsplit step.
         self.runner = StepRunner(model, optimizer, LossHead(model.store.device, temperature=float(getattr(loss, "temperature", 0.05))),
-                                 clip_grad=clip_grad, skip_nonfinite=skip_nonfinite)
+                                 clip_grad=clip_grad, skip_nonfinite=skip_nonfinite, micro_batches=micro_batch_config(config["trainer"]))
         # TVTS_TRAINER_GRAPH=1: batches of a repeating shape are replayed from a captured hipGraph (world 1, fused optimizer).  OPT-IN:
         # measured equal to slower than the eager loop once prepare_batch stopped synchronising (profiles/r06_bench_product_path*.txt:
         # 141.8 - 142.2 against 140.3 - 140.5 ms at 192 pairs, 16.4 against 15.7 - 16.0 ms at 12) -- the copy into the captured
