@@ -422,7 +422,9 @@ def ln_cols_check(dy, x, mean, rstd, dgamma, dbeta, dgamma0, dbeta0, *, what):
 # >= 3x that and under the whole-tensor gates (8e-3 forward, 2e-2 backward).  The streaming FULL, kv_len, dropout, tail, one-row and
 # split divided kernels of tests/test_attention_rows_gpu.py, against float64 on the output and lse2 they read, stay under the same
 # table without a case of their own: worst out 2.58e-3 (kv_len dropout), dq 3.22e-3 (split, B/16 time), dk 3.03e-3, dv 2.87e-3
-# (profiles/r09_attention_rows_bounds.txt); the bf16 roundings of P and dS alone give 2.9e-3 .. 4.2e-3 in float64
+# (profiles/r09_attention_rows_bounds.txt), and so do the fused divided site kernels at every tile class and launch layout of
+# tests/test_attention_fused_rows_gpu.py: worst out 2.09e-3, dq 3.24e-3, dk 3.00e-3, dv 3.01e-3, lse2 1.6e-5 absolute
+# (profiles/r26_attention_fused_rows_bounds.txt); the bf16 roundings of P and dS alone give 2.9e-3 .. 4.2e-3 in float64
 # (tests/test_kernel_bounds_cpu.py::test_bf16_rounding_emulation_sits_inside_the_attention_tolerances)
 ATTN_ROW_TOL = {"out": 7e-3, "dq": 1.2e-2, "dk": 1.2e-2, "dv": 1.2e-2}
 LSE2_TOL = 1e-3           # absolute, log2 domain: the gate test_short_sequence_attention holds between two kernels
@@ -574,16 +576,27 @@ def divided_bwd_same_inputs(qkv, dO, O_read, lse2_read, heads, dh, mode, T, n, *
     return attn_bwd_same_inputs(qkv, dO, O_read, lse2_read, heads, dh, allowed=divided_allowed(mode, T, n), **kw)
 
 
-def attn_conditioning(qkv, dO, heads, dh, *, floor=0.05, **kw):
+def divided_mixed_o_read(O_exact, out_kernel):
+    """[B, S, W] float64: the output the FUSED divided backward takes D = rowsum(dO o O) from.  Its patch rows form D in registers
+    from the unrounded output (O_exact, float64, stands for it); its CLS rows (row 0 of every clip) get D from attn_delta_kernel on
+    the bf16 `out` the forward stored (out_kernel, widened)."""
+    o = O_exact.double().clone()
+    o[:, 0] = out_kernel[:, 0].double()
+    return o
+
+
+def attn_conditioning(qkv, dO, heads, dh, *, floor=0.05, o_read=None, **kw):
     """How far float64 autograd is from ANY backward that takes delta from the saved bf16 output: per (row, head) rows_rel of
     attn_bwd_same_inputs(O_read = bf16(O_exact), lse2_exact) against autograd -> {"dq" | "dk" | "dv": [B * S, heads]}.
-    A property of the inputs alone (no kernel): with few keys dP - delta cancels and the rounding of O shows through in dQ / dK."""
+    A property of the inputs alone (no kernel): with few keys dP - delta cancels and the rounding of O shows through in dQ / dK.
+    o_read: the output a backward reads as a function of the exact one, where it is not bf16(O_exact) in every row
+    (divided_mixed_o_read)."""
     B, S, W3 = qkv.shape
     W = W3 // 3
     out, ref = attn_autograd(qkv, dO, heads, dh, **kw)
     with torch.no_grad():
         _, lse2, _ = attn_fwd_ref(qkv, heads, dh, **kw)
-        got = attn_bwd_same_inputs(qkv, dO, out.bfloat16(), lse2, heads, dh, **kw)
+        got = attn_bwd_same_inputs(qkv, dO, out.bfloat16() if o_read is None else o_read(out), lse2, heads, dh, **kw)
     res = {}
     for i, nm in enumerate(("dq", "dk", "dv")):
         sl = slice(i * W, (i + 1) * W)

@@ -270,7 +270,10 @@ def test_row_query_attention_per_row(K, dh):
 # shares with fp32 atomics into the first B * heads * 3 * dh elements whatever the size of the scratch, so every case passes that
 # minimum ("atomic"); one case passes the room for the fused kernels' ordered partials ("parts": the larger buffer is not misread)
 SPLIT_CASES = [("time", 8, 30, False, "atomic"), ("time", 33, 3, True, "atomic"), ("space", 2, 111, False, "atomic"),
-               ("space", 2, 111, False, "parts"), ("space", 2, 112, True, "atomic"), ("space", 1, 196, True, "atomic")]
+               ("space", 2, 111, False, "parts"), ("space", 2, 112, True, "atomic"), ("space", 1, 196, True, "atomic"),
+               # the first split sizes (SPACE n = 112 above, TIME T = 32); the last fused ones, n = 111 and T = 31, are held per
+               # (row, head) by tests/test_attention_fused_rows_gpu.py
+               ("time", 32, 3, True, "atomic")]
 
 
 def _split_divided(K, tag, mode, B, T, n, heads, dh, fused, acc_kind, seed):

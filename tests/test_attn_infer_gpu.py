@@ -62,10 +62,12 @@ def _pair(run):
 
 @pytest.mark.parametrize("dh", [64, 80])
 @pytest.mark.parametrize("mode,B,T,n,fused", [("space", 2, 4, 98, True), ("space", 1, 12, 49, True), ("time", 2, 12, 196, True),
-                                              ("time", 1, 16, 76, True), ("space", 2, 3, 196, False)])
+                                              ("time", 1, 16, 76, True), ("space", 2, 3, 196, False),
+                                              ("space", 2, 3, 16, True), ("time", 2, 20, 29, True), ("time", 2, 31, 3, True)])
 def test_divided_forward_only_keeps_the_bits(K, mode, B, T, n, fused, dh):
     """fused SPACE (n + 1 <= 112) and TIME: the same kernels with the LSE store skipped; the split SPACE path (fused=False at
-    n = 196: the streaming kernel + the CLS-query pass) likewise"""
+    n = 196: the streaming kernel + the CLS-query pass) likewise.  The last three: a SPACE tile with one live row, the last size of
+    the TIME <2, 20> class with a one-position last chunk, the largest TIME tile with waves that own no group"""
     heads = 2
     S, W = 1 + T * n, heads * dh
     qkv = _qkv(B * S, W, seed=3 * n + T)

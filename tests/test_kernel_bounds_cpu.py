@@ -778,3 +778,161 @@ def test_layernorm_edge_mistakes_are_rejected():
         fails(f(fwd, "row_late"), "outside the bound", "non-finite", "(row 6")     # a row's result one row late
         fails(f(fwd, "row_late", extra=2), "outside the bound", "(row 6")          # ... into a row past M (poison, not a guard)
         fails(b(bwd, "row_late"), "outside the bound", "(row 6")
+
+
+# ------------------------------------------------------------------------------------------------ fused divided site kernels
+import attn_fused_cases as FC  # noqa: E402
+
+
+def test_fused_divided_reference_is_within_half_the_tolerance_of_autograd_at_the_tiny_geometries():
+    """tests/test_attention_fused_rows_gpu.py holds the fused backward to float64 on what it read: the exact output in the patch
+    rows, the bf16 output in the CLS rows (divided_mixed_o_read).  With 2 .. 4 keys per query dP - delta cancels, so that reference
+    is first held to float64 autograd itself, with no kernel: at the sweep's smallest geometries, for the inputs the GPU test
+    draws, every (row, head) slice of dq / dk / dv is within HALF of its ATTN_ROW_TOL entry (dv does not read delta: exact).
+    The patch rows of the reference are autograd's up to the CLS query's share in dK; what is left comes from the bf16 rounding of
+    the CLS output row, and seven (geometry, dh) pairs take a later draw for it (attn_fused_cases.SEED_SHIFT)."""
+    worst = {}
+    for mode, T, n in FC.TINY_CASES:
+        for dh in (64, 80):
+            S, W = 1 + T * n, FC.HEADS * dh
+            qkv, dO = FC.plain_inputs(mode, T, n, dh)
+            e = KB.attn_conditioning(qkv.double().view(FC.B, S, 3 * W), dO.double().view(FC.B, S, W), FC.HEADS, dh,
+                                     allowed=KB.divided_allowed(mode, T, n), o_read=lambda o: KB.divided_mixed_o_read(o, o.bfloat16()))
+            for nm, v in e.items():
+                assert float(v.max()) <= TOL[nm] / 2, (mode, T, n, dh, nm, float(v.max()))
+                worst[nm] = max(worst.get(nm, 0.0), float(v.max()))
+            assert float(e["dq"].reshape(FC.B, S, FC.HEADS)[:, 1:].max()) < 1e-12   # patch queries: D from the exact output
+    print("CONDITIONING fused mixed reference, tiny geometries:", {k: f"{v:.3g}" for k, v in worst.items()})
+    # the first draw of one of the shifted geometries does exceed it: the shift is not decoration
+    qkv, dO = FC.plain_inputs("space", 1, 1, 80, seed=FC.seed_of("space", 1, 1, 80) - 100000 * FC.SEED_SHIFT[("space", 1, 1, 80)])
+    e = KB.attn_conditioning(qkv.double().view(FC.B, 2, -1), dO.double().view(FC.B, 2, -1), FC.HEADS, 80,
+                             allowed=KB.divided_allowed("space", 1, 1), o_read=lambda o: KB.divided_mixed_o_read(o, o.bfloat16()))
+    assert float(e["dq"].max()) > TOL["dq"], float(e["dq"].max())
+
+
+def test_fused_divided_stress_inputs_have_a_finite_reference_and_the_stated_scores():
+    """the second input family of the GPU sweep (attn_fused_cases.stress_inputs), no kernel: no reference slice is non-finite; in
+    head 0 the CLS row puts all but 2^-24 of its weight on the one aligned key (so its group's partial dominates every other by more
+    than 2^24) and some patch rows have one-key softmaxes; in head 1 lse2 = log2(keys) exactly and dq = dk = 0"""
+    for mode, T, n in FC.STRESS_CASES:
+        for dh in (64, 80):
+            S, W = 1 + T * n, FC.HEADS * dh
+            qkv, dO = FC.stress_inputs(mode, T, n, dh)
+            qkv, dO = qkv.double(), dO.double()
+            ro, rl = FC.forward_ref(qkv, mode, T, n, dh)
+            rd = FC.backward_ref(qkv, dO, ro, ro.bfloat16(), rl, mode, T, n, dh)
+            assert torch.isfinite(ro).all() and torch.isfinite(rl).all() and torch.isfinite(rd).all(), (mode, T, n, dh)
+            P = KB.divided_fwd_ref(qkv.view(FC.B, S, 3 * W), FC.HEADS, dh, mode, T, n)[2]
+            for b in range(FC.B):
+                r = FC.stress_row(mode, T, n, b)
+                assert r >= 1 and float(1.0 - P[b, 0, 0, r]) < 2.0 ** -24, (mode, T, n, dh, b, float(P[b, 0, 0, r]))
+            assert int((P[:, 0, 1:].max(-1).values > 1 - 2.0 ** -9).sum()) >= 4, (mode, T, n, dh)
+            keys = KB.divided_allowed(mode, T, n).sum(1).double()
+            assert float((rl.view(FC.B, S, FC.HEADS)[:, :, 1] - torch.log2(keys)).abs().max()) < 1e-13, (mode, T, n, dh)
+            z = rd.view(FC.B * S, 3, FC.HEADS, dh)
+            assert (z[:, :2, 1] == 0).all() and (z[:, 2, 1] != 0).any()
+
+
+def _site_refs(mode, T, n, dh):
+    qkv, dO = FC.plain_inputs(mode, T, n, dh)
+    qkv, dO = qkv.double(), dO.double()
+    ro, rl = FC.forward_ref(qkv, mode, T, n, dh)
+    return qkv, dO, ro, rl, FC.backward_ref(qkv, dO, ro, ro.bfloat16(), rl, mode, T, n, dh)
+
+
+def _with_extra_keys(qkv, dO, mode, T, n, dh, edit=None):
+    """(out, lse2, dqkv) of the site in float64 autograd with one edit (clip, query row, key rows, seen) of the key relation; key
+    S is a padding row (q = k = v = 0: a key at score 0 with a zero value) that no query sees unless the edit says so"""
+    S, W = 1 + T * n, FC.HEADS * dh
+    pad = lambda t: torch.cat([t.view(FC.B, S, -1), torch.zeros(FC.B, 1, t.shape[-1], dtype=t.dtype)], 1)  # noqa: E731
+    al = torch.zeros(FC.B, 1, S + 1, S + 1, dtype=torch.bool)
+    al[:, 0, :S, :S] = KB.divided_allowed(mode, T, n)
+    al[:, 0, S, S] = True
+    if edit is not None:
+        b, query, keys, seen = edit
+        al[b, 0, query, keys] = seen
+    out, dqkv = KB.attn_autograd(pad(qkv), pad(dO), FC.HEADS, dh, allowed=al)
+    lse2 = KB.attn_fwd_ref(pad(qkv), FC.HEADS, dh, allowed=al)[1]
+    return out[:, :S].reshape(FC.B * S, W), lse2[:, :S].reshape(FC.B * S, FC.HEADS), dqkv[:, :S].reshape(FC.B * S, 3 * W)
+
+
+def test_fused_divided_gates_catch_single_faults_of_the_fused_kernels():
+    """The gates of tests/test_attention_fused_rows_gpu.py (attn_fused_cases.gate_forward / gate_backward) on float64 results with
+    ONE fault of the kind the fused kernels can make, SPACE (n = 16, T = 3: one live row in the last tile) and TIME (T = 19, n = 29:
+    the <2, 20> tile, a one-position last chunk): each raises, and names the quantity.  The whole-tensor rel of
+    test_attention_site_forward / _backward (8e-3 / 2e-2) is computed for the same fault alone."""
+    dh = 64
+    W = FC.HEADS * dh
+    for mode, T, n in (("space", 3, 16), ("time", 19, 29)):
+        S = 1 + T * n
+        qkv, dO, ro, rl, rd = _site_refs(mode, T, n, dh)
+        tag = f"fault[{mode}]"
+
+        def gates(out=ro, lse=rl, dqkv=rd):
+            FC.gate_forward(tag, out, lse, ro, rl, S)
+            FC.gate_backward(tag, dqkv, rd, S)
+
+        def old(out=ro, dqkv=rd):
+            """the old gates' whole-tensor figures"""
+            return {"out": rel(out, ro), **{nm: rel(a, b) for (nm, a), b in zip(_thirds(dqkv, W).items(), _thirds(rd, W).values())}}
+
+        gates()                                                                 # the clean result passes
+        clean = _with_extra_keys(qkv, dO, mode, T, n, dh)
+        assert rel(clean[0], ro) < 1e-13 and rel(clean[1], rl) < 1e-13
+        if mode == "space":   # frame 1 of clip 1; its last row is the single live row of the second tile
+            b, last, nb = 1, 1 + 1 * n + (n - 1), n          # neighbouring group: the same row of the next frame
+            block = torch.arange(1 + n, 1 + 2 * n)           # the queries of that frame's block
+            left_out = block                                 # the keys of one frame's CLS partial
+        else:                 # patch position 28 of clip 0 (the one-position last chunk); its last row is row 19 of a 20-row tile
+            b, last, nb = 0, 1 + (T - 1) * n + 28, -1        # neighbouring group: the same frame of position 27
+            block = 1 + torch.arange(T) * n + 28             # the queries of chunk 1's block
+            p = torch.arange(2, 28, 4)                       # the positions of wave 2 of chunk 0
+            left_out = (1 + torch.arange(T)[:, None] * n + p[None, :]).reshape(-1)
+        r = b * S + last
+        seen = {}
+        # ---- (a) the last live row of the group's last tile also sees ONE padding key at score 0
+        bad = _with_extra_keys(qkv, dO, mode, T, n, dh, (b, last, S, True))
+        out_a, lse_a, dq_a = ro + (bad[0] - clean[0]), rl + (bad[1] - clean[1]), rd + (bad[2] - clean[2])
+        assert int(((out_a - ro).abs().sum(1) > 0).sum()) == 1               # one row of out; dK / dV of the group's keys follow
+        fails(lambda: gates(out=out_a), " out", f"[{r}, ")
+        fails(lambda: gates(lse=lse_a), "lse2", f"(row {r},")
+        fails(lambda: gates(dqkv=dq_a), " dq", f"[{r}, ")
+        seen["a"] = old(out_a, dq_a)
+        # ---- (b) the CLS output merged without one frame's (SPACE) / one wave's (TIME) partial
+        bad = _with_extra_keys(qkv, dO, mode, T, n, dh, (b, 0, left_out, False))
+        out_b, lse_b = ro.clone(), rl.clone()
+        out_b[b * S], lse_b[b * S] = bad[0][b * S], bad[1][b * S]
+        fails(lambda: gates(out=out_b), " out", f"[{b * S}, ")
+        fails(lambda: gates(lse=lse_b), "lse2", f"(row {b * S},")
+        seen["b"] = old(out_b)
+        # ---- (c) one patch row's result taken from the same row of the neighbouring group
+        out_c, lse_c, dq_c = ro.clone(), rl.clone(), rd.clone()
+        out_c[r], lse_c[r], dq_c[r] = ro[r + nb], rl[r + nb], rd[r + nb]
+        fails(lambda: gates(out=out_c), " out", f"[{r}, ")
+        fails(lambda: gates(lse=lse_c), "lse2", f"(row {r},")
+        fails(lambda: gates(dqkv=dq_c), " dq", f"[{r}, ")
+        seen["c"] = old(out_c, dq_c)
+        # ---- (d) dK of the CLS row without one block's share
+        qr = torch.zeros(FC.B, S, dtype=torch.bool)
+        qr[b, block] = True
+        share = KB.attn_bwd_same_inputs(qkv.view(FC.B, S, 3 * W), dO.view(FC.B, S, W), ro.view(FC.B, S, W), rl.view(FC.B, S, FC.HEADS),
+                                        FC.HEADS, dh, allowed=KB.divided_allowed(mode, T, n), q_rows=qr)[b, 0, W:2 * W]
+        dq_d = rd.clone()
+        dq_d[b * S, W:2 * W] -= share
+        fails(lambda: gates(dqkv=dq_d), " dk", f"[{b * S}, ")
+        seen["d"] = old(dqkv=dq_d)
+        for k, v in seen.items():
+            print(f"FAULT {mode} ({k}) whole-tensor rel:", {q: f"{x:.3g}" for q, x in v.items()})
+        # the whole-tensor gates of test_attention_site_forward / _backward with that fault alone.  Under them, i.e. invisible so far:
+        # the padding key in both modes (SPACE 4.4e-3 out, 4.4e-3 .. 4.7e-3 dq / dk / dv; TIME 9.7e-4, 1.0e-3 .. 1.2e-3) and the
+        # dropped wave partial of TIME (3.1e-3).  NOT under them at these sizes (B = 2, 98 / 1 104 rows), so not asserted: a whole
+        # frame's partial dropped from the SPACE CLS row (5.3e-2 of out), a row taken from the neighbouring group (SPACE 0.13 .. 0.14,
+        # TIME 3.6e-2 .. 4.5e-2: one wholly wrong row of so few is seen by a norm over all of them), the CLS dK short of a block
+        # (SPACE 0.10: a third of its queries; TIME 2.02e-2 against the 2e-2 gate).  So the premise this test set out with -- such
+        # single faults are invisible to the whole-tensor gates -- holds for 3 of the 8 at these sizes and NOT for most single-row
+        # faults: with 98 or 1 104 rows a wholly wrong row is 4e-2 .. 0.14 of the norm.  What the old gates cannot do at any size is
+        # name the row, and they miss the same faults once the batch is a few hundred times larger (the per-row gates do not dilute).
+        for k in {"space": ("b", "c", "d"), "time": ("c", "d")}[mode]:   # recorded, so that a change of these figures is noticed
+            assert seen[k]["out"] >= 8e-3 or max(seen[k][q] for q in ("dq", "dk", "dv")) >= 2e-2, (mode, k, seen[k])
+        for k in {"space": ("a",), "time": ("a", "b")}[mode]:
+            assert seen[k]["out"] < 8e-3 and max(seen[k][q] for q in ("dq", "dk", "dv")) < 2e-2, (mode, k, seen[k])

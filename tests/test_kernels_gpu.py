@@ -1793,7 +1793,7 @@ def test_short_sequence_attention_per_row_at_the_step_size(K, B):
 
 
 def _divided_case(geo, mode, seed):
-    c = KB.DIVIDED[geo]
+    c = KB.DIVIDED[geo] if isinstance(geo, str) else geo
     B, T, n, heads, dh = c["B"], c["T"], c["n"], c["heads"], c["dh"]
     S, W = 1 + T * n, heads * dh
     g = torch.Generator(device=DEV).manual_seed(seed)
@@ -1839,11 +1839,18 @@ def test_divided_attention_per_row_at_the_step_geometry(K, geo, mode, fused):
         KB.bound_line(f"{tag} {nm} (per-row rel)", w); KB.bound_line(f"{tag} {nm} CLS (per-row rel)", wc)
 
 
-@pytest.mark.parametrize("mode", ["time", "space"])
-def test_divided_attention_e4m3_copies_are_quantize_fp8_rows_of_the_outputs(K, mode):
-    """H/14 geometry (BASELINE config 5: n + 1 <= 112, T + 1 <= 32, the engine's _attn_q8): the per-tensor e4m3 copies the forward
-    and backward kernels write equal quantize_fp8_rows(result, tscale) of their bf16 results bit for bit, amax exact"""
-    (B, T, n, heads, dh, S, W), qkv, dO, ro, rd = _divided_case("H14", mode, seed=11)
+# the e4m3 copies at the edges of the fused kernels' tile classes: SPACE with the last tile one row short of full (n = 15, 63, 111:
+# MT = 1, 4, 7), TIME in each class (T = 1, 19, 31) with a one-position last chunk whose other three waves own no group (n = 29)
+Q8_EDGES = [pytest.param("space", dict(B=2, T=2, n=n, heads=3, dh=dh), id=f"space-n{n}-dh{dh}") for n in (15, 63, 111) for dh in (64, 80)] + \
+           [pytest.param("time", dict(B=2, T=T, n=29, heads=3, dh=dh), id=f"time-T{T}-dh{dh}") for T in (1, 19, 31) for dh in (64, 80)]
+
+
+@pytest.mark.parametrize("mode,geo", [pytest.param("time", "H14", id="time"), pytest.param("space", "H14", id="space")] + Q8_EDGES)
+def test_divided_attention_e4m3_copies_are_quantize_fp8_rows_of_the_outputs(K, mode, geo):
+    """H/14 geometry (BASELINE config 5: n + 1 <= 112, T + 1 <= 32, the engine's _attn_q8) and the tile-class edges of Q8_EDGES: the
+    per-tensor e4m3 copies the forward and backward kernels write equal quantize_fp8_rows(result, tscale) of their bf16 results bit
+    for bit, amax exact"""
+    (B, T, n, heads, dh, S, W), qkv, dO, ro, rd = _divided_case(geo, mode, seed=11)
     parts = max(T, -(-n // 28))
     out = torch.empty(B * S, W, dtype=torch.bfloat16, device=DEV)
     lse = torch.empty(B * S, heads, device=DEV)
