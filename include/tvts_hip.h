@@ -382,6 +382,25 @@ int tvts_attn_bwd_packed(const void* qkv, int ld, const int* seq_start, int N, i
 int tvts_attn_bwd_packed_last(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, const void* dO,
                               int lddo, const void* O, int ldo, const float* lse2, float* delta, void* dqkv, int lddq,
                               hipStream_t stream);
+/* BIDIRECTIONAL self-attention inside each sequence of a packed batch, with dropout on the probabilities: the DistilBERT tower of v1
+ * (v1/model/model_dist_TVTS.py:34,131-141; transformers MultiHeadSelfAttention: weights = dropout(softmax(scores))) over
+ * M = sum(len_i) rows instead of N * L.  The kernels, ownership, tile classes, descriptor guard and limits of tvts_attn_fwd_packed /
+ * tvts_attn_bwd_packed; every key tile of the sequence is multiplied and only the keys at or behind the sequence end are masked.
+ * lse2 (nullable): the layout of tvts_attn_fwd_packed_lse.  Mask rule: probability (sequence i, head h, query q, key k) takes the index
+ * ((i * heads + h) * L_pad + q) * L_pad + k of tvts_attn_fwd_len_drop on [N, L_pad] padded captions -- same generator, same
+ * (seed_dev, site), so the packed call draws the padded call's mask; the row sum is of the undropped probabilities.  p == 0 runs
+ * kernels without any generator work (seed_dev may then be NULL).  The backward regenerates the mask; one wave writes all rows of
+ * its group in all three thirds of dqkv: no atomics, no prior zeroing, run-to-run the same bits.
+ * _first: ONE query per sequence at its FIRST row ([CLS]) over all its keys, no dropout (the forward-only last block); it writes the
+ * rows seq_start[i] of out and no other.
+ * -22: as the causal entries (NULL, strides, max_len > 80), or L_pad < max_len, p outside [0, 1), p > 0 with seed_dev NULL. */
+int tvts_attn_fwd_packed_bidir(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, void* out, int ldo,
+                               float* lse2, float p, const long* seed_dev, long site, int L_pad, hipStream_t stream);
+int tvts_attn_bwd_packed_bidir(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, const void* dO,
+                               int lddo, const void* O, int ldo, const float* lse2, float* delta, void* dqkv, int lddq, float p,
+                               const long* seed_dev, long site, int L_pad, hipStream_t stream);
+int tvts_attn_fwd_packed_first(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, void* out, int ldo,
+                               hipStream_t stream);
 int tvts_attn80_fwd_len(const void* qkv, int ld, int B, int heads, int S, const int* kv_len, void* out, int ldo, float* lse2,
                         hipStream_t stream);
 int tvts_attn80_bwd_len(const void* qkv, int ld, int B, int heads, int S, const int* kv_len, const void* dO, int lddo,
@@ -624,6 +643,15 @@ int tvts_sort_assemble_bwd(const float* dxs, int ldx, int B, int S, int off, int
  * given.  The backward is the same call on the gradient (same seed / site => same mask). */
 int tvts_dropout_rows(const float* x, int ldx, int rows, int cols, float p, const long* seed_dev, long site,
                       const float* residual, int ldr, float* out, int ldo, void* out_bf16, int ldob, hipStream_t stream);
+/* the same over PACKED captions (x [M, cols], seq_start device int32[N + 1] as for tvts_text_embed_packed): element (r, c) with
+ * r = seq_start[i] + t uses the index (i * L_pad + t) * cols + c of its PADDED position, so the call draws the mask tvts_dropout_rows
+ * draws on the [N * L_pad, cols] buffer of the padded step (L_pad: that step's L, the longest caption).  The embedding dropout, every
+ * FFN.dropout and their backward calls of the v1 step with arch["text_unpadded"].  A row outside every caption or at a position
+ * >= L_pad is left unwritten.  -22: x / seq_start / seed_dev NULL, neither output, N, M, cols or L_pad <= 0, p outside [0, 1), a
+ * leading dimension below cols. */
+int tvts_dropout_rows_packed(const float* x, int ldx, const int* seq_start, int N, int M, int cols, int L_pad, float p,
+                             const long* seed_dev, long site, const float* residual, int ldr, float* out, int ldo, void* out_bf16,
+                             int ldob, hipStream_t stream);
 /* out = relu(x) (dy NULL) or out = dy * (x > 0) (its backward): the nn.ReLU of v1's txt_proj (v1/model/model_dist_TVTS.py:65-68) */
 int tvts_relu(const float* x, const float* dy, float* out, long n, hipStream_t stream);
 int tvts_rows_gather(const float* src, int ld_src, const int* rows, int R, int W, float* dst, int ld_dst, int scatter_add,

@@ -20,6 +20,11 @@
 // log-sum-exp per (packed row, head), lse2[row * heads + h], the layout of the FULL kernels for a [rows = M, heads] problem.
 // attn_bwd_packed_kernel keeps the forward's ownership -- a wave per (sequence, head) group, the same tile classes, the same guard --
 // so one wave writes a group's rows of all three thirds of dqkv: no atomics, no cross-wave reduction, run-to-run the same bits.
+//
+// BIDIRECTIONAL forms (the DistilBERT tower of v1 over packed captions, arch["text_unpadded"], DESIGN.md 8b "v1"): the same kernels
+// under the template parameters BIDIR / DROP, which default to the causal behaviour above (the causal instantiations are unchanged):
+// every key tile of the sequence is multiplied, only the keys at or behind the sequence end are masked, and the probabilities carry
+// the dropout mask of the padded kernels (PackedDrop).  tvts_attn_fwd_packed_bidir, tvts_attn_bwd_packed_bidir, tvts_attn_fwd_packed_first.
 #pragma once
 
 namespace NS_DH {
@@ -29,11 +34,22 @@ __device__ __forceinline__ int packed_tile_class(int m) {
     return t <= 3 ? t : (t <= 5 ? 5 : 0);
 }
 
-template <int MT, bool LSE = false>
+// dropout on the probabilities of the BIDIRECTIONAL forms (the DistilBERT tower of v1 over packed captions): probability (sequence
+// i, head h, query q, key k) has the index ((i * heads + h) * L_pad + q) * L_pad + k of the padded kernels (attn_fwd_shared_kernel's
+// DROP branch with S = L_pad), so a packed call draws the masks of tvts_attn_fwd_len_drop on the same (seed, site)
+struct PackedDrop { unsigned thr; float inv; const unsigned long long* seed; unsigned long long site; int L_pad; };
+
+// BIDIR: every key tile of the sequence is multiplied and only the keys at or behind the sequence end are masked (no causal mask);
+// DROP (BIDIR only): softmax first, dropout second -- the row sum is of the undropped probabilities, and P o m / (1 - p) is rounded to
+// bf16 for the MFMA: the arithmetic of attn_fwd_shared_kernel's DROP branch, operation for operation (a sequence of up to 64 rows is
+// ONE key tile there, so the packed call gives that kernel's bits)
+template <int MT, bool LSE = false, bool BIDIR = false, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_fwd_packed_kernel(const bf16* __restrict__ qkv, int ld, const int* __restrict__ seq_start,
                                                               int N, int M, int heads, float scale2, bf16* __restrict__ out, int ldo,
-                                                              float* __restrict__ lse2) {
+                                                              float* __restrict__ lse2, PackedDrop dr) {
+    static_assert(BIDIR || !DROP, "dropout exists for the bidirectional form only");
     extern __shared__ __attribute__((aligned(16))) char smem[];  // per wave: V tile | output-staging patch
+    const unsigned long long dseed = DROP ? dr.seed[0] + dr.site : 0ull;
     constexpr int RA = MT * 16, TB = RA * VSTRIDE, NU = (MT + 1) / 2;
     constexpr int WB = TB + 1024;
     constexpr int PT = (RA * NCH + 63) / 64;
@@ -99,14 +115,14 @@ __global__ __launch_bounds__(256) void attn_fwd_packed_kernel(const bf16* __rest
 #pragma unroll
             for (int t = 0; t < 2 * NU; ++t) {
                 st[t] = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-                if (t <= qt) {  // causal: key tiles above the diagonal are masked as a whole
+                if (BIDIR ? t < MT : t <= qt) {  // causal: key tiles above the diagonal are masked as a whole
                     f32x4 sc = {0, 0, 0, 0};
 #pragma unroll
                     for (int ks = 0; ks < KS; ++ks) sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kc[t][ks], qc[qt][ks], sc, 0, 0, 0);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int key = t * 16 + gq * 4 + e;
-                        const float v = (key < m && key <= qj) ? sc[e] * scale2 : -INFINITY;
+                        const float v = (key < m && (BIDIR || key <= qj)) ? sc[e] * scale2 : -INFINITY;
                         st[t][e] = v;
                         mx = fmaxf(mx, v);
                     }
@@ -118,7 +134,7 @@ __global__ __launch_bounds__(256) void attn_fwd_packed_kernel(const bf16* __rest
             for (int t = 0; t < 2 * NU; ++t)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float pp = t <= qt ? __builtin_amdgcn_exp2f(st[t][e] - mx) : 0.f;
+                    const float pp = (BIDIR ? t < MT : t <= qt) ? __builtin_amdgcn_exp2f(st[t][e] - mx) : 0.f;
                     st[t][e] = pp;
                     rs += pp;
                 }
@@ -128,10 +144,18 @@ __global__ __launch_bounds__(256) void attn_fwd_packed_kernel(const bf16* __rest
             for (int dt = 0; dt < DT; ++dt) o[dt] = (f32x4){0, 0, 0, 0};
 #pragma unroll
             for (int u = 0; u < NU; ++u) {
-                if (2 * u > qt) continue;
+                if (!BIDIR && 2 * u > qt) continue;
                 bf16x8 pf;
 #pragma unroll
-                for (int j = 0; j < 8; ++j) pf[j] = (bf16)st[2 * u + (j >> 2)][j & 3];
+                for (int j = 0; j < 8; ++j) {
+                    float pv = st[2 * u + (j >> 2)][j & 3];
+                    if (DROP) {
+                        const int key = (2 * u + (j >> 2)) * 16 + gq * 4 + (j & 3);
+                        const unsigned long long idx = ((unsigned long long)gid * dr.L_pad + qj) * dr.L_pad + key;  // gid = i * heads + h
+                        pv = drop_keep(dseed, idx, dr.thr) ? pv * dr.inv : 0.f;
+                    }
+                    pf[j] = (bf16)pv;
+                }
 #pragma unroll
                 for (int dt = 0; dt < DT; ++dt)
                     o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_T_lim<true>(Vs, u, dt, lane, RA), pf, o[dt], 0, 0, 0);
@@ -152,6 +176,9 @@ __global__ __launch_bounds__(256) void attn_fwd_packed_kernel(const bf16* __rest
 // ONE query per sequence, at its LAST row (the EOT token of a packed caption: the only row the last text block's output is read at,
 // v2/CLIP/clip/model.py:343-354), over all keys of the sequence.  A wave per (sequence, head): lanes over the keys for the scores
 // (fp32 dot products, up to two keys per lane), lanes over the 64 head columns for P V; probabilities stay fp32.  Writes that row only.
+// FIRST: the query sits at the sequence's FIRST row instead ([CLS] of a packed DistilBERT caption, v1/model/model_dist_TVTS.py:131-141)
+// and row seq_start[i] is the one written; every key of the sequence is visible to it either way.
+template <bool FIRST = false>
 __global__ __launch_bounds__(256) void attn_fwd_packed_last_kernel(const bf16* __restrict__ qkv, int ld, const int* __restrict__ seq_start,
                                                                    int N, int M, int heads, float scale2, bf16* __restrict__ out, int ldo,
                                                                    float* __restrict__ lse2) {
@@ -164,7 +191,7 @@ __global__ __launch_bounds__(256) void attn_fwd_packed_last_kernel(const bf16* _
     const bf16* base = qkv + (size_t)s0 * ld + h * DH;
     bf16x8 q[NCH];
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) q[c] = ldg8(base + (size_t)(m - 1) * ld + c * 8);
+    for (int c = 0; c < NCH; ++c) q[c] = ldg8(base + (size_t)(FIRST ? 0 : m - 1) * ld + c * 8);
     float sc[2];
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
@@ -190,8 +217,9 @@ __global__ __launch_bounds__(256) void attn_fwd_packed_last_kernel(const bf16* _
         const float p = __shfl(j < 64 ? p0 : p1, j & 63, 64);
         o = __builtin_fmaf(p, (float)vcol[(size_t)j * ld], o);
     }
-    out[(size_t)(s1 - 1) * ldo + h * DH + lane] = (bf16)(o / l);
-    if (lse2 && lane == 0) lse2[(size_t)(s1 - 1) * heads + h] = mx + log2f(l);
+    const size_t qrow = (size_t)(FIRST ? s0 : s1 - 1);
+    out[qrow * ldo + h * DH + lane] = (bf16)(o / l);
+    if (lse2 && lane == 0) lse2[qrow * heads + h] = mx + log2f(l);
 }
 
 // ---- backward of attn_fwd_packed_kernel: delta = rowsum(dO o O), then P = exp2(s * scale2 - lse2) from the stored log-sum-exp,
@@ -203,12 +231,16 @@ __global__ __launch_bounds__(256) void attn_fwd_packed_last_kernel(const bf16* _
 // sequence's rows can reach a product.  The 1 / 2 / 3-tile classes run two waves a block with the next group's rows in flight in
 // registers; the 5-tile class holds 52 KiB of tiles a wave -- one wave a block, three blocks a CU, no prefetch (its registers go to
 // the six score tiles of a query tile).
-template <int MT>
+// BIDIR / DROP as in the forward: phase A and phase B run over ALL tiles of the sequence, and the forward's mask m is regenerated from
+// (seed, site) -- dropped probabilities P o m / (1 - p) under dV, dS = P o (m / (1 - p) o dP - delta) under dQ and dK.
+template <int MT, bool BIDIR = false, bool DROP = false>
 __global__ __launch_bounds__(MT <= 3 ? 128 : 64) void attn_bwd_packed_kernel(
     const bf16* __restrict__ qkv, int ld, const int* __restrict__ seq_start, int N, int M, int heads, float scale2, float scale,
     const bf16* __restrict__ dO, int lddo, const bf16* __restrict__ O, int ldo, const float* __restrict__ lse2,
-    float* __restrict__ delta, bf16* __restrict__ dqkv, int lddq) {
+    float* __restrict__ delta, bf16* __restrict__ dqkv, int lddq, PackedDrop dr) {
+    static_assert(BIDIR || !DROP, "dropout exists for the bidirectional form only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    const unsigned long long dseed = DROP ? dr.seed[0] + dr.site : 0ull;
     constexpr int WV = MT <= 3 ? 2 : 1;
     constexpr int RA = MT * 16, TB = RA * VSTRIDE, NU = (MT + 1) / 2;
     constexpr int WB = 4 * TB + 2 * RA * 4 + 1024;  // one wave's region: Q | K | V | dO tiles, lse and delta of the rows, output patch
@@ -303,7 +335,7 @@ __global__ __launch_bounds__(MT <= 3 ? 128 : 64) void attn_bwd_packed_kernel(
 #pragma unroll
             for (int t = 0; t < 2 * NU; ++t) {
                 dS[t] = (f32x4){0, 0, 0, 0};
-                if (t <= qt) {
+                if (BIDIR ? t < MT : t <= qt) {
                     f32x4 sc = {0, 0, 0, 0}, dp = {0, 0, 0, 0};
 #pragma unroll
                     for (int ks = 0; ks < KS; ++ks) {
@@ -313,9 +345,14 @@ __global__ __launch_bounds__(MT <= 3 ? 128 : 64) void attn_bwd_packed_kernel(
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int key = t * 16 + gq * 4 + e;
-                        const bool ok = key < m && key <= qj && qj < m;
+                        const bool ok = key < m && (BIDIR || key <= qj) && qj < m;
                         const float pp = ok ? __builtin_amdgcn_exp2f(sc[e] * scale2 - lse) : 0.f;
-                        dS[t][e] = ok ? pp * (dp[e] - dlt) * scale : 0.f;
+                        float dpe = dp[e];
+                        if (DROP) {
+                            const unsigned long long idx = ((unsigned long long)gid * dr.L_pad + qj) * dr.L_pad + key;
+                            dpe = drop_keep(dseed, idx, dr.thr) ? dpe * dr.inv : 0.f;
+                        }
+                        dS[t][e] = ok ? pp * (dpe - dlt) * scale : 0.f;
                     }
                 }
             }
@@ -324,7 +361,7 @@ __global__ __launch_bounds__(MT <= 3 ? 128 : 64) void attn_bwd_packed_kernel(
             for (int dt = 0; dt < DT; ++dt) acc[dt] = (f32x4){0, 0, 0, 0};
 #pragma unroll
             for (int u = 0; u < NU; ++u) {
-                if (2 * u > qt) continue;
+                if (!BIDIR && 2 * u > qt) continue;
                 bf16x8 dsf;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) dsf[j] = (bf16)dS[2 * u + (j >> 2)][j & 3];
@@ -350,13 +387,13 @@ __global__ __launch_bounds__(MT <= 3 ? 128 : 64) void attn_bwd_packed_kernel(
             for (int dt = 0; dt < DT; ++dt) { dv[dt] = (f32x4){0, 0, 0, 0}; dk[dt] = (f32x4){0, 0, 0, 0}; }
 #pragma unroll
             for (int u = 0; u < NU; ++u) {
-                if (2 * u + 1 < kt) continue;     // both query tiles of this k-step lie above the diagonal
-                if (u * 32 >= m) continue;        // ... or behind the last row (wave-uniform)
+                if (!BIDIR && 2 * u + 1 < kt) continue;  // both query tiles of this k-step lie above the diagonal
+                if (u * 32 >= m) continue;               // ... or behind the last row (wave-uniform)
                 bf16x8 pf, dsf;
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
                     const int tile = 2 * u + t;
-                    if (tile < MT && tile >= kt) {
+                    if (tile < MT && (BIDIR || tile >= kt)) {
                         f32x4 sc = {0, 0, 0, 0}, dp = {0, 0, 0, 0};
 #pragma unroll
                         for (int ks = 0; ks < KS; ++ks) {
@@ -368,10 +405,15 @@ __global__ __launch_bounds__(MT <= 3 ? 128 : 64) void attn_bwd_packed_kernel(
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const int qi = tile * 16 + gq * 4 + e;
-                            const bool ok = qi < m && kj <= qi;
+                            const bool ok = qi < m && (BIDIR ? kj < m : kj <= qi);
                             const float pp = ok ? __builtin_amdgcn_exp2f(sc[e] * scale2 - l4[e]) : 0.f;
-                            pf[t * 4 + e] = (bf16)pp;
-                            dsf[t * 4 + e] = (bf16)(ok ? pp * (dp[e] - d4[e]) * scale : 0.f);
+                            float dm = 1.f;  // dropout factor m / (1 - p) of (query, key)
+                            if (DROP) {
+                                const unsigned long long idx = ((unsigned long long)gid * dr.L_pad + qi) * dr.L_pad + kj;
+                                dm = drop_keep(dseed, idx, dr.thr) ? dr.inv : 0.f;
+                            }
+                            pf[t * 4 + e] = (bf16)(DROP ? pp * dm : pp);
+                            dsf[t * 4 + e] = (bf16)(ok ? pp * ((DROP ? dp[e] * dm : dp[e]) - d4[e]) * scale : 0.f);
                         }
                     } else {
 #pragma unroll
@@ -472,10 +514,11 @@ static int packed_fwd(const void* qkv, int ld, const int* seq_start, int N, int 
     do {                                                                                                                       \
         if (lse2)                                                                                                              \
             hipLaunchKernelGGL((attn_fwd_packed_kernel<MT, true>), dim3(blocks), dim3(256), 4 * (MT * 16 * VSTRIDE + 1024),    \
-                               stream, (const bf16*)qkv, ld, seq_start, N, M, heads, scale2, (bf16*)out, ldo, lse2);           \
+                               stream, (const bf16*)qkv, ld, seq_start, N, M, heads, scale2, (bf16*)out, ldo, lse2, PackedDrop{});\
         else                                                                                                                   \
             hipLaunchKernelGGL((attn_fwd_packed_kernel<MT, false>), dim3(blocks), dim3(256), 4 * (MT * 16 * VSTRIDE + 1024),   \
-                               stream, (const bf16*)qkv, ld, seq_start, N, M, heads, scale2, (bf16*)out, ldo, (float*)nullptr);\
+                               stream, (const bf16*)qkv, ld, seq_start, N, M, heads, scale2, (bf16*)out, ldo, (float*)nullptr, \
+                               PackedDrop{});                                                                                  \
     } while (0)
     PACKED_LAUNCH(1);
     if (max_len > 16) PACKED_LAUNCH(2);
@@ -502,7 +545,7 @@ extern "C" int tvts_attn_fwd_packed_lse(const void* qkv, int ld, const int* seq_
 static int packed_fwd_last(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, void* out, int ldo, float* lse2,
                            hipStream_t stream) {
     const float scale2 = 1.4426950408889634f / sqrtf((float)DH);
-    hipLaunchKernelGGL(attn_fwd_packed_last_kernel, dim3(ceil_div(N * heads, 4)), dim3(256), 0, stream, (const bf16*)qkv, ld,
+    hipLaunchKernelGGL(attn_fwd_packed_last_kernel<false>, dim3(ceil_div(N * heads, 4)), dim3(256), 0, stream, (const bf16*)qkv, ld,
                        seq_start, N, M, heads, scale2, (bf16*)out, ldo, lse2);
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;
@@ -542,7 +585,7 @@ extern "C" int tvts_attn_bwd_packed(const void* qkv, int ld, const int* seq_star
         const int blocks = ceil_div(groups, WV) < 2048 ? ceil_div(groups, WV) : 2048;                                          \
         hipLaunchKernelGGL((attn_bwd_packed_kernel<MT>), dim3(blocks), dim3(64 * WV), WV * WB, stream, (const bf16*)qkv, ld,   \
                            seq_start, N, M, heads, scale2, scale, (const bf16*)dO, lddo, (const bf16*)O, ldo, lse2, delta,     \
-                           (bf16*)dqkv, lddq);                                                                                 \
+                           (bf16*)dqkv, lddq, PackedDrop{});                                                                   \
     } while (0)
     PACKED_LAUNCH(1);
     if (max_len > 16) PACKED_LAUNCH(2);
@@ -562,6 +605,82 @@ extern "C" int tvts_attn_bwd_packed_last(const void* qkv, int ld, const int* seq
     hipLaunchKernelGGL(attn_bwd_packed_last_kernel, dim3(ceil_div(N * heads, 4)), dim3(256), 0, stream, (const bf16*)qkv, ld,
                        seq_start, N, M, heads, scale2, scale, (const bf16*)dO, lddo, (const bf16*)O, ldo, lse2, delta, (bf16*)dqkv,
                        lddq);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
+// ---- bidirectional forms (the DistilBERT tower of v1 over packed captions): the same ownership, tile classes and guard;
+// p > 0 selects the DROP instantiations, p == 0 the ones without any generator work
+static int packed_drop_args(float p, const long* seed_dev, long site, int L_pad, int max_len, PackedDrop* dr) {
+    if (!(p >= 0.f) || p >= 1.f || L_pad < max_len || (p > 0.f && !seed_dev)) return TVTS_EINVAL;
+    *dr = PackedDrop{(unsigned)((double)p * 4294967296.0), 1.0f / (1.0f - p), (const unsigned long long*)seed_dev, (unsigned long long)site,
+                     L_pad};
+    return TVTS_OK;
+}
+
+extern "C" int tvts_attn_fwd_packed_bidir(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, void* out,
+                                          int ldo, float* lse2, float p, const long* seed_dev, long site, int L_pad, hipStream_t stream) {
+    int rc = packed_args_ok(qkv, ld, seq_start, N, M, heads, max_len, out, ldo);
+    if (rc) return rc;
+    PackedDrop dr;
+    if ((rc = packed_drop_args(p, seed_dev, site, L_pad, max_len, &dr))) return rc;
+    const float scale2 = 1.4426950408889634f / sqrtf((float)DH);
+    const int groups = N * heads;
+    const int blocks = ceil_div(groups, 4) < 1536 ? ceil_div(groups, 4) : 1536;
+#define PACKED_LAUNCH_(MT, LSE, DROP)                                                                                          \
+    hipLaunchKernelGGL((attn_fwd_packed_kernel<MT, LSE, true, DROP>), dim3(blocks), dim3(256), 4 * (MT * 16 * VSTRIDE + 1024), \
+                       stream, (const bf16*)qkv, ld, seq_start, N, M, heads, scale2, (bf16*)out, ldo, lse2, dr)
+#define PACKED_LAUNCH(MT)                                                   \
+    do {                                                                    \
+        if (p > 0.f) { if (lse2) PACKED_LAUNCH_(MT, true, true); else PACKED_LAUNCH_(MT, false, true); }   \
+        else { if (lse2) PACKED_LAUNCH_(MT, true, false); else PACKED_LAUNCH_(MT, false, false); }         \
+    } while (0)
+    PACKED_LAUNCH(1);
+    if (max_len > 16) PACKED_LAUNCH(2);
+    if (max_len > 32) PACKED_LAUNCH(3);
+    if (max_len > 48) PACKED_LAUNCH(5);
+#undef PACKED_LAUNCH
+#undef PACKED_LAUNCH_
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
+extern "C" int tvts_attn_fwd_packed_first(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len, void* out,
+                                          int ldo, hipStream_t stream) {
+    const int rc = packed_args_ok(qkv, ld, seq_start, N, M, heads, max_len, out, ldo);
+    if (rc) return rc;
+    const float scale2 = 1.4426950408889634f / sqrtf((float)DH);
+    hipLaunchKernelGGL(attn_fwd_packed_last_kernel<true>, dim3(ceil_div(N * heads, 4)), dim3(256), 0, stream, (const bf16*)qkv, ld,
+                       seq_start, N, M, heads, scale2, (bf16*)out, ldo, (float*)nullptr);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
+extern "C" int tvts_attn_bwd_packed_bidir(const void* qkv, int ld, const int* seq_start, int N, int M, int heads, int max_len,
+                                          const void* dO, int lddo, const void* O, int ldo, const float* lse2, float* delta, void* dqkv,
+                                          int lddq, float p, const long* seed_dev, long site, int L_pad, hipStream_t stream) {
+    int rc = packed_bwd_args_ok(qkv, ld, seq_start, N, M, heads, max_len, dO, lddo, O, ldo, lse2, delta, dqkv, lddq);
+    if (rc) return rc;
+    PackedDrop dr;
+    if ((rc = packed_drop_args(p, seed_dev, site, L_pad, max_len, &dr))) return rc;
+    const float scale = 1.0f / sqrtf((float)DH), scale2 = 1.4426950408889634f * scale;
+    const int groups = N * heads;
+#define PACKED_LAUNCH_(MT, DROP)                                                                                                \
+    do {                                                                                                                        \
+        constexpr int WV = MT <= 3 ? 2 : 1, WB = 4 * MT * 16 * VSTRIDE + 2 * MT * 16 * 4 + 1024;                                \
+        const int blocks = ceil_div(groups, WV) < 2048 ? ceil_div(groups, WV) : 2048;                                           \
+        hipLaunchKernelGGL((attn_bwd_packed_kernel<MT, true, DROP>), dim3(blocks), dim3(64 * WV), WV * WB, stream,              \
+                           (const bf16*)qkv, ld, seq_start, N, M, heads, scale2, scale, (const bf16*)dO, lddo, (const bf16*)O,  \
+                           ldo, lse2, delta, (bf16*)dqkv, lddq, dr);                                                            \
+    } while (0)
+#define PACKED_LAUNCH(MT)                                                          \
+    do { if (p > 0.f) PACKED_LAUNCH_(MT, true); else PACKED_LAUNCH_(MT, false); } while (0)
+    PACKED_LAUNCH(1);
+    if (max_len > 16) PACKED_LAUNCH(2);
+    if (max_len > 32) PACKED_LAUNCH(3);
+    if (max_len > 48) PACKED_LAUNCH(5);
+#undef PACKED_LAUNCH
+#undef PACKED_LAUNCH_
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;
 }

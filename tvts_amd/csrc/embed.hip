@@ -1148,6 +1148,50 @@ extern "C" int tvts_dropout_rows(const float* x, int ldx, int rows, int cols, fl
     return TVTS_OK;
 }
 
+// the same over PACKED captions (x [M, cols], seq_start as for tvts_text_embed_packed): element (row r, column c) uses the counter of
+// its PADDED position, ((i * L_pad + t) * cols + c) with r = seq_start[i] + t -- a packed call draws the mask tvts_dropout_rows draws
+// on the [N * L_pad, cols] buffer of the padded step.  A block walks rows; the row's caption is one binary search (block-uniform).
+// A row outside every caption or at a position t >= L_pad is left unwritten.
+__global__ __launch_bounds__(256) void dropout_rows_packed_kernel(const float* __restrict__ x, int ldx, const int* __restrict__ seq_start,
+                                                                  int N, int M, int cols, int L_pad, unsigned thr, float inv,
+                                                                  const unsigned long long* __restrict__ seed_dev, unsigned long long site,
+                                                                  const float* __restrict__ residual, int ldr, float* __restrict__ out,
+                                                                  int ldo, bf16* __restrict__ outb, int ldob) {
+    const unsigned long long seed = seed_dev[0] + site;
+    for (int r = blockIdx.x; r < M; r += gridDim.x) {
+        int lo = 0, hi = N;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (seq_start[mid] <= r) lo = mid; else hi = mid;
+        }
+        const int t = r - seq_start[lo];
+        if (t < 0 || t >= L_pad || r >= seq_start[lo + 1]) continue;
+        const unsigned long long i0 = ((unsigned long long)lo * L_pad + t) * cols;
+        for (int c = threadIdx.x; c < cols; c += 256) {
+            unsigned long long z = seed + (i0 + c) * 0x9E3779B97F4A7C15ull;
+            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+            z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+            z ^= z >> 31;
+            float v = ((unsigned)(z >> 32) >= thr) ? x[(size_t)r * ldx + c] * inv : 0.f;
+            if (residual) v += residual[(size_t)r * ldr + c];
+            if (out) out[(size_t)r * ldo + c] = v;
+            if (outb) outb[(size_t)r * ldob + c] = (bf16)v;
+        }
+    }
+}
+extern "C" int tvts_dropout_rows_packed(const float* x, int ldx, const int* seq_start, int N, int M, int cols, int L_pad, float p,
+                                        const long* seed_dev, long site, const float* residual, int ldr, float* out, int ldo,
+                                        void* out_bf16, int ldob, hipStream_t stream) {
+    if (!x || !seq_start || N <= 0 || M <= 0 || cols <= 0 || L_pad <= 0 || !(p >= 0.f) || p >= 1.f || !seed_dev || (!out && !out_bf16))
+        return TVTS_EINVAL;
+    if (ldx < cols || (residual && ldr < cols) || (out && ldo < cols) || (out_bf16 && ldob < cols)) return TVTS_EINVAL;
+    hipLaunchKernelGGL(dropout_rows_packed_kernel, dim3(M < 4096 ? M : 4096), dim3(256), 0, stream, x, ldx, seq_start, N, M, cols, L_pad,
+                       (unsigned)((double)p * 4294967296.0), 1.0f / (1.0f - p), (const unsigned long long*)seed_dev,
+                       (unsigned long long)site, residual, ldr, out, ldo, (bf16*)out_bf16, ldob);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- ReLU (v1 txt_proj)
 // y = max(x, 0) / dx = dy * (x > 0): the nn.ReLU in front of the v1 text projection (v1/model/model_dist_TVTS.py:65-68)
 __global__ void relu_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ out, long n) {

@@ -201,6 +201,10 @@ class Engine:
                                  "are no dead rows there")
             if self.dh_text != 64:
                 raise NotImplementedError("text_packed: the packed attention kernels are built for head dim 64")
+        # the v1 counterpart (opt-in, DESIGN.md 8b "v1"): the DistilBERT tower over M = sum(len_i) rows, bidirectional packed attention
+        self.text_unpadded = bool(a.get("text_unpadded"))
+        if self.text_unpadded and a.get("family") != "v1":
+            raise ValueError("text_unpadded is the v1 (DistilBERT) option; the CLIP text tower of v2 packs with text_packed")
         # Precision of the space-time blocks' residual stream (round 3).  Every consumer but the residual adds themselves reads
         # these tensors as bf16 anyway (LayerNorm outputs and GEMM operands are bf16): fp32 buys exact accumulation along the
         # 12 / 32 blocks, at 2.1 GB per block of HBM traffic in the forward + saved activations and 1.4 GB in the backward chain

@@ -85,7 +85,17 @@ class EngineV1(Engine):
     # One wiring for both passes, like the v2 towers (Engine._w): with a `tag` the buffers are the step's named tensors, which the
     # backward reads; with tag None they are encoder workspaces, no log-sum-exp and no pre-activation is written, and there is NO
     # dropout whatever _drop_active says.
-    def _pln_fwd(self, pre, x, xb, x_out, xb_out, tag, M, N, L, kv_len, layer=0, rows=None):
+    # arch["text_unpadded"] (DESIGN.md 8b "v1"): the same wiring over M = sum(len_i) rows, captions in batch order.  `pk` is the batch's
+    # device descriptor (seq_start, max_len; hip.pack_captions(lens=...)); with it the sequence-aware calls -- embedding, attention,
+    # dropout, embedding backward, the [CLS] row starts -- are the packed entry points, L is the PADDED step's L (the longest caption:
+    # the counter rule of the dropout masks) and every GEMM, LayerNorm and cast is the same call with M rows.
+    def _txt_drop(self, x, pk, N, L, **kw):
+        if pk is None:
+            K.dropout_rows(x, **kw)
+        else:
+            K.dropout_rows_packed(x, pk["seq_start"], N=N, L_pad=L, **kw)
+
+    def _pln_fwd(self, pre, x, xb, x_out, xb_out, tag, M, N, L, kv_len, layer=0, rows=None, pk=None):
         """one POST-LN DistilBERT block over N captions of L rows: x (fp32) / xb (bf16 copy) -> x_out / xb_out.
         rows (forward-only): the [CLS] row of every caption, for a last block whose output is read there only -- keys / values
         from every row, one query per caption (tvts_attn_fwd_first), everything behind the attention on N rows: x_out is [N, Wt]."""
@@ -96,7 +106,12 @@ class EngineV1(Engine):
         qkv = w(tag, ".qkv", "qkv", (M, 3 * Wt))
         for i, lin in enumerate(("q_lin", "k_lin", "v_lin")):  # three projections into the packed [M, 3 Wt] buffer
             w_, b_ = P.w(pre + f"attention.{lin}.weight"), P.p(pre + f"attention.{lin}.bias")
-            if rows is not None and i == 0:  # the one query of every caption: its [CLS] row (row stride L of the operand and of qkv)
+            if rows is not None and i == 0 and pk is not None:  # ... of packed captions: no row stride, the N rows are moved
+                xq, q_r = self._ib("xq_r", (N, Wt)), self._ib("q_r", (N, Wt))
+                K.rows_move("gather", rows, full_bf16=xb, packed_bf16=xq)
+                K.gemm_nt(xq, w_, q_r, M=N, bias=b_)
+                K.rows_move("scatter", rows, full_bf16=qkv[:, :Wt], packed_bf16=q_r)
+            elif rows is not None and i == 0:  # the one query of every caption: its [CLS] row (row stride L of the operand and of qkv)
                 K.gemm_nt(xb.view(N, L * Wt)[:, :Wt], w_, qkv.view(N, L * 3 * Wt)[:, :Wt], M=N, bias=b_)
             else:
                 K.gemm_nt(xb, w_, qkv[:, i * Wt:(i + 1) * Wt], M=M, bias=b_)
@@ -104,11 +119,17 @@ class EngineV1(Engine):
         res = x
         if rows is not None:
             assert tag is None, "the backward of the DistilBERT block is dense"
-            K.attn_fwd_first(qkv, kv_len, att, None, B=N, heads=h, S=L, head_dim=self.dh_text)
+            if pk is not None:
+                K.attn_fwd_packed_first(qkv, pk["seq_start"], att, N=N, heads=h, max_len=pk["max_len"])
+            else:
+                K.attn_fwd_first(qkv, kv_len, att, None, B=N, heads=h, S=L, head_dim=self.dh_text)
             att_r, res = self._ib("att_r", (N, Wt)), self._ib("x_r", (N, Wt), f32)
             K.rows_move("gather", rows, full_bf16=att, packed_bf16=att_r)
             K.rows_move("gather", rows, full_f32=x, packed_f32=res)
             att = att_r
+        elif pk is not None:  # (p = 0: the kernels without generator work)
+            K.attn_fwd_packed_bidir(qkv, pk["seq_start"], att, lse, N=N, heads=h, max_len=pk["max_len"], L_pad=L, p=dp,
+                                    seed=self.drop_seed, site=1 + 2 * layer)
         elif dp > 0.0:  # weights = dropout(softmax(scores)) inside the kernel
             K.attn_fwd_len_drop(qkv, kv_len, att, lse, B=N, heads=h, S=L, p=dp, seed=self.drop_seed, site=1 + 2 * layer, head_dim=self.dh_text)
         else:
@@ -124,14 +145,14 @@ class EngineV1(Engine):
         if dp > 0.0:  # pre2 = dropout(lin2(.)) + x1
             y2 = self._f("txt.s.y2", (R, Wt))
             self._lin(hact, pre + "ffn.lin2.weight", pre + "ffn.lin2.bias", y2, R)
-            K.dropout_rows(y2, p=dp, seed=self.drop_seed, site=2 + 2 * layer, residual=x1, out=pre2)
+            self._txt_drop(y2, pk, N, L, p=dp, seed=self.drop_seed, site=2 + 2 * layer, residual=x1, out=pre2)
         else:
             self._lin(hact, pre + "ffn.lin2.weight", pre + "ffn.lin2.bias", pre2, R, residual=x1)
         self._ln(pre2, pre + "output_layer_norm", 1e-12, x_out, tag and tag + ".ln_out")
         if xb_out is not None:
             K.cast_f32_bf16(x_out, xb_out)
 
-    def _pln_bwd(self, pre, xb_in, dx_out, dx_in, tag, M, N, L, kv_len, layer=0):
+    def _pln_bwd(self, pre, xb_in, dx_out, dx_in, tag, M, N, L, kv_len, layer=0, pk=None):
         """dx_out: fp32 grad wrt the block output; writes the fp32 grad wrt the block input into dx_in."""
         a, P, B_ = self.arch, self.P, self.buf
         dp = self._drop_active
@@ -143,7 +164,7 @@ class EngineV1(Engine):
         dy2b = dpre2b
         if dp > 0.0:  # gradient of lin2's output: the forward's mask again (the residual path keeps the unmasked dpre2)
             dy2b = self._b("txt.s.dy2b", (M, Wt))
-            K.dropout_rows(dpre2, p=dp, seed=self.drop_seed, site=2 + 2 * layer, out_bf16=dy2b)
+            self._txt_drop(dpre2, pk, N, L, p=dp, seed=self.drop_seed, site=2 + 2 * layer, out_bf16=dy2b)
         self._lin_bwd(dy2b, B_[tag + ".a"], pre + "ffn.lin2.weight", pre + "ffn.lin2.bias", dh, M, gate_h=B_[tag + ".h"], gate_act="gelu")
         dx1 = self._f("txt.s.dx1", (M, Wt))  # = dpre2 (residual) + lin1 dgrad, fused as the GEMM's fp32 residual epilogue
         self._lin_bwd(dh, B_[tag + ".x1b"], pre + "ffn.lin1.weight", pre + "ffn.lin1.bias", dx1, M, residual=dpre2)
@@ -153,7 +174,10 @@ class EngineV1(Engine):
         datt = self._b("txt.s.datt", (M, Wt))
         self._lin_bwd(dpre1b, B_[tag + ".att"], pre + "attention.out_lin.weight", pre + "attention.out_lin.bias", datt, M)
         dqkv, delta = self._b("txt.s.dqkv", (M, 3 * Wt)), self._f("txt.s.delta", (M, h))
-        if dp > 0.0:
+        if pk is not None:  # (every row of every caption is written in all three thirds: no zeroing)
+            K.attn_bwd_packed_bidir(B_[tag + ".qkv"], pk["seq_start"], datt, B_[tag + ".att"], B_[tag + ".lse"], delta, dqkv, N=N, heads=h,
+                                    max_len=pk["max_len"], L_pad=L, p=dp, seed=self.drop_seed, site=1 + 2 * layer)
+        elif dp > 0.0:
             K.attn_bwd_len_drop(B_[tag + ".qkv"], kv_len, datt, B_[tag + ".att"], B_[tag + ".lse"], delta, dqkv, B=N, heads=h, S=L,
                                 p=dp, seed=self.drop_seed, site=1 + 2 * layer, head_dim=self.dh_text)
         else:
@@ -167,32 +191,38 @@ class EngineV1(Engine):
                           residual=acc)
             acc = dst
 
-    def _text_tower_v1(self, ids, kv_len, cls_rows, N, L, tag):
+    def _text_tower_v1(self, ids, kv_len, cls_rows, N, L, tag, pk=None):
         """DistilBERT over N right-padded captions of L rows -> (before [N, Wt] fp32 = the last hidden state at [CLS],
         [N, E] = txt_proj(relu(before))).  tag "txt": the training step -- every block dense, every stream kept; None: forward-only
-        -- one stream x / xb updated in place, the last block for the [CLS] rows."""
+        -- one stream x / xb updated in place, the last block for the [CLS] rows.
+        pk: the descriptor of PACKED captions -- ids is then int32 [M], cls_rows = seq_start[:-1], no buffer carries a padding row."""
         a, P, w, f32 = self.arch, self.P, self._w, torch.float32
-        Wt, M, E, nl = a["text_width"], N * L, a["embed"], a["text_layers"]
+        Wt, M, E, nl = a["text_width"], (N * L if pk is None else pk["M"]), a["embed"], a["text_layers"]
         dp = self._drop_active if tag else 0.0
         emb = w(tag, ".emb", "s", (M, Wt), f32)
-        K.text_embed(ids, P.p("text_model.embeddings.word_embeddings.weight"),
-                     P.p("text_model.embeddings.position_embeddings.weight"), emb, N=N, L=L)
+        if pk is not None:
+            K.text_embed_packed(ids, pk["seq_start"], P.p("text_model.embeddings.word_embeddings.weight"),
+                                P.p("text_model.embeddings.position_embeddings.weight"), emb, N=N)
+        else:
+            K.text_embed(ids, P.p("text_model.embeddings.word_embeddings.weight"),
+                         P.p("text_model.embeddings.position_embeddings.weight"), emb, N=N, L=L)
         x, xb = w(tag, ".x0", "x", (M, Wt), f32), w(tag, ".x0b", "ln", (M, Wt))
         if dp > 0.0:  # Embeddings: dropout(LayerNorm(word + position))
             xln = self._f(tag + ".xln", (M, Wt))
             self._ln(emb, "text_model.embeddings.LayerNorm", 1e-12, xln, tag + ".ln_emb")
-            K.dropout_rows(xln, p=dp, seed=self.drop_seed, site=0, out=x, out_bf16=xb)
+            self._txt_drop(xln, pk, N, L, p=dp, seed=self.drop_seed, site=0, out=x, out_bf16=xb)
         else:
             self._ln(emb, "text_model.embeddings.LayerNorm", 1e-12, x, tag and tag + ".ln_emb")
             K.cast_f32_bf16(x, xb)
         packed = tag is None  # forward-only the last block runs for the rows the model reads; the step's backward is dense
         for l in range(nl - packed):
             xo, xbo = w(tag, f".x{l + 1}", "x", (M, Wt), f32), w(tag, f".x{l + 1}b", "ln", (M, Wt))
-            self._pln_fwd(f"text_model.transformer.layer.{l}.", x, xb, xo, xbo, tag and f"{tag}{l}", M, N, L, kv_len, layer=l)
+            self._pln_fwd(f"text_model.transformer.layer.{l}.", x, xb, xo, xbo, tag and f"{tag}{l}", M, N, L, kv_len, layer=l, pk=pk)
             x, xb = xo, xbo
         before = w(tag, ".before", "tbefore", (N, Wt), f32)
         if packed:
-            self._pln_fwd(f"text_model.transformer.layer.{nl - 1}.", x, xb, before, None, None, M, N, L, kv_len, layer=nl - 1, rows=cls_rows)
+            self._pln_fwd(f"text_model.transformer.layer.{nl - 1}.", x, xb, before, None, None, M, N, L, kv_len, layer=nl - 1, rows=cls_rows,
+                          pk=pk)
         else:
             K.rows_gather(x, cls_rows, before)
         act = w(tag, ".relu", "trelu", (N, Wt), f32)
@@ -201,14 +231,14 @@ class EngineV1(Engine):
         self._head_lin(act, "txt_proj.1.weight", "txt_proj.1.bias", t, N)
         return before, t
 
-    def text_forward_v1(self, ids, kv_len, cls_rows, N, L):
+    def text_forward_v1(self, ids, kv_len, cls_rows, N, L, pk=None):
         """the training step's text tower (new dropout masks per call in training mode) -> (text_before, text_emb) as _text_tower_v1"""
         self._advance_drop_seed()
-        return self._text_tower_v1(ids, kv_len, cls_rows, N, L, "txt")
+        return self._text_tower_v1(ids, kv_len, cls_rows, N, L, "txt", pk=pk)
 
-    def text_backward_v1(self, dt, ids, kv_len, cls_rows, N, L, tok_sort=None):
+    def text_backward_v1(self, dt, ids, kv_len, cls_rows, N, L, tok_sort=None, pk=None):
         a, P, B_ = self.arch, self.P, self.buf
-        Wt, M = a["text_width"], N * L
+        Wt, M = a["text_width"], (N * L if pk is None else pk["M"])
         dact = self._f("txt.dact", (N, Wt))
         self._head_lin_bwd(dt, B_["txt.relu"], "txt_proj.1.weight", "txt_proj.1.bias", dact, N)
         dbefore = self._f("txt.dbefore", (N, Wt))
@@ -217,16 +247,20 @@ class EngineV1(Engine):
         K.rows_gather(dbefore, cls_rows, dx, scatter_add=True)  # only the [CLS] rows of the last hidden state are consumed
         for l in reversed(range(a["text_layers"])):
             dxi = self._f("txt.dx" + self._ab(a["text_layers"], l), (M, Wt))
-            self._pln_bwd(f"text_model.transformer.layer.{l}.", B_[f"txt.x{l}b"], dx, dxi, f"txt{l}", M, N, L, kv_len, layer=l)
+            self._pln_bwd(f"text_model.transformer.layer.{l}.", B_[f"txt.x{l}b"], dx, dxi, f"txt{l}", M, N, L, kv_len, layer=l, pk=pk)
             dx = dxi
         if self._drop_active > 0.0:  # through the embedding dropout
             ddrop = self._f("txt.s.ddrop", (M, Wt))
-            K.dropout_rows(dx, p=self._drop_active, seed=self.drop_seed, site=0, out=ddrop)
+            self._txt_drop(dx, pk, N, L, p=self._drop_active, seed=self.drop_seed, site=0, out=ddrop)
             dx = ddrop
         demb = self._f("txt.demb", (M, Wt))
         self._ln_bwd(dx, B_["txt.emb"], "text_model.embeddings.LayerNorm", "txt.ln_emb", demb)
-        K.text_embed_bwd(demb, ids, P.g("text_model.embeddings.word_embeddings.weight"),
-                         P.g("text_model.embeddings.position_embeddings.weight"), N=N, L=L, tok_sort=tok_sort)
+        if pk is not None:
+            K.text_embed_bwd_packed(demb, ids, pk["seq_start"], P.g("text_model.embeddings.word_embeddings.weight"),
+                                    P.g("text_model.embeddings.position_embeddings.weight"), N=N, tok_sort=tok_sort, pos_sort=pk["pos_sort"])
+        else:
+            K.text_embed_bwd(demb, ids, P.g("text_model.embeddings.word_embeddings.weight"),
+                             P.g("text_model.embeddings.position_embeddings.weight"), N=N, L=L, tok_sort=tok_sort)
 
     # ------------------------------------------------------------------ tubelet ViT with joint attention
     def _vit_embed_v1(self, video, keep, B, tubes, tag, crop=None, channel_major=False, mix=None, aug=None, view=None):
@@ -407,12 +441,17 @@ class EngineV1(Engine):
         from .model.model_dist_TVTS import right_padded, tokenizer_inputs  # (that module imports this one)
         text = {k: data["text"][k].detach().to("cpu", torch.int64) for k in ("input_ids", "attention_mask")}
         assert right_padded(text["attention_mask"]), "attention_mask must be a right-padded prefix mask"
-        ids, kv_len, N, L = tokenizer_inputs(text, self.dev)
+        if self.text_unpadded:  # (the packed descriptors are made on the host and travel in one copy: _prepare_unpadded)
+            N, L = text["input_ids"].shape[0], int(text["attention_mask"].sum(-1).max())
+        else:
+            ids, kv_len, N, L = tokenizer_inputs(text, self.dev)
         NT = N // B
         keep = data["keep_ind"][:, :tubes].to(torch.int32).contiguous().to(self.dev)
         n = keep.shape[2]
         S = 1 + tubes * n
         So = S + NT
+        if self.text_unpadded:
+            return self._prepare_unpadded(text, dict(video=video, keep=keep, B=B, T=T, tubes=tubes, N=N, NT=NT, L=L, n=n, S=S), So)
         return dict(video=video, ids=ids, kv_len=kv_len,
                     tok_sort=tuple(t.to(self.dev) for t in K.token_sort(text["input_ids"][:, :L])),  # ordered word-embedding gradient sums
                     txt_cls_rows=(torch.arange(N) * L).to(torch.int32).to(self.dev), keep=keep, B=B, T=T, tubes=tubes, N=N, NT=NT, L=L,
@@ -420,12 +459,37 @@ class EngineV1(Engine):
                     sort_rows=(torch.arange(B)[:, None] * So + S + torch.arange(NT)[None, :]).reshape(-1).to(torch.int32).to(self.dev),
                     sort_rows64=(torch.arange(B)[:, None] * So + S + torch.arange(NT)[None, :]).reshape(-1).to(self.dev))
 
+    MAX_UNPADDED = 80  # the longest caption the packed attention kernels take (tile classes up to 5 x 16 rows)
+
+    def _prepare_unpadded(self, text, pb, So):
+        """the text half of prepare_batch under arch["text_unpadded"]: the captions packed by their lengths (hip.pack_captions), every
+        descriptor and row table of the batch in ONE staging copy (_stage_small).  pb["L"] stays the longest caption: the L of the
+        padded step, which the dropout masks are drawn for."""
+        lens = text["attention_mask"].sum(-1)
+        if int(lens.max()) > self.MAX_UNPADDED:
+            raise ValueError(f"text_unpadded: a caption of {int(lens.max())} tokens, the packed attention kernels take at most "
+                             f"{self.MAX_UNPADDED} (the trainer's tokenizer call truncates at 50)")
+        if int(lens.min()) < 1:
+            raise ValueError("text_unpadded: a caption without tokens")
+        B, NT, S = pb["B"], pb["NT"], pb["S"]
+        pk = K.pack_captions(text["input_ids"], self.arch["max_pos"], lens=lens)
+        small = {k: pk[k] for k in ("ids", "seq_start", "cls_rows", "tok_order", "tok_seg", "pos_order", "pos_seg")}
+        small["vid_rows"] = (torch.arange(B) * S).to(torch.int32)
+        small["sort_rows"] = (torch.arange(B)[:, None] * So + S + torch.arange(NT)[None, :]).reshape(-1).to(torch.int32)
+        d = self._stage_small(small)
+        M = int(pk["ids"].numel())
+        pb.update(ids=d["ids"], kv_len=None, tok_sort=(d["tok_order"], d["tok_seg"]), txt_cls_rows=d["cls_rows"], vid_rows=d["vid_rows"],
+                  sort_rows=d["sort_rows"], sort_rows64=d["sort_rows"].to(torch.int64), M=M, seq_start=d["seq_start"],
+                  max_len=pk["max_len"], txt_pk=dict(seq_start=d["seq_start"], max_len=pk["max_len"], M=M,
+                                                     pos_sort=(d["pos_order"], d["pos_seg"])))
+        return pb
+
     def forward(self, pb: dict):
         a = self.arch
         self.ctx = pb
         self._tick += 1  # (workspace: a buffer whose shape changes from here on belongs to a new step, see _b)
         B, N, NT, L, S, E = pb["B"], pb["N"], pb["NT"], pb["L"], pb["S"], a["embed"]
-        before, t = self.text_forward_v1(pb["ids"], pb["kv_len"], pb["txt_cls_rows"], N, L)
+        before, t = self.text_forward_v1(pb["ids"], pb["kv_len"], pb["txt_cls_rows"], N, L, pk=pb.get("txt_pk"))
         text_emb = self._f("mdl.text_emb", (B, E))
         tmean_scratch = self._f("mdl.text_before_e", (B, NT, E))
         K.text_mean(t, text_emb, tmean_scratch, NT=NT, B=B)          # mean over the NT captions (model_dist_TVTS.py:104-107)
@@ -443,7 +507,7 @@ class EngineV1(Engine):
         if d_text is not None:
             dt = self._f("mdl.dt", (N, E))
             K.text_mean_bwd(d_text, dt, NT=NT, B=B)
-            self.text_backward_v1(dt, pb["ids"], pb["kv_len"], pb["txt_cls_rows"], N, L, tok_sort=pb.get("tok_sort"))
+            self.text_backward_v1(dt, pb["ids"], pb["kv_len"], pb["txt_cls_rows"], N, L, tok_sort=pb.get("tok_sort"), pk=pb.get("txt_pk"))
             self._ready("text_model.")
             self._ready("txt_proj.")
         # vid_proj on the CLS token: dW += d_video^T cls, db += colsum, d_cls = d_video W
@@ -470,7 +534,8 @@ class EngineV1(Engine):
     # Seed rule: the text encoder NEVER applies dropout and NEVER advances drop_seed, whatever `training` says -- it is an
     # inference call, and an encoder call between two training steps must not shift the step's mask sequence.
     # (_advance_drop_seed is text_forward_v1's alone, and with tag None _pln_fwd / _text_tower_v1 do not look at _drop_active.)
-    # Base-class refusal (_inf_check) stays for encode_text_packed: there is no packed DistilBERT pass.
+    # Base-class refusal (_inf_check) stays for encode_text_packed (the causal CLIP pass); the packed DistilBERT pass is encode_text
+    # with a descriptor `pk` (TVTS.encode_text(text, packed=True)).
     def encode_video(self, video, keep, B, tubes, crop=None, channel_major=False, project=True, view=None):
         """-> (feat [B, W] fp32 = the normed CLS token, emb [B, E] = vid_proj(feat)).  Both are encoder workspaces: the next
         encoder call overwrites them.  project=False returns emb = None (a store without vid_proj: the downstream class).
@@ -497,7 +562,10 @@ class EngineV1(Engine):
         self._head_lin(feat, "vid_proj.0.weight", "vid_proj.0.bias", emb, B)
         return feat, emb
 
-    def encode_text(self, ids, kv_len, N, L):
+    def encode_text(self, ids, kv_len, N, L, pk=None):
         """-> (before [N, Wt] fp32 = DistilBERT's last hidden state at [CLS], emb [N, E] = txt_proj(relu(before))); both encoder
-        workspaces.  ids int32 [N, L], kv_len int32 [N] (right-padded captions) on the device.  No dropout, drop_seed untouched."""
+        workspaces.  ids int32 [N, L], kv_len int32 [N] (right-padded captions) on the device.  No dropout, drop_seed untouched.
+        pk: packed captions instead (ids int32 [M]; dict of seq_start, cls_rows, max_len, M on the device, hip.pack_captions(lens=...))."""
+        if pk is not None:
+            return self._text_tower_v1(ids, None, pk["cls_rows"], N, L, None, pk=pk)
         return self._text_tower_v1(ids, kv_len, self._row_starts("cls_rows", N, L), N, L, None)

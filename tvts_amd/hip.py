@@ -765,6 +765,55 @@ def attn_bwd_packed(qkv, seq_start, dO, O, lse2, delta, dqkv, *, N, heads, max_l
                             _p(dqkv), _ld(dqkv), _stream()), name)
 
 
+def attn_fwd_packed_bidir(qkv, seq_start, out, lse2=None, *, N, heads, max_len, L_pad, p=0.0, seed=None, site=0):
+    """bidirectional attention inside each sequence of a packed batch (the DistilBERT tower of v1), dropout p on the probabilities
+    with the mask tvts_attn_fwd_len_drop draws on [N, L_pad] padded captions from the same (seed, site).  lse2 fp32 [M, heads] or None."""
+    lib = _lib.load()
+    assert seq_start.dtype == torch.int32 and seq_start.numel() == N + 1
+    M = qkv.shape[0]
+    assert out.shape[0] == M and (seed is None or (seed.dtype == torch.int64 and seed.is_cuda))
+    assert lse2 is None or (lse2.dtype == torch.float32 and lse2.is_contiguous() and lse2.numel() >= M * heads)
+    _chk(lib.tvts_attn_fwd_packed_bidir(_p(qkv), _ld(qkv), _p(seq_start), N, M, heads, max_len, _p(out), _ld(out), _p(lse2), float(p),
+                                        _p(seed), _site(site), L_pad, _stream()), "tvts_attn_fwd_packed_bidir")
+
+
+def attn_bwd_packed_bidir(qkv, seq_start, dO, O, lse2, delta, dqkv, *, N, heads, max_len, L_pad, p=0.0, seed=None, site=0):
+    """backward of attn_fwd_packed_bidir (the mask regenerated from seed / site) into dqkv bf16 [M, 3W]: every row of a valid sequence
+    is written in all three thirds (no zeroing here), delta fp32 [M, heads] on the way; two runs give the same bits."""
+    lib = _lib.load()
+    assert seq_start.dtype == torch.int32 and seq_start.numel() == N + 1
+    M = qkv.shape[0]
+    assert dO.shape[0] == M and O.shape[0] == M and dqkv.shape[0] == M
+    assert lse2 is None or (lse2.dtype == torch.float32 and lse2.numel() >= M * heads)
+    assert delta is None or (delta.dtype == torch.float32 and delta.numel() >= M * heads)
+    assert seed is None or (seed.dtype == torch.int64 and seed.is_cuda)
+    _chk(lib.tvts_attn_bwd_packed_bidir(_p(qkv), _ld(qkv), _p(seq_start), N, M, heads, max_len, _p(dO), _ld(dO), _p(O), _ld(O), _p(lse2),
+                                        _p(delta), _p(dqkv), _ld(dqkv), float(p), _p(seed), _site(site), L_pad, _stream()),
+         "tvts_attn_bwd_packed_bidir")
+
+
+def attn_fwd_packed_first(qkv, seq_start, out, *, N, heads, max_len):
+    """one query per packed sequence at its FIRST row ([CLS]) over all its keys; only the rows seq_start[i] of out are written"""
+    lib = _lib.load()
+    assert seq_start.dtype == torch.int32 and seq_start.numel() == N + 1
+    M = qkv.shape[0]
+    assert out.shape[0] == M
+    _chk(lib.tvts_attn_fwd_packed_first(_p(qkv), _ld(qkv), _p(seq_start), N, M, heads, max_len, _p(out), _ld(out), _stream()),
+         "tvts_attn_fwd_packed_first")
+
+
+def dropout_rows_packed(x, seq_start, *, N, L_pad, p, seed, site, residual=None, out=None, out_bf16=None):
+    """dropout_rows over packed captions x fp32 [M, cols]: the mask dropout_rows draws on the [N * L_pad, cols] padded buffer, read
+    at every row's padded position; the backward is the same call on the gradient."""
+    lib = _lib.load()
+    assert x.dtype == torch.float32 and x.dim() == 2 and seed.dtype == torch.int64
+    assert seq_start.dtype == torch.int32 and seq_start.numel() == N + 1
+    _chk(lib.tvts_dropout_rows_packed(_p(x), _ld(x), _p(seq_start), N, x.shape[0], x.shape[1], L_pad, float(p), _p(seed), _site(site),
+                                      _p(residual), _ld(residual) if residual is not None else 0, _p(out),
+                                      _ld(out) if out is not None else 0, _p(out_bf16), _ld(out_bf16) if out_bf16 is not None else 0,
+                                      _stream()), "tvts_dropout_rows_packed")
+
+
 def attn_bwd_rowq(qkv, qpos, dO, O, lse2, delta, dqkv, *, B, heads, S, head_dim=64):
     """backward of attn_fwd_rowq into dqkv (zeroed here first: only the query row's dQ and the dK / dV of the keys it sees exist).
     dqkv: bf16 [B * S, 3W], contiguous or a row-major view with a wider leading dimension (a multiple of 8, 16-byte base)."""
@@ -1227,19 +1276,26 @@ def text_embed_bwd(dx, ids, demb, dpos, *, N, L, tok_sort=None):
                                  _p(order), _p(seg), _stream()), "tvts_text_embed_bwd")
 
 
-def pack_captions(ids_cpu, context=None):
+def pack_captions(ids_cpu, context=None, lens=None):
     """The host half of the packed text tower: [N, L] token ids (a host tensor; the EOT token is each row's largest id,
     CLIP/clip/model.py:343-354) -> the descriptors of the packed batch, all host tensors, no device access:
     ids int32 [M] (caption i's tokens up to and including its EOT, captions in the given order), seq_start int32 [N + 1],
-    eot_rows int32 [N] (= seq_start[1:] - 1), max_len (int), tok_order / tok_seg (token_sort of the packed ids) and
-    pos_order int32 [M] / pos_seg int32 [context + 1]: the rows sorted stably by their position inside their caption and the starts
-    of the runs of equal position (context: the rows of the positional table, default L)."""
+    eot_rows int32 [N] (= seq_start[1:] - 1), cls_rows int32 [N] (= seq_start[:-1]), max_len (int), tok_order / tok_seg (token_sort of
+    the packed ids) and pos_order int32 [M] / pos_seg int32 [context + 1]: the rows sorted stably by their position inside their
+    caption and the starts of the runs of equal position (context: the rows of the positional table, default L).
+    lens (host integers [N], optional): pack caption i's first lens[i] tokens instead of the CLIP rule -- the right-padded captions of
+    a tokenizer with their attention-mask sums (the kv_len of tokenizer_inputs: the DistilBERT tower of v1)."""
     import numpy as np
     assert ids_cpu.dim() == 2 and ids_cpu.shape[0] > 0 and ids_cpu.shape[1] > 0 and not ids_cpu.is_cuda
     a = ids_cpu.numpy()
     N, L = a.shape
     context = L if context is None else int(context)
-    lens = a.argmax(axis=1).astype(np.int64) + 1
+    if lens is None:
+        lens = a.argmax(axis=1).astype(np.int64) + 1
+    else:
+        lens = np.asarray(lens.numpy() if isinstance(lens, torch.Tensor) else lens).astype(np.int64).reshape(-1)
+        if lens.size != N or int(lens.min()) < 1 or int(lens.max()) > L:
+            raise ValueError(f"lens: expected {N} caption lengths in [1, {L}]")
     if int(lens.max()) > context:
         raise ValueError(f"a caption of {int(lens.max())} tokens does not fit the context of {context}")
     seq_start = np.zeros(N + 1, dtype=np.int64)
@@ -1251,8 +1307,9 @@ def pack_captions(ids_cpu, context=None):
     np.cumsum(np.bincount(pos, minlength=context), out=pos_seg[1:])
     tok_order, tok_seg = token_sort(torch.from_numpy(ids))
     i32 = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32))  # noqa: E731
-    return dict(ids=torch.from_numpy(ids), seq_start=i32(seq_start), eot_rows=i32(seq_start[1:] - 1), max_len=int(lens.max()),
-                tok_order=tok_order, tok_seg=tok_seg, pos_order=i32(np.argsort(pos, kind="stable")), pos_seg=i32(pos_seg))
+    return dict(ids=torch.from_numpy(ids), seq_start=i32(seq_start), eot_rows=i32(seq_start[1:] - 1), cls_rows=i32(seq_start[:-1]),
+                max_len=int(lens.max()), tok_order=tok_order, tok_seg=tok_seg, pos_order=i32(np.argsort(pos, kind="stable")),
+                pos_seg=i32(pos_seg))
 
 
 def text_embed_bwd_packed(dx, ids, seq_start, demb, dpos, *, N, tok_sort, pos_sort):

@@ -124,11 +124,26 @@ class TVTS(TVTSv2Base):
         return (emb if project else feat).clone()
 
     @torch.no_grad()
-    def encode_text(self, text_dict):
+    def encode_text(self, text_dict, packed=False):
         """-> [N, E] caption embeddings (compute_text's second output in eval mode) from the tokenizer's
-        {'input_ids', 'attention_mask'} (right-padded)."""
+        {'input_ids', 'attention_mask'} (right-padded).  packed: the tower over sum(len_i) token rows instead of N * max(len_i)
+        (captions of at most 80 tokens, bidirectional packed attention); the default gives the padded pass, bit for bit."""
         self._fresh_shadows()
-        _, t = self.engine.encode_text(*tokenizer_inputs(text_dict, self.store.device, validate=True, arch=self.arch))
+        if not packed:
+            _, t = self.engine.encode_text(*tokenizer_inputs(text_dict, self.store.device, validate=True, arch=self.arch))
+            return t.clone()
+        from .. import hip as K
+        eng = self.engine
+        longest = int(text_dict["attention_mask"].sum(-1).max())
+        if longest > eng.MAX_UNPADDED:
+            raise ValueError(f"encode_text(packed=True): a caption of {longest} tokens, the packed attention kernels take at most "
+                             f"{eng.MAX_UNPADDED}")
+        _, _, N, L = tokenizer_inputs(text_dict, "cpu", validate=True, arch=self.arch)  # (the checks; the rectangle stays on the host)
+        pk = K.pack_captions(text_dict["input_ids"].detach().to("cpu", torch.int64), self.arch["max_pos"],
+                             lens=text_dict["attention_mask"].detach().to("cpu", torch.int64).sum(-1))
+        d = eng._stage_small({k: pk[k] for k in ("ids", "seq_start", "cls_rows")})
+        _, t = eng.encode_text(d["ids"], None, N, L, pk=dict(seq_start=d["seq_start"], cls_rows=d["cls_rows"], max_len=pk["max_len"],
+                                                             M=int(pk["ids"].numel())))
         return t.clone()
 
 

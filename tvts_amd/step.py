@@ -148,6 +148,8 @@ class StepRunner:
             # (a rank that splits beside one that does not would run the same collectives, but a chunk count is part of what the
             # ranks must have in common: the batch each one hands over has to divide by it)
             D.agree(repr(("micro_batches", self.micro_batches)).encode(), "StepRunner: micro_batches")
+            # (the packed and the padded v1 text tower round differently: ranks that disagree would average gradients of two models)
+            D.agree(repr(("text_unpadded", bool(getattr(self.eng, "text_unpadded", False)))).encode(), "StepRunner: arch['text_unpadded']")
         if self.guarding:
             dev = self.store.device
             self.norm_coef = torch.zeros(2, dtype=torch.float32, device=dev)  # [global norm, clip coefficient] of the last step
