@@ -570,6 +570,33 @@ int tvts_patch_gather_tube_u8_aug(const unsigned char* frames, int Bs, int H0, i
 int tvts_patch_gather_tube_u8_view(const unsigned char* frames, int Bs, int Tsrc, int H0, int W0, const int* view_i, const int* keep,
                                    int B, int tubes, int tubelet, int n, int img, int patch, const float* mean3, const float* std3,
                                    void* out, int ldo, hipStream_t stream);
+/* ---- The Resize and crop of the v1 PRETRAINING transform on uint8 frames at source size, in front of tvts_patch_gather_tube_u8
+ * (v1/video_transforms/videoaug.py:8-22: TensorToNumpy -> Resize(int(crop * 1.2)) -> RandomCrop | CenterCrop -> ClipToTensor ->
+ * Normalize).  TensorToNumpy makes PIL images and v1/video_transforms/functional.py:56-59 maps every interpolation but 'bilinear' --
+ * the default 'nearest' included -- to PIL.Image.BILINEAR, so the Resize is Pillow's 8-bit bilinear resample (Resample.c,
+ * PRECISION_BITS = 22): two passes with fixed-point taps and a support that grows with the downscale.  It is integer arithmetic; the
+ * bytes written are Pillow's, `resized[top:top + img, left:left + img]` of every frame, and only that window is computed.
+ *   src     one packed byte buffer of source clips; clip b is uint8 [T, Hs_b, Ws_b, 3] contiguous at byte offset desc[b][0] (64-bit, any
+ *           alignment); the clips of one batch may differ in Hs_b x Ws_b
+ *   desc    int64 [B, 8] in DEVICE memory = (offset, Hs, Ws, top, left, ytab, xtab, 0): (top, left) the crop in RESIZED coordinates,
+ *           ytab / xtab the int32-element offsets in `tables` of the clip's row (Hs -> new_h) and column (Ws -> new_w) tables
+ *   tables  int32 in DEVICE memory, one table per distinct (n_in, n_out) of the batch, shared by the clips that use it:
+ *           (n_in, n_out, ksize, 0) | first[n_out] | count[n_out] | taps[n_out][ksize] -- output index i reads the source indices
+ *           first[i] .. first[i] + count[i] - 1 with the int32 taps taps[i][0 .. count[i]) (tvts_amd/data_loader/transforms.py
+ *           pil_bilinear_coeffs: Pillow's precompute_coeffs + normalize_coeffs_8bpc), 1 <= count[i] <= ksize
+ *   out     uint8 [B, T, img, img, 3], pixel rows ldo >= 3 * img bytes apart (3 * img: the contiguous clips the gather takes)
+ * One pass: acc = 2^21 + sum_j px[first + j] * taps[j] (int32: the taps are >= 0 and sum to 2^22 +- count), byte = clip8(acc >> 22).
+ * The horizontal pass runs first, over the source rows the vertical taps of the window read; the vertical pass reads its ROUNDED
+ * uint8 result (the rounding between the passes is part of Pillow's result).  An axis whose size does not change has identity taps.
+ * Intermediate storage: a buffer of the CALLER (nothing is allocated here), tmp uint8 [B, T, tmp_rows, img, 3] -- tmp_bytes >=
+ * B * T * tmp_rows * img * 3, tmp_rows >= the largest row span of a window in the batch, first[top + img - 1] + count[top + img - 1] -
+ * first[top] of a clip's row table (tvts_amd.hip.check_resize_plan returns it).  A window that would need more rows is cut at
+ * tmp_rows (its lower rows are wrong, nothing is written outside tmp or out).
+ * Returns -22 for a NULL src / desc / tables / tmp / out; B, T, img or tmp_rows <= 0 (B, T > 65535; img, tmp_rows > 32768); ldo < 3 * img;
+ * tmp_bytes below the rule.  desc and tables are DEVICE data and are not checked: tvts_amd.hip.check_resize_plan does (0 <= top <=
+ * new_h - img, 0 <= left <= new_w - img, every clip inside src, the tables those of its sizes). */
+int tvts_resize_crop_u8(const unsigned char* src, const long* desc, const int* tables, int B, int T, int img, int tmp_rows,
+                        unsigned char* tmp, long tmp_bytes, unsigned char* out, int ldo, hipStream_t stream);
 /* ---- RandAugment of the v1 fine-tuning recipe (v1/downstream/rand_augment.py applied at v1/downstream/ssv2.py:174-184, --aa
  * rand-m7-n4-mstd0.5-inc1) on uint8 frames at source size, in front of the augmentation gather above, with the bytes PIL gives.
  * work uint8 [Bs + 2 * B, T, H0, W0, 3]: the Bs uploaded source clips, then two regions of B views each.  B = Bs * num_sample views;

@@ -6,6 +6,8 @@
 //  tvts_patch_gather_tube*  the v1 tubelet (Conv3d) form of the same im2col: seven entry points -- fp32 clips frame- or channel-major,
 //                           uint8 frames behind a crop, test views, random-resized crop / flip / erase, each of the fine-tuning
 //                           forms with Mixup / CutMix -- over ONE kernel frame (tube_gather_kernel) and four source policies
+//  tvts_resize_crop_u8      the Resize (Pillow's 8-bit bilinear resample, with its bytes) and the crop of the v1 pretraining transform on
+//                           uint8 source clips of any sizes, in front of tvts_patch_gather_tube_u8
 //  tvts_vit_assemble(+_bwd) CLS + patch embedding + spatial/temporal position (:185-198) -> tokens [B*S, W]
 //  tvts_text_embed(+_bwd)   token embedding gather + positional add (model_dist_TVTSv2_ViT_B_16.py:98-100)
 //  tvts_text_mean(+_bwd)    clip-major captions [NT*B,E] -> mean over NT and the [B,NT,E] copy for the sort head (:69-76)
@@ -408,6 +410,101 @@ extern "C" int tvts_patch_gather_tube_u8_aug(const unsigned char* frames, int Bs
     if (!tube_rows_ok(frames, 1, r) || !u8_frames_ok(mean3, std3, H0, W0, 1) || !aug_i || Bs <= 0 || (!mix_i) != (!mix_f)) return TVTS_EINVAL;
     const U8Aug src{u8_frames(frames, H0, W0, mean3, std3), aug_i, Bs, tubes * tubelet, img};
     return mix_i ? tube_launch<true>(src, r, mix_i, mix_f, stream) : tube_launch<false>(src, r, nullptr, nullptr, stream);
+}
+
+// ---------------------------------------------------------------------------------------------- v1 Resize + crop, uint8 -> uint8
+// The Resize of the v1 pretraining transform (v1/video_transforms/videoaug.py:10,18 -> video_transform.py:181-188 -> functional.py:56-59:
+// on the PIL images TensorToNumpy makes, every interpolation but 'bilinear' -- the default 'nearest' included -- is PIL.Image.BILINEAR)
+// and the RandomCrop / CenterCrop behind it, for the crop window only: Pillow's two-pass 8-bit resample (Resample.c, PRECISION_BITS
+// 22) in its own integer arithmetic, so the bytes are Pillow's.  The taps are host tables (tvts_amd/data_loader/transforms.py
+// pil_bilinear_coeffs), one per distinct (n_in, n_out) of the batch; a clip's descriptor row names its two.  Table and descriptor
+// layouts: include/tvts_hip.h.
+//   resize_rows_kernel   the horizontal pass over the source rows [y0, y1) that the vertical taps of the window read and the img
+//                        columns of the window -> tmp uint8 [B, T, tmp_rows, img, 3] (the rounded bytes: Pillow rounds between the passes)
+//   resize_cols_kernel   the vertical pass over tmp -> out [B, T, img, img, 3] (rows ldo bytes apart)
+// One thread per pixel (three channels share the taps).  Every write index comes from the launch geometry: a clip whose window
+// needs more than tmp_rows source rows (a descriptor the host check would refuse) is cut at tmp_rows in both passes.
+struct ResizeTab {
+    const int *first, *count, *taps;
+    int ksize;
+};
+__device__ inline ResizeTab resize_tab(const int* __restrict__ tables, long off) {
+    const int* t = tables + off;  // (n_in, n_out, ksize, 0) | first[n_out] | count[n_out] | taps[n_out][ksize]
+    const int n_out = t[1];
+    return ResizeTab{t + 4, t + 4 + n_out, t + 4 + 2 * (size_t)n_out, t[2]};
+}
+__device__ inline unsigned char clip8(int v) { return (unsigned char)(v < 0 ? 0 : v > 255 ? 255 : v); }
+constexpr int kResizeBits = 22;
+
+struct ResizeClip {
+    long off;
+    int Hs, Ws, top, left, y0, rows;
+    ResizeTab ty, tx;
+};
+__device__ inline ResizeClip resize_clip(const long* __restrict__ desc, const int* __restrict__ tables, int b, int img, int tmp_rows) {
+    const long* d = desc + (size_t)b * 8;
+    ResizeClip c;
+    c.off = d[0], c.Hs = (int)d[1], c.Ws = (int)d[2], c.top = (int)d[3], c.left = (int)d[4];
+    c.ty = resize_tab(tables, d[5]), c.tx = resize_tab(tables, d[6]);
+    c.y0 = c.ty.first[c.top];  // first / first + count never decrease along an axis: the window's first and last output rows bound it
+    const int last = c.top + img - 1;
+    c.rows = min(c.ty.first[last] + c.ty.count[last] - c.y0, tmp_rows);
+    return c;
+}
+
+__global__ __launch_bounds__(256) void resize_rows_kernel(const unsigned char* __restrict__ src, const long* __restrict__ desc,
+                                                          const int* __restrict__ tables, int T, int img, int tmp_rows,
+                                                          unsigned char* __restrict__ tmp) {
+    const int b = blockIdx.z, f = blockIdx.y;
+    const ResizeClip c = resize_clip(desc, tables, b, img, tmp_rows);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int r = i / img, x = i - r * img;
+    if (r >= c.rows) return;
+    const int xo = c.left + x, n = c.tx.count[xo];
+    const unsigned char* p = src + c.off + (((size_t)f * c.Hs + (c.y0 + r)) * c.Ws + c.tx.first[xo]) * 3;
+    const int* k = c.tx.taps + (size_t)xo * c.tx.ksize;
+    int a0 = 1 << (kResizeBits - 1), a1 = a0, a2 = a0;
+    for (int j = 0; j < n; ++j, p += 3) {
+        const int kj = k[j];
+        a0 += p[0] * kj, a1 += p[1] * kj, a2 += p[2] * kj;
+    }
+    unsigned char* o = tmp + ((((size_t)b * T + f) * tmp_rows + r) * img + x) * 3;
+    o[0] = clip8(a0 >> kResizeBits), o[1] = clip8(a1 >> kResizeBits), o[2] = clip8(a2 >> kResizeBits);
+}
+
+__global__ __launch_bounds__(256) void resize_cols_kernel(const long* __restrict__ desc, const int* __restrict__ tables, int T, int img,
+                                                          int tmp_rows, const unsigned char* __restrict__ tmp,
+                                                          unsigned char* __restrict__ out, int ldo) {
+    const int b = blockIdx.z, f = blockIdx.y;
+    const ResizeClip c = resize_clip(desc, tables, b, img, tmp_rows);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int y = i / img, x = i - y * img;
+    if (y >= img) return;
+    const int yo = c.top + y, r0 = c.ty.first[yo] - c.y0, n = min(c.ty.count[yo], c.rows - r0);
+    const unsigned char* p = tmp + ((((size_t)b * T + f) * tmp_rows + r0) * img + x) * 3;
+    const int* k = c.ty.taps + (size_t)yo * c.ty.ksize;
+    int a0 = 1 << (kResizeBits - 1), a1 = a0, a2 = a0;
+    for (int j = 0; j < n; ++j, p += (size_t)img * 3) {
+        const int kj = k[j];
+        a0 += p[0] * kj, a1 += p[1] * kj, a2 += p[2] * kj;
+    }
+    unsigned char* o = out + (((size_t)b * T + f) * img + y) * ldo + x * 3;
+    o[0] = clip8(a0 >> kResizeBits), o[1] = clip8(a1 >> kResizeBits), o[2] = clip8(a2 >> kResizeBits);
+}
+
+extern "C" int tvts_resize_crop_u8(const unsigned char* src, const long* desc, const int* tables, int B, int T, int img, int tmp_rows,
+                                   unsigned char* tmp, long tmp_bytes, unsigned char* out, int ldo, hipStream_t stream) {
+    if (!src || !desc || !tables || !tmp || !out || B <= 0 || T <= 0 || img <= 0 || tmp_rows <= 0 || B > 65535 || T > 65535 ||
+        img > 32768 || tmp_rows > 32768 || ldo < 3 * img)
+        return TVTS_EINVAL;
+    if (tmp_bytes < (long)B * T * tmp_rows * img * 3) return TVTS_EINVAL;
+    hipLaunchKernelGGL(resize_rows_kernel, dim3((tmp_rows * img + 255) / 256, T, B), dim3(256), 0, stream, src, desc, tables, T, img,
+                       tmp_rows, tmp);
+    TVTS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(resize_cols_kernel, dim3((img * img + 255) / 256, T, B), dim3(256), 0, stream, desc, tables, T, img, tmp_rows,
+                       tmp, out, ldo);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
 }
 
 

@@ -302,12 +302,21 @@ class EngineV1(Engine):
                        P.p("video_model.temporal_embed").view(-1, W), keep, tok, B=B, T=tubes, n=n)
         return tok
 
-    def video_forward_v1(self, video, keep, B, tubes, cls_rows):
-        """-> (tokens [B*S, W] fp32 after the final norm, video_emb [B, E])"""
+    def video_forward_v1(self, video, keep, B, tubes, cls_rows, crop=None, resize=None):
+        """-> (tokens [B*S, W] fp32 after the final norm, video_emb [B, E]).  video: fp32 [B, T, 3, img, img]; uint8 [B, T, H0, W0, 3]
+        with crop (int32 [B, 2] on the device, None = centre); or, with resize (the device plan of prepare_batch: desc, tables,
+        tmp_rows), the packed uint8 source clips -- Pillow's Resize and the crop run first (tvts_resize_crop_u8) into a workspace of
+        [B, T, img, img, 3], which the uint8 gather then reads whole (its centre crop of an img x img frame is the identity)."""
         a = self.arch
         W, E, hv = a["width"], a["embed"], a["heads"]
         S = 1 + tubes * keep.shape[2]
-        tok = self._vit_embed_v1(video, keep, B, tubes, "vit")
+        if resize is not None:
+            T, img = tubes * a["tubelet"], a["image"]
+            frames = self._b("vit.u8frames", (B, T, img, img, 3), torch.uint8)
+            tmp = self._b("vit.u8rows", (B * T * resize["tmp_rows"] * img * 3,), torch.uint8)
+            K.resize_crop_u8(video, resize["desc"], resize["tables"], tmp, frames, B=B, T=T, img=img, tmp_rows=resize["tmp_rows"])
+            video, crop = frames, None
+        tok = self._vit_embed_v1(video, keep, B, tubes, "vit", crop)
         x = self._blocks_fwd("video_model.blocks.", _VIT_NAMES, tok, "vit", a["layers"], hv, "gelu", 1e-6,
                              lambda qkv, att, lse: K.attn_fwd("full", qkv, att, lse, B=B, heads=hv, S=S, causal=False, head_dim=W // hv),
                              recompute=self.recompute)
@@ -431,12 +440,107 @@ class EngineV1(Engine):
         self._ready("video_model.norm.")
 
     # ------------------------------------------------------------------ whole model
+    # uint8 wire formats of the pretraining step: the transform chain of v1/video_transforms/videoaug.py:8-22 behind
+    # the decoder runs on the device -- Resize (Pillow's 8-bit bilinear resample, tvts_resize_crop_u8) and the crop at the head of
+    # video_forward_v1, ClipToTensor and Normalize inside tvts_patch_gather_tube_u8.
+    def _u8_batch(self, data: dict):
+        """the HOST half of a uint8 batch: None for fp32 clips, else dict(B, T, clips, crop, plan) --
+          no data["resize"]   clips uint8 [B, T, H0, W0, 3], already resized (or cropped: H0 = W0 = img); crop int32 [B, 2] (top, left)
+                              from data["crop"], None = the centre crop; plan None
+          data["resize"]      clips = a tensor [B, T, Hs, Ws, 3] or a list of B tensors [T, Hs_b, Ws_b, 3] at the decoder's sizes;
+                              data["crop"] in RESIZED coordinates (None: centre); plan = hip.resize_plan(...), crop None (the plan has it)
+        ValueError by name for: uint8 that is not [..., 3]; a clip with fewer frames than the batch's T (the reference zero-pads short
+        clips BEHIND Normalize, v1/base/base_dataset.py:121-123, which uint8 frames cannot express); a (resized) side below img; a crop
+        outside the (resized) frame.  Nothing here touches the device."""
+        a, video = self.arch, data["video"]
+        img = a["image"]
+        ragged = isinstance(video, (list, tuple))
+        if not ragged and video.dtype != torch.uint8:
+            return None
+        clips = list(video) if ragged else video
+        if ragged and (not clips or any(not torch.is_tensor(c) or c.dtype != torch.uint8 for c in clips)):
+            raise ValueError("video: a list of clips must hold uint8 tensors [T, Hs, Ws, 3]")
+        for b, c in enumerate(clips if ragged else [video]):
+            if c.dim() != (4 if ragged else 5) or c.shape[-1] != 3:
+                raise ValueError(f"uint8 video must be [B, T, H, W, 3] (or a list of [T, H, W, 3] clips), got {tuple(c.shape)}"
+                                 + (f" for clip {b}" if ragged else ""))
+        B = len(clips) if ragged else int(video.shape[0])
+        T = max(int(c.shape[0]) for c in clips) if ragged else int(video.shape[1])
+        for b in range(B if ragged else 0):
+            if int(clips[b].shape[0]) != T:
+                raise ValueError(f"clip {b} has {int(clips[b].shape[0])} frames, the batch has clips of {T}: short clips are zero-padded "
+                                 "behind Normalize by the reference, which uint8 frames cannot express (pad them on the host as fp32)")
+        if T < a["tubelet"]:
+            raise ValueError(f"clips of {T} frames: fewer than one tubelet of {a['tubelet']}")
+        crop = data.get("crop")
+        if crop is not None:
+            crop = torch.as_tensor(crop).detach().to("cpu", torch.int32).contiguous()
+            if tuple(crop.shape) != (B, 2):
+                raise ValueError(f"crop {tuple(crop.shape)}: expected [{B}, 2] (top, left)")
+        if data.get("resize") is None:
+            if ragged:
+                raise ValueError("a list of clips needs data['resize']: without it the frames are one tensor [B, T, H0, W0, 3]")
+            H0, W0 = int(video.shape[2]), int(video.shape[3])
+            if H0 < img or W0 < img:
+                raise ValueError(f"uint8 frames of {H0} x {W0}: a side below the crop of {img} x {img}")
+            if crop is not None and bool(((crop < 0) | (crop[:, :1] > H0 - img) | (crop[:, 1:] > W0 - img)).any()):
+                raise ValueError(f"crop outside the frame: needs 0 <= top <= {H0 - img} and 0 <= left <= {W0 - img}")
+            return dict(B=B, T=T, clips=video, crop=crop, plan=None)
+        sizes = [(int(c.shape[1]), int(c.shape[2])) for c in clips] if ragged else [(int(video.shape[2]), int(video.shape[3]))] * B
+        plan = K.resize_plan(sizes, None if crop is None else crop.tolist(), size=int(data["resize"]), img=img, T=T)
+        return dict(B=B, T=T, clips=clips, crop=None, plan=plan)
+
+    def _u8_pb(self, u8, d):
+        """the prepared batch's share of a uint8 batch (d: the device tensors of _stage_small)"""
+        if u8 is None:
+            return {}
+        out = dict(crop=d.get("crop"))
+        if u8["plan"] is not None:
+            out["resize"] = dict(desc=d["rs_desc"], tables=d["rs_tables"], tmp_rows=u8["plan"]["tmp_rows"])
+        return out
+
+    def _packed_to_device(self, clips, plan):
+        """source clips of a resize plan -> ONE uint8 device buffer with clip b at plan["offsets"][b].  A tensor [B, T, Hs, Ws, 3] is
+        that buffer already; a list is packed into a page-locked staging buffer (a ring of STAGE_SLOTS, each guarded by the event of
+        its last copy, as _stage_small).  Either way ONE asynchronous copy on the engine's copy stream (_clip_to_device)."""
+        if torch.is_tensor(clips):
+            return self._clip_to_device(clips.contiguous().view(-1))
+        total = plan["nbytes"]
+        ring = getattr(self, "_clip_ring", None)
+        if ring is None:
+            ring = self._clip_ring = dict(i=0, slots=[None] * self.STAGE_SLOTS)
+        i = ring["i"] = (ring["i"] + 1) % self.STAGE_SLOTS
+        slot = ring["slots"][i]
+        if slot is None or slot[0].numel() < total:
+            slot = ring["slots"][i] = [torch.empty(total, dtype=torch.uint8, pin_memory=True), None]
+        if slot[1] is not None:
+            slot[1].synchronize()
+        from .data_loader.v1_input import pack_clips
+        dev = self._clip_to_device(pack_clips(clips, plan["offsets"].tolist(), slot[0])[:total])
+        if not torch.cuda.is_current_stream_capturing():
+            slot[1] = torch.cuda.Event()
+            slot[1].record(self._copy_stream)
+        return dev
+
     def prepare_batch(self, data: dict):
         """v1 batch dict (v1/trainer/trainer.py:121-131): text = the tokenizer's {'input_ids', 'attention_mask'} (right-padded),
-        video fp32 [B, T, 3, H, W], keep_ind int64 [B, n_tubes, n_keep] (one mask per tube)."""
+        video fp32 [B, T, 3, H, W] or one of the uint8 wire formats of _u8_batch, keep_ind int64 [B, n_tubes, n_keep] (one mask per
+        tube) or, without it, mask_seed (+ sample_offset): the masks drawn on the device."""
         a = self.arch
-        video = self._clip_to_device(data["video"]).to(torch.float32).contiguous()
-        B, T = video.shape[:2]
+        u8 = self._u8_batch(data)  # (host only: the uint8 wire formats below, checked before anything reaches the device)
+        if "keep_ind" not in data and "mask_seed" not in data:
+            raise KeyError("batch dict needs 'keep_ind' or 'mask_seed' (+ optional 'sample_offset')")
+        vsmall = {}  # the small tensors of a uint8 batch: they travel in one staging copy (_stage_small)
+        if u8 is None:
+            video = self._clip_to_device(data["video"]).to(torch.float32).contiguous()
+            B, T = video.shape[:2]
+        else:
+            B, T = u8["B"], u8["T"]
+            video = self._packed_to_device(u8["clips"], u8["plan"]) if u8["plan"] is not None else self._clip_to_device(u8["clips"]).contiguous()
+            if u8["crop"] is not None:
+                vsmall["crop"] = u8["crop"]
+            if u8["plan"] is not None:
+                vsmall["rs_desc"], vsmall["rs_tables"] = torch.from_numpy(u8["plan"]["desc"]), torch.from_numpy(u8["plan"]["tables"])
         tubes = T // a["tubelet"]
         from .model.model_dist_TVTS import right_padded, tokenizer_inputs  # (that module imports this one)
         text = {k: data["text"][k].detach().to("cpu", torch.int64) for k in ("input_ids", "attention_mask")}
@@ -446,13 +550,25 @@ class EngineV1(Engine):
         else:
             ids, kv_len, N, L = tokenizer_inputs(text, self.dev)
         NT = N // B
-        keep = data["keep_ind"][:, :tubes].to(torch.int32).contiguous().to(self.dev)
+        if "keep_ind" in data:
+            keep = data["keep_ind"][:, :tubes].to(torch.int32).contiguous().to(self.dev)
+        else:
+            # device-drawn tube masks: row (sample_offset + b) * n_temp + t of tvts_tube_mask is tube t of global clip sample_offset + b, so
+            # the draw depends on neither the batch split nor the clip length (the reference draws n_temp masks per clip in the dataset
+            # worker, v1/base/base_dataset.py:129-140, and ships them with the batch)
+            from .arch import n_keep, patches_per_frame
+            n_temp = a["num_frames"] // a["tubelet"]
+            if tubes > n_temp:
+                raise ValueError(f"mask_seed: clips of {tubes} tubes, the model draws {n_temp} masks per clip")
+            keep = K.tube_mask(int(data["mask_seed"]), int(data.get("sample_offset", 0)) * n_temp, B * n_temp, patches_per_frame(a),
+                               n_keep(a), device=self.dev).view(B, n_temp, -1)[:, :tubes].contiguous()
         n = keep.shape[2]
         S = 1 + tubes * n
         So = S + NT
         if self.text_unpadded:
-            return self._prepare_unpadded(text, dict(video=video, keep=keep, B=B, T=T, tubes=tubes, N=N, NT=NT, L=L, n=n, S=S), So)
-        return dict(video=video, ids=ids, kv_len=kv_len,
+            return self._prepare_unpadded(text, dict(video=video, keep=keep, B=B, T=T, tubes=tubes, N=N, NT=NT, L=L, n=n, S=S), So, u8, vsmall)
+        pb_u8 = self._u8_pb(u8, self._stage_small(vsmall) if vsmall else {})
+        return dict(video=video, ids=ids, kv_len=kv_len, **pb_u8,
                     tok_sort=tuple(t.to(self.dev) for t in K.token_sort(text["input_ids"][:, :L])),  # ordered word-embedding gradient sums
                     txt_cls_rows=(torch.arange(N) * L).to(torch.int32).to(self.dev), keep=keep, B=B, T=T, tubes=tubes, N=N, NT=NT, L=L,
                     n=n, S=S, vid_rows=(torch.arange(B) * S).to(torch.int32).to(self.dev),
@@ -461,10 +577,11 @@ class EngineV1(Engine):
 
     MAX_UNPADDED = 80  # the longest caption the packed attention kernels take (tile classes up to 5 x 16 rows)
 
-    def _prepare_unpadded(self, text, pb, So):
+    def _prepare_unpadded(self, text, pb, So, u8=None, vsmall=None):
         """the text half of prepare_batch under arch["text_unpadded"]: the captions packed by their lengths (hip.pack_captions), every
-        descriptor and row table of the batch in ONE staging copy (_stage_small).  pb["L"] stays the longest caption: the L of the
-        padded step, which the dropout masks are drawn for."""
+        descriptor and row table of the batch in ONE staging copy (_stage_small) -- the crop, resize descriptor and tap tables of a
+        uint8 batch (vsmall) among them.  pb["L"] stays the longest caption: the L of the padded step, which the dropout masks are
+        drawn for."""
         lens = text["attention_mask"].sum(-1)
         if int(lens.max()) > self.MAX_UNPADDED:
             raise ValueError(f"text_unpadded: a caption of {int(lens.max())} tokens, the packed attention kernels take at most "
@@ -476,7 +593,9 @@ class EngineV1(Engine):
         small = {k: pk[k] for k in ("ids", "seq_start", "cls_rows", "tok_order", "tok_seg", "pos_order", "pos_seg")}
         small["vid_rows"] = (torch.arange(B) * S).to(torch.int32)
         small["sort_rows"] = (torch.arange(B)[:, None] * So + S + torch.arange(NT)[None, :]).reshape(-1).to(torch.int32)
+        small.update(vsmall or {})
         d = self._stage_small(small)
+        pb.update(self._u8_pb(u8, d))
         M = int(pk["ids"].numel())
         pb.update(ids=d["ids"], kv_len=None, tok_sort=(d["tok_order"], d["tok_seg"]), txt_cls_rows=d["cls_rows"], vid_rows=d["vid_rows"],
                   sort_rows=d["sort_rows"], sort_rows64=d["sort_rows"].to(torch.int64), M=M, seq_start=d["seq_start"],
@@ -495,7 +614,7 @@ class EngineV1(Engine):
         K.text_mean(t, text_emb, tmean_scratch, NT=NT, B=B)          # mean over the NT captions (model_dist_TVTS.py:104-107)
         text_before = self._f("mdl.text_before", (B, NT, a["text_width"]))
         K.text_mean(before, self._f("mdl.tb_mean", (B, a["text_width"])), text_before, NT=NT, B=B)  # [NT,B,W] -> [B,NT,W] (:99-101)
-        out, video_emb = self.video_forward_v1(pb["video"], pb["keep"], B, pb["tubes"], pb["vid_rows"])
+        out, video_emb = self.video_forward_v1(pb["video"], pb["keep"], B, pb["tubes"], pb["vid_rows"], pb.get("crop"), pb.get("resize"))
         if self.embeds_ready is not None:
             self.embeds_ready(text_emb, video_emb)
         pred = self.sort_forward(out, text_before, B, S, NT) if NT != 1 else None

@@ -1224,6 +1224,124 @@ def patch_gather_tube_u8_view(frames, keep, out, view, *, B, tubes, tubelet, n, 
                                                     *_norm3(mean, std), _p(out), _ld(out), _stream()), "tvts_patch_gather_tube_u8_view")
 
 
+# ---- Resize + crop of the v1 pretraining transform on uint8 source clips (embed.hip: tvts_resize_crop_u8)
+_RESIZE_TABLES = {}
+
+
+def resize_table(n_in, n_out):
+    """the int32 table of one axis as tvts_resize_crop_u8 reads it: (n_in, n_out, ksize, 0) | first[n_out] | count[n_out] |
+    taps[n_out][ksize] from transforms.pil_bilinear_coeffs, cached per (n_in, n_out) -> 1-D numpy int32"""
+    import numpy as np
+    key = (int(n_in), int(n_out))
+    t = _RESIZE_TABLES.get(key)
+    if t is None:
+        from .data_loader.transforms import pil_bilinear_coeffs
+        rows = pil_bilinear_coeffs(*key)
+        ks = max(len(k) for _, k in rows)
+        taps = np.zeros((key[1], ks), dtype=np.int32)
+        for i, (_, k) in enumerate(rows):
+            taps[i, :len(k)] = k
+        t = _RESIZE_TABLES[key] = np.concatenate([np.array([key[0], key[1], ks, 0], dtype=np.int32),
+                                                  np.array([f for f, _ in rows], dtype=np.int32),
+                                                  np.array([len(k) for _, k in rows], dtype=np.int32), taps.reshape(-1)])
+        t.setflags(write=False)
+    return t
+
+
+def resize_plan(sizes, crops, *, size, img, T, offsets=None):
+    """the host half of tvts_resize_crop_u8 for a batch of source clips: sizes B x (Hs, Ws); crops B x (top, left) in RESIZED
+    coordinates or None (the centre crop of every clip: CenterCrop's round-half-to-even offsets, the rule of tvts_patch_gather_tube_u8
+    with crop = NULL); size: video_transform.Resize(size); offsets: the clips' byte offsets in the packed buffer (default: back to
+    back) -> dict(desc int64 [B, 8], tables int32, numpy; offsets; nbytes: what the clips occupy; tmp_rows).  ValueError by name for
+    a resized side below img and a crop outside the resized frame (check_resize_plan)."""
+    import numpy as np
+    from .data_loader.transforms import centre_crop_offset, resize_sizes
+    B = len(sizes)
+    desc = np.zeros((B, 8), dtype=np.int64)
+    where, parts, total, at = {}, [], 0, 0
+    for b, (hs, ws) in enumerate(sizes):
+        hs, ws = int(hs), int(ws)
+        if hs < 1 or ws < 1:
+            raise ValueError(f"resize plan: clip {b} has frames of {hs} x {ws}")
+        nh, nw = resize_sizes(hs, ws, int(size))
+        if nh < img or nw < img:
+            raise ValueError(f"resize plan: clip {b} ({hs} x {ws}) resizes to {nh} x {nw} under Resize({size}), below the crop of "
+                             f"{img} x {img}")
+        loc = []
+        for key in ((hs, nh), (ws, nw)):
+            if key not in where:
+                where[key] = total
+                parts.append(resize_table(*key))
+                total += parts[-1].size
+            loc.append(where[key])
+        top, left = (centre_crop_offset(nh - img), centre_crop_offset(nw - img)) if crops is None else (int(crops[b][0]), int(crops[b][1]))
+        off = at if offsets is None else int(offsets[b])
+        desc[b] = (off, hs, ws, top, left, loc[0], loc[1], 0)
+        at = off + T * hs * ws * 3
+    tables = np.concatenate(parts)
+    nbytes = int(max(desc[:, 0] + T * desc[:, 1] * desc[:, 2] * 3))
+    return dict(desc=desc, tables=tables, offsets=desc[:, 0].copy(), nbytes=nbytes,
+                tmp_rows=check_resize_plan(desc, tables, T=T, img=img, src_bytes=nbytes))
+
+
+def check_resize_plan(desc, tables, *, T, img, src_bytes):
+    """the host-side check of a resize plan (the C entry point takes both as unchecked device data): desc integer [B, 8] = (offset,
+    Hs, Ws, top, left, ytab, xtab, 0), tables int32 -> tmp_rows, the largest row span of a crop window (the size rule of the entry
+    point's tmp).  ValueError for a clip that leaves the src_bytes of the packed buffer, a table location outside `tables`, a table
+    that is not the one of its (n_in, n_out) or whose n_in is not the clip's side, a resized side below img, a crop outside the
+    resized frame (0 <= top <= new_h - img, 0 <= left <= new_w - img) or a nonzero reserved column."""
+    import numpy as np
+    d, tb = np.asarray(desc), np.asarray(tables)
+    if d.ndim != 2 or d.shape[0] < 1 or d.shape[1] != 8 or d.dtype.kind not in "iu" or tb.ndim != 1 or tb.dtype != np.int32:
+        raise ValueError(f"resize plan: integer desc [B, 8] and int32 tables [n], got {d.dtype} {d.shape} / {tb.dtype} {tb.shape}")
+    if T < 1 or img < 1:
+        raise ValueError(f"resize plan: T = {T}, img = {img}")
+    d = d.astype(np.int64)
+    tmp_rows, seen = 1, {}
+    for b, (off, hs, ws, top, left, yt, xt, zero) in enumerate(d.tolist()):
+        if hs < 1 or ws < 1 or off < 0 or off + T * hs * ws * 3 > src_bytes:
+            raise ValueError(f"resize plan: clip {b} ({T} x {hs} x {ws} x 3 bytes at offset {off}) leaves the buffer of {src_bytes} bytes")
+        if zero:
+            raise ValueError("resize plan: column 7 is reserved and must be 0")
+        for loc, n_in, at, ax in ((yt, hs, top, "top"), (xt, ws, left, "left")):
+            if loc not in seen:
+                if loc < 0 or loc + 4 > tb.size:
+                    raise ValueError(f"resize plan: clip {b} names a table at {loc}, outside the {tb.size} table elements")
+                t_in, n_out = int(tb[loc]), int(tb[loc + 1])
+                want = resize_table(t_in, n_out) if t_in >= 1 and n_out >= 1 else None
+                if want is None or loc + want.size > tb.size or not np.array_equal(tb[loc:loc + want.size], want):
+                    raise ValueError(f"resize plan: the table at {loc} is not pil_bilinear_coeffs({t_in}, {n_out})")
+                seen[loc] = (t_in, n_out, want)
+            t_in, n_out, want = seen[loc]
+            if t_in != n_in:
+                raise ValueError(f"resize plan: clip {b} has a side of {n_in}, its table resamples {t_in}")
+            if n_out < img:
+                raise ValueError(f"resize plan: clip {b} resizes to a side of {n_out}, below the crop of {img}")
+            if at < 0 or at > n_out - img:
+                raise ValueError(f"resize plan: clip {b}: crop outside the resized frame, needs 0 <= {ax} <= {n_out - img}, got {at}")
+            if ax == "top":
+                first, count = want[4:4 + n_out], want[4 + n_out:4 + 2 * n_out]
+                tmp_rows = max(tmp_rows, int(first[at + img - 1] + count[at + img - 1] - first[at]))
+    return tmp_rows
+
+
+def resize_crop_u8(src, desc, tables, tmp, out, *, B, T, img, tmp_rows):
+    """Pillow's 8-bit bilinear Resize + crop on the device: src uint8 [nbytes], the packed source clips; desc int64 [B, 8] and tables
+    int32, the device copies of a resize_plan(); tmp uint8 with >= B * T * tmp_rows * img * 3 elements; out uint8 [B, T, img, img, 3]
+    (or a row-strided 2-D view [B * T * img, 3 * img] of a wider buffer)"""
+    assert src.dtype == torch.uint8 and src.dim() == 1 and src.is_contiguous() and tmp.dtype == torch.uint8 and tmp.is_contiguous()
+    assert desc.dtype == torch.int64 and desc.is_contiguous() and tuple(desc.shape) == (B, 8) and tables.dtype == torch.int32
+    assert out.dtype == torch.uint8
+    if out.dim() == 2:
+        assert tuple(out.shape) == (B * T * img, 3 * img)
+        ldo = _ld(out)
+    else:
+        assert out.is_contiguous() and tuple(out.shape) == (B, T, img, img, 3)
+        ldo = 3 * img
+    _chk(_lib.load().tvts_resize_crop_u8(_p(src), _p(desc), _p(tables), B, T, img, tmp_rows, _p(tmp), tmp.numel(), _p(out), ldo,
+                                         _stream()), "tvts_resize_crop_u8")
+
+
 def text_embed(ids, emb, pos, x, *, N, L):
     lib = _lib.load()
     assert ids.dtype == torch.int32
