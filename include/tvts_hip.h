@@ -113,7 +113,10 @@ int tvts_gemm_tn_bf16(const void* P, int ldp, const void* Q, int ldq, int M, int
  * the stream has passed this call.  upload != 0 builds the plan in table_host and copies it with ONE hipMemcpyAsync on `stream`, in
  * front of the kernels that read it -- no host wait, ordered on whatever stream the caller launches on; upload == 0 re-uses the plan a
  * previous call with the SAME problems and workspace left in table_dev (table_host may be NULL).  Every problem's result has the bits
- * of tvts_gemm_tn_bf16 called with the same range count. */
+ * of tvts_gemm_tn_bf16 called with the same range count.
+ * Refused with -22 before any launch: n <= 0 or n > 64, a null problems / table_dev / workspace, table_bytes short, upload without
+ * table_host, a record tvts_gemm_tn_bf16 would refuse (null P / Q / out, M / Na / Nb <= 0, Na / Nb / ldp / ldq % 8, ldo % 4, ldp < Na,
+ * ldq < Nb, ldo < Nb), a workspace too small for the partials of the ranges. */
 int tvts_gemm_tn_bf16_grouped(const void* problems, int n, void* table_dev, void* table_host, long table_bytes, int upload,
                               float* workspace, long workspace_elems, int opts, hipStream_t stream);
 long tvts_gemm_tn_grouped_table_bytes(int n);

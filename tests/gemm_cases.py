@@ -93,6 +93,54 @@ def tn_ranges(M, splits, stage=64):
     return n, M - (n - 1) * per
 
 
+# ------------------------------------------------------------------------------------------------ the side kernels' edge cases
+# (tests/test_gemm_side_edges_gpu.py runs them, tests/test_kernel_bounds_cpu.py plants faults at the smallest of them)
+COLSUM_M = (1, 31, 33, 4096, 4097, 8193)  # one row; either side of the 32 row lanes; one range, two (2049 + 2048 rows), three
+COLSUM_N = (8, 72, 136)                   # one column thread; a ragged second / third 64-column block
+COLSUM_RANGE_ROWS = 4096                  # tvts_colsum_bf16: ceil(M / 4096) row ranges, at most 256, when the workspace holds them
+# (M, N, K) of tvts_gemm_small_f32 around its dispatch cut (the fp32 MFMA tile from M >= 32, N >= 32, K >= 16)
+SMALL_SHAPES = ((31, 32, 16), (32, 31, 16), (32, 32, 15), (32, 32, 16), (33, 65, 17), (64, 64, 32), (65, 63, 33), (64, 64, 64),
+                (36, 40, 20), (1, 1, 1), (17, 5, 3))
+ROWS_LINEAR_R = (1, 15, 16, 17, 33)
+ROWS_LINEAR_K = (32, 64, 96, 128, 160, 416, 512, 544)  # waves without a step; either side of the unrolled loop for waves 0 and 3
+ROWS_LINEAR_N = (16, 48)
+# name -> (forced range count, [(M, Na, Nb, accumulate, colsum, strided output)]) of tvts_gemm_tn_bf16_grouped
+TN_GROUPS = {
+    "one_strided": (2, [(65, 136, 72, False, True, True)]),
+    "one_dense": (2, [(65, 136, 72, True, True, False)]),
+    "one_split_dense": (2, [(520, 136, 72, True, True, False)]),
+    "trio_unsplit": (1, [(520, 136, 72, True, True, True), (520, 264, 8, False, False, False), (520, 128, 392, True, False, True)]),
+    "trio": (2, [(520, 136, 72, True, True, True), (520, 264, 8, False, False, False), (520, 128, 392, True, False, True)]),
+    "mixed_m": (2, [(1040, 136, 264, True, True, True), (300, 72, 136, False, False, True), (1040, 8, 8, False, True, False)]),
+    "few_items": (2, [(520, 8, 8, False, False, True), (64, 136, 8, True, True, False)]),
+}
+
+
+def small_vec_eligible(M, N, Kd, sa, sb):
+    """tvts_gemm_small_f32 stages the problem with 16-byte loads (given aligned bases): the MFMA tile, each operand unit-stride in
+    one direction with the other stride and the extent along the vector multiples of 4"""
+    if not (M >= 32 and N >= 32 and Kd >= 16):
+        return False
+    va = (sa[0] % 4 == 0 and Kd % 4 == 0) if sa[1] == 1 else (sa[0] == 1 and sa[1] % 4 == 0 and M % 4 == 0)
+    vb = (sb[0] % 4 == 0 and N % 4 == 0) if sb[1] == 1 else (sb[0] == 1 and sb[1] % 4 == 0 and Kd % 4 == 0)
+    return va and vb
+
+
+def tn_group_ranges(M, splits):
+    """the contraction ranges a member of a grouped launch gets from the group's range count: a member keeps at least 256 rows per
+    range (it takes fewer ranges than the group), then whole 64-row stages as in tn_ranges -> (ranges, rows of the last one)"""
+    sp = max(int(splits), 1)
+    while sp > 1 and M // sp < 256:
+        sp -= 1
+    return tn_ranges(M, sp)
+
+
+def tn_group_items(problems, splits):
+    """work items of a grouped launch: 128 x 128 output tiles times ranges, summed over the members"""
+    cdiv = lambda x, y: -(-x // y)  # noqa: E731
+    return sum(cdiv(Na, 128) * cdiv(Nb, 128) * tn_group_ranges(M, splits)[0] for (M, Na, Nb, *_) in problems)
+
+
 # ------------------------------------------------------------------------------------------------ form loops
 def form(got, a, b, **kw):
     """check_gemm of one form, its own line in the record"""

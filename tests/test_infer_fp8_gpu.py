@@ -53,7 +53,7 @@ def _model(a, seed):
 
 # ------------------------------------------------------------------------------------------------ 1. the kernel
 @pytest.mark.parametrize("N", [64, 200])
-@pytest.mark.parametrize("Kd", [128, 640])
+@pytest.mark.parametrize("Kd", [64, 128, 512, 640])  # 64: the smallest K; 512: exactly one 512-deep chunk of the decoded rows
 @pytest.mark.parametrize("R", [1, 3, 17])
 def test_rows_linear_fp8_against_exact_arithmetic(K, R, Kd, N):
     """out = residual + bias + row_scale[r] * w_scale * (a8 @ w8^T): both operands decoded on the host, the product in float64, every

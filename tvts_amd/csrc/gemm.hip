@@ -1113,6 +1113,9 @@ extern "C" int tvts_gemm_tn_bf16_grouped(const void* problems, int n, void* tabl
     int Mmax = 0;
     for (int i = 0; i < n; ++i) {
         if (pr[i].M <= 0 || pr[i].Na % 8 || pr[i].Nb % 8 || pr[i].ldp % 8 || pr[i].ldq % 8 || pr[i].ldo % 4 || pr[i].Nb % 4) return TVTS_EINVAL;
+        // ... and what tvts_gemm_tn_bf16 refuses of the same record: a row pitch shorter than its row lets rows overlap
+        if (pr[i].Na <= 0 || pr[i].Nb <= 0 || !pr[i].P || !pr[i].Q || !pr[i].out) return TVTS_EINVAL;
+        if (pr[i].ldp < pr[i].Na || pr[i].ldq < pr[i].Nb || pr[i].ldo < pr[i].Nb) return TVTS_EINVAL;
         tiles_total += (long)ceil_div(pr[i].Na, 128) * ceil_div(pr[i].Nb, 128);
         out_total += (long)pr[i].Na * pr[i].Nb;
         Mmax = pr[i].M > Mmax ? pr[i].M : Mmax;
