@@ -468,6 +468,26 @@ int tvts_patch_gather_u8(const unsigned char* frames, int H0, int W0, const int*
 int tvts_patch_gather_u8_resized(const unsigned char* frames, int Hs, int Ws, const int* ytab, const int* xtab, int H0, int W0,
                                  const int* crop, const int* keep, int B, int T, int n, int img, int patch, const float* mean3,
                                  const float* std3, void* out, int ldo, hipStream_t stream);
+/* the RAGGED form: the clips of one batch differ in source size, crop and length, as the reference's loaders hand them over -- every
+ * clip is resized on its own (v2/video_transforms/videoaug.py:12,21 -> functional.py:47-78) and a clip of fewer than T frames is
+ * zero-padded BEHIND Normalize (v2/base/base_dataset.py:116-130: final = zeros; final[:n] = imgs; under "loading": "lax" a failed
+ * decode is one black input_res x input_res frame followed by zero frames).
+ *   src     one packed byte buffer; clip b is uint8 [frames_b, Hs_b, Ws_b, 3] contiguous at byte offset desc[b][0] (64-bit, ANY
+ *           alignment: byte loads only)
+ *   desc    int64 [B, 8] in DEVICE memory = (offset, Hs, Ws, top, left, ytab, xtab, frames): (top, left) the crop in RESIZED
+ *           coordinates, always explicit (the centre crop is the host's centre_crop_offset); ytab / xtab the int32-element offsets in
+ *           `tables` of the clip's row (Hs -> new_h) and column (Ws -> new_w) tables; 1 <= frames <= T
+ *   tables  int32 in DEVICE memory, one table per distinct (n_in, n_out) of the batch, shared by the clips that use it:
+ *           (n_in, n_out) | index[n_out] -- Pillow's nearest-neighbour source index of every resized row / column
+ *           (tvts_amd/data_loader/transforms.py pil_nearest_table); an axis that is not resized has the identity table
+ *   out     the rows, columns and padding of tvts_patch_gather_u8: row (b, f, i), columns (ch, py, px), columns 3 * patch^2 .. ldo zero
+ * Rows of a frame f >= frames_b are +0 in all ldo columns; for f < frames_b the value is bf16((u / 255.0f - mean) / std) with the
+ * operations and order of tvts_patch_gather_u8, the bytes of tvts_patch_gather_u8_resized run on that clip alone.
+ * Returns -22 for a NULL src / desc / tables / keep / out / mean3 / std3; B, T, n, patch or img <= 0; img % patch; ldo % 8;
+ * ldo < 3 * patch^2.  desc and tables are DEVICE data and are not checked: tvts_amd.hip.check_gather_plan does (every clip inside
+ * src, the tables those of its sizes, 0 <= top <= new_h - img, 0 <= left <= new_w - img, 1 <= frames <= T). */
+int tvts_patch_gather_u8_ragged(const unsigned char* src, const long* desc, const int* tables, const int* keep, int B, int T, int n,
+                                int img, int patch, const float* mean3, const float* std3, void* out, int ldo, hipStream_t stream);
 /* tube mask drawn on the device (replaces the per-sample np.random.shuffle(arange(ppf))[:n_keep] of the dataset worker,
  * v2/data_loader/YTTemporal_dataset.py:207-213): keep[b, :] = the n_keep patch indices with the smallest counter-based
  * random keys of sample number first_sample + b -- an unsorted prefix of a uniformly random permutation, shared by all

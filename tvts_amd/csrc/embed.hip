@@ -3,6 +3,8 @@
 //  tvts_patch_gather        kept patches of every frame -> bf16 im2col rows [B*T*n, 3*p*p] in conv-weight order
 //                           (v2/model/video_encoder_ViT_B_16.py:180-184 + tube-mask gather :201-215; only kept
 //                           patches are embedded -- output-equivalent)
+//  tvts_patch_gather_u8*    the same from uint8 frames as decoded (crop, / 255, Normalize fused; _resized: Pillow's nearest Resize
+//                           through index tables; _ragged: per-clip source sizes, crops and lengths from a descriptor table)
 //  tvts_patch_gather_tube*  the v1 tubelet (Conv3d) form of the same im2col: seven entry points -- fp32 clips frame- or channel-major,
 //                           uint8 frames behind a crop, test views, random-resized crop / flip / erase, each of the fine-tuning
 //                           forms with Mixup / CutMix -- over ONE kernel frame (tube_gather_kernel) and four source policies
@@ -564,6 +566,56 @@ extern "C" int tvts_patch_gather_u8_resized(const unsigned char* frames, int Hs,
         return TVTS_EINVAL;
     hipLaunchKernelGGL(patch_gather_u8_kernel, dim3(B * T * n), dim3(256), 0, stream, frames, H0, W0, crop, keep, B, T, n, img,
                        patch, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (bf16*)out, ldo, ytab, xtab, Hs, Ws);
+    TVTS_LAUNCH_CHECK();
+    return TVTS_OK;
+}
+// RAGGED form of the same gather (DESIGN.md 8j "v2 ragged"): the clips of one batch differ in source size and length, as the
+// reference's loaders hand them over -- every clip resized on its own (videoaug.py:12,21, functional.py:47-78), a clip of fewer
+// than T frames zero-padded BEHIND Normalize (base_dataset.py:116-130).  One packed byte buffer and a descriptor row per clip
+// (layouts: include/tvts_hip.h) stand in for (frames, Hs, Ws, ytab, xtab, H0, W0, crop); the descriptor is block-uniform, read once
+// per block.  The value expression is patch_gather_u8_kernel's, token for token, so a clip's rows carry the bytes of
+// tvts_patch_gather_u8_resized run on that clip alone; a sibling kernel, so that kernel's launches stay what they were.
+__global__ __launch_bounds__(256) void patch_gather_u8_ragged_kernel(const unsigned char* __restrict__ src,
+                                                                     const long* __restrict__ desc, const int* __restrict__ tables,
+                                                                     const int* __restrict__ keep, int B, int T, int n, int img,
+                                                                     int p, float m0, float m1, float m2, float s0, float s1,
+                                                                     float s2, bf16* __restrict__ out, int ldo) {
+    const int K = 3 * p * p;
+    const int row = blockIdx.x;  // (b, f, i)
+    const int i = row % n, f = (row / n) % T, b = row / (n * T);
+    const long* d = desc + (size_t)b * 8;
+    const int frames = (int)d[7];
+    if (f >= frames) {  // the reference's zero frame behind Normalize: +0 in all ldo columns
+        for (int c = threadIdx.x; c < ldo; c += 256) out[(size_t)row * ldo + c] = (bf16)0.f;
+        return;
+    }
+    const int Hs = (int)d[1], Ws = (int)d[2], y0 = (int)d[3], x0 = (int)d[4];
+    const int* __restrict__ ytab = tables + d[5] + 2;  // (n_in, n_out) | index[n_out]
+    const int* __restrict__ xtab = tables + d[6] + 2;
+    const int g = img / p;
+    const int pi = keep[b * n + i];
+    const int gy = pi / g, gx = pi % g;
+    const unsigned char* fr = src + d[0] + (size_t)f * Hs * Ws * 3;
+    for (int c = threadIdx.x; c < ldo; c += 256) {
+        float v = 0.f;
+        if (c < K) {
+            const int ch = c / (p * p), rem = c % (p * p), py = rem / p, px = rem % p;
+            const int sy = ytab[y0 + gy * p + py], sx = xtab[x0 + gx * p + px];  // pixel of the (resized) picture -> source pixel
+            const float u = (float)fr[((size_t)sy * Ws + sx) * 3 + ch];
+            const float mean = ch == 0 ? m0 : ch == 1 ? m1 : m2, sd = ch == 0 ? s0 : ch == 1 ? s1 : s2;
+            v = (u / 255.0f - mean) / sd;
+        }
+        out[(size_t)row * ldo + c] = (bf16)v;
+    }
+}
+extern "C" int tvts_patch_gather_u8_ragged(const unsigned char* src, const long* desc, const int* tables, const int* keep, int B,
+                                           int T, int n, int img, int patch, const float* mean3, const float* std3, void* out,
+                                           int ldo, hipStream_t stream) {
+    if (!src || !desc || !tables || !keep || !out || !mean3 || !std3 || B <= 0 || T <= 0 || n <= 0 || patch <= 0 || img <= 0 ||
+        img % patch || ldo % 8 || ldo < 3 * patch * patch || (long)B * T * n > 2147483647L)
+        return TVTS_EINVAL;
+    hipLaunchKernelGGL(patch_gather_u8_ragged_kernel, dim3(B * T * n), dim3(256), 0, stream, src, desc, tables, keep, B, T, n, img,
+                       patch, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (bf16*)out, ldo);
     TVTS_LAUNCH_CHECK();
     return TVTS_OK;
 }

@@ -993,15 +993,17 @@ class Engine:
         cls_acc = self._f(scr + ".clsacc", (B, h, max(T, -(-n // 28)), 3, hd))
         K.attn_bwd(mode, qkv, datt, att, lse, delta, dqkv, B=B, heads=h, S=S, T=T, n=n, cls_acc=cls_acc, head_dim=hd, **kw8)
 
-    def _vit_embed(self, video, keep_dev, B, T, vid_rows, crop, resize, tag):
-        """patch gather (fp32 clips or uint8 frames) -> conv GEMM -> token assembly -> ln_pre: (the residual stream x [B * S, W],
+    def _vit_embed(self, video, keep_dev, B, T, vid_rows, crop, resize, tag, gather=None):
+        """patch gather (fp32 clips, uint8 frames or, with gather = dict(desc, tables), the packed ragged uint8 clips) -> conv GEMM -> token assembly -> ln_pre: (the residual stream x [B * S, W],
         the fp32 CLS rows [B, W] of the hybrid stream or None).  Forward-only (tag None) the fp32 temporaries live in the roles of
         the first block's LayerNorm, MLP and qkv buffers (free until then)."""
         a, w = self.arch, self._w
         W, p, n = a["width"], a["patch"], keep_dev.shape[1]
         M, Mp = B * (1 + T * n), B * T * n
         cols = w(tag, ".im2col", "ln", (Mp, self.P.conv_kpad))
-        if video.dtype == torch.uint8:
+        if gather is not None:
+            K.patch_gather_u8_ragged(video, gather["desc"], gather["tables"], keep_dev, cols, B=B, T=T, n=n, img=a["image"], patch=p)
+        elif video.dtype == torch.uint8:
             K.patch_gather_u8(video, keep_dev, cols, B=B, T=T, n=n, img=a["image"], patch=p, crop=crop, resize=resize)
         else:
             K.patch_gather(video, keep_dev, cols, B=B, T=T, n=n, img=a["image"], patch=p)
@@ -1081,7 +1083,8 @@ class Engine:
         lowres, cls = self.bf16_residual, self.cls32
         if vid_rows is None:
             vid_rows = (torch.arange(B, device=self.dev) * S).to(torch.int32)
-        x, xc = self._vit_embed(video, keep_dev, B, T, vid_rows, self.ctx.get("crop"), self.ctx.get("resize"), "vit")
+        x, xc = self._vit_embed(video, keep_dev, B, T, vid_rows, self.ctx.get("crop"), self.ctx.get("resize"), "vit",
+                                   gather=self.ctx.get("gather"))
         rc = self._rc_fwd["vit"] = self.recompute
         for l in range(a["layers"]):
             x, xc = self._vit_block(l, x, xc, "vit", B, T, n, recompute=rc)
@@ -1365,12 +1368,73 @@ class Engine:
         d.record_stream(cur)
         return d
 
+    def _packed_to_device(self, clips, plan):
+        """source clips of a resize plan -> ONE uint8 device buffer with clip b at plan["offsets"][b].  A tensor [B, T, Hs, Ws, 3] is
+        that buffer already; a list is packed into a page-locked staging buffer (a ring of STAGE_SLOTS, each guarded by the event of
+        its last copy, as _stage_small).  Either way ONE asynchronous copy on the engine's copy stream (_clip_to_device)."""
+        if torch.is_tensor(clips):
+            return self._clip_to_device(clips.contiguous().view(-1))
+        total = plan["nbytes"]
+        ring = getattr(self, "_clip_ring", None)
+        if ring is None:
+            ring = self._clip_ring = dict(i=0, slots=[None] * self.STAGE_SLOTS)
+        i = ring["i"] = (ring["i"] + 1) % self.STAGE_SLOTS
+        slot = ring["slots"][i]
+        if slot is None or slot[0].numel() < total:
+            slot = ring["slots"][i] = [torch.empty(total, dtype=torch.uint8, pin_memory=True), None]
+        if slot[1] is not None:
+            slot[1].synchronize()
+        from .data_loader.v1_input import pack_clips
+        dev = self._clip_to_device(pack_clips(clips, plan["offsets"].tolist(), slot[0])[:total])
+        if not torch.cuda.is_current_stream_capturing():
+            slot[1] = torch.cuda.Event()
+            slot[1].record(self._copy_stream)
+        return dev
+
+    def _ragged_batch(self, data: dict):
+        """the HOST half of a ragged uint8 batch (DESIGN.md 8j "v2 ragged"): data["video"] a list of B uint8 clips [T_b, Hs_b, Ws_b, 3]
+        as decoded, each resized (data["resize"]: video_transform.Resize's size, absent = none) and cropped (data["crop"] [B, 2] (top,
+        left) in RESIZED coordinates, absent = centre) on its own; a clip of T_b < T frames (T = data["num_frames"], default max T_b)
+        is followed by the reference's zero frames behind Normalize (v2/base/base_dataset.py:116-130) -> (clips, plan of
+        hip.gather_plan, B, T).  ValueError by name for a clip that is not uint8 [*, *, *, 3], a clip without frames or longer than
+        T, T beyond the temporal embedding, a resized side below img, a crop outside the frame.  Nothing here touches the device."""
+        a, clips = self.arch, list(data["video"])
+        if not clips:
+            raise ValueError("video: an empty list of clips")
+        for b, c in enumerate(clips):
+            if not torch.is_tensor(c) or c.dtype != torch.uint8 or c.dim() != 4 or c.shape[-1] != 3:
+                raise ValueError(f"video: clip {b} of a list must be a uint8 tensor [T, Hs, Ws, 3], got "
+                                 + (f"{c.dtype} {tuple(c.shape)}" if torch.is_tensor(c) else type(c).__name__))
+            if c.shape[0] < 1:
+                raise ValueError(f"video: clip {b} has no frames")
+        B = len(clips)
+        T = int(data["num_frames"]) if data.get("num_frames") is not None else max(int(c.shape[0]) for c in clips)
+        for b, c in enumerate(clips):
+            if int(c.shape[0]) > T:
+                raise ValueError(f"video: clip {b} has {int(c.shape[0])} frames, more than the batch's num_frames of {T}")
+        if T > a["num_frames"]:
+            raise ValueError(f"clips of {T} frames, the temporal embedding has {a['num_frames']} rows")
+        crop = data.get("crop")
+        if crop is not None:
+            crop = torch.as_tensor(crop).detach().to("cpu", torch.int64)
+            if tuple(crop.shape) != (B, 2):
+                raise ValueError(f"crop {tuple(crop.shape)}: expected [{B}, 2] (top, left)")
+            crop = crop.tolist()
+        plan = K.gather_plan([(int(c.shape[1]), int(c.shape[2])) for c in clips], [int(c.shape[0]) for c in clips], crop,
+                             size=None if data.get("resize") is None else int(data["resize"]), img=a["image"], T=T)
+        return clips, plan, B, T
+
     def prepare_batch(self, data: dict):
         """Host-side (plumbing): dtype/device normalisation of the reference batch dict."""
         a = self.arch
         video = data["video"]
-        crop = resize = crop_cpu = None
-        if video.dtype == torch.uint8:
+        crop = resize = crop_cpu = plan = None
+        if isinstance(video, (list, tuple)):
+            # ragged uint8 wire format: the clips at the decoder's sizes and lengths in ONE packed upload; Resize, crop, / 255,
+            # Normalize and the zero frames of short clips happen inside the patch gather (tvts_patch_gather_u8_ragged)
+            clips, plan, B, T = self._ragged_batch(data)
+            video = self._packed_to_device(clips, plan)
+        elif video.dtype == torch.uint8:
             # uint8 wire format (SURVEY.md 8f N3): [B, T, H0, W0, 3] frames as decoded + resized; crop / 255 / normalise
             # happen inside the patch gather.  data["crop"]: [B, 2] (top, left) of a random crop, absent = centre crop.
             if video.dim() == 4:
@@ -1386,7 +1450,8 @@ class Engine:
             if video.dim() == 4:
                 video = video.unsqueeze(1)
             video = self._clip_to_device(video).to(torch.float32).contiguous()
-        B, T = video.shape[:2]
+        if plan is None:
+            B, T = video.shape[:2]
         # the reference fails on these with an indexing / broadcasting error (temporal_embedding[:T], nn.Embedding, pos[keep_ind]); the
         # kernels would read or write past the tables instead, so the batch is checked where it enters
         if T > a["num_frames"]:
@@ -1440,6 +1505,8 @@ class Engine:
         small["vid_rows"] = (torch.arange(B) * S).to(torch.int32)
         if crop_cpu is not None:
             small["crop"] = crop_cpu
+        if plan is not None:
+            small["ga_desc"], small["ga_tables"] = torch.from_numpy(plan["desc"]), torch.from_numpy(plan["tables"])
         if "label" in data and NT != 1:
             small["labels"] = data["label"].detach().reshape(-1).to("cpu", torch.int32)
         d = self._stage_small(small)
@@ -1450,6 +1517,8 @@ class Engine:
                   n=n, S=S, sort_rows=d["sort_rows"], vid_rows=d["vid_rows"], labels=d.get("labels"))
         if pk is not None:
             pb.update(M=int(pk["ids"].numel()), seq_start=d["seq_start"], max_len=pk["max_len"], pos_sort=(d["pos_order"], d["pos_seg"]))
+        if plan is not None:
+            pb["gather"] = dict(desc=d["ga_desc"], tables=d["ga_tables"])
         return pb
 
     STAGE_SLOTS = 4
@@ -1638,9 +1707,10 @@ class Engine:
             return
         K.rows_linear(a_c, self.P.w(wname), out_c, bias=bias, residual=res_c)
 
-    def encode_video(self, video, keep_dev, B, T, crop=None, resize=None):
+    def encode_video(self, video, keep_dev, B, T, crop=None, resize=None, gather=None):
         """-> [B, E] fp32 video embeddings (an encoder workspace: the next encoder call overwrites it).  video: fp32 [B, T, 3, H, W]
-        or uint8 [B, T, H0, W0, 3] on the device; keep_dev: int32 [B, n] kept patches per frame."""
+        or uint8 [B, T, H0, W0, 3] on the device, or with gather = dict(desc, tables) (device copies of a hip.gather_plan) the packed
+        ragged uint8 clips; keep_dev: int32 [B, n] kept patches per frame."""
         self._inf_check()
         a, f32 = self.arch, torch.float32
         W, E, h = a["width"], a["embed"], a["heads"]
@@ -1648,7 +1718,7 @@ class Engine:
         S = 1 + T * n
         M = B * S
         vid_rows = self._row_starts("vid_rows", B, S)
-        x, xc = self._vit_embed(video, keep_dev, B, T, vid_rows, crop, resize, None)
+        x, xc = self._vit_embed(video, keep_dev, B, T, vid_rows, crop, resize, None, gather=gather)
         for l in range(a["layers"] - 1):
             x, xc = self._vit_block(l, x, xc, None, B, T, n)
         # the last block for the CLS rows: the time branch and the space qkv run on every row (they make the keys and values of

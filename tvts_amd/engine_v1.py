@@ -499,29 +499,6 @@ class EngineV1(Engine):
             out["resize"] = dict(desc=d["rs_desc"], tables=d["rs_tables"], tmp_rows=u8["plan"]["tmp_rows"])
         return out
 
-    def _packed_to_device(self, clips, plan):
-        """source clips of a resize plan -> ONE uint8 device buffer with clip b at plan["offsets"][b].  A tensor [B, T, Hs, Ws, 3] is
-        that buffer already; a list is packed into a page-locked staging buffer (a ring of STAGE_SLOTS, each guarded by the event of
-        its last copy, as _stage_small).  Either way ONE asynchronous copy on the engine's copy stream (_clip_to_device)."""
-        if torch.is_tensor(clips):
-            return self._clip_to_device(clips.contiguous().view(-1))
-        total = plan["nbytes"]
-        ring = getattr(self, "_clip_ring", None)
-        if ring is None:
-            ring = self._clip_ring = dict(i=0, slots=[None] * self.STAGE_SLOTS)
-        i = ring["i"] = (ring["i"] + 1) % self.STAGE_SLOTS
-        slot = ring["slots"][i]
-        if slot is None or slot[0].numel() < total:
-            slot = ring["slots"][i] = [torch.empty(total, dtype=torch.uint8, pin_memory=True), None]
-        if slot[1] is not None:
-            slot[1].synchronize()
-        from .data_loader.v1_input import pack_clips
-        dev = self._clip_to_device(pack_clips(clips, plan["offsets"].tolist(), slot[0])[:total])
-        if not torch.cuda.is_current_stream_capturing():
-            slot[1] = torch.cuda.Event()
-            slot[1].record(self._copy_stream)
-        return dev
-
     def prepare_batch(self, data: dict):
         """v1 batch dict (v1/trainer/trainer.py:121-131): text = the tokenizer's {'input_ids', 'attention_mask'} (right-padded),
         video fp32 [B, T, 3, H, W] or one of the uint8 wire formats of _u8_batch, keep_ind int64 [B, n_tubes, n_keep] (one mask per

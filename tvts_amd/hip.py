@@ -913,6 +913,112 @@ def patch_gather_u8(frames, keep, out, *, B, T, n, img, patch, crop=None, mean=I
                                   _p(out), _ld(out), _stream()), "tvts_patch_gather_u8")
 
 
+# ---- the ragged uint8 input of the v2 step (embed.hip: tvts_patch_gather_u8_ragged; DESIGN.md 8j "v2 ragged")
+_NEAREST_TABLES = {}
+
+
+def nearest_table(n_in, n_out):
+    """the int32 table of one axis as tvts_patch_gather_u8_ragged reads it: (n_in, n_out) | transforms.pil_nearest_table(n_in, n_out),
+    cached per (n_in, n_out) -> 1-D numpy int32"""
+    import numpy as np
+    key = (int(n_in), int(n_out))
+    t = _NEAREST_TABLES.get(key)
+    if t is None:
+        from .data_loader.transforms import pil_nearest_table
+        t = _NEAREST_TABLES[key] = np.array(list(key) + pil_nearest_table(*key), dtype=np.int32)
+        t.setflags(write=False)
+    return t
+
+
+def gather_plan(sizes, frames, crops, *, size, img, T, offsets=None):
+    """the host half of tvts_patch_gather_u8_ragged for a batch of source clips: sizes B x (Hs, Ws); frames B clip lengths (1 .. T);
+    crops B x (top, left) in RESIZED coordinates or None (the centre crop of every clip: CenterCrop's round-half-to-even offsets);
+    size: video_transform.Resize(size), None = no Resize (identity tables); offsets: the clips' byte offsets in the packed buffer
+    (default: back to back) -> dict(desc int64 [B, 8], tables int32, numpy; offsets; nbytes: what the clips occupy).  One table per
+    distinct (n_in, n_out), shared between the clips and axes that use it.  ValueError by name for what check_gather_plan refuses."""
+    import numpy as np
+    from .data_loader.transforms import centre_crop_offset, resize_sizes
+    B = len(sizes)
+    if B < 1 or len(frames) != B or (crops is not None and len(crops) != B) or (offsets is not None and len(offsets) != B):
+        raise ValueError(f"gather plan: {B} sizes, {len(frames)} lengths" + ("" if crops is None else f", {len(crops)} crops")
+                         + ("" if offsets is None else f", {len(offsets)} offsets"))
+    desc = np.zeros((B, 8), dtype=np.int64)
+    where, parts, total, at = {}, [], 0, 0
+    for b, (hs, ws) in enumerate(sizes):
+        hs, ws, fr = int(hs), int(ws), int(frames[b])
+        if hs < 1 or ws < 1:
+            raise ValueError(f"gather plan: clip {b} has frames of {hs} x {ws}")
+        if fr < 1 or fr > T:
+            raise ValueError(f"gather plan: clip {b} has {fr} frames, needs 1 <= frames <= {T}")
+        nh, nw = (hs, ws) if size is None else resize_sizes(hs, ws, int(size))
+        if nh < img or nw < img:
+            raise ValueError(f"gather plan: clip {b} ({hs} x {ws}) " + ("is" if size is None else f"resizes to {nh} x {nw} under "
+                             f"Resize({size}),") + f" below the crop of {img} x {img}")
+        loc = []
+        for key in ((hs, nh), (ws, nw)):
+            if key not in where:
+                where[key] = total
+                parts.append(nearest_table(*key))
+                total += parts[-1].size
+            loc.append(where[key])
+        top, left = (centre_crop_offset(nh - img), centre_crop_offset(nw - img)) if crops is None else (int(crops[b][0]), int(crops[b][1]))
+        off = at if offsets is None else int(offsets[b])
+        desc[b] = (off, hs, ws, top, left, loc[0], loc[1], fr)
+        at = off + fr * hs * ws * 3
+    tables = np.concatenate(parts)
+    nbytes = int(max(desc[:, 0] + desc[:, 7] * desc[:, 1] * desc[:, 2] * 3))
+    check_gather_plan(desc, tables, T=T, img=img, src_bytes=nbytes)
+    return dict(desc=desc, tables=tables, offsets=desc[:, 0].copy(), nbytes=nbytes)
+
+
+def check_gather_plan(desc, tables, *, T, img, src_bytes):
+    """the host-side check of a gather plan (the C entry point takes both as unchecked device data): desc integer [B, 8] = (offset,
+    Hs, Ws, top, left, ytab, xtab, frames), tables int32.  ValueError for frames outside [1, T], a clip that leaves the src_bytes of
+    the packed buffer, a table location outside `tables`, a table that is not the one of its (n_in, n_out) or whose n_in is not the
+    clip's side, a resized side below img, a crop outside the resized frame (0 <= top <= new_h - img, 0 <= left <= new_w - img)."""
+    import numpy as np
+    d, tb = np.asarray(desc), np.asarray(tables)
+    if d.ndim != 2 or d.shape[0] < 1 or d.shape[1] != 8 or d.dtype.kind not in "iu" or tb.ndim != 1 or tb.dtype != np.int32:
+        raise ValueError(f"gather plan: integer desc [B, 8] and int32 tables [n], got {d.dtype} {d.shape} / {tb.dtype} {tb.shape}")
+    if T < 1 or img < 1:
+        raise ValueError(f"gather plan: T = {T}, img = {img}")
+    seen = {}
+    for b, (off, hs, ws, top, left, yt, xt, fr) in enumerate(d.astype(np.int64).tolist()):
+        if fr < 1 or fr > T:
+            raise ValueError(f"gather plan: clip {b} has {fr} frames, needs 1 <= frames <= {T}")
+        if hs < 1 or ws < 1 or off < 0 or off + fr * hs * ws * 3 > src_bytes:
+            raise ValueError(f"gather plan: clip {b} ({fr} x {hs} x {ws} x 3 bytes at offset {off}) leaves the buffer of {src_bytes} bytes")
+        for loc, n_in, at, ax in ((yt, hs, top, "top"), (xt, ws, left, "left")):
+            if loc not in seen:
+                if loc < 0 or loc + 2 > tb.size:
+                    raise ValueError(f"gather plan: clip {b} names a table at {loc}, outside the {tb.size} table elements")
+                t_in, n_out = int(tb[loc]), int(tb[loc + 1])
+                if t_in < 1 or n_out < 1 or loc + 2 + n_out > tb.size or not np.array_equal(tb[loc:loc + 2 + n_out],
+                                                                                         nearest_table(t_in, n_out)):
+                    raise ValueError(f"gather plan: the table at {loc} is not pil_nearest_table({t_in}, {n_out})")
+                seen[loc] = (t_in, n_out)
+            t_in, n_out = seen[loc]
+            if t_in != n_in:
+                raise ValueError(f"gather plan: clip {b} has a side of {n_in}, its table resamples {t_in}")
+            if n_out < img:
+                raise ValueError(f"gather plan: clip {b} resizes to a side of {n_out}, below the crop of {img}")
+            if at < 0 or at > n_out - img:
+                raise ValueError(f"gather plan: clip {b}: crop outside the resized frame, needs 0 <= {ax} <= {n_out - img}, got {at}")
+
+
+def patch_gather_u8_ragged(src, desc, tables, keep, out, *, B, T, n, img, patch, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """the tube-mask gather over RAGGED uint8 clips: src uint8 [nbytes], the packed source clips; desc int64 [B, 8] and tables int32,
+    the device copies of a gather_plan(); keep int32 [B, n]; out bf16 [B * T * n, ldo] -- the rows of patch_gather_u8(resize=...) on
+    every clip alone, zero rows for the frames behind a short clip's end"""
+    import ctypes
+    assert src.dtype == torch.uint8 and src.dim() == 1 and src.is_contiguous() and keep.dtype == torch.int32 and keep.is_contiguous()
+    assert desc.dtype == torch.int64 and desc.is_contiguous() and tuple(desc.shape) == (B, 8) and tables.dtype == torch.int32
+    assert tuple(keep.shape) == (B, n) and out.dtype == torch.bfloat16 and out.shape[0] == B * T * n
+    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    _chk(_lib.load().tvts_patch_gather_u8_ragged(_p(src), _p(desc), _p(tables), _p(keep), B, T, n, img, patch, m3, s3, _p(out),
+                                                 _ld(out), _stream()), "tvts_patch_gather_u8_ragged")
+
+
 def tube_mask(seed, first_sample, B, ppf, n_keep, out=None, device=None):
     """keep_ind int32 [B, n_keep] drawn on the device: sample number first_sample + b gets the n_keep patch indices with the
     smallest counter-based random keys (an unsorted prefix of a random permutation, YTTemporal_dataset.py:207-213)."""

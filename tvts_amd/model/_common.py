@@ -274,7 +274,7 @@ class TVTSv2Base(nn.Module):
             video_data = video_data.unsqueeze(1)
         v = video_data.to(self.store.device).contiguous() if video_data.dtype == torch.uint8 else \
             video_data.to(self.store.device, torch.float32).contiguous()
-        self.engine.ctx = dict(self.engine.ctx, crop=None)
+        self.engine.ctx = dict(self.engine.ctx, crop=None, gather=None)
         B, T = v.shape[:2]
         keep = keep_ind.to(torch.int32).contiguous().to(self.store.device)
         out, pooled = self.engine.video_forward(v, keep, B, T)
@@ -286,22 +286,48 @@ class TVTSv2Base(nn.Module):
     # forward-only encoders (feature extraction / zero-shot: the reference's feature_extraction_* and zero_* scripts read the CLS
     # embedding only): no per-layer activations, no backward-only outputs, the last block for the CLS rows (Engine.encode_video)
     @torch.no_grad()
-    def encode_video(self, video, keep_ind=None):
-        """-> [B, E] video embeddings.  video: fp32 [B, T, 3, H, W] (or [B, 3, H, W]) or uint8 [B, T, H0, W0, 3] frames (centre
-        crop); keep_ind: [1, n] or [B, n] kept patches per frame, None = every patch."""
+    def encode_video(self, video, keep_ind=None, crop=None, resize=None, num_frames=None):
+        """-> [B, E] video embeddings.  video: fp32 [B, T, 3, H, W] (or [B, 3, H, W]), uint8 [B, T, H0, W0, 3] frames, or a list of B
+        uint8 clips [T_b, Hs_b, Ws_b, 3] as decoded (the ragged wire format of Engine.prepare_batch; num_frames: the T short clips are
+        zero-padded to, default max T_b).  uint8 only: resize = the size of video_transform.Resize (None: none), crop = [B, 2] (top,
+        left) in resized coordinates (None: centre).  keep_ind: [1, n] or [B, n] kept patches per frame, None = every patch."""
         self._fresh_shadows()
-        a, dev = self.arch, self.store.device
-        if video.dtype == torch.uint8:
+        a, dev, eng = self.arch, self.store.device, self.engine
+        crop_dev = tabs = gather = None
+        if isinstance(video, (list, tuple)):
+            clips, plan, B, T = eng._ragged_batch(dict(video=video, crop=crop, resize=resize, num_frames=num_frames))
+            v = eng._packed_to_device(clips, plan)
+            gather = eng._stage_small(dict(desc=torch.from_numpy(plan["desc"]), tables=torch.from_numpy(plan["tables"])))
+        elif video.dtype == torch.uint8:
             if video.dim() == 4:
                 video = video.unsqueeze(1)
             if video.dim() != 5 or video.shape[-1] != 3:
                 raise ValueError("uint8 video must be [B, T, H, W, 3]")
+            if crop is not None or resize is not None:
+                from ..data_loader.transforms import resize_sizes, resize_tables
+                hs, ws, img = int(video.shape[2]), int(video.shape[3]), a["image"]
+                nh, nw = (hs, ws) if resize is None else resize_sizes(hs, ws, int(resize))
+                if nh < img or nw < img:
+                    raise ValueError(f"uint8 frames of {hs} x {ws}" + ("" if resize is None else f" resize to {nh} x {nw} under "
+                                     f"Resize({resize})") + f": a side below the crop of {img} x {img}")
+                if crop is not None:
+                    c = torch.as_tensor(crop).detach().to("cpu", torch.int32).contiguous()
+                    if tuple(c.shape) != (video.shape[0], 2):
+                        raise ValueError(f"crop {tuple(c.shape)}: expected [{video.shape[0]}, 2] (top, left)")
+                    if bool(((c < 0) | (c[:, :1] > nh - img) | (c[:, 1:] > nw - img)).any()):
+                        raise ValueError(f"crop outside the frame: needs 0 <= top <= {nh - img} and 0 <= left <= {nw - img}")
+                    crop_dev = c.to(dev)
+                if resize is not None:
+                    tabs = resize_tables(hs, ws, int(resize), dev)
             v = video.to(dev).contiguous()
         else:
+            if crop is not None or resize is not None:
+                raise ValueError("crop / resize apply to uint8 frames; fp32 clips arrive cropped and normalised")
             if video.dim() == 4:
                 video = video.unsqueeze(1)
             v = video.to(dev, torch.float32).contiguous()
-        B, T = v.shape[:2]
+        if gather is None:
+            B, T = v.shape[:2]
         if T > a["num_frames"]:
             raise ValueError(f"clips of {T} frames, the temporal embedding has {a['num_frames']} rows")
         ppf = (a["image"] // a["patch"]) ** 2
@@ -311,7 +337,7 @@ class TVTSv2Base(nn.Module):
         if kc.numel() and (int(kc.min()) < 0 or int(kc.max()) >= ppf):
             raise IndexError(f"keep_ind must index the {ppf} patches of a frame")
         keep = kc.expand(B, -1).to(dev, torch.int32).contiguous()
-        return self.engine.encode_video(v, keep, B, T).clone()
+        return eng.encode_video(v, keep, B, T, crop=crop_dev, resize=tabs, gather=gather).clone()
 
     @torch.no_grad()
     def encode_text(self, text, packed=False):

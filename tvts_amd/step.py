@@ -64,13 +64,22 @@ def split_batch(data: dict, n: int):
     text is TRANSCRIPT-major (row t * B + b, what prepare_batch and the model's reshape(NT, B, -1) read): chunk rows are
     text.reshape(NT, B, L)[:, lo:hi], never a contiguous slice of rows.  video (fp32 or the uint8 wire format), keep_ind [B, n],
     crop [B, 2] and label are sliced by clip; keep_ind [1, n] and resize are kept; a device-drawn mask keeps mask_seed and moves
-    sample_offset by lo (tvts_tube_mask numbers the samples globally); everything else (meta, ...) is carried through untouched."""
+    sample_offset by lo (tvts_tube_mask numbers the samples globally); everything else (meta, ...) is carried through untouched.
+    A LIST video (the ragged uint8 wire format) is sliced by clip as well, each chunk planned by its own prepare_batch, and every
+    chunk gets num_frames = the whole batch's T."""
     if isinstance(n, bool) or not isinstance(n, int) or n < 1:
         raise ValueError(f"split_batch: n {n!r} must be an int >= 1")
     video = data["video"]
-    if video.dim() < 4:
+    ragged = isinstance(video, (list, tuple))  # (the ragged uint8 wire format: B clips [T_b, Hs_b, Ws_b, 3], sliced by clip)
+    if not ragged and video.dim() < 4:
         raise ValueError(f"split_batch: video {tuple(video.shape)} has no clip dimension")
-    B = int(video.shape[0])
+    B = len(video) if ragged else int(video.shape[0])
+    if ragged:
+        if B < 1:
+            raise ValueError("split_batch: video is an empty list of clips")
+        if any(not torch.is_tensor(c) or c.dim() != 4 for c in video):
+            raise ValueError("split_batch: a list video holds uint8 clips [T, Hs, Ws, 3]")
+        T = int(data["num_frames"]) if data.get("num_frames") is not None else max(int(c.shape[0]) for c in video)
     if B % n:
         raise ValueError(f"split_batch: micro_batches {n} does not divide the batch of {B} clips (unequal chunks are not built)")
     b = B // n
@@ -91,6 +100,8 @@ def split_batch(data: dict, n: int):
                 d[key] = text.reshape(NT, B, L)[:, lo:hi].reshape(NT * b, L)
             elif key in _PER_CLIP and torch.is_tensor(val) and not (key == "keep_ind" and val.shape[0] == 1):
                 d[key] = val[lo:hi]
+            elif key == "video" and ragged:
+                d[key] = list(val[lo:hi])
             elif key == "sample_offset":
                 continue
             else:
@@ -99,6 +110,8 @@ def split_batch(data: dict, n: int):
             d["sample_offset"] = int(data.get("sample_offset", 0)) + lo
         elif "sample_offset" in data:
             d["sample_offset"] = data["sample_offset"]
+        if ragged:  # every chunk pads its short clips to the WHOLE batch's T, so the chunks agree on the token rows per clip
+            d["num_frames"] = T
         out.append(d)
     return out
 
@@ -406,8 +419,9 @@ class GraphReplay:
         m._sync_requires_grad()
         pb = r.eng.prepare_batch(data)
         labels = r._labels(data, pb)
-        if pb.get("seq_start") is not None:
-            # packed captions (arch["text_packed"]): M and max_len change with every batch, a graph would never be replayed -- eager
+        if pb.get("seq_start") is not None or pb.get("gather") is not None:
+            # packed captions (arch["text_packed"]): M and max_len change with every batch, a graph would never be replayed -- eager;
+            # ragged uint8 clips (pb["gather"]): the packed buffer's size changes with every batch, eager as well
             self.eager += 1
             return r.run(pb, labels, device_step=True)
         sig = (_signature(pb), None if labels is None else tuple(labels.shape), bool(m.training),
